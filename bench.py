@@ -429,6 +429,24 @@ def spin_up(dbatch, ms: float = None) -> int:
     return n
 
 
+DUMP_FIELDS = ("gt", "gl", "sq", "tallies", "counts")
+DUMP_BYTES_MAX = 64_000_000
+
+
+def dump_outputs(res, out_dir: str, seed: int = 0) -> None:
+    """--dump-outputs: the result records the timed region's last pass left, as a caller of DeviceBatch.results() receives
+    them, one float64 array per field in DIR/<field>.npy, the units' indices in DIR/unit.npy.  When all units would exceed
+    DUMP_BYTES_MAX, a seeded sample of them (sorted, the same for every run over the same number of units)."""
+    n = res.n_units
+    per_unit = 8 * (1 + sum(int(np.prod(res.rec.dtype[f].shape, dtype=np.int64)) for f in DUMP_FIELDS))
+    keep = min(n, (DUMP_BYTES_MAX - 4096 * (1 + len(DUMP_FIELDS))) // per_unit)    # (4 KB of room per file for its .npy header)
+    unit = np.arange(n) if keep == n else np.sort(np.random.default_rng(seed).choice(n, keep, replace=False))
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "unit.npy"), unit.astype(np.float64))
+    for f in DUMP_FIELDS:
+        np.save(os.path.join(out_dir, f + ".npy"), res.rec[f][unit].astype(np.float64))
+
+
 def time_passes(dbatch, steps: int) -> float:
     """average launch duration in ms: HIP events on the launch stream around `steps` back-to-back passes"""
     spin_up(dbatch)
@@ -787,7 +805,12 @@ def main():
                     help="N > 1 (or --force-dist): the headline only -- no `strong` (configs[3]) / `c5` (configs[4]) legs, no pipelined steady state")
     ap.add_argument("--c5-units-per-rank", type=int, default=None,
                     help="(site, sample) units per rank of the N-rank `c5` leg [configs[4] literally: 16 M / N, at most 2 x --units]")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the results of the last timed step (rank 0's units) to DIR/<field>.npy as float64, at most 64 MB "
+                         "(a seeded sample of the units beyond that), to compare two builds on the same seeded inputs")
     args = ap.parse_args()
+    if args.steps < 1:
+        sys.exit("--steps must be at least 1")
     if args.no_dense_leg:
         args.no_extra_legs = True
     legs = set() if args.no_extra_legs else set(LEGS) if args.legs == "all" else set(x for x in args.legs.split(",") if x)
@@ -1674,6 +1697,8 @@ def main():
                 del big
             except Exception as e:
                 out["large_batch"] = {"error": repr(e)}
+        if args.dump_outputs:
+            dump_outputs(got, args.dump_outputs)
         print(json.dumps(out), file=json_out, flush=True)
 
     try:

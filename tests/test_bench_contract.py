@@ -143,3 +143,57 @@ def test_a_rank_builds_only_its_shard_of_the_strong_workload():
         want = whole.slice(*bounds[r])
         assert np.array_equal(shard.rec_offset, want.rec_offset) and np.array_equal(shard.units, want.units)
         assert shard.records.tobytes() == want.records.tobytes()
+
+
+@pytest.mark.gpu
+def test_dump_outputs_are_the_timed_results_whatever_the_steps(hip_device, tmp_path):
+    """--dump-outputs DIR: the results of the timed path's last step, float64, equal to the oracle over bench's own seeded
+    workload, and the same bytes from a run with another number of timed steps"""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    from oracle import c_oracle
+    n = 20000
+    dumps = []
+    for steps in (2, 5):
+        out = tmp_path / ("steps%d" % steps)
+        r = subprocess.run([sys.executable, "bench.py", "--steps", str(steps), "--warmup", "1", "--units", str(n), "--no-cpu-baseline",
+                            "--no-extra-legs", "--dump-outputs", str(out)], cwd=ROOT, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        assert json.loads(r.stdout)["steps"] == steps
+        assert sorted(p.name for p in out.iterdir()) == sorted(f + ".npy" for f in bench.DUMP_FIELDS + ("unit",))
+        dumps.append({p.stem: np.load(p) for p in out.iterdir()})
+    for name, a in dumps[0].items():
+        assert a.dtype == np.float64 and a.shape[0] == n, name
+        assert a.tobytes() == dumps[1][name].tobytes(), name
+    assert np.array_equal(dumps[0]["unit"], np.arange(n))
+    want = c_oracle.genotype_batch(bench.generate("c3_mixed_1m", n, 0, 1))
+    got = dumps[0]
+    assert np.array_equal(got["gt"], want.gt) and np.array_equal(got["counts"], want.counts)
+    for f in ("gl", "sq", "tallies"):
+        assert np.max(np.abs(got[f] - want.rec[f])) <= 1e-6, f
+
+
+def test_dump_outputs_samples_a_large_result_within_the_bound(tmp_path):
+    """host only: above 64 MB the dump is a sorted, seeded sample of the units -- the same one on every call -- and each file
+    holds exactly the sampled units' fields"""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    from svtyper_amd.evidence import Results
+    n = 500_000
+    res = Results.empty(n)
+    rng = np.random.default_rng(1)
+    for f in bench.DUMP_FIELDS:
+        res.rec[f] = rng.integers(-1, 1000, res.rec[f].shape)
+    runs = []
+    for k in range(2):
+        out = tmp_path / str(k)
+        bench.dump_outputs(res, str(out))
+        assert sum(p.stat().st_size for p in out.iterdir()) <= 64_000_000
+        runs.append({p.stem: np.load(p) for p in out.iterdir()})
+    unit = runs[0]["unit"].astype(np.int64)
+    assert 0 < len(unit) < n and np.all(np.diff(unit) > 0) and unit[-1] < n
+    for f in bench.DUMP_FIELDS:
+        assert runs[0][f].dtype == np.float64 and np.array_equal(runs[0][f], res.rec[f][unit]), f
+        assert runs[0][f].tobytes() == runs[1][f].tobytes(), f

@@ -2,7 +2,10 @@
 whatever devices the box has: with fewer devices than ranks the ranks share them and the gather goes over gloo
 (bench.py's rule, the same as tests/test_multi_device.py), with N devices the gather is RCCL.  Every line of the
 multi-rank code -- shard cut, max-over-ranks timing, uneven gather, value_with_gather, the strong-scaling byte
-equality -- has run before the first 8-GPU SCALE run.  Replaces the Pool fan-out of svtyper/singlesample.py:723-751."""
+equality -- has run before the first 8-GPU SCALE run.  Replaces the Pool fan-out of svtyper/singlesample.py:723-751.
+At most 4 ranks: together with the test process, which holds the device, and the launcher that is at most six processes
+with the device open, the limit of a GPU box shared with other jobs.  Four ranks still run every N > 2 line (uneven
+shards, the maximum over ranks, a gather of more than two shards)."""
 import json
 import os
 import socket
@@ -55,7 +58,7 @@ def _common(d, n, total_units):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("n", [2, 8])
+@pytest.mark.parametrize("n", [2, 4])
 def test_weak_scaling_line(hip_device, n):
     """the driver's own command: the workload PER rank, no collective inside a step, one gather at the end"""
     d = _launch(n, ["--units", "12000"])
@@ -86,7 +89,7 @@ def test_weak_scaling_line(hip_device, n):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("n,rec", [(2, 96), (8, 96), (2, 128)])
+@pytest.mark.parametrize("n,rec", [(2, 96), (4, 96), (2, 128)])
 def test_strong_scaling_gathers_the_single_rank_bytes(hip_device, n, rec):
     """configs[3] literally: ONE workload cut by distributed.shard_bounds; rank 0 runs it alone afterwards and compares the bytes
     (rec = 96, the default: tagged SVT_FLAG_RESULT96 records through the gather, put in order and expanded on rank 0)"""
@@ -99,7 +102,7 @@ def test_strong_scaling_gathers_the_single_rank_bytes(hip_device, n, rec):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("n,scaling", [(2, "weak"), (2, "strong"), (8, "strong")])
+@pytest.mark.parametrize("n,scaling", [(2, "weak"), (2, "strong"), (4, "strong")])
 def test_c5_multisample_shards_at_whole_sites(hip_device, n, scaling):
     """the configs[4] shape: 32 samples per site, per-sample libraries (library windows); shards are cut at multiples of 32"""
     sites = 96
