@@ -134,97 +134,125 @@ int d2h_results(svt_batch* b, svt_result* out)
     return SVT_OK;
 }
 
-// payload_of(u) = first payload item (16 bytes each) of unit u; upload(i0, i1) enqueues items [i0, i1) on b->stream
-template <typename PayloadOf, typename Upload>
-int run_pipelined(svt_batch* b, svt_result* out, bool* download_left, PayloadOf&& payload_of, Upload&& upload)
+// One piece of a pipelined one shot, its upload enqueued on b->stream: units [u0, u1) are genotyped on ps.compute once it has
+// landed (their tagged result records, SVT_FLAG_RESULT96, in slots [s0, s1)), and the records go down on ps.down -- into the
+// caller's page-locked array (`pinned_out`), or as 96-byte records into `scratch96` (*down: the event of that copy).  With
+// neither they stay on the device.
+int pipe_piece(svt_batch* b, PipeStreams& ps, uint64_t u0, uint64_t u1, uint64_t s0, uint64_t s1, svt_result* pinned_out,
+               void* scratch96, hipEvent_t* down)
 {
-    *download_left = false;
-    const uint64_t n = b->n_units;
-    StageTimer tm0;
-    PipeStreams ps;
-    SVT_TRY(g_handles.get_stream(&ps.compute));
-    SVT_TRY(g_handles.get_stream(&ps.down));
-    const bool r96 = (b->flags & SVT_FLAG_RESULT96) != 0;
-    const bool out_pinned = n && !r96 && g_pinned.is_pinned(out, n * sizeof(svt_result));
-    // 96-byte device records: every piece comes down into a page-locked scratch as soon as its launch is through and is
-    // expanded into the caller's array while the later pieces are still on their way
-    struct Scratch { void* p = nullptr; ~Scratch() { g_pinned.put(p); } } scratch;
-    struct Piece { uint64_t u0, u1, s0, s1; hipEvent_t down; };
-    std::vector<Piece> pieces;
-    StageTimer tm;
-    static const uint64_t piece_mb = std::getenv("SVT_PIPE_MB") ? std::strtoull(std::getenv("SVT_PIPE_MB"), nullptr, 10) : 64;
-    const uint64_t kPieceItems = (std::max<uint64_t>(piece_mb, 1) << 20) / 16;   // payload per piece (the staging ring's piece size)
-    // the pieces: whole units up to kPieceItems of payload each (at least one unit); their tagged result records
-    // (SVT_FLAG_RESULT96) take whole workgroups' worth of slots per launch
-    uint64_t total_slots = 0;
-    for (uint64_t u0 = 0; u0 < n;) {
-        uint64_t lo = u0 + 1, hi = n;
-        const uint64_t want = payload_of(u0) + kPieceItems;
-        while (lo < hi) {   // largest u1 with payload_of(u1) <= want
-            const uint64_t mid = lo + (hi - lo + 1) / 2;
-            if (payload_of(mid) <= want) lo = mid; else hi = mid - 1;
-        }
-        const uint64_t slots = r96 ? slots_of_launch(b, lo - u0) : lo - u0;
-        pieces.push_back(Piece{u0, lo, total_slots, total_slots + slots, nullptr});
-        total_slots += slots;
-        u0 = lo;
+    hipEvent_t landed, done;
+    SVT_TRY(ps.event(&landed));
+    HIP_TRY(hipEventRecord(landed, b->stream));
+    HIP_TRY(hipStreamWaitEvent(ps.compute, landed, 0));
+    SVT_TRY(launch_range(b, u0, u1, ps.compute, s0));
+    if (!pinned_out && !scratch96) return SVT_OK;
+    SVT_TRY(ps.event(&done));
+    HIP_TRY(hipEventRecord(done, ps.compute));
+    HIP_TRY(hipStreamWaitEvent(ps.down, done, 0));
+    if (pinned_out) {
+        HIP_TRY(hipMemcpyAsync(pinned_out + u0, b->out_dev + u0, (u1 - u0) * sizeof(svt_result), hipMemcpyDeviceToHost, ps.down));
+        return SVT_OK;
     }
-    if (r96 && n) {
-        if (total_slots >= 0xFFFFFFF0ull) return fail(SVT_ERR_INVALID, "too many result slots in one batch");
-        SVT_TRY(ensure_result_slots(b, total_slots));
-        b->out_slots = total_slots;
-        scratch.p = g_pinned.get(total_slots * sizeof(svt_result96));
-        if (!scratch.p) return fail(SVT_ERR_NOMEM, "page-locked scratch for the result records");
-    }
-    for (Piece& pc : pieces) {
-        const uint64_t u0 = pc.u0, u1 = pc.u1;
-        SVT_TRY(upload(payload_of(u0), payload_of(u1)));
-        hipEvent_t landed, done;
-        SVT_TRY(ps.event(&landed));
-        HIP_TRY(hipEventRecord(landed, b->stream));
-        HIP_TRY(hipStreamWaitEvent(ps.compute, landed, 0));
-        SVT_TRY(launch_range(b, u0, u1, ps.compute, pc.s0));
-        if (out_pinned) {
-            SVT_TRY(ps.event(&done));
-            HIP_TRY(hipEventRecord(done, ps.compute));
-            HIP_TRY(hipStreamWaitEvent(ps.down, done, 0));
-            HIP_TRY(hipMemcpyAsync(out + u0, b->out_dev + u0, (u1 - u0) * sizeof(svt_result), hipMemcpyDeviceToHost, ps.down));
-        } else if (r96) {
-            SVT_TRY(ps.event(&done));
-            HIP_TRY(hipEventRecord(done, ps.compute));
-            HIP_TRY(hipStreamWaitEvent(ps.down, done, 0));
-            HIP_TRY(hipMemcpyAsync(static_cast<unsigned char*>(scratch.p) + pc.s0 * sizeof(svt_result96),
-                                   reinterpret_cast<const unsigned char*>(b->out_dev) + pc.s0 * sizeof(svt_result96),
-                                   (pc.s1 - pc.s0) * sizeof(svt_result96), hipMemcpyDeviceToHost, ps.down));
-            SVT_TRY(ps.event(&pc.down));
-            HIP_TRY(hipEventRecord(pc.down, ps.down));
-        }
-    }
-    tm.mark("pipeline: pieces enqueued");
-    // (96-byte records: piece k is expanded as soon as it is down, while the later pieces are still going up; should the pass
-    // report a contract violation below, what was expanded is discarded with the error)
-    Placed placed(n);
-    if (r96)
-        for (const Piece& pc : pieces) {
-            HIP_TRY(hipEventSynchronize(pc.down));
-            expand96(static_cast<const svt_result96*>(scratch.p) + pc.s0, pc.s1 - pc.s0, out, placed);
-        }
-    HIP_TRY(hipStreamSynchronize(b->stream));
-    tm.mark("pipeline: uploads done");
-    HIP_TRY(hipStreamSynchronize(ps.compute));
-    b->have_results = true;
-    SVT_TRY(check_stream_errors(b));
-    tm.mark("pipeline: passes done");
-    if (r96) {
-        if (!placed.covers(n)) return fail(SVT_ERR_INTERNAL, "the device result records do not cover every unit exactly once");
-    } else if (out_pinned) {
-        HIP_TRY(hipStreamSynchronize(ps.down));
-    } else {
-        *download_left = true;   // pageable output: the caller downloads through the staging ring once it is free
-    }
-    tm.mark("pipeline: downloads done");
-    (void)tm0;
+    HIP_TRY(hipMemcpyAsync(static_cast<unsigned char*>(scratch96) + s0 * sizeof(svt_result96),
+                           reinterpret_cast<const unsigned char*>(b->out_dev) + s0 * sizeof(svt_result96),
+                           (s1 - s0) * sizeof(svt_result96), hipMemcpyDeviceToHost, ps.down));
+    SVT_TRY(ps.event(down));
+    HIP_TRY(hipEventRecord(*down, ps.down));
     return SVT_OK;
+}
+
+// The pipelined one shot of a batch whose payload create_stream / create_packed left to the caller: `items`, n_items of 16 bytes
+// in host memory (straight DMA when they are page-locked, else through the staging ring); payload_of(u) = first item of unit u.
+template <typename PayloadOf>
+int run_pipelined(svt_batch* b, svt_result* out, PayloadOf&& payload_of, const void* items, uint64_t n_items)
+{
+    bool download_left = false;   // pageable output: downloaded through the staging ring once it is free
+    {
+        Stager st(b->stream);   // (holds this device's staging ring, which d2h_results takes too)
+        const bool pinned = g_pinned.is_pinned(items, n_items * 16);
+        const uint64_t n = b->n_units;
+        StageTimer tm0;
+        PipeStreams ps;
+        SVT_TRY(g_handles.get_stream(&ps.compute));
+        SVT_TRY(g_handles.get_stream(&ps.down));
+        const bool r96 = (b->flags & SVT_FLAG_RESULT96) != 0;
+        const bool out_pinned = n && !r96 && g_pinned.is_pinned(out, n * sizeof(svt_result));
+        // 96-byte device records: every piece comes down into a page-locked scratch as soon as its launch is through and is
+        // expanded into the caller's array while the later pieces are still on their way
+        struct Scratch { void* p = nullptr; ~Scratch() { g_pinned.put(p); } } scratch;
+        struct Piece { uint64_t u0, u1, s0, s1; hipEvent_t down; };
+        std::vector<Piece> pieces;
+        StageTimer tm;
+        static const uint64_t piece_mb = std::getenv("SVT_PIPE_MB") ? std::strtoull(std::getenv("SVT_PIPE_MB"), nullptr, 10) : 64;
+        const uint64_t kPieceItems = (std::max<uint64_t>(piece_mb, 1) << 20) / 16;   // payload per piece (the staging ring's piece size)
+        // the pieces: whole units up to kPieceItems of payload each (at least one unit); their tagged result records
+        // (SVT_FLAG_RESULT96) take whole workgroups' worth of slots per launch
+        uint64_t total_slots = 0;
+        for (uint64_t u0 = 0; u0 < n;) {
+            uint64_t lo = u0 + 1, hi = n;
+            const uint64_t want = payload_of(u0) + kPieceItems;
+            while (lo < hi) {   // largest u1 with payload_of(u1) <= want
+                const uint64_t mid = lo + (hi - lo + 1) / 2;
+                if (payload_of(mid) <= want) lo = mid; else hi = mid - 1;
+            }
+            const uint64_t slots = r96 ? slots_of_launch(b, lo - u0) : lo - u0;
+            pieces.push_back(Piece{u0, lo, total_slots, total_slots + slots, nullptr});
+            total_slots += slots;
+            u0 = lo;
+        }
+        if (r96 && n) {
+            if (total_slots >= 0xFFFFFFF0ull) return fail(SVT_ERR_INVALID, "too many result slots in one batch");
+            SVT_TRY(ensure_result_slots(b, total_slots));
+            b->out_slots = total_slots;
+            scratch.p = g_pinned.get(total_slots * sizeof(svt_result96));
+            if (!scratch.p) return fail(SVT_ERR_NOMEM, "page-locked scratch for the result records");
+        }
+        for (Piece& pc : pieces) {
+            const uint64_t i0 = payload_of(pc.u0), i1 = payload_of(pc.u1);
+            char* dst = static_cast<char*>(b->d_records) + i0 * 16;
+            const char* src = static_cast<const char*>(items) + i0 * 16;
+            if (pinned) HIP_TRY(hipMemcpyAsync(dst, src, (i1 - i0) * 16, hipMemcpyHostToDevice, b->stream));
+            else SVT_TRY(st.copy(dst, src, (i1 - i0) * 16));
+            SVT_TRY(pipe_piece(b, ps, pc.u0, pc.u1, pc.s0, pc.s1, out_pinned ? out : nullptr, scratch.p, &pc.down));
+        }
+        tm.mark("pipeline: pieces enqueued");
+        // (96-byte records: piece k is expanded as soon as it is down, while the later pieces are still going up; should the pass
+        // report a contract violation below, what was expanded is discarded with the error)
+        Placed placed(n);
+        if (r96)
+            for (const Piece& pc : pieces) {
+                HIP_TRY(hipEventSynchronize(pc.down));
+                expand96(static_cast<const svt_result96*>(scratch.p) + pc.s0, pc.s1 - pc.s0, out, placed);
+            }
+        HIP_TRY(hipStreamSynchronize(b->stream));
+        tm.mark("pipeline: uploads done");
+        HIP_TRY(hipStreamSynchronize(ps.compute));
+        b->have_results = true;
+        SVT_TRY(check_stream_errors(b));
+        tm.mark("pipeline: passes done");
+        if (r96) {
+            if (!placed.covers(n)) return fail(SVT_ERR_INTERNAL, "the device result records do not cover every unit exactly once");
+        } else if (out_pinned) {
+            HIP_TRY(hipStreamSynchronize(ps.down));
+        } else {
+            download_left = true;
+        }
+        tm.mark("pipeline: downloads done");
+        (void)tm0;
+    }
+    return download_left ? d2h_results(b, out) : SVT_OK;
+}
+
+// The one shot through a resident batch: create(in, device, flags, &b), one pass, results, release.
+template <typename In>
+int genotype_one_batch(int (*create)(const In*, int, unsigned, svt_batch**), const In* in, svt_result* out, int device, unsigned flags)
+{
+    svt_batch* created = nullptr;
+    SVT_TRY(create(in, device, flags, &created));
+    const BatchOwner b(created);
+    SVT_TRY(svt_batch_genotype(b.get(), 1));
+    return svt_batch_results(b.get(), out, in->n_units);
 }
 
 constexpr uint64_t kPipelineMinUnits = 32768;   // below this one upload + one launch is as good

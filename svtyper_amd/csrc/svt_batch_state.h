@@ -1,5 +1,5 @@
 // svt_batch_state.h -- part of the single translation unit svtyper_hip.hip (included there, in order; not a stand-alone header):
-// the resident batch's device scratch pools, the workgroup plan (which kernel, how many units per workgroup, which small-launch kernel) and the pass launch.
+// the resident batch's lifetime, the entry points' device and evidence checks, its device scratch pools, the workgroup plan (which kernel, how many units per workgroup, which small-launch kernel) and the pass launch.
 
 
 void free_batch(svt_batch* b)
@@ -24,6 +24,58 @@ void free_batch(svt_batch* b)
     g_handles.put_event(b->ev1, true);
     g_handles.put_stream(b->stream);   // (idle: synchronised above)
     delete b;
+}
+
+// A batch on its way through a create path or a one shot: released on every early return.  Neither free_batch nor
+// svt_packed_free sets the error text (nothing they call does), so the message of what failed survives the release.
+struct BatchFree {
+    void operator()(svt_batch* b) const { free_batch(b); }
+};
+using BatchOwner = std::unique_ptr<svt_batch, BatchFree>;
+
+int new_batch(BatchOwner* owner, int device, unsigned flags, int layout, uint64_t n_units, uint64_t n_records)
+{
+    owner->reset(new (std::nothrow) svt_batch());
+    svt_batch* b = owner->get();
+    if (!b) return fail(SVT_ERR_NOMEM, "out of host memory");
+    b->device = device;
+    b->flags = flags;
+    b->layout = layout;
+    b->n_units = n_units;
+    b->n_records = n_records;
+    return SVT_OK;
+}
+
+// the device index an entry point was given (svt_genotype_multi checks every device of its list without selecting one)
+int check_device(int device)
+{
+    const int ndev = svt_device_count();
+    if (ndev <= 0) return fail(SVT_ERR_NO_DEVICE, "no HIP device available (this library has no CPU fallback)");
+    if (device < 0 || device >= ndev) return fail(SVT_ERR_NO_DEVICE, "device index out of range");
+    return SVT_OK;
+}
+
+int select_device(int device)
+{
+    SVT_TRY(check_device(device));
+    HIP_TRY(hipSetDevice(device));
+    return SVT_OK;
+}
+
+// What svt_batch_create refuses in a caller's evidence batch, in the order it checks: the message, or null when the batch is
+// acceptable.  records_may_be_null: the records come another way (svt_batch_create_segments, the device's own records).
+const char* evidence_error(const svt_evidence_batch* in, unsigned flags, bool records_may_be_null = false)
+{
+    const uint64_t n = in->n_units;
+    if (flags & ~kKnownFlags) return "unknown flag bits";
+    if (n >= 0xFFFFFFF0ull) return "too many units in one batch (< 2^32)";
+    if (in->n_libs == 0 || in->n_libs > 65536 || !in->libs) return "n_libs must be 1..65536";
+    if (n && (!in->rec_offset || !in->units)) return "null unit arrays";
+    if (n && in->rec_offset[0] != 0) return "rec_offset[0] must be 0";
+    if (n && in->rec_offset[n] && !in->records && !records_may_be_null) return "null records";
+    if (!(in->split_weight >= 0.0) || !(in->disc_weight >= 0.0) || !std::isfinite(in->split_weight) || !std::isfinite(in->disc_weight))
+        return "weights must be finite and >= 0";
+    return nullptr;
 }
 
 // device scratch that only lives during svt_batch_create

@@ -17,37 +17,13 @@ static int svt_batch_create_impl(const svt_evidence_batch* in, int device, unsig
 {
     if (!in || !out) return fail(SVT_ERR_INVALID, "null argument");
     *out = nullptr;
+    if (const char* e = evidence_error(in, flags)) return fail(SVT_ERR_INVALID, e);
+    SVT_TRY(select_device(device));
     const uint64_t n = in->n_units;
-    if (flags & ~kKnownFlags) return fail(SVT_ERR_INVALID, "unknown flag bits");
-    if (n >= 0xFFFFFFF0ull) return fail(SVT_ERR_INVALID, "too many units in one batch (< 2^32)");
-    if (in->n_libs == 0 || in->n_libs > 65536 || !in->libs) return fail(SVT_ERR_INVALID, "n_libs must be 1..65536");
-    if (n && (!in->rec_offset || !in->units)) return fail(SVT_ERR_INVALID, "null unit arrays");
-    if (n && in->rec_offset[0] != 0) return fail(SVT_ERR_INVALID, "rec_offset[0] must be 0");
-    if (n && in->rec_offset[n] && !in->records) return fail(SVT_ERR_INVALID, "null records");
-    if (!(in->split_weight >= 0.0) || !(in->disc_weight >= 0.0) || !std::isfinite(in->split_weight) ||
-        !std::isfinite(in->disc_weight))
-        return fail(SVT_ERR_INVALID, "weights must be finite and >= 0");
-
-    const int ndev = svt_device_count();
-    if (ndev <= 0) return fail(SVT_ERR_NO_DEVICE, "no HIP device available (this library has no CPU fallback)");
-    if (device < 0 || device >= ndev) return fail(SVT_ERR_NO_DEVICE, "device index out of range");
-    HIP_TRY(hipSetDevice(device));
-
-    svt_batch* b = new (std::nothrow) svt_batch();
-    if (!b) return fail(SVT_ERR_NOMEM, "out of host memory");
-    b->device = device;
-    b->flags = flags;
-    b->layout = kLayoutStream;
-    b->n_units = n;
-    b->n_records = n ? in->rec_offset[n] : 0;
-    const int rc = create_stream(in, b);
-    if (rc != SVT_OK) {
-        const std::string keep = g_err;
-        free_batch(b);
-        g_err = keep;
-        return rc;
-    }
-    *out = b;
+    BatchOwner b;
+    SVT_TRY(new_batch(&b, device, flags, kLayoutStream, n, n ? in->rec_offset[n] : 0));
+    SVT_TRY(create_stream(in, b.get()));
+    *out = b.release();
     return SVT_OK;
 }
 
@@ -94,43 +70,24 @@ static int svt_batch_create_segments_impl(const svt_evidence_batch* in, const sv
         }
         return svt_batch_create_impl(&eb, device, flags, out);
     }
-    // the checks of svt_batch_create_impl (the records are not looked at on the host: the pass itself checks their contract)
-    if (n >= 0xFFFFFFF0ull) return fail(SVT_ERR_INVALID, "too many units in one batch (< 2^32)");
-    if (in->n_libs == 0 || in->n_libs > 65536 || !in->libs) return fail(SVT_ERR_INVALID, "n_libs must be 1..65536");
-    if (n && !in->units) return fail(SVT_ERR_INVALID, "null unit arrays");
-    if (n && in->rec_offset[0] != 0) return fail(SVT_ERR_INVALID, "rec_offset[0] must be 0");
-    if (!(in->split_weight >= 0.0) || !(in->disc_weight >= 0.0) || !std::isfinite(in->split_weight) || !std::isfinite(in->disc_weight))
-        return fail(SVT_ERR_INVALID, "weights must be finite and >= 0");
-    const int ndev = svt_device_count();
-    if (ndev <= 0) return fail(SVT_ERR_NO_DEVICE, "no HIP device available (this library has no CPU fallback)");
-    if (device < 0 || device >= ndev) return fail(SVT_ERR_NO_DEVICE, "device index out of range");
-    HIP_TRY(hipSetDevice(device));
-    svt_batch* b = new (std::nothrow) svt_batch();
-    if (!b) return fail(SVT_ERR_NOMEM, "out of host memory");
-    b->device = device;
-    b->flags = flags;
-    b->layout = kLayoutStream;
-    b->n_units = n;
-    b->n_records = n_rec;
-    int rc = create_stream(&eb, b, nullptr, 0, /*defer_records=*/true);
-    if (rc == SVT_OK && b->records_resident) rc = fail(SVT_ERR_INTERNAL, "svt_batch_create_segments: create_stream wanted the records");
-    if (rc == SVT_OK) {
+    // the checks of svt_batch_create_impl but the records' (they are not looked at on the host: the pass itself checks their contract)
+    if (const char* e = evidence_error(&eb, flags, /*records_may_be_null=*/true)) return fail(SVT_ERR_INVALID, e);
+    SVT_TRY(select_device(device));
+    BatchOwner b;
+    SVT_TRY(new_batch(&b, device, flags, kLayoutStream, n, n_rec));
+    SVT_TRY(create_stream(&eb, b.get(), nullptr, 0, /*defer_records=*/true));
+    if (b->records_resident) return fail(SVT_ERR_INTERNAL, "svt_batch_create_segments: create_stream wanted the records");
+    {
         Stager st(b->stream);
         char* at = static_cast<char*>(b->d_records);
-        for (uint32_t k = 0; k < n_segments && rc == SVT_OK; ++k) {
-            rc = st.copy(at, segments[k].records, segments[k].n_records * sizeof(svt_record));
+        for (uint32_t k = 0; k < n_segments; ++k) {
+            SVT_TRY(st.copy(at, segments[k].records, segments[k].n_records * sizeof(svt_record)));
             at += segments[k].n_records * sizeof(svt_record);
         }
-        if (rc == SVT_OK) rc = st.finish();
-        if (rc == SVT_OK) b->records_resident = true;
+        SVT_TRY(st.finish());
     }
-    if (rc != SVT_OK) {
-        const std::string keep = g_err;
-        free_batch(b);
-        g_err = keep;
-        return rc;
-    }
-    *out = b;
+    b->records_resident = true;
+    *out = b.release();
     return SVT_OK;
 }
 
@@ -153,10 +110,7 @@ static int svt_batch_create_from_fragments_impl(const svt_fragment_batch* in, in
     if (n && in->frag_offset[0] != 0) return fail(SVT_ERR_INVALID, "frag_offset[0] must be 0");
     const uint64_t n_frag = n ? in->frag_offset[n] : 0;
     if (n_frag && !in->fragments) return fail(SVT_ERR_INVALID, "null fragments");
-    const int ndev = svt_device_count();
-    if (ndev <= 0) return fail(SVT_ERR_NO_DEVICE, "no HIP device available (this library has no CPU fallback)");
-    if (device < 0 || device >= ndev) return fail(SVT_ERR_NO_DEVICE, "device index out of range");
-    HIP_TRY(hipSetDevice(device));
+    SVT_TRY(select_device(device));
 
     // unit headers
     std::vector<svt_unit> units(n);
@@ -244,26 +198,14 @@ static int svt_batch_create_from_fragments_impl(const svt_fragment_batch* in, in
     eb.libs = in->libs;
     eb.split_weight = in->split_weight;
     eb.disc_weight = in->disc_weight;
-    if (!(eb.split_weight >= 0.0) || !(eb.disc_weight >= 0.0) || !std::isfinite(eb.split_weight) ||
-        !std::isfinite(eb.disc_weight))
-        return fail(SVT_ERR_INVALID, "weights must be finite and >= 0");
-    svt_batch* b = new (std::nothrow) svt_batch();
-    if (!b) return fail(SVT_ERR_NOMEM, "out of host memory");
-    b->device = device;
-    b->flags = flags;
-    b->layout = kLayoutStream;
-    b->n_units = n;
-    b->n_records = n_frag;
-    const uint64_t cap = d_records.cap;
-    const int rc = create_stream(&eb, b, d_records.p, cap);
+    // (the checks above leave only the weights to be refused here)
+    if (const char* e = evidence_error(&eb, flags, /*records_may_be_null=*/true)) return fail(SVT_ERR_INVALID, e);
+    BatchOwner b;
+    SVT_TRY(new_batch(&b, device, flags, kLayoutStream, n, n_frag));
+    const int rc = create_stream(&eb, b.get(), d_records.p, d_records.cap);
     if (b->d_records == d_records.p) d_records.release();   // the batch owns the records now
-    if (rc != SVT_OK) {
-        const std::string keep = g_err;
-        free_batch(b);
-        g_err = keep;
-        return rc;
-    }
-    *out = b;
+    SVT_TRY(rc);
+    *out = b.release();
     return SVT_OK;
 }
 

@@ -42,58 +42,26 @@ static int svt_genotype_impl(const svt_evidence_batch* in, svt_result* out, int 
         return SVT_OK;
     }
     // the streamed layout from host records: upload, pass and download overlap by unit ranges
-    if (in && out && !(flags & ~kKnownFlags) && in->n_units >= kPipelineMinUnits &&
-        in->n_units < 0xFFFFFFF0ull && in->rec_offset && in->units && in->records && in->n_libs >= 1 && in->n_libs <= 65536 && in->libs &&
-        in->rec_offset[0] == 0 && in->split_weight >= 0.0 && in->disc_weight >= 0.0 && std::isfinite(in->split_weight) &&
-        std::isfinite(in->disc_weight)) {
-        const int ndev = svt_device_count();
-        if (ndev <= 0) return fail(SVT_ERR_NO_DEVICE, "no HIP device available (this library has no CPU fallback)");
-        if (device < 0 || device >= ndev) return fail(SVT_ERR_NO_DEVICE, "device index out of range");
-        HIP_TRY(hipSetDevice(device));
-        svt_batch* b = new (std::nothrow) svt_batch();
-        if (!b) return fail(SVT_ERR_NOMEM, "out of host memory");
-        b->device = device;
-        b->flags = flags;
-        b->layout = kLayoutStream;
-        b->n_units = in->n_units;
-        b->n_records = in->rec_offset[in->n_units];
-        int rc = create_stream(in, b, nullptr, 0, /*defer_records=*/true);
+    if (in && out && in->records && in->n_units >= kPipelineMinUnits && !evidence_error(in, flags)) {
+        SVT_TRY(select_device(device));
+        BatchOwner b;
+        SVT_TRY(new_batch(&b, device, flags, kLayoutStream, in->n_units, in->rec_offset[in->n_units]));
+        int rc = create_stream(in, b.get(), nullptr, 0, /*defer_records=*/true);
         if (rc == SVT_OK && (b->mode == kMultiLds || b->records_resident)) {
             // library windows: the launch walks window chunks, not unit ranges -- upload in one piece (a batch without window
             // hints was uploaded by create_stream, which read the windows off the records), one launch
             if (!b->records_resident) rc = h2d_staged(b->d_records, in->records, b->n_records * sizeof(uint4), b->stream);
-            if (rc == SVT_OK) rc = svt_batch_genotype(b, 1);
-            if (rc == SVT_OK) rc = svt_batch_results(b, out, in->n_units);
+            if (rc == SVT_OK) rc = svt_batch_genotype(b.get(), 1);
+            if (rc == SVT_OK) rc = svt_batch_results(b.get(), out, in->n_units);
         } else if (rc == SVT_OK) {
-            bool download_left = false;
-            {
-            Stager st(b->stream);   // (holds this device's staging ring)
-            const bool pinned = g_pinned.is_pinned(in->records, b->n_records * sizeof(uint4));
-            rc = run_pipelined(b, out, &download_left, [&](uint64_t u) { return in->rec_offset[u]; },
-                               [&](uint64_t i0, uint64_t i1) -> int {
-                                   char* dst = static_cast<char*>(b->d_records) + i0 * 16;
-                                   const char* src = reinterpret_cast<const char*>(in->records) + i0 * 16;
-                                   if (pinned) { HIP_TRY(hipMemcpyAsync(dst, src, (i1 - i0) * 16, hipMemcpyHostToDevice, b->stream)); return SVT_OK; }
-                                   return st.copy(dst, src, (i1 - i0) * 16);
-                               });
-            }
-            if (rc == SVT_OK && download_left) rc = d2h_results(b, out);
+            rc = run_pipelined(b.get(), out, [&](uint64_t u) { return in->rec_offset[u]; }, in->records, b->n_records);
         }
-        const std::string keep = g_err;
         StageTimer tm;
-        free_batch(b);
+        b.reset();
         tm.mark("one shot: batch released");
-        g_err = keep;
         return rc;
     }
-    svt_batch* b = nullptr;
-    SVT_TRY(svt_batch_create(in, device, flags, &b));
-    int rc = svt_batch_genotype(b, 1);
-    if (rc == SVT_OK) rc = svt_batch_results(b, out, in->n_units);
-    const std::string keep = g_err;
-    svt_batch_destroy(b);
-    g_err = keep;
-    return rc;
+    return genotype_one_batch(svt_batch_create, in, out, device, flags);
 }
 
 int svt_genotype(const svt_evidence_batch* in, svt_result* out, int device, unsigned flags)
@@ -173,10 +141,7 @@ static int svt_genotype_multi_impl(const svt_evidence_batch* in, svt_result* out
     if (!in || !devices || n_devices <= 0 || n_devices > 64) return fail(SVT_ERR_INVALID, "bad device list");
     const uint64_t n = in->n_units;
     if (n && (!out || !in->rec_offset || !in->units)) return fail(SVT_ERR_INVALID, "null argument");
-    const int ndev = svt_device_count();
-    if (ndev <= 0) return fail(SVT_ERR_NO_DEVICE, "no HIP device available (this library has no CPU fallback)");
-    for (int d = 0; d < n_devices; ++d)
-        if (devices[d] < 0 || devices[d] >= ndev) return fail(SVT_ERR_NO_DEVICE, "device index out of range");
+    for (int d = 0; d < n_devices; ++d) SVT_TRY(check_device(devices[d]));
     for (uint64_t u = 0; u < n; ++u)
         if (in->rec_offset[u + 1] < in->rec_offset[u]) return fail(SVT_ERR_INVALID, "rec_offset not monotone");
     std::vector<uint64_t> bounds((size_t)n_devices + 1);

@@ -28,25 +28,11 @@ static int svt_batch_create_packed_impl(const svt_packed_evidence* in, int devic
     *out = nullptr;
     if (flags & ~(SVT_FLAG_SSO_ASSOCIATION | SVT_FLAG_RESULT96)) return fail(SVT_ERR_INVALID, "packed evidence takes SVT_FLAG_SSO_ASSOCIATION and SVT_FLAG_RESULT96 only");
     if (in->n_units >= 0x55555550ull) return fail(SVT_ERR_INVALID, "too many units in one batch");
-    const int ndev = svt_device_count();
-    if (ndev <= 0) return fail(SVT_ERR_NO_DEVICE, "no HIP device available (this library has no CPU fallback)");
-    if (device < 0 || device >= ndev) return fail(SVT_ERR_NO_DEVICE, "device index out of range");
-    HIP_TRY(hipSetDevice(device));
-    svt_batch* b = new (std::nothrow) svt_batch();
-    if (!b) return fail(SVT_ERR_NOMEM, "out of host memory");
-    b->device = device;
-    b->flags = flags;
-    b->layout = kLayoutPacked;
-    b->n_units = in->n_units;
-    b->n_records = in->n_records;
-    const int rc = create_packed(in, b);
-    if (rc != SVT_OK) {
-        const std::string keep = g_err;
-        free_batch(b);
-        g_err = keep;
-        return rc;
-    }
-    *out = b;
+    SVT_TRY(select_device(device));
+    BatchOwner b;
+    SVT_TRY(new_batch(&b, device, flags, kLayoutPacked, in->n_units, in->n_records));
+    SVT_TRY(create_packed(in, b.get()));
+    *out = b.release();
     return SVT_OK;
 }
 
@@ -59,46 +45,13 @@ static int svt_genotype_packed_impl(const svt_packed_evidence* in, svt_result* o
 {
     if (in && out && !(flags & ~(SVT_FLAG_SSO_ASSOCIATION | SVT_FLAG_RESULT96)) && in->n_units >= kPipelineMinUnits && in->n_units < 0x55555550ull &&
         in->slot_offset && in->slots) {
-        const int ndev = svt_device_count();
-        if (ndev <= 0) return fail(SVT_ERR_NO_DEVICE, "no HIP device available (this library has no CPU fallback)");
-        if (device < 0 || device >= ndev) return fail(SVT_ERR_NO_DEVICE, "device index out of range");
-        HIP_TRY(hipSetDevice(device));
-        svt_batch* b = new (std::nothrow) svt_batch();
-        if (!b) return fail(SVT_ERR_NOMEM, "out of host memory");
-        b->device = device;
-        b->flags = flags;
-        b->layout = kLayoutPacked;
-        b->n_units = in->n_units;
-        b->n_records = in->n_records;
-        int rc = create_packed(in, b, /*defer_slots=*/true);
-        if (rc == SVT_OK) {
-            bool download_left = false;
-            {
-            Stager st(b->stream);
-            const bool pinned = g_pinned.is_pinned(in->slots, in->n_slots * 16);
-            rc = run_pipelined(b, out, &download_left, [&](uint64_t u) { return (uint64_t)in->slot_offset[3 * u]; },
-                               [&](uint64_t i0, uint64_t i1) -> int {
-                                   char* dst = static_cast<char*>(b->d_records) + i0 * 16;
-                                   const char* src = static_cast<const char*>(in->slots) + i0 * 16;
-                                   if (pinned) { HIP_TRY(hipMemcpyAsync(dst, src, (i1 - i0) * 16, hipMemcpyHostToDevice, b->stream)); return SVT_OK; }
-                                   return st.copy(dst, src, (i1 - i0) * 16);
-                               });
-            }
-            if (rc == SVT_OK && download_left) rc = d2h_results(b, out);
-        }
-        const std::string keep = g_err;
-        free_batch(b);
-        g_err = keep;
-        return rc;
+        SVT_TRY(select_device(device));
+        BatchOwner b;
+        SVT_TRY(new_batch(&b, device, flags, kLayoutPacked, in->n_units, in->n_records));
+        SVT_TRY(create_packed(in, b.get(), /*defer_slots=*/true));
+        return run_pipelined(b.get(), out, [&](uint64_t u) { return (uint64_t)in->slot_offset[3 * u]; }, in->slots, in->n_slots);
     }
-    svt_batch* b = nullptr;
-    SVT_TRY(svt_batch_create_packed(in, device, flags, &b));
-    int rc = svt_batch_genotype(b, 1);
-    if (rc == SVT_OK) rc = svt_batch_results(b, out, in->n_units);
-    const std::string keep = g_err;
-    svt_batch_destroy(b);
-    g_err = keep;
-    return rc;
+    return genotype_one_batch(svt_batch_create_packed, in, out, device, flags);
 }
 
 int svt_genotype_packed(const svt_packed_evidence* in, svt_result* out, int device, unsigned flags)
@@ -124,16 +77,11 @@ static int svt_genotype_packed_from_records_impl(const svt_evidence_batch* in, s
         svt_packed_evidence* p = nullptr;
         SVT_TRY(pack_evidence(in, &p));
         const int rc = svt_genotype_packed(p, out, device, flags);
-        const std::string keep = g_err;
         svt_packed_free(p);
-        g_err = keep;
         return rc;
     };
     if (!overlap) return serial();
-    const int ndev = svt_device_count();
-    if (ndev <= 0) return fail(SVT_ERR_NO_DEVICE, "no HIP device available (this library has no CPU fallback)");
-    if (device < 0 || device >= ndev) return fail(SVT_ERR_NO_DEVICE, "device index out of range");
-    HIP_TRY(hipSetDevice(device));
+    SVT_TRY(select_device(device));
     // the most records of any unit (the log10 table's bound) -- the encoder itself checks the offsets' monotony
     uint64_t max_f = 0;
     {
@@ -154,13 +102,9 @@ static int svt_genotype_packed_from_records_impl(const svt_evidence_batch* in, s
     const uint64_t slots_cap = n_rec / 16 * (in->n_libs > 1 ? 6 : 5) + 3 * n + 4096;
     if (slots_cap >= 0xFFFFFFF0ull) return serial();
 
-    svt_batch* b = new (std::nothrow) svt_batch();
-    if (!b) return fail(SVT_ERR_NOMEM, "out of host memory");
-    b->device = device;
-    b->flags = flags;
-    b->layout = kLayoutPacked;
-    b->n_units = n;
-    b->n_records = n_rec;
+    BatchOwner owner;
+    SVT_TRY(new_batch(&owner, device, flags, kLayoutPacked, n, n_rec));
+    svt_batch* b = owner.get();
     svt_packed_evidence shell{};
     shell.n_units = n;
     shell.n_slots = slots_cap;
@@ -221,29 +165,12 @@ static int svt_genotype_packed_from_records_impl(const svt_evidence_batch* in, s
                                        hipMemcpyHostToDevice, b->stream));
             HIP_TRY(hipMemcpyAsync(b->d_soff + 3 * u0, a->off + 3 * u0, (3 * (u1 - u0) + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, b->stream));
             HIP_TRY(hipMemcpyAsync(b->d_units + u0, a->units + u0, (u1 - u0) * sizeof(svt_unit), hipMemcpyHostToDevice, b->stream));
-            hipEvent_t landed, done, down;
-            SVT_TRY(c.ps.event(&landed));
-            HIP_TRY(hipEventRecord(landed, b->stream));
-            HIP_TRY(hipStreamWaitEvent(c.ps.compute, landed, 0));
             const uint64_t r0 = c.next_slot, r1 = r0 + (c.r96 ? slots_of_launch(b, u1 - u0) : 0);
             if (c.r96 && r1 > c.slot_cap) return fail(SVT_ERR_INTERNAL, "result slots of the ranges exceed their bound");
             c.next_slot = r1;
-            SVT_TRY(launch_range(b, u0, u1, c.ps.compute, r0));
-            if (c.out_pinned || c.r96) {
-                SVT_TRY(c.ps.event(&done));
-                HIP_TRY(hipEventRecord(done, c.ps.compute));
-                HIP_TRY(hipStreamWaitEvent(c.ps.down, done, 0));
-                if (c.out_pinned)
-                    HIP_TRY(hipMemcpyAsync(c.out + u0, b->out_dev + u0, (u1 - u0) * sizeof(svt_result), hipMemcpyDeviceToHost, c.ps.down));
-                else {
-                    HIP_TRY(hipMemcpyAsync(static_cast<unsigned char*>(c.scratch) + r0 * sizeof(svt_result96),
-                                           reinterpret_cast<const unsigned char*>(b->out_dev) + r0 * sizeof(svt_result96),
-                                           (r1 - r0) * sizeof(svt_result96), hipMemcpyDeviceToHost, c.ps.down));
-                    SVT_TRY(c.ps.event(&down));
-                    HIP_TRY(hipEventRecord(down, c.ps.down));
-                    c.pieces.push_back(Piece{r0, r1, down});
-                }
-            }
+            hipEvent_t down = nullptr;
+            SVT_TRY(pipe_piece(b, c.ps, u0, u1, r0, r1, c.out_pinned ? c.out : nullptr, c.scratch, &down));
+            if (c.r96) c.pieces.push_back(Piece{r0, r1, down});
             return SVT_OK;
         };
         sink.drain = [](void* vctx) {
@@ -272,9 +199,7 @@ static int svt_genotype_packed_from_records_impl(const svt_evidence_batch* in, s
     g_pinned.put(arr.off);
     g_pinned.put(arr.units);
     g_pinned.put(arr.slots);
-    const std::string keep = g_err;
-    free_batch(b);
-    g_err = keep;
+    owner.reset();
     if (overflow) return serial();   // (more slots than estimated: the plain route sizes the array exactly)
     return rc;
 }

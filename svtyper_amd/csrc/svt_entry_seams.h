@@ -6,9 +6,7 @@ static int svt_bayes_gt_impl(const int32_t* ref, const int32_t* alt, const uint8
 {
     if (n == 0) return SVT_OK;
     if (!ref || !alt || !is_dup || !out) return fail(SVT_ERR_INVALID, "null argument");
-    const int ndev = svt_device_count();
-    if (ndev <= 0) return fail(SVT_ERR_NO_DEVICE, "no HIP device available (this library has no CPU fallback)");
-    if (device < 0 || device >= ndev) return fail(SVT_ERR_NO_DEVICE, "device index out of range");
+    SVT_TRY(select_device(device));
     int64_t max_total = 0;
     for (uint64_t i = 0; i < n; ++i) {
         if (ref[i] < 0 || alt[i] < 0) return fail(SVT_ERR_INVALID, "negative read count");
@@ -20,7 +18,6 @@ static int svt_bayes_gt_impl(const int32_t* ref, const int32_t* alt, const uint8
     for (size_t i = 1; i < l10.size(); ++i) l10[i] = py_log10((double)i);
     GtConsts c{};
     fill_gt_consts(c, 1.0, 1.0);
-    HIP_TRY(hipSetDevice(device));
     DevScratch d_ref, d_alt, d_dup, d_l10, d_out;
     SVT_TRY(d_ref.alloc(n * sizeof(int32_t)));
     SVT_TRY(d_alt.alloc(n * sizeof(int32_t)));
@@ -54,9 +51,7 @@ static int svt_genotype_counts_impl(const double* counts, const uint8_t* is_dup,
     if (!counts || !is_dup || !out) return fail(SVT_ERR_INVALID, "null argument");
     if (!(split_weight >= 0.0) || !(disc_weight >= 0.0) || !std::isfinite(split_weight) || !std::isfinite(disc_weight))
         return fail(SVT_ERR_INVALID, "weights must be finite and >= 0");
-    const int ndev = svt_device_count();
-    if (ndev <= 0) return fail(SVT_ERR_NO_DEVICE, "no HIP device available (this library has no CPU fallback)");
-    if (device < 0 || device >= ndev) return fail(SVT_ERR_NO_DEVICE, "device index out of range");
+    SVT_TRY(select_device(device));
     double max_total = 0.0;   // bound of QR + QA: the log10 table must reach it
     for (uint64_t i = 0; i < n; ++i) {
         const double* t = counts + 5 * i;
@@ -70,7 +65,6 @@ static int svt_genotype_counts_impl(const double* counts, const uint8_t* is_dup,
     for (size_t i = 1; i < l10.size(); ++i) l10[i] = py_log10((double)i);
     GtConsts c{};
     fill_gt_consts(c, split_weight, disc_weight);
-    HIP_TRY(hipSetDevice(device));
     DevScratch d_counts, d_dup, d_l10, d_out;
     SVT_TRY(d_counts.alloc(n * 5 * sizeof(double)));
     SVT_TRY(d_dup.alloc(n));

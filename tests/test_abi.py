@@ -133,3 +133,181 @@ def test_struct_layouts_match_the_header(tmp_path):
     # the enumerations the result record is indexed with
     assert list(ev.COUNT_NAMES) == ["QR", "QA", "GQ", "DP", "RO", "AO", "RS", "AS", "ASC", "RP", "AP"]
     assert list(ev.TALLY_NAMES) == ["ref_seq", "alt_seq", "alt_clip", "ref_span", "alt_span"]
+
+
+def _evidence(n_units=2, n_records=4, n_libs=1, libs=True, records=True, rec_offset0=0, split_weight=1.0, disc_weight=1.0):
+    """A small svt_evidence_batch (ctypes) and the arrays it points at (keep them alive while it is used)."""
+    import numpy as np
+    from svtyper_amd import evidence as ev
+    off = np.linspace(0, n_records, n_units + 1).astype(np.uint64)
+    off[0] = rec_offset0
+    units = np.zeros(n_units, ev.UNIT_DTYPE)
+    recs = np.zeros(max(n_records, 1), ev.RECORD_DTYPE)
+    hist = np.ones(4, np.uint32)
+    clibs = (ev.CLibrary * max(n_libs, 1))()
+    for l in clibs:
+        l.hist = hist.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32))
+        l.n_bins, l.mean, l.sd = 4, 300.0, 30.0
+    cb = ev.CEvidenceBatch()
+    cb.n_units = n_units
+    cb.rec_offset = off.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64))
+    cb.units = units.ctypes.data
+    cb.records = recs.ctypes.data if records else None
+    cb.n_libs = n_libs
+    cb.libs = clibs if libs else None
+    cb.split_weight, cb.disc_weight = split_weight, disc_weight
+    return cb, (off, units, recs, hist, clibs)
+
+
+def _fragments(n_units=2, n_frags=4, n_libs=1, frag_offset0=0, fragments=True):
+    import numpy as np
+    from svtyper_amd import evidence as ev, geometry as geo
+    off = np.linspace(0, n_frags, n_units + 1).astype(np.uint64)
+    off[0] = frag_offset0
+    bps = np.zeros(n_units, geo.BREAKPOINT_DTYPE)
+    frags = np.zeros(max(n_frags, 1), geo.FRAGMENT_DTYPE)
+    hist = np.ones(4, np.uint32)
+    clibs = (ev.CLibrary * max(n_libs, 1))()
+    for l in clibs:
+        l.hist = hist.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32))
+        l.n_bins, l.mean, l.sd = 4, 300.0, 30.0
+    fb = geo.CFragmentBatch()
+    fb.n_units = n_units
+    fb.frag_offset = off.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64))
+    fb.breakpoints = bps.ctypes.data
+    fb.fragments = frags.ctypes.data if fragments else None
+    fb.n_libs = n_libs
+    fb.libs = clibs
+    fb.split_weight = fb.disc_weight = 1.0
+    fb.min_aligned, fb.split_slop = 20, 7
+    return fb, (off, bps, frags, hist, clibs)
+
+
+def test_entry_point_argument_errors():
+    """Inputs the C entry points refuse before they touch a device: the return code and the exact svt_last_error()
+    text, including which check fires first when several would."""
+    import numpy as np
+    from svtyper_amd import evidence as ev, hip
+    L = hip.load()
+    nan = float("nan")
+    INVALID, NO_DEVICE = -1, -2
+    out = np.zeros(64, ev.RESULT_DTYPE)
+    h = ctypes.c_void_p()
+
+    def create(**kw):
+        flags = kw.pop("flags", 0)
+        cb, keep = _evidence(**kw)
+        return L.svt_batch_create(ctypes.byref(cb), 0, flags, ctypes.byref(h))
+
+    def segments(n_segments=1, seg_records=4, flags=0, **kw):
+        cb, keep = _evidence(records=False, **kw)
+        recs = np.zeros(max(seg_records, 1), np.dtype([("x", "u1", 16)]))
+        segs = np.zeros(max(n_segments, 1), np.dtype([("records", "<u8"), ("n_records", "<u8")]))
+        for k in range(n_segments):
+            segs[k] = (recs.ctypes.data, seg_records // n_segments)
+        return L.svt_batch_create_segments(ctypes.byref(cb), segs.ctypes.data, n_segments, 0, flags, ctypes.byref(h))
+
+    def fragments(flags=0, **kw):
+        fb, keep = _fragments(**kw)
+        return L.svt_batch_create_from_fragments(ctypes.addressof(fb), 0, flags, None, ctypes.byref(h))
+
+    def genotype(flags=0, **kw):
+        cb, keep = _evidence(**kw)
+        return L.svt_genotype(ctypes.byref(cb), out.ctypes.data, 0, flags)
+
+    def multi(devices=(0,), n_devices=None, flags=0, monotone=True, **kw):
+        cb, keep = _evidence(**kw)
+        if not monotone:
+            keep[0][1] = 3
+            keep[0][2] = 1
+        devs = (ctypes.c_int * max(len(devices), 1))(*devices)
+        n = len(devices) if n_devices is None else n_devices
+        return L.svt_genotype_multi(ctypes.byref(cb), out.ctypes.data, devs, n, 1, flags)
+
+    def packed_from_records(flags=0, **kw):
+        cb, keep = _evidence(**kw)
+        return L.svt_genotype_packed_from_records(ctypes.byref(cb), out.ctypes.data, 0, flags)
+
+    n_libs_text = "n_libs must be 1..65536"
+    weights_text = "weights must be finite and >= 0"
+    cases = [
+        # svt_batch_create
+        ("create null", lambda: L.svt_batch_create(None, 0, 0, ctypes.byref(h)), INVALID, "null argument"),
+        ("create null out", lambda: L.svt_batch_create(ctypes.byref(_evidence()[0]), 0, 0, None), INVALID, "null argument"),
+        ("create flags", lambda: create(flags=1 << 20), INVALID, "unknown flag bits"),
+        ("create flags first", lambda: create(flags=1 << 20, n_libs=0, split_weight=nan), INVALID, "unknown flag bits"),
+        ("create n_libs 0", lambda: create(n_libs=0), INVALID, n_libs_text),
+        ("create n_libs 65537", lambda: create(n_libs=65537), INVALID, n_libs_text),
+        ("create libs null", lambda: create(libs=False), INVALID, n_libs_text),
+        ("create n_libs before offsets", lambda: create(n_libs=0, rec_offset0=1), INVALID, n_libs_text),
+        ("create rec_offset[0]", lambda: create(rec_offset0=1), INVALID, "rec_offset[0] must be 0"),
+        ("create offsets before records", lambda: create(rec_offset0=1, records=False), INVALID, "rec_offset[0] must be 0"),
+        ("create null records", lambda: create(records=False), INVALID, "null records"),
+        ("create records before weights", lambda: create(records=False, disc_weight=nan), INVALID, "null records"),
+        ("create NaN weight", lambda: create(split_weight=nan), INVALID, weights_text),
+        ("create negative weight", lambda: create(disc_weight=-1.0), INVALID, weights_text),
+        ("create infinite weight", lambda: create(split_weight=float("inf")), INVALID, weights_text),
+        # svt_batch_create_segments (the records come in the segments: a null `records` is not an error)
+        ("segments null", lambda: L.svt_batch_create_segments(None, None, 0, 0, 0, ctypes.byref(h)), INVALID, "null argument"),
+        ("segments null list", lambda: L.svt_batch_create_segments(ctypes.byref(_evidence()[0]), None, 1, 0, 0, ctypes.byref(h)),
+         INVALID, "null argument"),
+        ("segments fewer", lambda: segments(seg_records=2), INVALID,
+         "svt_batch_create_segments: the segments hold fewer records than rec_offset[n_units]"),
+        ("segments more", lambda: segments(n_segments=2, seg_records=8), INVALID,
+         "svt_batch_create_segments: the segments hold more records than rec_offset[n_units]"),
+        ("segments flags", lambda: segments(flags=1 << 20, n_records=0, seg_records=0, n_segments=0), INVALID, "unknown flag bits"),
+        ("segments n_libs 0", lambda: segments(n_libs=0), INVALID, n_libs_text),
+        ("segments rec_offset[0]", lambda: segments(rec_offset0=1), INVALID, "rec_offset[0] must be 0"),
+        ("segments NaN weight", lambda: segments(split_weight=nan), INVALID, weights_text),
+        ("segments negative weight", lambda: segments(disc_weight=-0.5), INVALID, weights_text),
+        # svt_batch_create_from_fragments
+        ("fragments null", lambda: L.svt_batch_create_from_fragments(None, 0, 0, None, ctypes.byref(h)), INVALID, "null argument"),
+        ("fragments flags", lambda: fragments(flags=1 << 20), INVALID, "unknown flag bits"),
+        ("fragments n_libs 0", lambda: fragments(n_libs=0), INVALID, n_libs_text),
+        ("fragments n_libs 65537", lambda: fragments(n_libs=65537), INVALID, n_libs_text),
+        ("fragments frag_offset[0]", lambda: fragments(frag_offset0=1), INVALID, "frag_offset[0] must be 0"),
+        ("fragments null fragments", lambda: fragments(fragments=False), INVALID, "null fragments"),
+        # svt_genotype
+        ("genotype null", lambda: L.svt_genotype(None, out.ctypes.data, 0, 0), INVALID, "null argument"),
+        ("genotype flags", lambda: genotype(flags=1 << 20), INVALID, "unknown flag bits"),
+        ("genotype n_libs 0", lambda: genotype(n_libs=0), INVALID, n_libs_text),
+        ("genotype n_libs 65537", lambda: genotype(n_libs=65537), INVALID, n_libs_text),
+        ("genotype rec_offset[0]", lambda: genotype(rec_offset0=1), INVALID, "rec_offset[0] must be 0"),
+        ("genotype null records", lambda: genotype(records=False), INVALID, "null records"),
+        ("genotype NaN weight", lambda: genotype(split_weight=nan), INVALID, weights_text),
+        ("genotype negative weight", lambda: genotype(disc_weight=-1.0), INVALID, weights_text),
+        # svt_genotype_multi (the device list is checked before the offsets' monotony)
+        ("multi null", lambda: L.svt_genotype_multi(None, out.ctypes.data, (ctypes.c_int * 1)(0), 1, 1, 0), INVALID, "bad device list"),
+        ("multi null devices", lambda: L.svt_genotype_multi(ctypes.byref(_evidence()[0]), out.ctypes.data, None, 1, 1, 0),
+         INVALID, "bad device list"),
+        ("multi no devices", lambda: multi(n_devices=0), INVALID, "bad device list"),
+        ("multi 65 devices", lambda: multi(devices=(0,) * 65), INVALID, "bad device list"),
+        ("multi null out", lambda: L.svt_genotype_multi(ctypes.byref(_evidence()[0]), None, (ctypes.c_int * 1)(0), 1, 1, 0),
+         INVALID, "null argument"),
+        ("multi device -1", lambda: multi(devices=(0, -1), monotone=False), NO_DEVICE,
+         "device index out of range" if hip.device_count() > 0 else "no HIP device available (this library has no CPU fallback)"),
+        # svt_genotype_packed_from_records
+        ("packed null", lambda: L.svt_genotype_packed_from_records(None, out.ctypes.data, 0, 0), INVALID, "null argument"),
+        ("packed null out", lambda: L.svt_genotype_packed_from_records(ctypes.byref(_evidence()[0]), None, 0, 0), INVALID,
+         "null argument"),
+        ("packed flags", lambda: packed_from_records(flags=1 << 20), INVALID,
+         "packed evidence takes SVT_FLAG_SSO_ASSOCIATION and SVT_FLAG_RESULT96 only"),
+        ("packed general tables", lambda: packed_from_records(flags=ev.FLAG_GENERAL_TABLES), INVALID,
+         "packed evidence takes SVT_FLAG_SSO_ASSOCIATION and SVT_FLAG_RESULT96 only"),
+        ("packed n_libs 0", lambda: packed_from_records(n_libs=0), INVALID, n_libs_text),
+    ]
+    for name, call, code, text in cases:
+        got = call()
+        assert (got, L.svt_last_error().decode()) == (code, text), name
+
+
+def test_only_the_c_abi_is_exported():
+    """Every dynamic symbol the library defines is a svt_* C entry point (svt_exports.map): its C++ internals can be
+    neither interposed on nor reached from outside."""
+    import subprocess
+    from svtyper_amd import hip
+    hip.build()
+    nm = subprocess.check_output(["nm", "-D", "--defined-only", hip.LIB_PATH], text=True)
+    names = [l.split()[-1] for l in nm.splitlines() if l.strip()]
+    assert len(names) >= len(declared_symbols()) + len(declared_symbols("svtyper_reads.h"))
+    assert [n for n in names if not n.startswith("svt_")] == []
