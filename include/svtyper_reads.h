@@ -99,6 +99,66 @@ typedef struct svt_evidence {
 int svt_bam_evidence(const svt_bam* bam, const svt_summarise_args* args, const svt_evidence_params* geometry, svt_evidence* out);
 void svt_evidence_free(svt_evidence* e);
 
+/* ---- the same records built from inflated BAM bytes by ONE piece of walk source (ABI 19) ---------
+ * svtyper_amd/csrc/svt_evidence_walk.h restates decode / tag walk / split-read QC / fragment table of
+ * the reader above as bounds-checked functions over bytes, compiled for the host and for the device.
+ * It works inside a strict envelope (fixed capacities, well-formed records, known read groups); a unit
+ * outside it is never guessed at: it is flagged with one of the reasons below.
+ *
+ * svt_bam_evidence_walk_host: the walk over host memory, no GPU, NO fallback -- a flagged unit comes
+ * back empty with out_of_envelope[u] = its reason (0 = inside the envelope; a unit the max_reads rule
+ * skips is `skipped`, not flagged).  For every unit that is not flagged rec_offset / records / skipped
+ * are those of svt_bam_evidence, byte for byte.  `kept_reads` (n_units, may be null): reads the unit
+ * keeps -- what SVT_WALK_CAP_READS bounds.  Release `out` with svt_evidence_free.                    */
+#define SVT_WALK_RANGE 2       /* a record does not fit its range of inflated bytes (truncated / corrupt
+                                  BGZF or record, record > 64 KiB, window on an unknown reference)      */
+#define SVT_WALK_READS 3       /* more kept reads in the unit than SVT_WALK_CAP_READS                    */
+#define SVT_WALK_NAME 4        /* query name longer than SVT_WALK_CAP_NAME                               */
+#define SVT_WALK_CIGAR 5       /* more CIGAR operations (read or SA entry) than SVT_WALK_CAP_CIGAR       */
+#define SVT_WALK_SA_CAP 6      /* SA value with more entries / bytes than SVT_WALK_CAP_SA_ENTRIES / _BYTES */
+#define SVT_WALK_NO_RG 7       /* read without a usable RG tag                                           */
+#define SVT_WALK_UNKNOWN_RG 8  /* RG not in the call's table, or its library beyond the library table    */
+#define SVT_WALK_MALFORMED 9   /* malformed tag area, SA value or SA CIGAR                               */
+#define SVT_WALK_MAPQ 10       /* SA MAPQ outside 0..255                                                 */
+#define SVT_WALK_N_REASONS 11
+
+#define SVT_WALK_CAP_READS 0
+#define SVT_WALK_CAP_NAME 1
+#define SVT_WALK_CAP_CIGAR 2
+#define SVT_WALK_CAP_SA_ENTRIES 3
+#define SVT_WALK_CAP_SA_BYTES 4
+#define SVT_WALK_CAP_RECORD 5
+uint32_t svt_evidence_walk_capacity(int which);   /* SVT_WALK_CAP_*; 0 for an unknown one */
+
+int svt_bam_evidence_walk_host(const svt_bam* bam, const svt_summarise_args* args, const svt_evidence_params* geometry,
+                               svt_evidence* out, uint8_t* out_of_envelope, uint32_t* kept_reads);
+
+/* svt_bam_evidence_device: the reader stage with the walk on the GPU.  The host keeps the BAI lookup and the
+ * BGZF inflate, uploads every inflated block once, one workgroup per unit builds the unit's records in HBM
+ * (svt_evidence_kernel.h); every out-of-envelope unit is recomputed by the host reader and spliced in, so the
+ * resident batch `*out` is the one svt_batch_create(svt_bam_evidence(...)) builds -- or the call fails with
+ * the code and text svt_bam_evidence has for that unit.  `header`: n_units / units / n_libs / libs / weights of
+ * the batch (rec_offset and records are ignored; SVT_UNIT_SKIP is set here for skipped units).  `skipped`
+ * (n_units, may be null) and `stats` (may be null) are filled.  Needs a GPU.                               */
+typedef struct svt_evidence_device_stats {
+    uint64_t n_units;
+    uint64_t reads_walked;                          /* records in the units' ranges                         */
+    uint64_t units_skipped;
+    uint64_t units_host;                            /* recomputed by the host reader ...                    */
+    uint64_t units_host_by_reason[SVT_WALK_N_REASONS]; /* ... by SVT_WALK_* reason                          */
+    uint64_t n_records;
+    uint64_t bytes_uploaded;                        /* arena + ranges + unit arrays                         */
+    double host_arena_s;                            /* BAI lookup + inflate + arena                         */
+    double upload_s;
+    double device_walk_s;                           /* the two launches, host-observed                      */
+    double host_fallback_s;
+    double batch_create_s;
+} svt_evidence_device_stats;
+
+int svt_bam_evidence_device(const svt_bam* bam, const svt_summarise_args* args, const svt_evidence_params* geometry,
+                            const svt_evidence_batch* header, int device, unsigned flags, svt_batch** out,
+                            uint8_t* skipped, svt_evidence_device_stats* stats);
+
 /* Library statistics straight from the BAM (svtyper/parsers.py:501-576): what Library.from_bam scans
  * for, for ONE library given as its read-group ids, in three passes from the first record each --
  *   read_length : max query length (M/I/S/=/X) over the library's reads until 10 001 of them were seen

@@ -84,7 +84,7 @@ def sv_genotype(bam_string, vcf_in, vcf_out, min_aligned, split_weight, disc_wei
     if vcf_in is None:
         sys.stderr.write("Warning: VCF not found.\n")
     native = None
-    if reader == "native":      # C++ reader: library scans now, fetch + fragment summaries later
+    if reader in ("native", "device"):      # C++ reader: library scans now, fetch + fragment summaries later
         from .native_reads import COUNT_CLASSIC, NativeBam
         native = [NativeBam(p) for p in bam_string.split(",")]
     samples: List[Sample] = [setup_sample(b, lib_info, num_samp, MIN_LIB_PREVALENCE, nb)
@@ -98,13 +98,13 @@ def sv_genotype(bam_string, vcf_in, vcf_out, min_aligned, split_weight, disc_wei
     if engine is None:
         engine = default_engine()
     vcf = Vcf()
-    if reader == "native":      # C++ fetch + summariser; geometry in the reader's threads ("host") or on the device
+    if reader in ("native", "device"):      # C++ fetch + summariser; geometry in the reader's threads ("host") or on the device
         collector = NativeUnitCollector(samples, native, split_weight, disc_weight, min_aligned, COUNT_CLASSIC,
-                                        max_reads, geometry="device" if geometry == "device" else "reader")
+                                        max_reads, geometry="walk" if reader == "device" else "device" if geometry == "device" else "reader")
     elif reader == "python":
         collector = UnitCollector(samples, split_weight, disc_weight, min_aligned, geometry)
     else:
-        raise ValueError("reader must be 'python' or 'native'")
+        raise ValueError("reader must be 'python', 'native' or 'device'")
     pending: list = []      # ordered output actions of the current chunk
     header_lines: list = []
     n_samp = len(samples)
@@ -197,7 +197,7 @@ def sv_genotype(bam_string, vcf_in, vcf_out, min_aligned, split_weight, disc_wei
         if var.get_svtype() == "BND":
             var2 = var
             var = _take_first_mate(vcf, bp, var2)
-        if reader == "native":
+        if reader in ("native", "device"):
             first_unit = collector.add_site(bp)
         else:
             first_unit = len(collector)
@@ -220,7 +220,7 @@ def sv_genotype(bam_string, vcf_in, vcf_out, min_aligned, split_weight, disc_wei
     bulk = None
     bulk_stats = None
     unpaired = False        # first BND mates left in the bulk parser at the end
-    if (reader == "native" and not debug and hasattr(vcf_in, "readline") and hasattr(vcf_in, "read")
+    if (reader in ("native", "device") and not debug and hasattr(vcf_in, "readline") and hasattr(vcf_in, "read")
             and os.environ.get("SVT_BULK_VCF", "1") != "0"):
         from . import bulk_vcf
         if bulk_vcf.available():
@@ -265,6 +265,8 @@ def sv_genotype(bam_string, vcf_in, vcf_out, min_aligned, split_weight, disc_wei
     pipe.close()
     if stats is not None:       # (keyword-only extra: where the caller's thread spent its time, pipeline.BulkFeeder.laps)
         stats.update(bulk_stats[0] if bulk_stats else {}, route=bulk_stats[1] if bulk_stats else "per line")
+        if reader == "device":      # the counters of svt_bam_evidence_device, summed over the run's calls
+            stats["device_reader"] = collector.device_stats
     if vcf._bnd_pending or unpaired:
         logging.warning("Unpaired breakends found in file. These will not be present in output.")
     vcf_in.close()
@@ -319,9 +321,10 @@ def get_args():
     p.add_argument("--debug", action="store_true", help=argparse.SUPPRESS)
     p.add_argument("--verbose", action="store_true", default=False, help="Report status updates")
     # not in the reference: where the host work runs (same output bytes either way)
-    p.add_argument("--reader", choices=("python", "native"), default="native",
+    p.add_argument("--reader", choices=("python", "native", "device"), default="native",
                    help="BAM access + fragment assembly: the C++ threads of libsvtyper_hip.so feeding the device "
-                        "geometry stage, or the portable Python reader (same output bytes) [native]")
+                        "geometry stage, the same with the evidence records built on the GPU (device), or the portable Python "
+                        "reader (same output bytes) [native]")
     p.add_argument("--geometry", choices=("host", "device"), default="host",
                    help="with --reader python: breakpoint-dependent read predicates on the host or on the GPU [host]")
     args = p.parse_args()

@@ -1,0 +1,204 @@
+// svt_entry_evidence.h -- part of the single translation unit svtyper_hip.hip (included there, in order; not a stand-alone header):
+// C ABI: svt_bam_evidence_device (include/svtyper_reads.h) and the read-back of a resident batch's records for its parity tests.
+
+static int svt_bam_evidence_device_impl(const svt_bam* bam, const svt_summarise_args* args, const svt_evidence_params* geometry,
+                                        const svt_evidence_batch* header, int device, unsigned flags, svt_batch** out,
+                                        uint8_t* skipped_out, svt_evidence_device_stats* stats)
+{
+    if (!bam || !args || !geometry || !header || !out) return fail(SVT_ERR_INVALID, "null argument");
+    *out = nullptr;
+    const uint64_t n = args->n_units;
+    if (header->n_units != n) return fail(SVT_ERR_INVALID, "svt_bam_evidence_device: header and args differ in n_units");
+    if (n && !header->units) return fail(SVT_ERR_INVALID, "null unit arrays");
+    if (header->n_libs != geometry->n_libs) return fail(SVT_ERR_INVALID, "svt_bam_evidence_device: header and geometry differ in n_libs");
+    svt_evidence_device_stats st_local{};
+    svt_evidence_device_stats& S = stats ? *stats : st_local;
+    S = svt_evidence_device_stats{};
+    S.n_units = n;
+    auto now = [] { return std::chrono::steady_clock::now(); };
+    auto since = [&](std::chrono::steady_clock::time_point t0) { return std::chrono::duration<double>(now() - t0).count(); };
+
+    // ---- host: BAI lookup, inflate, arena
+    ew::Arena arena;
+    SVT_TRY(ew::build_arena(bam, args, geometry, arena));
+    S.host_arena_s = arena.build_s;
+    S.reads_walked = arena.records_in_ranges;
+    SVT_TRY(select_device(device));
+
+    hipStream_t s = nullptr;
+    SVT_TRY(g_handles.get_stream(&s));
+    struct StreamReturn { hipStream_t s; ~StreamReturn() { g_handles.put_stream(s); } } stream_return{s};
+    struct Pooled {
+        int device;
+        void* p = nullptr;
+        uint64_t cap = 0;
+        ~Pooled() { g_pool.put(device, p, cap); }
+        int get(uint64_t bytes, bool records = false) { return g_pool.get(device, bytes, &p, &cap, records); }
+        void* release() { void* q = p; p = nullptr; return q; }
+    } d_arena{device}, d_records{device};
+    DevScratch d_ranges, d_units, d_windows, d_bps, d_rgs, d_refs, d_blob, d_flank, d_status, d_rows, d_reads, d_off, d_src, d_src_off, d_dst_off;
+    // declared behind every device buffer, so it runs in front of their release on every way out: nothing goes back to a pool
+    // while a kernel of this call may still be running
+    struct StreamSync { hipStream_t s; ~StreamSync() { (void)hipStreamSynchronize(s); } } stream_sync{s};
+    const std::vector<double> flank(geometry->lib_flank, geometry->lib_flank + geometry->n_libs);
+    auto t0 = now();
+    {
+        Stager st(s);
+        SVT_TRY(d_arena.get(arena.bytes.size()));
+        SVT_TRY(st.copy(d_arena.p, arena.bytes.data(), arena.bytes.size()));
+        SVT_TRY(upload(d_ranges, arena.ranges, st));
+        SVT_TRY(upload(d_units, arena.units, st));
+        SVT_TRY(d_windows.alloc(n * sizeof(svt_fetch_unit)));
+        SVT_TRY(st.copy(d_windows.p, args->windows, n * sizeof(svt_fetch_unit)));
+        SVT_TRY(d_bps.alloc(n * sizeof(svt_breakpoint)));
+        SVT_TRY(st.copy(d_bps.p, args->breakpoints, n * sizeof(svt_breakpoint)));
+        SVT_TRY(upload(d_rgs, arena.rgs, st));
+        SVT_TRY(upload(d_refs, arena.refs, st));
+        SVT_TRY(upload(d_blob, arena.blob, st));
+        SVT_TRY(upload(d_flank, flank, st));
+        SVT_TRY(st.finish());
+        S.bytes_uploaded = arena.bytes.size() + arena.ranges.size() * sizeof(ew::Range) + n * (sizeof(ew::UnitRanges) + sizeof(svt_fetch_unit) + sizeof(svt_breakpoint)) + arena.blob.size();
+    }
+    SVT_TRY(d_status.alloc(n * sizeof(uint32_t)));
+    SVT_TRY(d_rows.alloc(n * sizeof(uint32_t)));
+    SVT_TRY(d_reads.alloc(n * sizeof(uint32_t)));
+    SVT_TRY(d_off.alloc((n + 1) * sizeof(uint64_t)));
+    HIP_TRY(hipStreamSynchronize(s));
+    S.upload_s = since(t0);
+
+    EvidenceArgs a{};
+    a.P = arena.params(args, geometry);
+    a.P.arena = static_cast<const uint8_t*>(d_arena.p);
+    a.P.ranges = d_ranges.as<ew::Range>();
+    a.P.units = d_units.as<ew::UnitRanges>();
+    a.P.windows = d_windows.as<svt_fetch_unit>();
+    a.P.bps = d_bps.as<svt_breakpoint>();
+    a.P.rgs = d_rgs.as<ew::NameRef>();
+    a.P.refs = d_refs.as<ew::NameRef>();
+    a.P.blob = d_blob.as<uint8_t>();
+    a.P.lib_flank = d_flank.as<double>();
+    a.n_units = (uint32_t)n;
+    a.status = d_status.as<uint32_t>();
+    a.n_rows = d_rows.as<uint32_t>();
+    a.n_reads = d_reads.as<uint32_t>();
+    a.rec_offset = d_off.as<uint64_t>();
+    a.records = nullptr;
+    const size_t lds = sizeof(ew::UnitScratch);
+    static_assert(sizeof(ew::UnitScratch) <= 80 * 1024, "two workgroups of the evidence kernel per CU");
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&svt_evidence_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&svt_evidence_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+
+    // ---- launch 1: status and rows per unit
+    t0 = now();
+    std::vector<uint32_t> status(n), rows(n);
+    if (n) {
+        hipLaunchKernelGGL(svt_evidence_kernel<false>, dim3((unsigned)n), dim3(kEvidenceBlock), lds, s, a);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(status.data(), d_status.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(rows.data(), d_rows.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    }
+    HIP_TRY(hipStreamSynchronize(s));
+    S.device_walk_s = since(t0);
+
+    // ---- host: the units outside the envelope, by the reader itself
+    t0 = now();
+    std::vector<uint64_t> host_ids;
+    for (uint64_t u = 0; u < n; ++u) {
+        if (status[u] >= ew::EW_N_STATUS) return fail(SVT_ERR_INTERNAL, "svt_bam_evidence_device: unit status out of range");
+        if (status[u] >= ew::EW_RANGE) {
+            host_ids.push_back(u);
+            ++S.units_host_by_reason[status[u]];
+        }
+    }
+    S.units_host = host_ids.size();
+    std::vector<svt_record> host_records;
+    std::vector<uint64_t> host_counts;
+    std::vector<uint8_t> host_skipped;
+    SVT_TRY(ew::host_units(bam, args, geometry, host_ids, host_records, host_counts, host_skipped));
+    S.host_fallback_s = since(t0);
+
+    // ---- rec_offset: the counts of both kinds of units in one scan
+    std::vector<uint64_t> rec_offset(n + 1, 0);
+    std::vector<svt_unit> units(header->units, header->units + n);
+    {
+        size_t hk = 0;
+        for (uint64_t u = 0; u < n; ++u) {
+            uint64_t cnt = rows[u];
+            bool skip = status[u] == ew::EW_SKIPPED;
+            if (hk < host_ids.size() && host_ids[hk] == u) { cnt = host_counts[hk]; skip = host_skipped[hk] != 0; ++hk; }
+            rec_offset[u + 1] = rec_offset[u] + cnt;
+            if (skip) { units[u].flags |= SVT_UNIT_SKIP; ++S.units_skipped; }
+            if (skipped_out) skipped_out[u] = skip ? 1 : 0;
+        }
+    }
+    const uint64_t n_rec = rec_offset[n];
+    S.n_records = n_rec;
+    if (n_rec > max_batch_records()) return fail(SVT_ERR_INVALID, "too many records in one batch (< 2^32): cut the call into fewer units");
+
+    // ---- launch 2: the records, where the batch wants them; then the host's units into their places
+    t0 = now();
+    SVT_TRY(d_records.get((n_rec + kBlockRecords) * sizeof(uint4), /*records=*/true));   // whole 128-byte blocks (kLayoutStream)
+    {
+        Stager st(s);
+        SVT_TRY(st.copy(d_off.p, rec_offset.data(), (n + 1) * sizeof(uint64_t)));
+        if (!host_ids.empty()) {
+            std::vector<uint64_t> src_off(host_ids.size() + 1, 0), dst_off(host_ids.size());
+            for (size_t k = 0; k < host_ids.size(); ++k) { src_off[k + 1] = src_off[k] + host_counts[k]; dst_off[k] = rec_offset[host_ids[k]]; }
+            SVT_TRY(upload(d_src, host_records, st));
+            SVT_TRY(upload(d_src_off, src_off, st));
+            SVT_TRY(upload(d_dst_off, dst_off, st));
+        }
+        SVT_TRY(st.finish());
+    }
+    a.records = static_cast<uint4*>(d_records.p);
+    if (n) {
+        hipLaunchKernelGGL(svt_evidence_kernel<true>, dim3((unsigned)n), dim3(kEvidenceBlock), lds, s, a);
+        HIP_TRY(hipGetLastError());
+    }
+    if (!host_ids.empty()) {
+        hipLaunchKernelGGL(svt_evidence_scatter_kernel, dim3((unsigned)host_ids.size()), dim3(kEvidenceBlock), 0, s, d_src.as<uint4>(),
+                           d_src_off.as<uint64_t>(), d_dst_off.as<uint64_t>(), (uint32_t)host_ids.size(), static_cast<uint4*>(d_records.p));
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipStreamSynchronize(s));
+    S.device_walk_s += since(t0);
+
+    // ---- the resident batch, from the records that are already in HBM
+    t0 = now();
+    svt_evidence_batch eb = *header;
+    eb.rec_offset = rec_offset.data();
+    eb.units = units.data();
+    eb.records = nullptr;
+    if (const char* e = evidence_error(&eb, flags, /*records_may_be_null=*/true)) return fail(SVT_ERR_INVALID, e);
+    BatchOwner b;
+    SVT_TRY(new_batch(&b, device, flags, kLayoutStream, n, n_rec));
+    const int rc = create_stream(&eb, b.get(), d_records.p, d_records.cap);
+    if (b->d_records == d_records.p) d_records.release();   // the batch owns the records now
+    SVT_TRY(rc);
+    S.batch_create_s = since(t0);
+    *out = b.release();
+    return SVT_OK;
+}
+
+int svt_bam_evidence_device(const svt_bam* bam, const svt_summarise_args* args, const svt_evidence_params* geometry,
+                            const svt_evidence_batch* header, int device, unsigned flags, svt_batch** out, uint8_t* skipped,
+                            svt_evidence_device_stats* stats)
+{
+    return guarded([&] { return svt_bam_evidence_device_impl(bam, args, geometry, header, device, flags, out, skipped, stats); });
+}
+
+// the records and offsets of a resident batch of canonical records, back on the host (parity tests of the device reader):
+// rec_offset holds n_units + 1 entries, records rec_offset[n_units] (pass null to fetch only the offsets)
+int svt_debug_batch_records(svt_batch* b, uint64_t* rec_offset, svt_record* records)
+{
+    return guarded([&]() -> int {
+        if (!b || !rec_offset) return fail(SVT_ERR_INVALID, "null argument");
+        if (b->layout != kLayoutStream || !b->records_resident) return fail(SVT_ERR_INVALID, "canonical resident records only");
+        HIP_TRY(hipSetDevice(b->device));
+        HIP_TRY(hipStreamSynchronize(b->stream));
+        if (b->n_units == 0) { rec_offset[0] = 0; return SVT_OK; }      // (a batch without units has no offsets in HBM)
+        HIP_TRY(hipMemcpy(rec_offset, b->d_off, (b->n_units + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost));
+        if (records && b->n_records) HIP_TRY(hipMemcpy(records, b->d_records, b->n_records * sizeof(svt_record), hipMemcpyDeviceToHost));
+        return SVT_OK;
+    });
+}

@@ -34,6 +34,7 @@
 
 #include "../../include/svtyper_reads.h"
 #include "svt_error.h"
+#include "svt_evidence_arena.h"
 #include "svt_geometry_math.h"
 #include "svt_host_cpus.h"
 
@@ -209,6 +210,8 @@ public:
     void mark_bad() { bad_ = true; }   // the record stream inside the blocks is corrupt
     uint64_t n_inflated = 0, n_shared_hits = 0, n_ahead = 0;   // (SVT_TRACE)
     double inflate_s = 0.0;
+    // when set: every block this reader loads is noted here (the arena of svt_bam_evidence_device is put together from them)
+    std::vector<std::pair<uint64_t, BlockRef>>* touched = nullptr;
 
     void seek(uint64_t voff)
     {
@@ -282,6 +285,7 @@ private:
         slots_[i] = b;
         block_ = b.get();
         coff_ = coff;
+        if (touched) touched->emplace_back(coff, b);
         return !block_->data.empty() || block_->next > coff;
     }
     bool park(uint64_t coff, bool is_bad)                // end of file / unusable block: an empty block that is its own successor
@@ -721,21 +725,16 @@ bool read_record(Bgzf& z, std::vector<uint8_t>& buf, Record& r)
     return true;
 }
 
-// pysam-style fetch: records with pos < end and reference end > beg, in file order; `fn` returns
-// false to stop.  Mirrors svtyper_amd/bam.py::AlignmentFile.fetch.
-template <typename Fn>
-bool fetch(const svt_bam& bam, Bgzf& z, int32_t tid, int64_t beg, int64_t end, std::vector<uint8_t>& buf, Fn&& fn)
+// the merged BAI chunks a fetch of [beg, end) on `tid` walks, in file order (scratch of the calling thread)
+const std::vector<std::pair<uint64_t, uint64_t>>& fetch_chunks(const svt_bam& bam, int32_t tid, int64_t beg, int64_t end)
 {
-    if (tid < 0 || tid >= (int32_t)bam.ref_names.size()) return false;
-    beg = std::max<int64_t>(beg, 0);
-    if (end <= beg) return true;
+    // (reused from fetch to fetch: two fetches per unit, three allocations each)
+    static thread_local std::vector<uint32_t> bins;
+    static thread_local std::vector<std::pair<uint64_t, uint64_t>> chunks, merged;
     const auto& ri = bam.index[tid];
     uint64_t min_off = 0;
     const size_t li = (size_t)(beg >> 14);
     if (!ri.linear.empty()) min_off = li < ri.linear.size() ? ri.linear[li] : ri.linear.back();
-    // (scratch of the calling thread, reused from fetch to fetch: two fetches per unit, three allocations each)
-    static thread_local std::vector<uint32_t> bins;
-    static thread_local std::vector<std::pair<uint64_t, uint64_t>> chunks, merged;
     reg2bins(beg, end, bins);
     chunks.clear();
     merged.clear();
@@ -745,13 +744,26 @@ bool fetch(const svt_bam& bam, Bgzf& z, int32_t tid, int64_t beg, int64_t end, s
         for (const auto& c : it->second)
             if (c.second > min_off) chunks.push_back(c);
     }
-    if (chunks.empty()) return true;
+    if (chunks.empty()) return merged;
     std::sort(chunks.begin(), chunks.end());
     merged.push_back(chunks[0]);
     for (size_t i = 1; i < chunks.size(); ++i) {
         if (chunks[i].first <= merged.back().second) merged.back().second = std::max(merged.back().second, chunks[i].second);
         else merged.push_back(chunks[i]);
     }
+    return merged;
+}
+
+// pysam-style fetch: records with pos < end and reference end > beg, in file order; `fn` returns
+// false to stop.  Mirrors svtyper_amd/bam.py::AlignmentFile.fetch.
+template <typename Fn>
+bool fetch(const svt_bam& bam, Bgzf& z, int32_t tid, int64_t beg, int64_t end, std::vector<uint8_t>& buf, Fn&& fn)
+{
+    if (tid < 0 || tid >= (int32_t)bam.ref_names.size()) return false;
+    beg = std::max<int64_t>(beg, 0);
+    if (end <= beg) return true;
+    const auto& merged = fetch_chunks(bam, tid, beg, end);
+    if (merged.empty()) return true;
     Record r;
     for (const auto& c : merged) {
         z.seek(c.first);
@@ -1347,11 +1359,269 @@ int process_unit(const svt_bam& bam, Bgzf& z, std::vector<uint8_t>& buf, const s
     return SVT_OK;
 }
 
+// one unit as evidence records (unit.recs): process_unit with the predicates of the device stage as its emitter
+int evidence_unit(const svt_bam& bam, Bgzf& z, std::vector<uint8_t>& buf, const svt_summarise_args& A, const svt_evidence_params& G,
+                  const std::unordered_map<std::string, int32_t>& rg_lib, uint64_t u, Workspace& ws, UnitOut& unit, std::string& err)
+{
+    const svt_breakpoint& bp = A.breakpoints[u];
+    if (bp.svtype > SVT_SVTYPE_BND) { err = "bad svtype"; return SVT_ERR_INVALID; }
+    return process_unit(bam, z, buf, A, rg_lib, u, ws, unit, err, [&](const svt_fragment& f) {
+        const uint32_t lib = f.read[0].reserved;
+        if (lib >= G.n_libs) { err = "library index of a fragment outside the library table"; return false; }
+        const svt::Record4 r = svt::geometry_record(svt::read_of(f.read[0]), svt::read_of(f.read[1]), svt::piece_of(f.seq[0]),
+                                                    svt::piece_of(f.seq[1]), svt::piece_of(f.clip[0]), svt::piece_of(f.clip[1]), bp,
+                                                    G.lib_flank[lib], G.min_aligned, G.split_slop);
+        static_assert(sizeof(svt_record) == sizeof r, "svt_record is four words");
+        unit.recs.emplace_back();
+        std::memcpy(&unit.recs.back(), &r, sizeof r);
+        return true;
+    });
+}
+
 }  // namespace
 
 // ------------------------------------------------------------------------------------------
 // C ABI
 // ------------------------------------------------------------------------------------------
+// ------------------------------------------------------------------------------------------
+// the arena of svt_evidence_walk.h and the host recomputation of single units (svt_evidence_arena.h)
+// ------------------------------------------------------------------------------------------
+namespace svt {
+namespace ew {
+
+namespace {
+
+unsigned arena_threads(const svt_summarise_args* args, uint64_t n)
+{
+    unsigned nt = args->n_threads > 0 ? (unsigned)args->n_threads : std::max(1u, svt::burst_threads((double)n * 350e-6, 48u) - 1u);
+    return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(nt ? nt : 1, n ? n : 1));
+}
+
+struct RawRange { uint64_t coff; uint32_t uoff; uint64_t len; };   // first record at (block, offset in it), `len` inflated bytes of records
+
+}  // namespace
+
+int build_arena(const svt_bam* bam, const svt_summarise_args* args, const svt_evidence_params* geometry, Arena& out)
+{
+    if (!bam || !args || !geometry) return fail(SVT_ERR_INVALID, "null argument");
+    if (geometry->n_libs == 0 || geometry->n_libs > 65536 || !geometry->lib_flank)
+        return fail(SVT_ERR_INVALID, "n_libs must be 1..65536 with a flank per library");
+    const uint64_t n = args->n_units;
+    if (n && (!args->windows || !args->breakpoints)) return fail(SVT_ERR_INVALID, "null unit arrays");
+    if (n >= 0xFFFFFFF0ull) return fail(SVT_ERR_INVALID, "too many units in one call (< 2^32)");
+    const auto t_begin = std::chrono::steady_clock::now();
+    out = Arena();
+    auto add_name = [&](std::vector<NameRef>& tab, const char* p, size_t len, int32_t value) {
+        tab.push_back(NameRef{(uint32_t)out.blob.size(), (uint32_t)len, value});
+        out.blob.insert(out.blob.end(), p, p + len);
+    };
+    for (uint32_t i = 0; i < args->n_read_groups; ++i) add_name(out.rgs, args->read_groups[i], std::strlen(args->read_groups[i]), args->read_group_lib[i]);
+    for (size_t i = 0; i < bam->ref_names.size(); ++i) add_name(out.refs, bam->ref_names[i].data(), bam->ref_names[i].size(), (int32_t)i);
+    out.blob.resize(out.blob.size() + 8, 0);
+
+    // ---- every unit's windows: the chunks a fetch walks, and in each the records up to the one that ends the fetch
+    struct UnitRaw { uint32_t first = 0; uint16_t n[2] = {0, 0}; uint32_t preset = EW_OK; };
+    std::vector<UnitRaw> raw_units(n);
+    const unsigned nt = arena_threads(args, n);
+    std::vector<std::vector<RawRange>> raw_ranges(nt);
+    std::vector<std::vector<std::pair<uint64_t, BlockRef>>> touched(nt);
+    std::vector<std::pair<uint64_t, unsigned>> unit_home(n);          // (offset of the unit's ranges in its worker's list, worker)
+    std::vector<uint64_t> n_records(nt, 0);
+    const std::unique_ptr<SharedBlocks> shared_blocks(new SharedBlocks());
+    std::atomic<uint64_t> next(0);
+    std::atomic<int> first_rc(SVT_OK);
+    auto worker = [&](unsigned t) {
+        Bgzf z(bam->file, shared_blocks.get());
+        if (!z.ok()) { first_rc.store(SVT_ERR_NOMEM); return; }
+        z.touched = &touched[t];
+        std::vector<uint8_t> buf;
+        for (;;) {
+            const uint64_t u0 = next.fetch_add(16);                   // neighbouring units share blocks: they stay on one worker
+            if (u0 >= n) return;
+            for (uint64_t u = u0; u < std::min(n, u0 + 16); ++u) {
+                UnitRaw& U = raw_units[u];
+                unit_home[u] = std::make_pair((uint64_t)raw_ranges[t].size(), t);
+                const svt_fetch_unit& w = args->windows[u];
+                const int32_t tids[2] = {w.tid_a, w.tid_b};
+                const int64_t los[2] = {w.lo_a, w.lo_b}, his[2] = {w.hi_a, w.hi_b};
+                if (args->breakpoints[u].svtype > SVT_SVTYPE_BND) U.preset = EW_RANGE;       // (the host reader's "bad svtype")
+                for (int s = 0; s < 2 && U.preset == EW_OK; ++s) {
+                    if (tids[s] < 0 || tids[s] >= (int32_t)bam->ref_names.size()) { U.preset = EW_RANGE; break; }   // ("BAM read error")
+                    const int64_t beg = std::max<int64_t>(los[s], 0), end = his[s];
+                    if (end <= beg) continue;
+                    bool window_done = false;
+                    for (const auto& c : fetch_chunks(*bam, tids[s], beg, end)) {
+                        if (window_done || U.preset != EW_OK) break;
+                        z.seek(c.first);
+                        RawRange r{0, 0, 0};
+                        bool open = false;
+                        while (z.tell() < c.second) {
+                            const uint64_t at = z.tell();
+                            uint32_t size = 0;
+                            const uint8_t* d = next_record(z, buf, size);
+                            if (!d) {                                  // end of the data, or a record that is not whole
+                                if (z.failed() || z.tell() != at) U.preset = EW_RANGE;
+                                break;
+                            }
+                            if ((int32_t)le32(d) != tids[s] || (int64_t)(int32_t)le32(d + 4) >= end) { window_done = true; break; }
+                            if (!open) { r.coff = at >> 16; r.uoff = (uint32_t)(at & 0xFFFF); open = true; }
+                            r.len += 4 + (uint64_t)size;
+                            ++n_records[t];
+                        }
+                        if (z.failed()) U.preset = EW_RANGE;
+                        if (open && U.n[s] == 0xFFFF) U.preset = EW_RANGE;
+                        if (open && U.preset == EW_OK) { raw_ranges[t].push_back(r); ++U.n[s]; }
+                    }
+                }
+                if (U.preset != EW_OK) {                               // no walk for this unit
+                    raw_ranges[t].resize(unit_home[u].first);
+                    U.n[0] = U.n[1] = 0;
+                }
+            }
+        }
+    };
+    run_threads(nt, worker);
+    if (first_rc.load() != SVT_OK) return fail(first_rc.load(), "cannot set up the inflate state");
+
+    // ---- the blocks the ranges need, side by side: runs of the file's block chain, every block once
+    std::unordered_map<uint64_t, BlockRef> blocks;
+    for (auto& log : touched) {
+        for (auto& e : log) blocks.emplace(e.first, e.second);
+        log.clear();
+    }
+    struct Need { uint64_t first, last; };
+    std::vector<Need> needs;
+    auto chain_end = [&](const RawRange& r, uint64_t* last) {          // the block that holds the range's last byte
+        uint64_t coff = r.coff, have = 0;
+        const uint64_t want = (uint64_t)r.uoff + r.len;
+        for (;;) {
+            auto it = blocks.find(coff);
+            if (it == blocks.end() || !it->second) return false;
+            if (coff == r.coff && r.uoff > it->second->data.size()) return false;
+            have += it->second->data.size();
+            if (have >= want) { *last = coff; return true; }
+            if (it->second->next <= coff) return false;
+            coff = it->second->next;
+        }
+    };
+    for (uint64_t u = 0; u < n; ++u) {
+        UnitRaw& U = raw_units[u];
+        const auto& list = raw_ranges[unit_home[u].second];
+        const uint64_t nr = (uint64_t)U.n[0] + U.n[1];
+        const size_t mark = needs.size();
+        for (uint64_t k = 0; k < nr && U.preset == EW_OK; ++k) {
+            uint64_t last = 0;
+            if (!chain_end(list[unit_home[u].first + k], &last)) U.preset = EW_RANGE;
+            else needs.push_back(Need{list[unit_home[u].first + k].coff, last});
+        }
+        if (U.preset != EW_OK) needs.resize(mark);
+    }
+    std::sort(needs.begin(), needs.end(), [](const Need& a, const Need& b) { return a.first < b.first; });
+    std::unordered_map<uint64_t, uint64_t> base;                      // block -> its offset in the arena
+    struct Copy { const BlockData* b; uint64_t at; };
+    std::vector<Copy> copies;
+    uint64_t total = 0;
+    for (size_t i = 0; i < needs.size();) {
+        uint64_t last = needs[i].last;
+        size_t j = i + 1;
+        while (j < needs.size() && needs[j].first <= last) { last = std::max(last, needs[j].last); ++j; }
+        for (uint64_t coff = needs[i].first;;) {
+            const BlockRef& b = blocks[coff];
+            base[coff] = total;
+            copies.push_back(Copy{b.get(), total});
+            total += b->data.size();
+            if (coff == last) break;
+            coff = b->next;
+        }
+        i = j;
+    }
+    // Offsets into the arena are 32 bits: the units whose ranges lie beyond 4 GiB of inflated blocks are left to the host reader
+    // (EW_RANGE; svt_evidence_device_stats.units_host_by_reason shows them).  The blocks stay alive in `blocks` until the arena
+    // is put together, so a call holds twice its inflated bytes for a moment: the drivers hand the reader blocks of sites
+    // (pipeline.CHUNK_UNITS), a few hundred MiB at 30x, far below either limit.
+    constexpr uint64_t kArenaLimit = 0xFFFF0000ull;
+    out.bytes.resize(std::min<uint64_t>(total, kArenaLimit) + 8);
+    {
+        std::atomic<size_t> at(0);
+        run_threads(std::min<unsigned>(nt, 16u), [&](unsigned) {
+            for (;;) {
+                const size_t k = at.fetch_add(8);
+                if (k >= copies.size()) return;
+                for (size_t c = k; c < std::min(copies.size(), k + 8); ++c)
+                    if (copies[c].at + copies[c].b->data.size() <= kArenaLimit && !copies[c].b->data.empty())
+                        std::memcpy(out.bytes.data() + copies[c].at, copies[c].b->data.data(), copies[c].b->data.size());
+            }
+        });
+    }
+    out.units.resize(n);
+    for (uint64_t u = 0; u < n; ++u) {
+        UnitRaw& U = raw_units[u];
+        const auto& list = raw_ranges[unit_home[u].second];
+        const uint64_t nr = (uint64_t)U.n[0] + U.n[1];
+        const size_t mark = out.ranges.size();
+        for (uint64_t k = 0; k < nr && U.preset == EW_OK; ++k) {
+            const RawRange& r = list[unit_home[u].first + k];
+            const uint64_t begin = base[r.coff] + r.uoff, end = begin + r.len;
+            if (end > kArenaLimit || end > total) U.preset = EW_RANGE;
+            else out.ranges.push_back(Range{(uint32_t)begin, (uint32_t)end});
+        }
+        if (U.preset != EW_OK) { out.ranges.resize(mark); U.n[0] = U.n[1] = 0; }
+        out.units[u] = UnitRanges{(uint32_t)mark, {U.n[0], U.n[1]}, U.preset};
+    }
+    out.ranges.push_back(Range{0, 0});                                // (never an empty array)
+    for (uint64_t c : n_records) out.records_in_ranges += c;
+    out.build_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_begin).count();
+    return SVT_OK;
+}
+
+int host_units(const svt_bam* bam, const svt_summarise_args* args, const svt_evidence_params* geometry, const std::vector<uint64_t>& ids,
+               std::vector<svt_record>& records, std::vector<uint64_t>& counts, std::vector<uint8_t>& skipped)
+{
+    const size_t m = ids.size();
+    records.clear();
+    counts.assign(m, 0);
+    skipped.assign(m, 0);
+    if (m == 0) return SVT_OK;
+    std::unordered_map<std::string, int32_t> rg_lib;
+    for (uint32_t i = 0; i < args->n_read_groups; ++i) rg_lib[args->read_groups[i]] = args->read_group_lib[i];
+    std::vector<std::vector<svt_record>> per(m);
+    const unsigned nt = arena_threads(args, m);
+    const std::unique_ptr<SharedBlocks> shared_blocks(new SharedBlocks());
+    std::atomic<size_t> next(0);
+    std::mutex err_lock;
+    size_t err_at = m;                                                // the first unit (in the units' order) that failed
+    int err_rc = SVT_OK;
+    std::string err_text;
+    run_threads(nt, [&](unsigned) {
+        Bgzf z(bam->file, shared_blocks.get());
+        std::vector<uint8_t> buf;
+        UnitOut unit;
+        Workspace ws;
+        for (;;) {
+            const size_t k = next.fetch_add(1);
+            if (k >= m) return;
+            std::string err;
+            const int rc = z.ok() ? evidence_unit(*bam, z, buf, *args, *geometry, rg_lib, ids[k], ws, unit, err) : SVT_ERR_NOMEM;
+            if (rc != SVT_OK) {
+                std::lock_guard<std::mutex> g(err_lock);
+                if (k < err_at) { err_at = k; err_rc = rc; err_text = z.ok() ? err : "cannot set up the inflate state"; }
+                continue;
+            }
+            per[k] = unit.recs;
+            skipped[k] = unit.skipped ? 1 : 0;
+        }
+    });
+    if (err_rc != SVT_OK) return fail(err_rc, err_text);
+    for (size_t k = 0; k < m; ++k) {
+        counts[k] = per[k].size();
+        records.insert(records.end(), per[k].begin(), per[k].end());
+    }
+    return SVT_OK;
+}
+
+}  // namespace ew
+}  // namespace svt
+
 // svt_trim()'s share of this file: the pooled huge-page buffers of the gather (up to SVT_READER_POOL_MB, 1 GiB by default)
 extern "C" void svt_reads_trim() { BufferPool::get().trim(); }      // (internal: not in include/svtyper_reads.h)
 
@@ -1575,19 +1845,7 @@ static int summarise_units(const svt_bam* bam, const svt_summarise_args* args, c
                 std::string err;
                 int rc;
                 if (geometry) {      // the predicates of the device stage, here: 16 bytes per fragment leave the reader
-                    const svt_breakpoint& bp = args->breakpoints[u];
-                    if (bp.svtype > SVT_SVTYPE_BND) { rc = SVT_ERR_INVALID; err = "bad svtype"; }
-                    else rc = process_unit(*bam, z, buf, *args, rg_lib, u, ws, unit, err, [&](const svt_fragment& f) {
-                        const uint32_t lib = f.read[0].reserved;
-                        if (lib >= geometry->n_libs) { err = "library index of a fragment outside the library table"; return false; }
-                        const svt::Record4 r = svt::geometry_record(svt::read_of(f.read[0]), svt::read_of(f.read[1]), svt::piece_of(f.seq[0]),
-                                                                    svt::piece_of(f.seq[1]), svt::piece_of(f.clip[0]), svt::piece_of(f.clip[1]), bp,
-                                                                    geometry->lib_flank[lib], geometry->min_aligned, geometry->split_slop);
-                        static_assert(sizeof(svt_record) == sizeof r, "svt_record is four words");
-                        unit.recs.emplace_back();
-                        std::memcpy(&unit.recs.back(), &r, sizeof r);
-                        return true;
-                    });
+                    rc = evidence_unit(*bam, z, buf, *args, *geometry, rg_lib, u, ws, unit, err);
                 } else {
                     rc = process_unit(*bam, z, buf, *args, rg_lib, u, ws, unit, err, [&](const svt_fragment& f) { unit.frags.push_back(f); return true; });
                 }
@@ -1713,6 +1971,73 @@ void svt_evidence_free(svt_evidence* e)
     void* elements = e->records;
     free_gathered(e->rec_offset, elements, e->skipped);
     e->records = nullptr;
+}
+
+static int svt_bam_evidence_walk_host_impl(const svt_bam* bam, const svt_summarise_args* args, const svt_evidence_params* geometry,
+                                           svt_evidence* out, uint8_t* out_of_envelope, uint32_t* kept_reads)
+{
+    if (!out || !out_of_envelope) return fail(SVT_ERR_INVALID, "null argument");
+    out->rec_offset = nullptr;
+    out->records = nullptr;
+    out->skipped = nullptr;
+    svt::ew::Arena arena;
+    if (const int rc = svt::ew::build_arena(bam, args, geometry, arena)) return rc;
+    const uint64_t n = args->n_units;
+    const svt::ew::Params P = arena.params(args, geometry);
+    std::vector<std::vector<svt::Record4>> per(n);
+    std::vector<uint32_t> status(n, 0);
+    std::atomic<uint64_t> next(0);
+    const unsigned nt = svt::ew::arena_threads(args, n);
+    run_threads(nt, [&](unsigned) {
+        std::unique_ptr<svt::ew::UnitScratch> S(new svt::ew::UnitScratch());
+        std::vector<svt::Record4> rows(svt::ew::kMaxReads);
+        for (;;) {
+            const uint64_t u = next.fetch_add(1);
+            if (u >= n) return;
+            svt::ew::walk_unit<svt::ew::HostCtx>(P, u, *S, rows.data());
+            status[u] = S->status;
+            if (kept_reads) kept_reads[u] = S->n_reads;
+            if (S->status == svt::ew::EW_OK) per[u].assign(rows.begin(), rows.begin() + S->n_rows);
+        }
+    });
+    uint64_t total = 0;
+    for (const auto& v : per) total += v.size();
+    out->rec_offset = static_cast<uint64_t*>(std::malloc((n + 1) * sizeof(uint64_t)));
+    out->records = static_cast<svt_record*>(std::malloc(std::max<uint64_t>(total, 1) * sizeof(svt_record)));
+    out->skipped = static_cast<uint8_t*>(std::malloc(std::max<uint64_t>(n, 1)));
+    if (!out->rec_offset || !out->records || !out->skipped) {
+        svt_evidence_free(out);
+        return fail(SVT_ERR_NOMEM, "out of host memory");
+    }
+    uint64_t off = 0;
+    for (uint64_t u = 0; u < n; ++u) {
+        out->rec_offset[u] = off;
+        if (!per[u].empty()) std::memcpy(out->records + off, per[u].data(), per[u].size() * sizeof(svt_record));
+        off += per[u].size();
+        out->skipped[u] = status[u] == svt::ew::EW_SKIPPED ? 1 : 0;
+        out_of_envelope[u] = status[u] >= svt::ew::EW_RANGE ? (uint8_t)status[u] : 0;
+    }
+    out->rec_offset[n] = off;
+    return SVT_OK;
+}
+
+int svt_bam_evidence_walk_host(const svt_bam* bam, const svt_summarise_args* args, const svt_evidence_params* geometry, svt_evidence* out,
+                               uint8_t* out_of_envelope, uint32_t* kept_reads)
+{
+    return guarded([&] { return svt_bam_evidence_walk_host_impl(bam, args, geometry, out, out_of_envelope, kept_reads); });
+}
+
+uint32_t svt_evidence_walk_capacity(int which)
+{
+    switch (which) {
+    case 0: return svt::ew::kMaxReads;
+    case 1: return svt::ew::kMaxName;
+    case 2: return svt::ew::kMaxCigar;
+    case 3: return svt::ew::kMaxSaEntries;
+    case 4: return svt::ew::kMaxSaBytes;
+    case 5: return svt::ew::kMaxRecord;
+    default: return 0;
+    }
 }
 
 static int svt_bam_scan_library_impl(const svt_bam* bam, uint32_t n_read_groups, const char* const* read_groups, int64_t num_samp,

@@ -45,6 +45,7 @@
 #include <vector>
 
 #include "../../include/svtyper_hip.h"
+#include "../../include/svtyper_reads.h"
 
 #ifndef SVT_WINDOW_TILES
 #define SVT_WINDOW_TILES 2   // library-window mode: tiles per wave of large launches (1 = always one)
@@ -64,6 +65,8 @@
 #include "svt_split_kernel.h"
 #include "svt_window_scan_kernel.h"
 #include "svt_geometry_kernel.h"
+#include "svt_evidence_kernel.h"
+#include "svt_evidence_arena.h"
 #include "svt_bayes_kernel.h"
 #include "svt_host_tables.h"
 #include "svt_host_transfer.h"
@@ -169,6 +172,7 @@ void* svt_batch_stream(svt_batch* b) { return b ? (void*)b->stream : nullptr; }
 void svt_batch_destroy(svt_batch* b) { free_batch(b); }
 
 #include "svt_entry_debug.h"
+#include "svt_entry_evidence.h"
 #include "svt_entry_oneshot.h"
 
 }  // extern "C"

@@ -16,7 +16,7 @@ from .evidence import GT_BLANK, CEvidenceBatch, CPackedEvidence, EvidenceBatch, 
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SVTYPER_HIP_LIB") or os.path.join(_HERE, "csrc", "libsvtyper_hip.so")
-ABI_VERSION = 18
+ABI_VERSION = 19
 
 EXPORTS = (
     "svt_version", "svt_device_count", "svt_last_error", "svt_batch_create", "svt_batch_create_segments", "svt_batch_create_from_fragments",
@@ -297,6 +297,17 @@ class DeviceBatch:
         self.device = int(device)
         cb = batch.as_c()
         _check(L.svt_batch_create(C.byref(cb), int(device), int(flags), C.byref(self._h)))
+
+    @classmethod
+    def adopt(cls, handle, n_units: int, n_records: int, device: int = 0):
+        """a resident batch some other entry of the library created (svt_bam_evidence_device): this object owns `handle` now"""
+        self = cls.__new__(cls)
+        self._lib = load()
+        self._h = handle if isinstance(handle, C.c_void_p) else C.c_void_p(handle)
+        self.n_units = int(n_units)
+        self.n_records = int(n_records)
+        self.device = int(device)
+        return self
 
     @classmethod
     def from_segments(cls, sbatch, device: int = 0, flags: int = 0):

@@ -47,6 +47,30 @@ class _LibraryScan(C.Structure):
                 ("hist_keys", C.POINTER(C.c_int64)), ("hist_counts", C.POINTER(C.c_uint64))]
 
 
+WALK_REASONS = {2: "range", 3: "reads", 4: "name", 5: "cigar", 6: "sa_cap", 7: "no_rg", 8: "unknown_rg", 9: "malformed", 10: "mapq"}
+WALK_CAPACITIES = ("reads", "name", "cigar", "sa_entries", "sa_bytes", "record")
+
+
+class _DeviceStats(C.Structure):
+    """include/svtyper_reads.h: svt_evidence_device_stats"""
+    _fields_ = [("n_units", C.c_uint64), ("reads_walked", C.c_uint64), ("units_skipped", C.c_uint64), ("units_host", C.c_uint64),
+                ("units_host_by_reason", C.c_uint64 * 11), ("n_records", C.c_uint64), ("bytes_uploaded", C.c_uint64),
+                ("host_arena_s", C.c_double), ("upload_s", C.c_double), ("device_walk_s", C.c_double),
+                ("host_fallback_s", C.c_double), ("batch_create_s", C.c_double)]
+
+    def as_dict(self) -> dict:
+        d = {k: getattr(self, k) for k, _ in self._fields_ if k != "units_host_by_reason"}
+        d["units_host_by_reason"] = {WALK_REASONS[r]: int(self.units_host_by_reason[r]) for r in WALK_REASONS
+                                     if self.units_host_by_reason[r]}
+        return d
+
+
+def walk_capacities() -> Dict[str, int]:
+    """the fixed capacities of the evidence walk (svt_evidence_walk.h)"""
+    L = _lib()
+    return {name: int(L.svt_evidence_walk_capacity(k)) for k, name in enumerate(WALK_CAPACITIES)}
+
+
 _declared = False
 
 
@@ -76,6 +100,16 @@ def _lib():
         L.svt_bam_evidence.argtypes = [C.c_void_p, C.POINTER(_Args), C.POINTER(_EvidenceParams), C.POINTER(_Evidence)]
         L.svt_evidence_free.restype = None
         L.svt_evidence_free.argtypes = [C.POINTER(_Evidence)]
+        L.svt_bam_evidence_walk_host.restype = C.c_int
+        L.svt_bam_evidence_walk_host.argtypes = [C.c_void_p, C.POINTER(_Args), C.POINTER(_EvidenceParams), C.POINTER(_Evidence),
+                                                 C.c_void_p, C.c_void_p]
+        L.svt_evidence_walk_capacity.restype = C.c_uint32
+        L.svt_evidence_walk_capacity.argtypes = [C.c_int]
+        L.svt_bam_evidence_device.restype = C.c_int
+        L.svt_bam_evidence_device.argtypes = [C.c_void_p, C.POINTER(_Args), C.POINTER(_EvidenceParams), C.c_void_p, C.c_int, C.c_uint,
+                                              C.POINTER(C.c_void_p), C.c_void_p, C.POINTER(_DeviceStats)]
+        L.svt_debug_batch_records.restype = C.c_int
+        L.svt_debug_batch_records.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.svt_bam_scan_library.restype = C.c_int
         L.svt_bam_scan_library.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_char_p), C.c_int64, C.POINTER(_LibraryScan)]
         L.svt_library_scan_free.restype = None
@@ -166,6 +200,63 @@ class NativeBam:
             recs = np.zeros(0, RECORD_DTYPE)
         return off, recs, skipped
 
+    def _walk_args(self, windows, breakpoints, read_groups, read_group_lib, max_reads, count_mode, lib_flank, min_aligned,
+                   split_slop, n_threads):
+        windows = np.ascontiguousarray(windows, dtype=FETCH_DTYPE)
+        breakpoints = np.ascontiguousarray(breakpoints, dtype=BREAKPOINT_DTYPE)
+        n = int(windows.shape[0])
+        if breakpoints.shape[0] != n:
+            raise ValueError("windows and breakpoints must have the same length")
+        names = (C.c_char_p * max(1, len(read_groups)))(*[rg.encode() for rg in read_groups])
+        libs = (C.c_int32 * max(1, len(read_groups)))(*[int(x) for x in read_group_lib])
+        flank = (C.c_double * max(1, len(lib_flank)))(*[float(x) for x in lib_flank])
+        a = _Args(n, windows.ctypes.data, breakpoints.ctypes.data, len(read_groups), names, libs,
+                  -1 if max_reads is None else int(max_reads), int(count_mode), int(n_threads))
+        g = _EvidenceParams(len(lib_flank), flank, int(min_aligned), int(split_slop))
+        return n, a, g, (windows, breakpoints, names, libs, flank)
+
+    def evidence_walk_host(self, windows: np.ndarray, breakpoints: np.ndarray, read_groups: Sequence[str],
+                           read_group_lib: Sequence[int], max_reads: Optional[int], count_mode: int, lib_flank: Sequence[float],
+                           min_aligned: int, split_slop: int, n_threads: int = 0):
+        """svt_bam_evidence_walk_host: evidence() computed by the one-source walk (svt_evidence_walk.h) over host memory, without
+        a fallback: (rec_offset, records, skipped, out_of_envelope uint8 [n] -- 0 or a WALK_REASONS key, such a unit has no
+        records --, kept_reads uint32 [n])."""
+        from .evidence import RECORD_DTYPE
+        n, a, g, _keep = self._walk_args(windows, breakpoints, read_groups, read_group_lib, max_reads, count_mode, lib_flank,
+                                         min_aligned, split_slop, n_threads)
+        out = _Evidence()
+        flagged = np.zeros(max(n, 1), np.uint8)
+        kept = np.zeros(max(n, 1), np.uint32)
+        hip._check(self._L.svt_bam_evidence_walk_host(self._h, C.byref(a), C.byref(g), C.byref(out), flagged.ctypes.data, kept.ctypes.data))
+        try:
+            off = np.ctypeslib.as_array(out.rec_offset, shape=(n + 1,)).copy()
+            total = int(off[-1])
+            skipped = np.ctypeslib.as_array(out.skipped, shape=(max(n, 1),))[:n].copy()
+            recs = np.zeros(total, RECORD_DTYPE)
+            if total:
+                C.memmove(recs.ctypes.data, out.records, total * RECORD_DTYPE.itemsize)
+        finally:
+            self._L.svt_evidence_free(C.byref(out))
+        return off, recs, skipped, flagged[:n], kept[:n]
+
+    def evidence_device(self, windows: np.ndarray, breakpoints: np.ndarray, read_groups: Sequence[str],
+                        read_group_lib: Sequence[int], max_reads: Optional[int], count_mode: int, lib_flank: Sequence[float],
+                        min_aligned: int, split_slop: int, header, device: int = 0, flags: int = 0, n_threads: int = 0):
+        """svt_bam_evidence_device: the reader stage with the walk on the GPU.  `header`: an EvidenceBatch whose units,
+        libraries and weights describe the batch (its rec_offset / records are ignored).  Returns (hip.DeviceBatch resident
+        in HBM -- what DeviceBatch(EvidenceBatch(*evidence(...))) builds --, skipped uint8 [n], stats dict)."""
+        n, a, g, _keep = self._walk_args(windows, breakpoints, read_groups, read_group_lib, max_reads, count_mode, lib_flank,
+                                         min_aligned, split_slop, n_threads)
+        if header.n_units != n:
+            raise ValueError("header and windows must have the same number of units")
+        cb = header.as_c()
+        handle = C.c_void_p()
+        skipped = np.zeros(max(n, 1), np.uint8)
+        st = _DeviceStats()
+        hip._check(self._L.svt_bam_evidence_device(self._h, C.byref(a), C.byref(g), C.byref(cb), int(device), int(flags),
+                                                   C.byref(handle), skipped.ctypes.data, C.byref(st)))
+        return hip.DeviceBatch.adopt(handle, n, int(st.n_records), device), skipped[:n], st.as_dict()
+
     def summarise(self, windows: np.ndarray, breakpoints: np.ndarray, read_groups: Sequence[str],
                   read_group_lib: Sequence[int], max_reads: Optional[int], count_mode: int,
                   n_threads: int = 0) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
@@ -214,3 +305,14 @@ class _SummariesOwner:
             self._lib.svt_summaries_free(C.byref(self._s))
         except Exception:
             pass
+
+
+def batch_records(dbatch) -> Tuple[np.ndarray, np.ndarray]:
+    """svt_debug_batch_records: (rec_offset, records) of a resident batch of canonical records, read back from HBM"""
+    from .evidence import RECORD_DTYPE
+    L = _lib()
+    off = np.zeros(dbatch.n_units + 1, np.uint64)
+    hip._check(L.svt_debug_batch_records(dbatch._h, off.ctypes.data, None))
+    recs = np.zeros(int(off[-1]), RECORD_DTYPE)
+    hip._check(L.svt_debug_batch_records(dbatch._h, off.ctypes.data, recs.ctypes.data if recs.size else None))
+    return off, recs

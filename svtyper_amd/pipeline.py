@@ -252,9 +252,12 @@ class NativeUnitCollector:
         """`geometry`: where the breakpoint-dependent predicates (parsers.py:785-857,1122-1215) are evaluated --
         "reader" (default): in the C++ reader's threads, which hands over 16-byte evidence records (svt_bam_evidence) for
         the canonical route of ANY engine; "device": 128-byte fragment summaries go to the device's geometry stage
-        (svt_bam_summarise -> svt_batch_create_from_fragments, the HIP engine only).  Same records either way."""
-        if geometry not in ("reader", "device"):
-            raise ValueError("geometry must be 'reader' or 'device'")
+        (svt_bam_summarise -> svt_batch_create_from_fragments, the HIP engine only); "walk" (the drivers' reader="device"):
+        the reader inflates, the evidence records are built on the GPU from the inflated bytes (svt_bam_evidence_device, the
+        HIP engine only; units outside the walk's envelope are the host reader's).  Same records either way."""
+        if geometry not in ("reader", "device", "walk"):
+            raise ValueError("geometry must be 'reader', 'device' or 'walk'")
+        self.device_stats: dict = {}     # geometry="walk": the counters of svt_bam_evidence_device, summed over the calls
         self.geometry = geometry
         self.samples = samples
         self.bams = native_bams
@@ -377,6 +380,8 @@ class NativeUnitCollector:
             sys.stderr.write("[NativeUnitCollector] %-22s %8.1f ms (at take(), on the caller's thread)\n" % ("site arrays (python)", prep_s * 1e3))
         if self.geometry == "reader":
             return self._run_records(prepared, engine, flags, kw, lap)
+        if self.geometry == "walk":
+            return self._run_walk(prepared, engine, flags, kw, lap)
         for k, (nbam, (bps, win)) in enumerate(zip(self.bams, prepared)):
             rgs, idx = self.rg_tables[k]
             with _READER_TURN:      # (two chunks in flight under ChunkPipeline: one reads, the other is on the device)
@@ -402,6 +407,45 @@ class NativeUnitCollector:
             res.site_qual = q
         return res
 
+
+    def _run_walk(self, prepared, engine: Engine, flags: int, kw: dict, lap) -> Results:
+        """geometry="walk": one resident batch per sample, its records built in HBM by svt_bam_evidence_device (no evidence
+        crosses PCIe but the units the host reader recomputes); the 128-byte result records of the samples are put side by
+        side site-major, QUAL over a site's samples is summed on the host -- as the per-sample route of geometry="device"."""
+        import numpy as np
+        from . import hip
+        if not isinstance(getattr(engine, "device", None), int) or not hasattr(engine, "genotype_fragments"):
+            raise TypeError("reader='device' needs the HIP engine")
+        n_sites = int(prepared[0][0].shape[0])
+        per_sample = []
+        for k, (nbam, (bps, win)) in enumerate(zip(self.bams, prepared)):
+            rgs, idx = self.rg_tables[k]
+            tables = self.group_tables[self.group_of[k]]
+            flank = [float(t.mean) + float(t.sd) * 3 for t in tables]
+            units = np.zeros(n_sites, ev.UNIT_DTYPE)
+            units["var_length"] = np.where(bps["svtype"] == ev.SVTYPE_CODE["DEL"], bps["var_length"], 0)
+            units["pos_delta"] = np.clip(bps["pos_b"].astype(np.int64) - bps["pos_a"].astype(np.int64), -2**31, 2**31 - 1)   # classic.py:339
+            units["sample"], units["svtype"] = k, bps["svtype"]
+            units["libs"] = self.sample_libs[k]
+            head = EvidenceBatch(np.zeros(n_sites + 1, np.uint64), units, np.zeros(0, ev.RECORD_DTYPE), tables, self.split_weight,
+                                 self.disc_weight)
+            with _READER_TURN:
+                d, _skipped, st = nbam.evidence_device(win, bps, rgs, idx, self.max_reads, self.count_mode, flank, self.min_aligned,
+                                                       SPLIT_SLOP, head, engine.device, flags, self.n_threads)
+            lap("svt_bam_evidence_device")
+            for key, v in st.items():
+                if isinstance(v, dict):
+                    mine = self.device_stats.setdefault(key, {})
+                    for r, c in v.items():
+                        mine[r] = mine.get(r, 0) + c
+                else:
+                    self.device_stats[key] = self.device_stats.get(key, 0) + v
+            with d:
+                d.genotype(sync=True)
+                per_sample.append(hip.host_sq(d.results()).rec)
+            lap("genotype pass + results")
+        res = Results(per_sample[0] if len(per_sample) == 1 else np.stack(per_sample, axis=1).reshape(-1))
+        return _with_site_qual(res, kw)
 
     def _run_records(self, prepared, engine: Engine, flags: int, kw: dict, lap) -> Results:
         """geometry="reader": evidence records straight from the reader, ONE canonical batch over the samples of a library

@@ -143,7 +143,7 @@ def sso_genotype(bam_string, vcf_in, vcf_out, min_aligned, split_weight, disc_we
         with open(lib_info_path) as f:
             lib_info = json.load(f)
     native = None
-    if reader == "native":      # C++ reader: library scans now, fetch + fragment summaries later
+    if reader in ("native", "device"):      # C++ reader: library scans now, fetch + fragment summaries later
         from .native_reads import COUNT_SSO, NativeBam
         native = NativeBam(full_bam_path)
     sample = setup_sample(bam, lib_info, num_samp, MIN_LIB_PREVALENCE, native)
@@ -157,7 +157,7 @@ def sso_genotype(bam_string, vcf_in, vcf_out, min_aligned, split_weight, disc_we
     # bulk route (reader="native"): the body as blocks of text -> breakpoint arrays -> output text in native calls
     # (bulk_vcf.py); the per-line route below stays the general one (and takes over at a BND line the parser cannot express)
     bulk = None
-    if reader == "native" and hasattr(vcf_in, "read") and os.environ.get("SVT_BULK_VCF", "1") != "0":
+    if reader in ("native", "device") and hasattr(vcf_in, "read") and os.environ.get("SVT_BULK_VCF", "1") != "0":
         from . import bulk_vcf
         if bulk_vcf.available():
             bulk = bulk_vcf
@@ -199,14 +199,14 @@ def sso_genotype(bam_string, vcf_in, vcf_out, min_aligned, split_weight, disc_we
     vcf.write_header(vcf_out)
 
     logit("Genotyping Input VCF (%s Mode)" % ("Serial" if cores is None else "Parallel"))
-    if reader == "native":      # C++ fetch + summariser (cores = its thread count); geometry in the reader's threads ("host") or on the device
+    if reader in ("native", "device"):      # C++ fetch + summariser (cores = its thread count); geometry in the reader's threads ("host") or on the device
         collector = NativeUnitCollector([sample], [native], split_weight, disc_weight, min_aligned,
                                         COUNT_SSO, max_reads, n_threads=cores or 0,
-                                        geometry="device" if geometry == "device" else "reader")
+                                        geometry="walk" if reader == "device" else "device" if geometry == "device" else "reader")
     elif reader == "python":
         collector = UnitCollector([sample], split_weight, disc_weight, min_aligned, geometry)
     else:
-        raise ValueError("reader must be 'python' or 'native'")
+        raise ValueError("reader must be 'python', 'native' or 'device'")
     pending: list = []
     pipe = ChunkPipeline()
 
@@ -269,7 +269,7 @@ def sso_genotype(bam_string, vcf_in, vcf_out, min_aligned, split_weight, disc_we
         if variant.get_svtype() == "BND":
             variant2 = variant
             variant = vcf._bnd_first.pop(bp["id"])
-        if reader == "native":
+        if reader in ("native", "device"):
             unit = collector.add_site(bp)
         else:
             fragments, many = gather_reads(sample, bp, max_reads)
@@ -317,6 +317,8 @@ def sso_genotype(bam_string, vcf_in, vcf_out, min_aligned, split_weight, disc_we
     pipe.close()
     if stats is not None:       # (keyword-only extra: where the caller's thread spent its time, pipeline.BulkFeeder.laps)
         stats.update(bulk_stats[0] if bulk_stats else {}, route=bulk_stats[1] if bulk_stats else "per line")
+        if reader == "device":      # the counters of svt_bam_evidence_device, summed over the run's calls
+            stats["device_reader"] = collector.device_stats
     sample.close()
 
 
@@ -355,9 +357,10 @@ def get_args():
     p.add_argument("--batch_size", type=int, metavar="INT", default=1000,
                    help="accepted for compatibility with the reference's worker batches")
     # not in the reference: where the host work runs (same output bytes either way)
-    p.add_argument("--reader", choices=("python", "native"), default="native",
+    p.add_argument("--reader", choices=("python", "native", "device"), default="native",
                    help="BAM access + fragment assembly: the C++ threads of libsvtyper_hip.so feeding the device "
-                        "geometry stage, or the portable Python reader (same output bytes) [native]")
+                        "geometry stage, the same with the evidence records built on the GPU (device), or the portable Python "
+                        "reader (same output bytes) [native]")
     p.add_argument("--geometry", choices=("host", "device"), default="host",
                    help="with --reader python: breakpoint-dependent read predicates on the host or on the GPU [host]")
     args = p.parse_args()

@@ -1,6 +1,8 @@
 #!/usr/bin/env python
 """Corrupted BAMs (bit flips, truncation, overwritten spans) through the native reader, one subprocess each: the
-reader must answer with an error (or a result), never crash."""
+reader must answer with an error (or a result), never crash.  `--walk` (or SVT_FUZZ_WALK=1): the same corpus also goes to
+svt_bam_evidence_walk_host, the one-source evidence walk without a fallback, against svt_bam_evidence: it must never crash,
+and wherever the host reader succeeds every unit the walk does not flag must carry the host reader's records."""
 import os, sys, subprocess, tempfile, random
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__))); sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
 child = r'''
@@ -16,11 +18,29 @@ try:
     nb = nr.NativeBam(path)
     pybam = bam.AlignmentFile(sys.argv[4])           # the intact copy, for the library / windows only
     sample = library.Sample.from_lib_info(pybam, info, 1e-3)
+    if os.environ.get("SVT_FUZZ_WALK") == "1":
+        import walkcases as W
+        for mode, limit in ((nr.COUNT_CLASSIC, None), (nr.COUNT_SSO, 150)):
+            a = W.unit_arrays(sites, sample, nb, mode)
+            got = nb.evidence_walk_host(a[0], a[1], a[2], a[3], limit, mode, a[4], 20, 3, 2)
+            try:
+                want = nb.evidence(a[0], a[1], a[2], a[3], limit, mode, a[4], 20, 3, 2)
+            except hip.SvtyperHipError:
+                assert got[3].any(), "the host reader fails and the walk flags nothing"
+                continue
+            for u in range(len(sites)):
+                if got[3][u]:
+                    assert got[0][u + 1] == got[0][u]
+                    continue
+                assert got[2][u] == want[2][u], "skip flag of unit %d" % u
+                assert got[1][int(got[0][u]):int(got[0][u + 1])].tobytes() == want[1][int(want[0][u]):int(want[0][u + 1])].tobytes(), "records of unit %d" % u
     N._native_summaries(sites, sample, nb, nr.COUNT_CLASSIC, None, 2)
     print("ok")
 except hip.SvtyperHipError as e:
     print("error:", str(e)[:80])
 '''
+if "--walk" in sys.argv[1:]:
+    os.environ["SVT_FUZZ_WALK"] = "1"
 tmp = tempfile.mkdtemp()
 import test_native_reads as N, json
 good = os.path.join(tmp, "good.bam")
