@@ -2,9 +2,10 @@
 //
 // ONE piece of source for both places that run it: the host (svt_bam_evidence_walk_host in svt_reads.cpp, any C++17 compiler:
 // this is where the walk is proven, fuzzed and sanitised) and the device (svt_evidence_kernel.h, hipcc, one workgroup per unit).
-// It restates what decode_core / decode_rest / find_z_tag / aligned_intervals / split_candidate / parse_cigar_string and
-// process_unit of svt_reads.cpp compute, as plain functions over `const uint8_t*` + length: no std::, no allocation, every
-// access checked against the length it was given, every loop bounded by a length or a capacity.
+// What a record means -- its fixed fields, CIGAR, tags, aligned intervals, the split-read candidate -- is svt_record_rules.h,
+// the same functions the host reader's process_unit calls.  The walk's own is here: its capacities and reasons, the two passes
+// over a unit's record ranges, the fragment table as a rank sort, the rows.  No std::, no allocation, every access checked
+// against the length it was given, every loop bounded by a length or a capacity.
 //
 // The envelope.  Whatever the walk does not handle EXACTLY as the host reader does sets a reason (EW_*) for the unit and stops:
 // the caller recomputes such a unit with process_unit (svt_bam_evidence_device) or returns it empty with its reason
@@ -22,9 +23,12 @@
 
 #include "../../include/svtyper_reads.h"
 #include "svt_geometry_math.h"
+#include "svt_record_rules.h"
 
 namespace svt {
 namespace ew {
+
+using namespace rr;
 
 // ---- capacities (the LDS arithmetic is beside the kernel, svt_evidence_kernel.h) ----------------------------------------
 constexpr uint32_t kMaxReads = 1024;        // kept reads of one unit (both windows, after the flag / library filters)
@@ -108,11 +112,6 @@ struct HostCtx {
 };
 
 // ---- bytes ----------------------------------------------------------------------------------------------------------------
-SVT_HD uint32_t ld32(const uint8_t* d) { return (uint32_t)d[0] | ((uint32_t)d[1] << 8) | ((uint32_t)d[2] << 16) | ((uint32_t)d[3] << 24); }
-SVT_HD int32_t clip32(int64_t x) { return (int32_t)(x < (int64_t)INT32_MIN ? (int64_t)INT32_MIN : x > (int64_t)INT32_MAX ? (int64_t)INT32_MAX : x); }
-SVT_HD int64_t min64(int64_t a, int64_t b) { return a < b ? a : b; }
-SVT_HD int64_t max64(int64_t a, int64_t b) { return a > b ? a : b; }
-SVT_HD int64_t abs64(int64_t a) { return a < 0 ? -a : a; }
 SVT_HD bool bytes_eq(const uint8_t* a, const uint8_t* b, uint32_t n)
 {
     for (uint32_t i = 0; i < n; ++i) if (a[i] != b[i]) return false;
@@ -133,48 +132,6 @@ SVT_HD int32_t find_name(const NameRef* tab, uint32_t n, const uint8_t* blob, co
     return -1;
 }
 
-// ---- CIGAR ------------------------------------------------------------------------------------------------------------------
-SVT_HD bool op_clip(uint32_t op) { return op == 4 || op == 5; }
-SVT_HD bool op_ref(uint32_t op) { return op == 0 || op == 2 || op == 3 || op == 7 || op == 8; }
-SVT_HD bool op_query(uint32_t op) { return op == 0 || op == 1 || op == 7 || op == 8; }
-SVT_HD bool op_aligned(uint32_t op) { return op == 0 || op == 7 || op == 8; }
-
-// what query_pos_from_cigar / left_clipped / the clip rules need of a CIGAR, gathered in one forward pass
-struct CigarStats {
-    uint32_t n, first_op, last_op;
-    int64_t first_len, last_len, query, clips, ref;
-};
-SVT_HD void cigar_begin(CigarStats& c) { c.n = 0; c.first_op = c.last_op = 0; c.first_len = c.last_len = c.query = c.clips = c.ref = 0; }
-SVT_HD void cigar_add(CigarStats& c, uint32_t op, int64_t len)
-{
-    if (c.n == 0) { c.first_op = op; c.first_len = len; }
-    c.last_op = op; c.last_len = len;
-    ++c.n;
-    if (op_clip(op)) c.clips += len;
-    else if (op_query(op)) c.query += len;
-    if (op_ref(op)) c.ref += len;
-}
-struct QPos { int64_t start, end, length; };
-// query_pos_from_cigar: the clip the walk meets first (the last operation of a reverse read) opens the query
-SVT_HD QPos query_pos(const CigarStats& c, bool reverse)
-{
-    QPos q;
-    int64_t lead = 0;
-    if (c.n) {
-        const uint32_t op = reverse ? c.last_op : c.first_op;
-        if (op_clip(op)) lead = reverse ? c.last_len : c.first_len;
-    }
-    q.start = lead;
-    q.end = lead + c.query;
-    q.length = c.clips + c.query;
-    return q;
-}
-SVT_HD bool left_clipped(const CigarStats& c)
-{
-    const bool lc = op_clip(c.first_op), rc = op_clip(c.last_op);
-    return (lc && !rc) || (lc && rc && c.first_len > c.last_len);
-}
-
 // a run of 1..15 decimal digits (everything strtoll would read differently is outside the envelope)
 SVT_HD bool digits(const uint8_t* p, uint32_t n, int64_t& v)
 {
@@ -187,226 +144,47 @@ SVT_HD bool digits(const uint8_t* p, uint32_t n, int64_t& v)
     return true;
 }
 
-// parse_cigar_string; EW_OK, EW_MALFORMED or EW_CIGAR
-SVT_HD uint32_t cigar_of_string(const uint8_t* s, uint32_t n, CigarStats& c)
-{
-    cigar_begin(c);
-    int64_t num = 0;
-    uint32_t nd = 0;
-    for (uint32_t i = 0; i < n; ++i) {
-        const uint8_t ch = s[i];
-        if (ch >= '0' && ch <= '9') {
-            if (++nd > 15) return EW_MALFORMED;
-            num = num * 10 + (ch - '0');
-            continue;
-        }
-        uint32_t op;
-        switch (ch) {
-        case 'M': op = 0; break; case 'I': op = 1; break; case 'D': op = 2; break; case 'N': op = 3; break; case 'S': op = 4; break;
-        case 'H': op = 5; break; case 'P': op = 6; break; case '=': op = 7; break; case 'X': op = 8; break;
-        default: return EW_MALFORMED;
-        }
-        if (nd == 0) return EW_MALFORMED;
-        if (c.n >= kMaxCigar) return EW_CIGAR;
-        cigar_add(c, op, num);
-        num = 0;
-        nd = 0;
-    }
-    return nd ? EW_MALFORMED : EW_OK;
-}
-
 // ---- one record -----------------------------------------------------------------------------------------------------------
-struct Core {
-    int32_t tid, pos, l_seq;
-    uint32_t l_name, n_cigar, flag, mapq, tags_off;
-    int64_t end;
-};
-// decode_core: false when the variable-length parts do not fit `size`
-SVT_HD bool decode_core(const uint8_t* d, uint32_t size, Core& r)
-{
-    if (size < 32) return false;
-    r.tid = (int32_t)ld32(d);
-    r.pos = (int32_t)ld32(d + 4);
-    r.l_name = d[8];
-    r.mapq = d[9];
-    r.n_cigar = (uint32_t)d[12] | ((uint32_t)d[13] << 8);
-    r.flag = (uint32_t)d[14] | ((uint32_t)d[15] << 8);
-    r.l_seq = (int32_t)ld32(d + 16);
-    uint64_t off = 32;
-    if (off + r.l_name + 4ull * r.n_cigar > size) return false;
-    off += r.l_name;
-    r.end = r.pos;
-    for (uint32_t k = 0; k < r.n_cigar; ++k) {
-        const uint32_t c = ld32(d + off + 4 * k);
-        if (op_ref(c & 0xF)) r.end += (int64_t)(c >> 4);
-    }
-    off += 4ull * r.n_cigar;
-    if (r.l_seq < 0) return false;         // (the host reader's size_t arithmetic rejects it the same way)
-    off += (uint64_t)(((int64_t)r.l_seq + 1) / 2 + (int64_t)r.l_seq);
-    if (off > size) return false;
-    r.tags_off = (uint32_t)off;
-    return true;
-}
-
-// the whole tag area, validated; the first RG:Z and the first SA:Z values (offset into the record, length without the NUL)
-struct Tags { uint32_t rg_off, rg_len, sa_off, sa_len; bool have_rg, have_sa; };
-SVT_HD bool walk_tags(const uint8_t* d, uint32_t size, uint32_t from, Tags& t)
-{
-    t.have_rg = t.have_sa = false;
-    t.rg_off = t.rg_len = t.sa_off = t.sa_len = 0;
-    uint64_t i = from;
-    const uint64_t n = size;
-    while (i + 3 <= n) {
-        const uint8_t a0 = d[i], a1 = d[i + 1], ty = d[i + 2];
-        i += 3;
-        uint64_t skip = 0;
-        switch (ty) {
-        case 'A': case 'c': case 'C': skip = 1; break;
-        case 's': case 'S': skip = 2; break;
-        case 'i': case 'I': case 'f': skip = 4; break;
-        case 'Z': case 'H': {
-            uint64_t q = i;
-            while (q < n && d[q]) ++q;
-            if (q >= n) return false;
-            if (ty == 'Z' && a0 == 'R' && a1 == 'G' && !t.have_rg) { t.have_rg = true; t.rg_off = (uint32_t)i; t.rg_len = (uint32_t)(q - i); }
-            if (ty == 'Z' && a0 == 'S' && a1 == 'A' && !t.have_sa) { t.have_sa = true; t.sa_off = (uint32_t)i; t.sa_len = (uint32_t)(q - i); }
-            skip = q - i + 1;
-            break;
-        }
-        case 'B': {
-            if (i + 5 > n) return false;
-            const uint8_t sub = d[i];
-            const uint32_t cnt = ld32(d + i + 1);
-            const uint64_t sz = (sub == 'c' || sub == 'C') ? 1 : (sub == 's' || sub == 'S') ? 2 : 4;
-            skip = 5 + (uint64_t)cnt * sz;
-            break;
-        }
-        default: return false;
-        }
-        i += skip;
-        if (i > n) return false;                            // a value that runs over the end of the record
-    }
-    return true;
-}
-
-// aligned_intervals: all gap-free aligned intervals when there are at most two, else the two nearest to the breakends in the
-// order of a stable sort by distance
-SVT_HD void aligned_intervals(const uint8_t* cig, uint32_t n_cigar, int64_t pos, int64_t near_a, int64_t near_b, ReadSum& out)
-{
-    int64_t fs[2] = {0, 0}, fe[2] = {0, 0};        // the first two, in order
-    int64_t bs[2] = {0, 0}, be[2] = {0, 0}, bd[2] = {0, 0};   // the two nearest, nearest first
-    uint32_t n = 0;
-    int64_t p = pos, cs = 0, ce = 0;
-    bool open = false;
-    auto close = [&]() {
-        auto one = [&](int64_t q) { return (cs <= q && q <= ce) ? (int64_t)0 : min64(abs64(cs - q), abs64(ce - q)); };
-        const int64_t dist = min64(one(near_a), one(near_b));
-        if (n < 2) { fs[n] = cs; fe[n] = ce; }
-        if (n == 0) { bs[0] = cs; be[0] = ce; bd[0] = dist; }
-        else if (n == 1) {
-            if (dist < bd[0]) { bs[1] = bs[0]; be[1] = be[0]; bd[1] = bd[0]; bs[0] = cs; be[0] = ce; bd[0] = dist; }
-            else { bs[1] = cs; be[1] = ce; bd[1] = dist; }
-        } else if (dist < bd[0]) { bs[1] = bs[0]; be[1] = be[0]; bd[1] = bd[0]; bs[0] = cs; be[0] = ce; bd[0] = dist; }
-        else if (dist < bd[1]) { bs[1] = cs; be[1] = ce; bd[1] = dist; }
-        ++n;
-    };
-    for (uint32_t k = 0; k < n_cigar; ++k) {
-        const uint32_t c = ld32(cig + 4 * k), op = c & 0xF;
-        const int64_t len = (int64_t)(c >> 4);
-        if (op_aligned(op)) {
-            if (!open) { cs = p; open = true; }
-            ce = p + len;
-            p += len;
-        } else if (op == 2 || op == 3) {
-            if (open) close();
-            open = false;
-            p += len;
-        }
-    }
-    if (open) close();
-    const uint32_t keep = n < 2 ? n : 2;
-    for (uint32_t k = 0; k < 2; ++k) {
-        const bool have = k < keep;
-        out.iv_s[k] = have ? clip32(n > 2 ? bs[k] : fs[k]) : 0;
-        out.iv_e[k] = have ? clip32(n > 2 ? be[k] : fe[k]) : 0;
-    }
-    out.bits = (uint8_t)((out.bits & ~RS_NIV) | keep);
-}
-
-// split_candidate for a primary read; EW_OK (candidate or not: RS_SPLIT in rs.bits) or a reason
+// the split candidate of a primary read; EW_OK (candidate or not: RS_SPLIT in rs.bits) or a reason
 SVT_HD uint32_t split_candidate(const Params& P, const uint8_t* d, const Core& r, const Tags& t, ReadSum& rs)
 {
     if (r.n_cigar == 0) return EW_OK;
-    const uint8_t* cig = d + 32 + r.l_name;
     CigarStats a;
-    cigar_begin(a);
-    for (uint32_t k = 0; k < r.n_cigar; ++k) {
-        const uint32_t c = ld32(cig + 4 * k);
-        cigar_add(a, c & 0xF, (int64_t)(c >> 4));
-    }
+    cigar_of_words(d + 32 + r.l_name, r.n_cigar, a);
     const bool a_rev = (r.flag & 0x10) != 0;
     if (!t.have_sa) {
-        const bool fc = op_clip(a.first_op), lc = op_clip(a.last_op);
-        if (!(fc || lc)) return EW_OK;
-        const int64_t clip_length = max64(fc ? a.first_len : 0, lc ? a.last_len : 0);
-        if (clip_length > 0 && ((int64_t)r.l_seq - a.query) <= 50) {
+        if (soft_clip_candidate(a, r.l_seq)) {
             rs.o_tid = -2; rs.o_start = 1; rs.o_end = 1; rs.o_mapq = 0;      // the dummy piece (chrom None)
             rs.bits |= (uint8_t)(RS_SPLIT | RS_SOFT | (a_rev ? RS_O_REV : 0) | (left_clipped(a) ? 0 : RS_SELF_LEFT));
         }
         return EW_OK;
     }
-    // SA:Z:chrom,pos,strand,CIGAR,mapQ,NM;...
     if (t.sa_len > kMaxSaBytes) return EW_SA_CAP;
     const uint8_t* sa = d + t.sa_off;
-    uint32_t len = t.sa_len;
-    while (len && sa[len - 1] == ';') --len;
-    uint32_t entries = 1;
-    for (uint32_t i = 0; i < len; ++i) if (sa[i] == ';') ++entries;
+    uint32_t fo[5], fl[5];
+    uint32_t entries;
+    const uint32_t fields = sa_fields(sa, t.sa_len, entries, fo, fl);
     if (entries > kMaxSaEntries) return EW_SA_CAP;
     if (entries > 1) return EW_OK;                                            // more than one entry: discarded
-    uint32_t fo[5] = {0, 0, 0, 0, 0}, fl[5] = {0, 0, 0, 0, 0}, n_fld = 0, p0 = 0;
-    for (uint32_t i = 0; i <= len; ++i) {
-        if (i == len || sa[i] == ',') {
-            if (n_fld < 5) { fo[n_fld] = p0; fl[n_fld] = i - p0; }
-            ++n_fld;
-            p0 = i + 1;
-        }
-    }
-    if (n_fld < 5) return EW_MALFORMED;
+    if (fields < 5) return EW_MALFORMED;
     int64_t mate_pos1 = 0, mate_mapq = 0;
     if (!digits(sa + fo[1], fl[1], mate_pos1) || !digits(sa + fo[4], fl[4], mate_mapq)) return EW_MALFORMED;
     if (mate_mapq > 255) return EW_MAPQ;
     CigarStats b;
-    const uint32_t cs = cigar_of_string(sa + fo[3], fl[3], b);
-    if (cs != EW_OK) return cs;
+    const uint32_t cs = cigar_of_string(sa + fo[3], fl[3], kMaxCigar, 15, b);
+    if (cs != CIGAR_OK) return cs == CIGAR_TOO_MANY ? EW_CIGAR : EW_MALFORMED;
     const int32_t b_at = find_name(P.refs, P.n_refs, P.blob, sa + fo[0], fl[0]);
-    const int32_t b_tid = b_at < 0 ? -3 : b_at;
-    const int64_t b_start = mate_pos1 - 1, b_end = b_start + b.ref;
-    const bool b_rev = fl[2] == 1 && sa[fo[2]] == '-';
     bool same_chrom = false;
     if (r.tid >= 0 && (uint32_t)r.tid < P.n_refs) {
         const NameRef& nr = P.refs[r.tid];
         same_chrom = nr.len == fl[0] && bytes_eq(P.blob + nr.off, sa + fo[0], fl[0]);
     }
-    const bool self_left = same_chrom ? !((int64_t)r.pos > b_start) : !left_clipped(a);
-    const QPos qa = query_pos(a, a_rev), qb = query_pos(b, b_rev);
-    const QPos &l = self_left ? qa : qb, &rq = self_left ? qb : qa;
-    const int64_t shared = max64(0, 1 + min64(l.end, rq.end) - max64(l.start, rq.start));
-    const int64_t non_overlap = min64(1 + l.end - l.start - shared, 1 + rq.end - rq.start - shared);
-    if (non_overlap < 20) return EW_OK;
-    const int32_t l_tid = self_left ? r.tid : b_tid, r_tid = self_left ? b_tid : r.tid;
-    const bool l_rev = self_left ? a_rev : b_rev, r_rev = self_left ? b_rev : a_rev;
-    if (l_tid == r_tid && l_rev == r_rev) {
-        const int64_t l_start = self_left ? (int64_t)r.pos : b_start, l_end = self_left ? r.end : b_end;
-        const int64_t r_start = self_left ? b_start : (int64_t)r.pos, r_end = self_left ? b_end : r.end;
-        const int64_t l_sd = l_start - (l_rev ? l.length - l.end : l.start), l_ed = l_end - (l_rev ? l.length - l.start : l.end);
-        const int64_t r_sd = r_start - (r_rev ? rq.length - rq.end : rq.start), r_ed = r_end - (r_rev ? rq.length - rq.start : rq.end);
-        const int64_t ins = l_rev ? r_ed - l_sd : l_ed - r_sd;
-        if (abs64(ins) < 50) return EW_OK;
-        const int64_t desert = rq.start - l.end - 1;
-        if (desert > 0 && desert - max64(0, ins) > 50) return EW_OK;
-    }
-    rs.o_tid = b_tid; rs.o_start = clip32(b_start); rs.o_end = clip32(b_end); rs.o_mapq = (uint8_t)mate_mapq;
+    const bool b_rev = fl[2] == 1 && sa[fo[2]] == '-';
+    const Piece pa = {r.tid, r.pos, r.end, a_rev, query_pos(a, a_rev)};
+    const Piece pb = {b_at < 0 ? -3 : b_at, mate_pos1 - 1, mate_pos1 - 1 + b.ref, b_rev, query_pos(b, b_rev)};
+    bool self_left;
+    if (!split_valid(pa, pb, same_chrom, left_clipped(a), self_left)) return EW_OK;
+    rs.o_tid = pb.tid; rs.o_start = clip32(pb.start); rs.o_end = clip32(pb.end); rs.o_mapq = (uint8_t)mate_mapq;
     rs.bits |= (uint8_t)(RS_SPLIT | (b_rev ? RS_O_REV : 0) | (self_left ? RS_SELF_LEFT : 0));
     return EW_OK;
 }
@@ -420,7 +198,7 @@ SVT_HD void eval_record(const Params& P, const uint8_t* d, uint32_t size, uint32
     e.ovl = e.counted = e.keep = false;
     e.early = e.late = EW_OK;
     Core r;
-    if (!decode_core(d, size, r) || r.tid != wtid || (int64_t)r.pos >= hi) { e.ovl = true; e.early = EW_RANGE; return; }   // (the builder ends a range in front of such a record)
+    if (!decode_core(d, size, r) || r.l_seq < 0 || r.tid != wtid || (int64_t)r.pos >= hi) { e.ovl = true; e.early = EW_RANGE; return; }   // (the builder ends a range in front of such a record)
     int64_t rend = r.end;
     if (r.n_cigar == 0 || rend <= r.pos) rend = (int64_t)r.pos + 1;
     if (!(rend > lo)) return;
@@ -428,7 +206,9 @@ SVT_HD void eval_record(const Params& P, const uint8_t* d, uint32_t size, uint32
     e.counted = !(r.flag & (0x4 | 0x100 | 0x200 | 0x400));
     if (r.flag & (0x4 | 0x400)) return;
     Tags t;
-    const bool tags_ok = walk_tags(d, size, r.tags_off, t);
+    tags_begin(t);
+    uint32_t tags_at = r.tags_off;
+    const bool tags_ok = walk_tags(d, size, tags_at, false, t) == TAGS_END;     // (a value that runs over the record's end counts as malformed here)
     if (!t.have_rg) { e.early = EW_NO_RG; return; }
     const int32_t at = find_name(P.rgs, P.n_rgs, P.blob, d + t.rg_off, t.rg_len);
     if (at < 0) { e.early = EW_UNKNOWN_RG; return; }
@@ -453,7 +233,11 @@ SVT_HD void eval_record(const Params& P, const uint8_t* d, uint32_t size, uint32
     rs.o_mapq = 0;
     rs.bits = (uint8_t)((r.flag & 0x10) ? RS_REV : 0);
     if (r.flag & (0x100 | 0x800)) return;                  // secondary / supplementary: only its (name, flag) counts
-    aligned_intervals(d + 32 + r.l_name, r.n_cigar, r.pos, near_a, near_b, rs);
+    Intervals iv;
+    aligned_intervals(d + 32 + r.l_name, r.n_cigar, r.pos, near_a, near_b, iv);
+    rs.iv_s[0] = clip32(iv.s[0]); rs.iv_e[0] = clip32(iv.e[0]);
+    rs.iv_s[1] = clip32(iv.s[1]); rs.iv_e[1] = clip32(iv.e[1]);
+    rs.bits |= (uint8_t)iv.n;
     e.late = split_candidate(P, d, r, t, rs);
 }
 

@@ -37,12 +37,14 @@
 #include "svt_evidence_arena.h"
 #include "svt_geometry_math.h"
 #include "svt_host_cpus.h"
+#include "svt_record_rules.h"
 
 namespace {
 
 using svt::fail;
 using svt::guarded;
 using svt::run_threads;
+namespace rr = svt::rr;
 
 std::atomic<double> g_cpu_s_per_unit{0.0};   // CPU seconds per unit of the last svt_bam_summarise / svt_bam_evidence call on any file
 
@@ -437,69 +439,8 @@ private:
 };
 
 // ------------------------------------------------------------------------------------------
-// CIGAR helpers (svtyper_amd/fragments.py, svtyper/parsers.py:922-947,1062-1101,1242-1253)
+// reads, pieces, fragments (what a record means is svt_record_rules.h)
 // ------------------------------------------------------------------------------------------
-typedef std::vector<std::pair<int, int64_t>> Cigar;   // (op, len)
-inline bool is_clip(int op) { return op == 4 || op == 5; }
-inline bool consumes_ref(int op) { return op == 0 || op == 2 || op == 3 || op == 7 || op == 8; }
-inline bool consumes_query(int op) { return op == 0 || op == 1 || op == 7 || op == 8; }
-inline bool is_aligned(int op) { return op == 0 || op == 7 || op == 8; }
-
-struct QueryPos { int64_t start = 0, end = 0, length = 0; };
-
-QueryPos query_pos_from_cigar(const Cigar& cigar, bool reverse)
-{
-    QueryPos q;
-    const size_t n = cigar.size();
-    for (size_t i = 0; i < n; ++i) {
-        const auto& c = reverse ? cigar[n - 1 - i] : cigar[i];
-        if (is_clip(c.first)) {
-            if (i == 0) { q.start += c.second; q.end += c.second; }
-            q.length += c.second;
-        } else if (consumes_query(c.first)) {
-            q.end += c.second;
-            q.length += c.second;
-        }
-    }
-    return q;
-}
-
-bool left_clipped(const Cigar& c)
-{
-    const bool lc = is_clip(c.front().first), rc = is_clip(c.back().first);
-    return (lc && !rc) || (lc && rc && c.front().second > c.back().second);
-}
-
-bool parse_cigar_string(const char* s, size_t n, Cigar& out)
-{
-    static const char* ops = "MIDNSHP=X";
-    int64_t num = 0;
-    bool have = false;
-    for (size_t i = 0; i < n; ++i) {
-        const char ch = s[i];
-        if (ch == 0) return false;      // (strchr would find the terminator of `ops`)
-        if (ch >= '0' && ch <= '9') { num = num * 10 + (ch - '0'); have = true; continue; }
-        const char* p = std::strchr(ops, ch);
-        if (!p || !have) return false;
-        out.emplace_back((int)(p - ops), num);
-        num = 0;
-        have = false;
-    }
-    return !have;
-}
-
-// ------------------------------------------------------------------------------------------
-// reads, pieces, fragments
-// ------------------------------------------------------------------------------------------
-struct Piece {
-    int32_t tid = 0;          // -2: dummy piece (chrom None); -3: chromosome not in the header
-    int64_t start = 0, end = 0;
-    bool reverse = false;
-    int64_t mapq = 0;
-    const Cigar* cigar = nullptr;   // not owned: the record's own operations, or split_candidate's scratch for an SA entry --
-    QueryPos qp;                    // a piece is copied around (left / right) and lives only until its PieceOut is taken
-};
-
 struct ReadInfo {                // what a primary read contributes to a summary (svt_read_summary)
     int32_t tid = -1;
     int64_t start = 0, end = 0;
@@ -518,11 +459,6 @@ struct PieceOut {                // what a split piece contributes to a summary 
 struct SplitOut {
     bool soft = false;
     PieceOut left, right;
-};
-
-struct Split {
-    bool soft = false;
-    Piece left, right;
 };
 
 struct Fragment {                // reused from unit to unit (its vectors keep their capacity)
@@ -544,70 +480,33 @@ struct Fragment {                // reused from unit to unit (its vectors keep t
     }
 };
 
-struct Record {               // one BAM alignment, decoded as far as the path needs
-    int32_t tid = -1;
-    int64_t pos = 0, end = 0;
-    uint16_t flag = 0;
-    int mapq = 0;
-    int64_t l_seq = 0;
-    int64_t tlen = 0;         // template_length
-    const char* name = "";    // query name: points into the record's bytes (the inflated block, or the caller's gather buffer for a
-    uint32_t name_len = 0;    // record that straddles blocks): valid until the next record is read
-    Cigar cigar;
-    const uint8_t* tags = nullptr;
-    size_t tags_len = 0;
-    std::string name_str() const { return std::string(name, name_len); }
+// One BAM alignment: the fixed fields (rr::Core) and the record's bytes -- inside the inflated block, or the caller's gather
+// buffer for a record that straddles blocks: valid until the next record is read.
+struct Record : rr::Core {
+    const uint8_t* data = nullptr;
+    uint32_t size = 0;
+    const char* name() const { return reinterpret_cast<const char*>(data + 32); }
+    uint32_t name_len() const { return l_name ? l_name - 1 : 0; }
+    const uint8_t* cigar() const { return data + 32 + l_name; }     // n_cigar words
+    int64_t tlen() const { return (int32_t)rr::ld32(data + 28); }   // template_length
+    std::string name_str() const { return std::string(name(), name_len()); }
 };
 
-// Z-typed tag value or nullptr; walks the tag area like svtyper_amd/bam.py::_parse_tags.
-// A kept read is asked for RG and then for SA: the second search need not walk the tags in front of RG again.  `from`: where
-// the walk starts; `resume` (optional): set to the offset behind the found tag; `other` (optional, with o0 o1): the first Z
-// value of that other tag met ON THE WAY to the found one.  First-match semantics are those of two full walks (search RG from
-// 0 noting SA, then -- when SA was not met -- search SA from `resume`); the tags VALIDATED are every tag of the read either
-// way: the caller walks what lies behind the second tag it found as well (`validate_only`), so a malformed tag anywhere
-// fails the call with SVT_ERR_INVALID -- as svtyper_amd/bam.py::_parse_tags, which parses the whole tag area of every read it
-// keeps, raises (tests/test_native_reads.py::test_truncated_tag_behind_rg_is_malformed_in_both_tag_orders).
-const char* find_z_tag(const Record& r, char k0, char k1, bool* malformed, size_t from = 0, size_t* resume = nullptr,
-                       char o0 = 0, char o1 = 0, const char** other = nullptr, bool validate_only = false)
+// The first leg of a kept read's tag walk (svtyper_amd/bam.py::_parse_tags): up to its RG value, noting an SA value met on the
+// way.  nullptr: no usable RG tag.  A read that becomes a split candidate walks on from `at` (tags_behind_rg); every other
+// kept read stops here.  A value that runs over the record's end ends the walk without a complaint (rr::TAGS_OVERRUN).
+const char* read_group(const Record& r, rr::Tags& t, uint32_t& at)
 {
-    const uint8_t* b = r.tags;
-    size_t i = from, n = r.tags_len;
-    while (i + 3 <= n) {
-        const char a0 = (char)b[i], a1 = (char)b[i + 1], t = (char)b[i + 2];
-        i += 3;
-        size_t skip = 0;
-        switch (t) {
-        case 'A': case 'c': case 'C': skip = 1; break;
-        case 's': case 'S': skip = 2; break;
-        case 'i': case 'I': case 'f': skip = 4; break;
-        case 'Z': case 'H': {
-            // (the values are short -- RG ids, MD strings of a few characters: a library call per tag costs more than the scan)
-            const uint8_t* q = b + i;
-            const uint8_t* const near_end = b + std::min(n, i + 24);
-            while (q < near_end && *q) ++q;
-            const void* z = (q < near_end) ? q : (q < b + n ? std::memchr(q, 0, (size_t)(b + n - q)) : nullptr);
-            if (!z) { *malformed = true; return nullptr; }
-            skip = (size_t)(static_cast<const uint8_t*>(z) - (b + i)) + 1;
-            if (!validate_only && a0 == k0 && a1 == k1 && t == 'Z') {
-                if (resume) *resume = i + skip;
-                return reinterpret_cast<const char*>(b + i);
-            }
-            if (other && !*other && a0 == o0 && a1 == o1 && t == 'Z') *other = reinterpret_cast<const char*>(b + i);
-            break;
-        }
-        case 'B': {
-            if (i + 5 > n) { *malformed = true; return nullptr; }
-            const char sub = (char)b[i];
-            const uint32_t cnt = b[i + 1] | (b[i + 2] << 8) | (b[i + 3] << 16) | ((uint32_t)b[i + 4] << 24);
-            const size_t sz = (sub == 'c' || sub == 'C') ? 1 : (sub == 's' || sub == 'S') ? 2 : 4;
-            skip = 5 + (size_t)cnt * sz;
-            break;
-        }
-        default: *malformed = true; return nullptr;
-        }
-        i += skip;
-    }
-    return nullptr;
+    rr::tags_begin(t);
+    at = r.tags_off;
+    if (rr::walk_tags(r.data, r.size, at, /*stop_at_rg=*/true, t) != rr::TAGS_AT_RG) return nullptr;
+    return reinterpret_cast<const char*>(r.data + t.rg_off);
+}
+// The second leg: every tag behind RG is validated (a malformed tag anywhere fails the call, as bam.py raises:
+// tests/test_native_reads.py::test_truncated_tag_behind_rg_is_malformed_in_both_tag_orders) and the first SA value noted.
+bool tags_behind_rg(const Record& r, rr::Tags& t, uint32_t at)
+{
+    return rr::walk_tags(r.data, r.size, at, false, t) != rr::TAGS_MALFORMED;
 }
 
 }  // namespace
@@ -646,7 +545,7 @@ void reg2bins(int64_t beg, int64_t end, std::vector<uint32_t>& bins)
         for (int64_t k = offs[l] + (beg >> shifts[l]); k <= (int64_t)offs[l] + (end >> shifts[l]); ++k) bins.push_back((uint32_t)k);
 }
 
-inline uint32_t le32(const uint8_t* d) { return (uint32_t)d[0] | (d[1] << 8) | (d[2] << 16) | ((uint32_t)d[3] << 24); }
+using rr::ld32;
 
 // The bytes of the next alignment (after its length word): in place inside the inflated block when the
 // record does not straddle a block boundary -- no copy, which is what makes walking up to a window cheap
@@ -655,7 +554,7 @@ const uint8_t* next_record(Bgzf& z, std::vector<uint8_t>& buf, uint32_t& size)
 {
     constexpr uint32_t kMaxRecord = 1u << 28;   // no alignment record is a quarter of a gigabyte: a corrupt length
     if (const uint8_t* h = z.contiguous(4)) {
-        size = le32(h);
+        size = ld32(h);
         if (size < 32 || size > kMaxRecord) { z.mark_bad(); return nullptr; }
         if (const uint8_t* d = z.contiguous(4 + (size_t)size)) {
             z.advance(4 + (size_t)size);
@@ -664,65 +563,26 @@ const uint8_t* next_record(Bgzf& z, std::vector<uint8_t>& buf, uint32_t& size)
     }
     uint8_t szb[4];
     if (z.read(szb, 4) != 4) return nullptr;
-    size = le32(szb);
+    size = ld32(szb);
     if (size < 32 || size > kMaxRecord) { z.mark_bad(); return nullptr; }
     buf.resize(size);
     if (z.read(buf.data(), size) != size) return nullptr;
     return buf.data();
 }
 
-struct RecordLayout { unsigned l_name = 0, n_cigar = 0; size_t tags_off = 0; };
-
 // fixed fields + reference end: all a fetch needs to decide whether the record overlaps its window
-bool decode_core(const uint8_t* d, uint32_t size, Record& r, RecordLayout& lay)
+bool decode(const uint8_t* d, uint32_t size, Record& r)
 {
-    r.tid = (int32_t)le32(d);
-    r.pos = (int32_t)le32(d + 4);
-    lay.l_name = d[8];
-    r.mapq = d[9];
-    lay.n_cigar = d[12] | (d[13] << 8);
-    r.flag = (uint16_t)(d[14] | (d[15] << 8));
-    r.l_seq = (int32_t)le32(d + 16);
-    r.tlen = (int32_t)le32(d + 28);
-    size_t off = 32;
-    if (off + lay.l_name + 4ull * lay.n_cigar > size) return false;
-    off += lay.l_name;
-    r.end = r.pos;
-    for (unsigned k = 0; k < lay.n_cigar; ++k) {
-        const uint32_t c = le32(d + off + 4 * k);
-        if (consumes_ref((int)(c & 0xF))) r.end += (int64_t)(c >> 4);
-    }
-    off += 4ull * lay.n_cigar;
-    off += (size_t)((r.l_seq + 1) / 2 + r.l_seq);
-    if (off > size) return false;
-    lay.tags_off = off;
-    return true;
-}
-
-// the variable-length parts a kept record is asked for: query name, CIGAR operations, tag area
-void decode_rest(const uint8_t* d, uint32_t size, const RecordLayout& lay, Record& r)
-{
-    r.name = reinterpret_cast<const char*>(d + 32);
-    r.name_len = lay.l_name ? lay.l_name - 1 : 0;
-
-    r.cigar.clear();
-    const uint8_t* c0 = d + 32 + lay.l_name;
-    for (unsigned k = 0; k < lay.n_cigar; ++k) {
-        const uint32_t c = le32(c0 + 4 * k);
-        r.cigar.emplace_back((int)(c & 0xF), (int64_t)(c >> 4));
-    }
-    r.tags = d + lay.tags_off;
-    r.tags_len = size - lay.tags_off;
+    r.data = d;
+    r.size = size;
+    return d && rr::decode_core(d, size, r);
 }
 
 bool read_record(Bgzf& z, std::vector<uint8_t>& buf, Record& r)
 {
     uint32_t size = 0;
     const uint8_t* d = next_record(z, buf, size);
-    RecordLayout lay;
-    if (!d || !decode_core(d, size, r, lay)) return false;
-    decode_rest(d, size, lay, r);
-    return true;
+    return decode(d, size, r);
 }
 
 // the merged BAI chunks a fetch of [beg, end) on `tid` walks, in file order (scratch of the calling thread)
@@ -770,174 +630,68 @@ bool fetch(const svt_bam& bam, Bgzf& z, int32_t tid, int64_t beg, int64_t end, s
         while (z.tell() < c.second) {
             uint32_t size = 0;
             const uint8_t* d = next_record(z, buf, size);
-            RecordLayout lay;
-            if (!d || !decode_core(d, size, r, lay)) break;
+            if (!decode(d, size, r)) break;
             if (r.tid != tid || r.pos >= end) return true;
             int64_t rend = r.end;
-            if (lay.n_cigar == 0 || rend <= r.pos) rend = r.pos + 1;
-            if (rend > beg) {      // most records walked on the way to the window stop here, undecoded
-                decode_rest(d, size, lay, r);
-                if (!fn(r)) return true;
-            }
+            if (r.n_cigar == 0 || rend <= r.pos) rend = (int64_t)r.pos + 1;
+            if (rend > beg && !fn(r)) return true;      // (most records walked on the way to the window stop here)
         }
     }
     return !z.failed();
 }
 
 // SplitRead.is_valid (parsers.py:959-1058 / fragments.py) -> fills `out` when the candidate is valid
-// returns 1 valid, 0 invalid, -1 malformed input
-// `sa_seen` / `tags_from`: what the caller's search for RG already knows -- an SA value it walked past, else where the tags it
-// has not looked at begin (0: the whole tag area)
-int split_candidate(const svt_bam& bam, const Record& r, Split& out, const char* sa_seen = nullptr, size_t tags_from = 0)
+// returns 1 valid, 0 invalid, -1 malformed input.  The rules are rr::; the host reader's own: an SA number is what strtoll
+// reads over the whole field, a chromosome name goes through the header's map, and there is no limit on lengths.
+int split_candidate(const svt_bam& bam, const Record& r, const rr::Tags& t, SplitOut& out)
 {
-    bool malformed = false;
-    const char* sa = sa_seen;
-    if (sa_seen) (void)find_z_tag(r, 0, 0, &malformed, tags_from, nullptr, 0, 0, nullptr, /*validate_only=*/true);   // (the full walk looked at every tag)
-    else {
-        size_t behind_sa = 0;
-        sa = find_z_tag(r, 'S', 'A', &malformed, tags_from, &behind_sa);
-        if (sa && !malformed) (void)find_z_tag(r, 0, 0, &malformed, behind_sa, nullptr, 0, 0, nullptr, /*validate_only=*/true);   // (the tags behind SA, too)
-    }
-    if (malformed) return -1;
-    if (r.cigar.empty()) return 0;   // a mapped read without a CIGAR cannot be a split candidate (fragments.py: add_read)
-    if (!sa) {   // the common read: no SA tag and no clipped end -> not a candidate, nothing to build
-        if (!is_clip(r.cigar.front().first) && !is_clip(r.cigar.back().first)) return 0;
-    }
-    Piece a;
-    a.tid = r.tid;
-    a.start = r.pos;
-    a.end = r.end;
-    a.reverse = (r.flag & 0x10) != 0;
-    a.mapq = r.mapq;
-    a.cigar = &r.cigar;
-    a.qp = query_pos_from_cigar(*a.cigar, a.reverse);
-    if (!sa) {
-        const bool fc = is_clip(r.cigar.front().first), lc = is_clip(r.cigar.back().first);
-        if (!(fc || lc)) return 0;
-        const int64_t clip_length = std::max(r.cigar.front().second * (fc ? 1 : 0), r.cigar.back().second * (lc ? 1 : 0));
-        int64_t q_aln = 0;
-        for (const auto& c : r.cigar) if (consumes_query(c.first)) q_aln += c.second;
-        if (clip_length > 0 && (r.l_seq - q_aln) <= 50) {
-            Piece dummy;
-            dummy.tid = -2;
-            dummy.start = 1;
-            dummy.end = 1;
-            dummy.reverse = a.reverse;
-            dummy.mapq = 0;
-            dummy.cigar = &r.cigar;
-            dummy.qp = query_pos_from_cigar(*dummy.cigar, dummy.reverse);
-            out.soft = true;
-            if (left_clipped(*a.cigar)) { out.left = dummy; out.right = a; }
-            else { out.left = a; out.right = dummy; }
-            return 1;
-        }
-        return 0;
-    }
-    // SA:Z:chrom,pos,strand,CIGAR,mapQ,NM;...   more than one entry -> discarded (:992-993).  Fields are cut in place (no
-    // string per field: a read with an SA tag used to cost a dozen allocations here)
-    size_t len = std::strlen(sa);
-    while (len && sa[len - 1] == ';') --len;
-    if (std::memchr(sa, ';', len)) return 0;
-    const char* fb[8];
-    size_t fl[8];
-    size_t n_fld = 0;
-    for (size_t p0 = 0;;) {
-        const char* c = static_cast<const char*>(std::memchr(sa + p0, ',', len - p0));
-        const size_t p1 = c ? (size_t)(c - sa) : len;
-        if (n_fld < 8) { fb[n_fld] = sa + p0; fl[n_fld] = p1 - p0; }
-        ++n_fld;
-        if (!c) break;
-        p0 = p1 + 1;
-    }
-    if (n_fld < 5) return -1;
-    auto whole_number = [](const char* b, size_t n, long long& v) {      // strtoll over the whole field, as before
-        char buf[32];
-        if (n == 0 || n >= sizeof buf) return false;
-        std::memcpy(buf, b, n);
-        buf[n] = 0;
-        char* endp = nullptr;
-        v = std::strtoll(buf, &endp, 10);
-        return *endp == 0;
-    };
-    long long mate_pos1 = 0, mate_mapq = 0;
-    if (!whole_number(fb[1], fl[1], mate_pos1)) return -1;
-    if (!whole_number(fb[4], fl[4], mate_mapq)) return -1;
-    Piece b;
-    const std::string sa_chrom(fb[0], fl[0]);          // (chromosome names fit the small-string buffer)
-    auto it = bam.tid_of.find(sa_chrom);
-    b.tid = it == bam.tid_of.end() ? -3 : it->second;
-    b.start = mate_pos1 - 1;
-    b.reverse = fl[2] == 1 && fb[2][0] == '-';
-    static thread_local Cigar sa_cigar;                // the SA entry's operations: scratch of this thread, alive while `out` is read
-    sa_cigar.clear();
-    if (!parse_cigar_string(fb[3], fl[3], sa_cigar)) return -1;
-    b.cigar = &sa_cigar;
-    b.mapq = mate_mapq;
-    b.end = b.start;
-    for (const auto& c : sa_cigar) if (consumes_ref(c.first)) b.end += c.second;
-    b.qp = query_pos_from_cigar(sa_cigar, b.reverse);
-    const bool same_chrom = r.tid >= 0 && bam.ref_names[r.tid] == sa_chrom;
-    out.soft = false;
-    if (same_chrom) {
-        if (r.pos > b.start) { out.left = b; out.right = a; }
-        else { out.left = a; out.right = b; }
-    } else if (a.cigar->empty()) {
-        return -1;
-    } else if (left_clipped(*a.cigar)) {
-        out.left = b; out.right = a;
+    if (r.n_cigar == 0) return 0;   // a mapped read without a CIGAR cannot be a split candidate (fragments.py: add_read)
+    rr::CigarStats a;
+    rr::cigar_of_words(r.cigar(), r.n_cigar, a);
+    const bool a_rev = (r.flag & 0x10) != 0;
+    const PieceOut self{r.tid, r.pos, r.end, (int64_t)r.mapq, a_rev};
+    bool self_left;
+    PieceOut other;
+    if (!t.have_sa) {
+        if (!rr::soft_clip_candidate(a, r.l_seq)) return 0;
+        other = PieceOut{-2, 1, 1, 0, a_rev};           // the dummy piece (chrom None)
+        self_left = !rr::left_clipped(a);
     } else {
-        out.left = a; out.right = b;
+        const uint8_t* sa = r.data + t.sa_off;
+        uint32_t fo[5], fl[5];
+        uint32_t entries;
+        const uint32_t fields = rr::sa_fields(sa, t.sa_len, entries, fo, fl);
+        if (entries > 1) return 0;                      // more than one entry -> discarded (:992-993)
+        if (fields < 5) return -1;
+        auto whole_number = [&](int k, long long& v) {  // strtoll over the whole field
+            char buf[32];
+            if (fl[k] == 0 || fl[k] >= sizeof buf) return false;
+            std::memcpy(buf, sa + fo[k], fl[k]);
+            buf[fl[k]] = 0;
+            char* endp = nullptr;
+            v = std::strtoll(buf, &endp, 10);
+            return *endp == 0;
+        };
+        long long mate_pos1 = 0, mate_mapq = 0;
+        rr::CigarStats b;
+        if (!whole_number(1, mate_pos1) || !whole_number(4, mate_mapq)) return -1;
+        if (rr::cigar_of_string(sa + fo[3], fl[3], UINT32_MAX, 18, b) != rr::CIGAR_OK) return -1;
+        const std::string sa_chrom(reinterpret_cast<const char*>(sa) + fo[0], fl[0]);    // (chromosome names fit the small-string buffer)
+        auto it = bam.tid_of.find(sa_chrom);
+        const bool b_rev = fl[2] == 1 && sa[fo[2]] == '-';
+        other = PieceOut{it == bam.tid_of.end() ? -3 : it->second, mate_pos1 - 1, mate_pos1 - 1 + b.ref, mate_mapq, b_rev};
+        const rr::Piece pa = {self.tid, self.start, self.end, a_rev, rr::query_pos(a, a_rev)};
+        const rr::Piece pb = {other.tid, other.start, other.end, b_rev, rr::query_pos(b, b_rev)};
+        const bool same_chrom = r.tid >= 0 && bam.ref_names[r.tid] == sa_chrom;
+        if (!rr::split_valid(pa, pb, same_chrom, rr::left_clipped(a), self_left)) return 0;
     }
-    const QueryPos &l = out.left.qp, &rq = out.right.qp;
-    const int64_t shared = std::max<int64_t>(0, 1 + std::min(l.end, rq.end) - std::max(l.start, rq.start));
-    const int64_t non_overlap = std::min(1 + l.end - l.start - shared, 1 + rq.end - rq.start - shared);
-    if (non_overlap < 20) return 0;
-    if (out.left.tid == out.right.tid && out.left.reverse == out.right.reverse) {
-        auto start_diag = [](const Piece& p) { return p.start - (p.reverse ? p.qp.length - p.qp.end : p.qp.start); };
-        auto end_diag = [](const Piece& p) { return p.end - (p.reverse ? p.qp.length - p.qp.start : p.qp.end); };
-        const int64_t ins = out.left.reverse ? end_diag(out.right) - start_diag(out.left)
-                                             : end_diag(out.left) - start_diag(out.right);
-        if (std::llabs(ins) < 50) return 0;
-        const int64_t desert = rq.start - l.end - 1;
-        if (desert > 0 && desert - std::max<int64_t>(0, ins) > 50) return 0;
-    }
+    out.soft = !t.have_sa;
+    out.left = self_left ? self : other;
+    out.right = self_left ? other : self;
     return 1;
 }
 
-// Maximal gap-free aligned reference intervals of a read (geometry.aligned_intervals), reduced to what a
-// summary keeps: all of them when there are at most two, else the two closest to the unit's breakends in
-// the order of a stable sort by distance (geometry._read_words).
-void aligned_intervals(const Record& r, int64_t near_a, int64_t near_b, std::vector<std::pair<int64_t, int64_t>>& scratch, ReadInfo& out)
-{
-    scratch.clear();
-    int64_t p = r.pos;
-    bool open = false;
-    for (const auto& c : r.cigar) {
-        if (is_aligned(c.first)) {
-            if (!open) { scratch.emplace_back(p, p + c.second); open = true; }
-            else scratch.back().second = p + c.second;
-            p += c.second;
-        } else if (c.first == 2 || c.first == 3) {
-            open = false;
-            p += c.second;
-        }
-    }
-    if (scratch.size() > 2) {
-        auto dist = [&](const std::pair<int64_t, int64_t>& iv) {
-            auto one = [&](int64_t q) { return (iv.first <= q && q <= iv.second) ? (int64_t)0 : std::min(std::llabs(iv.first - q), std::llabs(iv.second - q)); };
-            return std::min(one(near_a), one(near_b));
-        };
-        std::stable_sort(scratch.begin(), scratch.end(), [&](const auto& x, const auto& y) { return dist(x) < dist(y); });
-        scratch.resize(2);
-    }
-    out.n_iv = (int)scratch.size();
-    for (int k = 0; k < out.n_iv; ++k) {
-        out.iv_start[k] = scratch[(size_t)k].first;
-        out.iv_end[k] = scratch[(size_t)k].second;
-    }
-}
-
-inline int32_t clip32(int64_t x) { return (int32_t)std::max<int64_t>(INT32_MIN, std::min<int64_t>(INT32_MAX, x)); }
+using rr::clip32;
 
 void fill_read(svt_read_summary& d, const ReadInfo& r)
 {
@@ -950,17 +704,6 @@ void fill_read(svt_read_summary& d, const ReadInfo& r)
     }
     d.mapq = (uint8_t)r.mapq;
     d.flags = (uint8_t)(SVT_READ_PRESENT | (r.reverse ? SVT_READ_REVERSE : 0));
-}
-
-inline PieceOut piece_out(const Piece& p)
-{
-    PieceOut o;
-    o.tid = p.tid;
-    o.start = p.start;
-    o.end = p.end;
-    o.mapq = p.mapq;
-    o.reverse = p.reverse;
-    return o;
 }
 
 bool fill_piece(svt_piece_summary& d, const PieceOut& p)
@@ -991,7 +734,6 @@ struct Workspace {
     std::vector<uint32_t> order;
     std::vector<std::pair<uint64_t, uint32_t>> keys;
     std::vector<uint64_t> packed;
-    std::vector<std::pair<int64_t, int64_t>> intervals;
     std::vector<const SplitOut*> seq, clip;
     std::string last_rg;               // most reads of a unit share their read group
     int32_t last_lib = 0;
@@ -1293,12 +1035,10 @@ int process_unit(const svt_bam& bam, Bgzf& z, std::vector<uint8_t>& buf, const s
                 return false;
             }
             if (r.flag & (0x4 | 0x400)) return true;                   // unmapped / duplicate
-            bool malformed = false;
-            size_t behind_rg = 0;
-            const char* sa_seen = nullptr;
-            const char* rg = find_z_tag(r, 'R', 'G', &malformed, 0, &behind_rg, 'S', 'A', &sa_seen);
-
-            if (malformed || !rg) { err = "read without a usable RG tag: " + r.name_str(); rc = SVT_ERR_INVALID; return false; }
+            rr::Tags tags;
+            uint32_t behind_rg = 0;
+            const char* rg = read_group(r, tags, behind_rg);
+            if (!rg) { err = "read without a usable RG tag: " + r.name_str(); rc = SVT_ERR_INVALID; return false; }
             if (!ws.have_last_rg || ws.last_rg != rg) {
                 auto it = rg_lib.find(rg);
                 if (it == rg_lib.end()) { err = std::string("read group not in the library table: ") + rg; rc = SVT_ERR_INVALID; return false; }
@@ -1308,7 +1048,7 @@ int process_unit(const svt_bam& bam, Bgzf& z, std::vector<uint8_t>& buf, const s
             }
             if (ws.last_lib < 0) return true;                           // library below the prevalence cut
             if (A.count_mode == 0 && A.max_reads >= 0 && i > A.max_reads) { out.skipped = true; return false; }
-            Fragment& f = ws.fragment(r.name, r.name_len, ws.last_lib);             // SamFragment(read, lib) when new
+            Fragment& f = ws.fragment(r.name(), r.name_len(), ws.last_lib);             // SamFragment(read, lib) when new
             if (std::find(f.seen.begin(), f.seen.end(), r.flag) != f.seen.end()) return true;   // same (name, flag) again
             f.seen.push_back(r.flag);
             if (r.flag & (0x100 | 0x800)) return true;                  // secondary / supplementary
@@ -1317,14 +1057,17 @@ int process_unit(const svt_bam& bam, Bgzf& z, std::vector<uint8_t>& buf, const s
             ri.start = r.pos;
             ri.end = r.end;
             ri.reverse = (r.flag & 0x10) != 0;
-            ri.mapq = r.mapq;
-            aligned_intervals(r, near_a, near_b, ws.intervals, ri);
+            ri.mapq = (int)r.mapq;
+            rr::Intervals iv;
+            rr::aligned_intervals(r.cigar(), r.n_cigar, r.pos, near_a, near_b, iv);
+            ri.n_iv = (int)iv.n;
+            for (int k = 0; k < 2; ++k) { ri.iv_start[k] = iv.s[k]; ri.iv_end[k] = iv.e[k]; }
             f.primaries.push_back(ri);
             f.num_primary += 1;
-            Split sp;
-            const int v = split_candidate(bam, r, sp, sa_seen, behind_rg);
+            SplitOut sp;
+            const int v = tags_behind_rg(r, tags, behind_rg) ? split_candidate(bam, r, tags, sp) : -1;
             if (v < 0) { err = "malformed SA tag / CIGAR at read " + r.name_str(); rc = SVT_ERR_INVALID; return false; }
-            if (v > 0) f.splits.push_back(SplitOut{sp.soft, piece_out(sp.left), piece_out(sp.right)});
+            if (v > 0) f.splits.push_back(sp);
             return true;
         });
         if (rc != SVT_OK) return rc;
@@ -1463,7 +1206,7 @@ int build_arena(const svt_bam* bam, const svt_summarise_args* args, const svt_ev
                                 if (z.failed() || z.tell() != at) U.preset = EW_RANGE;
                                 break;
                             }
-                            if ((int32_t)le32(d) != tids[s] || (int64_t)(int32_t)le32(d + 4) >= end) { window_done = true; break; }
+                            if ((int32_t)ld32(d) != tids[s] || (int64_t)(int32_t)ld32(d + 4) >= end) { window_done = true; break; }
                             if (!open) { r.coff = at >> 16; r.uoff = (uint32_t)(at & 0xFFFF); open = true; }
                             r.len += 4 + (uint64_t)size;
                             ++n_records[t];
@@ -2053,15 +1796,19 @@ static int svt_bam_scan_library_impl(const svt_bam* bam, uint32_t n_read_groups,
     Record r;
     // 1 in the set, 0 not in the set, -1 no usable RG tag (an error where the reference calls get_tag)
     auto in_library = [&](const Record& rec) -> int {
-        bool malformed = false;
-        const char* rg = find_z_tag(rec, 'R', 'G', &malformed);
-        if (malformed || !rg) return -1;
+        rr::Tags tags;
+        uint32_t behind_rg = 0;
+        const char* rg = read_group(rec, tags, behind_rg);
+        if (!rg) return -1;
         return rgset.count(rg) ? 1 : 0;
     };
     auto no_rg = [&](const Record& rec) { return fail(SVT_ERR_INVALID, "read without a usable RG tag: " + rec.name_str()); };
     auto query_length = [](const Record& rec) {
         int64_t n = 0;
-        for (const auto& c : rec.cigar) if (c.first == 0 || c.first == 1 || c.first == 4 || c.first == 7 || c.first == 8) n += c.second;
+        for (uint32_t k = 0; k < rec.n_cigar; ++k) {
+            const uint32_t c = ld32(rec.cigar() + 4 * k);
+            if (rr::op_query(c & 0xF) || (c & 0xF) == 4) n += (int64_t)(c >> 4);
+        }
         return n;
     };
 
@@ -2085,14 +1832,14 @@ static int svt_bam_scan_library_impl(const svt_bam* bam, uint32_t n_read_groups,
     z.seek(bam->first_record);
     for (int64_t n = 0; read_record(z, buf, r) && r.tid >= 0;) {
         if ((r.flag & 0x10) || !(r.flag & 0x20) || (r.flag & (0x4 | 0x8)) || (r.flag & (0x100 | 0x800))) continue;
-        if (r.tlen <= 0) continue;
+        if (r.tlen() <= 0) continue;
         const int in = in_library(r);
         if (in < 0) return no_rg(r);
         if (!in) continue;
-        auto slot = hist_slot.find(r.tlen);
+        auto slot = hist_slot.find(r.tlen());
         if (slot == hist_slot.end()) {
-            hist_slot.emplace(r.tlen, hist_keys.size());
-            hist_keys.push_back(r.tlen);
+            hist_slot.emplace(r.tlen(), hist_keys.size());
+            hist_keys.push_back(r.tlen());
             hist_counts.push_back(1);
         } else {
             ++hist_counts[slot->second];

@@ -43,7 +43,7 @@ def encode_record(r):
     end = r["pos"] + max(1, ref_len(cigar))
     name = r["name"].encode() + b"\0"
     body = struct.pack("<iiBBHHHiiii", r["tid"], r["pos"], len(name), r["mapq"], reg2bin(r["pos"], end), len(cigar),
-                       r["flag"], l_seq, r["mtid"], r["mpos"], r["tlen"])
+                       r["flag"], r.get("l_seq_field", l_seq), r["mtid"], r["mpos"], r["tlen"])   # (l_seq_field: a header that lies)
     body += name
     body += b"".join(struct.pack("<I", (n << 4) | op) for op, n in cigar)
     if "seq4" in r:     # optional real content: packed 4-bit bases + qualities (realistic inflate cost)

@@ -411,3 +411,181 @@ def test_evidence_rejects_a_library_outside_the_table(setup):
     rgs = list(sample.rg_to_lib.keys())
     with pytest.raises(hip.SvtyperHipError):
         nbam.evidence(win, bps, rgs, [5] * len(rgs), None, nr.COUNT_CLASSIC, [400.0], 20, 3, 1)     # library 5 of a table of 1
+
+
+# ------------------------------------------------------------------------------------------
+# corners of the record rules (svtyper_amd/csrc/svt_record_rules.h) where the host reader and the evidence walk differ in what
+# they accept: one site with three plain reads (tests/walkcases.py) plus the read(s) of the case
+# ------------------------------------------------------------------------------------------
+def _corner(tmp_path, name, extra):
+    """(svt_bam_evidence's result or the text of its SvtyperHipError, the walk's result, the Python packer's result or None when
+    the Python reader raises, svt_bam_summarise's result -- every field of every piece -- or None); where the native and the
+    Python reader both have an answer, their summaries are equal"""
+    import walkcases as W
+    records = [W._read("ok%d" % k, 50_000 + k) for k in range(3)] + extra
+    sample, nbam = W.open_sample(W.write_case(tmp_path, name, records), W.INFO)
+    sites = [{"breakpoint": W.SITE}]
+    a = W.unit_arrays(sites, sample, nbam, nr.COUNT_SSO)
+    try:
+        host = nbam.evidence(a[0], a[1], a[2], a[3], 1000, nr.COUNT_SSO, a[4], 20, 3, 1)
+        summaries = _native_summaries(sites, sample, nbam, nr.COUNT_SSO, 1000, 1)
+    except hip.SvtyperHipError as e:
+        host, summaries = str(e), None
+    walk = nbam.evidence_walk_host(a[0], a[1], a[2], a[3], 1000, nr.COUNT_SSO, a[4], 20, 3, 1)
+    try:
+        py = _python_records(sites, sample, nr.COUNT_SSO, 1000)
+        py_summaries = _python_summaries(sites, sample, nr.COUNT_SSO, 1000)
+    except Exception:
+        py = py_summaries = None
+    if py is not None and summaries is not None:
+        assert _same(summaries, py_summaries)
+    return host, walk, py, summaries
+
+
+def _same(a, b):
+    return all(x.tobytes() == y.tobytes() for x, y in zip(a[:3], b[:3]))
+
+
+def _reason(walk):
+    return nr.WALK_REASONS.get(int(walk[3][0]), "")
+
+
+def _sa_read(pos="52001", mapq="60", cigar="40S60M"):
+    import walkcases as W
+    return W._read("s", 50_010, cigar="60M40S", tags=[("RG", "Z", "rg"), ("SA", "Z", "1,%s,+,%s,%s,0;" % (pos, cigar, mapq))])
+
+
+@pytest.mark.parametrize("field", ["pos", "mapq"])
+def test_numbers_of_an_sa_entry(tmp_path, field):
+    """The host reader reads an SA number with strtoll over the whole field: a sign and leading white space are read, anything
+    left over fails the call.  The walk takes 1 to 15 plain digits and flags everything else (such a unit goes back to the host
+    reader).  (Python's int() also takes trailing white space: "5 " is the one text where the native reader differs from
+    bam.py / fragments.py, which is pinned here as it is.)"""
+    plain, walk, py, plain_sum = _corner(tmp_path, "plain", [_sa_read(**{field: "5"})])
+    assert not isinstance(plain, str) and py is not None and _reason(walk) == "" and _same(plain, walk) and _same(plain, py)
+    assert (plain_sum[1]["seq"]["flags"] & 1).any()                          # (the entry makes a split candidate)
+    for k, text in enumerate(("+5", " 5")):
+        host, walk, py, summaries = _corner(tmp_path, "signed%d" % k, [_sa_read(**{field: text})])
+        assert _same(host, plain) and _same(py, plain) and _same(summaries, plain_sum)
+        assert _reason(walk) == "malformed" and len(walk[1]) == 0
+    for k, text in enumerate(("5 ", "")):
+        host, walk, py, _ = _corner(tmp_path, "left%d" % k, [_sa_read(**{field: text})])
+        assert isinstance(host, str) and "malformed SA tag" in host and _reason(walk) == "malformed"
+    host, walk, py, summaries = _corner(tmp_path, "minus", [_sa_read(**{field: "-1"})])
+    assert _reason(walk) == "malformed"
+    if field == "pos":
+        assert not isinstance(host, str) and py is not None and _same(host, py) and not _same(summaries, plain_sum)
+    else:
+        assert isinstance(host, str) and "MAPQ outside 0..255" in host
+    host, walk, py, summaries = _corner(tmp_path, "long", [_sa_read(**{field: "1000000000000005"})])       # 16 digits
+    assert _reason(walk) == "malformed" and not isinstance(host, str) and py is not None and _same(host, py)
+    assert not _same(summaries, plain_sum)
+    if field == "mapq":
+        assert _same(summaries, _corner(tmp_path, "m255", [_sa_read(mapq="255")])[3])
+
+
+def test_sa_mapq_above_255(tmp_path):
+    """the host reader stores 255; the walk takes 255 and flags what lies above"""
+    at_255, walk, py, sum_255 = _corner(tmp_path, "m255", [_sa_read(mapq="255")])
+    assert _reason(walk) == "" and _same(at_255, walk) and py is not None and _same(at_255, py)
+    assert not _same(sum_255, _corner(tmp_path, "m60", [_sa_read(mapq="60")])[3])
+    for text in ("256", "100000"):
+        host, walk, py, summaries = _corner(tmp_path, "m" + text, [_sa_read(mapq=text)])
+        assert _same(host, at_255) and _same(py, at_255) and _same(summaries, sum_255)
+        assert _reason(walk) == "mapq" and len(walk[1]) == 0
+
+
+def test_sa_cigar_numbers(tmp_path):
+    """an operation length of 16 to 18 digits is a number to the host reader (clipped to 32 bits on the way out) and outside
+    the walk's envelope"""
+    plain_sum = _corner(tmp_path, "plain", [_sa_read()])[3]
+    for digits in (16, 18):
+        host, walk, py, summaries = _corner(tmp_path, "c%d" % digits, [_sa_read(cigar="40S1%sM" % ("0" * (digits - 1)))])
+        assert not isinstance(host, str) and py is not None and _same(host, py) and (summaries[1]["seq"]["flags"] & 1).any()
+        assert not _same(summaries, plain_sum) and _reason(walk) == "malformed"
+
+
+def test_sa_cigar_number_beyond_64_bits(tmp_path):
+    """from 19 digits on an operation length need not fit 64 bits: malformed in both (the host reader used to add it up
+    regardless, a signed overflow)"""
+    for digits in (19, 25):
+        host, walk, _, _ = _corner(tmp_path, "c%d" % digits, [_sa_read(cigar="40S1%sM" % ("0" * (digits - 1)))])
+        assert isinstance(host, str) and "malformed SA tag" in host and _reason(walk) == "malformed"
+
+
+@pytest.mark.parametrize("which", ["supplementary", "repeated"])
+def test_truncated_tag_behind_rg_on_a_read_that_is_not_a_candidate(tmp_path, which):
+    """The host reader walks the tags behind RG only for a read that reaches split_candidate: a supplementary read and a
+    repeated (name, flag) stop at RG, the cut-off tag behind it is never seen and the unit has its records.  The walk validates
+    the whole tag area of every kept read and flags the unit.  (bam.py parses every tag of every read and raises.)"""
+    import walkcases as W
+    bad = ("XT", "raw", b"XTZno-terminator")
+    first = W._read("dup", 50_010, cigar="60M40S")
+    odd = W._read("dup", 50_020, cigar="60M40S", tags=[("RG", "Z", "rg"), bad], flag=(0x1 | 0x40) | (0x800 if which == "supplementary" else 0))
+    host, walk, py, summaries = _corner(tmp_path, which, [first, odd])
+    clean = _corner(tmp_path, which + "_clean", [first, dict(odd, tags=[("RG", "Z", "rg")])])
+    assert not isinstance(host, str) and _same(host, clean[0]) and _same(summaries, clean[3]) and len(host[1]) == 4 and py is None
+    assert _reason(walk) == "malformed" and len(walk[1]) == 0
+
+
+def test_a_value_that_runs_over_the_record_ends_the_host_readers_tag_walk(tmp_path):
+    """a fixed-size value or a B array that reaches beyond the record: the host reader's walk ends there without a complaint
+    (behind RG: the read is kept), the walk flags the unit"""
+    import struct
+    import walkcases as W
+    for k, raw in enumerate((b"XBBi" + struct.pack("<I", 1000) + b"\0" * 8, b"XIi\0\0")):
+        host, walk, _, summaries = _corner(tmp_path, "over%d" % k, [W._read("t", 50_010, tags=[("RG", "Z", "rg"), ("XX", "raw", raw)])])
+        clean = _corner(tmp_path, "over%d_clean" % k, [W._read("t", 50_010)])
+        assert not isinstance(host, str) and _same(host, clean[0]) and _same(summaries, clean[3]) and _reason(walk) == "malformed"
+
+
+def _interval_summaries(tmp_path, name, cigar, pos):
+    import walkcases as W
+    records = [W._read("ok%d" % k, 50_000 + k) for k in range(3)] + [W._read("iv", pos, cigar=cigar)]
+    sample, nbam = W.open_sample(W.write_case(tmp_path, name, records), W.INFO)
+    sites = [{"breakpoint": W.SITE}]
+    want = _python_summaries(sites, sample, nr.COUNT_SSO, 1000)
+    got = _native_summaries(sites, sample, nbam, nr.COUNT_SSO, 1000, 1)
+    assert np.array_equal(got[0], want[0]) and got[1].tobytes() == want[1].tobytes()
+    a = W.unit_arrays(sites, sample, nbam, nr.COUNT_SSO)
+    host = nbam.evidence(a[0], a[1], a[2], a[3], 1000, nr.COUNT_SSO, a[4], 20, 3, 1)
+    walk = nbam.evidence_walk_host(a[0], a[1], a[2], a[3], 1000, nr.COUNT_SSO, a[4], 20, 3, 1)
+    assert _reason(walk) == "" and _same(host, walk)
+    read = got[1]["read"][:, 0][[i for i in range(len(got[1])) if got[1]["read"][i, 0]["start"] == pos][0]]
+    return list(zip(read["iv_start"].tolist(), read["iv_end"].tolist()))
+
+
+def test_aligned_intervals_that_tie_and_gaps_of_both_kinds(tmp_path):
+    """More than two gap-free intervals: the two nearest to the breakends (50 050 and 50 851) in the order of a STABLE sort by
+    distance.  Here one interval is 130 away and three are 30 away (two from the first breakend, one from the second): the first
+    two of those three, in the order of the read.  Then a read with N and D gaps and no tie."""
+    assert _interval_summaries(tmp_path, "tie", "20M80N20M60D20M781N20M", 49_900) == [(50_000, 50_020), (50_080, 50_100)]
+    assert _interval_summaries(tmp_path, "tie2", "20M60D20M781N20M1000N20M", 50_000) == [(50_000, 50_020), (50_080, 50_100)]
+    assert _interval_summaries(tmp_path, "far_first", "20M30N20M20D20M", 49_900) == [(49_990, 50_010), (49_950, 49_970)]
+    assert _interval_summaries(tmp_path, "two", "30M5D30M5I40M", 50_000) == [(50_000, 50_030), (50_035, 50_105)]
+    assert _interval_summaries(tmp_path, "nd", "30M2D30M5N40M", 50_000) == [(50_032, 50_062), (50_067, 50_107)]
+
+
+def test_a_record_without_a_cigar_in_the_window(tmp_path):
+    """n_cigar = 0: the record overlaps as one base at its position, is a primary of its fragment and no split candidate
+    (geometry.py has no words for such a read: the native answer is pinned)"""
+    import walkcases as W
+    host, walk, _, summaries = _corner(tmp_path, "nocigar", [W._read("z", 50_010, cigar="*")])
+    assert not isinstance(host, str) and len(host[1]) == 4 and _reason(walk) == "" and _same(host, walk)
+    z = summaries[1][3]
+    assert (int(z["read"][0]["start"]), int(z["read"][0]["end"]), int(z["read"][0]["flags"]) & 1, int(z["read"][1]["flags"])) == (50_010, 50_010, 1, 0)
+    assert not z["read"][0]["iv_end"].any() and not (z["seq"]["flags"] | z["clip"]["flags"]).any()
+
+
+def test_a_record_whose_l_seq_does_not_fit(tmp_path):
+    """l_seq larger than the record: the host reader's fetch ends the chunk in front of such a record without a complaint (the
+    reads behind it are lost; bam.py differs), the walk flags the unit.  A small negative l_seq moves where the host reader
+    takes the tags to begin: it finds no RG tag there and fails the call; the walk flags the unit."""
+    import walkcases as W
+    host, walk, _, _ = _corner(tmp_path, "lseq_big", [W._read("a", 50_010), dict(W._read("big", 50_020), l_seq_field=1 << 20), W._read("b", 50_030)])
+    assert not isinstance(host, str) and len(host[1]) == 4 and not host[2].any()          # ok0..2 and "a"
+    assert _reason(walk) == "range" and len(walk[1]) == 0
+    host, walk, _, _ = _corner(tmp_path, "lseq_neg", [dict(W._read("neg", 50_020), l_seq_field=-1)])
+    assert isinstance(host, str) and "RG tag" in host and _reason(walk) == "range"
+    host, walk, _, _ = _corner(tmp_path, "lseq_min", [W._read("a", 50_010), dict(W._read("min", 50_020), l_seq_field=-(1 << 31))])
+    assert not isinstance(host, str) and len(host[1]) == 4 and _reason(walk) == "range"

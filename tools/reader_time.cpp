@@ -1,5 +1,6 @@
 // Times svt_bam_evidence over dumped units (windows + breakpoints as the ctypes layer hands them over), reader alone (no HIP):
 //   g++ -std=c++17 -O2 -I svtyper_amd/csrc -I include -o reader_time tools/reader_time.cpp svtyper_amd/csrc/svt_reads.cpp -lz -ldl -lpthread
+//   (the units: tools/dump_units.py DIR [REPEAT])
 //   reader_time <bam> <windows.bin> <breakpoints.bin> <threads> <repetitions> <read group>=<library index> ...
 #include <cstdio>
 #include <cstdlib>
