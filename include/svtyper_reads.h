@@ -159,6 +159,61 @@ int svt_bam_evidence_device(const svt_bam* bam, const svt_summarise_args* args, 
                             const svt_evidence_batch* header, int device, unsigned flags, svt_batch** out,
                             uint8_t* skipped, svt_evidence_device_stats* stats);
 
+/* ---- BGZF inflate by ONE piece of decoder source, and the device reader that uses it (additions to ABI 19) ----
+ * svtyper_amd/csrc/svt_inflate.h decodes the raw-deflate payload of a BGZF member (stored, fixed and dynamic blocks)
+ * into exactly ISIZE bytes or a status; it is compiled for the host and for the device (svt_inflate_kernel.h, one
+ * wavefront per member).  The verdict is the host reader's and zlib's: the stream ends with its final block having
+ * produced exactly ISIZE bytes; bytes behind the final block are ignored, the CRC32 is not checked.
+ *
+ * svt_bgzf_inflate_host / _device: `data[len]` holds whole BGZF members at block_off[0..n); member k goes to
+ * out + out_off[k] and has to fill out_off[k + 1] - out_off[k] bytes (the caller's prefix sums of ISIZE).
+ * status[k]: 0 or an SVT_INFLATE_* reason; the bytes of a failed member are undefined.  The return value is
+ * about the arguments (and the GPU), not about the members.                                                  */
+#define SVT_INFLATE_INPUT 1     /* the payload ends inside the stream                                         */
+#define SVT_INFLATE_BTYPE 2     /* block type 3                                                               */
+#define SVT_INFLATE_STORED 3    /* stored block: LEN / NLEN disagree                                          */
+#define SVT_INFLATE_LENGTHS 4   /* bad code-length set (over- / under-subscribed, bad repeat, no end-of-block)*/
+#define SVT_INFLATE_SYMBOL 5    /* bits that are no code / literal-length symbol 286, 287                     */
+#define SVT_INFLATE_DISTANCE 6  /* distance symbol 30, 31 / distance before the start of the output           */
+#define SVT_INFLATE_OUTPUT 7    /* more than ISIZE bytes                                                      */
+#define SVT_INFLATE_SHORT 8     /* the stream ends with fewer than ISIZE bytes                                */
+#define SVT_INFLATE_MEMBER 9    /* no BGZF member at the offset / ISIZE is not the place it was given         */
+int svt_bgzf_inflate_host(const uint8_t* data, uint64_t len, const uint64_t* block_off, uint64_t n, uint8_t* out,
+                          const uint64_t* out_off, uint32_t* status);
+int svt_bgzf_inflate_device(const uint8_t* data, uint64_t len, const uint64_t* block_off, uint64_t n, uint8_t* out,
+                            const uint64_t* out_off, uint32_t* status, int device);
+
+/* svt_bam_evidence_walk_open_host: svt_bam_evidence_walk_host over the arena of the route below, with no GPU:
+ * BAI lookup, a walk over BGZF headers only, every needed member inflated once by svt_inflate.h, one range per
+ * index chunk from its start to its end virtual offset, and the walk ending each window where the fetch does
+ * (the first record on another reference or at / behind the window's end).  A unit over a member that does
+ * not inflate is flagged SVT_WALK_RANGE.                                                                    */
+int svt_bam_evidence_walk_open_host(const svt_bam* bam, const svt_summarise_args* args, const svt_evidence_params* geometry,
+                                    svt_evidence* out, uint8_t* out_of_envelope, uint32_t* kept_reads);
+
+/* svt_bam_evidence_device_inflate: svt_bam_evidence_device with the BGZF inflate on the GPU too.  The host does the
+ * BAI lookup and the header walk and uploads the COMPRESSED members from the file mapping; svt_inflate_kernel
+ * writes the arena in HBM; units over a member that failed go to the host reader (SVT_WALK_RANGE).  Arguments
+ * and result are svt_bam_evidence_device's; `istats` (may be null) is filled; `count_host_blocks` != 0 also
+ * builds the host-inflate arena of the same call, only to report how many blocks that route touches (the open
+ * ranges of this one run to the end of every index chunk, the host reader stops at the first record behind the
+ * window).  The arena is limited to 4 GiB of inflated bytes per call, as svt_bam_evidence_device's is.       */
+typedef struct svt_evidence_inflate_stats {
+    uint64_t blocks_inflated;      /* members handed to the inflate kernel                                   */
+    uint64_t blocks_failed;        /* ... whose status is not 0                                              */
+    uint64_t compressed_bytes;     /* uploaded                                                               */
+    uint64_t inflated_bytes;       /* the arena                                                              */
+    uint64_t blocks_host_route;    /* blocks the host-inflate arena holds (0 unless count_host_blocks)       */
+    double host_index_s;           /* BAI lookup + header walk                                               */
+    double compressed_upload_s;
+    double inflate_kernel_s;       /* host-observed: launch to the statuses' arrival                         */
+} svt_evidence_inflate_stats;
+
+int svt_bam_evidence_device_inflate(const svt_bam* bam, const svt_summarise_args* args, const svt_evidence_params* geometry,
+                                    const svt_evidence_batch* header, int device, unsigned flags, svt_batch** out,
+                                    uint8_t* skipped, svt_evidence_device_stats* stats, svt_evidence_inflate_stats* istats,
+                                    int count_host_blocks);
+
 /* Library statistics straight from the BAM (svtyper/parsers.py:501-576): what Library.from_bam scans
  * for, for ONE library given as its read-group ids, in three passes from the first record each --
  *   read_length : max query length (M/I/S/=/X) over the library's reads until 10 001 of them were seen

@@ -22,7 +22,7 @@ from . import evidence as ev
 from .bam import open_alignment_file
 from .library import Sample, setup_sample, write_sample_json
 from .pipeline import (MIN_LIB_PREVALENCE, BulkFeeder, ChunkPipeline, NativeUnitCollector, SampleColumnWriter, UnitCollector, add_read_to,
-                       default_engine, fetch_window, resolve_reader, text_blocks)
+                       default_engine, check_inflate, fetch_window, resolve_reader, text_blocks)
 from .results import results_to_dicts
 from .vcf import VALID_SVTYPES, Variant, Vcf
 
@@ -66,10 +66,11 @@ def apply_result(var: Variant, sample_name: str, gt: int, res: dict) -> None:
 
 def sv_genotype(bam_string, vcf_in, vcf_out, min_aligned, split_weight, disc_weight, num_samp, lib_info_path,
                 debug, alignment_outpath, ref_fasta, sum_quals, max_reads, max_ci_dist, *, engine=None, geometry="host",
-                reader=None, stats=None):
+                reader=None, stats=None, inflate="host"):
     if alignment_outpath is not None:
         raise NotImplementedError("-w/--write_alignment (evidence BAM dump) is outside the MI355X hot path build")
     reader = resolve_reader(reader)
+    check_inflate(reader, inflate)
     bams = []
     for path in bam_string.split(","):
         if not (path.endswith(".bam") or path.endswith(".cram")):
@@ -100,7 +101,8 @@ def sv_genotype(bam_string, vcf_in, vcf_out, min_aligned, split_weight, disc_wei
     vcf = Vcf()
     if reader in ("native", "device"):      # C++ fetch + summariser; geometry in the reader's threads ("host") or on the device
         collector = NativeUnitCollector(samples, native, split_weight, disc_weight, min_aligned, COUNT_CLASSIC,
-                                        max_reads, geometry="walk" if reader == "device" else "device" if geometry == "device" else "reader")
+                                        max_reads, geometry="walk" if reader == "device" else "device" if geometry == "device" else "reader",
+                                        inflate=inflate)
     elif reader == "python":
         collector = UnitCollector(samples, split_weight, disc_weight, min_aligned, geometry)
     else:
@@ -325,6 +327,9 @@ def get_args():
                    help="BAM access + fragment assembly: the C++ threads of libsvtyper_hip.so feeding the device "
                         "geometry stage, the same with the evidence records built on the GPU (device), or the portable Python "
                         "reader (same output bytes) [native]")
+    p.add_argument("--inflate", choices=("host", "device"), default="host",
+                   help="with --reader device: BGZF blocks inflated by the reader's threads, or on the GPU from the "
+                        "compressed blocks (same output bytes) [host]")
     p.add_argument("--geometry", choices=("host", "device"), default="host",
                    help="with --reader python: breakpoint-dependent read predicates on the host or on the GPU [host]")
     args = p.parse_args()
@@ -344,13 +349,13 @@ def main():
     from . import sharded
     job = sharded.job()
     if job is None:
-        return sv_genotype(*call, geometry=args.geometry, reader=args.reader)
+        return sv_genotype(*call, geometry=args.geometry, reader=args.reader, inflate=args.inflate)
     # launched by torch.distributed.run with several ranks: one GPU each, variants sharded, one gather
     rank, world, local_rank = job
     call = call[:2] + (sharded.private_stdout(call[2]),) + call[3:]
     engine = sharded.init(local_rank)
     sharded.sv_genotype_sharded(*call, rank=rank, world=world, engine=engine, geometry=args.geometry,
-                                reader=args.reader)
+                                reader=args.reader, inflate=args.inflate)
     sharded.finish()
 
 

@@ -1,9 +1,31 @@
 // svt_entry_evidence.h -- part of the single translation unit svtyper_hip.hip (included there, in order; not a stand-alone header):
-// C ABI: svt_bam_evidence_device (include/svtyper_reads.h) and the read-back of a resident batch's records for its parity tests.
+// C ABI: svt_bam_evidence_device, svt_bam_evidence_device_inflate, svt_bgzf_inflate_device (include/svtyper_reads.h) and the
+// read-back of a resident batch's records for the parity tests.
 
+// `n` members of the compressed bytes at d_src into d_dst, one wavefront each; the statuses come back in `status`
+static int run_inflate_kernel(const uint8_t* d_src, uint64_t src_len, const inf::Member* d_members, uint64_t n, uint8_t* d_dst, uint64_t dst_len,
+                              uint32_t* d_status, std::vector<uint32_t>& status, hipStream_t s)
+{
+    status.assign(n, 0);
+    constexpr uint64_t kGrid = 1u << 30;
+    for (uint64_t at = 0; at < n; at += kGrid) {
+        const uint64_t m = std::min(kGrid, n - at);
+        hipLaunchKernelGGL(svt_inflate_kernel, dim3((unsigned)m), dim3(kInflateBlock), 0, s, d_src, src_len, d_members + at, (uint32_t)m, d_dst, dst_len,
+                           d_status + at);
+        HIP_TRY(hipGetLastError());
+    }
+    if (n) HIP_TRY(hipMemcpyAsync(status.data(), d_status, n * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return SVT_OK;
+}
+
+// Both device readers.  `istats` == null: the host builds the arena of inflated blocks (svt_bam_evidence_device); else the host
+// lays the arena out from BGZF headers and svt_inflate_kernel fills it in HBM (svt_bam_evidence_device_inflate).  Everything
+// behind the arena -- the walk launches, the fallback, the scan, the batch -- is the same code.
 static int svt_bam_evidence_device_impl(const svt_bam* bam, const svt_summarise_args* args, const svt_evidence_params* geometry,
                                         const svt_evidence_batch* header, int device, unsigned flags, svt_batch** out,
-                                        uint8_t* skipped_out, svt_evidence_device_stats* stats)
+                                        uint8_t* skipped_out, svt_evidence_device_stats* stats, svt_evidence_inflate_stats* istats = nullptr,
+                                        bool count_host_blocks = false)
 {
     if (!bam || !args || !geometry || !header || !out) return fail(SVT_ERR_INVALID, "null argument");
     *out = nullptr;
@@ -18,9 +40,22 @@ static int svt_bam_evidence_device_impl(const svt_bam* bam, const svt_summarise_
     auto now = [] { return std::chrono::steady_clock::now(); };
     auto since = [&](std::chrono::steady_clock::time_point t0) { return std::chrono::duration<double>(now() - t0).count(); };
 
-    // ---- host: BAI lookup, inflate, arena
+    // ---- host: BAI lookup, and either inflate + arena or the arena's layout from BGZF headers
     ew::Arena arena;
-    SVT_TRY(ew::build_arena(bam, args, geometry, arena));
+    ew::OpenPlan plan;
+    if (istats) {
+        *istats = svt_evidence_inflate_stats{};
+        if (count_host_blocks) {
+            ew::Arena host_route;
+            SVT_TRY(ew::build_arena(bam, args, geometry, host_route));
+            istats->blocks_host_route = host_route.blocks;
+        }
+        SVT_TRY(ew::build_arena_open(bam, args, geometry, arena, plan));
+        istats->host_index_s = plan.index_s;
+        istats->blocks_inflated = plan.members.size();
+        istats->compressed_bytes = plan.compressed_bytes;
+        istats->inflated_bytes = plan.arena_bytes;
+    } else SVT_TRY(ew::build_arena(bam, args, geometry, arena));
     S.host_arena_s = arena.build_s;
     S.reads_walked = arena.records_in_ranges;
     SVT_TRY(select_device(device));
@@ -35,7 +70,8 @@ static int svt_bam_evidence_device_impl(const svt_bam* bam, const svt_summarise_
         ~Pooled() { g_pool.put(device, p, cap); }
         int get(uint64_t bytes, bool records = false) { return g_pool.get(device, bytes, &p, &cap, records); }
         void* release() { void* q = p; p = nullptr; return q; }
-    } d_arena{device}, d_records{device};
+    } d_arena{device}, d_records{device}, d_compressed{device};
+    DevScratch d_members, d_member_status;
     DevScratch d_ranges, d_units, d_windows, d_bps, d_rgs, d_refs, d_blob, d_flank, d_status, d_rows, d_reads, d_off, d_src, d_src_off, d_dst_off;
     // declared behind every device buffer, so it runs in front of their release on every way out: nothing goes back to a pool
     // while a kernel of this call may still be running
@@ -45,7 +81,21 @@ static int svt_bam_evidence_device_impl(const svt_bam* bam, const svt_summarise_
     {
         Stager st(s);
         SVT_TRY(d_arena.get(arena.bytes.size()));
-        SVT_TRY(st.copy(d_arena.p, arena.bytes.data(), arena.bytes.size()));
+        if (istats) {
+            // the compressed members from the mapping, the inflate kernel, the statuses; a unit over a failed member is the host's
+            SVT_TRY(d_compressed.get(plan.compressed_bytes + 8));
+            for (const auto& sp : plan.spans) SVT_TRY(st.copy(static_cast<uint8_t*>(d_compressed.p) + sp.at, plan.file + sp.file_off, sp.bytes));
+            SVT_TRY(upload(d_members, plan.members, st));
+            SVT_TRY(d_member_status.alloc(plan.members.size() * sizeof(uint32_t)));
+            SVT_TRY(st.finish());
+            istats->compressed_upload_s = since(t0);
+            const auto t_kernel = now();
+            std::vector<uint32_t> member_status;
+            SVT_TRY(run_inflate_kernel(static_cast<const uint8_t*>(d_compressed.p), plan.compressed_bytes, d_members.as<inf::Member>(), plan.members.size(),
+                                       static_cast<uint8_t*>(d_arena.p), plan.arena_bytes, d_member_status.as<uint32_t>(), member_status, s));
+            istats->inflate_kernel_s = since(t_kernel);
+            istats->blocks_failed = ew::apply_member_status(plan, member_status, arena);
+        } else SVT_TRY(st.copy(d_arena.p, arena.bytes.data(), arena.bytes.size()));
         SVT_TRY(upload(d_ranges, arena.ranges, st));
         SVT_TRY(upload(d_units, arena.units, st));
         SVT_TRY(d_windows.alloc(n * sizeof(svt_fetch_unit)));
@@ -57,7 +107,7 @@ static int svt_bam_evidence_device_impl(const svt_bam* bam, const svt_summarise_
         SVT_TRY(upload(d_blob, arena.blob, st));
         SVT_TRY(upload(d_flank, flank, st));
         SVT_TRY(st.finish());
-        S.bytes_uploaded = arena.bytes.size() + arena.ranges.size() * sizeof(ew::Range) + n * (sizeof(ew::UnitRanges) + sizeof(svt_fetch_unit) + sizeof(svt_breakpoint)) + arena.blob.size();
+        S.bytes_uploaded = (istats ? plan.compressed_bytes + plan.members.size() * sizeof(inf::Member) : arena.bytes.size()) + arena.ranges.size() * sizeof(ew::Range) + n * (sizeof(ew::UnitRanges) + sizeof(svt_fetch_unit) + sizeof(svt_breakpoint)) + arena.blob.size();
     }
     SVT_TRY(d_status.alloc(n * sizeof(uint32_t)));
     SVT_TRY(d_rows.alloc(n * sizeof(uint32_t)));
@@ -185,6 +235,49 @@ int svt_bam_evidence_device(const svt_bam* bam, const svt_summarise_args* args, 
                             svt_evidence_device_stats* stats)
 {
     return guarded([&] { return svt_bam_evidence_device_impl(bam, args, geometry, header, device, flags, out, skipped, stats); });
+}
+
+int svt_bam_evidence_device_inflate(const svt_bam* bam, const svt_summarise_args* args, const svt_evidence_params* geometry,
+                                    const svt_evidence_batch* header, int device, unsigned flags, svt_batch** out, uint8_t* skipped,
+                                    svt_evidence_device_stats* stats, svt_evidence_inflate_stats* istats, int count_host_blocks)
+{
+    return guarded([&] {
+        svt_evidence_inflate_stats local{};
+        return svt_bam_evidence_device_impl(bam, args, geometry, header, device, flags, out, skipped, stats, istats ? istats : &local, count_host_blocks != 0);
+    });
+}
+
+// the parity entry of the inflate kernel: upload, one wavefront per member, download
+int svt_bgzf_inflate_device(const uint8_t* data, uint64_t len, const uint64_t* block_off, uint64_t n, uint8_t* out, const uint64_t* out_off,
+                            uint32_t* status, int device)
+{
+    return guarded([&]() -> int {
+        if (n && (!status || (!out && out_off && out_off[n]))) return fail(SVT_ERR_INVALID, "null argument");
+        std::vector<inf::Member> members(n);
+        SVT_TRY(ew::bgzf_members(data, len, block_off, n, out_off, members.data()));
+        SVT_TRY(select_device(device));
+        if (n == 0) return SVT_OK;
+        hipStream_t s = nullptr;
+        SVT_TRY(g_handles.get_stream(&s));
+        struct StreamReturn { hipStream_t s; ~StreamReturn() { g_handles.put_stream(s); } } stream_return{s};
+        DevScratch d_src, d_dst, d_members, d_status;
+        struct StreamSync { hipStream_t s; ~StreamSync() { (void)hipStreamSynchronize(s); } } stream_sync{s};
+        const uint64_t out_len = out_off[n];
+        SVT_TRY(d_src.alloc(len));
+        SVT_TRY(d_dst.alloc(out_len));
+        SVT_TRY(d_status.alloc(n * sizeof(uint32_t)));
+        {
+            Stager st(s);
+            SVT_TRY(st.copy(d_src.p, data, len));
+            SVT_TRY(upload(d_members, members, st));
+            SVT_TRY(st.finish());
+        }
+        std::vector<uint32_t> st_host;
+        SVT_TRY(run_inflate_kernel(d_src.as<uint8_t>(), len, d_members.as<inf::Member>(), n, d_dst.as<uint8_t>(), out_len, d_status.as<uint32_t>(), st_host, s));
+        std::memcpy(status, st_host.data(), n * sizeof(uint32_t));
+        if (out_len) SVT_TRY(d2h_staged(out, d_dst.p, out_len, s));
+        return SVT_OK;
+    });
 }
 
 // the records and offsets of a resident batch of canonical records, back on the host (parity tests of the device reader):

@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "svt_evidence_walk.h"
+#include "svt_inflate.h"
 
 namespace svt {
 namespace ew {
@@ -20,7 +21,9 @@ struct Arena {
     std::vector<NameRef> rgs, refs;
     std::vector<uint8_t> blob;             // the bytes of the read-group ids and reference names
     uint64_t records_in_ranges = 0;
+    uint64_t blocks = 0;                   // BGZF blocks in `bytes`
     double build_s = 0.0;
+    bool open_ranges = false;              // build_arena_open: the walk ends every window itself (Params.open_ranges)
     Params params(const svt_summarise_args* args, const svt_evidence_params* geometry) const
     {
         Params P{};
@@ -41,12 +44,41 @@ struct Arena {
         P.split_slop = geometry->split_slop;
         P.count_mode = args->count_mode;
         P.max_reads = args->max_reads;
+        P.open_ranges = open_ranges ? 1u : 0u;
         return P;
     }
 };
 
 // BAI lookup + BGZF inflate of every unit's windows (the reader's threads and block cache); 0 or SVT_ERR_* with the error text set
 int build_arena(const svt_bam* bam, const svt_summarise_args* args, const svt_evidence_params* geometry, Arena& out);
+
+// ---- the arena without inflating on the host (inflate = "device") ---------------------------------------------------------------
+// What build_arena_open leaves to its caller: the BGZF members whose ISIZE bytes make up the arena.  `members[k].src` is an offset
+// into the compressed bytes as they are uploaded -- the file spans `spans` side by side, span k at `spans[k].at` --, `dst` the
+// member's offset in the arena.  `range_members[r]`: the members arena.ranges[r] lies over (first, last).
+struct OpenPlan {
+    struct Span { uint64_t file_off, bytes, at; };
+    const uint8_t* file = nullptr;         // the mapping of the BAM
+    uint64_t file_size = 0;
+    std::vector<Span> spans;
+    uint64_t compressed_bytes = 0;         // sum of the spans
+    uint64_t arena_bytes = 0;              // sum of the members' ISIZE
+    std::vector<inf::Member> members;
+    std::vector<std::pair<uint32_t, uint32_t>> range_members;
+    double index_s = 0.0;
+};
+
+// BAI lookup and a walk over BGZF headers only: every chunk of every window becomes one range from the chunk's start to its end
+// virtual offset (an upper bound; Params.open_ranges makes the walk stop where the fetch does).  out.bytes is sized, not filled.
+int build_arena_open(const svt_bam* bam, const svt_summarise_args* args, const svt_evidence_params* geometry, Arena& out, OpenPlan& plan);
+// the members inflated on the CPU by svt_inflate.h, straight from the mapping into out.bytes; status[k] per member
+void inflate_open_host(const OpenPlan& plan, Arena& out, unsigned n_threads, std::vector<uint32_t>& status);
+// every unit with a range over a member whose status is not 0 gets preset = EW_RANGE; returns the number of failed members
+uint64_t apply_member_status(const OpenPlan& plan, const std::vector<uint32_t>& status, Arena& out);
+
+// the members at block_off[] of `data` as inf::Member (dst = out_off[k]); a member that is none, or whose ISIZE is not the place
+// out_off gives it, comes back with isize = inf::kNoMember
+int bgzf_members(const uint8_t* data, uint64_t len, const uint64_t* block_off, uint64_t n, const uint64_t* out_off, inf::Member* members);
 
 // the units `ids` (ascending) recomputed by the host reader: their records side by side in `records`, `counts[k]` of them for
 // ids[k], `skipped[k]`.  An error is the one svt_bam_evidence reports for that unit (code returned, text set).

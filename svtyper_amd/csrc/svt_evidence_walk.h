@@ -75,6 +75,7 @@ struct Params {
     int32_t min_aligned, split_slop;
     int32_t count_mode;
     int64_t max_reads;
+    uint32_t open_ranges;                  // != 0: a range ends at its chunk's end, not at the record that ends the fetch: the walk stops the window itself
 };
 
 // ---- the fixed-size summary of one kept read: what ReadInfo + SplitOut carry ---------------------------------------------
@@ -102,7 +103,7 @@ struct UnitScratch {
             uint16_t order[kMaxReads], rows[kMaxReads], rowoff[kMaxReads];
         } s;
     };
-    uint32_t n_reads, n_walked, status, nb, pos, n_ovl, n_counted, lcp, n_rows, range_done;
+    uint32_t n_reads, n_walked, status, nb, pos, n_ovl, n_counted, lcp, n_rows, range_done, window_done;
 };
 
 struct HostCtx {
@@ -257,10 +258,11 @@ SVT_HD void gather_window(const Params& P, UnitScratch& S, const Range* ranges, 
     const bool mode1 = P.count_mode == 1 && P.max_reads >= 0, mode0 = P.count_mode == 0 && P.max_reads >= 0;
     if (lo < 0) lo = 0;                                    // (fetch clamps the window's start)
     X::sync();                                             // (every lane has read S.status on its way in)
-    if (lane == 0) { S.n_ovl = 0; S.n_counted = 0; }
+    if (lane == 0) { S.n_ovl = 0; S.n_counted = 0; S.window_done = 0; }
     for (uint32_t ri = 0; ri < n_ranges; ++ri) {
         const Range rg = ranges[ri];
         X::sync();                                         // (every lane is past the status check that ended the range before)
+        if (S.window_done) break;                          // (open ranges: the fetch ended in a range before this one)
         if (lane == 0) {
             S.pos = rg.begin;
             S.range_done = 0;
@@ -276,6 +278,9 @@ SVT_HD void gather_window(const Params& P, UnitScratch& S, const Range* ranges, 
                     if ((uint64_t)pos + 4 > rg.end) { S.status = EW_RANGE; break; }
                     const uint32_t size = ld32(P.arena + pos);
                     if (size < 32 || size > kMaxRecord || (uint64_t)pos + 4 + size > rg.end) { S.status = EW_RANGE; break; }
+                    // the fetch's own stop rule (svt_reads.cpp: fetch() / build_arena): the first record on another reference or at /
+                    // behind the window's end ends the window
+                    if (P.open_ranges && ((int32_t)ld32(P.arena + pos + 4) != wtid || (int64_t)(int32_t)ld32(P.arena + pos + 8) >= hi)) { S.window_done = 1; break; }
                     S.b.off[nb] = pos + 4;
                     S.b.size[nb] = size;
                     ++nb;
@@ -284,7 +289,7 @@ SVT_HD void gather_window(const Params& P, UnitScratch& S, const Range* ranges, 
                 S.nb = nb;
                 S.pos = pos;
                 S.n_walked += nb;
-                if (pos >= rg.end || nb == 0) S.range_done = 1;
+                if (pos >= rg.end || nb == 0 || S.window_done) S.range_done = 1;
             }
             X::sync();
             if (S.status != EW_OK) break;

@@ -1313,7 +1313,212 @@ int build_arena(const svt_bam* bam, const svt_summarise_args* args, const svt_ev
     }
     out.ranges.push_back(Range{0, 0});                                // (never an empty array)
     for (uint64_t c : n_records) out.records_in_ranges += c;
+    out.blocks = copies.size();
     out.build_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_begin).count();
+    return SVT_OK;
+}
+
+// ---- the same arena from BGZF headers alone (svt_evidence_arena.h) ---------------------------------------------------------------
+int build_arena_open(const svt_bam* bam, const svt_summarise_args* args, const svt_evidence_params* geometry, Arena& out, OpenPlan& plan)
+{
+    if (!bam || !args || !geometry) return fail(SVT_ERR_INVALID, "null argument");
+    if (geometry->n_libs == 0 || geometry->n_libs > 65536 || !geometry->lib_flank)
+        return fail(SVT_ERR_INVALID, "n_libs must be 1..65536 with a flank per library");
+    const uint64_t n = args->n_units;
+    if (n && (!args->windows || !args->breakpoints)) return fail(SVT_ERR_INVALID, "null unit arrays");
+    if (n >= 0xFFFFFFF0ull) return fail(SVT_ERR_INVALID, "too many units in one call (< 2^32)");
+    const auto t_begin = std::chrono::steady_clock::now();
+    out = Arena();
+    out.open_ranges = true;
+    plan = OpenPlan();
+    plan.file = bam->file.data;
+    plan.file_size = bam->file.size;
+    auto add_name = [&](std::vector<NameRef>& tab, const char* p, size_t len, int32_t value) {
+        tab.push_back(NameRef{(uint32_t)out.blob.size(), (uint32_t)len, value});
+        out.blob.insert(out.blob.end(), p, p + len);
+    };
+    for (uint32_t i = 0; i < args->n_read_groups; ++i) add_name(out.rgs, args->read_groups[i], std::strlen(args->read_groups[i]), args->read_group_lib[i]);
+    for (size_t i = 0; i < bam->ref_names.size(); ++i) add_name(out.refs, bam->ref_names[i].data(), bam->ref_names[i].size(), (int32_t)i);
+    out.blob.resize(out.blob.size() + 8, 0);
+
+    // ---- every chunk of every window: its first block, the in-block offset of its first record, the last block it needs and
+    // its end as an offset from that block's start
+    struct OpenRange { uint64_t first, last; uint32_t uoff, end_in_last; };
+    struct UnitRaw { uint32_t first = 0; uint16_t n[2] = {0, 0}; uint32_t preset = EW_OK; };
+    std::vector<UnitRaw> raw_units(n);
+    const unsigned nt = arena_threads(args, n);
+    std::vector<std::vector<OpenRange>> raw_ranges(nt);
+    std::vector<std::pair<uint64_t, unsigned>> unit_home(n);
+    const uint8_t* file = plan.file;
+    const uint64_t file_size = plan.file_size;
+    // false: the chunk cannot be laid out from headers (the unit goes to the host reader); *empty: nothing to walk
+    auto chunk_range = [&](uint64_t vbeg, uint64_t vend, OpenRange& r, bool* empty) {
+        *empty = true;
+        if (vend <= vbeg) return true;
+        const uint64_t cb = vbeg >> 16, ce = vend >> 16;
+        const uint32_t ub = (uint32_t)(vbeg & 0xFFFF), ue = (uint32_t)(vend & 0xFFFF);
+        uint64_t coff = cb, src = 0, next = 0;
+        uint32_t clen = 0, isize = 0;
+        r.first = cb;
+        r.uoff = ub;
+        // (every step moves forward in the file by a whole member: the walk ends with the file)
+        for (;;) {
+            if (coff + 18 > file_size) {                               // the end of the file: the data ends in front of the chunk's end
+                if (coff == cb) return true;                           // (nothing at all: the host reader finds no record either)
+                break;
+            }
+            if (!inf::member_at(file, file_size, coff, src, clen, isize, next)) return false;
+            if (coff == cb && ub > isize) return false;                // a first offset beyond the block's bytes
+            r.last = coff;
+            r.end_in_last = isize;
+            if (coff == ce) { r.end_in_last = std::min(ue, isize); break; }   // (an end inside the EOF member: its 0 bytes)
+            if (next > ce) return false;                               // the chunk's end is not on the block chain
+            if (next == ce && ue == 0) break;                          // in-block offset 0 names the block BEHIND the last one needed
+            coff = next;
+        }
+        *empty = false;
+        return true;
+    };
+    {
+        std::atomic<uint64_t> next_unit(0);
+        run_threads(nt, [&](unsigned t) {
+            for (;;) {
+                const uint64_t u0 = next_unit.fetch_add(16);
+                if (u0 >= n) return;
+                for (uint64_t u = u0; u < std::min(n, u0 + 16); ++u) {
+                    UnitRaw& U = raw_units[u];
+                    unit_home[u] = std::make_pair((uint64_t)raw_ranges[t].size(), t);
+                    const svt_fetch_unit& w = args->windows[u];
+                    const int32_t tids[2] = {w.tid_a, w.tid_b};
+                    const int64_t los[2] = {w.lo_a, w.lo_b}, his[2] = {w.hi_a, w.hi_b};
+                    if (args->breakpoints[u].svtype > SVT_SVTYPE_BND) U.preset = EW_RANGE;
+                    for (int s = 0; s < 2 && U.preset == EW_OK; ++s) {
+                        if (tids[s] < 0 || tids[s] >= (int32_t)bam->ref_names.size()) { U.preset = EW_RANGE; break; }
+                        const int64_t beg = std::max<int64_t>(los[s], 0), end = his[s];
+                        if (end <= beg) continue;
+                        for (const auto& c : fetch_chunks(*bam, tids[s], beg, end)) {
+                            OpenRange r{0, 0, 0, 0};
+                            bool empty = true;
+                            if (!chunk_range(c.first, c.second, r, &empty) || (!empty && U.n[s] == 0xFFFF)) { U.preset = EW_RANGE; break; }
+                            if (!empty) { raw_ranges[t].push_back(r); ++U.n[s]; }
+                        }
+                    }
+                    if (U.preset != EW_OK) {
+                        raw_ranges[t].resize(unit_home[u].first);
+                        U.n[0] = U.n[1] = 0;
+                    }
+                }
+            }
+        });
+    }
+
+    // ---- the blocks the ranges need, side by side: runs of the file's block chain, every block once
+    struct Need { uint64_t first, last; };
+    std::vector<Need> needs;
+    for (const auto& list : raw_ranges)
+        for (const OpenRange& r : list) needs.push_back(Need{r.first, r.last});
+    std::sort(needs.begin(), needs.end(), [](const Need& a, const Need& b) { return a.first < b.first; });
+    constexpr uint64_t kArenaLimit = 0xFFFF0000ull;                   // (build_arena: 32-bit offsets, the rest is the host reader's)
+    std::unordered_map<uint64_t, uint32_t> member_of;                 // block -> its place in plan.members
+    uint64_t total = 0;
+    for (size_t i = 0; i < needs.size();) {
+        uint64_t last = needs[i].last;
+        size_t j = i + 1;
+        while (j < needs.size() && needs[j].first <= last) { last = std::max(last, needs[j].last); ++j; }
+        OpenPlan::Span span{needs[i].first, 0, plan.compressed_bytes};
+        for (uint64_t coff = needs[i].first;;) {
+            uint64_t src = 0, next = 0;
+            uint32_t clen = 0, isize = 0;
+            if (!inf::member_at(file, file_size, coff, src, clen, isize, next)) return fail(SVT_ERR_INTERNAL, "build_arena_open: block chain changed under the walk");
+            if (total + isize <= kArenaLimit) {
+                member_of[coff] = (uint32_t)plan.members.size();
+                plan.members.push_back(inf::Member{span.at + (src - span.file_off), clen, isize, total});
+                span.bytes = next - span.file_off;
+            }
+            total += isize;
+            if (coff == last) break;
+            coff = next;
+        }
+        if (span.bytes) { plan.spans.push_back(span); plan.compressed_bytes += span.bytes; }
+        i = j;
+    }
+    plan.arena_bytes = plan.members.empty() ? 0 : plan.members.back().dst + plan.members.back().isize;
+    out.bytes.resize(plan.arena_bytes + 8);
+    out.blocks = plan.members.size();
+    out.units.resize(n);
+    for (uint64_t u = 0; u < n; ++u) {
+        UnitRaw& U = raw_units[u];
+        const auto& list = raw_ranges[unit_home[u].second];
+        const uint64_t nr = (uint64_t)U.n[0] + U.n[1];
+        const size_t mark = out.ranges.size();
+        for (uint64_t k = 0; k < nr && U.preset == EW_OK; ++k) {
+            const OpenRange& r = list[unit_home[u].first + k];
+            const auto f = member_of.find(r.first), l = member_of.find(r.last);
+            if (f == member_of.end() || l == member_of.end()) { U.preset = EW_RANGE; break; }      // beyond the arena's 4 GiB
+            const uint64_t begin = plan.members[f->second].dst + r.uoff, end = plan.members[l->second].dst + r.end_in_last;
+            if (end > kArenaLimit) { U.preset = EW_RANGE; break; }
+            // (begin > end: a first record behind the chunk's end -- nothing to walk)
+            out.ranges.push_back(Range{(uint32_t)std::min(begin, end), (uint32_t)end});
+            plan.range_members.emplace_back(f->second, l->second);
+        }
+        if (U.preset != EW_OK) { out.ranges.resize(mark); plan.range_members.resize(mark); U.n[0] = U.n[1] = 0; }
+        out.units[u] = UnitRanges{(uint32_t)mark, {U.n[0], U.n[1]}, U.preset};
+    }
+    out.ranges.push_back(Range{0, 0});
+    plan.index_s = out.build_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_begin).count();
+    return SVT_OK;
+}
+
+void inflate_open_host(const OpenPlan& plan, Arena& out, unsigned n_threads, std::vector<uint32_t>& status)
+{
+    const size_t m = plan.members.size();
+    status.assign(m, inf::INF_OK);
+    std::atomic<size_t> next(0);
+    run_threads(std::max(1u, std::min<unsigned>(n_threads, (unsigned)std::max<size_t>(m, 1))), [&](unsigned) {
+        std::unique_ptr<inf::Scratch> S(new inf::Scratch());
+        for (;;) {
+            const size_t k0 = next.fetch_add(8);
+            if (k0 >= m) return;
+            for (size_t k = k0; k < std::min(m, k0 + 8); ++k) {
+                const inf::Member& mb = plan.members[k];
+                // (Member.src counts in the uploaded spans: back to the file through the member's span)
+                auto sp = std::upper_bound(plan.spans.begin(), plan.spans.end(), mb.src, [](uint64_t v, const OpenPlan::Span& s) { return v < s.at; });
+                --sp;
+                const uint8_t* cdata = plan.file + sp->file_off + (mb.src - sp->at);
+                status[k] = inf::inflate_member<inf::HostCtx>(cdata, mb.clen, out.bytes.data() + mb.dst, mb.isize, *S);
+            }
+        }
+    });
+}
+
+uint64_t apply_member_status(const OpenPlan& plan, const std::vector<uint32_t>& status, Arena& out)
+{
+    std::vector<uint32_t> failed(status.size() + 1, 0);
+    for (size_t k = 0; k < status.size(); ++k) failed[k + 1] = failed[k] + (status[k] != inf::INF_OK ? 1u : 0u);
+    if (failed.back() == 0) return 0;
+    for (auto& U : out.units) {
+        if (U.preset != EW_OK) continue;
+        const uint32_t nr = (uint32_t)U.n[0] + U.n[1];
+        for (uint32_t k = 0; k < nr; ++k) {
+            const auto& rm = plan.range_members[U.first + k];
+            if (failed[rm.second + 1] != failed[rm.first]) { U.preset = EW_RANGE; U.n[0] = U.n[1] = 0; break; }
+        }
+    }
+    return failed.back();
+}
+
+// the members at block_off[] of `data` as inf::Member (dst from out_off); a member that is none, or whose ISIZE is not the place it
+// was given, is marked kNoMember.  Shared with svt_bgzf_inflate_device (svt_entry_inflate.h) through svt_evidence_arena.h.
+int bgzf_members(const uint8_t* data, uint64_t len, const uint64_t* block_off, uint64_t n, const uint64_t* out_off, inf::Member* members)
+{
+    if ((!data && len) || (n && (!block_off || !out_off || !members))) return fail(SVT_ERR_INVALID, "null argument");
+    for (uint64_t k = 0; k < n; ++k) {
+        if (out_off[k + 1] < out_off[k]) return fail(SVT_ERR_INVALID, "svt_bgzf_inflate: out_off must not decrease");
+        uint64_t src = 0, next = 0;
+        uint32_t clen = 0, isize = 0;
+        const bool ok = inf::member_at(data, len, block_off[k], src, clen, isize, next) && out_off[k + 1] - out_off[k] == isize;
+        members[k] = inf::Member{ok ? src : 0, ok ? clen : 0, ok ? isize : inf::kNoMember, out_off[k]};
+    }
     return SVT_OK;
 }
 
@@ -1717,14 +1922,20 @@ void svt_evidence_free(svt_evidence* e)
 }
 
 static int svt_bam_evidence_walk_host_impl(const svt_bam* bam, const svt_summarise_args* args, const svt_evidence_params* geometry,
-                                           svt_evidence* out, uint8_t* out_of_envelope, uint32_t* kept_reads)
+                                           svt_evidence* out, uint8_t* out_of_envelope, uint32_t* kept_reads, bool open_ranges)
 {
     if (!out || !out_of_envelope) return fail(SVT_ERR_INVALID, "null argument");
     out->rec_offset = nullptr;
     out->records = nullptr;
     out->skipped = nullptr;
     svt::ew::Arena arena;
-    if (const int rc = svt::ew::build_arena(bam, args, geometry, arena)) return rc;
+    if (open_ranges) {
+        svt::ew::OpenPlan plan;
+        if (const int rc = svt::ew::build_arena_open(bam, args, geometry, arena, plan)) return rc;
+        std::vector<uint32_t> member_status;
+        svt::ew::inflate_open_host(plan, arena, svt::ew::arena_threads(args, plan.members.size()), member_status);
+        svt::ew::apply_member_status(plan, member_status, arena);
+    } else if (const int rc = svt::ew::build_arena(bam, args, geometry, arena)) return rc;
     const uint64_t n = args->n_units;
     const svt::ew::Params P = arena.params(args, geometry);
     std::vector<std::vector<svt::Record4>> per(n);
@@ -1767,7 +1978,30 @@ static int svt_bam_evidence_walk_host_impl(const svt_bam* bam, const svt_summari
 int svt_bam_evidence_walk_host(const svt_bam* bam, const svt_summarise_args* args, const svt_evidence_params* geometry, svt_evidence* out,
                                uint8_t* out_of_envelope, uint32_t* kept_reads)
 {
-    return guarded([&] { return svt_bam_evidence_walk_host_impl(bam, args, geometry, out, out_of_envelope, kept_reads); });
+    return guarded([&] { return svt_bam_evidence_walk_host_impl(bam, args, geometry, out, out_of_envelope, kept_reads, false); });
+}
+
+int svt_bam_evidence_walk_open_host(const svt_bam* bam, const svt_summarise_args* args, const svt_evidence_params* geometry, svt_evidence* out,
+                                    uint8_t* out_of_envelope, uint32_t* kept_reads)
+{
+    return guarded([&] { return svt_bam_evidence_walk_host_impl(bam, args, geometry, out, out_of_envelope, kept_reads, true); });
+}
+
+int svt_bgzf_inflate_host(const uint8_t* data, uint64_t len, const uint64_t* block_off, uint64_t n, uint8_t* out, const uint64_t* out_off,
+                          uint32_t* status)
+{
+    return guarded([&]() -> int {
+        if (n && (!status || (!out && out_off && out_off[n]))) return fail(SVT_ERR_INVALID, "null argument");
+        std::vector<svt::inf::Member> members(n);
+        if (const int rc = svt::ew::bgzf_members(data, len, block_off, n, out_off, members.data())) return rc;
+        std::unique_ptr<svt::inf::Scratch> S(new svt::inf::Scratch());
+        for (uint64_t k = 0; k < n; ++k) {
+            const svt::inf::Member& m = members[k];
+            status[k] = m.isize == svt::inf::kNoMember ? (uint32_t)svt::inf::INF_MEMBER
+                                                       : svt::inf::inflate_member<svt::inf::HostCtx>(data + m.src, m.clen, out + m.dst, m.isize, *S);
+        }
+        return SVT_OK;
+    });
 }
 
 uint32_t svt_evidence_walk_capacity(int which)

@@ -66,6 +66,7 @@
 #include "svt_window_scan_kernel.h"
 #include "svt_geometry_kernel.h"
 #include "svt_evidence_kernel.h"
+#include "svt_inflate_kernel.h"
 #include "svt_evidence_arena.h"
 #include "svt_bayes_kernel.h"
 #include "svt_host_tables.h"

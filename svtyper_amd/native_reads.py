@@ -65,6 +65,19 @@ class _DeviceStats(C.Structure):
         return d
 
 
+INFLATE_REASONS = {1: "input", 2: "btype", 3: "stored", 4: "lengths", 5: "symbol", 6: "distance", 7: "output", 8: "short", 9: "member"}
+
+
+class _InflateStats(C.Structure):
+    """include/svtyper_reads.h: svt_evidence_inflate_stats"""
+    _fields_ = [("blocks_inflated", C.c_uint64), ("blocks_failed", C.c_uint64), ("compressed_bytes", C.c_uint64),
+                ("inflated_bytes", C.c_uint64), ("blocks_host_route", C.c_uint64), ("host_index_s", C.c_double),
+                ("compressed_upload_s", C.c_double), ("inflate_kernel_s", C.c_double)]
+
+    def as_dict(self) -> dict:
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 def walk_capacities() -> Dict[str, int]:
     """the fixed capacities of the evidence walk (svt_evidence_walk.h)"""
     L = _lib()
@@ -108,6 +121,14 @@ def _lib():
         L.svt_bam_evidence_device.restype = C.c_int
         L.svt_bam_evidence_device.argtypes = [C.c_void_p, C.POINTER(_Args), C.POINTER(_EvidenceParams), C.c_void_p, C.c_int, C.c_uint,
                                               C.POINTER(C.c_void_p), C.c_void_p, C.POINTER(_DeviceStats)]
+        L.svt_bam_evidence_walk_open_host.restype = C.c_int
+        L.svt_bam_evidence_walk_open_host.argtypes = L.svt_bam_evidence_walk_host.argtypes
+        L.svt_bam_evidence_device_inflate.restype = C.c_int
+        L.svt_bam_evidence_device_inflate.argtypes = L.svt_bam_evidence_device.argtypes + [C.POINTER(_InflateStats), C.c_int]
+        L.svt_bgzf_inflate_host.restype = C.c_int
+        L.svt_bgzf_inflate_host.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.svt_bgzf_inflate_device.restype = C.c_int
+        L.svt_bgzf_inflate_device.argtypes = L.svt_bgzf_inflate_host.argtypes + [C.c_int]
         L.svt_debug_batch_records.restype = C.c_int
         L.svt_debug_batch_records.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.svt_bam_scan_library.restype = C.c_int
@@ -215,9 +236,14 @@ class NativeBam:
         g = _EvidenceParams(len(lib_flank), flank, int(min_aligned), int(split_slop))
         return n, a, g, (windows, breakpoints, names, libs, flank)
 
+    def evidence_walk_open_host(self, *a, **kw):
+        """svt_bam_evidence_walk_open_host: evidence_walk_host() over the arena of inflate="device" -- laid out from BGZF headers,
+        inflated by the one-source decoder (svt_inflate.h) on the CPU, open ranges ended by the walk.  Same arguments and result."""
+        return self.evidence_walk_host(*a, _entry="svt_bam_evidence_walk_open_host", **kw)
+
     def evidence_walk_host(self, windows: np.ndarray, breakpoints: np.ndarray, read_groups: Sequence[str],
                            read_group_lib: Sequence[int], max_reads: Optional[int], count_mode: int, lib_flank: Sequence[float],
-                           min_aligned: int, split_slop: int, n_threads: int = 0):
+                           min_aligned: int, split_slop: int, n_threads: int = 0, _entry: str = "svt_bam_evidence_walk_host"):
         """svt_bam_evidence_walk_host: evidence() computed by the one-source walk (svt_evidence_walk.h) over host memory, without
         a fallback: (rec_offset, records, skipped, out_of_envelope uint8 [n] -- 0 or a WALK_REASONS key, such a unit has no
         records --, kept_reads uint32 [n])."""
@@ -227,7 +253,7 @@ class NativeBam:
         out = _Evidence()
         flagged = np.zeros(max(n, 1), np.uint8)
         kept = np.zeros(max(n, 1), np.uint32)
-        hip._check(self._L.svt_bam_evidence_walk_host(self._h, C.byref(a), C.byref(g), C.byref(out), flagged.ctypes.data, kept.ctypes.data))
+        hip._check(getattr(self._L, _entry)(self._h, C.byref(a), C.byref(g), C.byref(out), flagged.ctypes.data, kept.ctypes.data))
         try:
             off = np.ctypeslib.as_array(out.rec_offset, shape=(n + 1,)).copy()
             total = int(off[-1])
@@ -241,10 +267,15 @@ class NativeBam:
 
     def evidence_device(self, windows: np.ndarray, breakpoints: np.ndarray, read_groups: Sequence[str],
                         read_group_lib: Sequence[int], max_reads: Optional[int], count_mode: int, lib_flank: Sequence[float],
-                        min_aligned: int, split_slop: int, header, device: int = 0, flags: int = 0, n_threads: int = 0):
+                        min_aligned: int, split_slop: int, header, device: int = 0, flags: int = 0, n_threads: int = 0,
+                        inflate: str = "host", count_host_blocks: bool = False):
         """svt_bam_evidence_device: the reader stage with the walk on the GPU.  `header`: an EvidenceBatch whose units,
         libraries and weights describe the batch (its rec_offset / records are ignored).  Returns (hip.DeviceBatch resident
-        in HBM -- what DeviceBatch(EvidenceBatch(*evidence(...))) builds --, skipped uint8 [n], stats dict)."""
+        in HBM -- what DeviceBatch(EvidenceBatch(*evidence(...))) builds --, skipped uint8 [n], stats dict).
+        inflate="device" (svt_bam_evidence_device_inflate): the BGZF members are inflated on the GPU as well; the stats then
+        carry svt_evidence_inflate_stats under "inflate" (`count_host_blocks`: also count the blocks of the host-inflate route)."""
+        if inflate not in ("host", "device"):
+            raise ValueError("inflate must be 'host' or 'device'")
         n, a, g, _keep = self._walk_args(windows, breakpoints, read_groups, read_group_lib, max_reads, count_mode, lib_flank,
                                          min_aligned, split_slop, n_threads)
         if header.n_units != n:
@@ -253,6 +284,14 @@ class NativeBam:
         handle = C.c_void_p()
         skipped = np.zeros(max(n, 1), np.uint8)
         st = _DeviceStats()
+        if inflate == "device":
+            ist = _InflateStats()
+            hip._check(self._L.svt_bam_evidence_device_inflate(self._h, C.byref(a), C.byref(g), C.byref(cb), int(device), int(flags),
+                                                               C.byref(handle), skipped.ctypes.data, C.byref(st), C.byref(ist),
+                                                               1 if count_host_blocks else 0))
+            stats = st.as_dict()
+            stats["inflate"] = ist.as_dict()
+            return hip.DeviceBatch.adopt(handle, n, int(st.n_records), device), skipped[:n], stats
         hip._check(self._L.svt_bam_evidence_device(self._h, C.byref(a), C.byref(g), C.byref(cb), int(device), int(flags),
                                                    C.byref(handle), skipped.ctypes.data, C.byref(st)))
         return hip.DeviceBatch.adopt(handle, n, int(st.n_records), device), skipped[:n], st.as_dict()
@@ -316,3 +355,44 @@ def batch_records(dbatch) -> Tuple[np.ndarray, np.ndarray]:
     recs = np.zeros(int(off[-1]), RECORD_DTYPE)
     hip._check(L.svt_debug_batch_records(dbatch._h, off.ctypes.data, recs.ctypes.data if recs.size else None))
     return off, recs
+
+
+def bgzf_members(data: bytes) -> Tuple[np.ndarray, np.ndarray]:
+    """(block_off uint64 [n], out_off uint64 [n + 1]) of the BGZF members that lie side by side in `data`, from their headers and
+    trailers alone: what svt_bgzf_inflate_host / _device take.  Stops at the first bytes that are no member."""
+    offs, sizes, at = [], [0], 0
+    while at + 18 <= len(data) and data[at] == 31 and data[at + 1] == 139:
+        xlen = data[at + 10] | data[at + 11] << 8
+        bsize, i = -1, 0
+        while i + 4 <= xlen:
+            x = at + 12 + i
+            if data[x] == 66 and data[x + 1] == 67 and i + 6 <= xlen:
+                bsize = data[x + 4] | data[x + 5] << 8
+            i += 4 + (data[x + 2] | data[x + 3] << 8)
+        if bsize < 0 or at + bsize + 1 > len(data) or bsize - xlen - 19 < 0:
+            break
+        offs.append(at)
+        sizes.append(sizes[-1] + int.from_bytes(data[at + bsize - 3:at + bsize + 1], "little"))
+        at += bsize + 1
+    return np.array(offs, np.uint64), np.array(sizes, np.uint64)
+
+
+def bgzf_inflate(data: bytes, block_off: np.ndarray, out_off: np.ndarray, device: Optional[int] = None) -> Tuple[np.ndarray, np.ndarray]:
+    """svt_bgzf_inflate_host (device None) / svt_bgzf_inflate_device: the members of `data` at `block_off` inflated by the
+    one-source decoder (svt_inflate.h) to out_off[k] .. out_off[k + 1].  Returns (bytes uint8 [out_off[-1]], status uint32 [n]:
+    0 or an INFLATE_REASONS key -- the bytes of such a member are undefined)."""
+    L = _lib()
+    block_off = np.ascontiguousarray(block_off, np.uint64)
+    out_off = np.ascontiguousarray(out_off, np.uint64)
+    n = int(block_off.shape[0])
+    if out_off.shape[0] != n + 1:
+        raise ValueError("out_off must hold one entry more than block_off")
+    buf = np.frombuffer(bytes(data), np.uint8) if len(data) else np.zeros(1, np.uint8)
+    out = np.zeros(max(int(out_off[-1]), 1), np.uint8)
+    status = np.zeros(max(n, 1), np.uint32)
+    args = [buf.ctypes.data, len(data), block_off.ctypes.data, n, out.ctypes.data, out_off.ctypes.data, status.ctypes.data]
+    if device is None:
+        hip._check(L.svt_bgzf_inflate_host(*args))
+    else:
+        hip._check(L.svt_bgzf_inflate_device(*args, int(device)))
+    return out[:int(out_off[-1])], status[:n]

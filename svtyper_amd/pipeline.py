@@ -125,6 +125,16 @@ def _with_site_qual(res: Results, kw: dict) -> Results:
     return res
 
 
+def check_inflate(reader: str, inflate: str) -> str:
+    """`inflate`: where the BGZF blocks of reader="device" are inflated -- "host" (default: the reader's threads, inflated blocks go
+    over PCIe) or "device" (svt_bam_evidence_device_inflate: compressed blocks go over PCIe, svt_inflate_kernel inflates them)."""
+    if inflate not in ("host", "device"):
+        raise ValueError("inflate must be 'host' or 'device'")
+    if inflate == "device" and reader != "device":
+        raise ValueError("inflate='device' is only legal with reader='device' (got reader=%r)" % (reader,))
+    return inflate
+
+
 def resolve_reader(reader: Optional[str]) -> str:
     """`reader=None` (the drivers' default, i.e. what a caller with the reference's positional arguments gets): the C++
     reader of libsvtyper_hip.so when the library is there -- fetch, fragment assembly and the geometry predicates in its
@@ -248,7 +258,7 @@ class NativeUnitCollector:
     every (site, sample) unit and the summaries go straight to the device geometry + likelihood stages."""
 
     def __init__(self, samples: List[Sample], native_bams, split_weight: float, disc_weight: float,
-                 min_aligned: int, count_mode: int, max_reads, n_threads: int = 0, geometry: str = "reader"):
+                 min_aligned: int, count_mode: int, max_reads, n_threads: int = 0, geometry: str = "reader", inflate: str = "host"):
         """`geometry`: where the breakpoint-dependent predicates (parsers.py:785-857,1122-1215) are evaluated --
         "reader" (default): in the C++ reader's threads, which hands over 16-byte evidence records (svt_bam_evidence) for
         the canonical route of ANY engine; "device": 128-byte fragment summaries go to the device's geometry stage
@@ -257,6 +267,9 @@ class NativeUnitCollector:
         HIP engine only; units outside the walk's envelope are the host reader's).  Same records either way."""
         if geometry not in ("reader", "device", "walk"):
             raise ValueError("geometry must be 'reader', 'device' or 'walk'")
+        if inflate not in ("host", "device") or (inflate == "device" and geometry != "walk"):
+            raise ValueError("inflate must be 'host' or 'device', and 'device' is only legal with geometry='walk' (reader='device')")
+        self.inflate = inflate           # geometry="walk": "device" = the BGZF inflate on the GPU too (svt_bam_evidence_device_inflate)
         self.device_stats: dict = {}     # geometry="walk": the counters of svt_bam_evidence_device, summed over the calls
         self.geometry = geometry
         self.samples = samples
@@ -431,7 +444,8 @@ class NativeUnitCollector:
                                  self.disc_weight)
             with _READER_TURN:
                 d, _skipped, st = nbam.evidence_device(win, bps, rgs, idx, self.max_reads, self.count_mode, flank, self.min_aligned,
-                                                       SPLIT_SLOP, head, engine.device, flags, self.n_threads)
+                                                       SPLIT_SLOP, head, engine.device, flags, self.n_threads, inflate=self.inflate,
+                                                       count_host_blocks=os.environ.get("SVT_COUNT_HOST_BLOCKS", "0") == "1")
             lap("svt_bam_evidence_device")
             for key, v in st.items():
                 if isinstance(v, dict):

@@ -21,7 +21,7 @@ from . import evidence as ev
 from .bam import open_alignment_file
 from .library import Sample, setup_sample, write_sample_json
 from .pipeline import (MIN_LIB_PREVALENCE, BulkFeeder, block_chars, ChunkPipeline, NativeUnitCollector, split_lines, SampleColumnWriter, UnitCollector, add_read_to,
-                       default_engine, fetch_window, resolve_reader)
+                       default_engine, check_inflate, fetch_window, resolve_reader)
 from .results import results_to_dicts
 from .vcf import Variant, Vcf
 
@@ -128,10 +128,11 @@ def assign_genotype(variant: Variant, sample_name: str, res: dict) -> None:
 
 def sso_genotype(bam_string, vcf_in, vcf_out, min_aligned, split_weight, disc_weight, num_samp, lib_info_path,
                  debug, ref_fasta, sum_quals, max_reads, max_ci_dist, cores, batch_size, *, engine=None, geometry="host",
-                 reader=None, stats=None):
+                 reader=None, stats=None, inflate="host"):
     if vcf_in is None:
         return
     reader = resolve_reader(reader)
+    check_inflate(reader, inflate)
     full_bam_path = os.path.abspath(bam_string)
     if not (full_bam_path.endswith(".bam") or full_bam_path.endswith(".cram")):
         sys.exit("Error: %s is not a valid alignment file (*.bam or *.cram)\n" % full_bam_path)
@@ -202,7 +203,8 @@ def sso_genotype(bam_string, vcf_in, vcf_out, min_aligned, split_weight, disc_we
     if reader in ("native", "device"):      # C++ fetch + summariser (cores = its thread count); geometry in the reader's threads ("host") or on the device
         collector = NativeUnitCollector([sample], [native], split_weight, disc_weight, min_aligned,
                                         COUNT_SSO, max_reads, n_threads=cores or 0,
-                                        geometry="walk" if reader == "device" else "device" if geometry == "device" else "reader")
+                                        geometry="walk" if reader == "device" else "device" if geometry == "device" else "reader",
+                                        inflate=inflate)
     elif reader == "python":
         collector = UnitCollector([sample], split_weight, disc_weight, min_aligned, geometry)
     else:
@@ -361,6 +363,9 @@ def get_args():
                    help="BAM access + fragment assembly: the C++ threads of libsvtyper_hip.so feeding the device "
                         "geometry stage, the same with the evidence records built on the GPU (device), or the portable Python "
                         "reader (same output bytes) [native]")
+    p.add_argument("--inflate", choices=("host", "device"), default="host",
+                   help="with --reader device: BGZF blocks inflated by the reader's threads, or on the GPU from the "
+                        "compressed blocks (same output bytes) [host]")
     p.add_argument("--geometry", choices=("host", "device"), default="host",
                    help="with --reader python: breakpoint-dependent read predicates on the host or on the GPU [host]")
     args = p.parse_args()
@@ -379,13 +384,13 @@ def main():
     from . import sharded
     job = sharded.job()
     if job is None:
-        return sso_genotype(*call, geometry=args.geometry, reader=args.reader)
+        return sso_genotype(*call, geometry=args.geometry, reader=args.reader, inflate=args.inflate)
     # launched by torch.distributed.run with several ranks: one GPU each, variants sharded, one gather
     rank, world, local_rank = job
     call = call[:2] + (sharded.private_stdout(call[2]),) + call[3:]
     engine = sharded.init(local_rank)
     sharded.sso_genotype_sharded(*call, rank=rank, world=world, engine=engine, geometry=args.geometry,
-                                 reader=args.reader)
+                                 reader=args.reader, inflate=args.inflate)
     sharded.finish()
 
 

@@ -1,10 +1,13 @@
 #!/usr/bin/env python
-"""A/B of reader="native" against reader="device" in ONE process on the same inputs, interleaved (a, b, a, b, ...): the
+"""A/B/C of reader="native", reader="device" and reader="device" + inflate="device" (route name "device_inflate") in ONE process
+on the same inputs, interleaved (a, b, c, a, b, c, ...): the
 `driver_sso` input (the fixture's 212 variant lines x 100) and the `driver_classic_8bam` input (8 whole-genome-like BAMs x
 10 530 DEL lines) that bench.py's real_data legs construct.  Per route: wall time (median and range over --reps runs after one
 untimed run each), process CPU seconds per unit, and for the device route the stage split svt_bam_evidence_device reports
-(host arena = BAI lookup + inflate, upload, device walk, host fallback, batch create) summed over the run's calls.  Prints one
-JSON object.  GPU box only."""
+(host arena = BAI lookup + inflate, upload, device walk, host fallback, batch create) summed over the run's calls; for the
+device-inflate route also svt_evidence_inflate_stats (host index, compressed upload, inflate kernel, blocks inflated against the
+blocks the host-inflate route touches: SVT_COUNT_HOST_BLOCKS=1 is set for the untimed run only).  Prints one JSON object.
+GPU box only."""
 import io
 import json
 import os
@@ -31,17 +34,28 @@ class Sink(io.StringIO):
         pass
 
 
+ROUTES = ("native", "device", "device_inflate")
+
+
+def route_kw(route):
+    return dict(reader="device", inflate="device") if route == "device_inflate" else dict(reader=route)
+
+
 def measure(run, n_units):
     out = {}
     texts = {}
-    for reader in ("native", "device"):
-        texts[reader] = run(reader, {})            # untimed: first touch of the files, kernels loaded
-    out["same_bytes"] = texts["native"] == texts["device"]
-    walls = {"native": [], "device": []}
-    cpus = {"native": [], "device": []}
-    stages = []
+    first = {}
+    for reader in ROUTES:
+        os.environ["SVT_COUNT_HOST_BLOCKS"] = "1"
+        first[reader] = {}
+        texts[reader] = run(reader, first[reader])  # untimed: first touch of the files, kernels loaded
+        os.environ["SVT_COUNT_HOST_BLOCKS"] = "0"
+    out["same_bytes"] = texts["native"] == texts["device"] == texts["device_inflate"]
+    walls = {r: [] for r in ROUTES}
+    cpus = {r: [] for r in ROUTES}
+    stages, stages_inflate = [], []
     for _ in range(reps):
-        for reader in ("native", "device"):
+        for reader in ROUTES:
             stats = {}
             c0, t0 = time.process_time(), time.perf_counter()
             run(reader, stats)
@@ -49,6 +63,8 @@ def measure(run, n_units):
             cpus[reader].append((time.process_time() - c0) / n_units * 1e6)
             if reader == "device":
                 stages.append(stats["device_reader"])
+            if reader == "device_inflate":
+                stages_inflate.append(stats["device_reader"])
     for reader in walls:
         w = sorted(walls[reader])
         out[reader] = {"wall_ms_median": statistics.median(w), "wall_ms_min": w[0], "wall_ms_max": w[-1],
@@ -56,6 +72,13 @@ def measure(run, n_units):
     last = stages[-1]
     out["device_stage_ms"] = {k[:-2]: statistics.median(s[k] for s in stages) * 1e3 for k in last if k.endswith("_s")}
     out["device_counters"] = {k: last[k] for k in last if not k.endswith("_s")}
+    last = stages_inflate[-1]
+    out["device_inflate_stage_ms"] = {k[:-2]: statistics.median(s[k] for s in stages_inflate) * 1e3 for k in last if k.endswith("_s")}
+    out["device_inflate_stage_ms"].update({"inflate." + k[:-2]: statistics.median(s["inflate"][k] for s in stages_inflate) * 1e3
+                                           for k in last["inflate"] if k.endswith("_s")})
+    out["device_inflate_counters"] = {k: last[k] for k in last if not k.endswith("_s") and k != "inflate"}
+    out["device_inflate_counters"]["inflate"] = {k: v for k, v in first["device_inflate"]["device_reader"]["inflate"].items() if not k.endswith("_s")}
+    out["device_inflate_vs_device_wall_ms"] = out["device_inflate"]["wall_ms_median"] - out["device"]["wall_ms_median"]
     native_range = out["native"]["wall_ms_max"] - out["native"]["wall_ms_min"]
     gain = out["native"]["wall_ms_median"] - out["device"]["wall_ms_median"]
     out["verdict"] = ("device faster than native by more than native's own range" if gain > native_range else
@@ -70,7 +93,7 @@ if only in (None, "sso"):
     def run_sso(reader, stats):
         sink = Sink()
         singlesample.sso_genotype(os.path.join(data, "NA12878.target_loci.sorted.bam"), io.StringIO(text), sink, 20, 1, 1, 1000000,
-                                  os.path.join(data, "NA12878.bam.json"), False, None, False, 1000, 1e10, None, 1000, reader=reader, stats=stats)
+                                  os.path.join(data, "NA12878.bam.json"), False, None, False, 1000, 1e10, None, 1000, stats=stats, **route_kw(reader))
         return "".join(l for l in sink.getvalue().splitlines(True) if not l.startswith("##fileDate"))
     result["driver_sso"] = measure(run_sso, 21100)
 if only in (None, "classic"):
@@ -91,7 +114,7 @@ if only in (None, "classic"):
         def run_classic(reader, stats):
             sink = Sink()
             classic.sv_genotype(",".join(paths), io.StringIO(vtext), sink, 20, 1, 1, 1000000, libs, False, None, None, False, None, 1e10,
-                                reader=reader, stats=stats)
+                                stats=stats, **route_kw(reader))
             return "".join(l for l in sink.getvalue().splitlines(True) if not l.startswith("##fileDate"))
         result["driver_classic_8bam"] = measure(run_classic, 8 * len(vlines) * n_rep)
 print(json.dumps(result, indent=1))
