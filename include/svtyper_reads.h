@@ -109,7 +109,9 @@ void svt_evidence_free(svt_evidence* e);
  * back empty with out_of_envelope[u] = its reason (0 = inside the envelope; a unit the max_reads rule
  * skips is `skipped`, not flagged).  For every unit that is not flagged rec_offset / records / skipped
  * are those of svt_bam_evidence, byte for byte.  `kept_reads` (n_units, may be null): reads the unit
- * keeps -- what SVT_WALK_CAP_READS bounds.  Release `out` with svt_evidence_free.                    */
+ * keeps -- what SVT_WALK_CAP_READS bounds; the true number also for a unit flagged SVT_WALK_READS.
+ * A unit of more than SVT_WALK_CAP_READS_LDS kept reads is walked by the deep tier of the same source
+ * (tables from the heap, an O(n log^2 n) order).  Release `out` with svt_evidence_free.              */
 #define SVT_WALK_RANGE 2       /* a record does not fit its range of inflated bytes (truncated / corrupt
                                   BGZF or record, record > 64 KiB, window on an unknown reference)      */
 #define SVT_WALK_READS 3       /* more kept reads in the unit than SVT_WALK_CAP_READS                    */
@@ -122,12 +124,13 @@ void svt_evidence_free(svt_evidence* e);
 #define SVT_WALK_MAPQ 10       /* SA MAPQ outside 0..255                                                 */
 #define SVT_WALK_N_REASONS 11
 
-#define SVT_WALK_CAP_READS 0
+#define SVT_WALK_CAP_READS 0        /* kept reads of a unit: the bound behind which it is flagged SVT_WALK_READS (16 384) */
 #define SVT_WALK_CAP_NAME 1
 #define SVT_WALK_CAP_CIGAR 2
 #define SVT_WALK_CAP_SA_ENTRIES 3
 #define SVT_WALK_CAP_SA_BYTES 4
 #define SVT_WALK_CAP_RECORD 5
+#define SVT_WALK_CAP_READS_LDS 6    /* kept reads up to which a unit's tables are on-chip (1 024); above: the deep tier    */
 uint32_t svt_evidence_walk_capacity(int which);   /* SVT_WALK_CAP_*; 0 for an unknown one */
 
 int svt_bam_evidence_walk_host(const svt_bam* bam, const svt_summarise_args* args, const svt_evidence_params* geometry,
@@ -135,8 +138,10 @@ int svt_bam_evidence_walk_host(const svt_bam* bam, const svt_summarise_args* arg
 
 /* svt_bam_evidence_device: the reader stage with the walk on the GPU.  The host keeps the BAI lookup and the
  * BGZF inflate, uploads every inflated block once, one workgroup per unit builds the unit's records in HBM
- * (svt_evidence_kernel.h); every out-of-envelope unit is recomputed by the host reader and spliced in, so the
- * resident batch `*out` is the one svt_batch_create(svt_bam_evidence(...)) builds -- or the call fails with
+ * (svt_evidence_kernel.h): units of up to SVT_WALK_CAP_READS_LDS kept reads with their tables in LDS, units of up
+ * to SVT_WALK_CAP_READS kept reads by the deep kernel, whose tables are slices of an HBM workspace (at most 256 MiB,
+ * allocated only by a call that has such units and released with it).  Every out-of-envelope unit is recomputed by
+ * the host reader and spliced in, so the resident batch `*out` is the one svt_batch_create(svt_bam_evidence(...)) builds -- or the call fails with
  * the code and text svt_bam_evidence has for that unit.  `header`: n_units / units / n_libs / libs / weights of
  * the batch (rec_offset and records are ignored; SVT_UNIT_SKIP is set here for skipped units).  `skipped`
  * (n_units, may be null) and `stats` (may be null) are filled.  Needs a GPU.                               */
@@ -158,6 +163,16 @@ typedef struct svt_evidence_device_stats {
 int svt_bam_evidence_device(const svt_bam* bam, const svt_summarise_args* args, const svt_evidence_params* geometry,
                             const svt_evidence_batch* header, int device, unsigned flags, svt_batch** out,
                             uint8_t* skipped, svt_evidence_device_stats* stats);
+
+/* The deep tier's share of the calling thread's most recent svt_bam_evidence_device / _device_inflate call
+ * (thread-local, as svt_last_error's text; zeros before the first call and for a call without deep units).  */
+typedef struct svt_evidence_deep_stats {
+    uint64_t units_deep;        /* units walked by the deep kernel      */
+    uint64_t reads_deep;        /* kept reads of those units            */
+    uint64_t workspace_bytes;   /* size of the HBM slab                 */
+    double   deep_walk_s;       /* both deep launches, host-observed    */
+} svt_evidence_deep_stats;
+int svt_evidence_device_deep_stats(svt_evidence_deep_stats* out);
 
 /* ---- BGZF inflate by ONE piece of decoder source, and the device reader that uses it (additions to ABI 19) ----
  * svtyper_amd/csrc/svt_inflate.h decodes the raw-deflate payload of a BGZF member (stored, fixed and dynamic blocks)

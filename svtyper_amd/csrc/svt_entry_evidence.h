@@ -19,6 +19,9 @@ static int run_inflate_kernel(const uint8_t* d_src, uint64_t src_len, const inf:
     return SVT_OK;
 }
 
+// the deep tier's figures of this thread's last device-reader call (svt_evidence_device_deep_stats)
+static thread_local svt_evidence_deep_stats g_deep_stats{};
+
 // Both device readers.  `istats` == null: the host builds the arena of inflated blocks (svt_bam_evidence_device); else the host
 // lays the arena out from BGZF headers and svt_inflate_kernel fills it in HBM (svt_bam_evidence_device_inflate).  Everything
 // behind the arena -- the walk launches, the fallback, the scan, the batch -- is the same code.
@@ -27,6 +30,8 @@ static int svt_bam_evidence_device_impl(const svt_bam* bam, const svt_summarise_
                                         uint8_t* skipped_out, svt_evidence_device_stats* stats, svt_evidence_inflate_stats* istats = nullptr,
                                         bool count_host_blocks = false)
 {
+    svt_evidence_deep_stats& DS = g_deep_stats;
+    DS = svt_evidence_deep_stats{};                          // (in front of every way out: the figures are this call's, also when it fails)
     if (!bam || !args || !geometry || !header || !out) return fail(SVT_ERR_INVALID, "null argument");
     *out = nullptr;
     const uint64_t n = args->n_units;
@@ -73,6 +78,7 @@ static int svt_bam_evidence_device_impl(const svt_bam* bam, const svt_summarise_
     } d_arena{device}, d_records{device}, d_compressed{device};
     DevScratch d_members, d_member_status;
     DevScratch d_ranges, d_units, d_windows, d_bps, d_rgs, d_refs, d_blob, d_flank, d_status, d_rows, d_reads, d_off, d_src, d_src_off, d_dst_off;
+    DevScratch d_deep_unit, d_deep_status, d_deep_rows, d_deep_workspace;   // only a call with deep units allocates these
     // declared behind every device buffer, so it runs in front of their release on every way out: nothing goes back to a pool
     // while a kernel of this call may still be running
     struct StreamSync { hipStream_t s; ~StreamSync() { (void)hipStreamSynchronize(s); } } stream_sync{s};
@@ -135,19 +141,61 @@ static int svt_bam_evidence_device_impl(const svt_bam* bam, const svt_summarise_
     a.records = nullptr;
     const size_t lds = sizeof(ew::UnitScratch);
     static_assert(sizeof(ew::UnitScratch) <= 80 * 1024, "two workgroups of the evidence kernel per CU");
+    static_assert(sizeof(ew::DeepScratch) <= 64 * 1024, "the deep kernel's static LDS");
     HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&svt_evidence_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&svt_evidence_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
 
     // ---- launch 1: status and rows per unit
     t0 = now();
-    std::vector<uint32_t> status(n), rows(n);
+    std::vector<uint32_t> status(n), rows(n), reads(n);
     if (n) {
         hipLaunchKernelGGL(svt_evidence_kernel<false>, dim3((unsigned)n), dim3(kEvidenceBlock), lds, s, a);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipMemcpyAsync(status.data(), d_status.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
         HIP_TRY(hipMemcpyAsync(rows.data(), d_rows.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(reads.data(), d_reads.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
     }
     HIP_TRY(hipStreamSynchronize(s));
+
+    // ---- launch 1b: the units the LDS tier counted beyond its table, up to the deep tier's capacity, with their tables in HBM.
+    // In d_status they stay EW_READS, so the LDS tier's write pass leaves them alone; their verdicts are the deep kernel's.
+    std::vector<uint32_t> deep_unit;
+    for (uint64_t u = 0; u < n; ++u)
+        if (status[u] == ew::EW_READS && reads[u] <= ew::kMaxReadsDeep) {
+            deep_unit.push_back((uint32_t)u);
+            DS.reads_deep += reads[u];
+        }
+    const uint32_t n_deep = (uint32_t)deep_unit.size(), deep_grid = std::min(n_deep, kDeepMaxSlices);
+    EvidenceDeepArgs da{};
+    std::vector<uint32_t> deep_status(n_deep), deep_rows(n_deep);
+    if (n_deep) {
+        const auto t_deep = now();
+        DS.units_deep = n_deep;
+        DS.workspace_bytes = (uint64_t)deep_grid * ew::kDeepSliceBytes;
+        SVT_TRY(d_deep_workspace.alloc(DS.workspace_bytes));
+        SVT_TRY(d_deep_status.alloc(n_deep * sizeof(uint32_t)));
+        SVT_TRY(d_deep_rows.alloc(n_deep * sizeof(uint32_t)));
+        {
+            Stager st(s);
+            SVT_TRY(upload(d_deep_unit, deep_unit, st));
+            SVT_TRY(st.finish());
+        }
+        da.P = a.P;
+        da.n_deep = n_deep;
+        da.unit = d_deep_unit.as<uint32_t>();
+        da.status = d_deep_status.as<uint32_t>();
+        da.n_rows = d_deep_rows.as<uint32_t>();
+        da.rec_offset = d_off.as<uint64_t>();
+        da.records = nullptr;
+        da.workspace = d_deep_workspace.as<uint8_t>();
+        hipLaunchKernelGGL(svt_evidence_deep_kernel<false>, dim3(deep_grid), dim3(kEvidenceBlock), 0, s, da);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(deep_status.data(), d_deep_status.p, n_deep * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(deep_rows.data(), d_deep_rows.p, n_deep * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        for (uint32_t k = 0; k < n_deep; ++k) { status[deep_unit[k]] = deep_status[k]; rows[deep_unit[k]] = deep_rows[k]; }
+        DS.deep_walk_s = since(t_deep);
+    }
     S.device_walk_s = since(t0);
 
     // ---- host: the units outside the envelope, by the reader itself
@@ -211,6 +259,14 @@ static int svt_bam_evidence_device_impl(const svt_bam* bam, const svt_summarise_
         HIP_TRY(hipGetLastError());
     }
     HIP_TRY(hipStreamSynchronize(s));
+    if (n_deep) {                                            // (behind a sync of its own: its time is reported apart)
+        const auto t_deep = now();
+        da.records = static_cast<uint4*>(d_records.p);
+        hipLaunchKernelGGL(svt_evidence_deep_kernel<true>, dim3(deep_grid), dim3(kEvidenceBlock), 0, s, da);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipStreamSynchronize(s));
+        DS.deep_walk_s += since(t_deep);
+    }
     S.device_walk_s += since(t0);
 
     // ---- the resident batch, from the records that are already in HBM
@@ -244,6 +300,15 @@ int svt_bam_evidence_device_inflate(const svt_bam* bam, const svt_summarise_args
     return guarded([&] {
         svt_evidence_inflate_stats local{};
         return svt_bam_evidence_device_impl(bam, args, geometry, header, device, flags, out, skipped, stats, istats ? istats : &local, count_host_blocks != 0);
+    });
+}
+
+int svt_evidence_device_deep_stats(svt_evidence_deep_stats* out)
+{
+    return guarded([&]() -> int {
+        if (!out) return fail(SVT_ERR_INVALID, "null argument");
+        *out = g_deep_stats;
+        return SVT_OK;
     });
 }
 

@@ -14,14 +14,26 @@
 // the host scans the counts into rec_offset (and gives the out-of-envelope units their place), <true> walks again and writes
 // each unit's records where they belong.  The records of host-recomputed units are scattered in by svt_evidence_scatter_kernel.
 //
-// Capacities and the LDS they cost (ew::UnitScratch, 72 232 bytes: two workgroups per CU of 160 KiB; with 1 536 reads it would
-// be one):
-//   reads per unit  1 024 x 52-byte summary = 53 248   (measured with svt_bam_evidence_walk_host: the fixture's 211 units keep 617 at most; 30x units ~530 on
-//                                                       average; svtyper-sso's --max_reads 1000 is per window)
-//   batch           256 x (52-byte summary + 20 bytes of offsets / counts / verdicts) = 18 944, reused after the gather for
-//   sort + rows     1 024 x (8-byte key + three 16-bit arrays) = 14 336
+//
+// Two tiers of kept reads per unit.  svt_evidence_kernel walks every unit with its tables in LDS, up to 1 024 reads; a unit
+// with more comes out of its count pass as EW_READS with its true number of kept reads.  Those of up to 16 384 reads are walked
+// again by svt_evidence_deep_kernel, the same walk with the tables in a slice of an HBM workspace; beyond that the unit is the
+// host reader's.
+//
+// Capacities and the memory they cost:
+//                   LDS tier (ew::UnitScratch, 72 240 bytes of LDS:   deep tier (ew::DeepScratch, 24 624 bytes of LDS, and a
+//                   two workgroups per CU of 160 KiB)                 slice of ew::kDeepSliceBytes = 1 179 648 bytes of HBM)
+//   reads per unit  1 024 x 52-byte summary = 53 248  LDS             16 384 x 52 = 851 968  HBM
+//   batch           256 x (52-byte summary + 22 bytes of offsets /    256 x (52 + 24) = 19 456  LDS, reused by the sort for
+//                   counts / verdicts) = 18 944  LDS, reused for      a tile of 2 048 x (8-byte key + 32-bit read) = 24 576
+//   sort + rows     1 024 x (8-byte key + three 16-bit arrays)        16 384 x (8-byte key + three 32-bit arrays)
+//                   = 14 336  LDS                                     = 327 680  HBM
 //   name bytes      128 (compared in HBM, the cap bounds the compare), CIGAR operations 256 (walked in HBM), SA entries 8 /
-//                   1 024 bytes: none of them costs LDS
+//                   1 024 bytes: none of them costs LDS, in either tier
+// (measured with svt_bam_evidence_walk_host: the fixture's 211 units keep 617 reads at most, 30x units ~530 on average;
+// svtyper-sso's --max_reads 1000 is per window, classic svtyper has no limit by default.)
+// The workspace holds a slice per deep workgroup, at most kDeepMaxSlices = 227 of them (<= 256 MiB); the deep kernel is
+// launched with min(deep units, 227) workgroups, each taking the deep units blockIdx.x, blockIdx.x + gridDim.x, ...
 // Everything is written with ordinary vector stores from plain C++.
 #ifndef SVT_EVIDENCE_KERNEL_H
 #define SVT_EVIDENCE_KERNEL_H
@@ -58,11 +70,45 @@ __global__ __launch_bounds__(kEvidenceBlock) void svt_evidence_kernel(const Evid
     if (kWrite && (a.status[u] != ew::EW_OK || a.n_rows[u] == 0)) return;      // (the same for every lane of the workgroup)
     static_assert(sizeof(Record4) == sizeof(uint4), "a record is four words");
     Record4* out = kWrite ? reinterpret_cast<Record4*>(a.records + a.rec_offset[u]) : nullptr;
-    ew::walk_unit<EvidenceDevCtx>(a.P, u, S, out);
+    ew::walk_unit<EvidenceDevCtx>(a.P, u, S, S.tables(), out);
     if (!kWrite && threadIdx.x == 0) {
         a.status[u] = S.status;
         a.n_rows[u] = S.status == ew::EW_OK ? S.n_rows : 0u;
         a.n_reads[u] = S.n_reads;
+    }
+}
+
+// ---- the deep tier ------------------------------------------------------------------------------------------------------------
+constexpr uint64_t kDeepWorkspaceMax = 256ull << 20;
+constexpr uint32_t kDeepMaxSlices = (uint32_t)(kDeepWorkspaceMax / ew::kDeepSliceBytes);
+static_assert(kDeepMaxSlices == 227 && ew::kDeepSliceBytes % 8 == 0, "the slices of the deep workspace");
+
+struct EvidenceDeepArgs {
+    ew::Params P;
+    uint32_t n_deep;
+    const uint32_t* unit;        // per deep unit: its index in the call
+    uint32_t* status;            // per deep unit: ew::EW_* (the unit's entry in EvidenceArgs::status stays EW_READS: the LDS tier passes it by)
+    uint32_t* n_rows;            // per deep unit: records (0 unless EW_OK)
+    const uint64_t* rec_offset;  // <true>: per unit of the call, where its records go
+    uint4* records;
+    uint8_t* workspace;          // gridDim.x slices of ew::kDeepSliceBytes
+};
+
+template <bool kWrite>
+__global__ __launch_bounds__(kEvidenceBlock) void svt_evidence_deep_kernel(const EvidenceDeepArgs a)
+{
+    __shared__ ew::DeepScratch S;
+    const ew::Tables<uint32_t> T = ew::deep_tables(a.workspace + (uint64_t)blockIdx.x * ew::kDeepSliceBytes);
+    for (uint32_t k = blockIdx.x; k < a.n_deep; k += gridDim.x) {                  // (k is the same for every lane of the workgroup)
+        if (kWrite && (a.status[k] != ew::EW_OK || a.n_rows[k] == 0)) continue;
+        const uint32_t u = a.unit[k];
+        Record4* out = kWrite ? reinterpret_cast<Record4*>(a.records + a.rec_offset[u]) : nullptr;
+        ew::walk_unit<EvidenceDevCtx>(a.P, u, S, T, out);
+        if (!kWrite && threadIdx.x == 0) {
+            a.status[k] = S.status;
+            a.n_rows[k] = S.status == ew::EW_OK ? S.n_rows : 0u;    // (its kept reads are the LDS tier's count: EvidenceArgs::n_reads)
+        }
+        __syncthreads();                                                           // (S is the next unit's from here on)
     }
 }
 

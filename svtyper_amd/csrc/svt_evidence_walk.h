@@ -4,8 +4,9 @@
 // this is where the walk is proven, fuzzed and sanitised) and the device (svt_evidence_kernel.h, hipcc, one workgroup per unit).
 // What a record means -- its fixed fields, CIGAR, tags, aligned intervals, the split-read candidate -- is svt_record_rules.h,
 // the same functions the host reader's process_unit calls.  The walk's own is here: its capacities and reasons, the two passes
-// over a unit's record ranges, the fragment table as a rank sort, the rows.  No std::, no allocation, every access checked
-// against the length it was given, every loop bounded by a length or a capacity.
+// over a unit's record ranges, the fragment table behind a sort by name (a rank sort up to kMaxReads reads, sorted tiles and
+// merges in the deep tier up to kMaxReadsDeep), the rows.  No std::, no allocation, every access checked against the length
+// it was given, every loop bounded by a length or a capacity.
 //
 // The envelope.  Whatever the walk does not handle EXACTLY as the host reader does sets a reason (EW_*) for the unit and stops:
 // the caller recomputes such a unit with process_unit (svt_bam_evidence_device) or returns it empty with its reason
@@ -13,9 +14,10 @@
 // host would not have looked at still flags the unit), never less.
 //
 // Execution.  The per-unit functions are written once against a context `X`: X::lane() / X::lanes() / X::sync().  On the host
-// there is one lane and sync() is nothing; on the device the lanes are the 256 threads of the unit's workgroup and the
-// per-unit state (UnitScratch) is LDS.  Work is dealt out as `for (k = lane; k < n; k += lanes)`; what has to happen in
-// arrival order (the chain of block_size words, the running counts of the max_reads rules, slot assignment) is lane 0's.
+// there is one lane and sync() is nothing; on the device the lanes are the 256 threads of the unit's workgroup, the per-unit
+// state (UnitScratch / DeepScratch) is LDS and the deep tier's tables are a slice of HBM.  Work is dealt out as
+// `for (k = lane; k < n; k += lanes)`; what has to happen in arrival order (the chain of block_size words, the running counts
+// of the max_reads rules, slot assignment) is lane 0's.
 #ifndef SVT_EVIDENCE_WALK_H
 #define SVT_EVIDENCE_WALK_H
 
@@ -30,8 +32,14 @@ namespace ew {
 
 using namespace rr;
 
-// ---- capacities (the LDS arithmetic is beside the kernel, svt_evidence_kernel.h) ----------------------------------------
-constexpr uint32_t kMaxReads = 1024;        // kept reads of one unit (both windows, after the flag / library filters)
+// ---- capacities (the LDS arithmetic is beside the kernels, svt_evidence_kernel.h) ---------------------------------------
+// Kept reads come in two tiers of the same walk.  A unit of up to kMaxReads has its tables in UnitScratch (LDS on the device);
+// one beyond that is flagged EW_READS by that tier WITH its true number of kept reads, and up to kMaxReadsDeep it is walked
+// again with its tables in memory handed in (DeepScratch + Tables<uint32_t>: a slice of an HBM workspace on the device, the
+// heap on the host).  Behind kMaxReadsDeep the unit stays EW_READS.
+constexpr uint32_t kMaxReads = 1024;        // kept reads of one unit (both windows, after the flag / library filters): the LDS tier
+constexpr uint32_t kMaxReadsDeep = 16384;   // ... the deep tier: what a unit is flagged EW_READS behind
+constexpr uint32_t kSortTile = 2048;        // deep tier: (key, read) pairs sorted side by side in the staging area, then merged
 constexpr uint32_t kMaxName = 128;          // query-name bytes of a kept read
 constexpr uint32_t kMaxCigar = 256;         // CIGAR operations of a kept read, and of an SA entry
 constexpr uint32_t kMaxSaEntries = 8;       // ';'-separated entries of an SA tag (more than one is discarded, as by the host)
@@ -44,7 +52,7 @@ enum : uint32_t {
     EW_OK = 0,
     EW_SKIPPED = 1,          // the max_reads rule of the host reader: the unit has no records (not a flag)
     EW_RANGE = 2,            // a record does not fit its arena range / bad block_size / record too long / bad window
-    EW_READS = 3,            // more kept reads than kMaxReads
+    EW_READS = 3,            // more kept reads than the tier's capacity (S.n_reads is the true number all the same)
     EW_NAME = 4,             // query name longer than kMaxName
     EW_CIGAR = 5,            // more CIGAR operations than kMaxCigar
     EW_SA_CAP = 6,           // SA value beyond kMaxSaEntries / kMaxSaBytes
@@ -89,22 +97,76 @@ struct ReadSum {
 };
 enum : uint8_t { RS_NIV = 3, RS_REV = 4, RS_SPLIT = 8, RS_SOFT = 16, RS_SELF_LEFT = 32, RS_O_REV = 64, RS_DUP = 128 };
 
+// the staging area of kBatch chain records (`Idx`: what holds a slot of the tier's read table, all ones = none)
+template <class Idx>
+struct Batch {
+    ReadSum rs[kBatch];
+    uint32_t off[kBatch], size[kBatch], idx[kBatch], cnt[kBatch];
+    Idx slot[kBatch];
+    uint8_t ovl[kBatch], counted[kBatch], ev[kBatch], keep[kBatch];
+};
+
+// The tables of one unit, handed to the walk as pointers: `cap` summaries, keys, and three index arrays.  order[] carries the
+// read's index with its top bit marking the first read of a run of one name; rows[] / rowoff[] hold rows per run and their
+// running sum (at most one row per read, so whatever holds a read index holds them).
+template <class IdxT>
+struct Tables {
+    typedef IdxT Idx;
+    static constexpr IdxT kNoSlot = (IdxT) ~(IdxT)0;
+    static constexpr IdxT kFirst = (IdxT)((IdxT)1 << (8 * sizeof(IdxT) - 1));
+    static constexpr IdxT kIndex = (IdxT)(kFirst - 1);
+    ReadSum* reads;
+    uint64_t* key;
+    IdxT *order, *rows, *rowoff;
+    uint32_t cap;
+};
+
+// the LDS tier: everything of a unit in one block (72 240 bytes: two workgroups per CU)
 struct UnitScratch {
+    typedef uint16_t Idx;
+    static constexpr bool kDeep = false;
     ReadSum reads[kMaxReads];
     union {
-        struct {                           // while the chain is walked
-            ReadSum rs[kBatch];
-            uint32_t off[kBatch], size[kBatch], idx[kBatch], cnt[kBatch];
-            uint16_t slot[kBatch];
-            uint8_t ovl[kBatch], counted[kBatch], ev[kBatch], keep[kBatch];
-        } b;
+        Batch<uint16_t> b;                 // while the chain is walked
         struct {                           // afterwards
             uint64_t key[kMaxReads];
             uint16_t order[kMaxReads], rows[kMaxReads], rowoff[kMaxReads];
         } s;
     };
     uint32_t n_reads, n_walked, status, nb, pos, n_ovl, n_counted, lcp, n_rows, range_done, window_done;
+    SVT_HD Tables<uint16_t> tables() { return Tables<uint16_t>{reads, s.key, s.order, s.rows, s.rowoff, kMaxReads}; }
 };
+static_assert(kMaxReads <= 0x7fff && kMaxReadsDeep <= 0x7fffffffu, "a read index and the first-of-run bit share an Idx");
+static_assert(sizeof(Batch<uint16_t>) == 18944 && sizeof(UnitScratch) == 72240, "the LDS tier keeps its layout: two workgroups of the evidence kernel per CU (<= 80 KiB each)");
+
+// the deep tier: the staging area and the sort's tile only (LDS on the device); the tables are the caller's (Tables<uint32_t>)
+struct DeepScratch {
+    typedef uint32_t Idx;
+    static constexpr bool kDeep = true;
+    union {
+        Batch<uint32_t> b;                 // while the chain is walked
+        struct {                           // while the reads are ordered
+            uint64_t key[kSortTile];
+            uint32_t idx[kSortTile];
+        } t;
+    };
+    uint32_t n_reads, n_walked, status, nb, pos, n_ovl, n_counted, lcp, n_rows, range_done, window_done;
+};
+static_assert(sizeof(DeepScratch) <= 64 * 1024, "two workgroups of the deep kernel per CU");
+// the tables of the deep tier as one slice of memory: summaries, keys, order / rows / rowoff
+constexpr uint64_t kDeepSliceBytes = (uint64_t)kMaxReadsDeep * (sizeof(ReadSum) + sizeof(uint64_t) + 3 * sizeof(uint32_t));
+static_assert(sizeof(ReadSum) == 52 && kDeepSliceBytes == 1179648, "1 179 648 bytes per slice");
+SVT_HD Tables<uint32_t> deep_tables(uint8_t* slice)       // `slice`: kDeepSliceBytes, 8-byte aligned
+{
+    Tables<uint32_t> T;
+    T.reads = reinterpret_cast<ReadSum*>(slice);
+    T.key = reinterpret_cast<uint64_t*>(slice + (uint64_t)kMaxReadsDeep * sizeof(ReadSum));
+    T.order = reinterpret_cast<uint32_t*>(T.key + kMaxReadsDeep);
+    T.rows = T.order + kMaxReadsDeep;
+    T.rowoff = T.rows + kMaxReadsDeep;
+    T.cap = kMaxReadsDeep;
+    return T;
+}
 
 struct HostCtx {
     static SVT_HD uint32_t lane() { return 0; }
@@ -243,19 +305,15 @@ SVT_HD void eval_record(const Params& P, const uint8_t* d, uint32_t size, uint32
 }
 
 // ---- one unit ---------------------------------------------------------------------------------------------------------------
-template <class X>
-SVT_HD void set_status(UnitScratch& S, uint32_t st)
-{
-    if (X::lane() == 0 && S.status == EW_OK) S.status = st;
-}
-
-// the reads of one window's ranges into S.reads, in arrival order; stops with S.status set
-template <class X>
-SVT_HD void gather_window(const Params& P, UnitScratch& S, const Range* ranges, uint32_t n_ranges, int32_t wtid, int64_t lo, int64_t hi,
+// the reads of one window's ranges into T.reads, in arrival order; stops with S.status set.  Behind T.cap reads the walk goes on
+// and only counts (S.n_reads): walk_unit flags the unit once both windows are through.
+template <class X, class SC>
+SVT_HD void gather_window(const Params& P, SC& S, const Tables<typename SC::Idx>& T, const Range* ranges, uint32_t n_ranges, int32_t wtid, int64_t lo, int64_t hi,
                           int64_t near_a, int64_t near_b)
 {
     const uint32_t lane = X::lane(), lanes = X::lanes();
     const bool mode1 = P.count_mode == 1 && P.max_reads >= 0, mode0 = P.count_mode == 0 && P.max_reads >= 0;
+    typedef Tables<typename SC::Idx> Tb;
     if (lo < 0) lo = 0;                                    // (fetch clamps the window's start)
     X::sync();                                             // (every lane has read S.status on its way in)
     if (lane == 0) { S.n_ovl = 0; S.n_counted = 0; S.window_done = 0; }
@@ -306,7 +364,7 @@ SVT_HD void gather_window(const Params& P, UnitScratch& S, const Range* ranges, 
             if (lane == 0) {                               // the running counts and the slots, in arrival order
                 uint32_t n_ovl = S.n_ovl, n_counted = S.n_counted, n_reads = S.n_reads, st = EW_OK;
                 for (uint32_t k = 0; k < nb && st == EW_OK; ++k) {
-                    S.b.slot[k] = 0xffff;
+                    S.b.slot[k] = Tb::kNoSlot;
                     if (!S.b.ovl[k]) continue;
                     const int64_t i = (int64_t)n_ovl++;    // enumerate() index of the fetch
                     const uint32_t early = S.b.ev[k] & 0xF, late = S.b.ev[k] >> 4;
@@ -316,8 +374,8 @@ SVT_HD void gather_window(const Params& P, UnitScratch& S, const Range* ranges, 
                     if (!S.b.keep[k]) continue;
                     if (mode0 && i > P.max_reads) { st = EW_SKIPPED; break; }
                     if (late != EW_OK) { st = late; break; }
-                    if (n_reads >= kMaxReads) { st = EW_READS; break; }
-                    S.b.slot[k] = (uint16_t)n_reads++;
+                    if (n_reads < T.cap) S.b.slot[k] = (typename SC::Idx)n_reads;
+                    ++n_reads;
                 }
                 S.n_ovl = n_ovl;
                 S.n_counted = n_counted;
@@ -327,7 +385,7 @@ SVT_HD void gather_window(const Params& P, UnitScratch& S, const Range* ranges, 
             X::sync();
             if (S.status != EW_OK) break;
             for (uint32_t k = lane; k < nb; k += lanes)
-                if (S.b.slot[k] != 0xffff) S.reads[S.b.slot[k]] = S.b.rs[k];
+                if (S.b.slot[k] != Tb::kNoSlot) T.reads[S.b.slot[k]] = S.b.rs[k];
             X::sync();
         }
         X::sync();
@@ -362,20 +420,136 @@ SVT_HD bool same_name(const Params& P, const ReadSum& a, const ReadSum& b)
     return a.name_len == b.name_len && bytes_eq(P.arena + a.name_off, P.arena + b.name_off, a.name_len);
 }
 
-// The whole unit.  `out` == nullptr: count only.  Results: S.status, S.n_rows, S.n_reads, S.n_walked (valid on every lane
-// after the call).  `out` holds S.n_rows records in sorted(query_name) order, as process_unit emits them.
-template <class X>
-SVT_HD void walk_unit(const Params& P, uint64_t u, UnitScratch& S, Record4* out)
+// ---- the order of a unit's reads: T.order[rank] = read, by (query name, arrival) -- a total order, so every correct sort
+// gives the same permutation.  T.key holds the eight name bytes behind the common prefix; whole names are compared only
+// between equal keys.
+template <class Idx>
+SVT_HD bool read_before(const Params& P, const Tables<Idx>& T, uint64_t ka, uint32_t a, uint64_t kb, uint32_t b)
 {
+    if (ka != kb) return ka < kb;
+    const int c = name_cmp(P.arena + T.reads[a].name_off, T.reads[a].name_len, P.arena + T.reads[b].name_off, T.reads[b].name_len);
+    return c != 0 ? c < 0 : a < b;
+}
+
+// the LDS tier: rank = reads in front of this one, n * n key compares side by side
+template <class X, class Idx>
+SVT_HD void order_by_rank(const Params& P, const Tables<Idx>& T, uint32_t n)
+{
+    const uint32_t lane = X::lane(), lanes = X::lanes();
+    for (uint32_t k = lane; k < n; k += lanes) {
+        const uint64_t key = T.key[k];
+        const ReadSum& me = T.reads[k];
+        uint32_t rank = 0;
+        for (uint32_t j = 0; j < n; ++j) {
+            const uint64_t kj = T.key[j];
+            bool less;
+            if (kj != key) less = kj < key;
+            else if (j == k) less = false;
+            else {
+                const int c = name_cmp(P.arena + T.reads[j].name_off, T.reads[j].name_len, P.arena + me.name_off, me.name_len);
+                less = c != 0 ? c < 0 : j < k;
+            }
+            rank += less ? 1u : 0u;
+        }
+        T.rowoff[k] = (Idx)rank;
+    }
+    X::sync();
+    for (uint32_t k = lane; k < n; k += lanes) T.order[T.rowoff[k]] = (Idx)k;
+    X::sync();
+}
+
+// The deep tier: O(n log^2 n).  Tiles of kSortTile (key, read) pairs are sorted in the staging area (a bitonic network: pairs
+// (i, i + stride) side by side, neighbouring lanes on neighbouring pairs -- at stride 1 the 8-byte keys of a wave lie 16 bytes
+// apart, a two-way bank conflict, every other stride reads consecutive keys); the sorted tiles are merged pairwise through
+// T.order and T.rows (free until the rows are counted), every element finding its place in the other run by a binary search
+// over T.key[] of that run's reads: log2(n / kSortTile) <= 3 passes, each reads its source in order and gathers ~log2(run)
+// keys per element from a table of n * 12 bytes that stays in L2.
+constexpr uint32_t kSortPad = 0xffffffffu;                     // fills a tile behind its last pair: sorts behind every read
+template <class X>
+SVT_HD void order_deep(const Params& P, DeepScratch& S, const Tables<uint32_t>& T, uint32_t n)
+{
+    const uint32_t lane = X::lane(), lanes = X::lanes();
+    auto before = [&](uint64_t ka, uint32_t a, uint64_t kb, uint32_t b) {
+        if (a == kSortPad || b == kSortPad) return a != kSortPad;      // (pad against pad: never swapped, either way)
+        return read_before(P, T, ka, a, kb, b);
+    };
+    for (uint32_t t0 = 0; t0 < n; t0 += kSortTile) {              // (at most kMaxReadsDeep / kSortTile tiles)
+        const uint32_t m = n - t0 < kSortTile ? n - t0 : kSortTile;
+        uint32_t tile = 2;
+        while (tile < m) tile <<= 1;                               // (<= kSortTile)
+        X::sync();
+        for (uint32_t k = lane; k < tile; k += lanes) {
+            S.t.key[k] = k < m ? T.key[t0 + k] : ~0ull;
+            S.t.idx[k] = k < m ? t0 + k : kSortPad;
+        }
+        X::sync();
+        for (uint32_t size = 2; size <= tile; size <<= 1) {
+            for (uint32_t stride = size >> 1; stride > 0; stride >>= 1) {
+                for (uint32_t k = lane; k < tile / 2; k += lanes) {
+                    const uint32_t i = 2 * k - (k & (stride - 1)), j = i + stride;
+                    const uint64_t ki = S.t.key[i], kj = S.t.key[j];
+                    const uint32_t ri = S.t.idx[i], rj = S.t.idx[j];
+                    const bool up = (i & size) == 0;
+                    if (up ? before(kj, rj, ki, ri) : before(ki, ri, kj, rj)) {
+                        S.t.key[i] = kj; S.t.idx[i] = rj;
+                        S.t.key[j] = ki; S.t.idx[j] = ri;
+                    }
+                }
+                X::sync();
+            }
+        }
+        for (uint32_t k = lane; k < m; k += lanes) T.order[t0 + k] = S.t.idx[k];
+    }
+    X::sync();
+    uint32_t* src = T.order;
+    uint32_t* dst = T.rows;
+    for (uint32_t run = kSortTile; run < n; run <<= 1) {          // (at most log2(kMaxReadsDeep / kSortTile) passes)
+        for (uint32_t k = lane; k < n; k += lanes) {
+            const uint32_t base = k / (2 * run) * (2 * run);
+            const uint32_t mid = base + run < n ? base + run : n, end = base + 2 * run < n ? base + 2 * run : n;
+            const bool left = k < mid;
+            const uint32_t me = src[k];
+            const uint64_t key = T.key[me];
+            uint32_t lo = left ? mid : base, hi = left ? end : mid;   // the other run: how many of it come in front of me
+            const uint32_t first = lo;
+            for (uint32_t it = 0; it < 32 && lo < hi; ++it) {
+                const uint32_t at = lo + (hi - lo) / 2, other = src[at];
+                if (read_before(P, T, T.key[other], other, key, me)) lo = at + 1;
+                else hi = at;
+            }
+            dst[base + (k - (left ? base : mid)) + (lo - first)] = me;
+        }
+        X::sync();
+        uint32_t* const was = src;
+        src = dst;
+        dst = was;
+    }
+    if (src != T.order) {
+        for (uint32_t k = lane; k < n; k += lanes) T.order[k] = src[k];
+        X::sync();
+    }
+}
+
+// The whole unit.  `out` == nullptr: count only.  Results: S.status, S.n_rows, S.n_reads, S.n_walked (valid on every lane
+// after the call).  `out` holds S.n_rows records in sorted(query_name) order, as process_unit emits them.  `S`: UnitScratch or
+// DeepScratch; `T`: the tier's tables (UnitScratch::tables() / deep_tables()).  S.n_reads is the unit's number of kept reads
+// also when that is more than T.cap: the unit is EW_READS then.
+template <class X, class SC>
+SVT_HD void walk_unit(const Params& P, uint64_t u, SC& S, const Tables<typename SC::Idx>& T, Record4* out)
+{
+    typedef typename SC::Idx Idx;
+    typedef Tables<Idx> Tb;
     const uint32_t lane = X::lane(), lanes = X::lanes();
     const UnitRanges ur = P.units[u];
     const svt_fetch_unit w = P.windows[u];
     const svt_breakpoint bp = P.bps[u];
     if (lane == 0) { S.n_reads = 0; S.n_walked = 0; S.n_rows = 0; S.status = ur.preset; S.lcp = 0; }
     X::sync();
-    if (S.status == EW_OK) gather_window<X>(P, S, P.ranges + ur.first, ur.n[0], w.tid_a, w.lo_a, w.hi_a, bp.pos_a, bp.pos_b);
+    if (S.status == EW_OK) gather_window<X>(P, S, T, P.ranges + ur.first, ur.n[0], w.tid_a, w.lo_a, w.hi_a, bp.pos_a, bp.pos_b);
     X::sync();
-    if (S.status == EW_OK) gather_window<X>(P, S, P.ranges + ur.first + ur.n[0], ur.n[1], w.tid_b, w.lo_b, w.hi_b, bp.pos_a, bp.pos_b);
+    if (S.status == EW_OK) gather_window<X>(P, S, T, P.ranges + ur.first + ur.n[0], ur.n[1], w.tid_b, w.lo_b, w.hi_b, bp.pos_a, bp.pos_b);
+    X::sync();
+    if (lane == 0 && S.status == EW_OK && S.n_reads > T.cap) S.status = EW_READS;
     X::sync();
     if (S.status != EW_OK) return;
     const uint32_t n = S.n_reads;
@@ -383,78 +557,60 @@ SVT_HD void walk_unit(const Params& P, uint64_t u, UnitScratch& S, Record4* out)
 
     // ---- order by (query name, arrival): the common prefix once, then eight bytes behind it as the key
     {
-        uint32_t lcp = S.reads[0].name_len;
-        const uint8_t* a = P.arena + S.reads[0].name_off;
+        uint32_t lcp = T.reads[0].name_len;
+        const uint8_t* a = P.arena + T.reads[0].name_off;
         for (uint32_t k = lane; k < n; k += lanes) {
-            const uint8_t* b = P.arena + S.reads[k].name_off;
-            const uint32_t m = lcp < S.reads[k].name_len ? lcp : S.reads[k].name_len;
+            const uint8_t* b = P.arena + T.reads[k].name_off;
+            const uint32_t m = lcp < T.reads[k].name_len ? lcp : T.reads[k].name_len;
             uint32_t i = 0;
             while (i < m && a[i] == b[i]) ++i;
             lcp = i;
         }
-        S.s.rows[lane] = (uint16_t)lcp;                      // (lanes() <= kMaxReads)
+        T.rows[lane] = (Idx)lcp;                      // (lanes() <= kMaxReads: a slot per lane)
         X::sync();
         if (lane == 0) {
-            uint32_t m = S.s.rows[0];
-            for (uint32_t k = 1; k < lanes; ++k) m = S.s.rows[k] < m ? S.s.rows[k] : m;
+            uint32_t m = T.rows[0];
+            for (uint32_t k = 1; k < lanes; ++k) m = T.rows[k] < m ? T.rows[k] : m;
             S.lcp = m;
         }
         X::sync();
     }
     const uint32_t lcp = S.lcp;
     for (uint32_t k = lane; k < n; k += lanes) {
-        const uint8_t* p = P.arena + S.reads[k].name_off + lcp;
-        const uint32_t have = S.reads[k].name_len - lcp;
+        const uint8_t* p = P.arena + T.reads[k].name_off + lcp;
+        const uint32_t have = T.reads[k].name_len - lcp;
         uint64_t key = 0;
         for (uint32_t i = 0; i < 8; ++i) key = (key << 8) | (i < have ? p[i] : 0u);
-        S.s.key[k] = key;
+        T.key[k] = key;
     }
     X::sync();
-    for (uint32_t k = lane; k < n; k += lanes) {              // rank = reads in front of this one
-        const uint64_t key = S.s.key[k];
-        const ReadSum& me = S.reads[k];
-        uint32_t rank = 0;
-        for (uint32_t j = 0; j < n; ++j) {
-            const uint64_t kj = S.s.key[j];
-            bool less;
-            if (kj != key) less = kj < key;
-            else if (j == k) less = false;
-            else {
-                const int c = name_cmp(P.arena + S.reads[j].name_off, S.reads[j].name_len, P.arena + me.name_off, me.name_len);
-                less = c != 0 ? c < 0 : j < k;
-            }
-            rank += less ? 1u : 0u;
-        }
-        S.s.rowoff[k] = (uint16_t)rank;
-    }
-    X::sync();
-    for (uint32_t k = lane; k < n; k += lanes) S.s.order[S.s.rowoff[k]] = (uint16_t)k;
-    X::sync();
-    // ---- fragments: runs of one name; bit 15 of order[] marks the first read of a run
+    if constexpr (SC::kDeep) order_deep<X>(P, S, T, n);
+    else order_by_rank<X>(P, T, n);
+    // ---- fragments: runs of one name; the top bit of order[] marks the first read of a run
     for (uint32_t p = lane; p < n; p += lanes) {
-        const bool first = p == 0 || !same_name(P, S.reads[S.s.order[p] & 0x7fff], S.reads[S.s.order[p - 1] & 0x7fff]);
-        S.s.rows[p] = first ? 1 : 0;
+        const bool first = p == 0 || !same_name(P, T.reads[T.order[p] & Tb::kIndex], T.reads[T.order[p - 1] & Tb::kIndex]);
+        T.rows[p] = first ? 1 : 0;
     }
     X::sync();
     for (uint32_t p = lane; p < n; p += lanes)
-        if (S.s.rows[p]) S.s.order[p] |= 0x8000;
+        if (T.rows[p]) T.order[p] |= Tb::kFirst;
     X::sync();
     for (uint32_t p = lane; p < n; p += lanes) {              // the same (name, flag) again: dropped
-        ReadSum& me = S.reads[S.s.order[p] & 0x7fff];
+        ReadSum& me = T.reads[T.order[p] & Tb::kIndex];
         bool dup = false;
-        for (uint32_t q = p; q > 0 && !(S.s.order[q] & 0x8000) && !dup;) {
+        for (uint32_t q = p; q > 0 && !(T.order[q] & Tb::kFirst) && !dup;) {
             --q;
-            dup = S.reads[S.s.order[q] & 0x7fff].flag == me.flag;
+            dup = T.reads[T.order[q] & Tb::kIndex].flag == me.flag;
         }
         if (dup) me.bits |= RS_DUP;
     }
     X::sync();
     for (uint32_t p = lane; p < n; p += lanes) {              // rows of the fragment: max(1, ceil(primaries / 2), |seq|, |clip|)
         uint32_t rows = 0;
-        if (S.s.order[p] & 0x8000) {
+        if (T.order[p] & Tb::kFirst) {
             uint32_t np = 0, ns = 0, nc = 0;
-            for (uint32_t q = p; q < n && (q == p || !(S.s.order[q] & 0x8000)); ++q) {
-                const ReadSum& m = S.reads[S.s.order[q] & 0x7fff];
+            for (uint32_t q = p; q < n && (q == p || !(T.order[q] & Tb::kFirst)); ++q) {
+                const ReadSum& m = T.reads[T.order[q] & Tb::kIndex];
                 if (!is_primary(m)) continue;
                 ++np;
                 if (m.bits & RS_SPLIT) { if (m.bits & RS_SOFT) ++nc; else ++ns; }
@@ -464,43 +620,43 @@ SVT_HD void walk_unit(const Params& P, uint64_t u, UnitScratch& S, Record4* out)
             rows = rows < ns ? ns : rows;
             rows = rows < nc ? nc : rows;
         }
-        S.s.rows[p] = (uint16_t)rows;
+        T.rows[p] = (Idx)rows;
     }
     X::sync();
     if (lane == 0) {
         uint32_t at = 0;
-        for (uint32_t p = 0; p < n; ++p) { S.s.rowoff[p] = (uint16_t)at; at += S.s.rows[p]; }
+        for (uint32_t p = 0; p < n; ++p) { T.rowoff[p] = (Idx)at; at += T.rows[p]; }
         S.n_rows = at;
     }
     X::sync();
     if (!out) return;
     for (uint32_t p = lane; p < n; p += lanes) {
-        const uint32_t rows = S.s.rows[p];
+        const uint32_t rows = T.rows[p];
         if (!rows) continue;
         uint32_t end = p + 1;
-        while (end < n && !(S.s.order[end] & 0x8000)) ++end;
-        const uint32_t lib = S.reads[S.s.order[p] & 0x7fff].lib;        // SamFragment(read, lib): the first read's
+        while (end < n && !(T.order[end] & Tb::kFirst)) ++end;
+        const uint32_t lib = T.reads[T.order[p] & Tb::kIndex].lib;        // SamFragment(read, lib): the first read's
         uint32_t np = 0;
-        for (uint32_t q = p; q < end; ++q) np += is_primary(S.reads[S.s.order[q] & 0x7fff]) ? 1u : 0u;
+        for (uint32_t q = p; q < end; ++q) np += is_primary(T.reads[T.order[q] & Tb::kIndex]) ? 1u : 0u;
         uint32_t qp = p, qs = p, qc = p;                   // cursors: next primary / seq candidate / clip candidate
         for (uint32_t k = 0; k < rows; ++k) {
             ReadS ra = absent_read(), rb = absent_read();
             PieceS sl = absent_piece(), sr = absent_piece(), cl = absent_piece(), cr = absent_piece();
             for (int j = 0; j < 2; ++j) {
-                while (qp < end && !is_primary(S.reads[S.s.order[qp] & 0x7fff])) ++qp;
-                if (qp < end) { (j ? rb : ra) = read_of_sum(S.reads[S.s.order[qp] & 0x7fff]); ++qp; }
+                while (qp < end && !is_primary(T.reads[T.order[qp] & Tb::kIndex])) ++qp;
+                if (qp < end) { (j ? rb : ra) = read_of_sum(T.reads[T.order[qp] & Tb::kIndex]); ++qp; }
             }
             for (; qs < end; ++qs) {
-                const ReadSum& m = S.reads[S.s.order[qs] & 0x7fff];
+                const ReadSum& m = T.reads[T.order[qs] & Tb::kIndex];
                 if (is_primary(m) && (m.bits & RS_SPLIT) && !(m.bits & RS_SOFT)) { sl = piece_of_sum(m, true); sr = piece_of_sum(m, false); ++qs; break; }
             }
             for (; qc < end; ++qc) {
-                const ReadSum& m = S.reads[S.s.order[qc] & 0x7fff];
+                const ReadSum& m = T.reads[T.order[qc] & Tb::kIndex];
                 if (is_primary(m) && (m.bits & RS_SPLIT) && (m.bits & RS_SOFT)) { cl = piece_of_sum(m, true); cr = piece_of_sum(m, false); ++qc; break; }
             }
             ra.extra = lib;
             rb.extra = ((k == 0 && np == 2) ? SVT_FRAG_PAIR : 0u) | (k > 0 ? SVT_FRAG_CONTINUATION : 0u);
-            out[S.s.rowoff[p] + k] = geometry_record(ra, rb, sl, sr, cl, cr, bp, P.lib_flank[lib], P.min_aligned, P.split_slop);
+            out[T.rowoff[p] + k] = geometry_record(ra, rb, sl, sr, cl, cr, bp, P.lib_flank[lib], P.min_aligned, P.split_slop);
         }
     }
     X::sync();

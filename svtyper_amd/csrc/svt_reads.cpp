@@ -1714,7 +1714,7 @@ static int summarise_units(const svt_bam* bam, const svt_summarise_args* args, c
     *out.elements = nullptr;
     *out.skipped = nullptr;
     if (geometry && (geometry->n_libs == 0 || geometry->n_libs > 65536 || !geometry->lib_flank))
-        return fail(SVT_ERR_INVALID, "n_libs must be 1..256 with a flank per library");
+        return fail(SVT_ERR_INVALID, "n_libs must be 1..65536 with a flank per library");
     const uint64_t n = args->n_units;
     if (n && (!args->windows || !args->breakpoints)) return fail(SVT_ERR_INVALID, "null unit arrays");
     std::unordered_map<std::string, int32_t> rg_lib;
@@ -1944,14 +1944,27 @@ static int svt_bam_evidence_walk_host_impl(const svt_bam* bam, const svt_summari
     const unsigned nt = svt::ew::arena_threads(args, n);
     run_threads(nt, [&](unsigned) {
         std::unique_ptr<svt::ew::UnitScratch> S(new svt::ew::UnitScratch());
-        std::vector<svt::Record4> rows(svt::ew::kMaxReads);
+        std::vector<svt::Record4> rows(svt::ew::kMaxReads);    // (a unit has at most one row per kept read)
+        // the deep tier's scratch and tables, from the heap once this thread meets a unit that needs them
+        std::unique_ptr<svt::ew::DeepScratch> D;
+        std::unique_ptr<uint64_t[]> slice;
         for (;;) {
             const uint64_t u = next.fetch_add(1);
             if (u >= n) return;
-            svt::ew::walk_unit<svt::ew::HostCtx>(P, u, *S, rows.data());
-            status[u] = S->status;
-            if (kept_reads) kept_reads[u] = S->n_reads;
-            if (S->status == svt::ew::EW_OK) per[u].assign(rows.begin(), rows.begin() + S->n_rows);
+            svt::ew::walk_unit<svt::ew::HostCtx>(P, u, *S, S->tables(), rows.data());
+            uint32_t st = S->status, n_reads = S->n_reads, n_rows = S->n_rows;
+            if (st == svt::ew::EW_READS && n_reads <= svt::ew::kMaxReadsDeep) {
+                if (!D) {
+                    D.reset(new svt::ew::DeepScratch());
+                    slice.reset(new uint64_t[svt::ew::kDeepSliceBytes / sizeof(uint64_t)]);
+                    rows.resize(svt::ew::kMaxReadsDeep);
+                }
+                svt::ew::walk_unit<svt::ew::HostCtx>(P, u, *D, svt::ew::deep_tables(reinterpret_cast<uint8_t*>(slice.get())), rows.data());
+                st = D->status; n_reads = D->n_reads; n_rows = D->n_rows;
+            }
+            status[u] = st;
+            if (kept_reads) kept_reads[u] = n_reads;
+            if (st == svt::ew::EW_OK) per[u].assign(rows.begin(), rows.begin() + n_rows);
         }
     });
     uint64_t total = 0;
@@ -2007,12 +2020,13 @@ int svt_bgzf_inflate_host(const uint8_t* data, uint64_t len, const uint64_t* blo
 uint32_t svt_evidence_walk_capacity(int which)
 {
     switch (which) {
-    case 0: return svt::ew::kMaxReads;
-    case 1: return svt::ew::kMaxName;
-    case 2: return svt::ew::kMaxCigar;
-    case 3: return svt::ew::kMaxSaEntries;
-    case 4: return svt::ew::kMaxSaBytes;
-    case 5: return svt::ew::kMaxRecord;
+    case SVT_WALK_CAP_READS: return svt::ew::kMaxReadsDeep;
+    case SVT_WALK_CAP_READS_LDS: return svt::ew::kMaxReads;
+    case SVT_WALK_CAP_NAME: return svt::ew::kMaxName;
+    case SVT_WALK_CAP_CIGAR: return svt::ew::kMaxCigar;
+    case SVT_WALK_CAP_SA_ENTRIES: return svt::ew::kMaxSaEntries;
+    case SVT_WALK_CAP_SA_BYTES: return svt::ew::kMaxSaBytes;
+    case SVT_WALK_CAP_RECORD: return svt::ew::kMaxRecord;
     default: return 0;
     }
 }

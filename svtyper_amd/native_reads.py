@@ -48,7 +48,7 @@ class _LibraryScan(C.Structure):
 
 
 WALK_REASONS = {2: "range", 3: "reads", 4: "name", 5: "cigar", 6: "sa_cap", 7: "no_rg", 8: "unknown_rg", 9: "malformed", 10: "mapq"}
-WALK_CAPACITIES = ("reads", "name", "cigar", "sa_entries", "sa_bytes", "record")
+WALK_CAPACITIES = ("reads", "name", "cigar", "sa_entries", "sa_bytes", "record", "reads_lds")
 
 
 class _DeviceStats(C.Structure):
@@ -63,6 +63,21 @@ class _DeviceStats(C.Structure):
         d["units_host_by_reason"] = {WALK_REASONS[r]: int(self.units_host_by_reason[r]) for r in WALK_REASONS
                                      if self.units_host_by_reason[r]}
         return d
+
+
+class _DeepStats(C.Structure):
+    """include/svtyper_reads.h: svt_evidence_deep_stats"""
+    _fields_ = [("units_deep", C.c_uint64), ("reads_deep", C.c_uint64), ("workspace_bytes", C.c_uint64), ("deep_walk_s", C.c_double)]
+
+    def as_dict(self) -> dict:
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+def deep_stats() -> dict:
+    """svt_evidence_device_deep_stats: the deep tier's share of this thread's last evidence_device() call"""
+    st = _DeepStats()
+    hip._check(_lib().svt_evidence_device_deep_stats(C.byref(st)))
+    return st.as_dict()
 
 
 INFLATE_REASONS = {1: "input", 2: "btype", 3: "stored", 4: "lengths", 5: "symbol", 6: "distance", 7: "output", 8: "short", 9: "member"}
@@ -129,6 +144,8 @@ def _lib():
         L.svt_bgzf_inflate_host.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
         L.svt_bgzf_inflate_device.restype = C.c_int
         L.svt_bgzf_inflate_device.argtypes = L.svt_bgzf_inflate_host.argtypes + [C.c_int]
+        L.svt_evidence_device_deep_stats.restype = C.c_int
+        L.svt_evidence_device_deep_stats.argtypes = [C.POINTER(_DeepStats)]
         L.svt_debug_batch_records.restype = C.c_int
         L.svt_debug_batch_records.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.svt_bam_scan_library.restype = C.c_int
@@ -271,7 +288,8 @@ class NativeBam:
                         inflate: str = "host", count_host_blocks: bool = False):
         """svt_bam_evidence_device: the reader stage with the walk on the GPU.  `header`: an EvidenceBatch whose units,
         libraries and weights describe the batch (its rec_offset / records are ignored).  Returns (hip.DeviceBatch resident
-        in HBM -- what DeviceBatch(EvidenceBatch(*evidence(...))) builds --, skipped uint8 [n], stats dict).
+        in HBM -- what DeviceBatch(EvidenceBatch(*evidence(...))) builds --, skipped uint8 [n], stats dict; under "deep" the
+        share of the units of more than walk_capacities()["reads_lds"] kept reads: svt_evidence_deep_stats).
         inflate="device" (svt_bam_evidence_device_inflate): the BGZF members are inflated on the GPU as well; the stats then
         carry svt_evidence_inflate_stats under "inflate" (`count_host_blocks`: also count the blocks of the host-inflate route)."""
         if inflate not in ("host", "device"):
@@ -291,10 +309,13 @@ class NativeBam:
                                                                1 if count_host_blocks else 0))
             stats = st.as_dict()
             stats["inflate"] = ist.as_dict()
+            stats["deep"] = deep_stats()
             return hip.DeviceBatch.adopt(handle, n, int(st.n_records), device), skipped[:n], stats
         hip._check(self._L.svt_bam_evidence_device(self._h, C.byref(a), C.byref(g), C.byref(cb), int(device), int(flags),
                                                    C.byref(handle), skipped.ctypes.data, C.byref(st)))
-        return hip.DeviceBatch.adopt(handle, n, int(st.n_records), device), skipped[:n], st.as_dict()
+        stats = st.as_dict()
+        stats["deep"] = deep_stats()
+        return hip.DeviceBatch.adopt(handle, n, int(st.n_records), device), skipped[:n], stats
 
     def summarise(self, windows: np.ndarray, breakpoints: np.ndarray, read_groups: Sequence[str],
                   read_group_lib: Sequence[int], max_reads: Optional[int], count_mode: int,

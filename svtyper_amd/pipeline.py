@@ -450,8 +450,8 @@ class NativeUnitCollector:
             for key, v in st.items():
                 if isinstance(v, dict):
                     mine = self.device_stats.setdefault(key, {})
-                    for r, c in v.items():
-                        mine[r] = mine.get(r, 0) + c
+                    for r, c in v.items():      # (the deep tier's workspace is a call's own: the largest, not the sum)
+                        mine[r] = max(mine.get(r, 0), c) if r == "workspace_bytes" else mine.get(r, 0) + c
                 else:
                     self.device_stats[key] = self.device_stats.get(key, 0) + v
             with d:
