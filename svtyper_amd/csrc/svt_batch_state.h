@@ -90,6 +90,27 @@ struct DevScratch {
     template <typename T> T* as() const { return static_cast<T*>(p); }
 };
 
+// one of a stage's big buffers, from the pool svt_batch_destroy refills (svt_host_transfer.h) and back to it on the way out
+struct Pooled {
+    int device;
+    void* p = nullptr;
+    uint64_t cap = 0;
+    ~Pooled() { g_pool.put(device, p, cap); }
+    int get(uint64_t bytes, bool records = false) { return g_pool.get(device, bytes, &p, &cap, records); }
+    void* release() { void* q = p; p = nullptr; return q; }
+};
+
+// The stream of one call that owns device buffers: taken from the handle cache, synchronised on the way out, then returned.  Base of
+// the struct that holds the call's buffers, with that struct's destructor calling drain(): a destructor's body runs in front of
+// the members' destructors and a base is destroyed behind them, so on every way out the stream is idle BEFORE a buffer is freed
+// or goes back to a pool, and the stream is returned LAST.
+struct CallStream {
+    hipStream_t s = nullptr;
+    ~CallStream() { if (s) g_handles.put_stream(s); }
+    int take() { return g_handles.get_stream(&s); }
+    void drain() { if (s) (void)hipStreamSynchronize(s); }
+};
+
 template <typename T>
 int upload(T** dptr, const std::vector<T>& v, Stager& st)
 {

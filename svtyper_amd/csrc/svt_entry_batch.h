@@ -140,15 +140,7 @@ static int svt_batch_create_from_fragments_impl(const svt_fragment_batch* in, in
     SVT_TRY(g_handles.get_stream(&s));
     struct StreamGuard { hipStream_t s; ~StreamGuard() { (void)hipStreamSynchronize(s); g_handles.put_stream(s); } } sg{s};
     StageTimer tm;
-    // the two big buffers of this stage come from the pool svt_batch_destroy refills (svt_host_transfer.h)
-    struct Pooled {
-        int device;
-        void* p = nullptr;
-        uint64_t cap = 0;
-        ~Pooled() { g_pool.put(device, p, cap); }
-        int get(uint64_t bytes, bool records = false) { return g_pool.get(device, bytes, &p, &cap, records); }
-        void* release() { void* q = p; p = nullptr; return q; }
-    } d_frags{device}, d_records{device};
+    Pooled d_frags{device}, d_records{device};                // the two big buffers of this stage (svt_batch_state.h)
     DevScratch d_frag_off, d_bps, d_libs, d_err;
     {
         Stager st(s);

@@ -22,154 +22,176 @@ static int run_inflate_kernel(const uint8_t* d_src, uint64_t src_len, const inf:
 // the deep tier's figures of this thread's last device-reader call (svt_evidence_device_deep_stats)
 static thread_local svt_evidence_deep_stats g_deep_stats{};
 
-// Both device readers.  `istats` == null: the host builds the arena of inflated blocks (svt_bam_evidence_device); else the host
-// lays the arena out from BGZF headers and svt_inflate_kernel fills it in HBM (svt_bam_evidence_device_inflate).  Everything
-// behind the arena -- the walk launches, the fallback, the scan, the batch -- is the same code.
-static int svt_bam_evidence_device_impl(const svt_bam* bam, const svt_summarise_args* args, const svt_evidence_params* geometry,
-                                        const svt_evidence_batch* header, int device, unsigned flags, svt_batch** out,
-                                        uint8_t* skipped_out, svt_evidence_device_stats* stats, svt_evidence_inflate_stats* istats = nullptr,
-                                        bool count_host_blocks = false)
-{
+// Who inflates the BGZF blocks of a device-reader call
+struct EvidenceRoute {
+    svt_evidence_inflate_stats* inflate_stats = nullptr;   // null: the host (svt_bam_evidence_device); else svt_inflate_kernel, into HBM
+    bool count_host_blocks = false;                        // device inflate only: build the host route's arena too, for blocks_host_route
+    bool device_inflate() const { return inflate_stats != nullptr; }
+};
+
+// One call of a device reader: its stream, its device buffers, the kernels' arguments and what one step leaves for the next.
+// Destruction order (CallStream, svt_batch_state.h): ~EvidenceCall drains the stream, then the buffers are freed or go back to
+// their pools, then the stream is returned.
+struct EvidenceCall : CallStream {
+    const svt_bam* const bam;
+    const svt_summarise_args* const args;
+    const svt_evidence_params* const geometry;
+    const svt_evidence_batch* const header;
+    const int device;
+    const unsigned flags;
+    const EvidenceRoute route;
+    svt_evidence_device_stats& S;
     svt_evidence_deep_stats& DS = g_deep_stats;
-    DS = svt_evidence_deep_stats{};                          // (in front of every way out: the figures are this call's, also when it fails)
-    if (!bam || !args || !geometry || !header || !out) return fail(SVT_ERR_INVALID, "null argument");
-    *out = nullptr;
     const uint64_t n = args->n_units;
-    if (header->n_units != n) return fail(SVT_ERR_INVALID, "svt_bam_evidence_device: header and args differ in n_units");
-    if (n && !header->units) return fail(SVT_ERR_INVALID, "null unit arrays");
-    if (header->n_libs != geometry->n_libs) return fail(SVT_ERR_INVALID, "svt_bam_evidence_device: header and geometry differ in n_libs");
-    svt_evidence_device_stats st_local{};
-    svt_evidence_device_stats& S = stats ? *stats : st_local;
-    S = svt_evidence_device_stats{};
-    S.n_units = n;
-    auto now = [] { return std::chrono::steady_clock::now(); };
-    auto since = [&](std::chrono::steady_clock::time_point t0) { return std::chrono::duration<double>(now() - t0).count(); };
-
-    // ---- host: BAI lookup, and either inflate + arena or the arena's layout from BGZF headers
-    ew::Arena arena;
-    ew::OpenPlan plan;
-    if (istats) {
-        *istats = svt_evidence_inflate_stats{};
-        if (count_host_blocks) {
-            ew::Arena host_route;
-            SVT_TRY(ew::build_arena(bam, args, geometry, host_route));
-            istats->blocks_host_route = host_route.blocks;
-        }
-        SVT_TRY(ew::build_arena_open(bam, args, geometry, arena, plan));
-        istats->host_index_s = plan.index_s;
-        istats->blocks_inflated = plan.members.size();
-        istats->compressed_bytes = plan.compressed_bytes;
-        istats->inflated_bytes = plan.arena_bytes;
-    } else SVT_TRY(ew::build_arena(bam, args, geometry, arena));
-    S.host_arena_s = arena.build_s;
-    S.reads_walked = arena.records_in_ranges;
-    SVT_TRY(select_device(device));
-
-    hipStream_t s = nullptr;
-    SVT_TRY(g_handles.get_stream(&s));
-    struct StreamReturn { hipStream_t s; ~StreamReturn() { g_handles.put_stream(s); } } stream_return{s};
-    struct Pooled {
-        int device;
-        void* p = nullptr;
-        uint64_t cap = 0;
-        ~Pooled() { g_pool.put(device, p, cap); }
-        int get(uint64_t bytes, bool records = false) { return g_pool.get(device, bytes, &p, &cap, records); }
-        void* release() { void* q = p; p = nullptr; return q; }
-    } d_arena{device}, d_records{device}, d_compressed{device};
+    Pooled d_arena{device}, d_records{device}, d_compressed{device};
     DevScratch d_members, d_member_status;
     DevScratch d_ranges, d_units, d_windows, d_bps, d_rgs, d_refs, d_blob, d_flank, d_status, d_rows, d_reads, d_off, d_src, d_src_off, d_dst_off;
     DevScratch d_deep_unit, d_deep_status, d_deep_rows, d_deep_workspace;   // only a call with deep units allocates these
-    // declared behind every device buffer, so it runs in front of their release on every way out: nothing goes back to a pool
-    // while a kernel of this call may still be running
-    struct StreamSync { hipStream_t s; ~StreamSync() { (void)hipStreamSynchronize(s); } } stream_sync{s};
-    const std::vector<double> flank(geometry->lib_flank, geometry->lib_flank + geometry->n_libs);
-    auto t0 = now();
-    {
-        Stager st(s);
-        SVT_TRY(d_arena.get(arena.bytes.size()));
-        if (istats) {
-            // the compressed members from the mapping, the inflate kernel, the statuses; a unit over a failed member is the host's
-            SVT_TRY(d_compressed.get(plan.compressed_bytes + 8));
-            for (const auto& sp : plan.spans) SVT_TRY(st.copy(static_cast<uint8_t*>(d_compressed.p) + sp.at, plan.file + sp.file_off, sp.bytes));
-            SVT_TRY(upload(d_members, plan.members, st));
-            SVT_TRY(d_member_status.alloc(plan.members.size() * sizeof(uint32_t)));
-            SVT_TRY(st.finish());
-            istats->compressed_upload_s = since(t0);
-            const auto t_kernel = now();
-            std::vector<uint32_t> member_status;
-            SVT_TRY(run_inflate_kernel(static_cast<const uint8_t*>(d_compressed.p), plan.compressed_bytes, d_members.as<inf::Member>(), plan.members.size(),
-                                       static_cast<uint8_t*>(d_arena.p), plan.arena_bytes, d_member_status.as<uint32_t>(), member_status, s));
-            istats->inflate_kernel_s = since(t_kernel);
-            istats->blocks_failed = ew::apply_member_status(plan, member_status, arena);
-        } else SVT_TRY(st.copy(d_arena.p, arena.bytes.data(), arena.bytes.size()));
-        SVT_TRY(upload(d_ranges, arena.ranges, st));
-        SVT_TRY(upload(d_units, arena.units, st));
-        SVT_TRY(d_windows.alloc(n * sizeof(svt_fetch_unit)));
-        SVT_TRY(st.copy(d_windows.p, args->windows, n * sizeof(svt_fetch_unit)));
-        SVT_TRY(d_bps.alloc(n * sizeof(svt_breakpoint)));
-        SVT_TRY(st.copy(d_bps.p, args->breakpoints, n * sizeof(svt_breakpoint)));
-        SVT_TRY(upload(d_rgs, arena.rgs, st));
-        SVT_TRY(upload(d_refs, arena.refs, st));
-        SVT_TRY(upload(d_blob, arena.blob, st));
-        SVT_TRY(upload(d_flank, flank, st));
-        SVT_TRY(st.finish());
-        S.bytes_uploaded = (istats ? plan.compressed_bytes + plan.members.size() * sizeof(inf::Member) : arena.bytes.size()) + arena.ranges.size() * sizeof(ew::Range) + n * (sizeof(ew::UnitRanges) + sizeof(svt_fetch_unit) + sizeof(svt_breakpoint)) + arena.blob.size();
-    }
-    SVT_TRY(d_status.alloc(n * sizeof(uint32_t)));
-    SVT_TRY(d_rows.alloc(n * sizeof(uint32_t)));
-    SVT_TRY(d_reads.alloc(n * sizeof(uint32_t)));
-    SVT_TRY(d_off.alloc((n + 1) * sizeof(uint64_t)));
-    HIP_TRY(hipStreamSynchronize(s));
-    S.upload_s = since(t0);
 
+    ew::Arena arena;
+    ew::OpenPlan plan;
     EvidenceArgs a{};
-    a.P = arena.params(args, geometry);
-    a.P.arena = static_cast<const uint8_t*>(d_arena.p);
-    a.P.ranges = d_ranges.as<ew::Range>();
-    a.P.units = d_units.as<ew::UnitRanges>();
-    a.P.windows = d_windows.as<svt_fetch_unit>();
-    a.P.bps = d_bps.as<svt_breakpoint>();
-    a.P.rgs = d_rgs.as<ew::NameRef>();
-    a.P.refs = d_refs.as<ew::NameRef>();
-    a.P.blob = d_blob.as<uint8_t>();
-    a.P.lib_flank = d_flank.as<double>();
-    a.n_units = (uint32_t)n;
-    a.status = d_status.as<uint32_t>();
-    a.n_rows = d_rows.as<uint32_t>();
-    a.n_reads = d_reads.as<uint32_t>();
-    a.rec_offset = d_off.as<uint64_t>();
-    a.records = nullptr;
-    const size_t lds = sizeof(ew::UnitScratch);
-    static_assert(sizeof(ew::UnitScratch) <= 80 * 1024, "two workgroups of the evidence kernel per CU");
-    static_assert(sizeof(ew::DeepScratch) <= 64 * 1024, "the deep kernel's static LDS");
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&svt_evidence_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&svt_evidence_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-
-    // ---- launch 1: status and rows per unit
-    t0 = now();
-    std::vector<uint32_t> status(n), rows(n), reads(n);
-    if (n) {
-        hipLaunchKernelGGL(svt_evidence_kernel<false>, dim3((unsigned)n), dim3(kEvidenceBlock), lds, s, a);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(status.data(), d_status.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipMemcpyAsync(rows.data(), d_rows.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipMemcpyAsync(reads.data(), d_reads.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    }
-    HIP_TRY(hipStreamSynchronize(s));
-
-    // ---- launch 1b: the units the LDS tier counted beyond its table, up to the deep tier's capacity, with their tables in HBM.
-    // In d_status they stay EW_READS, so the LDS tier's write pass leaves them alone; their verdicts are the deep kernel's.
-    std::vector<uint32_t> deep_unit;
-    for (uint64_t u = 0; u < n; ++u)
-        if (status[u] == ew::EW_READS && reads[u] <= ew::kMaxReadsDeep) {
-            deep_unit.push_back((uint32_t)u);
-            DS.reads_deep += reads[u];
-        }
-    const uint32_t n_deep = (uint32_t)deep_unit.size(), deep_grid = std::min(n_deep, kDeepMaxSlices);
     EvidenceDeepArgs da{};
-    std::vector<uint32_t> deep_status(n_deep), deep_rows(n_deep);
-    if (n_deep) {
+    static constexpr size_t kLds = sizeof(ew::UnitScratch);
+    std::vector<uint32_t> status, rows, reads;               // per unit, from the count passes
+    std::vector<uint32_t> deep_unit;
+    uint32_t n_deep = 0, deep_grid = 0;
+    std::vector<uint64_t> host_ids, host_counts;             // the units outside the envelope, by the reader itself
+    std::vector<svt_record> host_records;
+    std::vector<uint8_t> host_skipped;
+    std::vector<uint64_t> rec_offset;
+    std::vector<svt_unit> units;
+    uint64_t n_rec = 0;
+
+    EvidenceCall(const svt_bam* bam_, const svt_summarise_args* args_, const svt_evidence_params* geometry_, const svt_evidence_batch* header_,
+                 int device_, unsigned flags_, EvidenceRoute route_, svt_evidence_device_stats& S_)
+        : bam(bam_), args(args_), geometry(geometry_), header(header_), device(device_), flags(flags_), route(route_), S(S_) {}
+    ~EvidenceCall() { drain(); }
+    static std::chrono::steady_clock::time_point now() { return std::chrono::steady_clock::now(); }
+    static double since(std::chrono::steady_clock::time_point t0) { return std::chrono::duration<double>(now() - t0).count(); }
+
+    // host: BAI lookup, and either inflate + arena or the arena's layout from BGZF headers
+    int build_arena()
+    {
+        if (route.device_inflate()) {
+            svt_evidence_inflate_stats& I = *route.inflate_stats;
+            I = svt_evidence_inflate_stats{};
+            if (route.count_host_blocks) {
+                ew::Arena host_route;
+                SVT_TRY(ew::build_arena(bam, args, geometry, host_route));
+                I.blocks_host_route = host_route.blocks;
+            }
+            SVT_TRY(ew::build_arena_open(bam, args, geometry, arena, plan));
+            I.host_index_s = plan.index_s;
+            I.blocks_inflated = plan.members.size();
+            I.compressed_bytes = plan.compressed_bytes;
+            I.inflated_bytes = plan.arena_bytes;
+        } else SVT_TRY(ew::build_arena(bam, args, geometry, arena));
+        S.host_arena_s = arena.build_s;
+        S.reads_walked = arena.records_in_ranges;
+        return SVT_OK;
+    }
+    // the arena -- its bytes, or the compressed members and the inflate kernel --, the ranges, units, names and flanks; the buffers
+    // of the count pass
+    int upload_inputs()
+    {
+        const auto t0 = now();
+        const std::vector<double> flank(geometry->lib_flank, geometry->lib_flank + geometry->n_libs);
+        {
+            Stager st(s);
+            SVT_TRY(d_arena.get(arena.bytes.size()));
+            if (route.device_inflate()) {
+                // the compressed members from the mapping, the inflate kernel, the statuses; a unit over a failed member is the host's
+                svt_evidence_inflate_stats& I = *route.inflate_stats;
+                SVT_TRY(d_compressed.get(plan.compressed_bytes + 8));
+                for (const auto& sp : plan.spans) SVT_TRY(st.copy(static_cast<uint8_t*>(d_compressed.p) + sp.at, plan.file + sp.file_off, sp.bytes));
+                SVT_TRY(upload(d_members, plan.members, st));
+                SVT_TRY(d_member_status.alloc(plan.members.size() * sizeof(uint32_t)));
+                SVT_TRY(st.finish());
+                I.compressed_upload_s = since(t0);
+                const auto t_kernel = now();
+                std::vector<uint32_t> member_status;
+                SVT_TRY(run_inflate_kernel(static_cast<const uint8_t*>(d_compressed.p), plan.compressed_bytes, d_members.as<inf::Member>(), plan.members.size(),
+                                           static_cast<uint8_t*>(d_arena.p), plan.arena_bytes, d_member_status.as<uint32_t>(), member_status, s));
+                I.inflate_kernel_s = since(t_kernel);
+                I.blocks_failed = ew::apply_member_status(plan, member_status, arena);
+            } else SVT_TRY(st.copy(d_arena.p, arena.bytes.data(), arena.bytes.size()));
+            SVT_TRY(upload(d_ranges, arena.ranges, st));
+            SVT_TRY(upload(d_units, arena.units, st));
+            SVT_TRY(d_windows.alloc(n * sizeof(svt_fetch_unit)));
+            SVT_TRY(st.copy(d_windows.p, args->windows, n * sizeof(svt_fetch_unit)));
+            SVT_TRY(d_bps.alloc(n * sizeof(svt_breakpoint)));
+            SVT_TRY(st.copy(d_bps.p, args->breakpoints, n * sizeof(svt_breakpoint)));
+            SVT_TRY(upload(d_rgs, arena.rgs, st));
+            SVT_TRY(upload(d_refs, arena.refs, st));
+            SVT_TRY(upload(d_blob, arena.blob, st));
+            SVT_TRY(upload(d_flank, flank, st));
+            SVT_TRY(st.finish());
+            S.bytes_uploaded = (route.device_inflate() ? plan.compressed_bytes + plan.members.size() * sizeof(inf::Member) : arena.bytes.size()) + arena.ranges.size() * sizeof(ew::Range) + n * (sizeof(ew::UnitRanges) + sizeof(svt_fetch_unit) + sizeof(svt_breakpoint)) + arena.blob.size();
+        }
+        SVT_TRY(d_status.alloc(n * sizeof(uint32_t)));
+        SVT_TRY(d_rows.alloc(n * sizeof(uint32_t)));
+        SVT_TRY(d_reads.alloc(n * sizeof(uint32_t)));
+        SVT_TRY(d_off.alloc((n + 1) * sizeof(uint64_t)));
+        HIP_TRY(hipStreamSynchronize(s));
+        S.upload_s = since(t0);
+        return SVT_OK;
+    }
+    // the kernels' arguments over the uploaded buffers
+    int bind_arguments()
+    {
+        a.P = arena.params(args, geometry);
+        a.P.arena = static_cast<const uint8_t*>(d_arena.p);
+        a.P.ranges = d_ranges.as<ew::Range>();
+        a.P.units = d_units.as<ew::UnitRanges>();
+        a.P.windows = d_windows.as<svt_fetch_unit>();
+        a.P.bps = d_bps.as<svt_breakpoint>();
+        a.P.rgs = d_rgs.as<ew::NameRef>();
+        a.P.refs = d_refs.as<ew::NameRef>();
+        a.P.blob = d_blob.as<uint8_t>();
+        a.P.lib_flank = d_flank.as<double>();
+        a.n_units = (uint32_t)n;
+        a.status = d_status.as<uint32_t>();
+        a.n_rows = d_rows.as<uint32_t>();
+        a.n_reads = d_reads.as<uint32_t>();
+        a.rec_offset = d_off.as<uint64_t>();
+        a.records = nullptr;
+        static_assert(sizeof(ew::UnitScratch) <= 80 * 1024, "two workgroups of the evidence kernel per CU");
+        static_assert(sizeof(ew::DeepScratch) <= 64 * 1024, "the deep kernel's static LDS");
+        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&svt_evidence_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLds));
+        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&svt_evidence_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLds));
+        return SVT_OK;
+    }
+    // launch 1: status and rows per unit
+    int count_pass()
+    {
+        status.resize(n);
+        rows.resize(n);
+        reads.resize(n);
+        if (n) {
+            hipLaunchKernelGGL(svt_evidence_kernel<false>, dim3((unsigned)n), dim3(kEvidenceBlock), kLds, s, a);
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipMemcpyAsync(status.data(), d_status.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+            HIP_TRY(hipMemcpyAsync(rows.data(), d_rows.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+            HIP_TRY(hipMemcpyAsync(reads.data(), d_reads.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        }
+        HIP_TRY(hipStreamSynchronize(s));
+        return SVT_OK;
+    }
+    // launch 1b: the units the LDS tier counted beyond its table, up to the deep tier's capacity, with their tables in HBM.
+    // In d_status they stay EW_READS, so the LDS tier's write pass leaves them alone; their verdicts are the deep kernel's.
+    int deep_count()
+    {
+        for (uint64_t u = 0; u < n; ++u)
+            if (ew::deep_tier_unit(status[u], reads[u])) {
+                deep_unit.push_back((uint32_t)u);
+                DS.reads_deep += reads[u];
+            }
+        n_deep = (uint32_t)deep_unit.size();
+        deep_grid = std::min(n_deep, kDeepMaxSlices);
+        if (!n_deep) return SVT_OK;
         const auto t_deep = now();
+        std::vector<uint32_t> deep_status(n_deep), deep_rows(n_deep);
         DS.units_deep = n_deep;
         DS.workspace_bytes = (uint64_t)deep_grid * ew::kDeepSliceBytes;
         SVT_TRY(d_deep_workspace.alloc(DS.workspace_bytes));
@@ -195,30 +217,26 @@ static int svt_bam_evidence_device_impl(const svt_bam* bam, const svt_summarise_
         HIP_TRY(hipStreamSynchronize(s));
         for (uint32_t k = 0; k < n_deep; ++k) { status[deep_unit[k]] = deep_status[k]; rows[deep_unit[k]] = deep_rows[k]; }
         DS.deep_walk_s = since(t_deep);
+        return SVT_OK;
     }
-    S.device_walk_s = since(t0);
-
-    // ---- host: the units outside the envelope, by the reader itself
-    t0 = now();
-    std::vector<uint64_t> host_ids;
-    for (uint64_t u = 0; u < n; ++u) {
-        if (status[u] >= ew::EW_N_STATUS) return fail(SVT_ERR_INTERNAL, "svt_bam_evidence_device: unit status out of range");
-        if (status[u] >= ew::EW_RANGE) {
-            host_ids.push_back(u);
-            ++S.units_host_by_reason[status[u]];
-        }
-    }
-    S.units_host = host_ids.size();
-    std::vector<svt_record> host_records;
-    std::vector<uint64_t> host_counts;
-    std::vector<uint8_t> host_skipped;
-    SVT_TRY(ew::host_units(bam, args, geometry, host_ids, host_records, host_counts, host_skipped));
-    S.host_fallback_s = since(t0);
-
-    // ---- rec_offset: the counts of both kinds of units in one scan
-    std::vector<uint64_t> rec_offset(n + 1, 0);
-    std::vector<svt_unit> units(header->units, header->units + n);
+    // host: the units outside the envelope, by the reader itself
+    int host_fallback()
     {
+        for (uint64_t u = 0; u < n; ++u) {
+            if (status[u] >= ew::EW_N_STATUS) return fail(SVT_ERR_INTERNAL, "svt_bam_evidence_device: unit status out of range");
+            if (status[u] >= ew::EW_RANGE) {
+                host_ids.push_back(u);
+                ++S.units_host_by_reason[status[u]];
+            }
+        }
+        S.units_host = host_ids.size();
+        return ew::host_units(bam, args, geometry, host_ids, host_records, host_counts, host_skipped);
+    }
+    // rec_offset: the counts of both kinds of units in one scan
+    int offset_scan(uint8_t* skipped_out)
+    {
+        rec_offset.assign(n + 1, 0);
+        units.assign(header->units, header->units + n);
         size_t hk = 0;
         for (uint64_t u = 0; u < n; ++u) {
             uint64_t cnt = rows[u];
@@ -228,61 +246,103 @@ static int svt_bam_evidence_device_impl(const svt_bam* bam, const svt_summarise_
             if (skip) { units[u].flags |= SVT_UNIT_SKIP; ++S.units_skipped; }
             if (skipped_out) skipped_out[u] = skip ? 1 : 0;
         }
+        n_rec = rec_offset[n];
+        S.n_records = n_rec;
+        if (n_rec > max_batch_records()) return fail(SVT_ERR_INVALID, "too many records in one batch (< 2^32): cut the call into fewer units");
+        return SVT_OK;
     }
-    const uint64_t n_rec = rec_offset[n];
-    S.n_records = n_rec;
-    if (n_rec > max_batch_records()) return fail(SVT_ERR_INVALID, "too many records in one batch (< 2^32): cut the call into fewer units");
-
-    // ---- launch 2: the records, where the batch wants them; then the host's units into their places
-    t0 = now();
-    SVT_TRY(d_records.get((n_rec + kBlockRecords) * sizeof(uint4), /*records=*/true));   // whole 128-byte blocks (kLayoutStream)
+    // launch 2: the records, where the batch wants them; then the host's units into their places; then the deep units' records
+    int write_pass()
     {
-        Stager st(s);
-        SVT_TRY(st.copy(d_off.p, rec_offset.data(), (n + 1) * sizeof(uint64_t)));
-        if (!host_ids.empty()) {
-            std::vector<uint64_t> src_off(host_ids.size() + 1, 0), dst_off(host_ids.size());
-            for (size_t k = 0; k < host_ids.size(); ++k) { src_off[k + 1] = src_off[k] + host_counts[k]; dst_off[k] = rec_offset[host_ids[k]]; }
-            SVT_TRY(upload(d_src, host_records, st));
-            SVT_TRY(upload(d_src_off, src_off, st));
-            SVT_TRY(upload(d_dst_off, dst_off, st));
+        SVT_TRY(d_records.get((n_rec + kBlockRecords) * sizeof(uint4), /*records=*/true));   // whole 128-byte blocks (kLayoutStream)
+        {
+            Stager st(s);
+            SVT_TRY(st.copy(d_off.p, rec_offset.data(), (n + 1) * sizeof(uint64_t)));
+            if (!host_ids.empty()) {
+                std::vector<uint64_t> src_off(host_ids.size() + 1, 0), dst_off(host_ids.size());
+                for (size_t k = 0; k < host_ids.size(); ++k) { src_off[k + 1] = src_off[k] + host_counts[k]; dst_off[k] = rec_offset[host_ids[k]]; }
+                SVT_TRY(upload(d_src, host_records, st));
+                SVT_TRY(upload(d_src_off, src_off, st));
+                SVT_TRY(upload(d_dst_off, dst_off, st));
+            }
+            SVT_TRY(st.finish());
         }
-        SVT_TRY(st.finish());
-    }
-    a.records = static_cast<uint4*>(d_records.p);
-    if (n) {
-        hipLaunchKernelGGL(svt_evidence_kernel<true>, dim3((unsigned)n), dim3(kEvidenceBlock), lds, s, a);
-        HIP_TRY(hipGetLastError());
-    }
-    if (!host_ids.empty()) {
-        hipLaunchKernelGGL(svt_evidence_scatter_kernel, dim3((unsigned)host_ids.size()), dim3(kEvidenceBlock), 0, s, d_src.as<uint4>(),
-                           d_src_off.as<uint64_t>(), d_dst_off.as<uint64_t>(), (uint32_t)host_ids.size(), static_cast<uint4*>(d_records.p));
-        HIP_TRY(hipGetLastError());
-    }
-    HIP_TRY(hipStreamSynchronize(s));
-    if (n_deep) {                                            // (behind a sync of its own: its time is reported apart)
-        const auto t_deep = now();
-        da.records = static_cast<uint4*>(d_records.p);
-        hipLaunchKernelGGL(svt_evidence_deep_kernel<true>, dim3(deep_grid), dim3(kEvidenceBlock), 0, s, da);
-        HIP_TRY(hipGetLastError());
+        a.records = static_cast<uint4*>(d_records.p);
+        if (n) {
+            hipLaunchKernelGGL(svt_evidence_kernel<true>, dim3((unsigned)n), dim3(kEvidenceBlock), kLds, s, a);
+            HIP_TRY(hipGetLastError());
+        }
+        if (!host_ids.empty()) {
+            hipLaunchKernelGGL(svt_evidence_scatter_kernel, dim3((unsigned)host_ids.size()), dim3(kEvidenceBlock), 0, s, d_src.as<uint4>(),
+                               d_src_off.as<uint64_t>(), d_dst_off.as<uint64_t>(), (uint32_t)host_ids.size(), static_cast<uint4*>(d_records.p));
+            HIP_TRY(hipGetLastError());
+        }
         HIP_TRY(hipStreamSynchronize(s));
-        DS.deep_walk_s += since(t_deep);
+        if (n_deep) {                                            // (behind a sync of its own: its time is reported apart)
+            const auto t_deep = now();
+            da.records = static_cast<uint4*>(d_records.p);
+            hipLaunchKernelGGL(svt_evidence_deep_kernel<true>, dim3(deep_grid), dim3(kEvidenceBlock), 0, s, da);
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipStreamSynchronize(s));
+            DS.deep_walk_s += since(t_deep);
+        }
+        return SVT_OK;
     }
-    S.device_walk_s += since(t0);
+    // the resident batch, from the records that are already in HBM
+    int make_batch(svt_batch** out)
+    {
+        svt_evidence_batch eb = *header;
+        eb.rec_offset = rec_offset.data();
+        eb.units = units.data();
+        eb.records = nullptr;
+        if (const char* e = evidence_error(&eb, flags, /*records_may_be_null=*/true)) return fail(SVT_ERR_INVALID, e);
+        BatchOwner b;
+        SVT_TRY(new_batch(&b, device, flags, kLayoutStream, n, n_rec));
+        const int rc = create_stream(&eb, b.get(), d_records.p, d_records.cap);
+        if (b->d_records == d_records.p) d_records.release();   // the batch owns the records now
+        SVT_TRY(rc);
+        *out = b.release();
+        return SVT_OK;
+    }
+};
 
-    // ---- the resident batch, from the records that are already in HBM
-    t0 = now();
-    svt_evidence_batch eb = *header;
-    eb.rec_offset = rec_offset.data();
-    eb.units = units.data();
-    eb.records = nullptr;
-    if (const char* e = evidence_error(&eb, flags, /*records_may_be_null=*/true)) return fail(SVT_ERR_INVALID, e);
-    BatchOwner b;
-    SVT_TRY(new_batch(&b, device, flags, kLayoutStream, n, n_rec));
-    const int rc = create_stream(&eb, b.get(), d_records.p, d_records.cap);
-    if (b->d_records == d_records.p) d_records.release();   // the batch owns the records now
-    SVT_TRY(rc);
-    S.batch_create_s = since(t0);
-    *out = b.release();
+// Both device readers: everything behind the arena -- the walk launches, the fallback, the scan, the batch -- is the same code.
+static int svt_bam_evidence_device_impl(const svt_bam* bam, const svt_summarise_args* args, const svt_evidence_params* geometry,
+                                        const svt_evidence_batch* header, int device, unsigned flags, svt_batch** out,
+                                        uint8_t* skipped_out, svt_evidence_device_stats* stats, EvidenceRoute route)
+{
+    g_deep_stats = svt_evidence_deep_stats{};                // (in front of every way out: the figures are this call's, also when it fails)
+    if (!bam || !args || !geometry || !header || !out) return fail(SVT_ERR_INVALID, "null argument");
+    *out = nullptr;
+    if (header->n_units != args->n_units) return fail(SVT_ERR_INVALID, "svt_bam_evidence_device: header and args differ in n_units");
+    if (args->n_units && !header->units) return fail(SVT_ERR_INVALID, "null unit arrays");
+    if (header->n_libs != geometry->n_libs) return fail(SVT_ERR_INVALID, "svt_bam_evidence_device: header and geometry differ in n_libs");
+    svt_evidence_device_stats st_local{};
+    svt_evidence_device_stats& S = stats ? *stats : st_local;
+    S = svt_evidence_device_stats{};
+    S.n_units = args->n_units;
+
+    EvidenceCall c(bam, args, geometry, header, device, flags, route, S);
+    SVT_TRY(c.build_arena());
+    SVT_TRY(select_device(device));
+    SVT_TRY(c.take());
+    SVT_TRY(c.upload_inputs());                              // (S.upload_s; device inflate: its kernel too)
+    SVT_TRY(c.bind_arguments());
+
+    auto t0 = c.now();
+    SVT_TRY(c.count_pass());
+    SVT_TRY(c.deep_count());
+    S.device_walk_s = c.since(t0);
+    t0 = c.now();
+    SVT_TRY(c.host_fallback());
+    S.host_fallback_s = c.since(t0);
+    SVT_TRY(c.offset_scan(skipped_out));
+    t0 = c.now();
+    SVT_TRY(c.write_pass());
+    S.device_walk_s += c.since(t0);
+    t0 = c.now();
+    SVT_TRY(c.make_batch(out));
+    S.batch_create_s = c.since(t0);
     return SVT_OK;
 }
 
@@ -290,7 +350,7 @@ int svt_bam_evidence_device(const svt_bam* bam, const svt_summarise_args* args, 
                             const svt_evidence_batch* header, int device, unsigned flags, svt_batch** out, uint8_t* skipped,
                             svt_evidence_device_stats* stats)
 {
-    return guarded([&] { return svt_bam_evidence_device_impl(bam, args, geometry, header, device, flags, out, skipped, stats); });
+    return guarded([&] { return svt_bam_evidence_device_impl(bam, args, geometry, header, device, flags, out, skipped, stats, EvidenceRoute{}); });
 }
 
 int svt_bam_evidence_device_inflate(const svt_bam* bam, const svt_summarise_args* args, const svt_evidence_params* geometry,
@@ -299,7 +359,8 @@ int svt_bam_evidence_device_inflate(const svt_bam* bam, const svt_summarise_args
 {
     return guarded([&] {
         svt_evidence_inflate_stats local{};
-        return svt_bam_evidence_device_impl(bam, args, geometry, header, device, flags, out, skipped, stats, istats ? istats : &local, count_host_blocks != 0);
+        return svt_bam_evidence_device_impl(bam, args, geometry, header, device, flags, out, skipped, stats,
+                                            EvidenceRoute{istats ? istats : &local, count_host_blocks != 0});
     });
 }
 
@@ -322,25 +383,25 @@ int svt_bgzf_inflate_device(const uint8_t* data, uint64_t len, const uint64_t* b
         SVT_TRY(ew::bgzf_members(data, len, block_off, n, out_off, members.data()));
         SVT_TRY(select_device(device));
         if (n == 0) return SVT_OK;
-        hipStream_t s = nullptr;
-        SVT_TRY(g_handles.get_stream(&s));
-        struct StreamReturn { hipStream_t s; ~StreamReturn() { g_handles.put_stream(s); } } stream_return{s};
-        DevScratch d_src, d_dst, d_members, d_status;
-        struct StreamSync { hipStream_t s; ~StreamSync() { (void)hipStreamSynchronize(s); } } stream_sync{s};
+        struct InflateCall : CallStream {                        // (destruction order: CallStream, svt_batch_state.h)
+            DevScratch d_src, d_dst, d_members, d_status;
+            ~InflateCall() { drain(); }
+        } c;
+        SVT_TRY(c.take());
         const uint64_t out_len = out_off[n];
-        SVT_TRY(d_src.alloc(len));
-        SVT_TRY(d_dst.alloc(out_len));
-        SVT_TRY(d_status.alloc(n * sizeof(uint32_t)));
+        SVT_TRY(c.d_src.alloc(len));
+        SVT_TRY(c.d_dst.alloc(out_len));
+        SVT_TRY(c.d_status.alloc(n * sizeof(uint32_t)));
         {
-            Stager st(s);
-            SVT_TRY(st.copy(d_src.p, data, len));
-            SVT_TRY(upload(d_members, members, st));
+            Stager st(c.s);
+            SVT_TRY(st.copy(c.d_src.p, data, len));
+            SVT_TRY(upload(c.d_members, members, st));
             SVT_TRY(st.finish());
         }
         std::vector<uint32_t> st_host;
-        SVT_TRY(run_inflate_kernel(d_src.as<uint8_t>(), len, d_members.as<inf::Member>(), n, d_dst.as<uint8_t>(), out_len, d_status.as<uint32_t>(), st_host, s));
+        SVT_TRY(run_inflate_kernel(c.d_src.as<uint8_t>(), len, c.d_members.as<inf::Member>(), n, c.d_dst.as<uint8_t>(), out_len, c.d_status.as<uint32_t>(), st_host, c.s));
         std::memcpy(status, st_host.data(), n * sizeof(uint32_t));
-        if (out_len) SVT_TRY(d2h_staged(out, d_dst.p, out_len, s));
+        if (out_len) SVT_TRY(d2h_staged(out, c.d_dst.p, out_len, c.s));
         return SVT_OK;
     });
 }

@@ -49,7 +49,16 @@ struct Arena {
     }
 };
 
-// BAI lookup + BGZF inflate of every unit's windows (the reader's threads and block cache); 0 or SVT_ERR_* with the error text set
+// The tier rule, for both callers of the walk: a unit that the first tier (tables of kMaxReads) left with EW_READS and its true
+// number of kept reads is walked once more with the deep tier's tables when they hold that many.
+inline bool deep_tier_unit(uint32_t status, uint32_t n_reads) { return status == EW_READS && n_reads <= kMaxReadsDeep; }
+
+// The arena comes from ONE planner in svt_reads.cpp with two routes.  Shared: the argument checks, the names, every unit's windows
+// cut into index chunks on the reader's threads, the runs of blocks the ranges need, the 32-bit limit of the arena's offsets (a
+// unit behind it is preset to EW_RANGE) and the ranges.  A route says how a chunk becomes a range and how a run is placed.
+
+// The host route.  A chunk is inflated (the reader's block cache) and its records are walked up to the one that ends the fetch;
+// a run's blocks are copied side by side.  0 or SVT_ERR_* with the error text set.
 int build_arena(const svt_bam* bam, const svt_summarise_args* args, const svt_evidence_params* geometry, Arena& out);
 
 // ---- the arena without inflating on the host (inflate = "device") ---------------------------------------------------------------
@@ -68,8 +77,9 @@ struct OpenPlan {
     double index_s = 0.0;
 };
 
-// BAI lookup and a walk over BGZF headers only: every chunk of every window becomes one range from the chunk's start to its end
-// virtual offset (an upper bound; Params.open_ranges makes the walk stop where the fetch does).  out.bytes is sized, not filled.
+// The open route.  A chunk is followed through BGZF headers only and becomes one range from its start to its end virtual offset
+// (an upper bound; Params.open_ranges makes the walk stop where the fetch does); a run's blocks become `plan.members` out of one
+// span of the file.  out.bytes is sized, not filled.
 int build_arena_open(const svt_bam* bam, const svt_summarise_args* args, const svt_evidence_params* geometry, Arena& out, OpenPlan& plan);
 // the members inflated on the CPU by svt_inflate.h, straight from the mapping into out.bytes; status[k] per member
 void inflate_open_host(const OpenPlan& plan, Arena& out, unsigned n_threads, std::vector<uint32_t>& status);
