@@ -251,6 +251,55 @@ int svt_bam_scan_library(const svt_bam* bam, uint32_t n_read_groups, const char*
                          int64_t num_samp, svt_library_scan* out);
 void svt_library_scan_free(svt_library_scan* s);
 
+/* The scans of ALL libraries of a file in one walk over its record stream (svt_library_walk.h): the stream is cut
+ * into segments at the record starts the BAI linear index knows, a segment is one wavefront's work
+ * (svt_library_kernel.h) -- or one loop's on the host --, counted, capped against the three stop rules by a prefix
+ * sum on the host, and accumulated into tables with integer atomics.  Library `l` is the read groups
+ * read_groups[sum(rg_counts[0..l-1]) ...][rg_counts[l]]; out[l] is what svt_bam_scan_library gives for them, field
+ * for field and key for key, and is released with svt_library_scan_free.  The stream is taken in rounds of at most
+ * `round_bytes` of inflated bytes (0: the default, 64 MiB; 256 KiB .. 1 GiB otherwise), cut at segment starts.
+ * Whatever lies outside the walk's envelope makes the whole call svt_bam_scan_library's, library by library:
+ * stats->host_reason says why, and an error is the host scan's own (code and text).                      */
+#define SVT_LIBSCAN_DEVICE 0        /* answered by the walk                                               */
+#define SVT_LIBSCAN_NO_INDEX 1      /* the file has no index                                              */
+#define SVT_LIBSCAN_TABLES 2        /* more libraries / read groups than the tables hold, a read group twice */
+#define SVT_LIBSCAN_RECORD 3        /* a record beyond SVT_LIBSCAN_CAP_RECORD, malformed, or across a segment's end */
+#define SVT_LIBSCAN_OVERFLOW 4      /* the overflow list is full                                          */
+#define SVT_LIBSCAN_MEMBER 5        /* a BGZF member that is none or does not inflate                     */
+#define SVT_LIBSCAN_NO_RG 6         /* a scanned record without a usable RG tag (also one behind every stop,
+                                       when it lies in a round the walk took)                             */
+#define SVT_LIBSCAN_INDEX 7         /* a linear-index offset that is not on the block chain               */
+#define SVT_LIBSCAN_N_REASONS 8
+
+typedef struct svt_library_scan_stats {
+    uint64_t rounds, segments, members_inflated, compressed_bytes, inflated_bytes, overflow_entries, records_walked;
+    double index_s, upload_s, inflate_s, count_s, accumulate_s, merge_s, host_scan_s;
+    uint32_t host_reason;     /* SVT_LIBSCAN_*: 0, or why svt_bam_scan_library answered */
+    uint32_t reserved;
+} svt_library_scan_stats;
+
+#define SVT_LIBSCAN_CAP_LIBRARIES 0
+#define SVT_LIBSCAN_CAP_READ_GROUPS 1
+#define SVT_LIBSCAN_CAP_DENSE_KEYS 2     /* K: template lengths below it have a slot per library        */
+#define SVT_LIBSCAN_CAP_OVERFLOW 3       /* entries of the overflow list (template lengths >= K)         */
+#define SVT_LIBSCAN_CAP_RECORD 4
+#define SVT_LIBSCAN_CAP_ROUND_BYTES 5    /* the default round, in bytes                                  */
+uint32_t svt_library_scan_capacity(int which);   /* SVT_LIBSCAN_CAP_*; 0 for an unknown one */
+/* The overflow list of this thread's later calls holds `entries` (0, or more than the capacity: the capacity
+ * again).  For tests of the full list.                                                                   */
+void svt_library_scan_overflow_limit(uint32_t entries);
+
+/* the whole route without a GPU: the same walk with one lane, members inflated by svt_inflate.h */
+int svt_bam_scan_libraries_walk_host(const svt_bam* bam, uint32_t n_libs, const uint32_t* rg_counts,
+                                     const char* const* read_groups, int64_t num_samp, uint64_t round_bytes,
+                                     svt_library_scan* out, svt_library_scan_stats* stats);
+/* on `device`.  inflate_on_device != 0: the host walks BGZF headers only, the compressed members are uploaded
+ * from the file mapping and svt_inflate_kernel writes the arena; 0: host threads inflate, the arena is uploaded */
+int svt_bam_scan_libraries_device(const svt_bam* bam, uint32_t n_libs, const uint32_t* rg_counts,
+                                  const char* const* read_groups, int64_t num_samp, uint64_t round_bytes,
+                                  int inflate_on_device, int device, svt_library_scan* out,
+                                  svt_library_scan_stats* stats);
+
 #ifdef __cplusplus
 }
 #endif

@@ -68,6 +68,8 @@
 #include "svt_evidence_kernel.h"
 #include "svt_inflate_kernel.h"
 #include "svt_evidence_arena.h"
+#include "svt_library_kernel.h"
+#include "svt_library_arena.h"
 #include "svt_bayes_kernel.h"
 #include "svt_host_tables.h"
 #include "svt_host_transfer.h"
@@ -174,6 +176,7 @@ void svt_batch_destroy(svt_batch* b) { free_batch(b); }
 
 #include "svt_entry_debug.h"
 #include "svt_entry_evidence.h"
+#include "svt_entry_library.h"
 #include "svt_entry_oneshot.h"
 
 }  // extern "C"

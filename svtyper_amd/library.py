@@ -161,13 +161,33 @@ class Sample:
                    lib_info[name]["mapped"], lib_info[name]["unmapped"])
 
     @classmethod
-    def from_bam(cls, bam, num_samp, min_lib_prevalence, native=None) -> "Sample":
+    def from_bam(cls, bam, num_samp, min_lib_prevalence, native=None, library_scan="host", device=0, inflate="host") -> "Sample":
+        """`library_scan`: "host" -- three scans per library, in Python or, with `native`, in the C++ reader -- or "device": one
+        segmented walk of the C++ reader's handle for all libraries at once (NativeBam.scan_libraries; "walk_host" is the same
+        walk on the CPU), its BGZF members inflated by host threads or, with inflate="device", on the GPU.  The libraries are the same
+        either way."""
         name = bam.header["RG"][0]["SM"]
         lib_dict, rg_to_lib = {}, {}
+        scans = {}
+        if library_scan != "host":
+            if library_scan not in ("device", "walk_host"):
+                raise ValueError('library_scan must be "host" or "device", not %r' % (library_scan,))
+            if native is None:
+                raise ValueError('library_scan=%r needs the C++ reader (reader="native" or "device")' % (library_scan,))
+            names = []
+            for rg in bam.header["RG"]:
+                if rg.get("LB", "") not in names:
+                    names.append(rg.get("LB", ""))
+            groups = [[rg["ID"] for rg in bam.header["RG"] if rg.get("LB", "") == lib_name] for lib_name in names]
+            scans = dict(zip(names, zip(groups, native.scan_libraries(groups, num_samp, route=library_scan, inflate=inflate, device=device))))
         for rg in bam.header["RG"]:
             lib_name = rg.get("LB", "")
             if lib_name not in lib_dict:
-                lib_dict[lib_name] = Library.from_bam(lib_name, bam, num_samp, native)
+                if lib_name in scans:
+                    readgroups, (read_length, counts, in_lib, total) = scans[lib_name]
+                    lib_dict[lib_name] = Library._from_scan(lib_name, readgroups, read_length, Counter(counts), in_lib, total, bam)
+                else:
+                    lib_dict[lib_name] = Library.from_bam(lib_name, bam, num_samp, native)
             rg_to_lib[rg["ID"]] = lib_dict[lib_name]
         return cls(name, bam, lib_dict, rg_to_lib, min_lib_prevalence, bam.mapped, bam.unmapped)
 
@@ -200,8 +220,11 @@ def write_sample_json(sample_list: List[Sample], lib_info_file):
     lib_info_file.close()
 
 
-def setup_sample(bam, lib_info: Optional[dict], num_samp: int, min_lib_prevalence: float = 1e-3, native=None) -> Sample:
-    """`native`: a native_reads.NativeBam of the same file; the library scans then run in the C++ reader."""
+def setup_sample(bam, lib_info: Optional[dict], num_samp: int, min_lib_prevalence: float = 1e-3, native=None,
+                 library_scan: str = "host", device: int = 0, inflate: str = "host") -> Sample:
+    """`native`: a native_reads.NativeBam of the same file; the library scans then run in the C++ reader.
+    `library_scan`: "host", or "device" for the one-walk scan of all libraries on GPU `device`, members inflated where `inflate` says
+    (Sample.from_bam)."""
     if lib_info is not None:
         return Sample.from_lib_info(bam, lib_info, min_lib_prevalence)
-    return Sample.from_bam(bam, num_samp, min_lib_prevalence, native)
+    return Sample.from_bam(bam, num_samp, min_lib_prevalence, native, library_scan, device, inflate)

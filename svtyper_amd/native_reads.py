@@ -47,6 +47,35 @@ class _LibraryScan(C.Structure):
                 ("hist_keys", C.POINTER(C.c_int64)), ("hist_counts", C.POINTER(C.c_uint64))]
 
 
+LIBSCAN_REASONS = {0: None, 1: "no_index", 2: "tables", 3: "record", 4: "overflow", 5: "member", 6: "no_rg", 7: "index"}
+LIBSCAN_CAPACITIES = ("libraries", "read_groups", "dense_keys", "overflow", "record", "round_bytes")
+
+
+class _LibraryScanStats(C.Structure):
+    """include/svtyper_reads.h: svt_library_scan_stats"""
+    _fields_ = [("rounds", C.c_uint64), ("segments", C.c_uint64), ("members_inflated", C.c_uint64), ("compressed_bytes", C.c_uint64),
+                ("inflated_bytes", C.c_uint64), ("overflow_entries", C.c_uint64), ("records_walked", C.c_uint64),
+                ("index_s", C.c_double), ("upload_s", C.c_double), ("inflate_s", C.c_double), ("count_s", C.c_double),
+                ("accumulate_s", C.c_double), ("merge_s", C.c_double), ("host_scan_s", C.c_double),
+                ("host_reason", C.c_uint32), ("reserved", C.c_uint32)]
+
+    def as_dict(self) -> dict:
+        d = {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
+        d["host_reason"] = LIBSCAN_REASONS.get(int(self.host_reason), int(self.host_reason))
+        return d
+
+
+def library_scan_capacities() -> Dict[str, int]:
+    """the fixed capacities of the library walk (svt_library_walk.h)"""
+    L = _lib()
+    return {name: int(L.svt_library_scan_capacity(k)) for k, name in enumerate(LIBSCAN_CAPACITIES)}
+
+
+def library_scan_overflow_limit(entries: int) -> None:
+    """svt_library_scan_overflow_limit: a smaller overflow list for this thread's later scans (0: the capacity again)"""
+    _lib().svt_library_scan_overflow_limit(int(entries))
+
+
 WALK_REASONS = {2: "range", 3: "reads", 4: "name", 5: "cigar", 6: "sa_cap", 7: "no_rg", 8: "unknown_rg", 9: "malformed", 10: "mapq"}
 WALK_CAPACITIES = ("reads", "name", "cigar", "sa_entries", "sa_bytes", "record", "reads_lds")
 
@@ -152,6 +181,16 @@ def _lib():
         L.svt_bam_scan_library.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_char_p), C.c_int64, C.POINTER(_LibraryScan)]
         L.svt_library_scan_free.restype = None
         L.svt_library_scan_free.argtypes = [C.POINTER(_LibraryScan)]
+        L.svt_library_scan_capacity.restype = C.c_uint32
+        L.svt_library_scan_capacity.argtypes = [C.c_int]
+        L.svt_library_scan_overflow_limit.restype = None
+        L.svt_library_scan_overflow_limit.argtypes = [C.c_uint32]
+        L.svt_bam_scan_libraries_walk_host.restype = C.c_int
+        L.svt_bam_scan_libraries_walk_host.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_char_p), C.c_int64,
+                                                       C.c_uint64, C.POINTER(_LibraryScan), C.POINTER(_LibraryScanStats)]
+        L.svt_bam_scan_libraries_device.restype = C.c_int
+        L.svt_bam_scan_libraries_device.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_char_p), C.c_int64,
+                                                    C.c_uint64, C.c_int, C.c_int, C.POINTER(_LibraryScan), C.POINTER(_LibraryScanStats)]
         _declared = True
     return L
 
@@ -205,6 +244,44 @@ class NativeBam:
             return int(out.read_length), dict(zip(keys, counts)), int(out.in_lib), int(out.total)
         finally:
             self._L.svt_library_scan_free(C.byref(out))
+
+    def scan_libraries(self, read_groups: Sequence[Sequence[str]], num_samp: int, route: str = "device", inflate: str = "device",
+                       device: int = 0, round_bytes: int = 0, ordered: bool = False):
+        """scan_library() for all libraries of the file in one segmented walk (svt_library_walk.h): a list with one
+        (read_length, {template_length: count}, in_lib, total) per entry of `read_groups`, the dicts in the order of the keys'
+        first occurrence.  route="device": svt_bam_scan_libraries_device, with the BGZF members inflated on the GPU
+        (inflate="device") or by host threads (inflate="host"); route="walk_host": the same walk on the CPU.  Whatever is
+        outside the walk's envelope is answered by the host scan (self.library_scan_stats["host_reason"] says why).
+        `ordered`: the histograms as lists of (key, count) instead of dicts."""
+        if route not in ("device", "walk_host"):
+            raise ValueError('route must be "device" or "walk_host", not %r' % (route,))
+        if inflate not in ("device", "host"):
+            raise ValueError('inflate must be "device" or "host", not %r' % (inflate,))
+        n_libs = len(read_groups)
+        flat = [rg.encode() for lib in read_groups for rg in lib]
+        names = (C.c_char_p * max(1, len(flat)))(*flat)
+        counts = (C.c_uint32 * max(1, n_libs))(*[len(lib) for lib in read_groups])
+        out = (_LibraryScan * max(1, n_libs))()
+        st = _LibraryScanStats()
+        if route == "walk_host":
+            rc = self._L.svt_bam_scan_libraries_walk_host(self._h, n_libs, counts, names, int(num_samp), int(round_bytes), out, C.byref(st))
+        else:
+            rc = self._L.svt_bam_scan_libraries_device(self._h, n_libs, counts, names, int(num_samp), int(round_bytes),
+                                                       1 if inflate == "device" else 0, int(device), out, C.byref(st))
+        self.library_scan_stats = st.as_dict()
+        hip._check(rc)
+        try:
+            result = []
+            for l in range(n_libs):
+                n = int(out[l].n_hist)
+                keys = np.ctypeslib.as_array(out[l].hist_keys, shape=(max(n, 1),))[:n].tolist()
+                cnts = np.ctypeslib.as_array(out[l].hist_counts, shape=(max(n, 1),))[:n].tolist()
+                hist = list(zip(keys, cnts)) if ordered else dict(zip(keys, cnts))
+                result.append((int(out[l].read_length), hist, int(out[l].in_lib), int(out[l].total)))
+            return result
+        finally:
+            for l in range(n_libs):
+                self._L.svt_library_scan_free(C.byref(out[l]))
 
     def evidence(self, windows: np.ndarray, breakpoints: np.ndarray, read_groups: Sequence[str],
                  read_group_lib: Sequence[int], max_reads: Optional[int], count_mode: int, lib_flank: Sequence[float],

@@ -135,6 +135,18 @@ def check_inflate(reader: str, inflate: str) -> str:
     return inflate
 
 
+def check_library_scan(reader: str, library_scan: str) -> str:
+    """`library_scan`: who builds the libraries of a BAM that comes without a library file -- "host" (default: three scans per
+    library) or "device" (svt_bam_scan_libraries_device: one segmented walk on the GPU for all libraries; its BGZF members are inflated
+    where `inflate` says -- by host threads unless reader="device", inflate="device").
+    "device" goes through the C++ reader's handle, so it is only legal with reader="native" or reader="device"."""
+    if library_scan not in ("host", "device"):
+        raise ValueError("library_scan must be 'host' or 'device'")
+    if library_scan == "device" and reader not in ("native", "device"):
+        raise ValueError("library_scan='device' is only legal with reader='native' or reader='device' (got reader=%r)" % (reader,))
+    return library_scan
+
+
 def resolve_reader(reader: Optional[str]) -> str:
     """`reader=None` (the drivers' default, i.e. what a caller with the reference's positional arguments gets): the C++
     reader of libsvtyper_hip.so when the library is there -- fetch, fragment assembly and the geometry predicates in its

@@ -21,7 +21,7 @@ from . import evidence as ev
 from .bam import open_alignment_file
 from .library import Sample, setup_sample, write_sample_json
 from .pipeline import (MIN_LIB_PREVALENCE, BulkFeeder, block_chars, ChunkPipeline, NativeUnitCollector, split_lines, SampleColumnWriter, UnitCollector, add_read_to,
-                       default_engine, check_inflate, fetch_window, resolve_reader)
+                       default_engine, check_inflate, check_library_scan, fetch_window, resolve_reader)
 from .results import results_to_dicts
 from .vcf import Variant, Vcf
 
@@ -128,11 +128,12 @@ def assign_genotype(variant: Variant, sample_name: str, res: dict) -> None:
 
 def sso_genotype(bam_string, vcf_in, vcf_out, min_aligned, split_weight, disc_weight, num_samp, lib_info_path,
                  debug, ref_fasta, sum_quals, max_reads, max_ci_dist, cores, batch_size, *, engine=None, geometry="host",
-                 reader=None, stats=None, inflate="host"):
+                 reader=None, stats=None, inflate="host", library_scan="host"):
     if vcf_in is None:
         return
     reader = resolve_reader(reader)
     check_inflate(reader, inflate)
+    check_library_scan(reader, library_scan)
     full_bam_path = os.path.abspath(bam_string)
     if not (full_bam_path.endswith(".bam") or full_bam_path.endswith(".cram")):
         sys.exit("Error: %s is not a valid alignment file (*.bam or *.cram)\n" % full_bam_path)
@@ -147,7 +148,9 @@ def sso_genotype(bam_string, vcf_in, vcf_out, min_aligned, split_weight, disc_we
     if reader in ("native", "device"):      # C++ reader: library scans now, fetch + fragment summaries later
         from .native_reads import COUNT_SSO, NativeBam
         native = NativeBam(full_bam_path)
-    sample = setup_sample(bam, lib_info, num_samp, MIN_LIB_PREVALENCE, native)
+    if library_scan == "device" and lib_info is None and engine is None:
+        engine = default_engine()               # (the scan runs on the device the pass will use)
+    sample = setup_sample(bam, lib_info, num_samp, MIN_LIB_PREVALENCE, native, library_scan, getattr(engine, "device", 0) if library_scan == "device" else 0, inflate)
     if lib_info_path is not None and not os.path.exists(lib_info_path):
         logit("Writing library metrics to %s..." % lib_info_path)
         write_sample_json([sample], open(lib_info_path, "w"))
@@ -366,6 +369,10 @@ def get_args():
     p.add_argument("--inflate", choices=("host", "device"), default="host",
                    help="with --reader device: BGZF blocks inflated by the reader's threads, or on the GPU from the "
                         "compressed blocks (same output bytes) [host]")
+    p.add_argument("--library-scan", dest="library_scan", choices=("host", "device"), default="host",
+                   help="without a library file: the libraries' read length, insert-size histogram and prevalence from three "
+                        "scans per library on the host, or from one segmented walk on the GPU for all libraries, members inflated as --inflate says "
+                        "(needs --reader native or device; same library file, same output bytes) [host]")
     p.add_argument("--geometry", choices=("host", "device"), default="host",
                    help="with --reader python: breakpoint-dependent read predicates on the host or on the GPU [host]")
     args = p.parse_args()
@@ -384,13 +391,13 @@ def main():
     from . import sharded
     job = sharded.job()
     if job is None:
-        return sso_genotype(*call, geometry=args.geometry, reader=args.reader, inflate=args.inflate)
+        return sso_genotype(*call, geometry=args.geometry, reader=args.reader, inflate=args.inflate, library_scan=args.library_scan)
     # launched by torch.distributed.run with several ranks: one GPU each, variants sharded, one gather
     rank, world, local_rank = job
     call = call[:2] + (sharded.private_stdout(call[2]),) + call[3:]
     engine = sharded.init(local_rank)
     sharded.sso_genotype_sharded(*call, rank=rank, world=world, engine=engine, geometry=args.geometry,
-                                 reader=args.reader, inflate=args.inflate)
+                                 reader=args.reader, inflate=args.inflate, library_scan=args.library_scan)
     sharded.finish()
 
 
