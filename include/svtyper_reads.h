@@ -178,7 +178,8 @@ int svt_evidence_device_deep_stats(svt_evidence_deep_stats* out);
  * svtyper_amd/csrc/svt_inflate.h decodes the raw-deflate payload of a BGZF member (stored, fixed and dynamic blocks)
  * into exactly ISIZE bytes or a status; it is compiled for the host and for the device (svt_inflate_kernel.h, one
  * wavefront per member).  The verdict is the host reader's and zlib's: the stream ends with its final block having
- * produced exactly ISIZE bytes; bytes behind the final block are ignored, the CRC32 is not checked.
+ * produced exactly ISIZE bytes; bytes behind the final block are ignored.  The trailer's CRC32 is checked under verify only
+ * (the _verified entry points and svt_bam_set_verify below), by svtyper_amd/csrc/svt_crc32.h.
  *
  * svt_bgzf_inflate_host / _device: `data[len]` holds whole BGZF members at block_off[0..n); member k goes to
  * out + out_off[k] and has to fill out_off[k + 1] - out_off[k] bytes (the caller's prefix sums of ISIZE).
@@ -197,6 +198,48 @@ int svt_bgzf_inflate_host(const uint8_t* data, uint64_t len, const uint64_t* blo
                           const uint64_t* out_off, uint32_t* status);
 int svt_bgzf_inflate_device(const uint8_t* data, uint64_t len, const uint64_t* block_off, uint64_t n, uint8_t* out,
                             const uint64_t* out_off, uint32_t* status, int device);
+
+/* ---- the CRC-32 of BGZF members, by ONE piece of source on the host and on the device (additions to ABI 19) ----
+ * svtyper_amd/csrc/svt_crc32.h computes the CRC-32 of gzip over a member's inflated bytes: 64 chunks on 16-byte
+ * boundaries, a table-driven CRC per chunk, the registers joined by multiplications mod P (svt_crc32_kernel.h: one
+ * wavefront per member, one lane per chunk; on the host one loop over the chunks).
+ *
+ * svt_bgzf_crc32_host / _device: member k is bytes[off[k] .. off[k + 1]) -- off holds n + 1 non-decreasing offsets,
+ * a member has at most 65 536 bytes --, crc[k] receives its CRC-32.  Host memory for the one; for the other `bytes`
+ * is a pointer into the memory of `device` (off and crc are host arrays).
+ *
+ * svt_bgzf_inflate_host_verified / _device_verified: svt_bgzf_inflate_host / _device, and a member that inflates
+ * but whose CRC-32 is not the one its trailer stores gets SVT_INFLATE_CRC.  The decode verdict comes first: a member
+ * with another status keeps it.                                                                                */
+#define SVT_INFLATE_CRC 10      /* inflated to ISIZE bytes whose CRC-32 is not the trailer's (verify only)       */
+int svt_bgzf_crc32_host(const uint8_t* bytes, const uint64_t* off, uint64_t n, uint32_t* crc);
+int svt_bgzf_crc32_device(const uint8_t* bytes, const uint64_t* off, uint64_t n, uint32_t* crc, int device);
+int svt_bgzf_inflate_host_verified(const uint8_t* data, uint64_t len, const uint64_t* block_off, uint64_t n, uint8_t* out,
+                                   const uint64_t* out_off, uint32_t* status);
+int svt_bgzf_inflate_device_verified(const uint8_t* data, uint64_t len, const uint64_t* block_off, uint64_t n, uint8_t* out,
+                                     const uint64_t* out_off, uint32_t* status, int device);
+
+/* Verify: a property of the handle, off by default (0).  With it on, every call that takes the handle checks the
+ * CRC-32 of every BGZF member it inflates, where it inflates it: the host reader's threads (libdeflate's or zlib's
+ * crc32), or svt_crc32_kernel behind svt_inflate_kernel for the routes that inflate on the GPU (the expected values
+ * go up with the member table).  A member that fails is treated as one that does not inflate: the host reader fails
+ * the call with "BGZF block at offset N: CRC32 mismatch (stored 0x..., computed 0x...)", the walks flag its units
+ * SVT_WALK_RANGE / answer SVT_LIBSCAN_MEMBER, and the host reader that then answers meets the same member.  With it
+ * off nothing reads a trailer's CRC and nothing more is launched.  The blocks of the BAM header are read by
+ * svt_bam_open, before the property can be set: they are not checked.                                           */
+int svt_bam_set_verify(svt_bam* bam, int on);
+int svt_bam_get_verify(const svt_bam* bam);
+
+/* What verify did in the calling thread's most recent call that took a handle (thread-local, as svt_last_error's
+ * text; zeros with verify off).  The members are counted on the handle: calls that use one handle from several
+ * threads at the same time see each other's.                                                                    */
+typedef struct svt_bgzf_verify_counts {
+    uint64_t members_verified;  /* members whose CRC-32 was computed, on either side                             */
+    uint64_t members_failed;    /* ... and differed                                                              */
+    double host_crc_s;          /* in the host threads' CRC calls, summed over the threads                       */
+    double device_crc_s;        /* svt_crc32_kernel, host-observed: launch to the statuses' arrival              */
+} svt_bgzf_verify_counts;   /* (a C header cannot give a type and a function one name) */
+int svt_bgzf_verify_stats(svt_bgzf_verify_counts* out);
 
 /* svt_bam_evidence_walk_open_host: svt_bam_evidence_walk_host over the arena of the route below, with no GPU:
  * BAI lookup, a walk over BGZF headers only, every needed member inflated once by svt_inflate.h, one range per

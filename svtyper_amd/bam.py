@@ -30,8 +30,10 @@ _ALIGNED = (True, False, False, False, False, False, False, True, True)  # M = X
 class BgzfReader:
     """Random access over a BGZF file through (compressed offset, in-block offset) addresses."""
 
-    def __init__(self, path: str, cache_blocks: int = 64):
+    def __init__(self, path: str, cache_blocks: int = 64, verify: bool = False):
         self._f = open(path, "rb")
+        self.verify = verify             # check every block's CRC32 where it is inflated (verify="crc32")
+        self.members_verified = 0
         self._cache: "OrderedDict[int, Tuple[bytes, int]]" = OrderedDict()
         self._cache_blocks = cache_blocks
         self._coff = 0   # compressed offset of the current block
@@ -69,8 +71,14 @@ class BgzfReader:
             raise IOError("BGZF block without BC field")
         cdata_len = bsize - xlen - 19
         cdata = self._f.read(cdata_len)
-        self._f.read(8)  # crc32 + isize
+        trailer = self._f.read(8)  # crc32 + isize
         data = zlib.decompress(cdata, -15) if cdata_len > 0 else b""
+        if self.verify:
+            stored = struct.unpack_from("<I", trailer, 0)[0] if len(trailer) >= 4 else None
+            computed = zlib.crc32(data) & 0xFFFFFFFF
+            self.members_verified += 1
+            if stored != computed:
+                raise IOError("BGZF block at offset %d: CRC32 mismatch (stored 0x%08x, computed 0x%08x)" % (coff, stored or 0, computed))
         nxt = coff + bsize + 1
         self._cache[coff] = (data, nxt)
         if len(self._cache) > self._cache_blocks:
@@ -291,7 +299,7 @@ class AlignmentFile:
         if "c" in mode or path.endswith(".cram"):
             raise NotImplementedError("CRAM needs htslib; this reader handles BAM only")
         self.filename = path
-        self._bgzf = BgzfReader(path)
+        self._bgzf = BgzfReader(path, verify=bool(kwargs.get("verify", False)))
         if self._bgzf.read(4) != b"BAM\1":
             raise IOError("%s is not a BAM file" % path)
         l_text = struct.unpack("<i", self._bgzf.read(4))[0]
@@ -456,11 +464,14 @@ class AlignmentFile:
         return n
 
 
-def open_alignment_file(path: str, reference_fasta: Optional[str] = None):
+def open_alignment_file(path: str, reference_fasta: Optional[str] = None, verify: bool = False):
     """pysam.AlignmentFile when pysam is importable, else the built-in BAM reader
-    (svtyper/singlesample.py:53-62 semantics: the extension decides)."""
+    (svtyper/singlesample.py:53-62 semantics: the extension decides).  `verify`: the built-in reader, checking the CRC32 of
+    every BGZF block it inflates (the drivers' verify="crc32")."""
     if not (path.endswith(".bam") or path.endswith(".cram")):
         raise ValueError("Error: %s is not a valid alignment file (*.bam or *.cram)" % path)
+    if verify and path.endswith(".bam"):
+        return AlignmentFile(path, "rb", verify=True)
     try:
         import pysam  # type: ignore
         if path.endswith(".bam"):

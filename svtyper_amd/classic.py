@@ -22,7 +22,7 @@ from . import evidence as ev
 from .bam import open_alignment_file
 from .library import Sample, setup_sample, write_sample_json
 from .pipeline import (MIN_LIB_PREVALENCE, BulkFeeder, ChunkPipeline, NativeUnitCollector, SampleColumnWriter, UnitCollector, add_read_to,
-                       default_engine, check_inflate, check_library_scan, fetch_window, resolve_reader, text_blocks)
+                       default_engine, check_inflate, check_library_scan, check_verify, verify_stats, fetch_window, resolve_reader, text_blocks)
 from .results import results_to_dicts
 from .vcf import VALID_SVTYPES, Variant, Vcf
 
@@ -66,18 +66,19 @@ def apply_result(var: Variant, sample_name: str, gt: int, res: dict) -> None:
 
 def sv_genotype(bam_string, vcf_in, vcf_out, min_aligned, split_weight, disc_weight, num_samp, lib_info_path,
                 debug, alignment_outpath, ref_fasta, sum_quals, max_reads, max_ci_dist, *, engine=None, geometry="host",
-                reader=None, stats=None, inflate="host", library_scan="host"):
+                reader=None, stats=None, inflate="host", library_scan="host", verify="off"):
     if alignment_outpath is not None:
         raise NotImplementedError("-w/--write_alignment (evidence BAM dump) is outside the MI355X hot path build")
     reader = resolve_reader(reader)
     check_inflate(reader, inflate)
     check_library_scan(reader, library_scan)
+    verify_on = check_verify(verify)
     bams = []
     for path in bam_string.split(","):
         if not (path.endswith(".bam") or path.endswith(".cram")):
             sys.stderr.write("Error: %s is not a valid alignment file (*.bam or *.cram)\n" % path)
             sys.exit(1)
-        bams.append(open_alignment_file(path, ref_fasta))
+        bams.append(open_alignment_file(path, ref_fasta, verify=verify_on))
 
     lib_info = None
     if lib_info_path is not None and os.path.isfile(lib_info_path):
@@ -88,7 +89,7 @@ def sv_genotype(bam_string, vcf_in, vcf_out, min_aligned, split_weight, disc_wei
     native = None
     if reader in ("native", "device"):      # C++ reader: library scans now, fetch + fragment summaries later
         from .native_reads import COUNT_CLASSIC, NativeBam
-        native = [NativeBam(p) for p in bam_string.split(",")]
+        native = [NativeBam(p, verify=verify_on) for p in bam_string.split(",")]
     if library_scan == "device" and lib_info is None and engine is None:
         engine = default_engine()               # (the scan runs on the device the pass will use)
     samples: List[Sample] = [setup_sample(b, lib_info, num_samp, MIN_LIB_PREVALENCE, nb, library_scan, getattr(engine, "device", 0) if library_scan == "device" else 0, inflate)
@@ -272,6 +273,7 @@ def sv_genotype(bam_string, vcf_in, vcf_out, min_aligned, split_weight, disc_wei
         stats.update(bulk_stats[0] if bulk_stats else {}, route=bulk_stats[1] if bulk_stats else "per line")
         if reader == "device":      # the counters of svt_bam_evidence_device, summed over the run's calls
             stats["device_reader"] = collector.device_stats
+        stats["verify"] = verify_stats(native, () if native else bams)   # (with the C++ reader the Python one reads the header only)
     if vcf._bnd_pending or unpaired:
         logging.warning("Unpaired breakends found in file. These will not be present in output.")
     vcf_in.close()
@@ -333,6 +335,8 @@ def get_args():
     p.add_argument("--inflate", choices=("host", "device"), default="host",
                    help="with --reader device: BGZF blocks inflated by the reader's threads, or on the GPU from the "
                         "compressed blocks (same output bytes) [host]")
+    p.add_argument("--verify-bgzf", dest="verify_bgzf", action="store_true",
+                   help="check the CRC32 of every BGZF block where it is inflated (verify='crc32'); a mismatch is an error")
     p.add_argument("--library-scan", dest="library_scan", choices=("host", "device"), default="host",
                    help="without a library file: the libraries' read length, insert-size histogram and prevalence from three "
                         "scans per library on the host, or from one segmented walk on the GPU for all libraries, members inflated as --inflate says "
@@ -356,13 +360,15 @@ def main():
     from . import sharded
     job = sharded.job()
     if job is None:
-        return sv_genotype(*call, geometry=args.geometry, reader=args.reader, inflate=args.inflate, library_scan=args.library_scan)
+        return sv_genotype(*call, geometry=args.geometry, reader=args.reader, inflate=args.inflate, library_scan=args.library_scan,
+                           verify="crc32" if args.verify_bgzf else "off")
     # launched by torch.distributed.run with several ranks: one GPU each, variants sharded, one gather
     rank, world, local_rank = job
     call = call[:2] + (sharded.private_stdout(call[2]),) + call[3:]
     engine = sharded.init(local_rank)
     sharded.sv_genotype_sharded(*call, rank=rank, world=world, engine=engine, geometry=args.geometry,
-                                reader=args.reader, inflate=args.inflate, library_scan=args.library_scan)
+                                reader=args.reader, inflate=args.inflate, library_scan=args.library_scan,
+                           verify="crc32" if args.verify_bgzf else "off")
     sharded.finish()
 
 

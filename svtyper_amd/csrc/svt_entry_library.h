@@ -25,7 +25,9 @@ struct GrowBuffer {
 // is returned.
 struct LibraryCall : CallStream, lw::Backend {
     const bool inflate_on_device;
-    GrowBuffer d_arena, d_compressed, d_members, d_member_status, d_segments, d_counts, d_caps;
+    GrowBuffer d_arena, d_compressed, d_members, d_member_status, d_segments, d_counts, d_caps, d_crc_jobs;
+    DevScratch d_crc_tables;                                 // verify with inflate on the device: uploaded by the first round
+    int device = 0;
     DevScratch d_rgs, d_blob, d_dense_count, d_dense_first, d_small, d_overflow;
     std::vector<uint8_t> host_arena;                         // inflate on the host: the round's bytes in front of their upload
     uint64_t arena_len = 0;
@@ -83,16 +85,28 @@ struct LibraryCall : CallStream, lw::Backend {
             SVT_TRY(d_compressed.need(r.span_bytes + 8));
             SVT_TRY(d_members.need(r.members.size() * sizeof(inf::Member)));
             SVT_TRY(d_member_status.need(r.members.size() * sizeof(uint32_t)));
+            CrcCheck check;
             {
                 Stager st(s);
                 SVT_TRY(st.copy(d_compressed.d.p, r.file + r.span_off, r.span_bytes));
                 SVT_TRY(st.copy(d_members.d.p, r.members.data(), r.members.size() * sizeof(inf::Member)));
+                if (r.verify) {                                     // the expected CRC-32s go up with the member table
+                    std::vector<crc::Job> jobs;
+                    r.crc_jobs(jobs);
+                    SVT_TRY(d_crc_jobs.need(jobs.size() * sizeof(crc::Job)));
+                    SVT_TRY(st.copy(d_crc_jobs.d.p, jobs.data(), jobs.size() * sizeof(crc::Job)));
+                    if (!d_crc_tables.p) {
+                        SVT_TRY(d_crc_tables.alloc(sizeof(crc::Tables)));
+                        SVT_TRY(st.copy(d_crc_tables.p, &crc_tables(), sizeof(crc::Tables)));
+                    }
+                    check = CrcCheck{d_crc_jobs.as<crc::Job>(), d_crc_tables.as<crc::Tables>(), device, r.verify};
+                }
                 SVT_TRY(st.finish());
             }
             S.upload_s += since(t0);
             t0 = now();
             SVT_TRY(run_inflate_kernel(d_compressed.as<uint8_t>(), r.span_bytes, d_members.as<inf::Member>(), r.members.size(), d_arena.as<uint8_t>(),
-                                       r.arena_bytes, d_member_status.as<uint32_t>(), member_status, s));
+                                       r.arena_bytes, d_member_status.as<uint32_t>(), member_status, s, check));
             S.inflate_s += since(t0);
         } else {
             auto t0 = now();
@@ -159,7 +173,9 @@ int svt_bam_scan_libraries_device(const svt_bam* bam, uint32_t n_libs, const uin
 {
     return guarded([&]() -> int {
         SVT_TRY(select_device(device));
+        VerifyScope verify_scope(bam);
         LibraryCall c(inflate_on_device != 0);
+        c.device = device;
         SVT_TRY(c.take());
         return lw::scan_libraries(bam, n_libs, rg_counts, read_groups, num_samp, round_bytes, c, out, stats);
     });

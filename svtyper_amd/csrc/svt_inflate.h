@@ -6,7 +6,8 @@
 // X::sync().  On the host there is one lane and sync() is nothing.
 //
 // The verdict is the host reader's (Bgzf::inflate_block) and zlib's: success means the stream ends with its final block having
-// produced exactly ISIZE bytes.  Bytes behind the final block are not looked at, the CRC32 is not checked.  Every input read is
+// produced exactly ISIZE bytes.  Bytes behind the final block are not looked at.  The CRC32 of the trailer is not this decoder's
+// business: it is checked behind it, under verify, by svt_crc32.h (INF_CRC: svt_bgzf_inflate_*_verified, svt_bam_set_verify).  Every input read is
 // checked against `clen`, every output write against `isize`, every distance against the bytes produced so far; code-length sets
 // are checked for over- and under-subscription as zlib's inflate_table does (an incomplete set only with a single code of one
 // bit; no codes at all only for distances); every loop consumes input bits or ends.  No std::, no allocation.
@@ -40,7 +41,8 @@ enum : uint32_t {
     INF_OUTPUT = 7,          // more than ISIZE bytes
     INF_SHORT = 8,           // the stream ends with fewer than ISIZE bytes
     INF_MEMBER = 9,          // not a BGZF member, or it does not fit the bytes / the place it was given (decided by the caller)
-    INF_N_STATUS = 10
+    INF_CRC = 10,            // (verify only) the member inflated to ISIZE bytes whose CRC-32 is not the trailer's (svt_crc32.h)
+    INF_N_STATUS = 11
 };
 
 constexpr uint32_t kFastBits = 10;          // literal/length codes up to this length: one look-up
@@ -94,6 +96,13 @@ SVT_HD bool member_at(const uint8_t* data, uint64_t len, uint64_t off, uint64_t&
     isize = tail[4] | (tail[5] << 8) | (tail[6] << 16) | ((uint32_t)tail[7] << 24);
     next = off + (uint64_t)bsize + 1;
     return isize <= kMaxIsize;
+}
+
+// the CRC-32 its trailer stores for the member whose payload is data[src, src + clen) (member_at has vouched for the trailer's bytes)
+SVT_HD uint32_t member_crc(const uint8_t* data, uint64_t src, uint32_t clen)
+{
+    const uint8_t* t = data + src + clen;
+    return t[0] | (t[1] << 8) | (t[2] << 16) | ((uint32_t)t[3] << 24);
 }
 
 // ---- lane 0's bit buffer over Scratch.in ---------------------------------------------------------------------------------------

@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "../../include/svtyper_reads.h"
+#include "svt_evidence_arena.h"
 #include "svt_inflate.h"
 #include "svt_library_walk.h"
 
@@ -22,6 +23,13 @@ struct Round {
     uint64_t span_off = 0, span_bytes = 0, arena_bytes = 0;
     std::vector<inf::Member> members;
     std::vector<Segment> segments;
+    VerifyTally* verify = nullptr;       // svt_bam_set_verify: whoever loads the round checks its members' CRC-32 and counts here
+    const uint8_t* payload(const inf::Member& mb) const { return file + span_off + mb.src; }
+    void crc_jobs(std::vector<crc::Job>& jobs) const
+    {
+        jobs.resize(members.size());
+        for (size_t k = 0; k < members.size(); ++k) jobs[k] = crc::Job{members[k].dst, members[k].isize, inf::member_crc(payload(members[k]), 0, members[k].clen)};
+    }
 };
 
 // the host's copies of the tables, for the merge
@@ -44,7 +52,7 @@ struct Backend {
 };
 
 // the members of `r` inflated on `n_threads` host threads into dst[0, r.arena_bytes): by svt_inflate.h (`one_source`), or by the
-// reader's own decoder (libdeflate / zlib)
+// reader's own decoder (libdeflate / zlib); with r.verify a member that inflates has its CRC-32 checked there (inf::INF_CRC)
 void inflate_round_host(const Round& r, uint8_t* dst, unsigned n_threads, bool one_source, std::vector<uint32_t>& status);
 
 // the whole call.  0 or SVT_ERR_* with the error text set (the host scan's, when it answered).

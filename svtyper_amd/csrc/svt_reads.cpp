@@ -84,12 +84,14 @@ struct FastInflate {
     void* (*alloc)() = nullptr;
     int (*decompress)(void*, const void*, size_t, void*, size_t, size_t*) = nullptr;
     void (*release)(void*) = nullptr;
+    uint32_t (*crc)(uint32_t, const void*, size_t) = nullptr;   // verify: libdeflate_crc32, when the library has it
     FastInflate()
     {
         const char* want = std::getenv("SVT_INFLATE");
         if (want && std::strcmp(want, "zlib") == 0) return;
         void* h = dlopen("libdeflate.so.0", RTLD_NOW | RTLD_LOCAL);
         if (!h) return;
+        crc = reinterpret_cast<uint32_t (*)(uint32_t, const void*, size_t)>(dlsym(h, "libdeflate_crc32"));
         alloc = reinterpret_cast<void* (*)()>(dlsym(h, "libdeflate_alloc_decompressor"));
         decompress = reinterpret_cast<int (*)(void*, const void*, size_t, void*, size_t, size_t*)>(
             dlsym(h, "libdeflate_deflate_decompress"));
@@ -102,6 +104,13 @@ static const FastInflate& fast_inflate()
 {
     static const FastInflate f;
     return f;
+}
+
+std::string crc_mismatch_text(uint64_t coff, uint32_t stored, uint32_t computed)
+{
+    char text[128];
+    std::snprintf(text, sizeof text, "BGZF block at offset %llu: CRC32 mismatch (stored 0x%08x, computed 0x%08x)", (unsigned long long)coff, stored, computed);
+    return text;
 }
 
 // One inflated BGZF block: immutable once it is published, so readers on several threads can hold it.
@@ -193,7 +202,9 @@ private:
 
 class Bgzf {
 public:
-    explicit Bgzf(const FileMap& file, SharedBlocks* shared = nullptr) : file_(file), shared_(shared), empty_(std::make_shared<BlockData>())
+    // `verify` (svt_bam_set_verify; null: off): every block this reader inflates has its CRC-32 checked, and is counted there
+    explicit Bgzf(const FileMap& file, SharedBlocks* shared = nullptr, svt::VerifyTally* verify = nullptr)
+        : file_(file), shared_(shared), verify_(verify), empty_(std::make_shared<BlockData>())
     {
         std::memset(&zs_, 0, sizeof zs_);
         if (fast_inflate().usable()) fast_ = fast_inflate().alloc();
@@ -204,12 +215,16 @@ public:
     {
         if (fast_) fast_inflate().release(fast_);
         if (zs_ok_) inflateEnd(&zs_);
+        if (verify_) verify_->add(n_verified_, n_crc_failed_, crc_s_, 0.0);
     }
     Bgzf(const Bgzf&) = delete;
     Bgzf& operator=(const Bgzf&) = delete;
     bool ok() const { return file_.data != nullptr && (zs_ok_ || fast_); }
     bool failed() const { return bad_; }
     void mark_bad() { bad_ = true; }   // the record stream inside the blocks is corrupt
+    // verify: a block this reader inflated did not have the CRC-32 its trailer stores (it is failed() too); the text for the caller
+    bool crc_failed() const { return !crc_error_.empty(); }
+    const std::string& crc_error() const { return crc_error_; }
     uint64_t n_inflated = 0, n_shared_hits = 0, n_ahead = 0;   // (SVT_TRACE)
     double inflate_s = 0.0;
     // when set: every block this reader loads is noted here (the arena of svt_bam_evidence_device is put together from them)
@@ -350,6 +365,18 @@ private:
         }
         inflate_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - t_inflate).count();
         ++n_inflated;
+        if (verify_ && inflated) {                       // a mismatch is a block that does not inflate, with a text of its own
+            const auto t_crc = std::chrono::steady_clock::now();
+            const uint32_t stored = tail[0] | (tail[1] << 8) | (tail[2] << 16) | ((uint32_t)tail[3] << 24);
+            const uint32_t computed = svt::host_crc32(b->data.data(), b->data.size());
+            crc_s_ += std::chrono::duration<double>(std::chrono::steady_clock::now() - t_crc).count();
+            ++n_verified_;
+            if (stored != computed) {
+                ++n_crc_failed_;
+                inflated = false;
+                if (crc_error_.empty()) crc_error_ = crc_mismatch_text(coff, stored, computed);
+            }
+        }
         *unusable = !inflated;
         return b;
     }
@@ -430,6 +457,10 @@ private:
 
     const FileMap& file_;
     SharedBlocks* shared_;
+    svt::VerifyTally* verify_;
+    uint64_t n_verified_ = 0, n_crc_failed_ = 0;
+    double crc_s_ = 0.0;
+    std::string crc_error_;
     z_stream zs_;
     bool zs_ok_ = false;
     void* fast_ = nullptr;   // libdeflate decompressor of this reader
@@ -536,7 +567,62 @@ struct svt_bam {
     bool has_index = false;
     // CPU seconds per unit of the summariser's last calls on this file (0: none yet): sizes the next call's burst
     mutable std::atomic<double> cpu_s_per_unit{0.0};
+    // svt_bam_set_verify: off by default; the tally of everything that was verified through this handle
+    std::atomic<int> verify{0};
+    mutable svt::VerifyTally tally;
 };
+
+static thread_local svt_bgzf_verify_counts g_verify_stats{};   // svt_bgzf_verify_stats: this thread's last call that took a handle
+
+namespace svt {
+
+VerifyTally* bam_verify(const svt_bam* bam) { return bam && bam->verify.load() ? &bam->tally : nullptr; }
+
+uint32_t host_crc32(const uint8_t* p, size_t n)
+{
+    if (fast_inflate().crc) return fast_inflate().crc(0, p, n);
+    return (uint32_t)::crc32(0L, p, (uInt)n);              // (n <= 65 536)
+}
+
+VerifyScope::VerifyScope(const svt_bam* b) : bam(b)
+{
+    g_verify_stats = svt_bgzf_verify_counts{};
+    if (!bam) return;
+    verified = bam->tally.verified.load();
+    failed = bam->tally.failed.load();
+    host_ns = bam->tally.host_ns.load();
+    device_ns = bam->tally.device_ns.load();
+}
+VerifyScope::~VerifyScope()
+{
+    if (!bam) return;
+    g_verify_stats.members_verified = bam->tally.verified.load() - verified;
+    g_verify_stats.members_failed = bam->tally.failed.load() - failed;
+    g_verify_stats.host_crc_s = (double)(bam->tally.host_ns.load() - host_ns) * 1e-9;
+    g_verify_stats.device_crc_s = (double)(bam->tally.device_ns.load() - device_ns) * 1e-9;
+}
+
+// the tables of svt_crc32.h for this translation unit's callers
+const crc::Tables& crc_tables()
+{
+    static const crc::Tables* const T = [] { auto* t = new crc::Tables(); crc::fill_tables(*t); return t; }();
+    return *T;
+}
+
+// the arguments of svt_bgzf_crc32_host / _device
+int crc_check_offsets(const uint8_t* bytes, const uint64_t* off, uint64_t n, const uint32_t* crc)
+{
+    if (n && (!off || !crc)) return fail(SVT_ERR_INVALID, "null argument");
+    if (n > 0xFFFFFFFFull) return fail(SVT_ERR_INVALID, "svt_bgzf_crc32: too many members in one call (< 2^32)");
+    for (uint64_t k = 0; k < n; ++k) {
+        if (off[k + 1] < off[k]) return fail(SVT_ERR_INVALID, "svt_bgzf_crc32: off must not decrease");
+        if (off[k + 1] - off[k] > crc::kMaxLen) return fail(SVT_ERR_INVALID, "svt_bgzf_crc32: a member has at most 65536 bytes");
+    }
+    if (n && off[n] && !bytes) return fail(SVT_ERR_INVALID, "null argument");
+    return SVT_OK;
+}
+
+}  // namespace svt
 
 namespace {
 
@@ -637,10 +723,11 @@ bool fetch(const svt_bam& bam, Bgzf& z, int32_t tid, int64_t beg, int64_t end, s
             uint32_t size = 0;
             const uint8_t* d = next_record(z, buf, size);
             if (!decode(d, size, r)) break;
-            if (r.tid != tid || r.pos >= end) return true;
+            // (verify: a fetch that ends early has still read through a block whose CRC-32 did not match)
+            if (r.tid != tid || r.pos >= end) return !z.crc_failed();
             int64_t rend = r.end;
             if (r.n_cigar == 0 || rend <= r.pos) rend = (int64_t)r.pos + 1;
-            if (rend > beg && !fn(r)) return true;      // (most records walked on the way to the window stop here)
+            if (rend > beg && !fn(r)) return !z.crc_failed();      // (most records walked on the way to the window stop here)
         }
     }
     return !z.failed();
@@ -1077,7 +1164,7 @@ int process_unit(const svt_bam& bam, Bgzf& z, std::vector<uint8_t>& buf, const s
             return true;
         });
         if (rc != SVT_OK) return rc;
-        if (!ok) { err = "BAM read error"; return SVT_ERR_INVALID; }
+        if (!ok) { err = z.crc_failed() ? z.crc_error() : "BAM read error"; return SVT_ERR_INVALID; }
     }
     if (out.skipped) { out.frags.clear(); out.recs.clear(); return SVT_OK; }
 
@@ -1299,7 +1386,7 @@ struct HostWorker {
     Bgzf z;
     std::vector<uint8_t> buf;
     uint64_t& n_records;
-    HostWorker(HostRoute& route, unsigned t) : z(route.bam->file, &route.shared_blocks), n_records(route.n_records[t]) { z.touched = &route.touched[t]; }
+    HostWorker(HostRoute& route, unsigned t) : z(route.bam->file, &route.shared_blocks, svt::bam_verify(route.bam)), n_records(route.n_records[t]) { z.touched = &route.touched[t]; }
     bool ok() const { return z.ok(); }
     unsigned chunk(int32_t tid, int64_t end, uint64_t vbeg, uint64_t vend, RawRange& r)
     {
@@ -1458,7 +1545,7 @@ int build_arena_open(const svt_bam* bam, const svt_summarise_args* args, const s
     return SVT_OK;
 }
 
-void inflate_open_host(const OpenPlan& plan, Arena& out, unsigned n_threads, std::vector<uint32_t>& status)
+void inflate_open_host(const OpenPlan& plan, Arena& out, unsigned n_threads, std::vector<uint32_t>& status, VerifyTally* verify)
 {
     const size_t m = plan.members.size();
     status.assign(m, inf::INF_OK);
@@ -1470,11 +1557,14 @@ void inflate_open_host(const OpenPlan& plan, Arena& out, unsigned n_threads, std
             if (k0 >= m) return;
             for (size_t k = k0; k < std::min(m, k0 + 8); ++k) {
                 const inf::Member& mb = plan.members[k];
-                // (Member.src counts in the uploaded spans: back to the file through the member's span)
-                auto sp = std::upper_bound(plan.spans.begin(), plan.spans.end(), mb.src, [](uint64_t v, const OpenPlan::Span& s) { return v < s.at; });
-                --sp;
-                const uint8_t* cdata = plan.file + sp->file_off + (mb.src - sp->at);
+                const uint8_t* cdata = plan.payload(mb);
                 status[k] = inf::inflate_member<inf::HostCtx>(cdata, mb.clen, out.bytes.data() + mb.dst, mb.isize, *S);
+                if (verify && status[k] == inf::INF_OK) {
+                    const auto t0 = std::chrono::steady_clock::now();
+                    const bool same = host_crc32(out.bytes.data() + mb.dst, mb.isize) == inf::member_crc(cdata, 0, mb.clen);
+                    if (!same) status[k] = inf::INF_CRC;
+                    verify->add(1, same ? 0 : 1, std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(), 0.0);
+                }
             }
         }
     });
@@ -1530,7 +1620,7 @@ int host_units(const svt_bam* bam, const svt_summarise_args* args, const svt_evi
     int err_rc = SVT_OK;
     std::string err_text;
     run_threads(nt, [&](unsigned) {
-        Bgzf z(bam->file, shared_blocks.get());
+        Bgzf z(bam->file, shared_blocks.get(), svt::bam_verify(bam));
         std::vector<uint8_t> buf;
         UnitOut unit;
         Workspace ws;
@@ -1758,7 +1848,7 @@ static int summarise_units(const svt_bam* bam, const svt_summarise_args* args, c
     auto worker = [&](unsigned t) {
         const auto w_begin = std::chrono::steady_clock::now();
         stats[t].start_s = std::chrono::duration<double>(w_begin - t_begin).count();
-        Bgzf z(bam->file, shared_blocks.get());
+        Bgzf z(bam->file, shared_blocks.get(), svt::bam_verify(bam));
         struct Report {
             WorkerStat& st; Bgzf& z; std::chrono::steady_clock::time_point t0; double cpu0;
             ~Report() { st.cpu_s = thread_cpu_seconds() - cpu0; st.busy_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(); st.inflate_s = z.inflate_s; st.inflated = z.n_inflated; st.shared = z.n_shared_hits; st.ahead = z.n_ahead; }
@@ -1876,6 +1966,7 @@ int svt_bam_summarise(const svt_bam* bam, const svt_summarise_args* args, svt_su
 {
     return guarded([&] {
         if (!out) return fail(SVT_ERR_INVALID, "null argument");
+        svt::VerifyScope verify_scope(bam);
         void* elements = nullptr;
         const int rc = summarise_units(bam, args, nullptr, GatherOut{&out->frag_offset, &elements, &out->skipped, sizeof(svt_fragment)});
         out->fragments = static_cast<svt_fragment*>(elements);
@@ -1895,6 +1986,7 @@ int svt_bam_evidence(const svt_bam* bam, const svt_summarise_args* args, const s
 {
     return guarded([&] {
         if (!out || !geometry) return fail(SVT_ERR_INVALID, "null argument");
+        svt::VerifyScope verify_scope(bam);
         void* elements = nullptr;
         const int rc = summarise_units(bam, args, geometry, GatherOut{&out->rec_offset, &elements, &out->skipped, sizeof(svt_record)});
         out->records = static_cast<svt_record*>(elements);
@@ -1914,6 +2006,7 @@ static int svt_bam_evidence_walk_host_impl(const svt_bam* bam, const svt_summari
                                            svt_evidence* out, uint8_t* out_of_envelope, uint32_t* kept_reads, bool open_ranges)
 {
     if (!out || !out_of_envelope) return fail(SVT_ERR_INVALID, "null argument");
+    svt::VerifyScope verify_scope(bam);
     out->rec_offset = nullptr;
     out->records = nullptr;
     out->skipped = nullptr;
@@ -1922,7 +2015,7 @@ static int svt_bam_evidence_walk_host_impl(const svt_bam* bam, const svt_summari
         svt::ew::OpenPlan plan;
         if (const int rc = svt::ew::build_arena_open(bam, args, geometry, arena, plan)) return rc;
         std::vector<uint32_t> member_status;
-        svt::ew::inflate_open_host(plan, arena, svt::ew::arena_threads(args, plan.members.size()), member_status);
+        svt::ew::inflate_open_host(plan, arena, svt::ew::arena_threads(args, plan.members.size()), member_status, svt::bam_verify(bam));
         svt::ew::apply_member_status(plan, member_status, arena);
     } else if (const int rc = svt::ew::build_arena(bam, args, geometry, arena)) return rc;
     const uint64_t n = args->n_units;
@@ -1989,19 +2082,64 @@ int svt_bam_evidence_walk_open_host(const svt_bam* bam, const svt_summarise_args
     return guarded([&] { return svt_bam_evidence_walk_host_impl(bam, args, geometry, out, out_of_envelope, kept_reads, true); });
 }
 
+static int svt_bgzf_inflate_host_impl(const uint8_t* data, uint64_t len, const uint64_t* block_off, uint64_t n, uint8_t* out,
+                                      const uint64_t* out_off, uint32_t* status, bool verify)
+{
+    if (n && (!status || (!out && out_off && out_off[n]))) return fail(SVT_ERR_INVALID, "null argument");
+    std::vector<svt::inf::Member> members(n);
+    if (const int rc = svt::ew::bgzf_members(data, len, block_off, n, out_off, members.data())) return rc;
+    std::unique_ptr<svt::inf::Scratch> S(new svt::inf::Scratch());
+    std::unique_ptr<svt::crc::Scratch> C(verify ? new svt::crc::Scratch() : nullptr);
+    for (uint64_t k = 0; k < n; ++k) {
+        const svt::inf::Member& m = members[k];
+        status[k] = m.isize == svt::inf::kNoMember ? (uint32_t)svt::inf::INF_MEMBER
+                                                   : svt::inf::inflate_member<svt::inf::HostCtx>(data + m.src, m.clen, out + m.dst, m.isize, *S);
+        // (the one-source CRC, as the device entry's kernel runs it)
+        if (verify && status[k] == svt::inf::INF_OK &&
+            svt::crc::crc_member<svt::crc::HostCtx>(out + m.dst, m.isize, svt::crc_tables(), *C) != svt::inf::member_crc(data, m.src, m.clen))
+            status[k] = svt::inf::INF_CRC;
+    }
+    return SVT_OK;
+}
+
 int svt_bgzf_inflate_host(const uint8_t* data, uint64_t len, const uint64_t* block_off, uint64_t n, uint8_t* out, const uint64_t* out_off,
                           uint32_t* status)
 {
+    return guarded([&] { return svt_bgzf_inflate_host_impl(data, len, block_off, n, out, out_off, status, false); });
+}
+
+int svt_bgzf_inflate_host_verified(const uint8_t* data, uint64_t len, const uint64_t* block_off, uint64_t n, uint8_t* out,
+                                   const uint64_t* out_off, uint32_t* status)
+{
+    return guarded([&] { return svt_bgzf_inflate_host_impl(data, len, block_off, n, out, out_off, status, true); });
+}
+
+int svt_bgzf_crc32_host(const uint8_t* bytes, const uint64_t* off, uint64_t n, uint32_t* crc)
+{
     return guarded([&]() -> int {
-        if (n && (!status || (!out && out_off && out_off[n]))) return fail(SVT_ERR_INVALID, "null argument");
-        std::vector<svt::inf::Member> members(n);
-        if (const int rc = svt::ew::bgzf_members(data, len, block_off, n, out_off, members.data())) return rc;
-        std::unique_ptr<svt::inf::Scratch> S(new svt::inf::Scratch());
-        for (uint64_t k = 0; k < n; ++k) {
-            const svt::inf::Member& m = members[k];
-            status[k] = m.isize == svt::inf::kNoMember ? (uint32_t)svt::inf::INF_MEMBER
-                                                       : svt::inf::inflate_member<svt::inf::HostCtx>(data + m.src, m.clen, out + m.dst, m.isize, *S);
-        }
+        if (const int rc = svt::crc_check_offsets(bytes, off, n, crc)) return rc;
+        std::unique_ptr<svt::crc::Scratch> C(new svt::crc::Scratch());
+        for (uint64_t k = 0; k < n; ++k) crc[k] = svt::crc::crc_member<svt::crc::HostCtx>(bytes + off[k], (uint32_t)(off[k + 1] - off[k]), svt::crc_tables(), *C);
+        return SVT_OK;
+    });
+}
+
+int svt_bam_set_verify(svt_bam* bam, int on)
+{
+    return guarded([&]() -> int {
+        if (!bam) return fail(SVT_ERR_INVALID, "null argument");
+        bam->verify.store(on ? 1 : 0);
+        return SVT_OK;
+    });
+}
+
+int svt_bam_get_verify(const svt_bam* bam) { return bam ? bam->verify.load() : 0; }
+
+int svt_bgzf_verify_stats(svt_bgzf_verify_counts* out)
+{
+    return guarded([&]() -> int {
+        if (!out) return fail(SVT_ERR_INVALID, "null argument");
+        *out = g_verify_stats;
         return SVT_OK;
     });
 }
@@ -2027,7 +2165,7 @@ static int svt_bam_scan_library_impl(const svt_bam* bam, uint32_t n_read_groups,
     *out = svt_library_scan{};
     std::set<std::string> rgset;
     for (uint32_t i = 0; i < n_read_groups; ++i) rgset.insert(read_groups[i]);
-    Bgzf z(bam->file);
+    Bgzf z(bam->file, nullptr, svt::bam_verify(bam));
     if (!z.ok()) return fail(SVT_ERR_NOMEM, "cannot set up the inflate state");
     std::vector<uint8_t> buf;
     Record r;
@@ -2091,6 +2229,7 @@ static int svt_bam_scan_library_impl(const svt_bam* bam, uint32_t n_read_groups,
         out->in_lib += (uint64_t)in;
         ++out->total;
     }
+    if (z.crc_failed()) return fail(SVT_ERR_INVALID, z.crc_error());
     if (z.failed()) return fail(SVT_ERR_INVALID, "corrupt BGZF block in " + bam->path);
     out->n_hist = hist_keys.size();
     out->hist_keys = static_cast<int64_t*>(std::malloc(std::max<size_t>(hist_keys.size(), 1) * sizeof(int64_t)));
@@ -2108,7 +2247,10 @@ static int svt_bam_scan_library_impl(const svt_bam* bam, uint32_t n_read_groups,
 
 int svt_bam_scan_library(const svt_bam* bam, uint32_t n_read_groups, const char* const* read_groups, int64_t num_samp, svt_library_scan* out)
 {
-    return guarded([&] { return svt_bam_scan_library_impl(bam, n_read_groups, read_groups, num_samp, out); });
+    return guarded([&] {
+        svt::VerifyScope verify_scope(bam);
+        return svt_bam_scan_library_impl(bam, n_read_groups, read_groups, num_samp, out);
+    });
 }
 
 void svt_library_scan_free(svt_library_scan* s)
@@ -2348,6 +2490,12 @@ void inflate_round_host(const Round& r, uint8_t* dst, unsigned n_threads, bool o
                     zs.avail_out = (uInt)mb.isize;
                     status[k] = inflate(&zs, Z_FINISH) == Z_STREAM_END && zs.avail_out == 0 ? inf::INF_OK : inf::INF_INPUT;
                 } else status[k] = inf::INF_INPUT;
+                if (r.verify && status[k] == inf::INF_OK) {
+                    const auto t0 = std::chrono::steady_clock::now();
+                    const bool same = host_crc32(out, mb.isize) == inf::member_crc(cdata, 0, mb.clen);
+                    if (!same) status[k] = inf::INF_CRC;
+                    r.verify->add(1, same ? 0 : 1, std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(), 0.0);
+                }
             }
         }
         if (fd) fast_inflate().release(fd);
@@ -2416,6 +2564,7 @@ int scan_libraries(const svt_bam* bam, uint32_t n_libs, const uint32_t* rg_count
     for (;;) {
         t0 = std::chrono::steady_clock::now();
         if (const uint32_t reason = planner.plan(r)) return host_answer(reason);
+        r.verify = bam_verify(bam);
         S.index_s += seconds_since(t0);
         ++S.rounds;
         S.segments += r.segments.size();
@@ -2522,6 +2671,7 @@ int svt_bam_scan_libraries_walk_host(const svt_bam* bam, uint32_t n_libs, const 
                                      int64_t num_samp, uint64_t round_bytes, svt_library_scan* out, svt_library_scan_stats* stats)
 {
     return guarded([&] {
+        svt::VerifyScope verify_scope(bam);
         svt::lw::HostBackend backend;
         return svt::lw::scan_libraries(bam, n_libs, rg_counts, read_groups, num_samp, round_bytes, backend, out, stats);
     });

@@ -67,6 +67,7 @@
 #include "svt_geometry_kernel.h"
 #include "svt_evidence_kernel.h"
 #include "svt_inflate_kernel.h"
+#include "svt_crc32_kernel.h"
 #include "svt_evidence_arena.h"
 #include "svt_library_kernel.h"
 #include "svt_library_arena.h"

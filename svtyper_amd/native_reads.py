@@ -9,6 +9,7 @@ Python object is created at all.
 from __future__ import annotations
 
 import ctypes as C
+import threading
 from typing import Dict, Optional, Sequence, Tuple
 
 import numpy as np
@@ -109,7 +110,24 @@ def deep_stats() -> dict:
     return st.as_dict()
 
 
-INFLATE_REASONS = {1: "input", 2: "btype", 3: "stored", 4: "lengths", 5: "symbol", 6: "distance", 7: "output", 8: "short", 9: "member"}
+INFLATE_REASONS = {1: "input", 2: "btype", 3: "stored", 4: "lengths", 5: "symbol", 6: "distance", 7: "output", 8: "short", 9: "member",
+                   10: "crc"}
+INFLATE_CRC = 10
+
+
+class _VerifyStats(C.Structure):
+    """include/svtyper_reads.h: svt_bgzf_verify_counts"""
+    _fields_ = [("members_verified", C.c_uint64), ("members_failed", C.c_uint64), ("host_crc_s", C.c_double), ("device_crc_s", C.c_double)]
+
+    def as_dict(self) -> dict:
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+def verify_stats() -> dict:
+    """svt_bgzf_verify_stats: what verify did in this thread's last call that took a BAM handle"""
+    st = _VerifyStats()
+    hip._check(_lib().svt_bgzf_verify_stats(C.byref(st)))
+    return st.as_dict()
 
 
 class _InflateStats(C.Structure):
@@ -173,6 +191,20 @@ def _lib():
         L.svt_bgzf_inflate_host.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
         L.svt_bgzf_inflate_device.restype = C.c_int
         L.svt_bgzf_inflate_device.argtypes = L.svt_bgzf_inflate_host.argtypes + [C.c_int]
+        L.svt_bgzf_inflate_host_verified.restype = C.c_int
+        L.svt_bgzf_inflate_host_verified.argtypes = L.svt_bgzf_inflate_host.argtypes
+        L.svt_bgzf_inflate_device_verified.restype = C.c_int
+        L.svt_bgzf_inflate_device_verified.argtypes = L.svt_bgzf_inflate_device.argtypes
+        L.svt_bgzf_crc32_host.restype = C.c_int
+        L.svt_bgzf_crc32_host.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
+        L.svt_bgzf_crc32_device.restype = C.c_int
+        L.svt_bgzf_crc32_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_int]
+        L.svt_bam_set_verify.restype = C.c_int
+        L.svt_bam_set_verify.argtypes = [C.c_void_p, C.c_int]
+        L.svt_bam_get_verify.restype = C.c_int
+        L.svt_bam_get_verify.argtypes = [C.c_void_p]
+        L.svt_bgzf_verify_stats.restype = C.c_int
+        L.svt_bgzf_verify_stats.argtypes = [C.POINTER(_VerifyStats)]
         L.svt_evidence_device_deep_stats.restype = C.c_int
         L.svt_evidence_device_deep_stats.argtypes = [C.POINTER(_DeepStats)]
         L.svt_debug_batch_records.restype = C.c_int
@@ -198,11 +230,16 @@ def _lib():
 class NativeBam:
     """An indexed BAM opened by the C++ reader."""
 
-    def __init__(self, path: str):
+    def __init__(self, path: str, verify: bool = False):
         L = _lib()
         self._L = L
         self._h = C.c_void_p()
         hip._check(L.svt_bam_open(path.encode(), C.byref(self._h)))
+        # svt_bgzf_verify_stats summed over this object's calls (each read on the thread that made the call)
+        self.verify_stats = {"members_verified": 0, "members_failed": 0, "host_crc_s": 0.0, "device_crc_s": 0.0}
+        self._verify_lock = threading.Lock()
+        if verify:
+            self.verify = True
         self.filename = path
         n = L.svt_bam_n_references(self._h)
         self.references = tuple(L.svt_bam_reference_name(self._h, i).decode() for i in range(n))
@@ -216,6 +253,24 @@ class NativeBam:
             parts = line.split("\t")
             rec = {f[:2]: f[3:] for f in parts[1:] if len(f) >= 3 and f[2] == ":"}
             self.header.setdefault(parts[0][1:], []).append(rec)
+
+    @property
+    def verify(self) -> bool:
+        """svt_bam_get_verify / svt_bam_set_verify: every call on this handle checks the CRC32 of the BGZF members it inflates"""
+        return bool(self._L.svt_bam_get_verify(self._h))
+
+    @verify.setter
+    def verify(self, on: bool) -> None:
+        hip._check(self._L.svt_bam_set_verify(self._h, 1 if on else 0))
+
+    def _call(self, rc: int) -> None:
+        """hip._check for a call that took the handle: its share of the verify figures is noted first, also when it failed"""
+        st = _VerifyStats()
+        if self._L.svt_bgzf_verify_stats(C.byref(st)) == 0 and (st.members_verified or st.members_failed):
+            with self._verify_lock:
+                for k, v in st.as_dict().items():
+                    self.verify_stats[k] += v
+        hip._check(rc)
 
     def gettid(self, name: str) -> int:
         return self._tid.get(name, -1)
@@ -236,7 +291,7 @@ class NativeBam:
         the three scans of Library.from_bam (svtyper/parsers.py:501-576) in C++."""
         names = (C.c_char_p * max(1, len(read_groups)))(*[rg.encode() for rg in read_groups])
         out = _LibraryScan()
-        hip._check(self._L.svt_bam_scan_library(self._h, len(read_groups), names, int(num_samp), C.byref(out)))
+        self._call(self._L.svt_bam_scan_library(self._h, len(read_groups), names, int(num_samp), C.byref(out)))
         try:
             n = int(out.n_hist)
             keys = np.ctypeslib.as_array(out.hist_keys, shape=(max(n, 1),))[:n].tolist()
@@ -269,7 +324,7 @@ class NativeBam:
             rc = self._L.svt_bam_scan_libraries_device(self._h, n_libs, counts, names, int(num_samp), int(round_bytes),
                                                        1 if inflate == "device" else 0, int(device), out, C.byref(st))
         self.library_scan_stats = st.as_dict()
-        hip._check(rc)
+        self._call(rc)
         try:
             result = []
             for l in range(n_libs):
@@ -302,7 +357,7 @@ class NativeBam:
                   -1 if max_reads is None else int(max_reads), int(count_mode), int(n_threads))
         g = _EvidenceParams(len(lib_flank), flank, int(min_aligned), int(split_slop))
         out = _Evidence()
-        hip._check(self._L.svt_bam_evidence(self._h, C.byref(a), C.byref(g), C.byref(out)))
+        self._call(self._L.svt_bam_evidence(self._h, C.byref(a), C.byref(g), C.byref(out)))
         owner = _EvidenceOwner(self._L, out)    # frees the C buffers when the arrays below are gone
         off = np.ctypeslib.as_array(out.rec_offset, shape=(n + 1,)).copy()
         total = int(off[-1])
@@ -347,7 +402,7 @@ class NativeBam:
         out = _Evidence()
         flagged = np.zeros(max(n, 1), np.uint8)
         kept = np.zeros(max(n, 1), np.uint32)
-        hip._check(getattr(self._L, _entry)(self._h, C.byref(a), C.byref(g), C.byref(out), flagged.ctypes.data, kept.ctypes.data))
+        self._call(getattr(self._L, _entry)(self._h, C.byref(a), C.byref(g), C.byref(out), flagged.ctypes.data, kept.ctypes.data))
         try:
             off = np.ctypeslib.as_array(out.rec_offset, shape=(n + 1,)).copy()
             total = int(off[-1])
@@ -381,14 +436,14 @@ class NativeBam:
         st = _DeviceStats()
         if inflate == "device":
             ist = _InflateStats()
-            hip._check(self._L.svt_bam_evidence_device_inflate(self._h, C.byref(a), C.byref(g), C.byref(cb), int(device), int(flags),
+            self._call(self._L.svt_bam_evidence_device_inflate(self._h, C.byref(a), C.byref(g), C.byref(cb), int(device), int(flags),
                                                                C.byref(handle), skipped.ctypes.data, C.byref(st), C.byref(ist),
                                                                1 if count_host_blocks else 0))
             stats = st.as_dict()
             stats["inflate"] = ist.as_dict()
             stats["deep"] = deep_stats()
             return hip.DeviceBatch.adopt(handle, n, int(st.n_records), device), skipped[:n], stats
-        hip._check(self._L.svt_bam_evidence_device(self._h, C.byref(a), C.byref(g), C.byref(cb), int(device), int(flags),
+        self._call(self._L.svt_bam_evidence_device(self._h, C.byref(a), C.byref(g), C.byref(cb), int(device), int(flags),
                                                    C.byref(handle), skipped.ctypes.data, C.byref(st)))
         stats = st.as_dict()
         stats["deep"] = deep_stats()
@@ -408,7 +463,7 @@ class NativeBam:
         a = _Args(n, windows.ctypes.data, breakpoints.ctypes.data, len(read_groups), names, libs,
                   -1 if max_reads is None else int(max_reads), int(count_mode), int(n_threads))
         out = _Summaries()
-        hip._check(self._L.svt_bam_summarise(self._h, C.byref(a), C.byref(out)))
+        self._call(self._L.svt_bam_summarise(self._h, C.byref(a), C.byref(out)))
         owner = _SummariesOwner(self._L, out)   # frees the C buffers when the arrays below are gone
         off = np.ctypeslib.as_array(out.frag_offset, shape=(n + 1,)).copy()
         total = int(off[-1])
@@ -475,10 +530,61 @@ def bgzf_members(data: bytes) -> Tuple[np.ndarray, np.ndarray]:
     return np.array(offs, np.uint64), np.array(sizes, np.uint64)
 
 
-def bgzf_inflate(data: bytes, block_off: np.ndarray, out_off: np.ndarray, device: Optional[int] = None) -> Tuple[np.ndarray, np.ndarray]:
+def bgzf_crc32(data, off: np.ndarray, device: Optional[int] = None) -> np.ndarray:
+    """svt_bgzf_crc32_host (device None) / svt_bgzf_crc32_device: the CRC-32 of data[off[k] .. off[k + 1]) for every k, by the
+    one-source code of svt_crc32.h.  For the device `data` is put into HBM first: the entry point takes a device pointer."""
+    L = _lib()
+    off = np.ascontiguousarray(off, np.uint64)
+    n = int(off.shape[0]) - 1
+    if n < 0:
+        raise ValueError("off must hold n + 1 entries")
+    crc = np.zeros(max(n, 1), np.uint32)
+    if device is None:
+        buf = np.frombuffer(bytes(data), np.uint8) if len(data) else np.zeros(1, np.uint8)
+        hip._check(L.svt_bgzf_crc32_host(buf.ctypes.data, off.ctypes.data, n, crc.ctypes.data))
+        return crc[:n]
+    host = np.frombuffer(bytes(data), np.uint8) if len(data) else np.zeros(1, np.uint8)
+    rt = _hip_runtime()
+    ptr = C.c_void_p()
+    _hip_ok(rt.hipSetDevice(int(device)), "hipSetDevice")
+    _hip_ok(rt.hipMalloc(C.byref(ptr), C.c_size_t(max(host.size, 16))), "hipMalloc")
+    try:
+        _hip_ok(rt.hipMemcpy(ptr, C.c_void_p(host.ctypes.data), C.c_size_t(host.size), 1), "hipMemcpy")     # hipMemcpyHostToDevice
+        hip._check(L.svt_bgzf_crc32_device(ptr, off.ctypes.data, n, crc.ctypes.data, int(device)))
+    finally:
+        rt.hipFree(ptr)
+    return crc[:n]
+
+
+_hip_rt = None
+
+
+def _hip_runtime():
+    """the HIP runtime libsvtyper_hip.so is linked against, as this process has it loaded (bgzf_crc32 puts its bytes into HBM
+    itself: svt_bgzf_crc32_device takes a device pointer)"""
+    global _hip_rt
+    if _hip_rt is None:
+        _lib()
+        path = next((line.split()[-1] for line in open("/proc/self/maps") if "libamdhip64" in line), "libamdhip64.so")
+        _hip_rt = C.CDLL(path)
+        _hip_rt.hipMalloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
+        _hip_rt.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
+        _hip_rt.hipFree.argtypes = [C.c_void_p]
+        _hip_rt.hipSetDevice.argtypes = [C.c_int]
+    return _hip_rt
+
+
+def _hip_ok(rc: int, what: str) -> None:
+    if rc != 0:
+        raise hip.SvtyperHipError("%s failed with HIP error %d" % (what, rc))
+
+
+def bgzf_inflate(data: bytes, block_off: np.ndarray, out_off: np.ndarray, device: Optional[int] = None,
+                 verified: bool = False) -> Tuple[np.ndarray, np.ndarray]:
     """svt_bgzf_inflate_host (device None) / svt_bgzf_inflate_device: the members of `data` at `block_off` inflated by the
     one-source decoder (svt_inflate.h) to out_off[k] .. out_off[k + 1].  Returns (bytes uint8 [out_off[-1]], status uint32 [n]:
-    0 or an INFLATE_REASONS key -- the bytes of such a member are undefined)."""
+    0 or an INFLATE_REASONS key -- the bytes of such a member are undefined).  `verified`: the _verified entry points, which
+    also check every member's CRC-32 (INFLATE_CRC)."""
     L = _lib()
     block_off = np.ascontiguousarray(block_off, np.uint64)
     out_off = np.ascontiguousarray(out_off, np.uint64)
@@ -490,7 +596,7 @@ def bgzf_inflate(data: bytes, block_off: np.ndarray, out_off: np.ndarray, device
     status = np.zeros(max(n, 1), np.uint32)
     args = [buf.ctypes.data, len(data), block_off.ctypes.data, n, out.ctypes.data, out_off.ctypes.data, status.ctypes.data]
     if device is None:
-        hip._check(L.svt_bgzf_inflate_host(*args))
+        hip._check((L.svt_bgzf_inflate_host_verified if verified else L.svt_bgzf_inflate_host)(*args))
     else:
-        hip._check(L.svt_bgzf_inflate_device(*args, int(device)))
+        hip._check((L.svt_bgzf_inflate_device_verified if verified else L.svt_bgzf_inflate_device)(*args, int(device)))
     return out[:int(out_off[-1])], status[:n]

@@ -135,6 +135,27 @@ def check_inflate(reader: str, inflate: str) -> str:
     return inflate
 
 
+def check_verify(verify: str) -> bool:
+    """`verify`: "off" (default) or "crc32" -- the CRC32 of every BGZF block is checked where the block is inflated: zlib.crc32 in the
+    Python reader, the C++ reader's threads, or svt_crc32_kernel behind svt_inflate_kernel with inflate="device"
+    (svt_bam_set_verify).  A mismatch raises with "BGZF block at offset N: CRC32 mismatch ...".  Legal with every reader."""
+    if verify not in ("off", "crc32"):
+        raise ValueError("verify must be 'off' or 'crc32'")
+    return verify == "crc32"
+
+
+def verify_stats(native_bams, python_bams=()) -> dict:
+    """the `stats["verify"]` entry of the drivers: svt_bgzf_verify_stats summed over the run's native calls (and the blocks the
+    Python reader checked)"""
+    out = {"members_verified": 0, "members_failed": 0, "host_crc_s": 0.0, "device_crc_s": 0.0}
+    for nb in native_bams or ():
+        for k, v in nb.verify_stats.items():
+            out[k] += v
+    for b in python_bams or ():
+        out["members_verified"] += getattr(getattr(b, "_bgzf", None), "members_verified", 0)
+    return out
+
+
 def check_library_scan(reader: str, library_scan: str) -> str:
     """`library_scan`: who builds the libraries of a BAM that comes without a library file -- "host" (default: three scans per
     library) or "device" (svt_bam_scan_libraries_device: one segmented walk on the GPU for all libraries; its BGZF members are inflated

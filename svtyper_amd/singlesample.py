@@ -21,7 +21,7 @@ from . import evidence as ev
 from .bam import open_alignment_file
 from .library import Sample, setup_sample, write_sample_json
 from .pipeline import (MIN_LIB_PREVALENCE, BulkFeeder, block_chars, ChunkPipeline, NativeUnitCollector, split_lines, SampleColumnWriter, UnitCollector, add_read_to,
-                       default_engine, check_inflate, check_library_scan, fetch_window, resolve_reader)
+                       default_engine, check_inflate, check_library_scan, check_verify, verify_stats, fetch_window, resolve_reader)
 from .results import results_to_dicts
 from .vcf import Variant, Vcf
 
@@ -128,16 +128,17 @@ def assign_genotype(variant: Variant, sample_name: str, res: dict) -> None:
 
 def sso_genotype(bam_string, vcf_in, vcf_out, min_aligned, split_weight, disc_weight, num_samp, lib_info_path,
                  debug, ref_fasta, sum_quals, max_reads, max_ci_dist, cores, batch_size, *, engine=None, geometry="host",
-                 reader=None, stats=None, inflate="host", library_scan="host"):
+                 reader=None, stats=None, inflate="host", library_scan="host", verify="off"):
     if vcf_in is None:
         return
     reader = resolve_reader(reader)
     check_inflate(reader, inflate)
     check_library_scan(reader, library_scan)
+    verify_on = check_verify(verify)
     full_bam_path = os.path.abspath(bam_string)
     if not (full_bam_path.endswith(".bam") or full_bam_path.endswith(".cram")):
         sys.exit("Error: %s is not a valid alignment file (*.bam or *.cram)\n" % full_bam_path)
-    bam = open_alignment_file(full_bam_path, ref_fasta)
+    bam = open_alignment_file(full_bam_path, ref_fasta, verify=verify_on)
 
     lib_info = None
     if lib_info_path is not None and os.path.exists(lib_info_path):
@@ -147,7 +148,7 @@ def sso_genotype(bam_string, vcf_in, vcf_out, min_aligned, split_weight, disc_we
     native = None
     if reader in ("native", "device"):      # C++ reader: library scans now, fetch + fragment summaries later
         from .native_reads import COUNT_SSO, NativeBam
-        native = NativeBam(full_bam_path)
+        native = NativeBam(full_bam_path, verify=verify_on)
     if library_scan == "device" and lib_info is None and engine is None:
         engine = default_engine()               # (the scan runs on the device the pass will use)
     sample = setup_sample(bam, lib_info, num_samp, MIN_LIB_PREVALENCE, native, library_scan, getattr(engine, "device", 0) if library_scan == "device" else 0, inflate)
@@ -324,6 +325,7 @@ def sso_genotype(bam_string, vcf_in, vcf_out, min_aligned, split_weight, disc_we
         stats.update(bulk_stats[0] if bulk_stats else {}, route=bulk_stats[1] if bulk_stats else "per line")
         if reader == "device":      # the counters of svt_bam_evidence_device, summed over the run's calls
             stats["device_reader"] = collector.device_stats
+        stats["verify"] = verify_stats([native], ()) if native is not None else verify_stats([], [bam])
     sample.close()
 
 
@@ -369,6 +371,8 @@ def get_args():
     p.add_argument("--inflate", choices=("host", "device"), default="host",
                    help="with --reader device: BGZF blocks inflated by the reader's threads, or on the GPU from the "
                         "compressed blocks (same output bytes) [host]")
+    p.add_argument("--verify-bgzf", dest="verify_bgzf", action="store_true",
+                   help="check the CRC32 of every BGZF block where it is inflated (verify='crc32'); a mismatch is an error")
     p.add_argument("--library-scan", dest="library_scan", choices=("host", "device"), default="host",
                    help="without a library file: the libraries' read length, insert-size histogram and prevalence from three "
                         "scans per library on the host, or from one segmented walk on the GPU for all libraries, members inflated as --inflate says "
@@ -391,13 +395,15 @@ def main():
     from . import sharded
     job = sharded.job()
     if job is None:
-        return sso_genotype(*call, geometry=args.geometry, reader=args.reader, inflate=args.inflate, library_scan=args.library_scan)
+        return sso_genotype(*call, geometry=args.geometry, reader=args.reader, inflate=args.inflate, library_scan=args.library_scan,
+                            verify="crc32" if args.verify_bgzf else "off")
     # launched by torch.distributed.run with several ranks: one GPU each, variants sharded, one gather
     rank, world, local_rank = job
     call = call[:2] + (sharded.private_stdout(call[2]),) + call[3:]
     engine = sharded.init(local_rank)
     sharded.sso_genotype_sharded(*call, rank=rank, world=world, engine=engine, geometry=args.geometry,
-                                 reader=args.reader, inflate=args.inflate, library_scan=args.library_scan)
+                                 reader=args.reader, inflate=args.inflate, library_scan=args.library_scan,
+                            verify="crc32" if args.verify_bgzf else "off")
     sharded.finish()
 
 
