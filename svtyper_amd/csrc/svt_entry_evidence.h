@@ -1,65 +1,6 @@
 // svt_entry_evidence.h -- part of the single translation unit svtyper_hip.hip (included there, in order; not a stand-alone header):
-// C ABI: svt_bam_evidence_device, svt_bam_evidence_device_inflate, svt_bgzf_inflate_device (include/svtyper_reads.h) and the
-// read-back of a resident batch's records for the parity tests.
-
-// svt_crc32_kernel over `n` jobs on `bytes`: a grid sized to the device (its waves stage the tables once and loop over the jobs)
-static int launch_crc_kernel(const uint8_t* d_bytes, uint64_t bytes_len, const crc::Job* d_jobs, uint64_t n, const crc::Tables* d_tables,
-                             uint32_t* d_crc, uint32_t* d_status, int device, hipStream_t s)
-{
-    if (!n) return SVT_OK;
-    const uint64_t waves = (uint64_t)std::max<uint32_t>(cu_count(device), 1) * kCrcWavesPerCu;
-    hipLaunchKernelGGL(svt_crc32_kernel, dim3((unsigned)std::min(n, waves)), dim3(kCrcBlock), 0, s, d_bytes, bytes_len, d_jobs, (uint32_t)n, d_tables, d_crc,
-                       d_status);
-    HIP_TRY(hipGetLastError());
-    return SVT_OK;
-}
-
-// What verify adds to an inflate launch: the jobs (a member's place in the arena and the CRC-32 its trailer stores) and the
-// tables in HBM, and where the figures go.  Null jobs: no verify, nothing is launched.
-struct CrcCheck {
-    const crc::Job* d_jobs = nullptr;
-    const crc::Tables* d_tables = nullptr;
-    int device = 0;
-    VerifyTally* tally = nullptr;
-};
-
-// the jobs and the tables of a verified call into HBM (its buffers live as long as `d_jobs` / `d_tables`)
-static int upload_crc_check(const std::vector<crc::Job>& jobs, DevScratch& d_jobs, DevScratch& d_tables, Stager& st)
-{
-    SVT_TRY(upload(d_jobs, jobs, st));
-    SVT_TRY(d_tables.alloc(sizeof(crc::Tables)));
-    return st.copy(d_tables.p, &crc_tables(), sizeof(crc::Tables));
-}
-
-// `n` members of the compressed bytes at d_src into d_dst, one wavefront each; the statuses come back in `status`.  With a
-// check svt_crc32_kernel runs behind it over the same statuses (inf::INF_CRC), in a launch of its own that is timed apart.
-static int run_inflate_kernel(const uint8_t* d_src, uint64_t src_len, const inf::Member* d_members, uint64_t n, uint8_t* d_dst, uint64_t dst_len,
-                              uint32_t* d_status, std::vector<uint32_t>& status, hipStream_t s, const CrcCheck& check = CrcCheck())
-{
-    status.assign(n, 0);
-    if (n > 0xFFFFFFFFull) return fail(SVT_ERR_INVALID, "too many BGZF members in one call (< 2^32)");
-    constexpr uint64_t kGrid = 1u << 30;
-    for (uint64_t at = 0; at < n; at += kGrid) {
-        const uint64_t m = std::min(kGrid, n - at);
-        hipLaunchKernelGGL(svt_inflate_kernel, dim3((unsigned)m), dim3(kInflateBlock), 0, s, d_src, src_len, d_members + at, (uint32_t)m, d_dst, dst_len,
-                           d_status + at);
-        HIP_TRY(hipGetLastError());
-    }
-    std::chrono::steady_clock::time_point t_crc;
-    if (check.d_jobs && n) {
-        HIP_TRY(hipStreamSynchronize(s));                        // (only so that the CRC's time is its own)
-        t_crc = std::chrono::steady_clock::now();
-        SVT_TRY(launch_crc_kernel(d_dst, dst_len, check.d_jobs, n, check.d_tables, nullptr, d_status, check.device, s));
-    }
-    if (n) HIP_TRY(hipMemcpyAsync(status.data(), d_status, n * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    if (check.d_jobs && n && check.tally) {
-        uint64_t verified = 0, failed = 0;                       // (a member that did not inflate was not looked at)
-        for (uint32_t st : status) { verified += st == inf::INF_OK || st == inf::INF_CRC; failed += st == inf::INF_CRC; }
-        check.tally->add(verified, failed, 0.0, std::chrono::duration<double>(std::chrono::steady_clock::now() - t_crc).count());
-    }
-    return SVT_OK;
-}
+// C ABI: svt_bam_evidence_device, svt_bam_evidence_device_inflate (include/svtyper_reads.h) and the read-back of a resident
+// batch's records for the parity tests.  (Device inflate of the arena's members is svt_entry_inflate.h.)
 
 // the deep tier's figures of this thread's last device-reader call (svt_evidence_device_deep_stats)
 static thread_local svt_evidence_deep_stats g_deep_stats{};
@@ -86,7 +27,7 @@ struct EvidenceCall : CallStream {
     svt_evidence_deep_stats& DS = g_deep_stats;
     const uint64_t n = args->n_units;
     Pooled d_arena{device}, d_records{device}, d_compressed{device};
-    DevScratch d_members, d_member_status, d_crc_jobs, d_crc_tables;   // (the last two: verify only)
+    DeviceInflate inflate{device};                           // inflate = "device": the members of `plan`
     DevScratch d_ranges, d_units, d_windows, d_bps, d_rgs, d_refs, d_blob, d_flank, d_status, d_rows, d_reads, d_off, d_src, d_src_off, d_dst_off;
     DevScratch d_deep_unit, d_deep_status, d_deep_rows, d_deep_workspace;   // only a call with deep units allocates these
 
@@ -125,9 +66,9 @@ struct EvidenceCall : CallStream {
             }
             SVT_TRY(ew::build_arena_open(bam, args, geometry, arena, plan));
             I.host_index_s = plan.index_s;
-            I.blocks_inflated = plan.members.size();
-            I.compressed_bytes = plan.compressed_bytes;
-            I.inflated_bytes = plan.arena_bytes;
+            I.blocks_inflated = plan.set.members.size();
+            I.compressed_bytes = plan.set.compressed_bytes;
+            I.inflated_bytes = plan.set.arena_bytes;
         } else SVT_TRY(ew::build_arena(bam, args, geometry, arena));
         S.host_arena_s = arena.build_s;
         S.reads_walked = arena.records_in_ranges;
@@ -145,23 +86,13 @@ struct EvidenceCall : CallStream {
             if (route.device_inflate()) {
                 // the compressed members from the mapping, the inflate kernel, the statuses; a unit over a failed member is the host's
                 svt_evidence_inflate_stats& I = *route.inflate_stats;
-                SVT_TRY(d_compressed.get(plan.compressed_bytes + 8));
-                for (const auto& sp : plan.spans) SVT_TRY(st.copy(static_cast<uint8_t*>(d_compressed.p) + sp.at, plan.file + sp.file_off, sp.bytes));
-                SVT_TRY(upload(d_members, plan.members, st));
-                SVT_TRY(d_member_status.alloc(plan.members.size() * sizeof(uint32_t)));
-                CrcCheck check;
-                if (VerifyTally* tally = bam_verify(bam)) {       // the expected CRC-32s go up with the member table
-                    std::vector<crc::Job> jobs;
-                    plan.crc_jobs(jobs);
-                    SVT_TRY(upload_crc_check(jobs, d_crc_jobs, d_crc_tables, st));
-                    check = CrcCheck{d_crc_jobs.as<crc::Job>(), d_crc_tables.as<crc::Tables>(), device, tally};
-                }
+                SVT_TRY(d_compressed.get(plan.set.compressed_bytes + 8));
+                SVT_TRY(inflate.upload(plan.set, d_compressed.p, st, bam_verify(bam)));   // (verify: the expected CRC-32s go up with the member table)
                 SVT_TRY(st.finish());
                 I.compressed_upload_s = since(t0);
                 const auto t_kernel = now();
                 std::vector<uint32_t> member_status;
-                SVT_TRY(run_inflate_kernel(static_cast<const uint8_t*>(d_compressed.p), plan.compressed_bytes, d_members.as<inf::Member>(), plan.members.size(),
-                                           static_cast<uint8_t*>(d_arena.p), plan.arena_bytes, d_member_status.as<uint32_t>(), member_status, s, check));
+                SVT_TRY(inflate.run(d_compressed.p, d_arena.p, s, member_status));
                 I.inflate_kernel_s = since(t_kernel);
                 I.blocks_failed = ew::apply_member_status(plan, member_status, arena);
             } else SVT_TRY(st.copy(d_arena.p, arena.bytes.data(), arena.bytes.size()));
@@ -176,7 +107,7 @@ struct EvidenceCall : CallStream {
             SVT_TRY(upload(d_blob, arena.blob, st));
             SVT_TRY(upload(d_flank, flank, st));
             SVT_TRY(st.finish());
-            S.bytes_uploaded = (route.device_inflate() ? plan.compressed_bytes + plan.members.size() * sizeof(inf::Member) : arena.bytes.size()) + arena.ranges.size() * sizeof(ew::Range) + n * (sizeof(ew::UnitRanges) + sizeof(svt_fetch_unit) + sizeof(svt_breakpoint)) + arena.blob.size();
+            S.bytes_uploaded = (route.device_inflate() ? plan.set.compressed_bytes + plan.set.members.size() * sizeof(inf::Member) : arena.bytes.size()) + arena.ranges.size() * sizeof(ew::Range) + n * (sizeof(ew::UnitRanges) + sizeof(svt_fetch_unit) + sizeof(svt_breakpoint)) + arena.blob.size();
         }
         SVT_TRY(d_status.alloc(n * sizeof(uint32_t)));
         SVT_TRY(d_rows.alloc(n * sizeof(uint32_t)));
@@ -419,88 +350,6 @@ int svt_evidence_device_deep_stats(svt_evidence_deep_stats* out)
     return guarded([&]() -> int {
         if (!out) return fail(SVT_ERR_INVALID, "null argument");
         *out = g_deep_stats;
-        return SVT_OK;
-    });
-}
-
-// the parity entry of the inflate kernel: upload, one wavefront per member, download
-static int svt_bgzf_inflate_device_impl(const uint8_t* data, uint64_t len, const uint64_t* block_off, uint64_t n, uint8_t* out,
-                                        const uint64_t* out_off, uint32_t* status, int device, bool verify)
-{
-    {
-        if (n && (!status || (!out && out_off && out_off[n]))) return fail(SVT_ERR_INVALID, "null argument");
-        std::vector<inf::Member> members(n);
-        SVT_TRY(ew::bgzf_members(data, len, block_off, n, out_off, members.data()));
-        SVT_TRY(select_device(device));
-        if (n == 0) return SVT_OK;
-        struct InflateCall : CallStream {                        // (destruction order: CallStream, svt_batch_state.h)
-            DevScratch d_src, d_dst, d_members, d_status, d_crc_jobs, d_crc_tables;
-            ~InflateCall() { drain(); }
-        } c;
-        CrcCheck check;
-        SVT_TRY(c.take());
-        const uint64_t out_len = out_off[n];
-        SVT_TRY(c.d_src.alloc(len));
-        SVT_TRY(c.d_dst.alloc(out_len));
-        SVT_TRY(c.d_status.alloc(n * sizeof(uint32_t)));
-        {
-            Stager st(c.s);
-            SVT_TRY(st.copy(c.d_src.p, data, len));
-            SVT_TRY(upload(c.d_members, members, st));
-            if (verify) {
-                std::vector<crc::Job> jobs(n);
-                for (uint64_t k = 0; k < n; ++k) {
-                    const inf::Member& m = members[k];             // (a member that is none fails in the inflate kernel: its job is not looked at)
-                    jobs[k] = m.isize == inf::kNoMember ? crc::Job{0, 0, 0} : crc::Job{m.dst, m.isize, inf::member_crc(data, m.src, m.clen)};
-                }
-                SVT_TRY(upload_crc_check(jobs, c.d_crc_jobs, c.d_crc_tables, st));
-                check = CrcCheck{c.d_crc_jobs.as<crc::Job>(), c.d_crc_tables.as<crc::Tables>(), device, nullptr};
-            }
-            SVT_TRY(st.finish());
-        }
-        std::vector<uint32_t> st_host;
-        SVT_TRY(run_inflate_kernel(c.d_src.as<uint8_t>(), len, c.d_members.as<inf::Member>(), n, c.d_dst.as<uint8_t>(), out_len, c.d_status.as<uint32_t>(), st_host, c.s,
-                                   check));
-        std::memcpy(status, st_host.data(), n * sizeof(uint32_t));
-        if (out_len) SVT_TRY(d2h_staged(out, c.d_dst.p, out_len, c.s));
-        return SVT_OK;
-    }
-}
-
-int svt_bgzf_inflate_device(const uint8_t* data, uint64_t len, const uint64_t* block_off, uint64_t n, uint8_t* out, const uint64_t* out_off,
-                            uint32_t* status, int device)
-{
-    return guarded([&] { return svt_bgzf_inflate_device_impl(data, len, block_off, n, out, out_off, status, device, false); });
-}
-
-int svt_bgzf_inflate_device_verified(const uint8_t* data, uint64_t len, const uint64_t* block_off, uint64_t n, uint8_t* out,
-                                     const uint64_t* out_off, uint32_t* status, int device)
-{
-    return guarded([&] { return svt_bgzf_inflate_device_impl(data, len, block_off, n, out, out_off, status, device, true); });
-}
-
-// svt_crc32_kernel over bytes that are in HBM already: the jobs and the tables go up, the CRCs come back
-int svt_bgzf_crc32_device(const uint8_t* bytes, const uint64_t* off, uint64_t n, uint32_t* crc, int device)
-{
-    return guarded([&]() -> int {
-        SVT_TRY(crc_check_offsets(bytes, off, n, crc));
-        SVT_TRY(select_device(device));
-        if (n == 0) return SVT_OK;
-        struct CrcCall : CallStream {                            // (destruction order: CallStream, svt_batch_state.h)
-            DevScratch d_jobs, d_tables, d_crc;
-            ~CrcCall() { drain(); }
-        } c;
-        SVT_TRY(c.take());
-        std::vector<crc::Job> jobs(n);
-        for (uint64_t k = 0; k < n; ++k) jobs[k] = crc::Job{off[k], (uint32_t)(off[k + 1] - off[k]), 0};
-        SVT_TRY(c.d_crc.alloc(n * sizeof(uint32_t)));
-        {
-            Stager st(c.s);
-            SVT_TRY(upload_crc_check(jobs, c.d_jobs, c.d_tables, st));
-            SVT_TRY(st.finish());
-        }
-        SVT_TRY(launch_crc_kernel(bytes, off[n], c.d_jobs.as<crc::Job>(), n, c.d_tables.as<crc::Tables>(), c.d_crc.as<uint32_t>(), nullptr, device, c.s));
-        SVT_TRY(d2h_staged(crc, c.d_crc.p, n * sizeof(uint32_t), c.s));
         return SVT_OK;
     });
 }

@@ -5,36 +5,19 @@
 
 extern "C++" {
 
-// a device buffer that is kept from round to round and grows when a round needs more
-struct GrowBuffer {
-    DevScratch d;
-    size_t cap = 0;
-    int need(size_t bytes)
-    {
-        if (bytes <= cap && d.p) return SVT_OK;
-        if (d.p) { HIP_TRY(hipFree(d.p)); d.p = nullptr; cap = 0; }
-        const size_t want = bytes + bytes / 8 + 64;
-        SVT_TRY(d.alloc(want));
-        cap = want;
-        return SVT_OK;
-    }
-    template <typename T> T* as() const { return d.as<T>(); }
-};
-
 // Destruction order (CallStream, svt_batch_state.h): ~LibraryCall drains the stream, then the buffers are freed, then the stream
 // is returned.
 struct LibraryCall : CallStream, lw::Backend {
     const bool inflate_on_device;
-    GrowBuffer d_arena, d_compressed, d_members, d_member_status, d_segments, d_counts, d_caps, d_crc_jobs;
-    DevScratch d_crc_tables;                                 // verify with inflate on the device: uploaded by the first round
-    int device = 0;
+    GrowBuffer d_arena, d_compressed, d_segments, d_counts, d_caps;
+    DeviceInflate inflate;                                   // inflate on the device: kept from round to round
     DevScratch d_rgs, d_blob, d_dense_count, d_dense_first, d_small, d_overflow;
     std::vector<uint8_t> host_arena;                         // inflate on the host: the round's bytes in front of their upload
     uint64_t arena_len = 0;
     uint32_t n_rgs = 0, n_libs = 0, overflow_cap = 0;
     static constexpr size_t kSmallWords = 2 * lw::kMaxLibs + 1;   // read_length, in_lib, and the overflow counter in the low half of a word
 
-    explicit LibraryCall(bool on_device) : inflate_on_device(on_device) {}
+    LibraryCall(bool on_device, int device) : inflate_on_device(on_device), inflate(device) {}
     ~LibraryCall() override { drain(); }
     static std::chrono::steady_clock::time_point now() { return std::chrono::steady_clock::now(); }
     static double since(std::chrono::steady_clock::time_point t0) { return std::chrono::duration<double>(now() - t0).count(); }
@@ -78,43 +61,28 @@ struct LibraryCall : CallStream, lw::Backend {
     }
     int load(const lw::Round& r, std::vector<uint32_t>& member_status, svt_library_scan_stats& S) override
     {
-        arena_len = r.arena_bytes;
-        SVT_TRY(d_arena.need(r.arena_bytes + 8));
+        arena_len = r.set.arena_bytes;
+        SVT_TRY(d_arena.need(r.set.arena_bytes + 8));
         if (inflate_on_device) {
             auto t0 = now();
-            SVT_TRY(d_compressed.need(r.span_bytes + 8));
-            SVT_TRY(d_members.need(r.members.size() * sizeof(inf::Member)));
-            SVT_TRY(d_member_status.need(r.members.size() * sizeof(uint32_t)));
-            CrcCheck check;
+            SVT_TRY(d_compressed.need(r.set.compressed_bytes + 8));
             {
                 Stager st(s);
-                SVT_TRY(st.copy(d_compressed.d.p, r.file + r.span_off, r.span_bytes));
-                SVT_TRY(st.copy(d_members.d.p, r.members.data(), r.members.size() * sizeof(inf::Member)));
-                if (r.verify) {                                     // the expected CRC-32s go up with the member table
-                    std::vector<crc::Job> jobs;
-                    r.crc_jobs(jobs);
-                    SVT_TRY(d_crc_jobs.need(jobs.size() * sizeof(crc::Job)));
-                    SVT_TRY(st.copy(d_crc_jobs.d.p, jobs.data(), jobs.size() * sizeof(crc::Job)));
-                    if (!d_crc_tables.p) {
-                        SVT_TRY(d_crc_tables.alloc(sizeof(crc::Tables)));
-                        SVT_TRY(st.copy(d_crc_tables.p, &crc_tables(), sizeof(crc::Tables)));
-                    }
-                    check = CrcCheck{d_crc_jobs.as<crc::Job>(), d_crc_tables.as<crc::Tables>(), device, r.verify};
-                }
+                SVT_TRY(inflate.upload(r.set, d_compressed.d.p, st, r.verify));
                 SVT_TRY(st.finish());
             }
             S.upload_s += since(t0);
             t0 = now();
-            SVT_TRY(run_inflate_kernel(d_compressed.as<uint8_t>(), r.span_bytes, d_members.as<inf::Member>(), r.members.size(), d_arena.as<uint8_t>(),
-                                       r.arena_bytes, d_member_status.as<uint32_t>(), member_status, s, check));
+            SVT_TRY(inflate.run(d_compressed.d.p, d_arena.d.p, s, member_status));
             S.inflate_s += since(t0);
         } else {
             auto t0 = now();
-            host_arena.resize(r.arena_bytes + 8);
-            lw::inflate_round_host(r, host_arena.data(), host_threads(), /*one_source=*/false, member_status);
+            host_arena.resize(r.set.arena_bytes + 8);
+            const unsigned nt = std::min<unsigned>(host_threads(), (unsigned)std::max<size_t>(r.set.members.size() / 8, 1));
+            bgzf::inflate_members_host(r.set, host_arena.data(), nt, bgzf::Decoder::library, bgzf::Crc::library, r.verify, member_status);
             S.inflate_s += since(t0);
             t0 = now();
-            SVT_TRY(h2d_staged(d_arena.d.p, host_arena.data(), r.arena_bytes, s));
+            SVT_TRY(h2d_staged(d_arena.d.p, host_arena.data(), r.set.arena_bytes, s));
             S.upload_s += since(t0);
         }
         return SVT_OK;
@@ -174,8 +142,7 @@ int svt_bam_scan_libraries_device(const svt_bam* bam, uint32_t n_libs, const uin
     return guarded([&]() -> int {
         SVT_TRY(select_device(device));
         VerifyScope verify_scope(bam);
-        LibraryCall c(inflate_on_device != 0);
-        c.device = device;
+        LibraryCall c(inflate_on_device != 0, device);
         SVT_TRY(c.take());
         return lw::scan_libraries(bam, n_libs, rg_counts, read_groups, num_samp, round_bytes, c, out, stats);
     });

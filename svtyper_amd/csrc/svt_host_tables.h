@@ -55,8 +55,8 @@ inline void fill_gt_consts(GtConsts& c, double split_weight, double disc_weight)
 }
 
 // (The tables of the CRC-32 check -- the eight byte tables of slicing-by-8 and the powers of x for the lanes' join -- are host-built
-// too: crc::fill_tables in svt_crc32.h, kept once per process by svt::crc_tables() in svt_reads.cpp, which both translation units
-// of the library use; svt_entry_evidence.h uploads them for svt_crc32_kernel.)
+// too: crc::fill_tables in svt_crc32.h, kept once per process by svt::crc_tables() (svt_bgzf.h), which both translation units
+// of the library use; svt_entry_inflate.h uploads them for svt_crc32_kernel.)
 
 struct HostTables {
     std::vector<LibDesc> libs;

@@ -9,27 +9,18 @@
 #include <vector>
 
 #include "../../include/svtyper_reads.h"
+#include "svt_bgzf.h"
 #include "svt_evidence_arena.h"
-#include "svt_inflate.h"
 #include "svt_library_walk.h"
 
 namespace svt {
 namespace lw {
 
-// One round: the BGZF members file[span_off, span_off + span_bytes) side by side (Member.src counts from span_off, Member.dst in
-// the arena) and the segments of the arena they inflate to.
+// One round: whole BGZF members out of one span of the file (bgzf::MemberSet) and the segments of the arena they inflate to.
 struct Round {
-    const uint8_t* file = nullptr;
-    uint64_t span_off = 0, span_bytes = 0, arena_bytes = 0;
-    std::vector<inf::Member> members;
+    bgzf::MemberSet set;
     std::vector<Segment> segments;
     VerifyTally* verify = nullptr;       // svt_bam_set_verify: whoever loads the round checks its members' CRC-32 and counts here
-    const uint8_t* payload(const inf::Member& mb) const { return file + span_off + mb.src; }
-    void crc_jobs(std::vector<crc::Job>& jobs) const
-    {
-        jobs.resize(members.size());
-        for (size_t k = 0; k < members.size(); ++k) jobs[k] = crc::Job{members[k].dst, members[k].isize, inf::member_crc(payload(members[k]), 0, members[k].clen)};
-    }
 };
 
 // the host's copies of the tables, for the merge
@@ -50,10 +41,6 @@ struct Backend {
     virtual int accumulate(const std::vector<Segment>& segments, const std::vector<SegCaps>& caps) = 0;   // caps.size() segments
     virtual int finish(HostTables& T) = 0;
 };
-
-// the members of `r` inflated on `n_threads` host threads into dst[0, r.arena_bytes): by svt_inflate.h (`one_source`), or by the
-// reader's own decoder (libdeflate / zlib); with r.verify a member that inflates has its CRC-32 checked there (inf::INF_CRC)
-void inflate_round_host(const Round& r, uint8_t* dst, unsigned n_threads, bool one_source, std::vector<uint32_t>& status);
 
 // the whole call.  0 or SVT_ERR_* with the error text set (the host scan's, when it answered).
 int scan_libraries(const svt_bam* bam, uint32_t n_libs, const uint32_t* rg_counts, const char* const* read_groups, int64_t num_samp,

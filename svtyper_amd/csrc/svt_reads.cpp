@@ -1,24 +1,18 @@
 // svt_reads.cpp -- native BAM access + fragment summariser (include/svtyper_reads.h).
 //
-// Host-only C++ (no HIP): BGZF/BAM/BAI reader with the fetch()/count() semantics the SVTyper path
+// Host-only C++ (no HIP): BAM/BAI reader over the BGZF layer of svt_bgzf_reader.h, with the fetch()/count() semantics the SVTyper path
 // relies on (pysam's, as restated in svtyper_amd/bam.py), read-fragment assembly and split-read QC
 // (svtyper/parsers.py:729-768, 891-1058 as restated in svtyper_amd/fragments.py) and the emission of
 // svt_fragment summaries (svtyper_amd/geometry.py).  The Python modules are the portable
 // implementation and the checker of this file (tests/test_native_reads.py compares the summaries
 // byte for byte); this file exists because per-read Python objects, not the GPU, bound a real run.
 
-#include <dlfcn.h>
-#include <fcntl.h>
 #include <sys/mman.h>
-#include <sys/stat.h>
 #include <time.h>
-#include <unistd.h>
-#include <zlib.h>
 
 #include <algorithm>
 #include <atomic>
 #include <chrono>
-#include <condition_variable>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -33,11 +27,15 @@
 #include <vector>
 
 #include "../../include/svtyper_reads.h"
+#include "svt_bgzf.h"
 #include "svt_error.h"
 #include "svt_evidence_arena.h"
 #include "svt_geometry_math.h"
 #include "svt_host_cpus.h"
+#include "svt_library_arena.h"
 #include "svt_record_rules.h"
+
+#include "svt_bgzf_reader.h"   // FileMap, Bgzf and the host loop over a bgzf::MemberSet: this translation unit's BGZF layer
 
 namespace {
 
@@ -47,433 +45,6 @@ using svt::run_threads;
 namespace rr = svt::rr;
 
 std::atomic<double> g_cpu_s_per_unit{0.0};   // CPU seconds per unit of the last svt_bam_summarise / svt_bam_evidence call on any file
-
-// ------------------------------------------------------------------------------------------
-// BGZF: random access through (compressed offset << 16 | in-block offset) addresses
-// ------------------------------------------------------------------------------------------
-// the whole file, mapped read-only once per handle and shared by all worker threads: no read()
-// syscalls or stdio buffers on the fetch path, the inflate input is the mapping itself
-struct FileMap {
-    const uint8_t* data = nullptr;
-    size_t size = 0;
-    FileMap() = default;
-    FileMap(const FileMap&) = delete;
-    FileMap& operator=(const FileMap&) = delete;
-    ~FileMap() { if (data) munmap(const_cast<uint8_t*>(data), size); }
-    bool open(const std::string& path)
-    {
-        const int fd = ::open(path.c_str(), O_RDONLY);
-        if (fd < 0) return false;
-        struct stat st;
-        if (fstat(fd, &st) != 0 || st.st_size <= 0) { ::close(fd); return false; }
-        void* p = mmap(nullptr, (size_t)st.st_size, PROT_READ, MAP_SHARED, fd, 0);
-        ::close(fd);
-        if (p == MAP_FAILED) return false;
-        madvise(p, (size_t)st.st_size, MADV_RANDOM);   // region fetches, not a scan
-        data = static_cast<const uint8_t*>(p);
-        size = (size_t)st.st_size;
-        return true;
-    }
-};
-
-// Raw-deflate decoding of BGZF blocks is where a region fetch spends its time on real data (a window is reached by
-// inflating every block from the start of its 16-kb bin).  libdeflate's whole-buffer decoder is 2-3x faster
-// than zlib's streaming one; the image ships its runtime (libdeflate.so.0) without headers, so it is bound by
-// name at first use and zlib stays as the decoder when it is absent (or SVT_INFLATE=zlib asks for it).
-struct FastInflate {
-    void* (*alloc)() = nullptr;
-    int (*decompress)(void*, const void*, size_t, void*, size_t, size_t*) = nullptr;
-    void (*release)(void*) = nullptr;
-    uint32_t (*crc)(uint32_t, const void*, size_t) = nullptr;   // verify: libdeflate_crc32, when the library has it
-    FastInflate()
-    {
-        const char* want = std::getenv("SVT_INFLATE");
-        if (want && std::strcmp(want, "zlib") == 0) return;
-        void* h = dlopen("libdeflate.so.0", RTLD_NOW | RTLD_LOCAL);
-        if (!h) return;
-        crc = reinterpret_cast<uint32_t (*)(uint32_t, const void*, size_t)>(dlsym(h, "libdeflate_crc32"));
-        alloc = reinterpret_cast<void* (*)()>(dlsym(h, "libdeflate_alloc_decompressor"));
-        decompress = reinterpret_cast<int (*)(void*, const void*, size_t, void*, size_t, size_t*)>(
-            dlsym(h, "libdeflate_deflate_decompress"));
-        release = reinterpret_cast<void (*)(void*)>(dlsym(h, "libdeflate_free_decompressor"));
-        if (!alloc || !decompress || !release) alloc = nullptr;
-    }
-    bool usable() const { return alloc != nullptr; }
-};
-static const FastInflate& fast_inflate()
-{
-    static const FastInflate f;
-    return f;
-}
-
-std::string crc_mismatch_text(uint64_t coff, uint32_t stored, uint32_t computed)
-{
-    char text[128];
-    std::snprintf(text, sizeof text, "BGZF block at offset %llu: CRC32 mismatch (stored 0x%08x, computed 0x%08x)", (unsigned long long)coff, stored, computed);
-    return text;
-}
-
-// One inflated BGZF block: immutable once it is published, so readers on several threads can hold it.
-struct BlockData {
-    std::vector<uint8_t> data;
-    uint64_t next = 0;         // compressed offset of the block behind it (== its own offset: end of data / unusable block)
-};
-typedef std::shared_ptr<const BlockData> BlockRef;
-
-// Inflated blocks shared by the worker threads of ONE svt_bam_summarise call.  Workers take runs of neighbouring units,
-// and a worker that starts a run walks up to its first window through the blocks in front of it (a window is reached from
-// the start of its 16-kb bin: seven 64-KiB blocks at 30x on average) -- blocks the worker of the run before inflates too,
-// for its own last units.  Measured on 290 whole-genome-like sites: 24 % (8 workers) to 54 % (15) of all inflate calls were
-// such repeats, and inflate is three quarters of the reader's time there.  A block is looked up here after the reader's own
-// slots missed and published after it was inflated: one short critical section per 64 KiB of records.  64 shards x 16 ways
-// = 1 024 blocks (64 MiB) at most, first-in-first-out per shard; a block a reader still holds outlives its eviction.
-class SharedBlocks {
-public:
-    // The block at `coff`, or null with *claimed = true: the caller inflates it and then calls publish() or abandon().
-    // While one worker inflates a block the others that want it wait here instead of inflating it too (workers start
-    // their runs side by side: with 47 of them 2 291 inflate calls for 929 blocks before this).
-    // With `in_flight` the call does not wait: a block somebody else is inflating comes back as null, *in_flight = true.
-    BlockRef find_or_claim(uint64_t coff, bool* claimed, bool* in_flight = nullptr)
-    {
-        Shard& sh = shard(coff);
-        std::unique_lock<std::mutex> g(sh.lock);
-        *claimed = false;
-        if (in_flight) *in_flight = false;
-        for (;;) {
-            int at = -1;
-            for (int i = 0; i < kWays; ++i)
-                if (sh.coff[i] == coff) { at = i; break; }
-            if (at >= 0 && sh.block[at]) return sh.block[at];
-            if (at < 0) {                                    // nobody has it, nobody is on it: the caller's
-                sh.coff[sh.clock] = coff;
-                sh.block[sh.clock].reset();
-                sh.clock = (sh.clock + 1) % kWays;
-                *claimed = true;
-                return BlockRef();
-            }
-            if (in_flight) {
-                *in_flight = true;
-                return BlockRef();
-            }
-            sh.ready.wait(g);                                // in flight: published, abandoned or pushed out when we wake
-        }
-    }
-    void publish(uint64_t coff, const BlockRef& b)
-    {
-        Shard& sh = shard(coff);
-        {
-            std::lock_guard<std::mutex> g(sh.lock);
-            int at = -1;
-            for (int i = 0; i < kWays; ++i)
-                if (sh.coff[i] == coff) { at = i; break; }
-            if (at < 0) {                                    // (its place went to sixteen newer blocks meanwhile)
-                at = sh.clock;
-                sh.clock = (sh.clock + 1) % kWays;
-                sh.coff[at] = coff;
-            }
-            sh.block[at] = b;
-        }
-        sh.ready.notify_all();
-    }
-    void abandon(uint64_t coff)                              // the block is unusable: whoever waits finds that out for itself
-    {
-        Shard& sh = shard(coff);
-        {
-            std::lock_guard<std::mutex> g(sh.lock);
-            for (int i = 0; i < kWays; ++i)
-                if (sh.coff[i] == coff && !sh.block[i]) sh.coff[i] = ~0ull;
-        }
-        sh.ready.notify_all();
-    }
-
-private:
-    static constexpr int kShards = 64, kWays = 16;
-    struct Shard {
-        std::mutex lock;
-        std::condition_variable ready;
-        uint64_t coff[kWays];
-        BlockRef block[kWays];                               // null under a valid offset: being inflated
-        int clock = 0;
-        Shard() { for (auto& c : coff) c = ~0ull; }
-    };
-    Shard& shard(uint64_t coff) { return shards_[(coff * 0x9E3779B97F4A7C15ull) >> 58]; }
-    Shard shards_[kShards];
-};
-
-class Bgzf {
-public:
-    // `verify` (svt_bam_set_verify; null: off): every block this reader inflates has its CRC-32 checked, and is counted there
-    explicit Bgzf(const FileMap& file, SharedBlocks* shared = nullptr, svt::VerifyTally* verify = nullptr)
-        : file_(file), shared_(shared), verify_(verify), empty_(std::make_shared<BlockData>())
-    {
-        std::memset(&zs_, 0, sizeof zs_);
-        if (fast_inflate().usable()) fast_ = fast_inflate().alloc();
-        if (!fast_) zs_ok_ = inflateInit2(&zs_, -15) == Z_OK;   // one inflate state per reader, reset per block
-        block_ = empty_.get();
-    }
-    ~Bgzf()
-    {
-        if (fast_) fast_inflate().release(fast_);
-        if (zs_ok_) inflateEnd(&zs_);
-        if (verify_) verify_->add(n_verified_, n_crc_failed_, crc_s_, 0.0);
-    }
-    Bgzf(const Bgzf&) = delete;
-    Bgzf& operator=(const Bgzf&) = delete;
-    bool ok() const { return file_.data != nullptr && (zs_ok_ || fast_); }
-    bool failed() const { return bad_; }
-    void mark_bad() { bad_ = true; }   // the record stream inside the blocks is corrupt
-    // verify: a block this reader inflated did not have the CRC-32 its trailer stores (it is failed() too); the text for the caller
-    bool crc_failed() const { return !crc_error_.empty(); }
-    const std::string& crc_error() const { return crc_error_; }
-    uint64_t n_inflated = 0, n_shared_hits = 0, n_ahead = 0;   // (SVT_TRACE)
-    double inflate_s = 0.0;
-    // when set: every block this reader loads is noted here (the arena of svt_bam_evidence_device is put together from them)
-    std::vector<std::pair<uint64_t, BlockRef>>* touched = nullptr;
-
-    void seek(uint64_t voff)
-    {
-        load(voff >> 16);
-        uoff_ = (size_t)(voff & 0xFFFF);
-    }
-    uint64_t tell() const
-    {
-        if (uoff_ >= block_->data.size() && !block_->data.empty()) return block_->next << 16;
-        return (coff_ << 16) | uoff_;
-    }
-    // The position as it stands, where tell() carries the end of a block over to the start of the next.  Behind a read: the block
-    // that holds the last byte read, and the offset behind that byte.
-    void last_read(uint64_t* coff, uint32_t* end) const { *coff = coff_; *end = (uint32_t)uoff_; }
-    // after seek(): an offset behind the bytes of a block that has none (tell() reports it as it is; the next read starts in the
-    // block behind it)
-    bool offset_in_empty_block() const { return uoff_ > 0 && block_->data.empty(); }
-    // returns the number of bytes actually read
-    size_t read(void* dst, size_t n)
-    {
-        size_t got = 0;
-        uint8_t* out = static_cast<uint8_t*>(dst);
-        while (got < n) {
-            const size_t avail = block_->data.size() - std::min(uoff_, block_->data.size());
-            if (avail == 0) {
-                const uint64_t next = block_->next;
-                if (block_ != empty_.get() && next == coff_) break;
-                if (!load(next)) break;
-                uoff_ = 0;
-                continue;
-            }
-            const size_t take = std::min(avail, n - got);
-            std::memcpy(out + got, block_->data.data() + uoff_, take);
-            uoff_ += take;
-            got += take;
-        }
-        return got;
-    }
-
-    // n bytes at the read position as one span inside the current inflated block, or nullptr when they
-    // straddle a block boundary / the file ends (the caller then falls back to read()).  The pointer stays
-    // valid until the next call that may load a block.
-    const uint8_t* contiguous(size_t n)
-    {
-        if (uoff_ >= block_->data.size()) {
-            const uint64_t next = block_->next;
-            if (block_ != empty_.get() && next == coff_) return nullptr;
-            if (!load(next)) return nullptr;
-            uoff_ = 0;
-        }
-        return block_->data.size() - uoff_ >= n ? block_->data.data() + uoff_ : nullptr;
-    }
-    void advance(size_t n) { uoff_ += n; }   // over bytes contiguous() has just vouched for
-
-private:
-    // Recently used blocks of this reader: the two windows of a unit and its neighbours walk forward through the same
-    // blocks, and a list of sites often comes back to a region (both ends of a large event, overlapping calls, the same
-    // targets again).  kSlots references, 8 MiB of blocks at most; the offsets sit in an array of their own: a look-up is
-    // one pass over 1 KiB.  (32 slots: a cycle over ~50 blocks -- the fixture's 211 sites, repeated -- missed on every
-    // third site, a third of the reader's time.)
-    static constexpr int kSlots = 128;
-    int slot_for(uint64_t coff) const
-    {
-        for (int i = 0; i < n_slots_; ++i)
-            if (coffs_[i] == coff) return i;
-        return -1;
-    }
-    bool use(uint64_t coff, const BlockRef& b)           // make `b` the current block, remembered under `coff`
-    {
-        int i;
-        if (n_slots_ < kSlots) i = n_slots_++;
-        else {
-            i = clock_;
-            clock_ = (clock_ + 1) % kSlots;
-        }
-        coffs_[i] = coff;
-        slots_[i] = b;
-        block_ = b.get();
-        coff_ = coff;
-        if (touched) touched->emplace_back(coff, b);
-        return !block_->data.empty() || block_->next > coff;
-    }
-    bool park(uint64_t coff, bool is_bad)                // end of file / unusable block: an empty block that is its own successor
-    {
-        if (is_bad) bad_ = true;
-        auto b = std::make_shared<BlockData>();
-        b->next = coff;
-        use(coff, b);
-        return false;
-    }
-    // The block at `coff` inflated into a fresh BlockData; null with *unusable = false at the end of the file, null with
-    // *unusable = true for a header that cannot be one.  A stream that does not inflate still returns its block (the
-    // bytes stay readable) with *unusable = true.
-    std::shared_ptr<BlockData> inflate_block(uint64_t coff, bool* unusable)
-    {
-        *unusable = false;
-        if (coff + 18 > file_.size) return nullptr;                    // end of file
-        *unusable = true;
-        const uint8_t* hdr = file_.data + coff;
-        if (hdr[0] != 31 || hdr[1] != 139) return nullptr;
-        const size_t xlen = hdr[10] | (hdr[11] << 8);
-        if (coff + 12 + xlen > file_.size) return nullptr;
-        int bsize = -1;
-        for (size_t i = 0; i + 4 <= xlen;) {
-            const uint8_t* x = hdr + 12 + i;
-            const size_t slen = x[2] | (x[3] << 8);
-            if (x[0] == 66 && x[1] == 67 && i + 6 <= xlen) bsize = x[4] | (x[5] << 8);
-            i += 4 + slen;
-        }
-        if (bsize < 0 || coff + (uint64_t)bsize + 1 > file_.size) return nullptr;
-        const int clen = bsize - (int)xlen - 19;
-        if (clen < 0) return nullptr;
-        const uint8_t* cdata = hdr + 12 + xlen;
-        const uint8_t* tail = cdata + clen;
-        const uint32_t isize = tail[4] | (tail[5] << 8) | (tail[6] << 16) | ((uint32_t)tail[7] << 24);
-        if (isize > 65536u) return nullptr;              // a BGZF block inflates to at most 64 KiB
-        auto b = std::make_shared<BlockData>();
-        b->data.resize(isize);
-        b->next = coff + (uint64_t)bsize + 1;
-        bool inflated = true;
-        const auto t_inflate = std::chrono::steady_clock::now();
-        if (isize && fast_) {
-            // exactly isize bytes or an error (a null "actual size" pointer makes a short stream a failure)
-            if (fast_inflate().decompress(fast_, cdata, (size_t)clen, b->data.data(), b->data.size(), nullptr) != 0) inflated = false;
-        } else if (isize) {
-            if (inflateReset(&zs_) != Z_OK) inflated = false;
-            else {
-                zs_.next_in = const_cast<Bytef*>(cdata);
-                zs_.avail_in = (uInt)clen;
-                zs_.next_out = b->data.data();
-                zs_.avail_out = (uInt)b->data.size();
-                if (inflate(&zs_, Z_FINISH) != Z_STREAM_END) inflated = false;
-            }
-        }
-        inflate_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - t_inflate).count();
-        ++n_inflated;
-        if (verify_ && inflated) {                       // a mismatch is a block that does not inflate, with a text of its own
-            const auto t_crc = std::chrono::steady_clock::now();
-            const uint32_t stored = tail[0] | (tail[1] << 8) | (tail[2] << 16) | ((uint32_t)tail[3] << 24);
-            const uint32_t computed = svt::host_crc32(b->data.data(), b->data.size());
-            crc_s_ += std::chrono::duration<double>(std::chrono::steady_clock::now() - t_crc).count();
-            ++n_verified_;
-            if (stored != computed) {
-                ++n_crc_failed_;
-                inflated = false;
-                if (crc_error_.empty()) crc_error_ = crc_mismatch_text(coff, stored, computed);
-            }
-        }
-        *unusable = !inflated;
-        return b;
-    }
-    // offset of the block behind the one at `coff`, from its header alone; 0 when there is none to be had
-    uint64_t next_offset(uint64_t coff) const
-    {
-        if (coff + 18 > file_.size) return 0;
-        const uint8_t* hdr = file_.data + coff;
-        if (hdr[0] != 31 || hdr[1] != 139) return 0;
-        const size_t xlen = hdr[10] | (hdr[11] << 8);
-        if (coff + 12 + xlen > file_.size) return 0;
-        for (size_t i = 0; i + 4 <= xlen;) {
-            const uint8_t* x = hdr + 12 + i;
-            if (x[0] == 66 && x[1] == 67 && i + 6 <= xlen) return coff + (uint64_t)(x[4] | (x[5] << 8)) + 1;
-            i += 4 + (size_t)(x[2] | (x[3] << 8));
-        }
-        return 0;
-    }
-    struct Claim {                                       // a claimed block that is not published is given up on every way out
-        SharedBlocks* shared = nullptr;
-        uint64_t coff = 0;
-        ~Claim() { if (shared) shared->abandon(coff); }
-    };
-    // Somebody else is inflating the block this reader needs next.  Readers walk forward, so the blocks behind it are
-    // wanted too -- by this reader, and by the one it waits for: instead of waiting, inflate the first of the next
-    // kAhead blocks nobody has or is on.  Workers that walk up to neighbouring windows through the same blocks thereby
-    // inflate them side by side instead of queueing behind one another (47 workers on 290 whole-genome-like sites spent
-    // two thirds of their time in that queue).  False when there was nothing to do.
-    bool help_ahead(uint64_t coff)
-    {
-        static constexpr int kAhead = 12;
-        uint64_t c = coff;
-        for (int k = 0; k < kAhead; ++k) {
-            c = next_offset(c);
-            if (c == 0 || c + 18 > file_.size) return false;
-            if (slot_for(c) >= 0) continue;
-            bool claimed = false, in_flight = false;
-            if (shared_->find_or_claim(c, &claimed, &in_flight) || in_flight) continue;
-            Claim claim{shared_, c};
-            bool unusable = false;
-            std::shared_ptr<BlockData> b = inflate_block(c, &unusable);
-            if (!b || unusable) return false;            // (left to the reader that gets there: it reports the failure)
-            shared_->publish(c, b);
-            claim.shared = nullptr;
-            ++n_ahead;
-            return true;
-        }
-        return false;
-    }
-    bool load(uint64_t coff)
-    {
-        const int hit = slot_for(coff);
-        if (hit >= 0) {
-            block_ = slots_[hit].get();
-            coff_ = coff;
-            return !block_->data.empty() || block_->next > coff;
-        }
-        Claim claim;
-        if (shared_) {
-            for (;;) {
-                bool claimed = false, in_flight = false;
-                if (BlockRef b = shared_->find_or_claim(coff, &claimed, &in_flight)) { ++n_shared_hits; return use(coff, b); }
-                if (claimed) { claim.shared = shared_; claim.coff = coff; break; }
-                if (help_ahead(coff)) continue;          // (in flight elsewhere: useful work first, then look again)
-                if (BlockRef b = shared_->find_or_claim(coff, &claimed)) { ++n_shared_hits; return use(coff, b); }   // waits
-                if (claimed) { claim.shared = shared_; claim.coff = coff; }
-                break;
-            }
-        }
-        bool unusable = false;
-        std::shared_ptr<BlockData> b = inflate_block(coff, &unusable);
-        if (!b) return park(coff, unusable);
-        if (unusable) bad_ = true;                       // (its bytes stay readable, as before: the caller sees failed())
-        if (claim.shared && !unusable) { shared_->publish(coff, b); claim.shared = nullptr; }
-        use(coff, b);
-        return true;
-    }
-
-    const FileMap& file_;
-    SharedBlocks* shared_;
-    svt::VerifyTally* verify_;
-    uint64_t n_verified_ = 0, n_crc_failed_ = 0;
-    double crc_s_ = 0.0;
-    std::string crc_error_;
-    z_stream zs_;
-    bool zs_ok_ = false;
-    void* fast_ = nullptr;   // libdeflate decompressor of this reader
-    BlockRef slots_[kSlots];
-    uint64_t coffs_[kSlots];
-    int n_slots_ = 0;
-    int clock_ = 0;
-    std::shared_ptr<BlockData> empty_;
-    const BlockData* block_ = nullptr;
-    uint64_t coff_ = 0;
-    size_t uoff_ = 0;
-    bool bad_ = false;
-};
 
 // ------------------------------------------------------------------------------------------
 // reads, pieces, fragments (what a record means is svt_record_rules.h)
@@ -578,12 +149,6 @@ namespace svt {
 
 VerifyTally* bam_verify(const svt_bam* bam) { return bam && bam->verify.load() ? &bam->tally : nullptr; }
 
-uint32_t host_crc32(const uint8_t* p, size_t n)
-{
-    if (fast_inflate().crc) return fast_inflate().crc(0, p, n);
-    return (uint32_t)::crc32(0L, p, (uInt)n);              // (n <= 65 536)
-}
-
 VerifyScope::VerifyScope(const svt_bam* b) : bam(b)
 {
     g_verify_stats = svt_bgzf_verify_counts{};
@@ -600,26 +165,6 @@ VerifyScope::~VerifyScope()
     g_verify_stats.members_failed = bam->tally.failed.load() - failed;
     g_verify_stats.host_crc_s = (double)(bam->tally.host_ns.load() - host_ns) * 1e-9;
     g_verify_stats.device_crc_s = (double)(bam->tally.device_ns.load() - device_ns) * 1e-9;
-}
-
-// the tables of svt_crc32.h for this translation unit's callers
-const crc::Tables& crc_tables()
-{
-    static const crc::Tables* const T = [] { auto* t = new crc::Tables(); crc::fill_tables(*t); return t; }();
-    return *T;
-}
-
-// the arguments of svt_bgzf_crc32_host / _device
-int crc_check_offsets(const uint8_t* bytes, const uint64_t* off, uint64_t n, const uint32_t* crc)
-{
-    if (n && (!off || !crc)) return fail(SVT_ERR_INVALID, "null argument");
-    if (n > 0xFFFFFFFFull) return fail(SVT_ERR_INVALID, "svt_bgzf_crc32: too many members in one call (< 2^32)");
-    for (uint64_t k = 0; k < n; ++k) {
-        if (off[k + 1] < off[k]) return fail(SVT_ERR_INVALID, "svt_bgzf_crc32: off must not decrease");
-        if (off[k + 1] - off[k] > crc::kMaxLen) return fail(SVT_ERR_INVALID, "svt_bgzf_crc32: a member has at most 65536 bytes");
-    }
-    if (n && off[n] && !bytes) return fail(SVT_ERR_INVALID, "null argument");
-    return SVT_OK;
 }
 
 }  // namespace svt
@@ -1432,11 +977,11 @@ struct OpenWorker {
         r.uoff = ub;
         // (every step moves forward in the file by a whole member: the walk ends with the file)
         for (;;) {
-            if (coff + 18 > f.file_size) {                             // the end of the file: the data ends in front of the chunk's end
+            if (coff + 18 > f.set.file_size) {                             // the end of the file: the data ends in front of the chunk's end
                 if (coff == cb) return 0;                              // (nothing at all: the host reader finds no record either)
                 break;
             }
-            if (!inf::member_at(f.file, f.file_size, coff, src, clen, isize, next)) return kChunkHost;
+            if (!inf::member_at(f.set.file, f.set.file_size, coff, src, clen, isize, next)) return kChunkHost;
             if (coff == cb && ub > isize) return kChunkHost;           // a first offset beyond the block's bytes
             r.last = coff;
             r.end_in_last = isize;
@@ -1509,8 +1054,8 @@ int build_arena_open(const svt_bam* bam, const svt_summarise_args* args, const s
     out = Arena();
     out.open_ranges = true;
     plan = OpenPlan();
-    plan.file = bam->file.data;
-    plan.file_size = bam->file.size;
+    plan.set.file = bam->file.data;
+    plan.set.file_size = bam->file.size;
     arena_names(bam, args, out);
     UnitPlan units;
     if (const int rc = plan_units<OpenWorker>(bam, args, arena_threads(args, args->n_units), plan, units)) return rc;
@@ -1519,55 +1064,30 @@ int build_arena_open(const svt_bam* bam, const svt_summarise_args* args, const s
     std::unordered_map<uint64_t, Placed> placed;
     uint64_t total = 0;
     const int rc = place_runs(units, [&](uint64_t first, uint64_t last) {
-        OpenPlan::Span span{first, 0, plan.compressed_bytes};
+        bgzf::MemberSet::Span span{first, 0, plan.set.compressed_bytes};
         for (uint64_t coff = first;;) {
             uint64_t src = 0, next = 0;
             uint32_t clen = 0, isize = 0;
-            if (!inf::member_at(plan.file, plan.file_size, coff, src, clen, isize, next)) return fail(SVT_ERR_INTERNAL, "build_arena_open: block chain changed under the walk");
+            if (!inf::member_at(plan.set.file, plan.set.file_size, coff, src, clen, isize, next)) return fail(SVT_ERR_INTERNAL, "build_arena_open: block chain changed under the walk");
             if (total + isize <= kArenaLimit) {
-                placed[coff] = Placed{total, (uint32_t)plan.members.size()};
-                plan.members.push_back(inf::Member{span.at + (src - span.file_off), clen, isize, total});
+                placed[coff] = Placed{total, (uint32_t)plan.set.members.size()};
+                plan.set.members.push_back(inf::Member{span.at + (src - span.file_off), clen, isize, total});
                 span.bytes = next - span.file_off;
             }
             total += isize;
             if (coff == last) break;
             coff = next;
         }
-        if (span.bytes) { plan.spans.push_back(span); plan.compressed_bytes += span.bytes; }
+        if (span.bytes) { plan.set.spans.push_back(span); plan.set.compressed_bytes += span.bytes; }
         return (int)SVT_OK;
     });
     if (rc) return rc;
-    plan.arena_bytes = plan.members.empty() ? 0 : plan.members.back().dst + plan.members.back().isize;
-    out.bytes.resize(plan.arena_bytes + 8);
-    out.blocks = plan.members.size();
+    plan.set.arena_bytes = plan.set.members.empty() ? 0 : plan.set.members.back().dst + plan.set.members.back().isize;
+    out.bytes.resize(plan.set.arena_bytes + 8);
+    out.blocks = plan.set.members.size();
     finish_ranges(units, placed, out, &plan.range_members);
     plan.index_s = out.build_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_begin).count();
     return SVT_OK;
-}
-
-void inflate_open_host(const OpenPlan& plan, Arena& out, unsigned n_threads, std::vector<uint32_t>& status, VerifyTally* verify)
-{
-    const size_t m = plan.members.size();
-    status.assign(m, inf::INF_OK);
-    std::atomic<size_t> next(0);
-    run_threads(std::max(1u, std::min<unsigned>(n_threads, (unsigned)std::max<size_t>(m, 1))), [&](unsigned) {
-        std::unique_ptr<inf::Scratch> S(new inf::Scratch());
-        for (;;) {
-            const size_t k0 = next.fetch_add(8);
-            if (k0 >= m) return;
-            for (size_t k = k0; k < std::min(m, k0 + 8); ++k) {
-                const inf::Member& mb = plan.members[k];
-                const uint8_t* cdata = plan.payload(mb);
-                status[k] = inf::inflate_member<inf::HostCtx>(cdata, mb.clen, out.bytes.data() + mb.dst, mb.isize, *S);
-                if (verify && status[k] == inf::INF_OK) {
-                    const auto t0 = std::chrono::steady_clock::now();
-                    const bool same = host_crc32(out.bytes.data() + mb.dst, mb.isize) == inf::member_crc(cdata, 0, mb.clen);
-                    if (!same) status[k] = inf::INF_CRC;
-                    verify->add(1, same ? 0 : 1, std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(), 0.0);
-                }
-            }
-        }
-    });
 }
 
 uint64_t apply_member_status(const OpenPlan& plan, const std::vector<uint32_t>& status, Arena& out)
@@ -1584,21 +1104,6 @@ uint64_t apply_member_status(const OpenPlan& plan, const std::vector<uint32_t>& 
         }
     }
     return failed.back();
-}
-
-// the members at block_off[] of `data` as inf::Member (dst from out_off); a member that is none, or whose ISIZE is not the place it
-// was given, is marked kNoMember.  Shared with svt_bgzf_inflate_device (svt_entry_inflate.h) through svt_evidence_arena.h.
-int bgzf_members(const uint8_t* data, uint64_t len, const uint64_t* block_off, uint64_t n, const uint64_t* out_off, inf::Member* members)
-{
-    if ((!data && len) || (n && (!block_off || !out_off || !members))) return fail(SVT_ERR_INVALID, "null argument");
-    for (uint64_t k = 0; k < n; ++k) {
-        if (out_off[k + 1] < out_off[k]) return fail(SVT_ERR_INVALID, "svt_bgzf_inflate: out_off must not decrease");
-        uint64_t src = 0, next = 0;
-        uint32_t clen = 0, isize = 0;
-        const bool ok = inf::member_at(data, len, block_off[k], src, clen, isize, next) && out_off[k + 1] - out_off[k] == isize;
-        members[k] = inf::Member{ok ? src : 0, ok ? clen : 0, ok ? isize : inf::kNoMember, out_off[k]};
-    }
-    return SVT_OK;
 }
 
 int host_units(const svt_bam* bam, const svt_summarise_args* args, const svt_evidence_params* geometry, const std::vector<uint64_t>& ids,
@@ -2015,7 +1520,9 @@ static int svt_bam_evidence_walk_host_impl(const svt_bam* bam, const svt_summari
         svt::ew::OpenPlan plan;
         if (const int rc = svt::ew::build_arena_open(bam, args, geometry, arena, plan)) return rc;
         std::vector<uint32_t> member_status;
-        svt::ew::inflate_open_host(plan, arena, svt::ew::arena_threads(args, plan.members.size()), member_status, svt::bam_verify(bam));
+        const size_t m = plan.set.members.size();
+        svt::bgzf::inflate_members_host(plan.set, arena.bytes.data(), std::min<unsigned>(svt::ew::arena_threads(args, m), (unsigned)std::max<size_t>(m, 1)),
+                                        svt::bgzf::Decoder::one_source, svt::bgzf::Crc::library, svt::bam_verify(bam), member_status);
         svt::ew::apply_member_status(plan, member_status, arena);
     } else if (const int rc = svt::ew::build_arena(bam, args, geometry, arena)) return rc;
     const uint64_t n = args->n_units;
@@ -2085,20 +1592,13 @@ int svt_bam_evidence_walk_open_host(const svt_bam* bam, const svt_summarise_args
 static int svt_bgzf_inflate_host_impl(const uint8_t* data, uint64_t len, const uint64_t* block_off, uint64_t n, uint8_t* out,
                                       const uint64_t* out_off, uint32_t* status, bool verify)
 {
-    if (n && (!status || (!out && out_off && out_off[n]))) return fail(SVT_ERR_INVALID, "null argument");
-    std::vector<svt::inf::Member> members(n);
-    if (const int rc = svt::ew::bgzf_members(data, len, block_off, n, out_off, members.data())) return rc;
-    std::unique_ptr<svt::inf::Scratch> S(new svt::inf::Scratch());
-    std::unique_ptr<svt::crc::Scratch> C(verify ? new svt::crc::Scratch() : nullptr);
-    for (uint64_t k = 0; k < n; ++k) {
-        const svt::inf::Member& m = members[k];
-        status[k] = m.isize == svt::inf::kNoMember ? (uint32_t)svt::inf::INF_MEMBER
-                                                   : svt::inf::inflate_member<svt::inf::HostCtx>(data + m.src, m.clen, out + m.dst, m.isize, *S);
-        // (the one-source CRC, as the device entry's kernel runs it)
-        if (verify && status[k] == svt::inf::INF_OK &&
-            svt::crc::crc_member<svt::crc::HostCtx>(out + m.dst, m.isize, svt::crc_tables(), *C) != svt::inf::member_crc(data, m.src, m.clen))
-            status[k] = svt::inf::INF_CRC;
-    }
+    svt::bgzf::MemberSet set;
+    if (const int rc = svt::bgzf::bgzf_members(data, len, block_off, n, out, out_off, status, set)) return rc;
+    // (the one-source decoder and CRC on this thread, as the device entry's kernels run them; nothing is counted)
+    svt::VerifyTally uncounted;
+    std::vector<uint32_t> st;
+    svt::bgzf::inflate_members_host(set, out, 1, svt::bgzf::Decoder::one_source, svt::bgzf::Crc::one_source, verify ? &uncounted : nullptr, st);
+    if (n) std::memcpy(status, st.data(), n * sizeof(uint32_t));
     return SVT_OK;
 }
 
@@ -2268,7 +1768,6 @@ void svt_library_scan_free(svt_library_scan* s)
 // ------------------------------------------------------------------------------------------
 // the library scans of a whole file in one segmented walk (svt_library_walk.h, svt_library_arena.h)
 // ------------------------------------------------------------------------------------------
-#include "svt_library_arena.h"
 
 namespace svt {
 namespace lw {
@@ -2311,7 +1810,8 @@ struct Planner {
     uint32_t plan(Round& r)
     {
         r = Round();
-        r.file = bam->file.data;
+        r.set.file = bam->file.data;
+        r.set.file_size = bam->file.size;
         member_coff.clear();
         open = false;
         const uint64_t file_size = bam->file.size;
@@ -2322,21 +1822,21 @@ struct Planner {
         uint64_t coff = start >> 16, dst = 0;
         const uint32_t first_uoff = (uint32_t)(start & 0xFFFF);
         std::vector<uint64_t> ends;                      // file offset behind member k
-        r.span_off = coff;
+        const uint64_t span_off = coff;
         bool eof = false;
         for (;;) {
             if (coff + 18 > file_size) { eof = true; break; }     // (where the reader's Bgzf ends the data)
             uint64_t src = 0, next = 0;
             uint32_t clen = 0, isize = 0;
             if (!inf::member_at(bam->file.data, file_size, coff, src, clen, isize, next)) return LW_MEMBER;
-            if (r.members.empty() && first_uoff > isize) return LW_INDEX;
+            if (r.set.members.empty() && first_uoff > isize) return LW_INDEX;
             if (ci < cuts.size() && (cuts[ci] >> 16) < coff) return LW_INDEX;      // an offset into a block the chain passed by
             for (; ci < cuts.size() && (cuts[ci] >> 16) == coff; ++ci) {
                 const uint32_t u = (uint32_t)(cuts[ci] & 0xFFFF);
                 if (u > isize) return LW_INDEX;
-                bounds.push_back(Bound{dst + u, r.members.size() + (u ? 1u : 0u), ci});
+                bounds.push_back(Bound{dst + u, r.set.members.size() + (u ? 1u : 0u), ci});
             }
-            r.members.push_back(inf::Member{src - r.span_off, clen, isize, dst});
+            r.set.members.push_back(inf::Member{src - span_off, clen, isize, dst});
             member_coff.push_back(coff);
             ends.push_back(next);
             dst += isize;
@@ -2349,24 +1849,25 @@ struct Planner {
         size_t n_bounds = bounds.size();
         if (!eof && n_bounds) {                                                     // ends at the last segment start
             const Bound& last = bounds.back();
-            r.members.resize(last.members);
+            r.set.members.resize(last.members);
             member_coff.resize(last.members);
             ends.resize(last.members);
             start = cuts[last.cut];
             next_cut = last.cut + 1;
         }
-        r.arena_bytes = r.members.empty() ? 0 : r.members.back().dst + r.members.back().isize;
-        r.span_bytes = r.members.empty() ? 0 : ends.back() - r.span_off;
-        member_coff.push_back(r.members.empty() ? r.span_off : ends.back());
-        if (begin > r.arena_bytes) return LW_INDEX;
+        r.set.arena_bytes = r.set.members.empty() ? 0 : r.set.members.back().dst + r.set.members.back().isize;
+        r.set.compressed_bytes = r.set.members.empty() ? 0 : ends.back() - span_off;
+        r.set.spans.assign(1, bgzf::MemberSet::Span{span_off, r.set.compressed_bytes, 0});
+        member_coff.push_back(r.set.members.empty() ? span_off : ends.back());
+        if (begin > r.set.arena_bytes) return LW_INDEX;
         for (size_t k = 0; k < n_bounds; ++k) {
-            if (bounds[k].at < begin || bounds[k].at > r.arena_bytes) return LW_INDEX;
+            if (bounds[k].at < begin || bounds[k].at > r.set.arena_bytes) return LW_INDEX;
             r.segments.push_back(Segment{(uint32_t)begin, (uint32_t)bounds[k].at, seg_index++, 0});
             begin = bounds[k].at;
         }
-        if (eof) r.segments.push_back(Segment{(uint32_t)begin, (uint32_t)r.arena_bytes, seg_index++, 0});
+        if (eof) r.segments.push_back(Segment{(uint32_t)begin, (uint32_t)r.set.arena_bytes, seg_index++, 0});
         else if (!n_bounds) {
-            r.segments.push_back(Segment{(uint32_t)begin, (uint32_t)r.arena_bytes, seg_index++, 1});
+            r.segments.push_back(Segment{(uint32_t)begin, (uint32_t)r.set.arena_bytes, seg_index++, 1});
             open = true;
         }
         return LW_OK;
@@ -2375,11 +1876,11 @@ struct Planner {
     uint32_t advance(const Round& r, const SegCount& last)
     {
         if (!open) return LW_OK;
-        if (last.stop <= r.segments.back().begin || last.stop > r.arena_bytes) return LW_RECORD;   // (a round holds a whole record at least)
-        size_t k = r.members.size();
-        while (k > 0 && r.members[k - 1].dst > last.stop) --k;                     // the last member that begins at or in front of it
+        if (last.stop <= r.segments.back().begin || last.stop > r.set.arena_bytes) return LW_RECORD;   // (a round holds a whole record at least)
+        size_t k = r.set.members.size();
+        while (k > 0 && r.set.members[k - 1].dst > last.stop) --k;                     // the last member that begins at or in front of it
         if (k == 0) return LW_RECORD;
-        const inf::Member& m = r.members[k - 1];
+        const inf::Member& m = r.set.members[k - 1];
         if (last.stop - m.dst >= m.isize) start = member_coff[k] << 16;            // (behind its bytes: the next block's first)
         else start = (member_coff[k - 1] << 16) | (last.stop - m.dst);
         return LW_OK;
@@ -2424,8 +1925,8 @@ struct HostBackend : Backend {
     int load(const Round& r, std::vector<uint32_t>& status, svt_library_scan_stats& S_) override
     {
         const auto t0 = std::chrono::steady_clock::now();
-        arena.assign(r.arena_bytes + 8, 0);
-        inflate_round_host(r, arena.data(), 1, /*one_source=*/true, status);
+        arena.assign(r.set.arena_bytes + 8, 0);
+        bgzf::inflate_members_host(r.set, arena.data(), 1, bgzf::Decoder::one_source, bgzf::Crc::library, r.verify, status);
         S_.inflate_s += seconds_since(t0);
         return SVT_OK;
     }
@@ -2460,48 +1961,6 @@ void free_scans(svt_library_scan* out, uint32_t n)
 }
 
 }  // namespace
-
-void inflate_round_host(const Round& r, uint8_t* dst, unsigned n_threads, bool one_source, std::vector<uint32_t>& status)
-{
-    const size_t m = r.members.size();
-    status.assign(m, inf::INF_OK);
-    std::atomic<size_t> next(0);
-    const bool fast = !one_source && fast_inflate().usable();
-    run_threads(std::max(1u, std::min<unsigned>(n_threads, (unsigned)std::max<size_t>(m / 8, 1))), [&](unsigned) {
-        std::unique_ptr<inf::Scratch> S(one_source ? new inf::Scratch() : nullptr);
-        void* fd = fast ? fast_inflate().alloc() : nullptr;
-        z_stream zs;
-        std::memset(&zs, 0, sizeof zs);
-        const bool zs_ok = !one_source && !fd && inflateInit2(&zs, -15) == Z_OK;
-        for (;;) {
-            const size_t k0 = next.fetch_add(8);
-            if (k0 >= m) break;
-            for (size_t k = k0; k < std::min(m, k0 + 8); ++k) {
-                const inf::Member& mb = r.members[k];
-                const uint8_t* cdata = r.file + r.span_off + mb.src;
-                uint8_t* out = dst + mb.dst;
-                if (one_source) status[k] = inf::inflate_member<inf::HostCtx>(cdata, mb.clen, out, mb.isize, *S);
-                else if (mb.isize == 0) status[k] = inf::INF_OK;
-                else if (fd) status[k] = fast_inflate().decompress(fd, cdata, mb.clen, out, mb.isize, nullptr) == 0 ? inf::INF_OK : inf::INF_INPUT;
-                else if (zs_ok && inflateReset(&zs) == Z_OK) {
-                    zs.next_in = const_cast<Bytef*>(cdata);
-                    zs.avail_in = (uInt)mb.clen;
-                    zs.next_out = out;
-                    zs.avail_out = (uInt)mb.isize;
-                    status[k] = inflate(&zs, Z_FINISH) == Z_STREAM_END && zs.avail_out == 0 ? inf::INF_OK : inf::INF_INPUT;
-                } else status[k] = inf::INF_INPUT;
-                if (r.verify && status[k] == inf::INF_OK) {
-                    const auto t0 = std::chrono::steady_clock::now();
-                    const bool same = host_crc32(out, mb.isize) == inf::member_crc(cdata, 0, mb.clen);
-                    if (!same) status[k] = inf::INF_CRC;
-                    r.verify->add(1, same ? 0 : 1, std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(), 0.0);
-                }
-            }
-        }
-        if (fd) fast_inflate().release(fd);
-        if (zs_ok) inflateEnd(&zs);
-    });
-}
 
 int scan_libraries(const svt_bam* bam, uint32_t n_libs, const uint32_t* rg_counts, const char* const* read_groups, int64_t num_samp,
                    uint64_t round_bytes, Backend& backend, svt_library_scan* out, svt_library_scan_stats* stats)
@@ -2568,9 +2027,9 @@ int scan_libraries(const svt_bam* bam, uint32_t n_libs, const uint32_t* rg_count
         S.index_s += seconds_since(t0);
         ++S.rounds;
         S.segments += r.segments.size();
-        S.members_inflated += r.members.size();
-        S.compressed_bytes += r.span_bytes;
-        S.inflated_bytes += r.arena_bytes;
+        S.members_inflated += r.set.members.size();
+        S.compressed_bytes += r.set.compressed_bytes;
+        S.inflated_bytes += r.set.arena_bytes;
         if (const int rc = backend.load(r, member_status, S)) return rc;
         for (uint32_t st : member_status)
             if (st != inf::INF_OK) return host_answer(LW_MEMBER);

@@ -68,6 +68,7 @@
 #include "svt_evidence_kernel.h"
 #include "svt_inflate_kernel.h"
 #include "svt_crc32_kernel.h"
+#include "svt_bgzf.h"
 #include "svt_evidence_arena.h"
 #include "svt_library_kernel.h"
 #include "svt_library_arena.h"
@@ -176,6 +177,7 @@ void* svt_batch_stream(svt_batch* b) { return b ? (void*)b->stream : nullptr; }
 void svt_batch_destroy(svt_batch* b) { free_batch(b); }
 
 #include "svt_entry_debug.h"
+#include "svt_entry_inflate.h"
 #include "svt_entry_evidence.h"
 #include "svt_entry_library.h"
 #include "svt_entry_oneshot.h"

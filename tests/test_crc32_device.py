@@ -118,3 +118,25 @@ def test_device_library_scan_with_verify(tmp_path, hip_device, damaged, inflate)
         b.scan_libraries([[rg["ID"] for rg in b.header["RG"]]], 1000000, route="device", inflate=inflate)
     assert b.library_scan_stats["host_reason"] == "member"
     b.close()
+
+
+def test_device_library_scan_with_verify_over_many_rounds(hip_device, damaged):
+    """the device side of a round's members keeps its buffers and the CRC tables from round to round: verify on at the smallest
+    round size, where the fixture takes 19 rounds instead of one"""
+    import libscancases as lc
+    b = nr.NativeBam(cc.FIXTURE, verify=True)
+    groups = [[rg["ID"] for rg in b.header["RG"]]]
+    want = lc.host_scan(b, groups, 1000000)
+    got = b.scan_libraries(groups, 1000000, route="device", inflate="device", round_bytes=lc.SMALL_ROUND, ordered=True)
+    st, vs = b.library_scan_stats, nr.verify_stats()
+    print(st, vs)
+    assert got == want and st["host_reason"] is None
+    assert st["rounds"] > 1
+    assert vs["members_verified"] == st["members_inflated"] > 0 and vs["members_failed"] == 0
+    b.close()
+    path, offset = damaged
+    b = nr.NativeBam(path, verify=True)
+    with pytest.raises(hip.SvtyperHipError, match=MISMATCH % offset):
+        b.scan_libraries(groups, 1000000, route="device", inflate="device", round_bytes=lc.SMALL_ROUND)
+    assert b.library_scan_stats["host_reason"] == "member"
+    b.close()

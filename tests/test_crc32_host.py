@@ -159,3 +159,22 @@ def test_library_walk_on_the_host_ends_in_the_error(damaged):
     assert b.verify_stats["members_failed"] >= 2
     b.close()
     clean.close()
+
+
+def test_library_walk_on_the_host_with_verify_over_many_rounds(damaged):
+    """the host twin of the device scan's many-rounds case: svt_bam_scan_libraries_walk_host at the smallest round size"""
+    b = nr.NativeBam(cc.FIXTURE, verify=True)
+    groups = [[rg["ID"] for rg in b.header["RG"]]]
+    want = lc.host_scan(b, groups, 1000000)
+    got = b.scan_libraries(groups, 1000000, route="walk_host", round_bytes=lc.SMALL_ROUND, ordered=True)
+    st, vs = b.library_scan_stats, nr.verify_stats()
+    assert got == want and st["host_reason"] is None
+    assert st["rounds"] > 1
+    assert vs["members_verified"] == st["members_inflated"] > 0 and vs["members_failed"] == 0
+    b.close()
+    path, offset = damaged
+    b = nr.NativeBam(path, verify=True)
+    with pytest.raises(hip.SvtyperHipError, match="BGZF block at offset %d: CRC32 mismatch" % offset):
+        b.scan_libraries(groups, 1000000, route="walk_host", round_bytes=lc.SMALL_ROUND)
+    assert b.library_scan_stats["host_reason"] == "member"
+    b.close()
