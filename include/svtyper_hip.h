@@ -36,6 +36,14 @@
 extern "C" {
 #endif
 
+/* 19 since the device reader's deep units.  Added since WITHOUT a new number (no struct layout and no signature moved, and
+ * svt_pack_evidence answers what it answered): svt_pack_evidence_flags + SVT_PACK_MANY_LIBRARIES, and packed evidence of up
+ * to 65536 libraries (svt_packed_evidence.n_libs, the wide library switch) in svt_batch_create_packed, svt_genotype_packed
+ * and svt_genotype_packed_from_records.  One answer of an existing entry point did change: svt_genotype_packed_from_records
+ * used to return SVT_ERR_UNSUPPORTED for a batch of more than 256 libraries and now genotypes it.
+ * svt_version() therefore does NOT tell a caller whether these additions are there: a library of the same number built
+ * before them lacks the symbol.  Probe for it -- dlsym(handle, "svt_pack_evidence_flags") != NULL (in Python,
+ * hasattr(lib, "svt_pack_evidence_flags")) -- and treat its presence as "packed evidence takes up to 65536 libraries".  */
 #define SVT_ABI_VERSION 19
 
 /* ---- error codes (0 = ok, <0 = error; text via svt_last_error()) ---------- */
@@ -184,7 +192,7 @@ typedef struct svt_evidence_batch {
     const uint64_t* rec_offset; /* n_units + 1 entries, rec_offset[0] == 0        */
     const svt_unit* units;      /* n_units                                        */
     const svt_record* records;  /* rec_offset[n_units]                            */
-    uint32_t n_libs;            /* 1..65536 (packed evidence: 1..256)             */
+    uint32_t n_libs;            /* 1..65536                                       */
     const svt_library* libs;
     double split_weight;        /* --split_weight (classic.py:38)                 */
     double disc_weight;         /* --disc_weight  (classic.py:39)                 */
@@ -530,6 +538,10 @@ int svt_genotype(const svt_evidence_batch* in, svt_result* out, int device,
  * the first entry coded against another library than the one before (a sample with one library: one switch per
  * unit, 2 bytes; interleaved libraries: ~4.5 bytes per record).  The pass then reads the histogram tables through
  * L2 instead of LDS (svt_packed_kernel<several libraries>); results bit-identical as before.
+ * Up to 65536 libraries, like the canonical records: the switch half-word names libraries 0..255; a library beyond them
+ * is named by a WIDE switch, four bytes on a 4-byte boundary (the wide bit alone, then the 16-bit library index), and the
+ * pass reads that library's descriptor from device memory instead of LDS (svt_packed_kernel<kLibsInHbm>).  A batch of at
+ * most 256 libraries has the slots it always had.
  * Limits: libraries of at most 2047 histogram bins, DEL lengths >= 0, |var_length| <= 2^30, |key_min| <= 2^29,
  * mean + 3 sd of a library not within 4e-6 of an integer (svt_pack_evidence returns SVT_ERR_UNSUPPORTED
  * otherwise and the caller keeps the canonical records).                                                     */
@@ -542,9 +554,10 @@ typedef struct svt_packed_evidence {
     const svt_unit* units;       /* n_units                                                                 */
     const void* slots;           /* n_slots * 16 bytes                                                      */
     uint32_t common_mapq;        /* mapq_a | mapq_b << 8 of the one-half-word pair entries                  */
-    uint32_t n_libs;             /* 1..256; several: a unit's pair stream starts in the context of libs[0] and
-                                    carries a library-switch half-word (l + 1) << 3 in front of the first entry
-                                    coded against libs[l]; every n_bins <= 2047                             */
+    uint32_t n_libs;             /* 1..65536; several: a unit's pair stream starts in the context of libs[0] and
+                                    carries a library switch in front of the first entry coded against libs[l]:
+                                    the half-word (l + 1) << 3 for l < 256, else the pair 0x8000, l on a 4-byte
+                                    boundary; every n_bins <= 2047                                          */
     const svt_library* libs;
     double split_weight;
     double disc_weight;
@@ -563,6 +576,13 @@ void svt_pinned_free(void* p);
  * materialises canonical records (the host packer, svtyper_amd/packer.py; a reader) calls this per chunk of
  * units it has just produced -- or writes the slots itself.  Release with svt_packed_free.                    */
 int svt_pack_evidence(const svt_evidence_batch* in, svt_packed_evidence** out);
+/* The same with flags.  SVT_PACK_MANY_LIBRARIES: a batch of 257..65536 libraries is encoded (wide library switches).
+ * Without it -- svt_pack_evidence is svt_pack_evidence_flags(in, 0, out) -- such a batch is answered with
+ * SVT_ERR_UNSUPPORTED as it always was, which callers read as "keep the canonical records"; a caller that
+ * wants the compact route for a large cohort says so.  The slots of a batch of at most 256 libraries do not depend on
+ * the flag.  Unknown bits: SVT_ERR_INVALID.  Added without a new SVT_ABI_VERSION: probe for the symbol (see there).   */
+#define SVT_PACK_MANY_LIBRARIES 0x1u
+int svt_pack_evidence_flags(const svt_evidence_batch* in, unsigned pack_flags, svt_packed_evidence** out);
 void svt_packed_free(svt_packed_evidence* p);
 
 /* svt_batch_create for packed evidence (flags: SVT_FLAG_SSO_ASSOCIATION only): upload + tables; the pass

@@ -92,8 +92,10 @@ struct PackedOwner {             // what svt_pack_evidence returns: the public s
 };
 
 // svt_pack_evidence: the encoder itself is host-only code in svt_pack.cpp; here it gets the page-locked pool as allocator
-int pack_evidence(const svt_evidence_batch* in, svt_packed_evidence** out)
+int pack_evidence(const svt_evidence_batch* in, svt_packed_evidence** out, const unsigned pack_flags = 0)
 {
+    if (pack_flags & ~SVT_PACK_MANY_LIBRARIES) return fail(SVT_ERR_INVALID, "unknown flag bits");
+    const bool many = (pack_flags & SVT_PACK_MANY_LIBRARIES) != 0;
     if (!in || !out) return fail(SVT_ERR_INVALID, "null argument");
     *out = nullptr;
     const PackAlloc pool{[](uint64_t bytes) { return g_pinned.get(bytes); }, [](void* p) { g_pinned.put(p); }};
@@ -111,10 +113,10 @@ int pack_evidence(const svt_evidence_batch* in, svt_packed_evidence** out)
             last_u1 = u1;
             return SVT_OK;
         };
-        SVT_TRY(encode_packed(in, pool, &arr, &sink));
+        SVT_TRY(encode_packed(in, pool, &arr, &sink, many));
         if (last_u1 != in->n_units) { g_pinned.put(arr.off); g_pinned.put(arr.units); g_pinned.put(arr.slots); return fail(SVT_ERR_INTERNAL, "ranged encoder: units missing"); }
     } else
-    SVT_TRY(encode_packed(in, pool, &arr));
+    SVT_TRY(encode_packed(in, pool, &arr, nullptr, many));
     auto owner = std::make_unique<PackedOwner>();
     owner->off = arr.off;
     owner->units = arr.units;
@@ -149,7 +151,7 @@ int create_packed(const svt_packed_evidence* in, svt_batch* b, bool defer_slots 
 {
     const uint64_t n = in->n_units;
     StageTimer tm;
-    if (in->n_libs == 0 || in->n_libs > 256 || !in->libs) return fail(SVT_ERR_INVALID, "n_libs must be 1..256");
+    if (in->n_libs == 0 || in->n_libs > 65536 || !in->libs) return fail(SVT_ERR_INVALID, "n_libs must be 1..65536");
     if (!defer_all) {
     if (n && (!in->slot_offset || !in->units)) return fail(SVT_ERR_INVALID, "null unit arrays");
     if (n && in->slot_offset[0] != 0) return fail(SVT_ERR_INVALID, "slot_offset[0] must be 0");
@@ -195,7 +197,7 @@ int create_packed(const svt_packed_evidence* in, svt_batch* b, bool defer_slots 
                 const uint32_t* o = in->slot_offset + 3 * u;
                 if (o[1] < o[0] || o[2] < o[1] || o[3] < o[2]) bad |= 1;
                 if (U.svtype > SVT_SVTYPE_BND) bad |= 2;
-                if ((U.libs >> 16) != 0 || (U.flags & ~SVT_UNIT_SKIP)) bad |= 4;
+                if ((U.libs >> 24) != 0 || (U.flags & ~SVT_UNIT_SKIP)) bad |= 4;
                 if (U.var_length < -(1 << 30) || U.var_length > (1 << 30)) bad |= 8;
                 if (U.svtype == SVT_SVTYPE_DEL && U.var_length < 0) bad |= 16;
                 m = std::max(m, std::max<uint64_t>((uint64_t)(o[1] - o[0]) * 8, std::max<uint64_t>((uint64_t)(o[2] - o[1]) * 7, (uint64_t)(o[3] - o[2]) * 7)));
@@ -237,7 +239,8 @@ int create_packed(const svt_packed_evidence* in, svt_batch* b, bool defer_slots 
         SVT_TRY(st.finish());
     }
     tm.mark("H2D slots + unit arrays + tables");
-    const bool multi = in->n_libs > 1;     // library switches in the pair streams: descriptors in LDS, tables through L2
+    const bool multi = in->n_libs > 1;     // library switches in the pair streams: descriptors in LDS (more than 256: in device memory), tables through L2
+    const bool libs_in_lds = packed_libs_mode(in->n_libs) == kLibsInLds;
     b->mode = multi ? kGeneral : kSingleLds;
     b->n_slots = in->n_slots;
     PackedArgs& a = b->pargs;
@@ -253,7 +256,7 @@ int create_packed(const svt_packed_evidence* in, svt_batch* b, bool defer_slots 
     a.n_l10 = (uint32_t)T.l10.size();
     a.total_bins = (uint32_t)T.bins.size();
     a.common_mq = in->common_mapq;
-    size_t tables = kLdsBins + (multi ? (size_t)in->n_libs * sizeof(LibDesc) : (size_t)a.total_bins * sizeof(Bin));
+    size_t tables = kLdsBins + (libs_in_lds ? (size_t)in->n_libs * sizeof(LibDesc) : multi ? 0 : (size_t)a.total_bins * sizeof(Bin));
     tables = (tables + 127) & ~size_t(127);
     constexpr size_t kLdsPerWg = (160 * 1024 / 3) & ~size_t(127);   // three workgroups per CU
     const size_t l10_bytes = ((size_t)a.n_l10 * 8 + 127) & ~size_t(127);

@@ -371,12 +371,17 @@ int launch_stream(svt_batch* b, StreamArgs& a, hipStream_t stream)
     return SVT_OK;
 }
 
-// the pass over packed evidence: one library (tables in LDS) / several (library switches, tables through L2)
+// the pass over packed evidence: one library (tables in LDS) / several (library switches, tables through L2; the descriptors in
+// LDS up to 256 libraries, in device memory beyond)
+int packed_libs_mode(const uint32_t n_libs) { return n_libs <= 1 ? kOneLibrary : n_libs <= kShortSwitchLibs ? kLibsInLds : kLibsInHbm; }
 const void* packed_kernel_of(const svt_batch* b)
 {
-    const bool sso = (b->flags & SVT_FLAG_SSO_ASSOCIATION) != 0, multi = b->pargs.n_libs > 1;
-    return sso ? (multi ? reinterpret_cast<const void*>(&svt_packed_kernel<true, 1, true>) : reinterpret_cast<const void*>(&svt_packed_kernel<true, 1, false>))
-               : (multi ? reinterpret_cast<const void*>(&svt_packed_kernel<false, 1, true>) : reinterpret_cast<const void*>(&svt_packed_kernel<false, 1, false>));
+    const bool sso = (b->flags & SVT_FLAG_SSO_ASSOCIATION) != 0;
+    switch (packed_libs_mode(b->pargs.n_libs)) {
+    case kOneLibrary: return sso ? reinterpret_cast<const void*>(&svt_packed_kernel<true, 1, kOneLibrary>) : reinterpret_cast<const void*>(&svt_packed_kernel<false, 1, kOneLibrary>);
+    case kLibsInLds: return sso ? reinterpret_cast<const void*>(&svt_packed_kernel<true, 1, kLibsInLds>) : reinterpret_cast<const void*>(&svt_packed_kernel<false, 1, kLibsInLds>);
+    default: return sso ? reinterpret_cast<const void*>(&svt_packed_kernel<true, 1, kLibsInHbm>) : reinterpret_cast<const void*>(&svt_packed_kernel<false, 1, kLibsInHbm>);
+    }
 }
 
 // units [u0, u1) of a streamed layout (stream: not the library-window mode, whose launch covers window chunks);

@@ -23,6 +23,15 @@ namespace svt {
 //     LIBRARY SWITCH: the entries behind it were coded against the tables of library l, until the next switch or the end
 //     of the unit.  Entries stay in record order whatever their library (the sums are order-dependent), the gate of
 //     classic.py:339,383 is the entry's own library's.  A batch of one library never holds a switch.
+//     More than 256 libraries (svt_pack_evidence_flags + SVT_PACK_MANY_LIBRARIES, added under ABI 19 without a new number; n_libs <= 65536): the half-word
+//     above is the SHORT switch.  The encoder writes it for l < kShortSwitchLibs = 256 -- every batch of at most 256
+//     libraries therefore keeps exactly the slots it had -- and a WIDE SWITCH for the others: a 4-byte-aligned pair of
+//     half-words like a wide entry, kWideSwitch = 0x8000 (the wide bit alone) then the 16-bit library index l, behind a
+//     zero half-word where it would start at an odd one.  0x8000 cannot be anything else: it is not zero (no-op), its bit
+//     15 is set (a short switch has it clear), and a stored entry, wide or not, has a straddle bit (f3 != 0; entries
+//     without one are never stored) where 0x8000 has none.  Its second half-word sits where a wide entry keeps its MAPQs,
+//     so a reader skips it the same way.  The decoder takes either form for any library either can name (the short
+//     one's field ends at l = 4094); where the short form ends is the encoder's rule.
 //     f3   = alt | refA << 1 | refB << 2 straddle bits
 //     code = ospan_len translated into the index space of the library's histogram tables: with
 //            r = ospan_len - key_min, the kernel needs thr[r] (parsers.py:870-872) and, for a
@@ -48,6 +57,8 @@ namespace svt {
 // Order inside a stream is record order, so every sum sees the reference's additions in the reference's order.
 
 constexpr uint32_t kWideEntry = 0x8000u;      // pair stream: the next half-word holds this entry's MAPQs
+constexpr uint32_t kWideSwitch = kWideEntry;  // pair stream: the wide bit and nothing else -- the next half-word is the library the stream switches to
+constexpr uint32_t kShortSwitchLibs = 256u;   // libraries [0, 256) are named by the short switch (l + 1) << 3, the others by the wide one
 constexpr uint32_t kDefaultCommonMapq = 60u | (60u << 8);
 constexpr uint32_t kVoteRecords = 1u << 14;   // records the (host-side) MAPQ vote looks at
 

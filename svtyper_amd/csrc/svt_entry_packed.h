@@ -16,6 +16,11 @@ int svt_pack_evidence(const svt_evidence_batch* in, svt_packed_evidence** out)
     return guarded([&] { return pack_evidence(in, out); });
 }
 
+int svt_pack_evidence_flags(const svt_evidence_batch* in, unsigned pack_flags, svt_packed_evidence** out)
+{
+    return guarded([&] { return pack_evidence(in, out, pack_flags); });
+}
+
 void svt_packed_free(svt_packed_evidence* p)
 {
     if (!p) return;
@@ -70,12 +75,12 @@ static int svt_genotype_packed_from_records_impl(const svt_evidence_batch* in, s
     if (!in || (!out && in->n_units)) return fail(SVT_ERR_INVALID, "null argument");
     if (flags & ~(SVT_FLAG_SSO_ASSOCIATION | SVT_FLAG_RESULT96)) return fail(SVT_ERR_INVALID, "packed evidence takes SVT_FLAG_SSO_ASSOCIATION and SVT_FLAG_RESULT96 only");
     const uint64_t n = in->n_units;
-    const bool overlap = n >= kPipelineMinUnits && n < 0x55555550ull && in->n_libs >= 1 && in->n_libs <= 256 && in->libs && in->rec_offset && in->units && in->records &&
+    const bool overlap = n >= kPipelineMinUnits && n < 0x55555550ull && in->n_libs >= 1 && in->n_libs <= 65536 && in->libs && in->rec_offset && in->units && in->records &&
                          in->rec_offset[0] == 0 && in->split_weight >= 0.0 && in->disc_weight >= 0.0 && std::isfinite(in->split_weight) &&
                          std::isfinite(in->disc_weight) && !std::getenv("SVT_PACKED_SERIAL");
     auto serial = [&]() -> int {   // small batches, and whatever the overlapped form declines: encode, then the packed one shot
         svt_packed_evidence* p = nullptr;
-        SVT_TRY(pack_evidence(in, &p));
+        SVT_TRY(pack_evidence(in, &p, SVT_PACK_MANY_LIBRARIES));   // (the caller chose the packed route: any number of libraries)
         const int rc = svt_genotype_packed(p, out, device, flags);
         svt_packed_free(p);
         return rc;
@@ -98,8 +103,13 @@ static int svt_genotype_packed_from_records_impl(const svt_evidence_batch* in, s
     if (max_f > 0x3FFFFFFFull) return fail(SVT_ERR_INVALID, "unit with too many records");
     const uint64_t n_rec = in->rec_offset[n];
     // 5 bytes per record (3.1 is typical; several libraries: 6, a switch in front of most pair entries of a sample sequenced more
-    // than once) + a slot per stream and unit
-    const uint64_t slots_cap = n_rec / 16 * (in->n_libs > 1 ? 6 : 5) + 3 * n + 4096;
+    // than once; wide switches: 8) + a slot per stream and unit.  An estimate, not a bound: the pair stream alone can take 10
+    // bytes per record (a padded wide switch and a wide entry each).  Three libraries per sample, every fifth entry wide, pack
+    // to 6.2 bytes per record; two libraries >= 256 alternating record by record with EVERY entry wide and every record stored to
+    // 8.4 with units of 60 records, which the slot per stream and unit still covers -- whatever exceeds it is caught by the
+    // encoder before it writes (SVT_ERR_PACK_OVERFLOW: tests/native/asan_pack_many_main.cpp drives that answer at 300
+    // libraries) and takes the plain sequence below, which sizes the array exactly: time, not correctness.
+    const uint64_t slots_cap = n_rec / 16 * (in->n_libs > kShortSwitchLibs ? 8 : in->n_libs > 1 ? 6 : 5) + 3 * n + 4096;
     if (slots_cap >= 0xFFFFFFF0ull) return serial();
 
     BatchOwner owner;
@@ -180,7 +190,7 @@ static int svt_genotype_packed_from_records_impl(const svt_evidence_batch* in, s
             if (c.ps.down) (void)hipStreamSynchronize(c.ps.down);
         };
         const PackAlloc pool{[](uint64_t bytes) { return g_pinned.get(bytes); }, [](void* p) { g_pinned.put(p); }};
-        rc = encode_packed(in, pool, &arr, &sink);
+        rc = encode_packed(in, pool, &arr, &sink, /*many_libraries=*/true);
         overflow = rc == SVT_ERR_PACK_OVERFLOW;
     }
     // whatever was enqueued has to be through before anything is released

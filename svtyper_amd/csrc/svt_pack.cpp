@@ -95,7 +95,14 @@ struct PairStream {
     inline void sync_lib()
     {
         if (want_lib != cur_lib) {
-            begin[n++] = (uint16_t)((want_lib + 1u) << 3);
+            if (want_lib < kShortSwitchLibs) {
+                begin[n++] = (uint16_t)((want_lib + 1u) << 3);
+            } else {                               // the wide switch: aligned like a wide entry, the library in its second half-word
+                begin[n] = 0;
+                n += n & 1u;
+                begin[n++] = (uint16_t)kWideSwitch;
+                begin[n++] = (uint16_t)want_lib;
+            }
             cur_lib = want_lib;
         }
     }
@@ -251,6 +258,7 @@ inline void encode_records_runs(const Slot* recs, const uint64_t r0, const uint6
 // second record: the first-of-fragment bits then depend on the records before it) is left to encode_records.
 // one-half-word pair entries `ent` of the lanes in `run`, of libraries `libv`: compressed to the front; a switch half-word goes
 // in front of every entry whose library differs from the entry before it (the first one: from the stream's current library).
+// Short switches only: every library of `run` is below kShortSwitchLibs (the caller sends other groups entry by entry).
 // Switches and entries interleaved lane by lane (s0 e0 s1 e1 ...), the lanes that exist compressed once more and stored.
 __attribute__((target("avx512f,avx512bw,avx512vl,bmi2")))
 inline void emit_mixed_run(PairStream& S, const __m512i ent, const __m512i libv, const __mmask16 run, const uint32_t n_libs)
@@ -338,7 +346,7 @@ inline void encode_records_avx512(const Slot* recs, const uint64_t r0, const uin
             // every record's library as an index into the unit's window of sixteen; the window moves to the group's libraries
             // when a record falls outside it, its entries are filled when first named
             const __mmask16 valid = (__mmask16)((1u << n_here) - 1u);
-            libv = _mm512_and_si512(_mm512_srli_epi32(fw, SVT_REC_LIB_SHIFT), _mm512_set1_epi32(0xff));
+            libv = _mm512_and_si512(_mm512_srli_epi32(fw, SVT_REC_LIB_SHIFT), _mm512_set1_epi32(0xffff));
             __m512i idx = _mm512_sub_epi32(libv, _mm512_set1_epi32((int32_t)M->lo));
             if (_mm512_mask_cmpge_epu32_mask(valid, idx, _mm512_set1_epi32(16))) {
                 const uint32_t gmin = _mm512_mask_reduce_min_epu32(valid, libv), gmax = _mm512_mask_reduce_max_epu32(valid, libv);
@@ -396,12 +404,21 @@ inline void encode_records_avx512(const Slot* recs, const uint64_t r0, const uin
             if (MULTI && mixed) {
                 // one-half-word entries in runs between the (few) wide ones, each run with its switches (emit_mixed_run)
                 alignas(64) uint32_t e32[16], m32[16], l32[16];
-                if (wide) {
+                // a kept entry of a library only the wide switch names: the group goes out entry by entry (PairStream::put)
+                const bool far = _mm512_mask_cmpge_epu32_mask(keep, libv, _mm512_set1_epi32((int32_t)kShortSwitchLibs)) != 0;
+                if (wide || far) {
                     _mm512_store_si512(e32, ent);
                     _mm512_store_si512(m32, mq);
                     _mm512_store_si512(l32, libv);
                 }
                 unsigned from = 0;
+                if (far) {
+                    for (unsigned m = keep; m; m &= m - 1u) {
+                        const unsigned i = (unsigned)__builtin_ctz(m);
+                        S.want_lib = l32[i] < M->n_libs ? l32[i] : 0u;
+                        S.put(e32[i], m32[i], M->common);
+                    }
+                } else
                 while (true) {
                     const unsigned i = wide ? (unsigned)__builtin_ctz(wide) : 16u;
                     const __mmask16 run = (__mmask16)(keep & ((1u << i) - 1u) & ~((1u << from) - 1u));
@@ -814,14 +831,17 @@ int run_ranged_phases(unsigned nt, uint64_t n_ranges, First&& first, Between&& b
 }
 }  // namespace
 
-int encode_packed(const svt_evidence_batch* in, const PackAlloc& A, PackedArrays* out, const PackSink* sink)
+int encode_packed(const svt_evidence_batch* in, const PackAlloc& A, PackedArrays* out, const PackSink* sink, const bool many_libraries)
 {
     if (!in || !out) return fail(SVT_ERR_INVALID, "null argument");
     *out = PackedArrays{};
     const uint64_t n = in->n_units;
     if (n >= 0x55555550ull) return fail(SVT_ERR_INVALID, "too many units in one batch");
     if (in->n_libs == 0 || in->n_libs > 65536 || !in->libs) return fail(SVT_ERR_INVALID, "n_libs must be 1..65536");
-    if (in->n_libs > 256) return fail(SVT_ERR_UNSUPPORTED, "packed evidence names a library with eight bits: a batch of more than 256 libraries stays canonical");
+    // (the caller's choice, not the format's limit: svt_pack_evidence keeps its answer of ABI <= 18 for callers that take it as
+    // "this batch stays canonical"; svt_pack_evidence_flags + SVT_PACK_MANY_LIBRARIES and svt_genotype_packed_from_records lift it)
+    if (in->n_libs > kShortSwitchLibs && !many_libraries)
+        return fail(SVT_ERR_UNSUPPORTED, "packed evidence of more than 256 libraries is asked for with SVT_PACK_MANY_LIBRARIES: without it such a batch stays canonical");
     if (n && (!in->rec_offset || !in->units)) return fail(SVT_ERR_INVALID, "null unit arrays");
     if (n && in->rec_offset[0] != 0) return fail(SVT_ERR_INVALID, "rec_offset[0] must be 0");
     if (!(in->split_weight >= 0.0) || !(in->disc_weight >= 0.0) || !std::isfinite(in->split_weight) || !std::isfinite(in->disc_weight))
@@ -993,9 +1013,10 @@ int encode_packed(const svt_evidence_batch* in, const PackAlloc& A, PackedArrays
                 if (multi && SVT_UNIT_LIBS_FIRST(U.libs) < n_libs) M.lo = SVT_UNIT_LIBS_FIRST(U.libs);     // (the hint, where there is one: the sample's first library)
                 const uint64_t f = r1 - r0;
                 // worst case per stream: every record a wide pair entry behind a pad half-word (3 half-words; several libraries:
-                // and a library switch in front of it), one reference-read entry, two candidate entries; + two or three slots:
+                // and a library switch in front of it -- a wide one is two half-words on a 4-byte boundary, the entry behind it
+                // then needs no pad), one reference-read entry, two candidate entries; + two or three slots:
                 // the vector form stores sixteen half-words at once
-                const uint64_t cap_s = ((multi ? 4 : 3) * f + 8 + 7) / 8 + 3, cap_r = f / 7 + 4, cap_x = 2 * f / 7 + 2;
+                const uint64_t cap_s = ((n_libs > kShortSwitchLibs ? 5 : multi ? 4 : 3) * f + 8 + 7) / 8 + 3, cap_r = f / 7 + 4, cap_x = 2 * f / 7 + 2;
                 if (W.scratch.size() < (cap_s + cap_r + cap_x) * 8) W.scratch.resize((cap_s + cap_r + cap_x) * 8);
                 PairStream S(W.scratch.data());
                 WeightStream R(W.scratch.data() + cap_s * 8), X(W.scratch.data() + (cap_s + cap_r) * 8);

@@ -47,10 +47,13 @@ struct PackSink {
 };
 constexpr int SVT_ERR_PACK_OVERFLOW = -1000;   // internal: never leaves the library
 
-// Encode `in` (canonical records, one library) as packed evidence.  On success the caller owns out->off / units / slots
+// Encode `in` (canonical records, 1..65536 libraries) as packed evidence.  On success the caller owns out->off / units / slots
 // (allocated with A.get); on failure nothing is left allocated.  SVT_ERR_UNSUPPORTED: the batch cannot be expressed
 // in the packed format (keep the canonical records); SVT_ERR_INVALID: it breaks the contract of include/svtyper_hip.h.
-int encode_packed(const svt_evidence_batch* in, const PackAlloc& A, PackedArrays* out, const PackSink* sink = nullptr);
+// many_libraries: a batch of more than 256 libraries is encoded (wide library switches, svt_entry_formats.h) instead of answered
+// with SVT_ERR_UNSUPPORTED; a batch of at most 256 gets the same slots either way.
+int encode_packed(const svt_evidence_batch* in, const PackAlloc& A, PackedArrays* out, const PackSink* sink = nullptr,
+                  bool many_libraries = false);
 
 }  // namespace svt
 

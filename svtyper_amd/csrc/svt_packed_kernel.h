@@ -25,7 +25,7 @@ struct PackedArgs {
     const double* pm;             // 256
     const double* l10;            // n_l10
     const Bin* bins;              // every library's n_bins + 1
-    const LibDesc* libs;          // n_libs (several libraries: staged in LDS; their tables are read from bins[] through L2)
+    const LibDesc* libs;          // n_libs (2..256 libraries: staged in LDS, more: read where they are; the tables are read from bins[] through L2)
     uint32_t n_libs;
     const PairWeights* wtab;      // 32
     uint32_t n_l10;
@@ -44,8 +44,9 @@ struct PackedArgs {
     GtConsts c;
 };
 
-// MULTI: packed evidence of several libraries (library switches in the pair stream, svt_entry_formats.h)
-template <bool SSO, int R, bool MULTI>
+// MULTI (svt_unit_math.h: kOneLibrary / kLibsInLds / kLibsInHbm): packed evidence of several libraries (library switches in
+// the pair stream, svt_entry_formats.h) and where a switch finds the library's descriptor
+template <bool SSO, int R, int MULTI>
 __global__ __launch_bounds__(kBlock, 3) void svt_packed_kernel(const PackedArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -81,7 +82,9 @@ __global__ __launch_bounds__(kBlock, 3) void svt_packed_kernel(const PackedArgs 
         reinterpret_cast<double*>(smem + kLdsWcolC)[tid] = pp0 * w.w_alt;
         reinterpret_cast<double*>(smem + kLdsWcolC + kWcolRef)[tid] = pp0 * w.w_ref;
     }
-    if (MULTI) {     // the library descriptors, where the one-library form keeps its bins
+    if (MULTI == kLibsInHbm) {
+        // nothing to stage: the descriptors stay in device memory, the region behind kLdsBins starts with log10 / the rings
+    } else if (MULTI) {     // the library descriptors, where the one-library form keeps its bins
         for (uint32_t i = tid; i < a.n_libs * (uint32_t)(sizeof(LibDesc) / 8); i += kBlock)
             reinterpret_cast<uint64_t*>(smem + kLdsBins)[i] = reinterpret_cast<const uint64_t*>(a.libs)[i];
     } else {
@@ -162,10 +165,10 @@ __global__ __launch_bounds__(kBlock, 3) void svt_packed_kernel(const PackedArgs 
                     if (__any(is_pair)) {
                         const uint32_t x = is_pair ? w[j].x : 0u, y = is_pair ? w[j].y : 0u, z = is_pair ? w[j].z : 0u,
                                        v = is_pair ? w[j].w : 0u;
-                        short_pair_dword<MULTI>(x, c, acc, a.bins);
-                        short_pair_dword<MULTI>(y, c, acc, a.bins);
-                        short_pair_dword<MULTI>(z, c, acc, a.bins);
-                        short_pair_dword<MULTI>(v, c, acc, a.bins);
+                        short_pair_dword<MULTI>(x, c, acc, a.bins, a.libs);
+                        short_pair_dword<MULTI>(y, c, acc, a.bins, a.libs);
+                        short_pair_dword<MULTI>(z, c, acc, a.bins, a.libs);
+                        short_pair_dword<MULTI>(v, c, acc, a.bins, a.libs);
                     }
                     if (__any(is_ref))
                         ref_read_row<SSO>(is_ref ? make_uint4(w[j].x, w[j].y, w[j].z, w[j].w) : make_uint4(0, 0, 0, 0), acc);

@@ -5,6 +5,7 @@
 #define SVT_UNIT_MATH_H
 
 #include "svt_device_types.h"
+#include "svt_entry_formats.h"
 
 namespace svt {
 
@@ -158,7 +159,8 @@ __device__ __forceinline__ void pair_evidence(const uint32_t o, const uint32_t m
 // n_bins + 1 Bin{thr, hist}, a few hundred KB at most: L2) -- the libraries of a batch do not fit LDS together, and a launch
 // over unit ranges (the route encodes ahead of the wire) cannot group its workgroups by library window the way the
 // canonical route does.  The pass over packed evidence is a few per cent of its route either way.
-template <bool MULTI>
+// MULTI is kOneLibrary / kLibsInLds / kLibsInHbm (below).
+template <int MULTI>
 __device__ __forceinline__ void pair_tables(const uint32_t code4, const LaneCtx& c, const Bin* bins, int32_t& thr1, uint32_t& h2)
 {
     if (MULTI) {
@@ -171,20 +173,42 @@ __device__ __forceinline__ void pair_tables(const uint32_t code4, const LaneCtx&
     }
 }
 
-// a half-word of the pair stream that is not the MAPQ half of a wide entry: a library switch (l + 1) << 3 moves the lane's
-// table context to library l (clamped to the batch's libraries: slots a caller wrote itself are not trusted with addresses)
-__device__ __forceinline__ void switch_library(const uint32_t h, LaneCtx& c)
+// Where the pass over packed evidence keeps the library descriptors a switch re-derives the lane's context from:
+//   kLibsInLds   2..256 libraries: LibDesc[n_libs] staged in the workgroup's LDS (8 KB at most)
+//   kLibsInHbm   257..65536 libraries (2 MB of descriptors at most): nothing is staged, so there is no staging area to
+//                overflow however many libraries a workgroup's units name -- every switch reads its descriptor from the
+//                LibDesc[] the batch uploaded (the canonical route's array), 16 bytes through L2, and understands the wide
+//                switch as well.  A lane is a unit: a switch is that lane's own affair, no barrier and no vote is involved.
+constexpr int kOneLibrary = 0, kLibsInLds = 1, kLibsInHbm = 2;
+
+// the lane's table context moves to library l (clamped to the batch's libraries: slots a caller wrote itself are not trusted
+// with addresses)
+template <int MULTI>
+__device__ __forceinline__ void enter_library(const uint32_t l, LaneCtx& c, const LibDesc* libs)
 {
-    if ((h & 0x8007u) == 0u && h != 0u) {
-        const uint32_t at = c.libs_at + min((h >> 3) - 1u, c.lib_last) * (uint32_t)sizeof(LibDesc);
-        const uint32_t n_bins = lds_u32(at + 8u);
-        c.tab8 = lds_u32(at) * (uint32_t)sizeof(Bin);
-        c.nb4 = n_bins * 4u;
-        c.off2_4 = c.is_del ? min((uint32_t)c.var_length, n_bins) * 4u : 0x80000000u;
+    uint32_t tab_off, n_bins;
+    if (MULTI == kLibsInHbm) {
+        const uint4 d = *reinterpret_cast<const uint4*>(libs + min(l, c.lib_last));     // {tab_off, key_min, n_bins, pad}
+        tab_off = d.x;
+        n_bins = d.z;
+    } else {
+        const uint32_t at = c.libs_at + min(l, c.lib_last) * (uint32_t)sizeof(LibDesc);
+        tab_off = lds_u32(at);
+        n_bins = lds_u32(at + 8u);
     }
+    c.tab8 = tab_off * (uint32_t)sizeof(Bin);
+    c.nb4 = n_bins * 4u;
+    c.off2_4 = c.is_del ? min((uint32_t)c.var_length, n_bins) * 4u : 0x80000000u;
 }
 
-template <bool MULTI>
+// a half-word of the pair stream that is not the MAPQ half of a wide entry: a short library switch (l + 1) << 3
+template <int MULTI>
+__device__ __forceinline__ void switch_library(const uint32_t h, LaneCtx& c, const LibDesc* libs)
+{
+    if ((h & 0x8007u) == 0u && h != 0u) enter_library<MULTI>((h >> 3) - 1u, c, libs);
+}
+
+template <int MULTI>
 __device__ __forceinline__ void pair_eval_single(const uint32_t code4, const uint32_t f3x8, const double pp,
                                                  const LaneCtx& c, Acc& a, const Bin* bins)
 {
@@ -198,17 +222,20 @@ __device__ __forceinline__ void pair_eval_single(const uint32_t code4, const uin
     a.ref_span += pp * w_ref;
 }
 
-template <bool MULTI>
-__device__ __forceinline__ void short_pair_dword(const uint32_t e, LaneCtx& c, Acc& a, const Bin* bins)
+template <int MULTI>
+__device__ __forceinline__ void short_pair_dword(const uint32_t e, LaneCtx& c, Acc& a, const Bin* bins, const LibDesc* libs)
 {
     const bool wide = (e & 0x8000u) != 0u;
     const uint32_t hi = e >> 16;
     const uint32_t mq = wide ? hi : c.common_mq;
     const double pm_a = lds_f64(kLdsPm + byte0_x8(mq)), pm_b = lds_f64(kLdsPm + byte1_x8(mq));
     // (a library switch is then also evaluated as the entry it is not: no straddle bit, both weights 0, the sums receive +0.0)
-    if (MULTI) switch_library(e & 0xffffu, c);
+    if (MULTI) switch_library<MULTI>(e & 0xffffu, c, libs);
+    // the wide switch (kWideSwitch, then the library): the dword is evaluated like the wide entry it resembles -- no straddle
+    // bit, +0.0 -- against whichever library's tables the context names, old or new: both are whole contexts
+    if (MULTI == kLibsInHbm && (e & 0xffffu) == kWideSwitch) enter_library<MULTI>(hi, c, libs);
     pair_eval_single<MULTI>((e >> 1) & 0x3ffcu, (e << 3) & 0x38u, pm_a * pm_b, c, a, bins);
-    if (MULTI && !wide) switch_library(hi, c);
+    if (MULTI && !wide) switch_library<MULTI>(hi, c, libs);
     // the high half: a second entry with the common MAPQs -- its products pmA * pmB * {w_alt, w_ref} come ready from the
     // second decision table -- or the MAPQ bytes of the wide entry just added: then the straddle bits read as 0,
     // both table values are 0 and the sums receive +0.0

@@ -24,7 +24,7 @@ EXPORTS = (
     "svt_batch_genotype_n", "svt_batch_sync", "svt_batch_genotype_timed", "svt_batch_tune_placement", "svt_batch_results", "svt_batch_device_results",
     "svt_batch_bind_device_results", "svt_batch_bind_device_results2", "svt_batch_result_order", "svt_batch_bytes", "svt_batch_layout", "svt_batch_site_qual",
     "svt_batch_stream", "svt_batch_destroy", "svt_trim", "svt_bayes_gt", "svt_genotype_counts", "svt_genotype", "svt_genotype_multi", "svt_shard_bounds",
-    "svt_pinned_alloc", "svt_pinned_free", "svt_pack_evidence", "svt_packed_free", "svt_batch_create_packed", "svt_genotype_packed",
+    "svt_pinned_alloc", "svt_pinned_free", "svt_pack_evidence", "svt_pack_evidence_flags", "svt_packed_free", "svt_batch_create_packed", "svt_genotype_packed",
     "svt_format_results", "svt_format_free", "svt_results_host_sq", "svt_batch_result_bytes", "svt_batch_result_slots", "svt_results_expand96",
     "svt_genotype_packed_from_records", "svt_chunk_bounds",
 )
@@ -122,6 +122,8 @@ def load() -> C.CDLL:
     L.svt_pinned_free.argtypes = [C.c_void_p]
     L.svt_pack_evidence.restype = C.c_int
     L.svt_pack_evidence.argtypes = [C.POINTER(CEvidenceBatch), C.POINTER(C.POINTER(CPackedEvidence))]
+    L.svt_pack_evidence_flags.restype = C.c_int
+    L.svt_pack_evidence_flags.argtypes = [C.POINTER(CEvidenceBatch), C.c_uint, C.POINTER(C.POINTER(CPackedEvidence))]
     L.svt_packed_free.restype = None
     L.svt_packed_free.argtypes = [C.POINTER(CPackedEvidence)]
     L.svt_batch_create_packed.restype = C.c_int
@@ -158,24 +160,28 @@ def device_count() -> int:
 
 
 ERR_UNSUPPORTED = -7
+PACK_MANY_LIBRARIES = 0x1      # SVT_PACK_MANY_LIBRARIES
 
 
 class PackedEvidence:
     """Packed evidence of a batch on the host (svt_packed_evidence, svt_pack_evidence): three sparse streams of small
-    entries per unit instead of 16-byte records -- what crosses PCIe when the records were produced on the host."""
+    entries per unit instead of 16-byte records -- what crosses PCIe when the records were produced on the host.
+    `many_libraries`: encode a batch of 257..65536 libraries too (svt_pack_evidence_flags, SVT_PACK_MANY_LIBRARIES);
+    without it such a batch is declined, as it always was."""
 
-    def __init__(self, batch: EvidenceBatch):
+    def __init__(self, batch: EvidenceBatch, many_libraries: bool = False):
         L = load()
         self._lib = L
         self._p = C.POINTER(CPackedEvidence)()
         cb = batch.as_c()
-        _check(L.svt_pack_evidence(C.byref(cb), C.byref(self._p)))
+        _check(L.svt_pack_evidence_flags(C.byref(cb), PACK_MANY_LIBRARIES if many_libraries else 0, C.byref(self._p)))
 
     @classmethod
-    def try_pack(cls, batch: EvidenceBatch):
-        """None when the batch cannot be expressed as packed evidence (a histogram of more than 2047 bins, ...)."""
+    def try_pack(cls, batch: EvidenceBatch, many_libraries: bool = False):
+        """None when the batch cannot be expressed as packed evidence (a histogram of more than 2047 bins, more than 256
+        libraries without `many_libraries`, ...)."""
         try:
-            return cls(batch)
+            return cls(batch, many_libraries)
         except SvtyperHipError as e:
             if "error %d" % ERR_UNSUPPORTED in str(e):
                 return None
