@@ -226,6 +226,8 @@ class AlignedSegment:
         return ov
 
     # ---- tags
+    _STRING_TAGS = ("RG", "SA")
+
     def _parse_tags(self):
         tags: Dict[str, object] = {}
         b = self._tagbytes
@@ -260,7 +262,10 @@ class AlignedSegment:
                 val = list(struct.unpack_from("<%d%s" % (cnt, fmt), b, i)); i += cnt * sz
             else:
                 raise ValueError("unknown BAM tag type %r" % t)
-            tags[key] = val
+            # A record holds a tag name once (SAM 1.5) and RG and SA are strings.  Where a record departs from that the native
+            # reader's rule holds (rr::walk_tags): the first value of a name, and under RG and SA only a value of type Z.
+            if key not in tags and (t == "Z" or key not in self._STRING_TAGS):
+                tags[key] = val
         self._tags = tags
 
     def has_tag(self, key: str) -> bool:

@@ -153,7 +153,7 @@ SVT_HD void tags_begin(Tags& t)
 enum : uint32_t {
     TAGS_END = 0,            // the whole tag area is walked
     TAGS_AT_RG = 1,          // stopped behind the first RG:Z
-    TAGS_MALFORMED = 2,      // unknown type, Z / H value without its NUL, B header cut off
+    TAGS_MALFORMED = 2,      // unknown type or B subtype, Z / H value without its NUL, B header cut off
     TAGS_OVERRUN = 3         // a fixed-size value or a B array that reaches beyond the record
 };
 SVT_HD uint32_t walk_tags(const uint8_t* d, uint32_t size, uint32_t& at, bool stop_at_rg, Tags& t)
@@ -184,7 +184,8 @@ SVT_HD uint32_t walk_tags(const uint8_t* d, uint32_t size, uint32_t& at, bool st
             if (i + 5 > n) return TAGS_MALFORMED;
             const uint8_t sub = d[i];
             const uint32_t cnt = ld32(d + i + 1);
-            const uint64_t sz = (sub == 'c' || sub == 'C') ? 1 : (sub == 's' || sub == 'S') ? 2 : 4;
+            const uint64_t sz = (sub == 'c' || sub == 'C') ? 1 : (sub == 's' || sub == 'S') ? 2 : (sub == 'i' || sub == 'I' || sub == 'f') ? 4 : 0;
+            if (sz == 0) return TAGS_MALFORMED;
             skip = 5 + (uint64_t)cnt * sz;
             break;
         }

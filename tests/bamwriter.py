@@ -5,6 +5,7 @@ import struct
 import zlib
 
 CIGAR_OPS = "MIDNSHP=X"
+SCALAR_CODES = {"c": "b", "C": "B", "s": "h", "S": "H", "i": "i", "I": "I", "f": "f"}   # BAM type code -> struct code
 
 
 def reg2bin(beg, end):
@@ -56,15 +57,16 @@ def encode_record(r):
             body += val
             continue
         body += key.encode() + typ.encode()
-        if typ == "Z":
+        if typ == "Z" or typ == "H":   # (H: the hex digits as text)
             body += val.encode() + b"\0"
-        elif typ == "C":
-            body += struct.pack("<B", val)
-        elif typ == "i":
-            body += struct.pack("<i", val)
+        elif typ == "A":
+            assert len(val) == 1
+            body += val.encode()
+        elif typ in SCALAR_CODES:
+            body += struct.pack("<" + SCALAR_CODES[typ], val)
         elif typ == "B":   # (subtype, values)
             sub, vals = val
-            code = {"c": "b", "C": "B", "s": "h", "S": "H", "i": "i", "I": "I", "f": "f"}[sub]
+            code = SCALAR_CODES[sub]
             body += sub.encode() + struct.pack("<I", len(vals)) + b"".join(struct.pack("<" + code, v) for v in vals)
         else:
             raise ValueError(typ)
