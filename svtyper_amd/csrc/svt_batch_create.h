@@ -70,6 +70,25 @@ uint64_t max_batch_records()
     return cached;
 }
 
+// The LDS of a kernel for launches of less than one round: `region_bytes` of its own behind the tables that end at `tab`.
+// l10_in_front: the log10 table goes between the two when the workgroup then still takes no more than half a CU's LDS (two
+// workgroups per CU); else the epilogues read it through L2.  lds_bytes == 0: the region does not fit a CU.
+SmallRegion small_region(size_t tab, const size_t region_bytes, const bool l10_in_front, const size_t l10_bytes = 0, const uint32_t n_l10 = 0)
+{
+    SmallRegion r;
+    if (l10_in_front && tab + l10_bytes + region_bytes <= (160 * 1024 / 2)) {
+        r.l10_where = kL10Shared;
+        r.lds_l10 = (uint32_t)tab;
+        r.l10_entries = n_l10;
+        tab += l10_bytes;
+    }
+    if (tab + region_bytes <= 160 * 1024) {
+        r.region = (uint32_t)tab;
+        r.lds_bytes = tab + region_bytes;
+    }
+    return r;
+}
+
 int create_stream(const svt_evidence_batch* in, svt_batch* b, void* d_records_resident = nullptr, uint64_t resident_cap = 0,
                   bool defer_records = false)   // defer_records: the caller uploads the records itself (pipelined one-shot)
 {
@@ -414,59 +433,38 @@ int create_stream(const svt_evidence_batch* in, svt_batch* b, void* d_records_re
         a.l10_lds_entries = 0;
     }
     a.lds_rings = (uint32_t)tables;
-    // the cooperative kernel (one library): its own region behind the tables, two workgroups per CU
+    // the cooperative kernel (one library): its own region behind the tables (without the streaming kernel's log10 table), two
+    // workgroups per CU
     if (b->mode == kSingleLds && a.l10_where != kL10Ring) {
-        size_t ctab = (a.lds_winlibs + 127) & ~size_t(127);     // the tables without the log10 table
-        b->coop_l10_where = kL10Global;
-        b->coop_lds_l10 = 0;
-        b->coop_l10_entries = 0;
-        if (ctab + l10_bytes + kCoopRegionBytes <= (160 * 1024 / 2)) {
-            b->coop_l10_where = kL10Shared;
-            b->coop_lds_l10 = (uint32_t)ctab;
-            b->coop_l10_entries = n_l10;
-            ctab += l10_bytes;
-        }
-        if (ctab + kCoopRegionBytes <= 160 * 1024) {
-            b->coop_region = (uint32_t)ctab;
-            b->coop_lds_bytes = ctab + kCoopRegionBytes;
+        const size_t tab = (a.lds_winlibs + 127) & ~size_t(127);
+        b->coop = small_region(tab, kCoopRegionBytes, true, l10_bytes, n_l10);
+        if (b->coop.lds_bytes) {
             int wgs = 2;
             hipFuncAttributes fa{};
             if (hipFuncGetAttributes(&fa, coop_kernel_of(b)) == hipSuccess && fa.numRegs > 0) wgs = std::max(1, std::min(4, 512 / ((fa.numRegs + 7) / 8 * 8) * 4 / kCoopWaves));
             else (void)hipGetLastError();
-            b->coop_resident = (uint32_t)std::min<size_t>((size_t)wgs, (160 * 1024) / b->coop_lds_bytes) * cu_count(b->device);
-            if (b->coop_lds_bytes > 64 * 1024) HIP_TRY(hipFuncSetAttribute(coop_kernel_of(b), hipFuncAttributeMaxDynamicSharedMemorySize, (int)b->coop_lds_bytes));
+            b->coop_resident = (uint32_t)std::min<size_t>((size_t)wgs, (160 * 1024) / b->coop.lds_bytes) * cu_count(b->device);
+            if (b->coop.lds_bytes > 64 * 1024) HIP_TRY(hipFuncSetAttribute(coop_kernel_of(b), hipFuncAttributeMaxDynamicSharedMemorySize, (int)b->coop.lds_bytes));
         }
         // ... and the kernel with K lanes per unit
-        size_t stab = (a.lds_winlibs + 127) & ~size_t(127);
-        if (stab + l10_bytes + kSplitRegionBytes <= (160 * 1024 / 2)) {
-            b->split_l10_where = kL10Shared;
-            b->split_lds_l10 = (uint32_t)stab;
-            b->split_l10_entries = n_l10;
-            stab += l10_bytes;
-        }
-        if (stab + kSplitRegionBytes <= 160 * 1024) {
-            b->split_region = (uint32_t)stab;
-            b->split_lds_bytes = stab + kSplitRegionBytes;
-            if (b->split_lds_bytes > 64 * 1024)
-                for (int lanes = 2; lanes <= 4; lanes += 2)
-                    HIP_TRY(hipFuncSetAttribute(split_kernel_of(b, lanes), hipFuncAttributeMaxDynamicSharedMemorySize, (int)b->split_lds_bytes));
-        }
+        b->split = small_region(tab, kSplitRegionBytes, true, l10_bytes, n_l10);
+        if (b->split.lds_bytes > 64 * 1024)
+            for (int lanes = 2; lanes <= 4; lanes += 2)
+                HIP_TRY(hipFuncSetAttribute(split_kernel_of(b, lanes), hipFuncAttributeMaxDynamicSharedMemorySize, (int)b->split.lds_bytes));
     }
     if (b->mode == kMultiLds && a.l10_where != kL10Ring) {
-        // the kernel with K lanes per unit over library windows: its region behind the window tables (and the log10 table where
-        // the streaming kernel keeps it beside them)
-        const size_t stab = (tables + 127) & ~size_t(127);
-        if (stab + kSplitRegionBytes <= 160 * 1024) {
-            b->split_region = (uint32_t)stab;
-            b->split_lds_bytes = stab + kSplitRegionBytes;
-            b->split_l10_where = a.l10_where;
-            b->split_lds_l10 = a.lds_l10;
-            b->split_l10_entries = a.l10_lds_entries;
-            if (b->split_lds_bytes > 64 * 1024)
-                for (int lanes = 2; lanes <= 4; lanes += 2)
-                    if (lanes == 4 || !(b->flags & SVT_FLAG_SSO_ASSOCIATION))
-                        HIP_TRY(hipFuncSetAttribute(split_kernel_of(b, lanes), hipFuncAttributeMaxDynamicSharedMemorySize, (int)b->split_lds_bytes));
+        // the kernel with K lanes per unit over library windows: its region behind the window tables -- and behind the log10 table
+        // where the streaming kernel keeps it beside them: the epilogues find it where the streaming kernel's do
+        b->split = small_region((tables + 127) & ~size_t(127), kSplitRegionBytes, false);
+        if (b->split.lds_bytes) {
+            b->split.l10_where = a.l10_where;
+            b->split.lds_l10 = a.lds_l10;
+            b->split.l10_entries = a.l10_lds_entries;
         }
+        if (b->split.lds_bytes > 64 * 1024)
+            for (int lanes = 2; lanes <= 4; lanes += 2)
+                if (lanes == 4 || !(b->flags & SVT_FLAG_SSO_ASSOCIATION))
+                    HIP_TRY(hipFuncSetAttribute(split_kernel_of(b, lanes), hipFuncAttributeMaxDynamicSharedMemorySize, (int)b->split.lds_bytes));
     }
     a.n_units = n;
     a.unit_begin = 0;

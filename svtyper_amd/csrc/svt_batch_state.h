@@ -273,12 +273,12 @@ int split_lanes_for(const svt_batch* b, uint64_t units)
 {
     const int kind = g_small_kind.load(std::memory_order_relaxed);
     const bool sso = (b->flags & SVT_FLAG_SSO_ASSOCIATION) != 0;
-    if (!b->split_lds_bytes || !units) return 0;
+    if (!b->split.lds_bytes || !units) return 0;
     if (kind == 3) return sso && b->mode == kMultiLds ? 0 : 2;
     if (kind == 4) return 4;
     if (kind != 0) return 0;
     const uint64_t cus = cu_count(b->device);
-    const bool coop_first = b->coop_lds_bytes && units <= std::min<uint64_t>(cus * SVT_COOP_CU_UNITS, g_coop_max_units.load(std::memory_order_relaxed));
+    const bool coop_first = b->coop.lds_bytes && units <= std::min<uint64_t>(cus * SVT_COOP_CU_UNITS, g_coop_max_units.load(std::memory_order_relaxed));
     if (coop_first) return 0;
     return units <= cus * SVT_SPLIT4_CU_UNITS ? 4 : units <= cus * SVT_SPLIT2_CU_UNITS && !sso ? 2 : 0;
 }
@@ -291,7 +291,7 @@ WgPlan wg_plan(const svt_batch* b, uint64_t units)
     {
         const int kind = g_small_kind.load(std::memory_order_relaxed);
         const int lanes = split_lanes_for(b, units);
-        if (lanes && b->split_lds_bytes && units && !g_force_per_wg.load(std::memory_order_relaxed)) {
+        if (lanes && b->split.lds_bytes && units && !g_force_per_wg.load(std::memory_order_relaxed)) {
             p.split = lanes;
             p.tiles = 1;
             p.per_wg = (uint32_t)kBlock;
@@ -300,7 +300,7 @@ WgPlan wg_plan(const svt_batch* b, uint64_t units)
         }
         if (kind == 1 || kind == 3 || kind == 4) goto stream;
     }
-    if (b->coop_lds_bytes && units && g_small_kind.load(std::memory_order_relaxed) != 1 &&
+    if (b->coop.lds_bytes && units && g_small_kind.load(std::memory_order_relaxed) != 1 &&
         (units <= std::min<uint64_t>((uint64_t)cu_count(b->device) * SVT_COOP_CU_UNITS, g_coop_max_units.load(std::memory_order_relaxed)) ||
          g_small_kind.load(std::memory_order_relaxed) == 2) &&
         !g_force_per_wg.load(std::memory_order_relaxed)) {
@@ -345,24 +345,18 @@ int launch_stream(svt_batch* b, StreamArgs& a, hipStream_t stream)
     a.units_per_wg = p.per_wg;
     if (p.split) {
         StreamArgs c = a;
-        c.lds_rings = b->split_region;
-        c.l10_where = b->split_l10_where;
-        c.lds_l10 = b->split_lds_l10;
-        c.l10_lds_entries = b->split_l10_entries;
+        b->split.apply(c);
         const dim3 grid(p.n_wg), block(kBlock * p.split);
         void* params[] = {&c};
-        HIP_TRY(hipLaunchKernel(split_kernel_of(b, p.split), grid, block, params, b->split_lds_bytes, stream));
+        HIP_TRY(hipLaunchKernel(split_kernel_of(b, p.split), grid, block, params, b->split.lds_bytes, stream));
         return SVT_OK;
     }
     if (p.coop) {
         StreamArgs c = a;
-        c.lds_rings = b->coop_region;
-        c.l10_where = b->coop_l10_where;
-        c.lds_l10 = b->coop_lds_l10;
-        c.l10_lds_entries = b->coop_l10_entries;
+        b->coop.apply(c);
         const dim3 grid(p.n_wg), block(kCoopBlock);
         void* params[] = {&c};
-        HIP_TRY(hipLaunchKernel(coop_kernel_of(b), grid, block, params, b->coop_lds_bytes, stream));
+        HIP_TRY(hipLaunchKernel(coop_kernel_of(b), grid, block, params, b->coop.lds_bytes, stream));
         return SVT_OK;
     }
     const dim3 grid(p.n_wg), block(kBlock);
@@ -422,14 +416,11 @@ int launch_genotype(svt_batch* b)
         // a launch of less than one round: K lanes per unit (svt_split_kernel.h; the chunks hold at most 256 units)
         if (const int lanes = split_lanes_for(b, b->n_units)) {
             StreamArgs c = b->sargs;
-            c.lds_rings = b->split_region;
-            c.l10_where = b->split_l10_where;
-            c.lds_l10 = b->split_lds_l10;
-            c.l10_lds_entries = b->split_l10_entries;
+            b->split.apply(c);
             c.chunk_begin = 0;
             const dim3 grid(b->n_chunks), block(kBlock * lanes);
             void* params[] = {&c};
-            HIP_TRY(hipLaunchKernel(split_kernel_of(b, lanes), grid, block, params, b->split_lds_bytes, b->stream));
+            HIP_TRY(hipLaunchKernel(split_kernel_of(b, lanes), grid, block, params, b->split.lds_bytes, b->stream));
             return SVT_OK;
         }
     }

@@ -36,15 +36,8 @@
 #ifndef SVT_COOP_DEPTH
 #define SVT_COOP_DEPTH 4      // tile steps of records a producer lane keeps in flight (HBM latency ~0.45 us, a step ~0.2-0.3 us)
 #endif
-#ifndef SVT_COOP_PROBE
-#define SVT_COOP_PROBE 0      // timing only (wrong results), bits: 1 = the producers do not write their addends, 2 = the consumer sums nothing,
-                              // 4 = no record loads, 8 = no look-ups
-#endif
 #ifndef SVT_COOP_WAVES_PER_SIMD
 #define SVT_COOP_WAVES_PER_SIMD 6   // the register allocation must allow this many waves per SIMD
-#endif
-#ifndef SVT_COOP_TRACE
-#define SVT_COOP_TRACE 0      // debugging: workgroup 0 prints the shader-clock time of its phases
 #endif
 #ifndef SVT_COOP_NT
 #define SVT_COOP_NT 1         // record loads non-temporal
@@ -64,7 +57,7 @@ static_assert(kCoopDepth % 2 == 0, "the stage parity of an unrolled step must be
 constexpr uint32_t kCoopStageBytes = 8u * 3u * 64u * 16u; // one tile step of addends: [slot 8][plane 3][position 64] x 16 bytes
 constexpr uint32_t kCoopTiles = kBlock / kWave;           // 64-unit tiles of a workgroup's (up to) 256 units
 // the cooperative region of the workgroup's LDS, byte offsets from StreamArgs::lds_rings (128-byte aligned)
-constexpr uint32_t kCoopTileAt = 0;                                  // uint4[256]  {first record, records, sub2, flags} by sorted position
+constexpr uint32_t kCoopTileAt = 0;                                  // uint4[256]  tile entries by sorted position (svt_wg_parts.h)
 constexpr uint32_t kCoopUnitAt = kCoopTileAt + kBlock * 16u;         // uint32[256] unit index (kPadUnit: none)
 constexpr uint32_t kCoopMiscAt = kCoopUnitAt + kBlock * 4u;          // uint32 tmax[4], cont[4]
 constexpr uint32_t kCoopTallyAt = kCoopMiscAt + 128u;                // double[5][256] tallies of the finished tiles
@@ -72,8 +65,6 @@ constexpr uint32_t kCoopStageAt = kCoopTallyAt + 5u * kBlock * 8u;   // two adde
 constexpr uint32_t kCoopRegionBytes = kCoopStageAt + 2u * kCoopStageBytes;
 static_assert(kCoopStageAt % 128u == 0u, "stages (and the result rings that reuse them) are line-aligned");
 static_assert(2u * kCoopStageBytes >= kCoopTiles * kRingBytes + 3u * (kMaxSortKey + 1u) * 4u, "the result rings / the sort scratch fit the stages");
-// flags word of a tile entry
-constexpr uint32_t kCoopFmask = 7u, kCoopDel16 = 16u, kCoopSvtypeShift = 8u, kCoopUflagsShift = 16u;
 
 // ---- the record arithmetic of record_single (svt_stream_kernel.h) in two halves ---------------------------------------
 struct CoopLook {
@@ -117,7 +108,6 @@ __global__ __launch_bounds__(kCoopBlock, SVT_COOP_WAVES_PER_SIMD) void svt_coop_
     static_assert(MODE == kSingleLds, "one library (library windows: next)");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     if ((uint32_t)(size_t)(__attribute__((address_space(3))) unsigned char*)smem != 0u) __builtin_trap();   // tables at absolute LDS addresses
-    const uint64_t trace_t0 = SVT_COOP_TRACE ? clock64() : 0;
     const uint32_t tid = threadIdx.x, lane = tid % kWave;
     const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(tid / kWave));
     unsigned char* region = smem + a.lds_rings;
@@ -129,8 +119,8 @@ __global__ __launch_bounds__(kCoopBlock, SVT_COOP_WAVES_PER_SIMD) void svt_coop_
     unsigned char* stages = region + kCoopStageAt;
     const uint32_t stage_addr = (uint32_t)(size_t)(__attribute__((address_space(3))) unsigned char*)stages;
 
-    const uint32_t wg_base = a.unit_begin + blockIdx.x * a.units_per_wg;
-    const uint32_t n_here = min(a.units_per_wg, a.unit_end - wg_base);
+    const WgUnits g = wg_units<MODE>(a);
+    const uint32_t wg_base = g.wg_base, n_here = g.n_here;
     const bool sorter = tid < (uint32_t)kBlock;    // the first four waves hold the workgroup's (up to) 256 units
 
     // ---- this thread's unit: record range and header (the loads overlap the table staging below)
@@ -142,76 +132,19 @@ __global__ __launch_bounds__(kCoopBlock, SVT_COOP_WAVES_PER_SIMD) void svt_coop_
         cnt = (uint32_t)(hi - lo);
         U = a.units[wg_base + tid];
     }
-    // ---- tables (the layout of svt_stream_kernel: kSPm ...)
-    for (uint32_t i = tid; i < 256; i += kCoopBlock) {
-        const double p = a.pm[i];
-        reinterpret_cast<double*>(smem + kSPm)[i] = p;
-        reinterpret_cast<double*>(smem + kSPmHalf)[i] = p * 0.5;
-    }
-    if (tid < 32) {
-        const PairWeights pw = a.wtab[tid];
-        reinterpret_cast<double*>(smem + kSWtab)[tid] = pw.w_alt;
-        reinterpret_cast<double*>(smem + kSWtab + kSWref)[tid] = pw.w_ref;
-    }
-    {
-        int16_t* s_thr = reinterpret_cast<int16_t*>(smem + kSBins);
-        uint16_t* s_hst = reinterpret_cast<uint16_t*>(smem + kSBins) + a.total_bins;
-        for (uint32_t i = tid; i < a.total_bins; i += kCoopBlock) {
-            const Bin bn = a.bins[i];
-            s_thr[i] = (int16_t)bn.thr;
-            s_hst[i] = (uint16_t)bn.hist;
-        }
-    }
-    if (a.l10_where == kL10Shared) {
-        double* s_l10 = reinterpret_cast<double*>(smem + a.lds_l10);
-        for (uint32_t i = tid; i < a.n_l10; i += kCoopBlock) s_l10[i] = a.l10[i];
-    }
+    // ---- tables (the high words at kSWhi are not used here)
+    stage_tables<MODE, kCoopBlock, false>(smem, a, g.wd, tid);
     for (uint32_t i = tid; i < 5u * kBlock; i += kCoopBlock) s_tally[i] = 0.0;
     if (tid < 8) s_tmax[tid] = 0u;     // tmax[4], cont[4]
 
-    // ---- counting sort of the units by block count, longest first (wg_sort_into_tiles, with the other waves only meeting the
-    // barriers).  What moves is the tile entry: everything a record's look-ups need to know of its unit (record_single's StreamCtx).
-    {
-        uint32_t* s_hist = reinterpret_cast<uint32_t*>(stages);
-        uint32_t* s_start = s_hist + (kMaxSortKey + 1);
-        uint32_t* s_wsum = s_start + (kMaxSortKey + 1);
-        const uint32_t nblk = cnt ? ((beg & 7u) + cnt + 7u) >> 3 : 0u;
-        // (a unit without records still sorts in front of the padding threads: the workgroup's units fill its first tiles)
-        const uint32_t key = sorter && tid < n_here ? min(nblk + 1u, kMaxSortKey) : 0u;
-        if (sorter) s_hist[tid] = 0u;
-        __syncthreads();
-        uint32_t rank = 0u;
-        if (sorter) rank = atomicAdd(&s_hist[key], 1u);
-        __syncthreads();
-        uint32_t h = 0u, incl = 0u;
-        if (sorter) {
-            h = s_hist[kMaxSortKey - tid];
-            incl = wave_inclusive_scan(h, lane);
-            if (lane == kWave - 1) s_wsum[wave] = incl;
-        }
-        __syncthreads();
-        if (sorter) {
-            uint32_t before = 0;
-#pragma unroll
-            for (int w = 0; w < kWavesPerBlock; ++w) before += (uint32_t)w < wave ? s_wsum[w] : 0u;
-            const uint32_t pos = before + incl - h;      // first sorted position of bucket kMaxSortKey - tid
-            s_start[kMaxSortKey - tid] = pos;
-        }
-        __syncthreads();
-        if (sorter) {
-            const bool is_del = U.svtype == SVT_SVTYPE_DEL;
-            const bool small_del = is_del && ((double)U.pos_delta < a.lib0.sd2);   // classic.py:339,383
-            const uint32_t flags = (small_del ? 0u : kCoopFmask) | (is_del ? kCoopDel16 : 0u) | ((uint32_t)U.svtype << kCoopSvtypeShift) |
-                                   ((uint32_t)U.flags << kCoopUflagsShift);
-            const uint32_t sub2 = is_del ? (uint32_t)U.var_length + (uint32_t)a.lib0.key_min : 0x80000000u;
-            const uint32_t pos = s_start[key] + rank;
-            s_tile[pos] = make_uint4(beg, cnt, sub2, flags);
-            s_unit[pos] = tid < n_here ? wg_base + tid : kPadUnit;
-            // the tile's longest unit (sorted: its first -- unless it sits in the last bucket, which keeps arrival order)
-            atomicMax(&s_tmax[pos >> 6], nblk);
-        }
-        __syncthreads();
-    }
+    // ---- counting sort of the units by block count, longest first; what moves is the unit's tile entry
+    const uint32_t nblk = cnt ? ((beg & 7u) + cnt + 7u) >> 3 : 0u;
+    wg_sort_units(stages, nblk, sorter && tid < n_here, sorter, tid, lane, wave, [&](const uint32_t pos) {
+        s_tile[pos] = make_tile_entry<MODE>(U, beg, cnt, a);
+        s_unit[pos] = tid < n_here ? wg_base + tid : kPadUnit;
+        // the tile's longest unit (sorted: its first -- unless it sits in the last bucket, which keeps arrival order)
+        atomicMax(&s_tmax[pos >> 6], nblk);
+    });
     uint32_t tmax[kCoopTiles];
     uint32_t steps = 0u;
 #pragma unroll
@@ -221,7 +154,6 @@ __global__ __launch_bounds__(kCoopBlock, SVT_COOP_WAVES_PER_SIMD) void svt_coop_
     }
     // (sorted longest first: an empty tile is followed by empty tiles only)
     const uint32_t rounds = (steps + 1u + kCoopDepth - 1u) / kCoopDepth;   // the consumers trail the producers by one step
-    const uint64_t trace_t1 = SVT_COOP_TRACE ? clock64() : 0;
     RecordCheck<MODE> check;
     if (wave >= (uint32_t)kCoopConsumers) {
         // =================================================== producers ===================================================
@@ -273,8 +205,7 @@ __global__ __launch_bounds__(kCoopBlock, SVT_COOP_WAVES_PER_SIMD) void svt_coop_
                 const bool valid = l_base[j] - l_first[j] < l_nrec[j];   // first <= record < first + records, unsigned
                 const uint32_t at = min(valid ? l_base[j] : l_first[j], last_rec);
                 const u32x4* src = reinterpret_cast<const u32x4*>(rec_bytes + ((uint64_t)at << 4));
-                if (SVT_COOP_PROBE & 4) dst[j] = u32x4{at, at, at, 0u};
-                else dst[j] = SVT_COOP_NT ? __builtin_nontemporal_load(src) : *src;
+                dst[j] = SVT_COOP_NT ? __builtin_nontemporal_load(src) : *src;
                 l_base[j] += kBlockRecords;
             }
             if (left_l && --left_l == 0u) {
@@ -305,15 +236,10 @@ __global__ __launch_bounds__(kCoopBlock, SVT_COOP_WAVES_PER_SIMD) void svt_coop_
                     w.w = mine ? w.w : 0u;
                     check.see(w);
                     CoopLook L;
-                    if (SVT_COOP_PROBE & 8) {
-                        L.pm_a = L.pm_b = L.rs_a = L.rs_b = L.s0 = L.s1 = L.c0 = L.c1 = __hiloint2double((int)w.x, (int)w.y);
-                        L.thr1 = (int32_t)w.z;
-                        L.h2 = w.w;
-                    } else
                     coop_look(w, kmin, nb, w_sub2[j], hist_at, L);
                     const bool p_conc = (int32_t)L.h2 <= L.thr1;
-                    const uint32_t wt0 = kSWtab + (w_flags[j] & kCoopDel16) * 8u;
-                    const uint32_t wa = (p_conc ? wt0 + 8u * 8u : wt0) | ((w.w & w_flags[j] & kCoopFmask) << 3);   // &w_alt[f3 | p_conc << 3 | del16]
+                    const uint32_t wt0 = kSWtab + (w_flags[j] & kTileDel16) * 8u;
+                    const uint32_t wa = (p_conc ? wt0 + 8u * 8u : wt0) | ((w.w & w_flags[j] & kTileFmask) << 3);   // &w_alt[f3 | p_conc << 3 | del16]
                     const double w_alt = lds_f64(wa), w_ref = lds_f64(wa + kSWref);
                     const double pp = L.pm_a * L.pm_b;
                     double rs_a = L.rs_a, p_seq = L.s0 + L.s1;
@@ -324,10 +250,6 @@ __global__ __launch_bounds__(kCoopBlock, SVT_COOP_WAVES_PER_SIMD) void svt_coop_
                         p_seq = cont ? -p_seq : p_seq;
                     }
                     const uint32_t at = st + st_at[j];
-                    if (SVT_COOP_PROBE & 1) {
-                        if (rs_a + L.rs_b + L.s0 + L.s1 + L.c0 + L.c1 + pp * w_alt + pp * w_ref == 1.2345e-300) *reinterpret_cast<lds_u32x4*>((size_t)at) = pack2d_v(rs_a, L.rs_b);
-                        continue;
-                    }
                     *reinterpret_cast<lds_u32x4*>((size_t)at) = pack2d_v(rs_a, L.rs_b);
                     *reinterpret_cast<lds_u32x4*>((size_t)(at + 1024u)) = pack2d_v(p_seq, L.c0 + L.c1);
                     *reinterpret_cast<lds_u32x4*>((size_t)(at + 2048u)) = pack2d_v(pp * w_alt, pp * w_ref);
@@ -358,8 +280,7 @@ __global__ __launch_bounds__(kCoopBlock, SVT_COOP_WAVES_PER_SIMD) void svt_coop_
 #pragma unroll
                 for (int s = 0; s < 8; ++s) v[s] = *reinterpret_cast<lds_cu32x4_*>((size_t)(rd[s] + off));
                 const bool has_cont = SSO && wave != 2u && s_cont[(g - 1u) & 3u] != 0u;
-                if (SVT_COOP_PROBE & 2) {
-                } else if (wave == 2u) {   // classic.py:339-405 / singlesample.py:278-353: the spans know no fragments
+                if (wave == 2u) {   // classic.py:339-405 / singlesample.py:278-353: the spans know no fragments
 #pragma unroll
                     for (int s = 0; s < 8; ++s) {
                         acc0 += lo_f64(v[s]);
@@ -425,46 +346,15 @@ __global__ __launch_bounds__(kCoopBlock, SVT_COOP_WAVES_PER_SIMD) void svt_coop_
             __syncthreads();
         }
     }
-    const uint64_t trace_t2 = SVT_COOP_TRACE ? clock64() : 0;
     __syncthreads();   // every tile's tallies are in LDS; the stages are free for the result rings
 
     // ---- epilogues: wave w takes tile w (classic.py:425-513 in unit_epilogue)
     const uint32_t n_tiles = (a.units_per_wg + kWave - 1u) / kWave;   // tiles this workgroup owns result slots for (uniform over the launch)
-    if (wave < n_tiles && wave < kCoopTiles) {
-        const uint32_t pos = wave * kWave + lane;
-        Acc acc = {s_tally[pos], s_tally[kBlock + pos], s_tally[2 * kBlock + pos], s_tally[3 * kBlock + pos], s_tally[4 * kBlock + pos], 0.0, 0.0, 0.0};
-        if (SVT_COOP_PROBE) {   // timing only: the sums are garbage and must not index the log10 table -- mask them with what the compiler cannot fold
-            const uint64_t keep = a.unit_end < a.unit_begin ? ~0ull : 0ull;
-            acc.ref_seq = __longlong_as_double((long long)((uint64_t)__double_as_longlong(acc.ref_seq) & keep));
-            acc.alt_seq = __longlong_as_double((long long)((uint64_t)__double_as_longlong(acc.alt_seq) & keep));
-            acc.alt_clip = __longlong_as_double((long long)((uint64_t)__double_as_longlong(acc.alt_clip) & keep));
-            acc.ref_span = __longlong_as_double((long long)((uint64_t)__double_as_longlong(acc.ref_span) & keep));
-            acc.alt_span = __longlong_as_double((long long)((uint64_t)__double_as_longlong(acc.alt_span) & keep));
-        }
-        const uint32_t unit = s_unit[pos], flags = s_tile[pos].w;
-        const double* lds_l10 = reinterpret_cast<const double*>(smem + a.lds_l10);
-        uint4 piece[8];
-        unit_epilogue(acc, (flags >> kCoopSvtypeShift) & 0xffu, flags >> kCoopUflagsShift, a.c, lds_l10, a.l10, a.l10_where == kL10Shared ? a.l10_lds_entries : 0u, piece);
-        uint32_t unit_out = unit;
-        if (a.out_samples > 1u && unit != kPadUnit) {
-            const uint32_t sample = unit / a.out_sites;
-            unit_out = (unit - sample * a.out_sites) * a.out_samples + sample;
-        }
-        uint32_t tile_slot = 0xFFFFFFFFu;
-        if (a.result96) {
-            piece[5] = make_uint4(piece[5].x, piece[7].y, unit_out, 0u);
-            tile_slot = a.slot_begin + (blockIdx.x * n_tiles + wave) * kWave;
-        }
-        store_result_records_through_ring(stages + wave * kRingBytes, piece, unit_out, lane, reinterpret_cast<unsigned char*>(a.out), a.result96 ? 6u : 8u, tile_slot);
-    }
+    if (wave < n_tiles && wave < kCoopTiles)
+        tally_epilogue(a, smem, s_tally, s_tile, s_unit, wave * kWave + lane, stages + wave * kRingBytes, lane,
+                       a.slot_begin + (blockIdx.x * n_tiles + wave) * kWave);
     const uint32_t bad = check.bits(a.n_libs);
     if (bad) atomicOr(a.err, bad);
-    if (SVT_COOP_TRACE && (blockIdx.x % 61u) == 0 && lane == 0 && (wave == 0 || wave == 5)) {
-        const uint64_t trace_t3 = clock64();
-        printf("coop wg %u wave %u (realtime %llu): steps %u (tiles %u %u %u %u) prologue %llu loop %llu (%.0f per step) epilogue %llu cycles\n", blockIdx.x, wave, (unsigned long long)wall_clock64(), steps, tmax[0], tmax[1], tmax[2], tmax[3],
-               (unsigned long long)(trace_t1 - trace_t0), (unsigned long long)(trace_t2 - trace_t1), (double)(trace_t2 - trace_t1) / (double)max(steps, 1u),
-               (unsigned long long)(trace_t3 - trace_t2));
-    }
 }
 
 }  // namespace svt

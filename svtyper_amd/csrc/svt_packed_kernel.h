@@ -188,7 +188,7 @@ __global__ __launch_bounds__(kBlock, 3) void svt_packed_kernel(const PackedArgs 
         // svt_result96: {GQ, GT, unit} behind QR / QA; the tile's records leave in the tile's own order (svt_stream_kernel.h)
         uint32_t tile_slot = 0xFFFFFFFFu;
         if (a.result96) {
-            piece[5] = make_uint4(piece[5].x, piece[7].y, unit, 0u);
+            result96_tag(piece, unit);
             tile_slot = a.slot_begin + blockIdx.x * (uint32_t)(kBlock * R) + ((uint32_t)r * kWavesPerBlock + ((r & 1) ? (uint32_t)kWavesPerBlock - 1u - wave : wave)) * kWave;
         }
         store_result_records_through_ring(ring, piece, unit, lane, reinterpret_cast<unsigned char*>(a.out), a.result96 ? 6u : 8u, tile_slot);

@@ -198,6 +198,42 @@ __device__ __forceinline__ void wg_sort_into_tiles(unsigned char* rings, const u
     __syncthreads();   // the rings are free from here on
 }
 
+// The same sort for the kernels whose workgroup holds (up to) 256 units in more than four waves (svt_split_kernel.h,
+// svt_coop_kernel.h: launches of less than one round).  `sorter`: the thread is one of the first kBlock, which hold a unit and
+// own a bucket each; the other waves only meet the barriers.  The key is the block count + 1: a unit without records still
+// sorts in front of the padding threads (`has_unit` false: key 0), so the workgroup's units fill its first positions.
+// place(pos) writes what the kernel keeps per sorted position; the barrier behind it frees the scratch.
+template <class PLACE>
+__device__ __forceinline__ void wg_sort_units(unsigned char* scratch, const uint32_t nblk, const bool has_unit, const bool sorter,
+                                              const uint32_t tid, const uint32_t lane, const uint32_t wave, PLACE&& place)
+{
+    uint32_t* s_hist = reinterpret_cast<uint32_t*>(scratch);
+    uint32_t* s_start = s_hist + (kMaxSortKey + 1);
+    uint32_t* s_wsum = s_start + (kMaxSortKey + 1);
+    const uint32_t key = has_unit ? min(nblk + 1u, kMaxSortKey) : 0u;
+    if (sorter) s_hist[tid] = 0u;
+    __syncthreads();
+    uint32_t rank = 0u;
+    if (sorter) rank = atomicAdd(&s_hist[key], 1u);
+    __syncthreads();
+    uint32_t h = 0u, incl = 0u;
+    if (sorter) {
+        h = s_hist[kMaxSortKey - tid];
+        incl = wave_inclusive_scan(h, lane);
+        if (lane == kWave - 1) s_wsum[wave] = incl;
+    }
+    __syncthreads();
+    if (sorter) {
+        uint32_t before = 0;
+#pragma unroll
+        for (int w = 0; w < kWavesPerBlock; ++w) before += (uint32_t)w < wave ? s_wsum[w] : 0u;
+        s_start[kMaxSortKey - tid] = before + incl - h;
+    }
+    __syncthreads();
+    if (sorter) place(s_start[key] + rank);
+    __syncthreads();
+}
+
 // the block count of the longest and of the shortest unit of a sorted tile (wave-uniform)
 __device__ __forceinline__ void tile_block_range(const uint32_t nblk, uint32_t& max_blk, uint32_t& min_blk)
 {
@@ -223,10 +259,6 @@ __device__ __forceinline__ void tile_block_range(const uint32_t nblk, uint32_t& 
 // wait state -- and one build of the two-tile window kernel, whose register allocation put a spill reload right
 // behind such a store, wrote a foreign dword into four pieces of a few result records.
 // SVT_STORE_POLICY (measurements only): "" / " sc1" / " sc0 sc1" select an assembly store with that policy (+ s_nop).
-#ifndef SVT_STORE_DIRECT
-#define SVT_STORE_DIRECT 0    // 1: every lane stores the eight pieces of its own record (no LDS staging)
-#endif
-
 __device__ __forceinline__ void store_piece(uint4* dst, const uint4 v)
 {
     const u32x4 vv = {v.x, v.y, v.z, v.w};
@@ -235,30 +267,6 @@ __device__ __forceinline__ void store_piece(uint4* dst, const uint4 v)
 #else
     __builtin_nontemporal_store(vv, reinterpret_cast<u32x4*>(dst));
 #endif
-}
-
-// result records of a tile: lane-major into the ring, unit-major out of it, one full 128-byte line per eight lanes
-__device__ __forceinline__ void store_results_through_ring(unsigned char* ring, const uint4 (&piece)[8], const uint32_t unit,
-                                                           const uint32_t lane, svt_result* __restrict__ out)
-{
-#if SVT_STORE_DIRECT
-    if (unit != kPadUnit) {
-#pragma unroll
-        for (int p = 0; p < 8; ++p) store_piece(reinterpret_cast<uint4*>(out + unit) + p, piece[p]);
-    }
-    return;
-#endif
-    const uint32_t o = lane >> 3, rr = lane & 7u, sw = (lane >> 1) & 7u;
-    const uint32_t col_even = (rr ^ (o >> 1)) << 4, col_odd = col_even ^ 64u;
-    uint4* st = reinterpret_cast<uint4*>(ring + lane * 128u);
-#pragma unroll
-    for (int p = 0; p < 8; ++p) st[(uint32_t)p ^ sw] = piece[p];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        const uint32_t dst_unit = (uint32_t)__shfl((int)unit, 8 * i + (int)o, kWave);
-        const uint4 v = *reinterpret_cast<const uint4*>(ring + (uint32_t)i * 1024u + o * 128u + ((i & 1) ? col_odd : col_even));
-        if (dst_unit != kPadUnit) store_piece(reinterpret_cast<uint4*>(out + dst_unit) + rr, v);
-    }
 }
 
 #ifndef SVT_STORE_UNROLL
@@ -301,6 +309,15 @@ __device__ __forceinline__ void store_result_records_through_ring(unsigned char*
         }
         if (dst_unit != kPadUnit) store_piece(reinterpret_cast<uint4*>(out + (uint64_t)dst_unit * stride) + p, v);
     }
+}
+
+
+// svt_result96: GL, SQ, tallies, QR, QA | GQ, GT, unit -- pieces 0-4 as they are, piece 5 = {GQ, GT, unit, 0}; the tile's 64
+// records then go to the tile's own 6 KB of the result buffer, in the tile's (length-sorted) order: the caller hands the tile's
+// first slot to store_result_records_through_ring as `sorted_base`.  (A padding lane: unit_out == kPadUnit == SVT_NO_UNIT.)
+__device__ __forceinline__ void result96_tag(uint4 (&piece)[8], const uint32_t unit_out)
+{
+    piece[5] = make_uint4(piece[5].x, piece[7].y, unit_out, 0u);
 }
 
 }  // namespace svt

@@ -24,14 +24,10 @@
 
 #include "svt_stream_kernel.h"
 
-#ifndef SVT_SPLIT_TRACE
-#define SVT_SPLIT_TRACE 0
-#endif
-
 namespace svt {
 
 // the split region of the workgroup's LDS, byte offsets from StreamArgs::lds_rings (128-byte aligned)
-constexpr uint32_t kSplitTileAt = 0;                                  // uint4[256]  {first record, records, sub2, flags} by sorted position
+constexpr uint32_t kSplitTileAt = 0;                                  // uint4[256]  tile entries by sorted position (svt_wg_parts.h)
 constexpr uint32_t kSplitUnitAt = kSplitTileAt + kBlock * 16u;        // uint32[256] unit index (kPadUnit: none)
 constexpr uint32_t kSplitGateAt = kSplitUnitAt + kBlock * 4u;         // uint32[256] library windows: bit l = the small-deletion gate of the window's l-th library is closed
 constexpr uint32_t kSplitTallyAt = kSplitGateAt + kBlock * 4u;        // double[5][256] tallies by sorted position
@@ -39,7 +35,6 @@ constexpr uint32_t kSplitRingAt = kSplitTallyAt + 5u * kBlock * 8u;   // per-wav
                                                                       // before the steps, the four result rings after them
 constexpr uint32_t kSplitRegionBytes = kSplitRingAt + (uint32_t)(kBlock / kWave) * kRingBytes;
 static_assert(kSplitRingAt % 128u == 0u, "rings are line-aligned");
-constexpr uint32_t kSplitFmask = 7u, kSplitDel16 = 16u, kSplitSvtypeShift = 8u, kSplitUflagsShift = 16u;
 
 typedef __attribute__((address_space(3))) const u32x4 lds_cu32x4_s;
 
@@ -106,79 +101,29 @@ __global__ __launch_bounds__(kBlock * K, 4) void svt_split_kernel(const StreamAr
     double* s_tally = reinterpret_cast<double*>(region + kSplitTallyAt);
     unsigned char* rings = region + kSplitRingAt;
 
-    // this workgroup's units: 256 consecutive ones, or (library windows) a chunk of at most 256 units of the permutation that groups
-    // the units by the libraries of their sample
-    const uint32_t wg_index = MODE == kMultiLds ? blockIdx.x + a.chunk_begin : blockIdx.x;
-    uint32_t wg_base = a.unit_begin + blockIdx.x * a.units_per_wg, n_here;
-    WgDesc wd{};
-    if (MODE == kMultiLds) {
-        const uint2 ch = a.chunks[wg_index];
-        wg_base = ch.x;
-        n_here = min(ch.y, (uint32_t)kBlock);
-        wd = a.windows[wg_index];
-    } else {
-        n_here = min(a.units_per_wg, a.unit_end - wg_base);
-    }
+    // this workgroup's units: 256 consecutive ones, or (library windows) a chunk of at most 256 units
+    const WgUnits g = wg_units<MODE>(a, (uint32_t)kBlock);
+    const uint32_t wg_base = g.wg_base, n_here = g.n_here, wg_index = g.wg_index;
+    const WgDesc wd = g.wd;
     const bool sorter = tid < (uint32_t)kBlock;    // the first four waves hold the workgroup's (up to) 256 units
 
     // ---- this thread's unit: record range and header (the loads overlap the table staging below)
     uint32_t beg = 0u, cnt = 0u, my_unit = kPadUnit;
     svt_unit U{};
     if (sorter && tid < n_here) {
-        my_unit = MODE == kMultiLds && a.perm ? a.perm[wg_base + tid] : wg_base + tid;
+        my_unit = wg_unit_at<MODE>(a, wg_base, tid);
         const uint64_t lo = a.rec_offset[my_unit], hi = a.rec_offset[my_unit + 1];
         beg = (uint32_t)lo;
         cnt = (uint32_t)(hi - lo);
         U = a.units[my_unit];
     }
-    // ---- tables (the layout of svt_stream_kernel: kSPm ...)
-    for (uint32_t i = tid; i < 256; i += kThreads) {
-        const double p = a.pm[i];
-        reinterpret_cast<double*>(smem + kSPm)[i] = p;
-        reinterpret_cast<double*>(smem + kSPmHalf)[i] = p * 0.5;
-    }
-    if (tid < 32) {
-        const PairWeights pw = a.wtab[tid];
-        reinterpret_cast<double*>(smem + kSWtab)[tid] = pw.w_alt;
-        reinterpret_cast<double*>(smem + kSWtab + kSWref)[tid] = pw.w_ref;
-    }
-    if (MODE == kSingleLds) {
-        int16_t* s_thr = reinterpret_cast<int16_t*>(smem + kSBins);
-        uint16_t* s_hst = reinterpret_cast<uint16_t*>(smem + kSBins) + a.total_bins;
-        for (uint32_t i = tid; i < a.total_bins; i += kThreads) {
-            const Bin bn = a.bins[i];
-            s_thr[i] = (int16_t)bn.thr;
-            s_hst[i] = (uint16_t)bn.hist;
-        }
-    } else {
-        // the window's bins as thr[bin_cnt], hist[bin_cnt] and one WinLib per library of the window (svt_stream_kernel.h)
-        int16_t* s_thr = reinterpret_cast<int16_t*>(smem + kSBins);
-        uint16_t* s_hst = reinterpret_cast<uint16_t*>(smem + kSBins) + wd.bin_cnt;
-        for (uint32_t i = tid; i < wd.bin_cnt; i += kThreads) {
-            const Bin bn = a.bins[wd.bin_lo + i];
-            s_thr[i] = (int16_t)bn.thr;
-            s_hst[i] = (uint16_t)bn.hist;
-        }
-        if (tid < wd.lib_cnt) {
-            const LibDesc L = a.libs[wd.lib_lo + tid];
-            WinLib wl;
-            wl.kmin = (uint32_t)L.key_min;
-            wl.nb = L.n_bins;
-            wl.thr_at = kSBins + (L.tab_off - wd.bin_lo) * 2u;
-            wl.hist_at = kSBins + (wd.bin_cnt + L.tab_off - wd.bin_lo) * 2u;
-            wl.sd2 = L.sd2;
-            wl.pad = 0.0;
-            reinterpret_cast<WinLib*>(smem + a.lds_winlibs)[tid] = wl;
-        }
-    }
-    if (a.l10_where == kL10Shared) {
-        double* s_l10 = reinterpret_cast<double*>(smem + a.lds_l10);
-        for (uint32_t i = tid; i < a.n_l10; i += kThreads) s_l10[i] = a.l10[i];
-    }
+    // ---- tables (the high words at kSWhi are not used here)
+    stage_tables<MODE, kThreads, false>(smem, a, wd, tid);
     for (uint32_t i = tid; i < 5u * kBlock; i += kThreads) s_tally[i] = 0.0;
 
-    // ---- counting sort of the units by block count, longest first (wg_sort_into_tiles; the other waves only meet the barriers).
-    // What moves is the tile entry: everything a record's look-ups need to know of its unit (record_single's StreamCtx).
+    // ---- counting sort of the units by block count, longest first: wg_sort_units (svt_ring_engine.h) with make_tile_entry
+    // (svt_wg_parts.h), written out -- as calls they change this kernel's register allocation, and so does tally_epilogue
+    // below (profiles/wg_parts_kernel_resources.txt).  The other waves only meet the barriers.
     {
         uint32_t* s_hist = reinterpret_cast<uint32_t*>(rings);
         uint32_t* s_start = s_hist + (kMaxSortKey + 1);
@@ -208,8 +153,8 @@ __global__ __launch_bounds__(kBlock * K, 4) void svt_split_kernel(const StreamAr
         if (sorter) {
             const bool is_del = U.svtype == SVT_SVTYPE_DEL;
             const bool small_del = MODE == kSingleLds && is_del && ((double)U.pos_delta < a.lib0.sd2);   // classic.py:339,383
-            const uint32_t flags = (small_del ? 0u : kSplitFmask) | (is_del ? kSplitDel16 : 0u) | ((uint32_t)U.svtype << kSplitSvtypeShift) |
-                                   ((uint32_t)U.flags << kSplitUflagsShift);
+            const uint32_t flags = (small_del ? 0u : kTileFmask) | (is_del ? kTileDel16 : 0u) | ((uint32_t)U.svtype << kTileSvtypeShift) |
+                                   ((uint32_t)U.flags << kTileUflagsShift);
             // one library: DEL ? var_length + key_min : never in range; windows: DEL ? var_length : never -- the library's key_min is added per record
             const uint32_t sub2 = is_del ? (uint32_t)U.var_length + (MODE == kSingleLds ? (uint32_t)a.lib0.key_min : 0u) : 0x80000000u;
             const uint32_t pos = s_start[key] + rank;
@@ -241,16 +186,16 @@ __global__ __launch_bounds__(kBlock * K, 4) void svt_split_kernel(const StreamAr
     for (int d = 1; d < kWave; d <<= 1) min_blk = min(min_blk, (uint32_t)__shfl_xor((int)min_blk, d, kWave));
     min_blk = (uint32_t)__builtin_amdgcn_readfirstlane((int)min_blk);
     StreamCtx sc;
-    sc.fmask = me.w & kSplitFmask;
+    sc.fmask = me.w & kTileFmask;
     sc.kmin = (uint32_t)a.lib0.key_min;
     sc.nb = a.lib0.n_bins;
     sc.sub2 = me.z;
     sc.hist_at = kSBins + a.total_bins * 2u;
-    sc.wt0 = kSWtab + (me.w & kSplitDel16) * 8u;
+    sc.wt0 = kSWtab + (me.w & kTileDel16) * 8u;
     sc.wt1 = sc.wt0 + 8u * 8u;
     sc.wh0 = 0u;
     const uint32_t gated = MODE == kMultiLds ? s_gate[pos] : 0u;
-    const bool is_del = (me.w & kSplitDel16) != 0u;
+    const bool is_del = (me.w & kTileDel16) != 0u;
     const uint32_t lib_last = wd.lib_cnt - 1u, winlibs_at = a.lds_winlibs;
     const uint32_t neutral_w = MODE == kMultiLds ? wd.lib_lo << SVT_REC_LIB_SHIFT : 0u;
     const uint32_t lib_key = MODE == kMultiLds && wd.lib_cnt == 1u ? wd.lib_lo << SVT_REC_LIB_SHIFT : 0u;
@@ -431,7 +376,7 @@ __global__ __launch_bounds__(kBlock * K, 4) void svt_split_kernel(const StreamAr
         const uint32_t unit = s_unit[p], flags = s_tile[p].w;
         const double* lds_l10 = reinterpret_cast<const double*>(smem + a.lds_l10);
         uint4 piece[8];
-        unit_epilogue(acc, (flags >> kSplitSvtypeShift) & 0xffu, flags >> kSplitUflagsShift, a.c, lds_l10, a.l10, a.l10_where == kL10Shared ? a.l10_lds_entries : 0u, piece);
+        unit_epilogue(acc, (flags >> kTileSvtypeShift) & 0xffu, flags >> kTileUflagsShift, a.c, lds_l10, a.l10, a.l10_where == kL10Shared ? a.l10_lds_entries : 0u, piece);
         uint32_t unit_out = unit;
         if (a.out_samples > 1u && unit != kPadUnit) {
             const uint32_t sample = unit / a.out_sites;

@@ -48,72 +48,9 @@
 
 #include <type_traits>
 
-#include "svt_ring_engine.h"
+#include "svt_wg_parts.h"
 
 namespace svt {
-
-// LDS layout of the streaming kernel, absolute byte addresses (the kernel has no static LDS, so the dynamic
-// segment starts at 0 -- checked at run time): the one-library record consumer turns every field of a record
-// into an LDS address with one instruction and the table base as the ds_read's immediate offset.
-constexpr uint32_t kSPm = 0;                          // double[256]  prob_mapq(q)                      (utils.py:74-75)
-constexpr uint32_t kSPmHalf = kSPm + 256 * 8;         // double[256]  prob_mapq(q) / 2 (exact: a power-of-two scaling)
-constexpr uint32_t kSWtab = kSPmHalf + 256 * 8;       // kSingleLds: double w_alt[32], w_ref[32] (columns); kGeneral: PairWeights[32]
-constexpr uint32_t kSWref = 32 * 8;                   // byte distance w_alt[i] -> w_ref[i]
-constexpr uint32_t kSWhi = kSWtab + 2 * 32 * 8;       // kSingleLds / kMultiLds: uint32 high words of w_alt[32], w_ref[32] (their low words are 0)
-constexpr uint32_t kSWhiRef = 32 * 4;                 // byte distance w_alt_hi[i] -> w_ref_hi[i]
-constexpr uint32_t kSBins = kSWhi + 2 * 32 * 4;       // kSingleLds: int16 thr[total_bins], uint16 hist[total_bins] (ranks, svt_host_tables.h); kGeneral: LibDesc[n_libs]
-
-struct StreamArgs {
-    const uint4* records;        // canonical records; the allocation ends on a 128-byte block boundary, tail zeroed
-    const uint64_t* rec_offset;  // n_units + 1
-    const svt_unit* units;
-    const double* pm;            // 256
-    const double* l10;           // n_l10, allocation padded to whole KiB
-    const LibDesc* libs;
-    const Bin* bins;
-    const PairWeights* wtab;     // 32
-    uint32_t n_l10;
-    uint32_t n_libs;
-    uint32_t total_bins;
-    uint32_t last_blk;           // index of the last 128-byte block of the records
-    uint32_t lds_bins;           // bins staged in LDS (kSingleLds: the whole table)
-    uint32_t lds_libs;           // library descriptors staged in LDS
-    uint32_t lds_rings;          // byte offset of wave 0's ring (128-byte aligned)
-    uint32_t l10_where;          // kL10Shared / kL10Ring / kL10Global
-    uint32_t lds_l10;            // kL10Shared: byte offset of the workgroup's copy of the log10 table
-    uint32_t l10_lds_entries;    // entries of the table the epilogue finds in LDS (kL10Shared: all; kL10Ring: what one ring stage holds --
-                                 // a unit whose read count reaches beyond takes the table through L2; kL10Global: 0)
-    uint64_t n_units;
-    svt_result* out;
-    uint32_t* err;
-    // kMultiLds: units grouped by the library window of their sample (svt_unit.libs)
-    const uint32_t* perm;        // unit indices, grouped by window, original order inside a group; nullptr = the identity
-    const uint2* chunks;         // one per workgroup: {first position in perm, units (<= 256 * R)} -- never crosses a group
-    const WgDesc* windows;       // one per workgroup: the libraries / bins it stages
-    uint32_t lds_winlibs;        // byte offset of the WinLib descriptors (after the bins)
-    uint32_t unit_begin;         // this launch covers units [unit_begin, unit_end) (the pipelined one-shot launches
-    uint32_t unit_end;           // one range per uploaded piece; a pass over a resident batch: [0, n_units))
-    uint32_t units_per_wg;       // (not the window mode) consecutive units of one workgroup, <= 256 * R: the host cuts a launch into
-                                 // EQUAL workgroups that fill whole rounds of the chip's resident workgroups (svtyper_hip.hip: wg_plan)
-    uint32_t chunk_begin;        // (library windows) this launch covers the chunks from this one on
-    uint32_t result96;           // SVT_FLAG_RESULT96: `out` holds 96-byte records (svt_result96) in the workgroups' own order, tagged with their unit
-    uint32_t slot_begin;         // ... the first of them this launch writes (workgroup w of the launch: slot_begin + w * 256 * R)
-    uint32_t out_samples;        // svt_batch_result_order: > 1 = the units are sample-major (unit = sample * out_sites + site) and the
-    uint32_t out_sites;          // result record of a unit goes to index site * out_samples + sample (site-major); 0 = unit order
-    LibDesc lib0;
-    GtConsts c;
-};
-
-// kMultiLds: one library of the workgroup's window, 32 bytes in LDS
-struct WinLib {
-    uint32_t kmin;      // (uint32) key_min
-    uint32_t nb;        // n_bins == index of the library's sentinel bin
-    uint32_t thr_at;    // LDS byte address of this library's thr[0]
-    uint32_t hist_at;   // LDS byte address of this library's hist[0]
-    double sd2;         // 2 * sd: the small-deletion gate (classic.py:339,383)
-    double pad;
-};
-static_assert(sizeof(WinLib) == 32, "WinLib is read as two 16-byte halves");
 
 // The record contract of include/svtyper_hip.h, accumulated over the records of a lane's units at 3-4
 // instructions per record.
@@ -142,17 +79,6 @@ struct RecordCheck {
         return (lone > 0x10u ? kErrStraddleNoPair : 0u) | (bad_lib ? kErrLibIndex : 0u) |
                ((flags_or & ~SVT_REC_FLAG_MASK) ? kErrReservedBits : 0u) | ((int32_t)span_or < 0 ? kErrNegativeSpan : 0u);
     }
-};
-
-// per-lane constants of the unit for the one-library record consumer
-struct StreamCtx {
-    uint32_t fmask;    // straddle-bit mask with the small-DEL gate applied (classic.py:339,383)
-    uint32_t kmin;     // (uint32) key_min
-    uint32_t nb;       // n_bins == index of the sentinel bin
-    uint32_t sub2;     // DEL ? var_length + key_min : 0x80000000 (never in range)
-    uint32_t hist_at;  // LDS address of hist[0]
-    uint32_t wt0, wt1; // LDS address of w_alt[del16] / w_alt[del16 + 8] (p_concordant = 0 / 1)
-    uint32_t wh0;      // LDS address of w_alt_hi[del16]
 };
 
 // One canonical record, one library, tables at fixed LDS addresses: the arithmetic of weight_evidence +
@@ -259,29 +185,16 @@ __global__ __launch_bounds__(kBlock, MODE == kSingleLds ? SVT_STREAM_WAVES : MOD
     static_assert(WK == 0 || (MODE == kMultiLds && !SSO), "window kinds: classic library-window kernels only");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];   // (lds_rings is 128-byte aligned)
     constexpr uint32_t kUnitsPerWg = kBlock * R;
-    double* s_pm = reinterpret_cast<double*>(smem + kSPm);
-    PairWeights* s_wtab = reinterpret_cast<PairWeights*>(smem + kSWtab);   // kGeneral
-    LibDesc* s_lib = reinterpret_cast<LibDesc*>(smem + kSBins);            // kGeneral
     // the one-library consumer addresses the tables by absolute LDS byte offsets
     if (MODE != kGeneral && (uint32_t)(size_t)(__attribute__((address_space(3))) unsigned char*)smem != 0u) __builtin_trap();
     unsigned char* rings = smem + a.lds_rings;
     const uint32_t tid = threadIdx.x, lane = tid % kWave;
     const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(tid / kWave));   // wave-uniform: ring addresses stay in SGPRs
-    // this workgroup's units: 256 * R consecutive ones, or (library windows) a chunk of the permutation that groups
-    // the units by the libraries of their sample
-    uint32_t wg_base = a.unit_begin + blockIdx.x * a.units_per_wg, n_here;
-    WgDesc wd{};
-    const uint32_t wg_index = MODE == kMultiLds ? blockIdx.x + a.chunk_begin : blockIdx.x;   // (the launch's chunk range / workgroup)
-    if (MODE == kMultiLds) {
-        const uint2 ch = a.chunks[wg_index];
-        wg_base = ch.x;
-        n_here = ch.y;
-        wd = a.windows[wg_index];
-    } else {
-        n_here = min(a.units_per_wg, a.unit_end - wg_base);
-    }
-    // (library windows: a.perm == nullptr when the units already come grouped by window)
-    auto unit_at = [&](const uint32_t local) -> uint32_t { return MODE == kMultiLds && a.perm ? a.perm[wg_base + local] : wg_base + local; };
+    // this workgroup's units: 256 * R consecutive ones, or a chunk of the window permutation
+    const WgUnits g = wg_units<MODE>(a);
+    const uint32_t wg_base = g.wg_base, n_here = g.n_here, wg_index = g.wg_index;
+    const WgDesc wd = g.wd;
+    auto unit_at = [&](const uint32_t local) -> uint32_t { return wg_unit_at<MODE>(a, wg_base, local); };
 
     // ---- this thread's R units: record range and sort key (the loads overlap the table staging below)
     uint32_t beg[R], cnt[R];
@@ -298,69 +211,16 @@ __global__ __launch_bounds__(kBlock, MODE == kSingleLds ? SVT_STREAM_WAVES : MOD
         }
     }
 
-    // ---- stage the tables in LDS
-    for (uint32_t i = tid; i < 256; i += kBlock) {
-        const double p = a.pm[i];
-        s_pm[i] = p;
-        reinterpret_cast<double*>(smem + kSPmHalf)[i] = p * 0.5;
-    }
-    if (tid < 32) {
-        const PairWeights pw = a.wtab[tid];
-        if (MODE != kGeneral) {
-            reinterpret_cast<double*>(smem + kSWtab)[tid] = pw.w_alt;
-            reinterpret_cast<double*>(smem + kSWtab + kSWref)[tid] = pw.w_ref;
-            reinterpret_cast<uint32_t*>(smem + kSWhi)[tid] = (uint32_t)__double2hiint(pw.w_alt);
-            reinterpret_cast<uint32_t*>(smem + kSWhi + kSWhiRef)[tid] = (uint32_t)__double2hiint(pw.w_ref);
-        } else {
-            s_wtab[tid] = pw;
-        }
-    }
-    if (MODE == kSingleLds) {
-        // thr[] and hist[] as two 2-byte arrays (svt_host_tables.h replaced the counts by their ranks, which is
-        // all `hist[o - v] <= thr[o]` needs): the random look-ups of a wave spread over every LDS bank
-        int16_t* s_thr = reinterpret_cast<int16_t*>(smem + kSBins);
-        uint16_t* s_hst = reinterpret_cast<uint16_t*>(smem + kSBins) + a.total_bins;
-        for (uint32_t i = tid; i < a.total_bins; i += kBlock) {
-            const Bin bn = a.bins[i];
-            s_thr[i] = (int16_t)bn.thr;
-            s_hst[i] = (uint16_t)bn.hist;
-        }
-    } else if (MODE == kMultiLds) {
-        // the window's bins as thr[bin_cnt], hist[bin_cnt] and one WinLib per library of the window
-        int16_t* s_thr = reinterpret_cast<int16_t*>(smem + kSBins);
-        uint16_t* s_hst = reinterpret_cast<uint16_t*>(smem + kSBins) + wd.bin_cnt;
-        for (uint32_t i = tid; i < wd.bin_cnt; i += kBlock) {
-            const Bin bn = a.bins[wd.bin_lo + i];
-            s_thr[i] = (int16_t)bn.thr;
-            s_hst[i] = (uint16_t)bn.hist;
-        }
-        if (tid < wd.lib_cnt) {
-            const LibDesc L = a.libs[wd.lib_lo + tid];
-            WinLib wl;
-            wl.kmin = (uint32_t)L.key_min;
-            wl.nb = L.n_bins;
-            wl.thr_at = kSBins + (L.tab_off - wd.bin_lo) * 2u;
-            wl.hist_at = kSBins + (wd.bin_cnt + L.tab_off - wd.bin_lo) * 2u;
-            wl.sd2 = L.sd2;
-            wl.pad = 0.0;
-            reinterpret_cast<WinLib*>(smem + a.lds_winlibs)[tid] = wl;
-        }
-    } else {
-        for (uint32_t i = tid; i < a.n_libs * (uint32_t)(sizeof(LibDesc) / 8); i += kBlock)
-            reinterpret_cast<uint64_t*>(s_lib)[i] = reinterpret_cast<const uint64_t*>(a.libs)[i];
-    }
-    if (a.l10_where == kL10Shared) {
-        double* s_l10 = reinterpret_cast<double*>(smem + a.lds_l10);
-        for (uint32_t i = tid; i < a.n_l10; i += kBlock) s_l10[i] = a.l10[i];
-    }
+    // ---- stage the tables in LDS (with the high words at kSWhi)
+    stage_tables<MODE, kBlock, true>(smem, a, wd, tid);
     // ---- counting sort of the workgroup's units by block count, longest first; R tiles per wave
     uint4 info[R];
     wg_sort_into_tiles<R>(rings, beg, cnt, n_here, tid, lane, wave, info);
 
     Tables t;   // kGeneral: tables through ordinary pointers, bins through L2
-    t.pm = s_pm;
-    t.wtab = s_wtab;
-    t.libs = s_lib;
+    t.pm = reinterpret_cast<double*>(smem + kSPm);
+    t.wtab = reinterpret_cast<PairWeights*>(smem + kSWtab);
+    t.libs = reinterpret_cast<LibDesc*>(smem + kSBins);
     t.bins = a.bins;
 
     unsigned char* ring = rings + wave * kStreamRingBytes;
@@ -606,25 +466,19 @@ __global__ __launch_bounds__(kBlock, MODE == kSingleLds ? SVT_STREAM_WAVES : MOD
         unit_epilogue(acc, (uint32_t)U.svtype, (uint32_t)U.flags, a.c, lds_l10, a.l10, a.l10_lds_entries, piece);
 
         // where the record goes: the unit's own index, or (svt_batch_result_order) the site-major index of a sample-major unit
+        // (result_destination of svt_wg_parts.h, written out: as a call it moves the SGPR spills of the two-tile kernels)
         uint32_t unit_out = unit;
         if (a.out_samples > 1u && unit != kPadUnit) {
             const uint32_t sample = unit / a.out_sites;
             unit_out = (unit - sample * a.out_sites) * a.out_samples + sample;
         }
-        {
-#if SVT_STORE_DIRECT
-            store_results_through_ring(ring, piece, unit_out, lane, a.out);
-#else
-            // svt_result96: GL, SQ, tallies, QR, QA | GQ, GT, unit -- pieces 0-4 as they are, piece 5 = {GQ, GT, unit, 0}; the tile's 64
-            // records go to the tile's own 6 KB of the result buffer, in the tile's (length-sorted) order
-            uint32_t tile_slot = 0xFFFFFFFFu;
-            if (a.result96) {
-                piece[5] = make_uint4(piece[5].x, piece[7].y, unit_out, 0u);   // (a padding lane: unit_out == kPadUnit == SVT_NO_UNIT)
-                tile_slot = a.slot_begin + wg_index * kUnitsPerWg + ((uint32_t)r * kWavesPerBlock + ((r & 1) ? (uint32_t)kWavesPerBlock - 1u - wave : wave)) * kWave;
-            }
-            store_result_records_through_ring(ring, piece, unit_out, lane, reinterpret_cast<unsigned char*>(a.out), a.result96 ? 6u : 8u, tile_slot);
-#endif
+        // the tile's records to their units, or (svt_result96) tagged into the tile's own slots
+        uint32_t tile_slot = 0xFFFFFFFFu;
+        if (a.result96) {
+            result96_tag(piece, unit_out);
+            tile_slot = a.slot_begin + wg_index * kUnitsPerWg + ((uint32_t)r * kWavesPerBlock + ((r & 1) ? (uint32_t)kWavesPerBlock - 1u - wave : wave)) * kWave;
         }
+        store_result_records_through_ring(ring, piece, unit_out, lane, reinterpret_cast<unsigned char*>(a.out), a.result96 ? 6u : 8u, tile_slot);
     }
     const uint32_t bad = check.bits(MODE == kMultiLds ? wd.lib_cnt : a.n_libs);
     if (bad) atomicOr(a.err, bad);

@@ -100,6 +100,19 @@ extern template __global__ void svt_split_kernel<true, kMultiLds, 4>(const Strea
 // ------------------------------------------------------------------------------------------
 constexpr unsigned kKnownFlags = SVT_FLAG_SSO_ASSOCIATION | SVT_FLAG_GENERAL_TABLES | SVT_FLAG_RESULT96;
 
+// Where a kernel for launches of less than one round keeps its region in LDS, and the log10 table of its epilogues
+struct SmallRegion {
+    size_t lds_bytes = 0;            // dynamic LDS of a launch (0: the kernel is not for this batch)
+    uint32_t region = 0, l10_where = kL10Global, lds_l10 = 0, l10_entries = 0;
+    void apply(StreamArgs& a) const
+    {
+        a.lds_rings = region;
+        a.l10_where = l10_where;
+        a.lds_l10 = lds_l10;
+        a.l10_lds_entries = l10_entries;
+    }
+};
+
 struct svt_batch {
     int device = 0;
     unsigned flags = 0;
@@ -139,13 +152,10 @@ struct svt_batch {
     int wgs_per_cu = 3;              // workgroups per CU the pass's kernel was budgeted for (registers -> LDS per workgroup)
     uint32_t resident_wgs = 0;       // workgroups of the pass's kernel the device holds at once (registers, LDS, CUs); 0 = unknown
     uint64_t one_tile_round_units = 0;   // units ONE round of the one-tile-per-wave kernel's resident workgroups holds (one library); 0 = unknown
-    // the cooperative kernel for launches of less than one round (svt_coop_kernel.h); 0 bytes = not for this batch
-    size_t coop_lds_bytes = 0;
-    uint32_t coop_region = 0, coop_l10_where = kL10Global, coop_lds_l10 = 0, coop_l10_entries = 0;
-    uint32_t coop_resident = 0;      // workgroups of it the device holds at once
-    // K lanes per unit (svt_split_kernel.h): the same for its region
-    size_t split_lds_bytes = 0;
-    uint32_t split_region = 0, split_l10_where = kL10Global, split_lds_l10 = 0, split_l10_entries = 0;
+    // the kernels for launches of less than one round -- the cooperative one (svt_coop_kernel.h) and K lanes per unit
+    // (svt_split_kernel.h) -- keep a region of their own behind the tables; 0 bytes = not for this batch
+    SmallRegion coop, split;
+    uint32_t coop_resident = 0;      // workgroups of the cooperative kernel the device holds at once
     StreamArgs sargs{};
     // kLayoutPacked: packed evidence as uploaded (svt_packed_kernel.h); d_records holds the slots, d_soff the 3n+1 offsets
     uint32_t* d_soff = nullptr;

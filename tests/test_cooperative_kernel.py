@@ -34,6 +34,24 @@ def _resident(batch, device, flags, order=0):
         return d.results().rec.tobytes(), d.result_slots()
 
 
+def _block_counts(batch):
+    """128-byte blocks a unit's records touch (the kernels' sort key): ((first record & 7) + records + 7) >> 3, 0 without records"""
+    off = np.asarray(batch.rec_offset, dtype=np.uint64)
+    cnt = off[1:] - off[:-1]
+    return np.where(cnt > 0, ((off[:-1] & 7) + cnt + 7) >> 3, 0).astype(np.int64)
+
+
+def _last_bucket_units(fixture_library, seed):
+    """130 units (two tiles and a ragged third) of ~2 036 records: block counts on both sides of the sort's last bucket (key
+    min(blocks + 1, 255): 254 blocks and above share it and keep arrival order), so that a tile's first unit is not its longest"""
+    batch = synth.make_units(130, seed, [fixture_library], svtype_mix=(0.5, 0.2, 0.2, 0.1), mean_frags=2036, sd_frags=12, min_frags=0,
+                             max_frags=2500, frac_empty=0.03)
+    nblk = _block_counts(batch)
+    assert {0, 253, 254, 255} <= set(nblk.tolist()) and (nblk >= 256).any()
+    assert nblk[0] < nblk[:64].max()
+    return batch
+
+
 def test_same_bytes_as_the_streaming_kernel_and_the_oracle(hip_device, fixture_library):
     from oracle import c_oracle
     from svtyper_amd import hip
@@ -45,6 +63,7 @@ def test_same_bytes_as_the_streaming_kernel_and_the_oracle(hip_device, fixture_l
         synth.make_units(20_011, 6, [fixture_library], svtype_mix=(0.7, 0.15, 0.15, 0.0)),  # the configs[2] shape, a last workgroup that is not full
         synth.make_units(1, 7, [fixture_library]),
         synth.make_units(65, 8, [fixture_library], mean_frags=3, sd_frags=2, min_frags=0, max_frags=9),
+        _last_bucket_units(fixture_library, 41),
     ]
     try:
         for batch in batches:
@@ -80,6 +99,7 @@ def test_lanes_per_unit_kernels_same_bytes(hip_device, fixture_library):
                          frac_empty=0.04, frac_skip=0.02),
         synth.make_units(40_011, 16, [fixture_library], svtype_mix=(0.7, 0.15, 0.15, 0.0)),
         synth.make_units(3, 17, [fixture_library]),
+        _last_bucket_units(fixture_library, 41),
     ]
     try:
         for batch in batches:
@@ -111,8 +131,10 @@ def test_lanes_per_unit_kernels_over_library_windows(hip_device, fixture_library
     by_sample, _ = synth.to_sample_major(multi, 8)
     nohint = ev.EvidenceBatch(multi.rec_offset, multi.units.copy(), multi.records, multi.libs, multi.split_weight, multi.disc_weight)
     nohint.units["libs"] = 0
+    long_units = synth.make_multisample(20, 8, seed=43, mean_frags=2036, sd_frags=12, min_frags=0, max_frags=2500)   # the sort's last bucket
+    assert (_block_counts(long_units) >= 255).any()
     try:
-        for batch, order in ((multi, 0), (shuffled, 0), (wide, 0), (by_sample, 8), (nohint, 0)):
+        for batch, order in ((multi, 0), (shuffled, 0), (wide, 0), (by_sample, 8), (nohint, 0), (long_units, 0)):
             for flags in FLAGS:
                 lib.svt_debug_small_kind(1)
                 want, slots_stream = _resident(batch, hip_device, flags, order)

@@ -108,4 +108,4 @@ for _ in range(int(os.environ.get("AB_ROUNDS", "8"))):
 print("%s%s: %d units, %d records, every build over the record / result buffers of %s" % (wl, " (96-byte result records)" if r96 else "", batch.n_units, batch.n_records, builds[0].name))
 for b in builds:
     t = sorted(times[b.name])
-    print("%-34s best %.4f ms  median %.4f  frac(best) %.3f  digest %s" % (b.name, t[0], t[len(t) // 2], alg / t[0] / 1e6 / 8000, b.digest()), flush=True)
+    print("%-34s best %.4f ms  median %.4f  worst %.4f  frac(best) %.3f  digest %s" % (b.name, t[0], t[len(t) // 2], t[-1], alg / t[0] / 1e6 / 8000, b.digest()), flush=True)
