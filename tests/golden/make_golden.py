@@ -12,6 +12,9 @@ Outputs (committed; the reference itself never travels):
   library_from_bam.json.gz  Sample.from_bam() statistics of the fixture BAM
   fake_sites.json.gz     synthetic fake-read sites: libraries, breakpoint, the reads themselves,
                          packed records, reference tallies + result
+  geometry_edges.json.gz the boundary lattice of tests/geomcases.py (fragments on both sides of every threshold
+                         of the geometry predicates), in the format of fake_sites plus the number of records
+                         of each fragment
 
 Floats are stored as float.hex() strings so they round-trip bit-exactly.
 """
@@ -214,6 +217,50 @@ def make_fake(ref, n_sites=420):
                                 "min_aligned": 20, "split_slop": 3})
 
 
+def make_geometry_edges(ref):
+    """The deterministic boundary lattice of tests/geomcases.py through the reference, exactly as make_fake does it."""
+    import geomcases
+    libs = geomcases.library_specs()
+    groups = []
+    for grp in geomcases.corpus():
+        ref_libs = [ref.parsers.Library(name, None, rgs, rl, dict(hist), None, mean, sd, 1.0, 0)
+                    for (name, rgs, mean, sd, rl, hist) in libs]
+        rg_to_lib = {rg: L for L, spec in zip(ref_libs, libs) for rg in spec[1]}
+        libs_json, lib_index = lib_tables(ref_libs)
+        sites = []
+        for site in grp["sites"]:
+            bp, reads = site["breakpoint"], site["reads"]
+            frags = {}
+            for r in reads:                      # as gather_reads does (singlesample.py:194-203)
+                lib = rg_to_lib[r.get_tag("RG")]
+                if r.query_name in frags:
+                    frags[r.query_name].add_read(r)
+                else:
+                    frags[r.query_name] = ref.parsers.SamFragment(r, lib)
+            recs = packer.pack_fragments(frags, bp, lib_index, 20, 3)
+            per_fragment = [len(packer.pack_fragments({n: frags[n]}, bp, lib_index, 20, 3)) for n in sorted(frags)]
+            assert sum(per_fragment) == len(recs)
+            counts = ref.singlesample.tally_variant_read_fragments(3, 20, bp, frags, False)
+            if sum(counts.values()) == 0:
+                result = blank_like(ref)
+            else:
+                result = result_to_json(ref.singlesample.bayesian_genotype(bp, counts, 1, 1, False))
+            sites.append({
+                "breakpoint": bp,
+                "reads": [list(r.astuple()) for r in reads],
+                "records": [[int(x) for x in row] for row in recs.tolist()],
+                "record_fragments": per_fragment,
+                "shared_reads": site["shared_reads"],
+                "fits_int32": site["fits_int32"],
+                "tallies_sso": {t: hx(counts[t]) for t in TALLIES},
+                "result": result,
+            })
+        groups.append({"name": grp["name"], "bam": grp["bam"], "ref_length": grp["ref_length"], "libraries": libs_json,
+                       "sites": sites})
+    dump("geometry_edges.json.gz", {"groups": groups, "read_fields": list(fakereads.READ_FIELDS),
+                                    "min_aligned": 20, "split_slop": 3})
+
+
 def make_library_from_bam(ref):
     """Library statistics built empirically from the fixture BAM by the reference
     (parsers.py:472-583, statistics.py:40-121) -- pins svtyper_amd.library.Library.from_bam."""
@@ -269,6 +316,7 @@ if __name__ == "__main__":
     make_bayes_grid(ref)
     make_fixture(ref)
     make_fake(ref)
+    make_geometry_edges(ref)
     make_library_from_bam(ref)
     make_multisample_vcf(ref)
     make_three_sample_vcf(ref)
