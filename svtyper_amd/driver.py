@@ -1,0 +1,254 @@
+"""The one driver under `classic.sv_genotype` and `singlesample.sso_genotype`, and the one command line under their `main()`s.
+
+`Driver.run` is the run both programs share: option checks, alignment files and native handles, libraries, the collector
+for the chosen reader, device batches through `ChunkPipeline`, the bulk VCF route with its hand-over to the per-line
+route, the `stats=` block.  What the reference's two programs do differently is NOT here: `classic.Classic` and
+`singlesample.Sso` subclass `Driver` and state it, each piece with its `file:line` in the reference --
+
+    data     flags, site_quals            the device pass
+             count_mode                   how the reader counts towards max_reads
+             qual_mode, bulk_under_debug  the bulk route
+             skip_hash_lines              '#' lines in the body, on both routes
+    methods  alignment_paths()            the names in `bam_string`, or the exit for one that is no *.bam / *.cram
+             read_library_file(), write_library_file()
+             open_vcf(bulk)               header in, header out, `self.fast`; the body as lines or as blocks of text
+             warn(text), gather(sample, bp, max_reads)      inside handle_line
+             render_actions(results, actions)               results -> the text of every output action
+             finish(unpaired)             the end of a run
+
+No method takes a flag that names its caller, and a driver's hooks run per line handed to the per-line route and per
+block, never per site of the bulk route (`BulkFeeder._block` / `_write_block`).
+"""
+from __future__ import annotations
+
+import argparse
+import os
+import sys
+from itertools import chain
+
+from .bam import open_alignment_file
+from .library import setup_sample
+from .pipeline import (MIN_LIB_PREVALENCE, BulkFeeder, ChunkPipeline, NativeUnitCollector, UnitCollector, check_inflate,
+                       check_library_scan, check_verify, default_engine, resolve_reader, split_lines, verify_stats)
+from .vcf import Variant, Vcf
+
+
+class Driver:
+    flags = 0
+    site_quals = False
+    bulk_under_debug = True
+
+    def __init__(self, bam_string, vcf_in, vcf_out, min_aligned, split_weight, disc_weight, num_samp, lib_info_path, debug,
+                 ref_fasta, sum_quals, max_reads, max_ci_dist, n_threads=0):
+        self.bam_string, self.vcf_in, self.vcf_out = bam_string, vcf_in, vcf_out
+        self.min_aligned, self.split_weight, self.disc_weight = min_aligned, split_weight, disc_weight
+        self.num_samp, self.lib_info_path, self.debug, self.ref_fasta = num_samp, lib_info_path, debug, ref_fasta
+        self.sum_quals, self.max_reads, self.max_ci_dist = sum_quals, max_reads, max_ci_dist
+        self.n_threads = n_threads      # of the C++ reader (0 = the library's default)
+        self.fast = None                # SampleColumnWriter, made by open_vcf() once the header is known
+
+    def run(self, chunk_units, engine=None, geometry="host", reader=None, stats=None, inflate="host", library_scan="host",
+            verify="off"):
+        reader = resolve_reader(reader)
+        check_inflate(reader, inflate)
+        check_library_scan(reader, library_scan)
+        verify_on = check_verify(verify)
+        paths, bams = [], []
+        for path in self.alignment_paths():
+            paths.append(path)
+            bams.append(open_alignment_file(path, self.ref_fasta, verify=verify_on))
+        lib_info = self.read_library_file()
+        if self.vcf_in is None:     # classic.py:142-143 (sso_genotype does not get here without a VCF)
+            sys.stderr.write("Warning: VCF not found.\n")
+        native = None
+        if reader in ("native", "device"):      # C++ reader: library scans now, fetch + fragment summaries later
+            from .native_reads import NativeBam
+            native = [NativeBam(p, verify=verify_on) for p in paths]
+        if library_scan == "device" and lib_info is None and engine is None:
+            engine = default_engine()               # (the scan runs on the device the pass will use)
+        scan_device = getattr(engine, "device", 0) if library_scan == "device" else 0
+        self.samples = [setup_sample(b, lib_info, self.num_samp, MIN_LIB_PREVALENCE, nb, library_scan, scan_device, inflate)
+                        for b, nb in zip(bams, native or [None] * len(bams))]
+        self.write_library_file()
+        if self.vcf_in is None:
+            return
+
+        if engine is None:
+            engine = default_engine()
+        self.vcf = Vcf()
+        if native is not None:      # C++ fetch + summariser; geometry in the reader's threads ("host") or on the device
+            collector = NativeUnitCollector(self.samples, native, self.split_weight, self.disc_weight, self.min_aligned,
+                                            self.count_mode, self.max_reads, n_threads=self.n_threads,
+                                            geometry="walk" if reader == "device" else "device" if geometry == "device" else "reader",
+                                            inflate=inflate)
+        elif reader == "python":
+            collector = UnitCollector(self.samples, self.split_weight, self.disc_weight, self.min_aligned, geometry)
+        else:
+            raise ValueError("reader must be 'python', 'native' or 'device'")
+        self.collector, self.native_sites = collector, native is not None
+        pending: list = []      # ordered output actions of the current chunk
+        pipe = ChunkPipeline()
+        write = self.vcf_out.write
+
+        def flush():
+            actions = list(pending)
+            pending.clear()
+            # (classic) the incoming QUAL of every site: 0 unless --sum_quals
+            quals = [float(a[1].qual) for a in actions if a[0] == "gt"] if self.site_quals else None
+            pipe.submit(collector.take(engine, self.flags, site_quals=quals), lambda results: write_out(results, actions))
+
+        def write_out(results, actions):
+            for text in self.render_actions(results, actions):
+                write(text)
+
+        def per_line(lines):
+            """the general route: one Variant object per line, device batches of `chunk_units` units"""
+            for line in lines:
+                if self.skip_hash_lines and line.startswith("#"):
+                    continue
+                action = self.handle_line(line)
+                if action is not None:
+                    pending.append(action)
+                if len(collector) >= chunk_units:
+                    flush()
+
+        # bulk route (C++ reader): blocks of lines -> breakpoint arrays -> output text in native calls (bulk_vcf.py); lines it
+        # hands back, and everything once it stops in front of a BND line it cannot express, take the per-line route above
+        bulk = None
+        if (native is not None and (self.bulk_under_debug or not self.debug) and hasattr(self.vcf_in, "read")
+                and os.environ.get("SVT_BULK_VCF", "1") != "0"):
+            from . import bulk_vcf
+            if bulk_vcf.available():
+                bulk = bulk_vcf
+        lines, blocks = self.open_vcf(bulk is not None)
+        feeder = rest = None
+        if blocks is not None:
+            feeder = BulkFeeder(bulk, self.vcf, collector, pipe, engine, self.flags, len(self.samples), self.fast, self.qual_mode,
+                                self.max_ci_dist, self.sum_quals, self.skip_hash_lines, self.handle_line, self.render_actions, write)
+            rest = feeder.run(blocks)
+            if rest is not None:      # the per-line route from here on, with the BND mates the parser was holding
+                for held in feeder.pending_lines():
+                    mate = Variant(held.split("\t"), self.vcf)
+                    if not self.sum_quals:
+                        mate.qual = 0
+                    self.vcf._bnd_pending[mate.var_id] = mate
+                lines = chain(rest, chain.from_iterable(map(split_lines, blocks)))
+        if lines is not None:
+            per_line(lines)
+        flush()
+        pipe.close()
+        if stats is not None:       # (keyword-only extra: where the caller's thread spent its time, pipeline.BulkFeeder.laps)
+            stats.update(feeder.laps if feeder else {},
+                         route="per line" if feeder is None else "bulk" if rest is None else "bulk, then per line")
+            if reader == "device":      # the counters of svt_bam_evidence_device, summed over the run's calls
+                stats["device_reader"] = collector.device_stats
+            stats["verify"] = verify_stats(native, () if native else bams)   # (with the C++ reader the Python one reads the header only)
+        # first BND mates whose partner never came: in the Vcf model, or left in the bulk parser at the end
+        self.finish(bool(self.vcf._bnd_pending) or (feeder is not None and rest is None and feeder.n_pending() > 0))
+
+    def handle_line(self, line, unit_base=0):
+        """One variant line -> its output action (classic.py:213-278, singlesample.py:587-627), or None for a first BND
+        mate (it waits for its partner in the Vcf model); its units go to the collector."""
+        vcf, collector = self.vcf, self.collector
+        var = Variant(line.rstrip().split("\t"), vcf)
+        if not self.sum_quals:
+            var.qual = 0
+        if not var.has_svtype():
+            self.warn("Warning: SVTYPE missing at variant %s. Skipping.\n" % var.var_id)
+            return ("raw", var)
+        if not var.is_valid_svtype():
+            self.warn("Warning: Unsupported SVTYPE at variant %s (%s). Skipping.\n" % (var.var_id, var.get_svtype()))
+            return ("raw", var)
+        bp = vcf.get_variant_breakpoints(var, self.max_ci_dist)
+        if bp is None:
+            return None
+        var2 = None
+        if var.get_svtype() == "BND":       # the pair is written at the second mate's place, first mate first
+            var2 = var
+            var = vcf._bnd_first.pop(bp["id"])
+        if self.native_sites:
+            first_unit = collector.add_site(bp)
+        else:
+            first_unit = len(collector)
+            for k, sample in enumerate(self.samples):
+                fragments, many = self.gather(sample, bp, self.max_reads)
+                collector.add(bp, k, fragments, skip=many)
+        return ("gt", var, var2, first_unit - unit_base)
+
+
+# ------------------------------------------------------------------------------------------ CLI
+def parse_arguments(p, bam_help, max_reads, own):
+    """The command line of `p` parsed: the arguments `svtyper` and `svtyper-sso` share, with `own(p)` adding a program's own
+    where its help lists them."""
+    p.add_argument("-i", "--input_vcf", metavar="FILE", type=argparse.FileType("r"), default=None,
+                   help="VCF input (default: stdin)")
+    p.add_argument("-o", "--output_vcf", metavar="FILE", type=argparse.FileType("w"), default=sys.stdout,
+                   help="output VCF to write (default: stdout)")
+    p.add_argument("-B", "--bam", metavar="FILE", type=str, required=True, help=bam_help)
+    p.add_argument("-T", "--ref_fasta", metavar="FILE", type=str, default=None,
+                   help="Indexed reference FASTA file (recommended for reading CRAM files)")
+    p.add_argument("-S", "--split_bam", type=str, help=argparse.SUPPRESS)
+    p.add_argument("-l", "--lib_info", metavar="FILE", dest="lib_info_path", type=str, default=None,
+                   help="create/read JSON file of library information")
+    p.add_argument("-m", "--min_aligned", metavar="INT", type=int, default=20,
+                   help="minimum number of aligned bases to consider read as evidence [20]")
+    p.add_argument("-n", dest="num_samp", metavar="INT", type=int, default=1000000,
+                   help="number of reads to sample from BAM file for building insert size distribution [1000000]")
+    p.add_argument("-q", "--sum_quals", action="store_true",
+                   help="add genotyping quality to existing QUAL (default: overwrite QUAL field)")
+    p.add_argument("--max_reads", metavar="INT", type=int, default=max_reads,
+                   help="maximum number of reads to assess at any variant (default: %s)"
+                        % ("unlimited" if max_reads is None else max_reads))
+    p.add_argument("--max_ci_dist", metavar="INT", type=int, default=1e10,
+                   help="maximum size of a confidence interval before 95%% CI is used intead (default: 1e10)")
+    p.add_argument("--split_weight", metavar="FLOAT", type=float, default=1, help="weight for split reads [1]")
+    p.add_argument("--disc_weight", metavar="FLOAT", type=float, default=1,
+                   help="weight for discordant paired-end reads [1]")
+    p.add_argument("--debug", action="store_true", help=argparse.SUPPRESS)
+    own(p)
+    # not in the reference: where the host work runs (same output bytes either way)
+    p.add_argument("--reader", choices=("python", "native", "device"), default="native",
+                   help="BAM access + fragment assembly: the C++ threads of libsvtyper_hip.so feeding the device "
+                        "geometry stage, the same with the evidence records built on the GPU (device), or the portable Python "
+                        "reader (same output bytes) [native]")
+    p.add_argument("--inflate", choices=("host", "device"), default="host",
+                   help="with --reader device: BGZF blocks inflated by the reader's threads, or on the GPU from the "
+                        "compressed blocks (same output bytes) [host]")
+    p.add_argument("--verify-bgzf", dest="verify_bgzf", action="store_true",
+                   help="check the CRC32 of every BGZF block where it is inflated (verify='crc32'); a mismatch is an error")
+    p.add_argument("--library-scan", dest="library_scan", choices=("host", "device"), default="host",
+                   help="without a library file: the libraries' read length, insert-size histogram and prevalence from three "
+                        "scans per library on the host, or from one segmented walk on the GPU for all libraries, members inflated as --inflate says "
+                        "(needs --reader native or device; same library file, same output bytes) [host]")
+    p.add_argument("--geometry", choices=("host", "device"), default="host",
+                   help="with --reader python: breakpoint-dependent read predicates on the host or on the GPU [host]")
+    args = p.parse_args()
+    if args.input_vcf is None and not sys.stdin.isatty():
+        args.input_vcf = sys.stdin
+    return args
+
+
+def run_main(driver, sharded_driver, call, args):
+    """The tail of both `main()`s: `driver(*call)` with the options that are not in the reference -- or, launched by
+    torch.distributed.run with several ranks, its sharded form: one GPU each, variants sharded, one gather."""
+    from . import sharded
+    if args.split_bam is not None:
+        sys.stderr.write("Warning: --split_bam (-S) is deprecated. Ignoring %s.\n" % args.split_bam)
+    options = dict(geometry=args.geometry, reader=args.reader, inflate=args.inflate, library_scan=args.library_scan,
+                   verify="crc32" if args.verify_bgzf else "off")
+    job = sharded.job()
+    if job is None:
+        return driver(*call, **options)
+    rank, world, local_rank = job
+    call = call[:2] + (sharded.private_stdout(call[2]),) + call[3:]
+    engine = sharded.init(local_rank)
+    sharded_driver(*call, rank=rank, world=world, engine=engine, **options)
+    sharded.finish()
+
+
+def run_cli(main):
+    try:
+        sys.exit(main())
+    except IOError as e:
+        if e.errno != 32:   # EPIPE
+            raise

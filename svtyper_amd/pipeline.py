@@ -181,6 +181,26 @@ def resolve_reader(reader: Optional[str]) -> str:
         return "python"
 
 
+def _library_tables(collector, samples: List[Sample]) -> None:
+    """One device batch per group of samples (library_groups), on either collector: `groups`, `group_of` (sample -> group),
+    `group_tables` (per group its library table; a sample's libraries are contiguous in it, from `sample_base`), `sample_libs`
+    (per sample the svt_unit.libs hint) and `lib_tables` (every table, in order)."""
+    collector.groups = library_groups(samples)
+    collector.group_of = [g for g, members in enumerate(collector.groups) for _ in members]
+    collector.group_tables = []
+    collector.sample_base = []
+    collector.sample_libs = []
+    for members in collector.groups:
+        tables = []
+        for k in members:
+            libs = list(samples[k].lib_dict.values())
+            collector.sample_base.append(len(tables))
+            collector.sample_libs.append(ev.unit_libs(len(tables), len(libs)))   # (0 = no hint when it does not fit)
+            tables.extend(lib.table() for lib in libs)
+        collector.group_tables.append(tables)
+    collector.lib_tables = [t for tables in collector.group_tables for t in tables]
+
+
 class UnitCollector:
     """Packs (breakpoint, sample) units of one chunk of variants and remembers where each went.
 
@@ -197,23 +217,10 @@ class UnitCollector:
         self.min_aligned = min_aligned
         self.split_weight = split_weight
         self.disc_weight = disc_weight
-        # one device batch per group of samples (library_groups): its library table, the index of every library in it, and per
-        # sample the svt_unit.libs hint (a sample's libraries are contiguous in its group's table)
-        self.groups = library_groups(samples)
-        self.group_of = [g for g, members in enumerate(self.groups) for _ in members]
-        self.group_tables: List[list] = []
-        self.lib_index: Dict[int, int] = {}
-        self.sample_libs = []
-        for members in self.groups:
-            tables = []
-            for k in members:
-                first = len(tables)
-                for lib in samples[k].lib_dict.values():
-                    self.lib_index[id(lib)] = len(tables)
-                    tables.append(lib.table())
-                self.sample_libs.append(ev.unit_libs(first, len(tables) - first))   # (0 = no hint when it does not fit)
-            self.group_tables.append(tables)
-        self.lib_tables = [t for tables in self.group_tables for t in tables]
+        _library_tables(self, samples)
+        # the index of every library in its group's table
+        self.lib_index: Dict[int, int] = {id(lib): base + i for s, base in zip(samples, self.sample_base)
+                                          for i, lib in enumerate(s.lib_dict.values())}
         self._reset()
 
     def _reset(self):
@@ -313,26 +320,13 @@ class NativeUnitCollector:
         self.n_threads = n_threads or int(os.environ.get("SVT_READER_THREADS", "0"))   # 0 = the library's default
         self.split_weight = split_weight
         self.disc_weight = disc_weight
-        # one device batch per group of samples (library_groups): per group its library table; per sample the read groups
-        # with their library's index in the group's table (-1: not active) and the svt_unit.libs hint
-        self.groups = library_groups(samples)
-        self.group_of = [g for g, members in enumerate(self.groups) for _ in members]
-        self.group_tables: List[list] = []
-        self.rg_tables = []          # per sample: (read group ids, library index or -1)
-        self.sample_libs = []        # per sample: svt_unit.libs hint
-        for members in self.groups:
-            tables = []
-            for k in members:
-                s = samples[k]
-                base = len(tables)
-                libs = list(s.lib_dict.values())
-                tables.extend(lib.table() for lib in libs)
-                self.sample_libs.append(ev.unit_libs(base, len(libs)))   # (0 = no hint when it does not fit)
-                rgs = list(s.rg_to_lib.keys())
-                idx = [base + libs.index(s.rg_to_lib[rg]) if s.rg_to_lib[rg].name in s.active_libs else -1 for rg in rgs]
-                self.rg_tables.append((rgs, idx))
-            self.group_tables.append(tables)
-        self.lib_tables = [t for tables in self.group_tables for t in tables]
+        _library_tables(self, samples)
+        self.rg_tables = []          # per sample: (read group ids, their library's index in the group's table or -1: not active)
+        for s, base in zip(samples, self.sample_base):
+            libs = list(s.lib_dict.values())
+            rgs = list(s.rg_to_lib.keys())
+            idx = [base + libs.index(s.rg_to_lib[rg]) if s.rg_to_lib[rg].name in s.active_libs else -1 for rg in rgs]
+            self.rg_tables.append((rgs, idx))
         self.sites: List[dict] = []
         self.site_arrays: list = []      # bulk_vcf.SiteArrays blocks, in front of the dict sites
 
@@ -453,6 +447,19 @@ class NativeUnitCollector:
             res.site_qual = q
         return res
 
+    def _unit_headers(self, k: int, bps):
+        """the svt_unit array of sample k over the sites of `bps` (svt_breakpoint[]); `flags` are left 0"""
+        import numpy as np
+        units = np.zeros(bps.shape[0], ev.UNIT_DTYPE)
+        units["var_length"] = np.where(bps["svtype"] == ev.SVTYPE_CODE["DEL"], bps["var_length"], 0)
+        units["pos_delta"] = np.clip(bps["pos_b"].astype(np.int64) - bps["pos_a"].astype(np.int64), -2**31, 2**31 - 1)   # classic.py:339
+        units["sample"], units["svtype"] = k, bps["svtype"]
+        units["libs"] = self.sample_libs[k]
+        return units
+
+    def _flanks(self, k: int) -> List[float]:
+        """mean + 3 sd of every library of sample k's group (svt_batch_create_from_fragments' v_nondel)"""
+        return [float(t.mean) + float(t.sd) * 3 for t in self.group_tables[self.group_of[k]]]
 
     def _run_walk(self, prepared, engine: Engine, flags: int, kw: dict, lap) -> Results:
         """geometry="walk": one resident batch per sample, its records built in HBM by svt_bam_evidence_device (no evidence
@@ -467,14 +474,9 @@ class NativeUnitCollector:
         for k, (nbam, (bps, win)) in enumerate(zip(self.bams, prepared)):
             rgs, idx = self.rg_tables[k]
             tables = self.group_tables[self.group_of[k]]
-            flank = [float(t.mean) + float(t.sd) * 3 for t in tables]
-            units = np.zeros(n_sites, ev.UNIT_DTYPE)
-            units["var_length"] = np.where(bps["svtype"] == ev.SVTYPE_CODE["DEL"], bps["var_length"], 0)
-            units["pos_delta"] = np.clip(bps["pos_b"].astype(np.int64) - bps["pos_a"].astype(np.int64), -2**31, 2**31 - 1)   # classic.py:339
-            units["sample"], units["svtype"] = k, bps["svtype"]
-            units["libs"] = self.sample_libs[k]
-            head = EvidenceBatch(np.zeros(n_sites + 1, np.uint64), units, np.zeros(0, ev.RECORD_DTYPE), tables, self.split_weight,
-                                 self.disc_weight)
+            flank = self._flanks(k)
+            head = EvidenceBatch(np.zeros(n_sites + 1, np.uint64), self._unit_headers(k, bps), np.zeros(0, ev.RECORD_DTYPE), tables,
+                                 self.split_weight, self.disc_weight)
             with _READER_TURN:
                 d, _skipped, st = nbam.evidence_device(win, bps, rgs, idx, self.max_reads, self.count_mode, flank, self.min_aligned,
                                                        SPLIT_SLOP, head, engine.device, flags, self.n_threads, inflate=self.inflate,
@@ -504,17 +506,13 @@ class NativeUnitCollector:
         per_sample = []
         for k, (nbam, (bps, win)) in enumerate(zip(self.bams, prepared)):
             rgs, idx = self.rg_tables[k]
-            flank = [float(t.mean) + float(t.sd) * 3 for t in self.group_tables[self.group_of[k]]]   # (svt_batch_create_from_fragments' v_nondel)
+            flank = self._flanks(k)
             with _READER_TURN:
                 off, recs, skipped = nbam.evidence(win, bps, rgs, idx, self.max_reads, self.count_mode, flank, self.min_aligned,
                                                    SPLIT_SLOP, self.n_threads)
             lap("svt_bam_evidence")
-            units = np.zeros(n_sites, ev.UNIT_DTYPE)
-            units["var_length"] = np.where(bps["svtype"] == ev.SVTYPE_CODE["DEL"], bps["var_length"], 0)
-            units["pos_delta"] = np.clip(bps["pos_b"].astype(np.int64) - bps["pos_a"].astype(np.int64), -2**31, 2**31 - 1)   # classic.py:339
-            units["sample"], units["svtype"] = k, bps["svtype"]
+            units = self._unit_headers(k, bps)
             units["flags"] = np.where(skipped != 0, ev.UNIT_SKIP, 0)
-            units["libs"] = self.sample_libs[k]
             per_sample.append((off, units, recs))
         if len(self.groups) == 1:
             return self._run_group(per_sample, self.group_tables[0], n_sites, engine, flags, kw, lap)
