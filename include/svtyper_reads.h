@@ -13,7 +13,7 @@
  * and what svtyper_amd/bam.py + fragments.py + geometry.py do in Python (those stay the portable
  * implementation and are the checker of this one: tests/test_native_reads.py).
  *
- * Plain C ABI, host memory only; no GPU is needed for these calls.  BAM + .bai only (no CRAM).
+ * Plain C ABI, host memory only; no GPU is needed for these calls.  BAM with a .bai or a .csi index (no CRAM).
  */
 #ifndef SVTYPER_READS_H
 #define SVTYPER_READS_H
@@ -28,9 +28,14 @@ extern "C" {
 
 typedef struct svt_bam svt_bam; /* opaque: header + index of one BAM file */
 
-/* Open `path` (and `path`.bai or the .bai next to it).  0 or SVT_ERR_*; text via svt_last_error(). */
+/* Open `path` and its index: the first there is of `path`.bai, the .bai next to it, `path`.csi, the .csi next to it; the file's
+ * magic, not its name, says whether it is a BAI or a CSI.  0 or SVT_ERR_*; text via svt_last_error(). */
 int svt_bam_open(const char* path, svt_bam** out);
 void svt_bam_close(svt_bam* bam);
+/* Which index svt_bam_open took: *kind 1 for a BAI (min_shift 14, depth 5), 2 for a CSI with the scheme it names (positions
+ * below 2^(min_shift + 3 * depth)); a null pointer is skipped.  Added under ABI 19 without a new number: a library built before
+ * it lacks the symbol -- probe for it (dlsym / hasattr), as for svt_pack_evidence_flags. */
+int svt_bam_index_info(const svt_bam* bam, int* kind, int* min_shift, int* depth);
 
 int32_t svt_bam_n_references(const svt_bam* bam);
 const char* svt_bam_reference_name(const svt_bam* bam, int32_t tid);

@@ -1,4 +1,4 @@
-"""Minimal BGZF / BAM / BAI reader with the slice of the pysam API the SVTyper path relies on.
+"""Minimal BGZF / BAM / BAI / CSI reader with the slice of the pysam API the SVTyper path relies on.
 
 pysam (htslib) is what the reference uses (svtyper/classic.py:126-129, parsers.py:480-558); it
 is not available in this image and cannot be installed, so the host side ships its own reader.
@@ -288,17 +288,24 @@ class AlignedSegment:
             self.query_name, self.flag, self.reference_name, self.reference_start, self.mapping_quality)
 
 
-def _reg2bins(beg: int, end: int) -> List[int]:
-    """UCSC binning scheme bins overlapping [beg, end) (SAM spec 5.3)."""
+def _reg2bins(beg: int, end: int, min_shift: int = 14, depth: int = 5) -> List[int]:
+    """Bins overlapping [beg, end) in a scheme of `depth` levels over leaves of 2^min_shift positions (SAM spec 5.3, CSIv1):
+    level l starts at bin (8^l - 1) / 7 and shifts by min_shift + 3 (depth - l).  (14, 5) is the BAI's UCSC scheme."""
     end -= 1
-    bins = [0]
-    for shift, off in ((26, 1), (23, 9), (20, 73), (17, 585), (14, 4681)):
+    bins: List[int] = []
+    for l in range(depth + 1):
+        shift, off = min_shift + 3 * (depth - l), ((1 << (3 * l)) - 1) // 7
         bins.extend(range(off + (beg >> shift), off + (end >> shift) + 1))
     return bins
 
 
+def _pseudo_bin(depth: int) -> int:
+    """the bin number that carries a reference's mapped / unmapped counts: 37450 at depth 5"""
+    return ((1 << (3 * (depth + 1))) - 1) // 7 + 1
+
+
 class AlignmentFile:
-    """BAM file opened for reading, with its .bai index when present."""
+    """BAM file opened for reading, with its .bai or .csi index when present."""
 
     def __init__(self, path: str, mode: str = "rb", **kwargs):
         if "c" in mode or path.endswith(".cram"):
@@ -322,7 +329,11 @@ class AlignmentFile:
         self.header = self._parse_header(self.text)
         self._index = None
         self._index_stats = None
-        for cand in (path + ".bai", os.path.splitext(path)[0] + ".bai"):
+        self._index_scheme = None         # (kind "bai" | "csi", min_shift, depth)
+        # .bai first: a call that found its index before .csi was read opens the same file as before (htslib would take a
+        # .csi first; the answers are the same).  What a file is, its magic says, not its name.
+        stem = os.path.splitext(path)[0]
+        for cand in (path + ".bai", stem + ".bai", path + ".csi", stem + ".csi"):
             if os.path.exists(cand):
                 self._load_index(cand)
                 break
@@ -344,6 +355,12 @@ class AlignmentFile:
     def _load_index(self, path: str):
         with open(path, "rb") as f:
             data = f.read()
+        if data[:2] == b"\x1f\x8b":
+            self._load_csi(path)
+        else:
+            self._load_bai(path, data)
+
+    def _load_bai(self, path: str, data: bytes):
         if data[:4] != b"BAI\1":
             raise IOError("%s is not a BAI index" % path)
         off = 4
@@ -364,11 +381,102 @@ class AlignmentFile:
                     bins[b] = chunks
             n_intv = struct.unpack_from("<i", data, off)[0]; off += 4
             linear = list(struct.unpack_from("<%dQ" % n_intv, data, off)); off += 8 * n_intv
-            index.append((bins, linear))
+            index.append((bins, linear, None))
         if off + 8 <= len(data):
             unmapped += struct.unpack_from("<Q", data, off)[0]
         self._index = index
         self._index_stats = (mapped, unmapped)
+        self._index_scheme = ("bai", 14, 5)
+
+    def _load_csi(self, path: str):
+        """A CSI index (CSIv1): a BGZF file, read through BgzfReader with every member's CRC32 checked.  Per reference the bins
+        with their chunks and one `loffset` each instead of a linear index; the pseudo-bin and n_no_coor as in a BAI."""
+        try:
+            z = BgzfReader(path, verify=True)
+            try:
+                parts = []
+                while True:
+                    part = z.read(1 << 20)
+                    if not part:
+                        break
+                    parts.append(part)
+            finally:
+                z.close()
+        except (IOError, zlib.error, struct.error) as e:
+            raise IOError("%s: the BGZF layer of the index does not inflate (%s)" % (path, e))
+        data = b"".join(parts)
+        if data[:4] != b"CSI\1":
+            raise IOError("%s is not a CSI index (wrong magic behind the BGZF layer)" % path)
+        try:
+            min_shift, depth, l_aux = struct.unpack_from("<iii", data, 4)
+            if min_shift < 0 or depth < 0 or min_shift + 3 * depth > 62 or depth > 10:
+                raise IOError("%s: CSI min_shift / depth out of range (%d, %d)" % (path, min_shift, depth))
+            if l_aux < 0:
+                raise IOError("%s: negative count in CSI (l_aux)" % path)
+            off = 16 + l_aux
+            n_ref = struct.unpack_from("<i", data, off)[0]; off += 4
+            if n_ref < 0:
+                raise IOError("%s: negative count in CSI (n_ref)" % path)
+            pseudo = _pseudo_bin(depth)
+            index = []
+            mapped = unmapped = 0
+            for _ in range(n_ref):
+                n_bin = struct.unpack_from("<i", data, off)[0]; off += 4
+                if n_bin < 0:
+                    raise IOError("%s: negative count in CSI (n_bin)" % path)
+                bins: Dict[int, List[Tuple[int, int]]] = {}
+                loffset: Dict[int, int] = {}
+                for _ in range(n_bin):
+                    b, loff, n_chunk = struct.unpack_from("<IQi", data, off); off += 16
+                    if n_chunk < 0:
+                        raise IOError("%s: negative count in CSI (n_chunk)" % path)
+                    if off + 16 * n_chunk > len(data):
+                        raise IOError("%s: truncated CSI (chunks)" % path)
+                    chunks = list(struct.iter_unpack("<QQ", data[off:off + 16 * n_chunk])); off += 16 * n_chunk
+                    if b == pseudo:
+                        if len(chunks) >= 2:
+                            mapped += chunks[1][0]
+                            unmapped += chunks[1][1]
+                    else:
+                        bins[b] = chunks
+                        loffset[b] = loff
+                index.append((bins, None, loffset))
+            if off + 8 <= len(data):
+                unmapped += struct.unpack_from("<Q", data, off)[0]
+        except struct.error:
+            raise IOError("%s: truncated CSI" % path)
+        self._index = index
+        self._index_stats = (mapped, unmapped)
+        self._index_scheme = ("csi", min_shift, depth)
+
+    def index_info(self) -> Optional[dict]:
+        """which index was loaded: {"kind": "bai" | "csi", "min_shift", "depth"}, or None without one"""
+        if self._index_scheme is None:
+            return None
+        kind, min_shift, depth = self._index_scheme
+        return {"kind": kind, "min_shift": min_shift, "depth": depth}
+
+    def _min_offset(self, tid: int, beg: int) -> int:
+        """An offset no record overlapping [beg, ...) lies in front of.  BAI: the linear index's entry of beg's 16-kbp window.
+        CSI: htslib's rule -- the loffset of the leaf bin holding beg, else of the nearest present bin met by stepping to the
+        previous sibling and, from a first sibling, to the parent; 0 when none is present."""
+        _bins, linear, loffset = self._index[tid]
+        _kind, min_shift, depth = self._index_scheme
+        if loffset is None:
+            if not linear:
+                return 0
+            li = beg >> 14
+            return linear[li] if li < len(linear) else linear[-1]
+        if not loffset:
+            return 0
+        b = ((1 << (3 * depth)) - 1) // 7 + (min(beg, (1 << (min_shift + 3 * depth)) - 1) >> min_shift)
+        while True:
+            if b in loffset:
+                return loffset[b]
+            if b == 0:
+                return 0
+            parent = (b - 1) >> 3
+            b = b - 1 if b > (parent << 3) + 1 else parent
 
     @property
     def mapped(self) -> int:
@@ -425,13 +533,17 @@ class AlignmentFile:
             return
         if self._index is None:
             raise ValueError("fetch called on bamfile without index")
-        bins, linear = self._index[tid]
-        min_off = 0
-        li = beg >> 14
-        if linear:
-            min_off = linear[li] if li < len(linear) else linear[-1]
+        bins = self._index[tid][0]
+        _kind, min_shift, depth = self._index_scheme
+        # the window as the index sees it: clipped to the positions its scheme covers and to the contig
+        bin_end = min(end, 1 << (min_shift + 3 * depth))
+        if self.lengths[tid] > 0:
+            bin_end = min(bin_end, self.lengths[tid])
+        if bin_end <= beg:
+            return
+        min_off = self._min_offset(tid, beg)
         chunks = []
-        for b in _reg2bins(beg, end):
+        for b in _reg2bins(beg, bin_end, min_shift, depth):
             for cb, ce in bins.get(b, ()):
                 if ce > min_off:
                     chunks.append((cb, ce))

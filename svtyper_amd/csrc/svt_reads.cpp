@@ -27,6 +27,7 @@
 #include <vector>
 
 #include "../../include/svtyper_reads.h"
+#include "svt_bam_index.h"
 #include "svt_bgzf.h"
 #include "svt_error.h"
 #include "svt_evidence_arena.h"
@@ -130,12 +131,8 @@ struct svt_bam {
     std::vector<int64_t> ref_lengths;
     std::unordered_map<std::string, int32_t> tid_of;
     uint64_t first_record = 0;
-    struct RefIndex {
-        std::unordered_map<uint32_t, std::vector<std::pair<uint64_t, uint64_t>>> bins;
-        std::vector<uint64_t> linear;
-    };
-    std::vector<RefIndex> index;
-    bool has_index = false;
+    svt::bamidx::Index index;      // BAI or CSI behind one model (svt_bam_index.h); kind KIND_NONE: the file has none
+    bool has_index() const { return index.kind != svt::bamidx::KIND_NONE; }
     // CPU seconds per unit of the summariser's last calls on this file (0: none yet): sizes the next call's burst
     mutable std::atomic<double> cpu_s_per_unit{0.0};
     // svt_bam_set_verify: off by default; the tally of everything that was verified through this handle
@@ -170,17 +167,6 @@ VerifyScope::~VerifyScope()
 }  // namespace svt
 
 namespace {
-
-void reg2bins(int64_t beg, int64_t end, std::vector<uint32_t>& bins)
-{
-    --end;
-    bins.clear();
-    bins.push_back(0);
-    const int shifts[5] = {26, 23, 20, 17, 14};
-    const uint32_t offs[5] = {1, 9, 73, 585, 4681};
-    for (int l = 0; l < 5; ++l)
-        for (int64_t k = offs[l] + (beg >> shifts[l]); k <= (int64_t)offs[l] + (end >> shifts[l]); ++k) bins.push_back((uint32_t)k);
-}
 
 using rr::ld32;
 
@@ -222,32 +208,13 @@ bool read_record(Bgzf& z, std::vector<uint8_t>& buf, Record& r)
     return decode(d, size, r);
 }
 
-// the merged BAI chunks a fetch of [beg, end) on `tid` walks, in file order (scratch of the calling thread)
+// the merged index chunks a fetch of [beg, end) on `tid` walks, in file order (scratch of the calling thread)
 const std::vector<std::pair<uint64_t, uint64_t>>& fetch_chunks(const svt_bam& bam, int32_t tid, int64_t beg, int64_t end)
 {
     // (reused from fetch to fetch: two fetches per unit, three allocations each)
     static thread_local std::vector<uint32_t> bins;
     static thread_local std::vector<std::pair<uint64_t, uint64_t>> chunks, merged;
-    const auto& ri = bam.index[tid];
-    uint64_t min_off = 0;
-    const size_t li = (size_t)(beg >> 14);
-    if (!ri.linear.empty()) min_off = li < ri.linear.size() ? ri.linear[li] : ri.linear.back();
-    reg2bins(beg, end, bins);
-    chunks.clear();
-    merged.clear();
-    for (uint32_t b : bins) {
-        auto it = ri.bins.find(b);
-        if (it == ri.bins.end()) continue;
-        for (const auto& c : it->second)
-            if (c.second > min_off) chunks.push_back(c);
-    }
-    if (chunks.empty()) return merged;
-    std::sort(chunks.begin(), chunks.end());
-    merged.push_back(chunks[0]);
-    for (size_t i = 1; i < chunks.size(); ++i) {
-        if (chunks[i].first <= merged.back().second) merged.back().second = std::max(merged.back().second, chunks[i].second);
-        else merged.push_back(chunks[i]);
-    }
+    bam.index.fetch_chunks(tid, beg, end, bam.ref_lengths[tid], bins, chunks, merged);
     return merged;
 }
 
@@ -1194,10 +1161,13 @@ static int svt_bam_open_impl(const char* path, svt_bam** out)
         b->ref_lengths.push_back(l_ref);
     }
     b->first_record = z.tell();
-    // index: <path>.bai, else the .bai next to the file
-    std::string cand[2] = {b->path + ".bai", b->path};
-    const size_t dot = cand[1].rfind('.');
-    if (dot != std::string::npos) cand[1] = cand[1].substr(0, dot) + ".bai";
+    // index: <path>.bai, the .bai next to the file, <path>.csi, the .csi next to it.  .bai first: a call that found its index
+    // before this list grew reads the same file as before (htslib would take a .csi first; the answers are the same).  What a
+    // file is, its magic says, not its name.
+    std::string stem = b->path;
+    const size_t dot = stem.rfind('.');
+    if (dot != std::string::npos) stem = stem.substr(0, dot);
+    const std::string cand[4] = {b->path + ".bai", stem + ".bai", b->path + ".csi", stem + ".csi"};
     for (const std::string& p : cand) {
         FILE* f = std::fopen(p.c_str(), "rb");
         if (!f) continue;
@@ -1206,40 +1176,12 @@ static int svt_bam_open_impl(const char* path, svt_bam** out)
         size_t n;
         while ((n = std::fread(tmp, 1, sizeof tmp, f)) > 0) data.insert(data.end(), tmp, tmp + n);
         std::fclose(f);
-        if (data.size() < 8 || std::memcmp(data.data(), "BAI\1", 4) != 0) return fail(SVT_ERR_INVALID, p + " is not a BAI index");
-        size_t off = 4;
-        auto u32 = [&](size_t o) { return (uint32_t)data[o] | (data[o + 1] << 8) | (data[o + 2] << 16) | ((uint32_t)data[o + 3] << 24); };
-        auto u64 = [&](size_t o) { return (uint64_t)u32(o) | ((uint64_t)u32(o + 4) << 32); };
-        const uint32_t nr = u32(off);
-        off += 4;
-        b->index.resize(nr);
-        for (uint32_t r = 0; r < nr; ++r) {
-            if (off + 4 > data.size()) return fail(SVT_ERR_INVALID, "truncated BAI");
-            const uint32_t n_bin = u32(off);
-            off += 4;
-            for (uint32_t k = 0; k < n_bin; ++k) {
-                if (off + 8 > data.size()) return fail(SVT_ERR_INVALID, "truncated BAI");
-                const uint32_t bin = u32(off), n_chunk = u32(off + 4);
-                off += 8;
-                if (off + 16ull * n_chunk > data.size()) return fail(SVT_ERR_INVALID, "truncated BAI");
-                if (bin != 37450) {
-                    auto& v = b->index[r].bins[bin];
-                    for (uint32_t c = 0; c < n_chunk; ++c) v.emplace_back(u64(off + 16 * c), u64(off + 16 * c + 8));
-                }
-                off += 16ull * n_chunk;
-            }
-            if (off + 4 > data.size()) return fail(SVT_ERR_INVALID, "truncated BAI");
-            const uint32_t n_intv = u32(off);
-            off += 4;
-            if (off + 8ull * n_intv > data.size()) return fail(SVT_ERR_INVALID, "truncated BAI");
-            for (uint32_t k = 0; k < n_intv; ++k) b->index[r].linear.push_back(u64(off + 8 * k));
-            off += 8ull * n_intv;
-        }
-        b->has_index = true;
+        std::string err;
+        if (!svt::bamidx::load(data.data(), data.size(), p, b->index, err)) return fail(SVT_ERR_INVALID, err);
         break;
     }
-    if (!b->has_index) return fail(SVT_ERR_INVALID, std::string("no .bai index found for ") + path);
-    if (b->index.size() < b->ref_names.size()) b->index.resize(b->ref_names.size());
+    if (!b->has_index()) return fail(SVT_ERR_INVALID, std::string("no .bai index found for ") + path + " (nor a .csi)");
+    if (b->index.refs.size() < b->ref_names.size()) b->index.refs.resize(b->ref_names.size());
     *out = b.release();
     return SVT_OK;
 }
@@ -1250,6 +1192,15 @@ int svt_bam_open(const char* path, svt_bam** out)
 }
 
 void svt_bam_close(svt_bam* bam) { delete bam; }
+
+int svt_bam_index_info(const svt_bam* bam, int* kind, int* min_shift, int* depth)
+{
+    if (!bam) return fail(SVT_ERR_INVALID, "null argument");
+    if (kind) *kind = bam->index.kind;
+    if (min_shift) *min_shift = bam->index.min_shift;
+    if (depth) *depth = bam->index.depth;
+    return SVT_OK;
+}
 
 int32_t svt_bam_n_references(const svt_bam* bam) { return bam ? (int32_t)bam->ref_names.size() : 0; }
 
@@ -1790,7 +1741,7 @@ double seconds_since(std::chrono::steady_clock::time_point t0)
 struct Planner {
     const svt_bam* bam;
     const uint64_t round_bytes;
-    std::vector<uint64_t> cuts;                          // the distinct linear-index offsets behind first_record, ascending
+    std::vector<uint64_t> cuts;                          // the index's record starts behind first_record, ascending and distinct
     size_t next_cut = 0;
     uint64_t start;                                      // virtual offset of the next round's first record
     uint32_t seg_index = 0;
@@ -1800,11 +1751,7 @@ struct Planner {
 
     Planner(const svt_bam* b, uint64_t rb) : bam(b), round_bytes(rb), start(b->first_record)
     {
-        for (const auto& ri : b->index)
-            for (uint64_t v : ri.linear)
-                if (v > b->first_record) cuts.push_back(v);
-        std::sort(cuts.begin(), cuts.end());
-        cuts.erase(std::unique(cuts.begin(), cuts.end()), cuts.end());
+        b->index.record_starts(b->first_record, cuts);       // (BAI: the linear offsets; CSI: loffsets and chunk begins)
     }
 
     uint32_t plan(Round& r)
@@ -1989,7 +1936,7 @@ int scan_libraries(const svt_bam* bam, uint32_t n_libs, const uint32_t* rg_count
         S.host_scan_s = seconds_since(t0);
         return SVT_OK;
     };
-    if (!bam->has_index) return host_answer(LW_NO_INDEX);
+    if (!bam->has_index()) return host_answer(LW_NO_INDEX);
     if (n_libs == 0) return SVT_OK;
     if (n_libs > kMaxLibs || n_rgs > kMaxReadGroups) return host_answer(LW_TABLES);
     std::vector<ew::NameRef> rgs;

@@ -157,6 +157,9 @@ def _lib():
         L.svt_bam_open.argtypes = [C.c_char_p, C.POINTER(C.c_void_p)]
         L.svt_bam_close.restype = None
         L.svt_bam_close.argtypes = [C.c_void_p]
+        if hasattr(L, "svt_bam_index_info"):       # (added under ABI 19: a library built before it lacks the symbol)
+            L.svt_bam_index_info.restype = C.c_int
+            L.svt_bam_index_info.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
         L.svt_bam_n_references.restype = C.c_int32
         L.svt_bam_n_references.argtypes = [C.c_void_p]
         L.svt_bam_reference_name.restype = C.c_char_p
@@ -274,6 +277,14 @@ class NativeBam:
 
     def gettid(self, name: str) -> int:
         return self._tid.get(name, -1)
+
+    def index_info(self) -> Dict[str, object]:
+        """svt_bam_index_info: which index the handle was opened with -- {"kind": "bai" | "csi", "min_shift", "depth"}"""
+        if not hasattr(self._L, "svt_bam_index_info"):
+            raise hip.SvtyperHipError("this libsvtyper_hip.so has no svt_bam_index_info (built before CSI indexes were read)")
+        kind, min_shift, depth = C.c_int(), C.c_int(), C.c_int()
+        hip._check(self._L.svt_bam_index_info(self._h, C.byref(kind), C.byref(min_shift), C.byref(depth)))
+        return {"kind": {1: "bai", 2: "csi"}[kind.value], "min_shift": min_shift.value, "depth": depth.value}
 
     def close(self):
         if self._h:
