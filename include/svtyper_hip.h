@@ -43,7 +43,8 @@ extern "C" {
  * used to return SVT_ERR_UNSUPPORTED for a batch of more than 256 libraries and now genotypes it.
  * svt_version() therefore does NOT tell a caller whether these additions are there: a library of the same number built
  * before them lacks the symbol.  Probe for it -- dlsym(handle, "svt_pack_evidence_flags") != NULL (in Python,
- * hasattr(lib, "svt_pack_evidence_flags")) -- and treat its presence as "packed evidence takes up to 65536 libraries".  */
+ * hasattr(lib, "svt_pack_evidence_flags")) -- and treat its presence as "packed evidence takes up to 65536 libraries".
+ * Added the same way, a symbol to probe for: svt_batch_verdicts (the per-record verdicts behind `svtyper -w`).            */
 #define SVT_ABI_VERSION 19
 
 /* ---- error codes (0 = ok, <0 = error; text via svt_last_error()) ---------- */
@@ -470,6 +471,31 @@ int svt_batch_create_from_fragments(const svt_fragment_batch* in, int device, un
  * `qual_out` (host) receives n_sites doubles.                                                  */
 int svt_batch_site_qual(svt_batch* b, uint32_t n_samples, const double* initial, double* qual_out,
                         uint64_t n_sites);
+
+/* ---- per-record verdicts: what `svtyper -w` needs from the device --------------------------------
+ * The reference's -w/--write_alignment dump tags the reads of a fragment XV:A:A or XV:A:R by p_concordant and the
+ * small-deletion gate (svtyper/classic.py:339-408, parsers.py:771-782,861-882), which this library evaluates on the
+ * device only.  svt_batch_verdicts writes one byte per canonical record of the resident batch to `out` (host memory,
+ * n_records bytes), in the batch's record order (rec_offset order; a batch created from segments counts as the joined
+ * array):
+ *
+ *   bit 0  the alt-straddle branch is taken (classic.py:359): SVT_REC_ALT_STRADDLE behind the small-deletion gate,
+ *          on a record with SVT_REC_HAS_PAIR
+ *   bit 1  that branch tags A: its p_alt > 0, p_alt = (1 - p_conc) * pm[mapq_a] * pm[mapq_b] for DEL and
+ *          pm[mapq_a] * pm[mapq_b] otherwise, pm = prob_mapq (pm[0] == 0.0); else it tags R
+ *   bit 2  the ref-straddle branch is taken (classic.py:398-401): (refA or refB) and (not (refA and refB) or DEL),
+ *          behind the same gate
+ *   bit 3  that branch tags A: p_conc is false (tag_span(1 - p_conc)); else R
+ *   bit 4  the record's non-soft-clip split candidate has p_alt > 0: (pm[seq_l] + pm[seq_r]) / 2 > 0 (classic.py:324,330)
+ *   bit 5  the same for its soft-clip candidate (clip_l, clip_r)
+ *   bits 6, 7 are 0.
+ *
+ * A record with SVT_REC_CONTINUATION carries bits 4 and 5 only; every record of a unit with SVT_UNIT_SKIP gets 0.
+ * The bytes do not depend on the table mode the batch's pass runs in.  The call may come before or after
+ * svt_batch_genotype and changes nothing in the batch: result records are the same bytes with and without it.
+ * SVT_ERR_INVALID: a batch of packed evidence (it has no canonical records), or n_records != rec_offset[n_units].
+ * Added without a new SVT_ABI_VERSION: probe for the symbol, as for svt_pack_evidence_flags.                        */
+int svt_batch_verdicts(svt_batch* b, uint8_t* out, uint64_t n_records);
 
 /* ---- host-side helper: result records -> text of VCF sample columns ---------------------------
  * The values the reference writes per sample (svtyper/classic.py:454-513, singlesample.py:207-227,

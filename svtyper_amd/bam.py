@@ -6,10 +6,12 @@ Only what SURVEY.md section 3.5 lists is implemented:
 
     AlignmentFile(path, 'rb'): filename, header['RG'], references, lengths, gettid(), fetch(),
                                count(read_callback='all'), mapped, unmapped, close()
+    AlignmentFile(path, 'wb', template=...): write(read), close() -- the evidence dump of `svtyper -w`: the template's
+                               header, every record without its sequence, BGZF through zlib
     AlignedSegment: query_name, flag and its bits, reference_id/name, reference_start (= pos),
                     reference_end, mapping_quality, template_length, cigar (= cigartuples),
                     has_tag/get_tag/set_tag, get_overlap, query_length, query_alignment_length,
-                    infer_query_length
+                    infer_query_length, query_sequence = None (the only value it takes)
 
 CRAM is not supported (the reference needs htslib + a reference FASTA for it).
 If a real pysam is importable, `open_alignment_file` prefers it.
@@ -118,17 +120,105 @@ class BgzfReader:
         return b"".join(out)
 
 
+BGZF_EOF = bytes.fromhex("1f8b08040000000000ff0600424302001b0003000000000000000000")      # the empty last member (SAM spec 4.1.2)
+_BGZF_PAYLOAD = 0xff00      # bytes of payload per member, htslib's block size: with its header a stored member stays within 64 KiB
+
+
+class BgzfWriter:
+    """A BGZF file written member by member through zlib: at most 65 280 bytes of payload each, its CRC32 and ISIZE behind
+    the deflate stream, the 28-byte empty member at the end.  (Readable by any BGZF reader; not the bytes htslib's deflate
+    would produce.)"""
+
+    def __init__(self, path: str, level: int = 6):
+        self._f = open(path, "wb")
+        self._level = level
+        self._buf = bytearray()
+
+    def write(self, data: bytes) -> None:
+        self._buf += data
+        while len(self._buf) >= _BGZF_PAYLOAD:
+            self._member(bytes(self._buf[:_BGZF_PAYLOAD]))
+            del self._buf[:_BGZF_PAYLOAD]
+
+    def write_record(self, data: bytes) -> None:
+        """`data` kept inside one member where it fits one"""
+        if self._buf and len(self._buf) + len(data) > _BGZF_PAYLOAD:
+            self.flush()
+        self.write(data)
+
+    def flush(self) -> None:
+        if self._buf:
+            self._member(bytes(self._buf))
+            del self._buf[:]
+
+    def _member(self, payload: bytes) -> None:
+        for level in (self._level, 0):      # (level 0 = stored: payload + 5 bytes per deflate block, always within a member)
+            z = zlib.compressobj(level, zlib.DEFLATED, -15)
+            cdata = z.compress(payload) + z.flush()
+            if len(cdata) + 26 <= 0x10000:
+                break
+        self._f.write(b"\x1f\x8b\x08\x04\0\0\0\0\0\xff\x06\0BC\x02\0" + struct.pack("<H", len(cdata) + 25) + cdata
+                      + struct.pack("<II", zlib.crc32(payload) & 0xFFFFFFFF, len(payload)))
+
+    def close(self) -> None:
+        if self._f is not None:
+            self.flush()
+            self._f.write(BGZF_EOF)
+            self._f.close()
+            self._f = None
+
+
+_TAG_SIZE = {"A": 1, "c": 1, "C": 1, "s": 2, "S": 2, "i": 4, "I": 4, "f": 4}
+
+
+def _without_tag(b: bytes, key: str) -> bytes:
+    """the tag area `b` without the fields named `key`"""
+    name = key.encode("ascii")
+    out = []
+    i, n = 0, len(b)
+    while i + 3 <= n:
+        t = chr(b[i + 2])
+        j = i + 3
+        if t in _TAG_SIZE:
+            j += _TAG_SIZE[t]
+        elif t in "ZH":
+            j = b.index(b"\0", j) + 1
+        elif t == "B":
+            j += 5 + struct.unpack_from("<I", b, j + 1)[0] * _TAG_SIZE[chr(b[j])]
+        else:
+            raise ValueError("unknown BAM tag type %r" % t)
+        if b[i:i + 2] != name:
+            out.append(b[i:j])
+        i = j
+    return b"".join(out)
+
+
+def _encode_tag(key: str, value) -> bytes:
+    name = key.encode("ascii")
+    if isinstance(value, str):
+        if len(value) == 1:
+            return name + b"A" + value.encode("ascii")
+        return name + b"Z" + value.encode("ascii") + b"\0"
+    if isinstance(value, float):
+        return name + b"f" + struct.pack("<f", value)
+    if isinstance(value, int):
+        return name + b"i" + struct.pack("<i", value)
+    raise TypeError("tag %s: a value of type %s is not written" % (key, type(value).__name__))
+
+
 class AlignedSegment:
     """One BAM record; attribute names follow pysam."""
 
     __slots__ = ("_file", "query_name", "flag", "reference_id", "reference_start", "mapping_quality",
                  "next_reference_id", "next_reference_start", "template_length", "cigar", "query_length",
-                 "_tagbytes", "_tags", "_ref_end", "_raw_seq")
+                 "_tagbytes", "_tags", "_ref_end", "_raw_seq", "_raw", "_set_tags")
 
     def __init__(self, afile, data: bytes):
         (ref_id, pos, l_read_name, mapq, _bin, n_cigar, flag, l_seq, next_ref, next_pos, tlen) = \
             struct.unpack_from("<iiBBHHHiiii", data, 0)
         self._file = afile
+        self._raw = data                 # the record as it lies in the file (behind block_size): what AlignmentFile.write starts from
+        self._set_tags = None            # the names set_tag was given, in the order of their last call
         self.reference_id = ref_id
         self.reference_start = pos
         self.mapping_quality = mapq
@@ -282,6 +372,21 @@ class AlignedSegment:
         if self._tags is None:
             self._parse_tags()
         self._tags[key] = value
+        if self._set_tags is None:
+            self._set_tags = []
+        elif key in self._set_tags:
+            self._set_tags.remove(key)
+        self._set_tags.append(key)
+
+    @property
+    def query_sequence(self):
+        """the reader never decodes the sequence; svtyper/utils.py:14 sets it to None before a read is written"""
+        return None
+
+    @query_sequence.setter
+    def query_sequence(self, value):
+        if value is not None:
+            raise NotImplementedError("query_sequence can only be set to None (the sequence is dropped on write)")
 
     def __repr__(self):
         return "<AlignedSegment %s flag=%d %s:%d mapq=%d>" % (
@@ -307,21 +412,34 @@ def _pseudo_bin(depth: int) -> int:
 class AlignmentFile:
     """BAM file opened for reading, with its .bai or .csi index when present."""
 
-    def __init__(self, path: str, mode: str = "rb", **kwargs):
+    def __init__(self, path: str, mode: str = "rb", template=None, **kwargs):
         if "c" in mode or path.endswith(".cram"):
             raise NotImplementedError("CRAM needs htslib; this reader handles BAM only")
         self.filename = path
+        self._writer = None
+        if mode.startswith("w"):
+            if mode != "wb":
+                raise NotImplementedError("only BAM output (mode 'wb') is written")
+            self._open_for_writing(path, kwargs.get("template", template))
+            return
         self._bgzf = BgzfReader(path, verify=bool(kwargs.get("verify", False)))
-        if self._bgzf.read(4) != b"BAM\1":
+        raw = []        # the header as it lies in the file: a file opened 'wb' with this one as template starts with these bytes
+
+        def read(n):
+            data = self._bgzf.read(n)
+            raw.append(data)
+            return data
+        if read(4) != b"BAM\1":
             raise IOError("%s is not a BAM file" % path)
-        l_text = struct.unpack("<i", self._bgzf.read(4))[0]
-        self.text = self._bgzf.read(l_text).split(b"\0", 1)[0].decode("ascii", "replace")
-        n_ref = struct.unpack("<i", self._bgzf.read(4))[0]
+        l_text = struct.unpack("<i", read(4))[0]
+        self.text = read(l_text).split(b"\0", 1)[0].decode("ascii", "replace")
+        n_ref = struct.unpack("<i", read(4))[0]
         refs, lens = [], []
         for _ in range(n_ref):
-            l_name = struct.unpack("<i", self._bgzf.read(4))[0]
-            refs.append(self._bgzf.read(l_name)[:-1].decode("ascii"))
-            lens.append(struct.unpack("<i", self._bgzf.read(4))[0])
+            l_name = struct.unpack("<i", read(4))[0]
+            refs.append(read(l_name)[:-1].decode("ascii"))
+            lens.append(struct.unpack("<i", read(4))[0])
+        self._header_bytes = b"".join(raw)
         self.references = tuple(refs)
         self.lengths = tuple(lens)
         self._tid = {r: i for i, r in enumerate(refs)}
@@ -497,7 +615,41 @@ class AlignmentFile:
         return self.references[tid]
 
     def close(self):
+        if self._writer is not None:
+            self._writer.close()
+            return
         self._bgzf.close()
+
+    # ---- writing (mode 'wb')
+    def _open_for_writing(self, path: str, template):
+        """pysam.AlignmentFile(path, 'wb', template): the template's header text and reference list, byte for byte."""
+        header = getattr(template, "_header_bytes", None)
+        if header is None:
+            raise TypeError("mode 'wb' needs template=: an AlignmentFile of this module opened for reading")
+        self.text, self.header = template.text, template.header
+        self.references, self.lengths = template.references, template.lengths
+        self._tid = dict(template._tid)
+        self._writer = BgzfWriter(path)
+        self._writer.write(header)
+        self._writer.flush()            # (records start in a block of their own, as htslib leaves them)
+
+    def write(self, read: AlignedSegment) -> None:
+        """One record behind the others: the record as it was read, without its sequence and qualities (l_seq = 0; `bin` stays
+        the original's), its tag area the original's without the names set_tag was given, those appended in the order they
+        were set.  A one-character string goes out as type A (XV:A:R, what `svtyper -w` sets), a longer one as Z, an int as i,
+        a float as f."""
+        if self._writer is None:
+            raise IOError("%s is not open for writing" % self.filename)
+        raw = read._raw
+        l_read_name, n_cigar = raw[8], struct.unpack_from("<H", raw, 12)[0]
+        body_end = 32 + l_read_name + 4 * n_cigar
+        tags = read._tagbytes
+        for key in read._set_tags or ():
+            tags = _without_tag(tags, key)
+        for key in read._set_tags or ():
+            tags += _encode_tag(key, read._tags[key])
+        rec = raw[:16] + b"\0\0\0\0" + raw[20:body_end] + tags
+        self._writer.write_record(struct.pack("<i", len(rec)) + rec)
 
     # ---- iteration
     def _next_record(self) -> Optional[AlignedSegment]:

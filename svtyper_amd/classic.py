@@ -184,10 +184,13 @@ class Classic(Driver):
 def sv_genotype(bam_string, vcf_in, vcf_out, min_aligned, split_weight, disc_weight, num_samp, lib_info_path,
                 debug, alignment_outpath, ref_fasta, sum_quals, max_reads, max_ci_dist, *, engine=None, geometry="host",
                 reader=None, stats=None, inflate="host", library_scan="host", verify="off"):
-    if alignment_outpath is not None:
-        raise NotImplementedError("-w/--write_alignment (evidence BAM dump) is outside the MI355X hot path build")
+    """`alignment_outpath` (-w): the reads that entered the tallies go to a BAM, tagged XV:A:R / XV:A:A as the reference tags them
+    (driver.tag_and_write; the tags that depend on p_concordant come from the device, svt_batch_verdicts).  Legal with
+    reader="python" (what reader=None then means) and geometry="host"; ValueError otherwise, and for an engine without
+    supports_verdicts."""
     run = Classic(bam_string, vcf_in, vcf_out, min_aligned, split_weight, disc_weight, num_samp, lib_info_path, debug, ref_fasta,
                   sum_quals, max_reads, max_ci_dist)
+    run.alignment_outpath = alignment_outpath
     return run.run(CHUNK_UNITS, engine=engine, geometry=geometry, reader=reader, stats=stats, inflate=inflate,
                    library_scan=library_scan, verify=verify)
 
@@ -216,6 +219,11 @@ def get_args():
 
 def main():
     args = get_args()
+    if args.alignment_outpath is not None:
+        if sharded.job() is not None:
+            raise ValueError(sharded.WRITE_ALIGNMENT_SHARDED)
+        if args.reader is None:
+            args.reader = "python"      # the reader that keeps the reads it tallied (sv_genotype: reader=None with -w)
     logging.basicConfig(format="%(message)s", level=logging.INFO if args.verbose else logging.WARNING)
     call = (args.bam, args.input_vcf, args.output_vcf, args.min_aligned, args.split_weight, args.disc_weight,
             args.num_samp, args.lib_info_path, args.debug, args.alignment_outpath, args.ref_fasta,

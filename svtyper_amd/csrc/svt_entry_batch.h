@@ -1,5 +1,5 @@
 // svt_entry_batch.h -- part of the single translation unit svtyper_hip.hip (included there, in order; not a stand-alone header):
-// C ABI: svt_version ... svt_batch_create* / genotype* / results / result order / device results / site QUAL.
+// C ABI: svt_version ... svt_batch_create* / genotype* / results / result order / device results / site QUAL / verdicts.
 
 
 int svt_version(void) { return SVT_ABI_VERSION; }
@@ -561,5 +561,44 @@ static int svt_batch_site_qual_impl(svt_batch* b, uint32_t n_samples, const doub
 int svt_batch_site_qual(svt_batch* b, uint32_t n_samples, const double* initial, double* qual_out, uint64_t n_sites)
 {
     return guarded([&] { return svt_batch_site_qual_impl(b, n_samples, initial, qual_out, n_sites); });
+}
+
+
+// svt_batch_verdicts (include/svtyper_hip.h): one launch of svt_verdict_kernel over the resident records on the batch's stream --
+// behind whatever pass is in flight there, which it neither waits on nor disturbs: it reads the records and the tables, and writes
+// scratch of its own that lives for this call.
+static int svt_batch_verdicts_impl(svt_batch* b, uint8_t* out, uint64_t n_records)
+{
+    if (!b || (!out && n_records)) return fail(SVT_ERR_INVALID, "null argument");
+    if (b->layout != kLayoutStream) return fail(SVT_ERR_INVALID, "svt_batch_verdicts: a batch of packed evidence has no canonical records to give verdicts on");
+    if (n_records != b->n_records) return fail(SVT_ERR_INVALID, "svt_batch_verdicts: n_records differs from the batch's rec_offset[n_units]");
+    if (!b->records_resident) return fail(SVT_ERR_STATE, "svt_batch_verdicts: the batch's records are not resident");
+    if (n_records == 0 || b->n_units == 0) return SVT_OK;
+    HIP_TRY(hipSetDevice(b->device));
+    DevScratch d_out;
+    SVT_TRY(d_out.alloc(n_records));
+    VerdictArgs a{};
+    a.records = static_cast<const uint4*>(b->d_records);
+    a.rec_offset = b->d_off;
+    a.units = b->d_units;
+    a.pm = b->d_pm;
+    a.wtab = b->d_wtab;
+    a.libs = b->d_libs;
+    a.bins = b->d_bins;
+    a.out = d_out.as<uint8_t>();
+    a.n_records = n_records;
+    a.n_units = (uint32_t)b->n_units;
+    a.n_libs = b->sargs.n_libs;
+    // a wavefront per unit and step; no more workgroups than a few rounds of the chip (grid-stride over the units)
+    const uint64_t wgs = (b->n_units + kVerdictBlock / kWave - 1) / (kVerdictBlock / kWave);
+    const dim3 grid((unsigned)std::min<uint64_t>(wgs, (uint64_t)cu_count(b->device) * 32u)), block(kVerdictBlock);
+    hipLaunchKernelGGL(svt_verdict_kernel, grid, block, 0, b->stream, a);
+    HIP_TRY(hipGetLastError());
+    return d2h_staged(out, d_out.p, n_records, b->stream);
+}
+
+int svt_batch_verdicts(svt_batch* b, uint8_t* out, uint64_t n_records)
+{
+    return guarded([&] { return svt_batch_verdicts_impl(b, out, n_records); });
 }
 

@@ -108,15 +108,14 @@ __device__ __forceinline__ void weight_evidence(const uint32_t wa, const uint32_
     }
 }
 
-// Paired-end evidence of one fragment (classic.py:339-408).
-//   o = ospan_len, mq = mapq_a | mapq_b << 8, f3 = alt | refA << 1 | refB << 2, lib = library index
-__device__ __forceinline__ void pair_evidence(const uint32_t o, const uint32_t mq, uint32_t f3,
-                                              const uint32_t lib_idx, const Tables& t, const LaneCtx& c, Acc& a)
+// The small-deletion gate (classic.py:339,383) and p_concordant (parsers.py:861-882) of one fragment's pair, for
+// pair_evidence below and for the verdicts of svt_verdict_kernel.h: f3 comes back 0 behind the gate, the return value is
+// p_concordant.
+//   o = ospan_len, f3 = alt | refA << 1 | refB << 2, lib_idx = library index
+__device__ __forceinline__ bool pair_gate_and_concordance(const uint32_t o, uint32_t& f3, const uint32_t lib_idx, const Tables& t,
+                                                          const LaneCtx& c)
 {
-    const double pm_a = t.pm[mq & 0xffu];
-    const double pm_b = t.pm[(mq >> 8) & 0xffu];
-
-    // p_concordant (parsers.py:861-882) as an integer test: with d1 = hist[o]/N fixed, the
+    // p_concordant as an integer test: with d1 = hist[o]/N fixed, the
     // reference's binary64 expression d1*0.95/(0.95*d1 + 0.05*d2) > 0.5 is monotone in
     // h2 = hist[o - v]; bins[o].thr is the largest h2 for which it still holds (found on the host
     // with the reference's own expression), -1 where hist[o] == 0 (p == 0 or ZeroDivisionError).
@@ -144,7 +143,17 @@ __device__ __forceinline__ void pair_evidence(const uint32_t o, const uint32_t m
         const bool in2 = ok2 && ((uint64_t)i2 < (uint64_t)lib.n_bins);
         h2 = t.bins[lib.tab_off + (in2 ? (uint32_t)i2 : lib.n_bins)].hist;
     }
-    const bool p_conc = (int32_t)h2 <= thr1;
+    return (int32_t)h2 <= thr1;
+}
+
+// Paired-end evidence of one fragment (classic.py:339-408).
+//   o = ospan_len, mq = mapq_a | mapq_b << 8, f3 = alt | refA << 1 | refB << 2, lib = library index
+__device__ __forceinline__ void pair_evidence(const uint32_t o, const uint32_t mq, uint32_t f3,
+                                              const uint32_t lib_idx, const Tables& t, const LaneCtx& c, Acc& a)
+{
+    const double pm_a = t.pm[mq & 0xffu];
+    const double pm_b = t.pm[(mq >> 8) & 0xffu];
+    const bool p_conc = pair_gate_and_concordance(o, f3, lib_idx, t, c);
     const PairWeights pw = t.wtab[f3 | (p_conc ? 8u : 0u) | c.del16];
     const double pp = pm_a * pm_b;
     a.alt_span += pp * pw.w_alt;

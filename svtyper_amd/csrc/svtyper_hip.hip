@@ -73,6 +73,7 @@
 #include "svt_library_kernel.h"
 #include "svt_library_arena.h"
 #include "svt_bayes_kernel.h"
+#include "svt_verdict_kernel.h"
 #include "svt_host_tables.h"
 #include "svt_host_transfer.h"
 

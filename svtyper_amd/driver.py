@@ -15,6 +15,7 @@ route, the `stats=` block.  What the reference's two programs do differently is 
              warn(text), gather(sample, bp, max_reads)      inside handle_line
              render_actions(results, actions)               results -> the text of every output action
              finish(unpaired)             the end of a run
+    data     alignment_outpath            (`svtyper -w`) the evidence dump: tag_and_write below, per chunk, in output order
 
 No method takes a flag that names its caller, and a driver's hooks run per line handed to the per-line route and per
 block, never per site of the bulk route (`BulkFeeder._block` / `_write_block`).
@@ -26,17 +27,76 @@ import os
 import sys
 from itertools import chain
 
-from .bam import open_alignment_file
+from .bam import AlignmentFile, open_alignment_file
 from .library import setup_sample
 from .pipeline import (MIN_LIB_PREVALENCE, BulkFeeder, ChunkPipeline, NativeUnitCollector, UnitCollector, check_inflate,
                        check_library_scan, check_verify, default_engine, resolve_reader, split_lines, verify_stats)
 from .vcf import Variant, Vcf
 
 
+# (breakpoint, sample) units per device batch of a run that writes the evidence dump (`svtyper -w`): every read object of a
+# chunk stays alive until the chunk's verdicts are back, and ChunkPipeline keeps up to three chunks in flight.  A memory bound,
+# not a measured optimum: 1 000 units of a few hundred reads each, a kilobyte or two per read object with its raw record, are a
+# few hundred MB per chunk at the worst.
+WRITE_CHUNK_UNITS = 1_000
+
+
+def tag_and_write(evidence, out_bam, written: set) -> None:
+    """The reads `svtyper -w` writes for the units of one chunk, tagged as the reference tags them (classic.py:296-413,
+    parsers.py:771-782,1218-1228, utils.py:13-22).  `evidence`: per unit, in output order, None (a unit skipped by --max_reads, or
+    one without reads) or (fragments, [packer.FragmentSpan], verdict bytes of the unit's records): is_ref_seq comes from the side
+    table -- ungated, a hit with MAPQ 0 counts --, everything that depends on p_concordant, the small-deletion gate or a
+    weight from the device (svt_batch_verdicts, bits 0-5).  `written`: the (query_name, flag) set of the whole run."""
+    for unit in evidence:
+        if unit is None:
+            continue
+        fragments, spans, verdicts = unit
+        for span in spans:                                      # classic.py:296: sorted(query_name)
+            fragment = fragments[span.name]
+            first = int(verdicts[span.first])
+            write_fragment = False
+            for read, hit in zip(fragment.primary_reads, span.ref_hits):     # classic.py:306-314
+                if hit:
+                    read.set_tag("XV", "R")
+                    write_fragment = True
+            alt_split = set()                                   # classic.py:330: the candidates with p_alt > 0
+            for k, split in enumerate(span.seq):
+                if verdicts[span.first + k] & 16:
+                    alt_split.add(id(split))
+            for k, split in enumerate(span.clip):
+                if verdicts[span.first + k] & 32:
+                    alt_split.add(id(split))
+            for split in fragment.split_reads:                  # classic.py:317-332
+                if id(split) in alt_split:
+                    split.read.set_tag("XV", "A")               # tag_split(p_alt > 0)
+                    write_fragment = True
+            if first & 1:                                       # classic.py:359-380: tag_span(p_alt)
+                _tag_span(fragment, "A" if first & 2 else "R")
+                write_fragment = True
+            if first & 4:                                       # classic.py:398-408: tag_span(1 - p_conc)
+                _tag_span(fragment, "A" if first & 8 else "R")
+                write_fragment = True
+            if write_fragment:                                  # classic.py:411-413
+                for read in fragment.primary_reads + [split.read for split in fragment.split_reads]:
+                    read.query_sequence = None                  # utils.py:13-22
+                    key = (read.query_name, read.flag)
+                    if key not in written:
+                        out_bam.write(read)
+                        written.add(key)
+
+
+def _tag_span(fragment, value: str) -> None:
+    """parsers.py:771-782: the primary reads that carry no XV yet"""
+    for read in fragment.primary_reads:
+        if not read.has_tag("XV"):
+            read.set_tag("XV", value)
+
+
 class Driver:
     flags = 0
     site_quals = False
     bulk_under_debug = True
+    alignment_outpath = None            # (`svtyper -w`; classic.Classic sets it)
 
     def __init__(self, bam_string, vcf_in, vcf_out, min_aligned, split_weight, disc_weight, num_samp, lib_info_path, debug,
                  ref_fasta, sum_quals, max_reads, max_ci_dist, n_threads=0):
@@ -49,14 +109,22 @@ class Driver:
 
     def run(self, chunk_units, engine=None, geometry="host", reader=None, stats=None, inflate="host", library_scan="host",
             verify="off"):
+        writing = self.alignment_outpath is not None
+        if writing and reader is None:
+            reader = "python"           # the one route that keeps the reads it tallied
         reader = resolve_reader(reader)
+        if writing:
+            self.check_write_alignment(reader, geometry, engine)
+            chunk_units = min(chunk_units, WRITE_CHUNK_UNITS)
         check_inflate(reader, inflate)
         check_library_scan(reader, library_scan)
         verify_on = check_verify(verify)
         paths, bams = [], []
         for path in self.alignment_paths():
             paths.append(path)
-            bams.append(open_alignment_file(path, self.ref_fasta, verify=verify_on))
+            # (`-w` writes the records the built-in reader keeps the raw bytes of)
+            bams.append(AlignmentFile(path, "rb", verify=verify_on) if writing and path.endswith(".bam")
+                        else open_alignment_file(path, self.ref_fasta, verify=verify_on))
         lib_info = self.read_library_file()
         if self.vcf_in is None:     # classic.py:142-143 (sso_genotype does not get here without a VCF)
             sys.stderr.write("Warning: VCF not found.\n")
@@ -69,10 +137,35 @@ class Driver:
         scan_device = getattr(engine, "device", 0) if library_scan == "device" else 0
         self.samples = [setup_sample(b, lib_info, self.num_samp, MIN_LIB_PREVALENCE, nb, library_scan, scan_device, inflate)
                         for b, nb in zip(bams, native or [None] * len(bams))]
+        out_bam, written = None, set()
+        if writing:     # classic.py:161-166: the first alignment file is the template, its header is the dump's
+            template = AlignmentFile(paths[0], "rb")
+            out_bam = AlignmentFile(self.alignment_outpath, "wb", template=template)
+            template.close()
         self.write_library_file()
         if self.vcf_in is None:
+            if out_bam is not None:     # classic.py:177-180
+                out_bam.close()
             return
+        try:
+            self._run_body(chunk_units, engine, geometry, reader, stats, inflate, native, bams, out_bam, written)
+        finally:
+            if out_bam is not None:     # classic.py:527-531
+                out_bam.close()
 
+    def check_write_alignment(self, reader, geometry, engine):
+        """`-w` needs the reads of a chunk alive when its verdicts come back, canonical records to give verdicts on, and an
+        engine that gives them."""
+        if reader != "python":
+            raise ValueError("-w/--write_alignment needs reader='python': reader=%r keeps no reads to write" % (reader,))
+        if geometry == "device":
+            raise ValueError("-w/--write_alignment needs geometry='host': with geometry='device' there are no canonical records on "
+                             "the host to match the verdicts to")
+        if engine is not None and not getattr(engine, "supports_verdicts", False):
+            raise ValueError("-w/--write_alignment needs an engine with supports_verdicts (per-record verdicts beside the results)")
+
+    def _run_body(self, chunk_units, engine, geometry, reader, stats, inflate, native, bams, out_bam, written):
+        writing = out_bam is not None
         if engine is None:
             engine = default_engine()
         self.vcf = Vcf()
@@ -82,7 +175,8 @@ class Driver:
                                             geometry="walk" if reader == "device" else "device" if geometry == "device" else "reader",
                                             inflate=inflate)
         elif reader == "python":
-            collector = UnitCollector(self.samples, self.split_weight, self.disc_weight, self.min_aligned, geometry)
+            collector = UnitCollector(self.samples, self.split_weight, self.disc_weight, self.min_aligned, geometry,
+                                      keep_reads=writing)
         else:
             raise ValueError("reader must be 'python', 'native' or 'device'")
         self.collector, self.native_sites = collector, native is not None
@@ -98,6 +192,8 @@ class Driver:
             pipe.submit(collector.take(engine, self.flags, site_quals=quals), lambda results: write_out(results, actions))
 
         def write_out(results, actions):
+            if writing:
+                tag_and_write(results.evidence, out_bam, written)
             for text in self.render_actions(results, actions):
                 write(text)
 
@@ -207,7 +303,7 @@ def parse_arguments(p, bam_help, max_reads, own):
     p.add_argument("--debug", action="store_true", help=argparse.SUPPRESS)
     own(p)
     # not in the reference: where the host work runs (same output bytes either way)
-    p.add_argument("--reader", choices=("python", "native", "device"), default="native",
+    p.add_argument("--reader", choices=("python", "native", "device"), default=None,
                    help="BAM access + fragment assembly: the C++ threads of libsvtyper_hip.so feeding the device "
                         "geometry stage, the same with the evidence records built on the GPU (device), or the portable Python "
                         "reader (same output bytes) [native]")
@@ -234,7 +330,7 @@ def run_main(driver, sharded_driver, call, args):
     from . import sharded
     if args.split_bam is not None:
         sys.stderr.write("Warning: --split_bam (-S) is deprecated. Ignoring %s.\n" % args.split_bam)
-    options = dict(geometry=args.geometry, reader=args.reader, inflate=args.inflate, library_scan=args.library_scan,
+    options = dict(geometry=args.geometry, reader=args.reader or "native", inflate=args.inflate, library_scan=args.library_scan,
                    verify="crc32" if args.verify_bgzf else "off")
     job = sharded.job()
     if job is None:

@@ -293,6 +293,8 @@ class Results:
     def __init__(self, rec: np.ndarray):
         self.rec = np.ascontiguousarray(rec, dtype=RESULT_DTYPE)
         self.site_qual = None   # float64 [n_sites] when the engine also accumulated QUAL over the samples
+        self.evidence = None    # (pipeline.UnitCollector(keep_reads=True)) per unit what driver.tag_and_write takes
+        self.verdicts = None    # uint8 [n_records] when the engine was asked for them (svt_batch_verdicts: what `svtyper -w` tags by)
 
     @classmethod
     def empty(cls, n: int) -> "Results":

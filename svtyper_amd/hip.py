@@ -26,7 +26,7 @@ EXPORTS = (
     "svt_batch_stream", "svt_batch_destroy", "svt_trim", "svt_bayes_gt", "svt_genotype_counts", "svt_genotype", "svt_genotype_multi", "svt_shard_bounds",
     "svt_pinned_alloc", "svt_pinned_free", "svt_pack_evidence", "svt_pack_evidence_flags", "svt_packed_free", "svt_batch_create_packed", "svt_genotype_packed",
     "svt_format_results", "svt_format_free", "svt_results_host_sq", "svt_batch_result_bytes", "svt_batch_result_slots", "svt_results_expand96",
-    "svt_genotype_packed_from_records", "svt_chunk_bounds",
+    "svt_genotype_packed_from_records", "svt_chunk_bounds", "svt_batch_verdicts",
 )
 
 _lib: Optional[C.CDLL] = None
@@ -138,6 +138,9 @@ def load() -> C.CDLL:
     L.svt_genotype_counts.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_double, C.c_double, C.c_void_p, C.c_int]
     L.svt_genotype.restype = C.c_int
     L.svt_genotype.argtypes = [C.POINTER(CEvidenceBatch), C.c_void_p, C.c_int, C.c_uint]
+    if hasattr(L, "svt_batch_verdicts"):      # (added without a new ABI number: a library built before it lacks the symbol)
+        L.svt_batch_verdicts.restype = C.c_int
+        L.svt_batch_verdicts.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64]
     if L.svt_version() != ABI_VERSION:
         raise SvtyperHipError("ABI mismatch: library %d, binding %d" % (L.svt_version(), ABI_VERSION))
     _lib = L
@@ -405,6 +408,16 @@ class DeviceBatch:
         gives one in page-locked memory, which the records reach by straight DMA."""
         out = Results.empty(self.n_units) if out is None else _check_out(out, self.n_units)
         _check(self._lib.svt_batch_results(self._h, C.c_void_p(out.ptr()), self.n_units))
+        return out
+
+    def verdicts(self) -> np.ndarray:
+        """svt_batch_verdicts: one byte per canonical record of the batch, in record order -- which of the reference's tagging
+        branches the record's fragment takes and the XV tag each sets (bits 0-5: include/svtyper_hip.h).  What `svtyper -w`
+        needs from the device; legal before or after genotype(), and the result records do not change by it."""
+        if not hasattr(self._lib, "svt_batch_verdicts"):
+            raise SvtyperHipError("this libsvtyper_hip.so has no svt_batch_verdicts (built before it was added): rebuild it")
+        out = np.zeros(self.n_records, np.uint8)
+        _check(self._lib.svt_batch_verdicts(self._h, C.c_void_p(out.ctypes.data) if out.size else None, self.n_records))
         return out
 
     def result_order(self, n_samples: int):

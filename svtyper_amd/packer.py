@@ -15,6 +15,7 @@ the device.
 """
 from __future__ import annotations
 
+from collections import namedtuple
 from typing import Dict, List, Optional, Sequence
 
 import numpy as np
@@ -40,9 +41,19 @@ def _clamp32(x) -> int:
     return int(min(max(int(x), _I32_MIN), _I32_MAX))
 
 
+# One fragment of a unit's side table (pack_fragments(..., side_table=True)): what `svtyper -w` needs beside the records to
+# tag and write the fragment's reads once the device's verdicts are back (driver.tag_and_write).
+#   name          query name (the key into the unit's fragments)
+#   first, count  the fragment's records are [first, first + count) of the unit's
+#   ref_hits      per primary read: is_ref_seq at A or B, UNGATED -- a hit with MAPQ 0 still tags the read R and writes the
+#                 fragment (classic.py:309-314), which the record cannot show: its gated MAPQ byte is 0 either way
+#   seq, clip     the split objects behind the seq_l/seq_r (clip_l/clip_r) bytes of record first + k, k = 0, 1, ...
+FragmentSpan = namedtuple("FragmentSpan", "name first count ref_hits seq clip")
+
+
 def pack_fragments(fragments: Dict[str, object], breakpoint: dict, lib_index: Dict[int, int],
-                   min_aligned: int, split_slop: int) -> np.ndarray:
-    """Evidence records of one unit.
+                   min_aligned: int, split_slop: int, side_table: bool = False):
+    """Evidence records of one unit; with `side_table` the pair (records, [FragmentSpan per fragment, in record order]).
 
     fragments : {query_name: SamFragment-like}
     breakpoint: {'svtype', optional 'var_length', 'A': {chrom,pos,ci,is_reverse}, 'B': {...}}
@@ -56,6 +67,7 @@ def pack_fragments(fragments: Dict[str, object], breakpoint: dict, lib_index: Di
     svtype = breakpoint["svtype"]
     zero_ci = [0, 0]
     rows: List[tuple] = []
+    spans: List[FragmentSpan] = []
 
     for name in sorted(fragments.keys()):                       # classic.py:296
         frag = fragments[name]
@@ -63,20 +75,23 @@ def pack_fragments(fragments: Dict[str, object], breakpoint: dict, lib_index: Di
         base_flags = lib << ev.REC_LIB_SHIFT
 
         # ---- gated MAPQs of the primary reads (classic.py:306-311)
-        rs = []
+        rs, hits = [], []
         for read in frag.primary_reads:
             hit = (frag.is_ref_seq(read, None, chromA, posA, ciA, min_aligned)
                    or frag.is_ref_seq(read, None, chromB, posB, ciB, min_aligned))
             rs.append(_mapq(read.mapping_quality) if hit else 0)
+            hits.append(bool(hit))
 
         # ---- gated MAPQs of the split candidates (classic.py:317-328)
         seq, clip = [], []
+        seq_splits, clip_splits = [], []
         for split in frag.split_reads:
             left, right = split.is_split_straddle(chromA, posA, ciA, chromB, posB, ciB, o1, o2,
                                                   svtype, split_slop)
             pair = (_mapq(split.query_left.mapping_quality) if left else 0,
                     _mapq(split.query_right.mapping_quality) if right else 0)
             (clip if split.is_soft_clip else seq).append(pair)
+            (clip_splits if split.is_soft_clip else seq_splits).append(split)
 
         # ---- paired-end bits (classic.py:339-396), WITHOUT the small-deletion gate
         flags = base_flags
@@ -110,6 +125,8 @@ def pack_fragments(fragments: Dict[str, object], breakpoint: dict, lib_index: Di
         # ---- emit: first record carries the pair; extra primaries / same-kind candidates go into
         # continuation records (only the sso association distinguishes them)
         n_rec = max(1, (len(rs) + 1) // 2, len(seq), len(clip))
+        if side_table:
+            spans.append(FragmentSpan(name, len(rows), n_rec, hits, seq_splits, clip_splits))
         for k in range(n_rec):
             ra = rs[2 * k] if 2 * k < len(rs) else 0
             rb = rs[2 * k + 1] if 2 * k + 1 < len(rs) else 0
@@ -125,7 +142,7 @@ def pack_fragments(fragments: Dict[str, object], breakpoint: dict, lib_index: Di
         arr = np.array(rows, dtype=np.int64)
         for i, name in enumerate(RECORD_DTYPE.names):
             rec[name] = arr[:, i]
-    return rec
+    return (rec, spans) if side_table else rec
 
 
 def unit_header(breakpoint: dict, sample_index: int = 0, skip: bool = False, libs: int = 0) -> np.ndarray:

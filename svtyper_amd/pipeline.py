@@ -39,9 +39,12 @@ _READER_TURN = threading.Lock()   # svt_bam_summarise starts a pool of threads t
 class HipEngine:
     """EvidenceBatch -> Results on one MI355X through the C ABI (include/svtyper_hip.h)."""
 
-    def __init__(self, device: int = 0):
+    def __init__(self, device: int = 0, verdicts: bool = False):
+        """`verdicts`: every call also asks the resident batch for its per-record verdicts (svt_batch_verdicts) and puts them
+        beside the records as Results.verdicts -- what `svtyper -w` tags its reads by.  Off, nothing new is launched or allocated."""
         from . import hip
         hip.load()   # raises if libsvtyper_hip.so is missing
+        self.verdicts = bool(verdicts)
         if hip.device_count() <= device:
             raise hip.SvtyperHipError(
                 "no MI355X visible as device %d: svtyper_amd has no CPU fallback for the likelihood path" % device)
@@ -59,7 +62,20 @@ class HipEngine:
     # 16 bytes per fragment on the host
     accepts_sample_major = True
 
-    def __call__(self, batch: EvidenceBatch, flags: int = 0, site_qual=None, sample_major: int = 0) -> Results:
+    # `verdicts=True` (per call, or for every call from the constructor): Results.verdicts, one byte per record of the batch
+    supports_verdicts = True
+
+    def __call__(self, batch: EvidenceBatch, flags: int = 0, site_qual=None, sample_major: int = 0, verdicts=None) -> Results:
+        if self.verdicts if verdicts is None else verdicts:
+            if sample_major > 1:
+                raise ValueError("verdicts are in the batch's record order: not with sample_major")
+            with self._hip.DeviceBatch(batch, self.device, flags) as d:      # the resident route: the pass, then the verdict kernel
+                d.genotype(sync=True)
+                res = self._hip.host_sq(d.results())
+                res.verdicts = d.verdicts()
+            if site_qual is not None:
+                res.site_qual = self._hip.site_qual_host(res, site_qual[0], site_qual[1])
+            return res
         if sample_major > 1:
             from .evidence import SegmentedBatch
             make = self._hip.DeviceBatch.from_segments if isinstance(batch, SegmentedBatch) else self._hip.DeviceBatch
@@ -206,13 +222,21 @@ class UnitCollector:
 
     geometry="host":   fragments -> evidence records here (packer.py), likelihood on the device;
     geometry="device": fragments -> breakpoint-independent summaries here (geometry.py), predicates
-                       and likelihood on the device (needs an engine with genotype_fragments)."""
+                       and likelihood on the device (needs an engine with genotype_fragments).
+
+    keep_reads (`svtyper -w`, geometry="host"): the fragments of every unit and the packer's side table stay with the chunk, the
+    engine is asked for the verdicts of every batch (engine(..., verdicts=True) -> Results.verdicts), and the job's Results
+    carry `evidence`: per unit, in add() order, None or (fragments, side table, the verdict bytes of the unit's records) --
+    what driver.tag_and_write takes.  With several library groups the verdicts of each group's batch go back to its units."""
 
     def __init__(self, samples: List[Sample], split_weight: float, disc_weight: float, min_aligned: int,
-                 geometry: str = "host"):
+                 geometry: str = "host", keep_reads: bool = False):
         if geometry not in ("host", "device"):
             raise ValueError("geometry must be 'host' or 'device'")
+        if keep_reads and geometry != "host":
+            raise ValueError("keep_reads needs geometry='host' (canonical records on the host)")
         self.geometry = geometry
+        self.keep_reads = keep_reads
         self.samples = samples
         self.min_aligned = min_aligned
         self.split_weight = split_weight
@@ -226,6 +250,7 @@ class UnitCollector:
     def _reset(self):
         self.builders = [self._new_builder(tables) for tables in self.group_tables]
         self.slots: List[List[int]] = [[] for _ in self.groups]      # per group: where its units go in the order they were added
+        self.kept: List[list] = [[] for _ in self.groups]            # keep_reads, per group and unit: None or (fragments, side table)
         self.n_units = 0
 
     def _new_builder(self, tables):
@@ -246,10 +271,15 @@ class UnitCollector:
             self.builders[g].add(breakpoint_record(breakpoint, tid_of, sample_index, skip, self.sample_libs[sample_index]), frs)
         else:
             unit = unit_header(breakpoint, sample_index, skip, self.sample_libs[sample_index])
-            recs = None
+            recs = kept = None
             if fragments and not skip:
-                recs = pack_fragments(fragments, breakpoint, self.lib_index, self.min_aligned, SPLIT_SLOP)
+                recs = pack_fragments(fragments, breakpoint, self.lib_index, self.min_aligned, SPLIT_SLOP, side_table=self.keep_reads)
+                if self.keep_reads:
+                    recs, spans = recs
+                    kept = (fragments, spans)
             self.builders[g].add(unit, recs)
+            if self.keep_reads:
+                self.kept[g].append(kept)
         self.slots[g].append(self.n_units)
         self.n_units += 1
         return self.n_units - 1
@@ -262,12 +292,15 @@ class UnitCollector:
         empty again and can be filled while the job runs on another thread (ChunkPipeline).  `site_quals`
         (incoming QUAL of every site, units site-major over self.samples) asks an engine that can for
         Results.site_qual."""
-        builders, slots, n_units = self.builders, self.slots, self.n_units
+        builders, slots, kept, n_units = self.builders, self.slots, self.kept, self.n_units
         self._reset()
         geometry = self.geometry
+        keep_reads = self.keep_reads
         kw = _site_qual_kw(engine, len(self.samples), site_quals)
+        if keep_reads and not getattr(engine, "supports_verdicts", False):
+            raise TypeError("keep_reads needs an engine with supports_verdicts")
 
-        def run_one(builder, **kw) -> Results:
+        def run_one(builder, group: int, evidence: list, **kw) -> Results:
             batch = builder.build()
             if batch.n_units == 0:
                 return Results.empty(0)
@@ -275,17 +308,31 @@ class UnitCollector:
                 if not hasattr(engine, "genotype_fragments"):
                     raise TypeError("geometry='device' needs an engine with genotype_fragments (the HIP engine)")
                 return engine.genotype_fragments(batch, flags, **kw)
-            return engine(batch, flags, **kw)
+            if not keep_reads:
+                return engine(batch, flags, **kw)
+            res = engine(batch, flags, verdicts=True, **kw)
+            if res.verdicts is None or len(res.verdicts) != batch.n_records:
+                raise RuntimeError("the engine returned no verdicts for the batch's %d records" % batch.n_records)
+            off = batch.rec_offset.tolist()      # the verdicts of the group's batch go back to its units
+            for k, (where, unit) in enumerate(zip(slots[group], kept[group])):
+                if unit is not None:
+                    evidence[where] = (unit[0], unit[1], res.verdicts[off[k]:off[k + 1]])
+            return res
 
         def job() -> Results:
+            evidence = [None] * n_units
             if len(builders) == 1:
-                return run_one(builders[0], **kw)
-            import numpy as np
-            out = Results.empty(n_units)
-            for builder, where in zip(builders, slots):      # one device batch per group of samples, results back in add() order
-                if where:
-                    out.rec[np.asarray(where, dtype=np.int64)] = run_one(builder).rec
-            return _with_site_qual(out, kw)
+                out = run_one(builders[0], 0, evidence, **kw)
+            else:
+                import numpy as np
+                out = Results.empty(n_units)
+                for g, (builder, where) in enumerate(zip(builders, slots)):      # one device batch per group of samples, results back in add() order
+                    if where:
+                        out.rec[np.asarray(where, dtype=np.int64)] = run_one(builder, g, evidence).rec
+                out = _with_site_qual(out, kw)
+            if keep_reads:
+                out.evidence = evidence
+            return out
         return job
 
     def run(self, engine: Engine, flags: int) -> Results:

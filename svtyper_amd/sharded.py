@@ -254,9 +254,15 @@ def finish() -> None:
         dist.destroy_process_group()
 
 
+WRITE_ALIGNMENT_SHARDED = ("-w/--write_alignment is not available under torch.distributed.run: every rank would write the same "
+                           "file; run the dump in one process")
+
+
 def sv_genotype_sharded(bam_string, vcf_in, vcf_out, *rest, rank: int, world: int, **kw) -> None:
-    """classic.sv_genotype's arguments (lib_info_path is the 8th positional) plus rank / world."""
+    """classic.sv_genotype's arguments (lib_info_path is the 8th positional, alignment_outpath the 10th) plus rank / world."""
     from .classic import sv_genotype
+    if len(rest) > 6 and rest[6] is not None:
+        raise ValueError(WRITE_ALIGNMENT_SHARDED)
     run_sharded(sv_genotype, bam_string, vcf_in, vcf_out, *rest, rank=rank, world=world, lib_info_index=4, **kw)
 
 
