@@ -15,6 +15,9 @@ Outputs (committed; the reference itself never travels):
   geometry_edges.json.gz the boundary lattice of tests/geomcases.py (fragments on both sides of every threshold
                          of the geometry predicates), in the format of fake_sites plus the number of records
                          of each fragment
+  concordance_edges.json.gz  (tests/golden/make_golden_concordance.py) SamFragment.p_concordant on the lattice of
+                         tests/concordcases.py: histograms at the edges of the device's threshold tables, the points asked
+                         and the reference's booleans
 
 Floats are stored as float.hex() strings so they round-trip bit-exactly.
 """

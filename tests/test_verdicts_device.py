@@ -1,7 +1,8 @@
 """GPU: the bytes of svt_verdict_kernel (svt_batch_verdicts, DeviceBatch.verdicts()) against the Python restatement of the six
 bits (tests/verdictcases.py: restate, after svtyper/classic.py:317-408 with oracle.py_oracle.p_concordant) -- byte for byte, so no
-tolerance: every bit is a comparison the reference makes, and the device's integer test for p_concordant is exact by construction
-(svt_host_tables.h).  Over the 211 fixture units, the boundary lattice of the geometry predicates and a synthetic batch of 300
+tolerance: every bit is a comparison the reference makes, and the device's integer test for p_concordant (svt_host_tables.h) is
+held to the reference point by point on the lattice of tests/concordcases.py (test_concordance_host.py, test_concordance_device.py:
+the same bytes there on histograms in exact ratio 19 : 1, at the caps and at the limits of the tables).  Over the 211 fixture units, the boundary lattice of the geometry predicates and a synthetic batch of 300
 libraries with DEL units on both sides of 2 sd, non-DEL units whose float Counter key is and is not integral, spans in the
 sentinel bin, units of 0, 1, 63, 64, 65 and 129 records (a wavefront strides over a unit's records by 64), an empty first and
 last unit and a skipped one."""
