@@ -44,7 +44,9 @@ extern "C" {
  * svt_version() therefore does NOT tell a caller whether these additions are there: a library of the same number built
  * before them lacks the symbol.  Probe for it -- dlsym(handle, "svt_pack_evidence_flags") != NULL (in Python,
  * hasattr(lib, "svt_pack_evidence_flags")) -- and treat its presence as "packed evidence takes up to 65536 libraries".
- * Added the same way, a symbol to probe for: svt_batch_verdicts (the per-record verdicts behind `svtyper -w`).            */
+ * Added the same way, symbols to probe for: svt_batch_verdicts (the per-record verdicts behind `svtyper -w`) and
+ * svt_bam_evidence_device_dump with svt_bam_evidence_dump_walk_host / svt_evidence_dump_free (include/svtyper_reads.h: the
+ * reads `svtyper -w` writes, built on the GPU behind the device reader).                                                */
 #define SVT_ABI_VERSION 19
 
 /* ---- error codes (0 = ok, <0 = error; text via svt_last_error()) ---------- */

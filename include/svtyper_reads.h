@@ -277,6 +277,44 @@ int svt_bam_evidence_device_inflate(const svt_bam* bam, const svt_summarise_args
                                     uint8_t* skipped, svt_evidence_device_stats* stats, svt_evidence_inflate_stats* istats,
                                     int count_host_blocks);
 
+/* ---- the evidence dump of `svtyper -w` from the device reader (added under ABI 19 without a new number, like
+ * svt_batch_verdicts: a library built before it lacks the symbols -- probe for svt_bam_evidence_device_dump) ----
+ * The reads the reference writes to its -w BAM, as finished BAM records (block_size first; l_seq = 0, no sequence, no
+ * qualities, XV:A:R|A set as classic.py:296-413 sets it), built where the alignment records already lie: the walk
+ * (svt_evidence_walk.h) leaves one source row per evidence record, svtyper_amd/csrc/svt_dump_rules.h turns verdict bytes
+ * (svt_batch_verdicts) + source rows + arena into the records, unit after unit, inside a unit fragment after fragment in
+ * record order, inside a fragment its primary reads in arrival order.  The run-wide (query_name, flag) set stays the caller's.
+ * Owned by the library: release with svt_evidence_dump_free.                                                          */
+typedef struct svt_evidence_dump {
+    uint8_t* bytes;               /* unit_offset[n_units] bytes                                                        */
+    uint64_t* unit_offset;        /* n_units + 1: unit u's records are bytes[unit_offset[u] .. unit_offset[u + 1])     */
+    uint8_t* unit_host;           /* n_units: 1 = this unit's reads must come from elsewhere (it was recomputed by the
+                                     host reader, or it lies outside the dump's envelope); it has no bytes             */
+    uint64_t n_bytes, n_reads;    /* bytes and records written                                                         */
+    uint64_t units_dumped;        /* units with bytes                                                                  */
+    uint64_t units_host;          /* units with unit_host = 1 ...                                                      */
+    uint64_t units_outside_dump;  /* ... of them inside the walk's envelope and outside the dump's                     */
+    double dump_s;                /* host-observed: the verdict kernel, both dump launches, the bytes' arrival         */
+} svt_evidence_dump;
+void svt_evidence_dump_free(svt_evidence_dump* d);
+
+/* svt_bam_evidence_device_dump: svt_bam_evidence_device (inflate_on_device == 0; istats and count_host_blocks are ignored)
+ * or svt_bam_evidence_device_inflate (!= 0) -- the same resident batch `*out` --, and behind it, on the call's stream,
+ * svt_verdict_kernel over the new batch (its bytes stay in HBM) and the two launches of svt_dump_kernel.h.  The two
+ * entries above launch and allocate nothing of this.                                                                  */
+int svt_bam_evidence_device_dump(const svt_bam* bam, const svt_summarise_args* args, const svt_evidence_params* geometry,
+                                 const svt_evidence_batch* header, int device, unsigned flags, svt_batch** out,
+                                 uint8_t* skipped, svt_evidence_device_stats* stats, svt_evidence_inflate_stats* istats,
+                                 int count_host_blocks, int inflate_on_device, svt_evidence_dump* dump);
+
+/* The same with no GPU: svt_bam_evidence_walk_host with source rows, plus the dump rules on one lane.  There is no host
+ * implementation of the verdicts: `verdicts` are handed IN, one byte per record in the record order of
+ * svt_bam_evidence_walk_host on the same arguments (n_verdicts = its rec_offset[n_units]).  `out` / `out_of_envelope` are
+ * svt_bam_evidence_walk_host's.  A unit outside the walk's or the dump's envelope has unit_host = 1 and no bytes.        */
+int svt_bam_evidence_dump_walk_host(const svt_bam* bam, const svt_summarise_args* args, const svt_evidence_params* geometry,
+                                    const uint8_t* verdicts, uint64_t n_verdicts, svt_evidence* out, uint8_t* out_of_envelope,
+                                    svt_evidence_dump* dump);
+
 /* Library statistics straight from the BAM (svtyper/parsers.py:501-576): what Library.from_bam scans
  * for, for ONE library given as its read-group ids, in three passes from the first record each --
  *   read_length : max query length (M/I/S/=/X) over the library's reads until 10 001 of them were seen

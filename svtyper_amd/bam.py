@@ -651,6 +651,15 @@ class AlignmentFile:
         rec = raw[:16] + b"\0\0\0\0" + raw[20:body_end] + tags
         self._writer.write_record(struct.pack("<i", len(rec)) + rec)
 
+    def write_raw(self, record_bytes: bytes) -> None:
+        """One FINISHED record behind the others -- its block_size and everything behind it, as write() would have put it
+        together (the device reader's evidence dump hands over such records) -- through the same BgzfWriter.write_record."""
+        if self._writer is None:
+            raise IOError("%s is not open for writing" % self.filename)
+        if len(record_bytes) < 36 or struct.unpack_from("<i", record_bytes, 0)[0] != len(record_bytes) - 4:
+            raise ValueError("write_raw takes one whole record: block_size and block_size bytes")
+        self._writer.write_record(bytes(record_bytes))
+
     # ---- iteration
     def _next_record(self) -> Optional[AlignedSegment]:
         szb = self._bgzf.read(4)

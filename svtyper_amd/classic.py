@@ -186,8 +186,9 @@ def sv_genotype(bam_string, vcf_in, vcf_out, min_aligned, split_weight, disc_wei
                 reader=None, stats=None, inflate="host", library_scan="host", verify="off"):
     """`alignment_outpath` (-w): the reads that entered the tallies go to a BAM, tagged XV:A:R / XV:A:A as the reference tags them
     (driver.tag_and_write; the tags that depend on p_concordant come from the device, svt_batch_verdicts).  Legal with
-    reader="python" (what reader=None then means) and geometry="host"; ValueError otherwise, and for an engine without
-    supports_verdicts."""
+    reader="python" (what reader=None then means) or reader="device" (the reads are cut and tagged on the GPU: the evidence dump of
+    svt_bam_evidence_device_dump; the default engine, or one with supports_dump) and geometry="host"; ValueError otherwise, and for
+    an engine without supports_verdicts."""
     run = Classic(bam_string, vcf_in, vcf_out, min_aligned, split_weight, disc_weight, num_samp, lib_info_path, debug, ref_fasta,
                   sum_quals, max_reads, max_ci_dist)
     run.alignment_outpath = alignment_outpath

@@ -567,6 +567,7 @@ int svt_batch_site_qual(svt_batch* b, uint32_t n_samples, const double* initial,
 // svt_batch_verdicts (include/svtyper_hip.h): one launch of svt_verdict_kernel over the resident records on the batch's stream --
 // behind whatever pass is in flight there, which it neither waits on nor disturbs: it reads the records and the tables, and writes
 // scratch of its own that lives for this call.
+static int launch_verdicts(svt_batch* b, uint8_t* d_out, hipStream_t stream);
 static int svt_batch_verdicts_impl(svt_batch* b, uint8_t* out, uint64_t n_records)
 {
     if (!b || (!out && n_records)) return fail(SVT_ERR_INVALID, "null argument");
@@ -577,6 +578,14 @@ static int svt_batch_verdicts_impl(svt_batch* b, uint8_t* out, uint64_t n_record
     HIP_TRY(hipSetDevice(b->device));
     DevScratch d_out;
     SVT_TRY(d_out.alloc(n_records));
+    SVT_TRY(launch_verdicts(b, d_out.as<uint8_t>(), b->stream));
+    return d2h_staged(out, d_out.p, n_records, b->stream);
+}
+
+// the launch itself: `d_out` holds b->n_records bytes of device memory (also behind the device reader's dump, whose verdicts stay in HBM)
+static int launch_verdicts(svt_batch* b, uint8_t* d_out, hipStream_t stream)
+{
+    const uint64_t n_records = b->n_records;
     VerdictArgs a{};
     a.records = static_cast<const uint4*>(b->d_records);
     a.rec_offset = b->d_off;
@@ -585,16 +594,16 @@ static int svt_batch_verdicts_impl(svt_batch* b, uint8_t* out, uint64_t n_record
     a.wtab = b->d_wtab;
     a.libs = b->d_libs;
     a.bins = b->d_bins;
-    a.out = d_out.as<uint8_t>();
+    a.out = d_out;
     a.n_records = n_records;
     a.n_units = (uint32_t)b->n_units;
     a.n_libs = b->sargs.n_libs;
     // a wavefront per unit and step; no more workgroups than a few rounds of the chip (grid-stride over the units)
     const uint64_t wgs = (b->n_units + kVerdictBlock / kWave - 1) / (kVerdictBlock / kWave);
     const dim3 grid((unsigned)std::min<uint64_t>(wgs, (uint64_t)cu_count(b->device) * 32u)), block(kVerdictBlock);
-    hipLaunchKernelGGL(svt_verdict_kernel, grid, block, 0, b->stream, a);
+    hipLaunchKernelGGL(svt_verdict_kernel, grid, block, 0, stream, a);
     HIP_TRY(hipGetLastError());
-    return d2h_staged(out, d_out.p, n_records, b->stream);
+    return SVT_OK;
 }
 
 int svt_batch_verdicts(svt_batch* b, uint8_t* out, uint64_t n_records)

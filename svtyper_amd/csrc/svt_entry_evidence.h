@@ -9,6 +9,7 @@ static thread_local svt_evidence_deep_stats g_deep_stats{};
 struct EvidenceRoute {
     svt_evidence_inflate_stats* inflate_stats = nullptr;   // null: the host (svt_bam_evidence_device); else svt_inflate_kernel, into HBM
     bool count_host_blocks = false;                        // device inflate only: build the host route's arena too, for blocks_host_route
+    svt_evidence_dump* dump = nullptr;                     // svt_bam_evidence_device_dump: source rows from the write pass, dump_pass() behind the batch
     bool device_inflate() const { return inflate_stats != nullptr; }
 };
 
@@ -30,6 +31,8 @@ struct EvidenceCall : CallStream {
     DeviceInflate inflate{device};                           // inflate = "device": the members of `plan`
     DevScratch d_ranges, d_units, d_windows, d_bps, d_rgs, d_refs, d_blob, d_flank, d_status, d_rows, d_reads, d_off, d_src, d_src_off, d_dst_off;
     DevScratch d_deep_unit, d_deep_status, d_deep_rows, d_deep_workspace;   // only a call with deep units allocates these
+    DevScratch d_src_rows, d_verdicts, d_unit_host, d_slot_len, d_slot_state, d_slot_off, d_unit_bytes, d_unit_reads, d_unit_outside, d_unit_offset, d_dump_error;   // only a dump call
+    Pooled d_dump_bytes{device};
 
     ew::Arena arena;
     ew::OpenPlan plan;
@@ -248,7 +251,15 @@ struct EvidenceCall : CallStream {
             SVT_TRY(st.finish());
         }
         a.records = static_cast<uint4*>(d_records.p);
-        if (n) {
+        if (route.dump) {                                        // a source row beside every record (all ones where a row is the host reader's)
+            SVT_TRY(d_src_rows.alloc(n_rec * sizeof(ew::SrcRow)));
+            if (n_rec) HIP_TRY(hipMemsetAsync(d_src_rows.p, 0xff, n_rec * sizeof(ew::SrcRow), s));
+            HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&svt_evidence_src_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLds));
+        }
+        if (n && route.dump) {
+            hipLaunchKernelGGL(svt_evidence_src_kernel, dim3((unsigned)n), dim3(kEvidenceBlock), kLds, s, a, d_src_rows.as<ew::SrcRow>());
+            HIP_TRY(hipGetLastError());
+        } else if (n) {
             hipLaunchKernelGGL(svt_evidence_kernel<true>, dim3((unsigned)n), dim3(kEvidenceBlock), kLds, s, a);
             HIP_TRY(hipGetLastError());
         }
@@ -261,7 +272,8 @@ struct EvidenceCall : CallStream {
         if (n_deep) {                                            // (behind a sync of its own: its time is reported apart)
             const auto t_deep = now();
             da.records = static_cast<uint4*>(d_records.p);
-            hipLaunchKernelGGL(svt_evidence_deep_kernel<true>, dim3(deep_grid), dim3(kEvidenceBlock), 0, s, da);
+            if (route.dump) hipLaunchKernelGGL(svt_evidence_deep_src_kernel, dim3(deep_grid), dim3(kEvidenceBlock), 0, s, da, d_src_rows.as<ew::SrcRow>());
+            else hipLaunchKernelGGL(svt_evidence_deep_kernel<true>, dim3(deep_grid), dim3(kEvidenceBlock), 0, s, da);
             HIP_TRY(hipGetLastError());
             HIP_TRY(hipStreamSynchronize(s));
             DS.deep_walk_s += since(t_deep);
@@ -282,6 +294,88 @@ struct EvidenceCall : CallStream {
         if (b->d_records == d_records.p) d_records.release();   // the batch owns the records now
         SVT_TRY(rc);
         *out = b.release();
+        return SVT_OK;
+    }
+    // The evidence dump, behind the batch: svt_verdict_kernel over the new batch (its bytes stay in HBM), then the two launches of
+    // svt_dump_kernel.h with the host's prefix sum between them, all on the call's stream.
+    int dump_pass(svt_batch* b)
+    {
+        svt_evidence_dump& D = *route.dump;
+        const auto t0 = now();
+        D.unit_offset = static_cast<uint64_t*>(std::calloc(n + 1, sizeof(uint64_t)));
+        D.unit_host = static_cast<uint8_t*>(std::calloc(std::max<uint64_t>(n, 1), 1));
+        if (!D.unit_offset || !D.unit_host) return fail(SVT_ERR_NOMEM, "out of host memory");
+        for (const uint64_t u : host_ids) D.unit_host[u] = 1;
+        if (n == 0 || n_rec == 0) {
+            D.units_host = host_ids.size();
+            D.bytes = static_cast<uint8_t*>(std::malloc(1));
+            D.dump_s = since(t0);
+            return D.bytes ? SVT_OK : fail(SVT_ERR_NOMEM, "out of host memory");
+        }
+        HIP_TRY(hipStreamSynchronize(b->stream));                // (the batch's tables and offsets are up)
+        SVT_TRY(d_verdicts.alloc(n_rec));
+        SVT_TRY(launch_verdicts(b, d_verdicts.as<uint8_t>(), s));
+        SVT_TRY(d_unit_host.alloc(n));
+        SVT_TRY(d_slot_len.alloc(2 * n_rec * sizeof(uint32_t)));
+        SVT_TRY(d_slot_state.alloc(2 * n_rec));
+        SVT_TRY(d_slot_off.alloc(2 * n_rec * sizeof(uint32_t)));
+        SVT_TRY(d_unit_bytes.alloc(n * sizeof(uint64_t)));
+        SVT_TRY(d_unit_outside.alloc(n * sizeof(uint32_t)));
+        SVT_TRY(d_unit_reads.alloc(n * sizeof(uint32_t)));
+        SVT_TRY(d_unit_offset.alloc((n + 1) * sizeof(uint64_t)));
+        SVT_TRY(d_dump_error.alloc(sizeof(uint32_t)));
+        HIP_TRY(hipMemcpyAsync(d_unit_host.p, D.unit_host, n, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemsetAsync(d_slot_len.p, 0, 2 * n_rec * sizeof(uint32_t), s));
+        HIP_TRY(hipMemsetAsync(d_slot_state.p, 0, 2 * n_rec, s));
+        HIP_TRY(hipMemsetAsync(d_dump_error.p, 0, sizeof(uint32_t), s));
+        DumpArgs da2{};
+        da2.arena = static_cast<const uint8_t*>(d_arena.p);
+        da2.arena_len = arena.bytes.size();
+        da2.rows = d_src_rows.as<ew::SrcRow>();
+        da2.verdicts = d_verdicts.as<uint8_t>();
+        da2.rec_offset = b->d_off;
+        da2.unit_host = d_unit_host.as<uint8_t>();
+        da2.n_units = (uint32_t)n;
+        da2.slot_len = d_slot_len.as<uint32_t>();
+        da2.slot_state = d_slot_state.as<uint8_t>();
+        da2.slot_off = d_slot_off.as<uint32_t>();
+        da2.unit_bytes = d_unit_bytes.as<uint64_t>();
+        da2.unit_outside = d_unit_outside.as<uint32_t>();
+        da2.unit_reads = d_unit_reads.as<uint32_t>();
+        da2.unit_offset = d_unit_offset.as<uint64_t>();
+        da2.error = d_dump_error.as<uint32_t>();
+        constexpr unsigned kUnitsPerWg = kDumpBlock / kWave;
+        hipLaunchKernelGGL(svt_dump_size_kernel, dim3((unsigned)((n + kUnitsPerWg - 1) / kUnitsPerWg)), dim3(kDumpBlock), 0, s, da2);
+        HIP_TRY(hipGetLastError());
+        std::vector<uint64_t> unit_bytes(n);
+        std::vector<uint32_t> unit_outside(n), unit_reads(n);
+        HIP_TRY(hipMemcpyAsync(unit_bytes.data(), d_unit_bytes.p, n * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(unit_outside.data(), d_unit_outside.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(unit_reads.data(), d_unit_reads.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        for (uint64_t u = 0; u < n; ++u) {
+            if (unit_outside[u] && !D.unit_host[u]) { D.unit_host[u] = 1; ++D.units_outside_dump; }
+            D.unit_offset[u + 1] = D.unit_offset[u] + (D.unit_host[u] ? 0 : unit_bytes[u]);
+            D.units_host += D.unit_host[u];
+            D.units_dumped += D.unit_offset[u + 1] != D.unit_offset[u];
+            if (!D.unit_host[u]) D.n_reads += unit_reads[u];
+        }
+        D.n_bytes = D.unit_offset[n];
+        D.bytes = static_cast<uint8_t*>(std::malloc(std::max<uint64_t>(D.n_bytes, 1)));
+        if (!D.bytes) return fail(SVT_ERR_NOMEM, "out of host memory");
+        if (D.n_bytes) {
+            SVT_TRY(d_dump_bytes.get(D.n_bytes));
+            da2.bytes = static_cast<uint8_t*>(d_dump_bytes.p);
+            HIP_TRY(hipMemcpyAsync(d_unit_host.p, D.unit_host, n, hipMemcpyHostToDevice, s));      // (with the units outside the dump's envelope)
+            HIP_TRY(hipMemcpyAsync(d_unit_offset.p, D.unit_offset, (n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, s));
+            hipLaunchKernelGGL(svt_dump_write_kernel, dim3((unsigned)n), dim3(kDumpBlock), 0, s, da2);
+            HIP_TRY(hipGetLastError());
+            uint32_t error = 0;
+            HIP_TRY(hipMemcpyAsync(&error, d_dump_error.p, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+            SVT_TRY(d2h_staged(D.bytes, d_dump_bytes.p, D.n_bytes, s));
+            if (error) return fail(SVT_ERR_INTERNAL, "svt_bam_evidence_device_dump: a read does not give the bytes it was sized for");
+        }
+        D.dump_s = since(t0);
         return SVT_OK;
     }
 };
@@ -324,6 +418,16 @@ static int svt_bam_evidence_device_impl(const svt_bam* bam, const svt_summarise_
     t0 = c.now();
     SVT_TRY(c.make_batch(out));
     S.batch_create_s = c.since(t0);
+    if (route.dump) {
+        const int rc = c.dump_pass(*out);
+        if (rc != SVT_OK) {                                      // (no batch without its dump)
+            c.drain();
+            BatchOwner(*out).reset();
+            *out = nullptr;
+            svt_evidence_dump_free(route.dump);
+            return rc;
+        }
+    }
     return SVT_OK;
 }
 
@@ -342,6 +446,22 @@ int svt_bam_evidence_device_inflate(const svt_bam* bam, const svt_summarise_args
         svt_evidence_inflate_stats local{};
         return svt_bam_evidence_device_impl(bam, args, geometry, header, device, flags, out, skipped, stats,
                                             EvidenceRoute{istats ? istats : &local, count_host_blocks != 0});
+    });
+}
+
+int svt_bam_evidence_device_dump(const svt_bam* bam, const svt_summarise_args* args, const svt_evidence_params* geometry,
+                                 const svt_evidence_batch* header, int device, unsigned flags, svt_batch** out, uint8_t* skipped,
+                                 svt_evidence_device_stats* stats, svt_evidence_inflate_stats* istats, int count_host_blocks,
+                                 int inflate_on_device, svt_evidence_dump* dump)
+{
+    return guarded([&] {
+        if (!dump) return fail(SVT_ERR_INVALID, "null argument");
+        *dump = svt_evidence_dump{};
+        svt_evidence_inflate_stats local{};
+        EvidenceRoute route;
+        if (inflate_on_device) { route.inflate_stats = istats ? istats : &local; route.count_host_blocks = count_host_blocks != 0; }
+        route.dump = dump;
+        return svt_bam_evidence_device_impl(bam, args, geometry, header, device, flags, out, skipped, stats, route);
     });
 }
 

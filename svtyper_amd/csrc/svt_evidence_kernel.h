@@ -112,6 +112,31 @@ __global__ __launch_bounds__(kEvidenceBlock) void svt_evidence_deep_kernel(const
     }
 }
 
+// ---- the write pass with source rows (the evidence dump: svt_dump_kernel.h) ----------------------------------------------------
+// svt_evidence_kernel<true> and svt_evidence_deep_kernel<true> with ew::walk_unit's kSrc: beside every record its ew::SrcRow, at
+// the record's index.  Kernels of their own, so that the four instantiations above are what they are without the dump.
+__global__ __launch_bounds__(kEvidenceBlock) void svt_evidence_src_kernel(const EvidenceArgs a, ew::SrcRow* src)
+{
+    extern __shared__ __align__(16) unsigned char svt_evidence_lds[];
+    ew::UnitScratch& S = *reinterpret_cast<ew::UnitScratch*>(svt_evidence_lds);
+    const uint32_t u = blockIdx.x;
+    if (u >= a.n_units) return;
+    if (a.status[u] != ew::EW_OK || a.n_rows[u] == 0) return;                    // (the same for every lane of the workgroup)
+    ew::walk_unit<EvidenceDevCtx, ew::UnitScratch, true>(a.P, u, S, S.tables(), reinterpret_cast<Record4*>(a.records + a.rec_offset[u]), src + a.rec_offset[u]);
+}
+
+__global__ __launch_bounds__(kEvidenceBlock) void svt_evidence_deep_src_kernel(const EvidenceDeepArgs a, ew::SrcRow* src)
+{
+    __shared__ ew::DeepScratch S;
+    const ew::Tables<uint32_t> T = ew::deep_tables(a.workspace + (uint64_t)blockIdx.x * ew::kDeepSliceBytes);
+    for (uint32_t k = blockIdx.x; k < a.n_deep; k += gridDim.x) {                  // (k is the same for every lane of the workgroup)
+        if (a.status[k] != ew::EW_OK || a.n_rows[k] == 0) continue;
+        const uint32_t u = a.unit[k];
+        ew::walk_unit<EvidenceDevCtx, ew::DeepScratch, true>(a.P, u, S, T, reinterpret_cast<Record4*>(a.records + a.rec_offset[u]), src + a.rec_offset[u]);
+        __syncthreads();                                                           // (S is the next unit's from here on)
+    }
+}
+
 // records of the units the host recomputed: `src` holds them side by side, unit k's `count[k]` records go to `dst_off[k]`
 __global__ __launch_bounds__(kEvidenceBlock) void svt_evidence_scatter_kernel(const uint4* __restrict__ src, const uint64_t* __restrict__ src_off,
                                                                               const uint64_t* __restrict__ dst_off, uint32_t n, uint4* __restrict__ dst)

@@ -97,6 +97,18 @@ struct ReadSum {
 };
 enum : uint8_t { RS_NIV = 3, RS_REV = 4, RS_SPLIT = 8, RS_SOFT = 16, RS_SELF_LEFT = 32, RS_O_REV = 64, RS_DUP = 128 };
 
+// ---- the source row of one record (the evidence dump of `svtyper -w`: svt_dump_rules.h) -----------------------------------
+// Which alignment records a row was made of, and what the row's gated bytes cannot show.  rec[]: the arena offset of the
+// block_size word of the row's primary ra, its primary rb, the read behind its seq candidate and the read behind its clip
+// candidate; kNoRecord = absent.  bits: SRC_HIT_A / SRC_HIT_B = the UNGATED is_ref_seq_at answer, at breakend A or at B, for ra /
+// rb (a hit with MAPQ 0 still tags the read R, classic.py:309-314; the record's gated MAPQ byte is 0 either way);
+// SRC_CONTINUATION = the row continues the fragment of the row before.  Rows k = 0, 1, ... of a fragment list its primaries
+// 2k and 2k + 1 in arrival order and the k-th seq / clip candidate: packer.FragmentSpan's ref_hits, seq[k] and clip[k].
+struct SrcRow { uint32_t rec[4]; uint32_t bits; };
+constexpr uint32_t kNoRecord = 0xffffffffu;
+enum : uint32_t { SRC_HIT_A = 1, SRC_HIT_B = 2, SRC_CONTINUATION = 4 };
+static_assert(sizeof(SrcRow) == 20, "a source row is five words");
+
 // the staging area of kBatch chain records (`Idx`: what holds a slot of the tier's read table, all ones = none)
 template <class Idx>
 struct Batch {
@@ -534,8 +546,10 @@ SVT_HD void order_deep(const Params& P, DeepScratch& S, const Tables<uint32_t>& 
 // after the call).  `out` holds S.n_rows records in sorted(query_name) order, as process_unit emits them.  `S`: UnitScratch or
 // DeepScratch; `T`: the tier's tables (UnitScratch::tables() / deep_tables()).  S.n_reads is the unit's number of kept reads
 // also when that is more than T.cap: the unit is EW_READS then.
-template <class X, class SC>
-SVT_HD void walk_unit(const Params& P, uint64_t u, SC& S, const Tables<typename SC::Idx>& T, Record4* out)
+// kSrc (the evidence dump): the write pass also leaves one SrcRow per record in `src`; without it -- every instantiation there
+// was before the dump -- or with `src` null the walk is what it is without.
+template <class X, class SC, bool kSrc = false>
+SVT_HD void walk_unit(const Params& P, uint64_t u, SC& S, const Tables<typename SC::Idx>& T, Record4* out, SrcRow* src = nullptr)
 {
     typedef typename SC::Idx Idx;
     typedef Tables<Idx> Tb;
@@ -642,21 +656,45 @@ SVT_HD void walk_unit(const Params& P, uint64_t u, SC& S, const Tables<typename 
         for (uint32_t k = 0; k < rows; ++k) {
             ReadS ra = absent_read(), rb = absent_read();
             PieceS sl = absent_piece(), sr = absent_piece(), cl = absent_piece(), cr = absent_piece();
+            SrcRow row = {{kNoRecord, kNoRecord, kNoRecord, kNoRecord}, k > 0 ? (uint32_t)SRC_CONTINUATION : 0u};   // (dead without kSrc)
             for (int j = 0; j < 2; ++j) {
                 while (qp < end && !is_primary(T.reads[T.order[qp] & Tb::kIndex])) ++qp;
-                if (qp < end) { (j ? rb : ra) = read_of_sum(T.reads[T.order[qp] & Tb::kIndex]); ++qp; }
+                if (qp < end) {
+                    const ReadSum& m = T.reads[T.order[qp] & Tb::kIndex];
+                    (j ? rb : ra) = read_of_sum(m);
+                    if constexpr (kSrc) row.rec[j] = m.name_off - 36;      // (the name lies 32 bytes into the record, behind block_size)
+                    ++qp;
+                }
             }
             for (; qs < end; ++qs) {
                 const ReadSum& m = T.reads[T.order[qs] & Tb::kIndex];
-                if (is_primary(m) && (m.bits & RS_SPLIT) && !(m.bits & RS_SOFT)) { sl = piece_of_sum(m, true); sr = piece_of_sum(m, false); ++qs; break; }
+                if (is_primary(m) && (m.bits & RS_SPLIT) && !(m.bits & RS_SOFT)) {
+                    sl = piece_of_sum(m, true); sr = piece_of_sum(m, false);
+                    if constexpr (kSrc) row.rec[2] = m.name_off - 36;
+                    ++qs;
+                    break;
+                }
             }
             for (; qc < end; ++qc) {
                 const ReadSum& m = T.reads[T.order[qc] & Tb::kIndex];
-                if (is_primary(m) && (m.bits & RS_SPLIT) && (m.bits & RS_SOFT)) { cl = piece_of_sum(m, true); cr = piece_of_sum(m, false); ++qc; break; }
+                if (is_primary(m) && (m.bits & RS_SPLIT) && (m.bits & RS_SOFT)) {
+                    cl = piece_of_sum(m, true); cr = piece_of_sum(m, false);
+                    if constexpr (kSrc) row.rec[3] = m.name_off - 36;
+                    ++qc;
+                    break;
+                }
             }
             ra.extra = lib;
             rb.extra = ((k == 0 && np == 2) ? SVT_FRAG_PAIR : 0u) | (k > 0 ? SVT_FRAG_CONTINUATION : 0u);
             out[T.rowoff[p] + k] = geometry_record(ra, rb, sl, sr, cl, cr, bp, P.lib_flank[lib], P.min_aligned, P.split_slop);
+            if constexpr (kSrc) {
+                if (src) {
+                    const int32_t m = P.min_aligned;
+                    if (is_ref_seq_at(ra, bp.tid_a, bp.pos_a, m) || is_ref_seq_at(ra, bp.tid_b, bp.pos_b, m)) row.bits |= SRC_HIT_A;
+                    if (is_ref_seq_at(rb, bp.tid_a, bp.pos_a, m) || is_ref_seq_at(rb, bp.tid_b, bp.pos_b, m)) row.bits |= SRC_HIT_B;
+                    src[T.rowoff[p] + k] = row;
+                }
+            }
         }
     }
     X::sync();

@@ -29,6 +29,7 @@
 #include "../../include/svtyper_reads.h"
 #include "svt_bam_index.h"
 #include "svt_bgzf.h"
+#include "svt_dump_rules.h"
 #include "svt_error.h"
 #include "svt_evidence_arena.h"
 #include "svt_geometry_math.h"
@@ -1458,14 +1459,20 @@ void svt_evidence_free(svt_evidence* e)
     e->records = nullptr;
 }
 
+// `dump` (svt_bam_evidence_dump_walk_host): the walk also leaves its source rows, and the dump rules run over them and `verdicts`
+static int dump_units_host(const svt::ew::Arena& arena, const std::vector<std::vector<svt::ew::SrcRow>>& src, const std::vector<uint32_t>& status,
+                           const uint64_t* rec_offset, const uint8_t* verdicts, svt_evidence_dump* dump);
+
 static int svt_bam_evidence_walk_host_impl(const svt_bam* bam, const svt_summarise_args* args, const svt_evidence_params* geometry,
-                                           svt_evidence* out, uint8_t* out_of_envelope, uint32_t* kept_reads, bool open_ranges)
+                                           svt_evidence* out, uint8_t* out_of_envelope, uint32_t* kept_reads, bool open_ranges,
+                                           const uint8_t* verdicts = nullptr, uint64_t n_verdicts = 0, svt_evidence_dump* dump = nullptr)
 {
     if (!out || !out_of_envelope) return fail(SVT_ERR_INVALID, "null argument");
     svt::VerifyScope verify_scope(bam);
     out->rec_offset = nullptr;
     out->records = nullptr;
     out->skipped = nullptr;
+    if (dump) *dump = svt_evidence_dump{};
     svt::ew::Arena arena;
     if (open_ranges) {
         svt::ew::OpenPlan plan;
@@ -1479,32 +1486,39 @@ static int svt_bam_evidence_walk_host_impl(const svt_bam* bam, const svt_summari
     const uint64_t n = args->n_units;
     const svt::ew::Params P = arena.params(args, geometry);
     std::vector<std::vector<svt::Record4>> per(n);
+    std::vector<std::vector<svt::ew::SrcRow>> src(dump ? n : 0);
     std::vector<uint32_t> status(n, 0);
     std::atomic<uint64_t> next(0);
     const unsigned nt = svt::ew::arena_threads(args, n);
     run_threads(nt, [&](unsigned) {
         std::unique_ptr<svt::ew::UnitScratch> S(new svt::ew::UnitScratch());
         std::vector<svt::Record4> rows(svt::ew::kMaxReads);    // (a unit has at most one row per kept read)
+        std::vector<svt::ew::SrcRow> src_rows(dump ? svt::ew::kMaxReads : 0);
         // the deep tier's scratch and tables, from the heap once this thread meets a unit that needs them
         std::unique_ptr<svt::ew::DeepScratch> D;
         std::unique_ptr<uint64_t[]> slice;
         for (;;) {
             const uint64_t u = next.fetch_add(1);
             if (u >= n) return;
-            svt::ew::walk_unit<svt::ew::HostCtx>(P, u, *S, S->tables(), rows.data());
+            if (dump) svt::ew::walk_unit<svt::ew::HostCtx, svt::ew::UnitScratch, true>(P, u, *S, S->tables(), rows.data(), src_rows.data());
+            else svt::ew::walk_unit<svt::ew::HostCtx>(P, u, *S, S->tables(), rows.data());
             uint32_t st = S->status, n_reads = S->n_reads, n_rows = S->n_rows;
             if (svt::ew::deep_tier_unit(st, n_reads)) {
                 if (!D) {
                     D.reset(new svt::ew::DeepScratch());
                     slice.reset(new uint64_t[svt::ew::kDeepSliceBytes / sizeof(uint64_t)]);
                     rows.resize(svt::ew::kMaxReadsDeep);
+                    if (dump) src_rows.resize(svt::ew::kMaxReadsDeep);
                 }
-                svt::ew::walk_unit<svt::ew::HostCtx>(P, u, *D, svt::ew::deep_tables(reinterpret_cast<uint8_t*>(slice.get())), rows.data());
+                const svt::ew::Tables<uint32_t> T = svt::ew::deep_tables(reinterpret_cast<uint8_t*>(slice.get()));
+                if (dump) svt::ew::walk_unit<svt::ew::HostCtx, svt::ew::DeepScratch, true>(P, u, *D, T, rows.data(), src_rows.data());
+                else svt::ew::walk_unit<svt::ew::HostCtx>(P, u, *D, T, rows.data());
                 st = D->status; n_reads = D->n_reads; n_rows = D->n_rows;
             }
             status[u] = st;
             if (kept_reads) kept_reads[u] = n_reads;
             if (st == svt::ew::EW_OK) per[u].assign(rows.begin(), rows.begin() + n_rows);
+            if (dump && st == svt::ew::EW_OK) src[u].assign(src_rows.begin(), src_rows.begin() + n_rows);
         }
     });
     uint64_t total = 0;
@@ -1525,7 +1539,101 @@ static int svt_bam_evidence_walk_host_impl(const svt_bam* bam, const svt_summari
         out_of_envelope[u] = status[u] >= svt::ew::EW_RANGE ? (uint8_t)status[u] : 0;
     }
     out->rec_offset[n] = off;
+    if (dump) {
+        if (n_verdicts != off || (off && !verdicts)) {
+            svt_evidence_free(out);
+            return fail(SVT_ERR_INVALID, "svt_bam_evidence_dump_walk_host: one verdict byte per record of svt_bam_evidence_walk_host on the same arguments");
+        }
+        if (const int rc = dump_units_host(arena, src, status, out->rec_offset, verdicts, dump)) {
+            svt_evidence_free(out);
+            return rc;
+        }
+    }
     return SVT_OK;
+}
+
+// the dump rules on one lane, unit after unit
+static int dump_units_host(const svt::ew::Arena& arena, const std::vector<std::vector<svt::ew::SrcRow>>& src, const std::vector<uint32_t>& status,
+                           const uint64_t* rec_offset, const uint8_t* verdicts, svt_evidence_dump* dump)
+{
+    namespace dr = svt::dr;
+    const auto t0 = std::chrono::steady_clock::now();
+    const uint64_t n = src.size();
+    dump->unit_offset = static_cast<uint64_t*>(std::calloc(n + 1, sizeof(uint64_t)));
+    dump->unit_host = static_cast<uint8_t*>(std::calloc(std::max<uint64_t>(n, 1), 1));
+    if (!dump->unit_offset || !dump->unit_host) { svt_evidence_dump_free(dump); return fail(SVT_ERR_NOMEM, "out of host memory"); }
+    std::vector<std::vector<uint32_t>> slot_len(n);
+    std::vector<std::vector<uint8_t>> slot_state(n);
+    auto unit_of = [&](uint64_t u) {
+        dr::Unit U;
+        U.arena = arena.bytes.data();
+        U.arena_len = arena.bytes.size();
+        U.rows = src[u].data();
+        U.verdicts = verdicts + rec_offset[u];
+        U.n_rows = (uint32_t)src[u].size();
+        U.slot_len = slot_len[u].data();
+        U.slot_state = slot_state[u].data();
+        return U;
+    };
+    for (uint64_t u = 0; u < n; ++u) {
+        dump->unit_offset[u + 1] = dump->unit_offset[u];
+        if (status[u] >= svt::ew::EW_RANGE) { dump->unit_host[u] = 1; ++dump->units_host; continue; }   // outside the walk's envelope
+        if (src[u].empty()) continue;                                                                    // skipped, or without reads
+        slot_len[u].assign(2 * src[u].size(), 0);
+        slot_state[u].assign(2 * src[u].size(), 0);
+        uint64_t bytes = 0;
+        uint32_t reads = 0;
+        if (!dr::size_unit<svt::ew::HostCtx>(unit_of(u), bytes, reads)) {                                       // outside the dump's
+            dump->unit_host[u] = 1;
+            ++dump->units_host;
+            ++dump->units_outside_dump;
+            slot_len[u].clear();
+            continue;
+        }
+        dump->unit_offset[u + 1] += bytes;
+        dump->n_reads += reads;
+        ++dump->units_dumped;
+    }
+    dump->n_bytes = dump->unit_offset[n];
+    dump->bytes = static_cast<uint8_t*>(std::malloc(std::max<uint64_t>(dump->n_bytes, 1)));
+    if (!dump->bytes) { svt_evidence_dump_free(dump); return fail(SVT_ERR_NOMEM, "out of host memory"); }
+    std::vector<uint32_t> slot_off;
+    for (uint64_t u = 0; u < n; ++u) {
+        if (slot_len[u].empty() || dump->unit_offset[u + 1] == dump->unit_offset[u]) continue;
+        const dr::Unit U = unit_of(u);
+        uint32_t partial[1];
+        slot_off.assign(slot_len[u].size(), 0);
+        dr::place_slots<svt::ew::HostCtx>(U.slot_len, slot_off.data(), 2 * U.n_rows, partial);
+        for (uint32_t k = 0; k < 2 * U.n_rows; ++k) {
+            if (!U.slot_len[k]) continue;
+            if (!dr::emit_read<svt::ew::HostCtx>(U.arena, U.arena_len, U.rows[k / 2].rec[k & 1], U.slot_state[k], dump->bytes + dump->unit_offset[u] + slot_off[k], U.slot_len[k])) {
+                svt_evidence_dump_free(dump);
+                return fail(SVT_ERR_INTERNAL, "svt_bam_evidence_dump_walk_host: a read does not give the bytes it was sized for");
+            }
+        }
+    }
+    dump->dump_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    return SVT_OK;
+}
+
+void svt_evidence_dump_free(svt_evidence_dump* d)
+{
+    if (!d) return;
+    std::free(d->bytes);
+    std::free(d->unit_offset);
+    std::free(d->unit_host);
+    d->bytes = nullptr;
+    d->unit_offset = nullptr;
+    d->unit_host = nullptr;
+}
+
+int svt_bam_evidence_dump_walk_host(const svt_bam* bam, const svt_summarise_args* args, const svt_evidence_params* geometry, const uint8_t* verdicts,
+                                    uint64_t n_verdicts, svt_evidence* out, uint8_t* out_of_envelope, svt_evidence_dump* dump)
+{
+    return guarded([&] {
+        if (!dump) return fail(SVT_ERR_INVALID, "null argument");
+        return svt_bam_evidence_walk_host_impl(bam, args, geometry, out, out_of_envelope, nullptr, false, verdicts, n_verdicts, dump);
+    });
 }
 
 int svt_bam_evidence_walk_host(const svt_bam* bam, const svt_summarise_args* args, const svt_evidence_params* geometry, svt_evidence* out,

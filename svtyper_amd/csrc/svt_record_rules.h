@@ -197,6 +197,47 @@ SVT_HD uint32_t walk_tags(const uint8_t* d, uint32_t size, uint32_t& at, bool st
     return TAGS_END;
 }
 
+// One field of a tag area, by the grammar of walk_tags: the field at `at` ends at `next` (TAG_FIELD), or fewer than three
+// bytes are left (TAGS_END), or the field is what walk_tags calls TAGS_MALFORMED / TAGS_OVERRUN.  For callers that need every
+// field's extent (svt_dump_rules.h: the XV fields of a record).  walk_tags is not restated over it: doing so moves the register
+// and spill lines of the walk and library kernels, which hold walk_tags on their hot path; that the two end alike on every
+// record of the dump corpus is checked by tests/native/asan_dump_rules_main.cpp.
+constexpr uint32_t TAG_FIELD = 4;
+SVT_HD uint32_t tag_field(const uint8_t* d, uint32_t size, uint32_t at, uint32_t& next)
+{
+    uint64_t i = at;
+    const uint64_t n = size;
+    if (i + 3 > n) return TAGS_END;
+    const uint8_t ty = d[i + 2];
+    i += 3;
+    uint64_t skip = 0;
+    switch (ty) {
+    case 'A': case 'c': case 'C': skip = 1; break;
+    case 's': case 'S': skip = 2; break;
+    case 'i': case 'I': case 'f': skip = 4; break;
+    case 'Z': case 'H': {
+        uint64_t q = i;
+        while (q < n && d[q]) ++q;
+        if (q >= n) return TAGS_MALFORMED;
+        skip = q - i + 1;
+        break;
+    }
+    case 'B': {
+        if (i + 5 > n) return TAGS_MALFORMED;
+        const uint8_t sub = d[i];
+        const uint32_t cnt = ld32(d + i + 1);
+        const uint64_t sz = (sub == 'c' || sub == 'C') ? 1 : (sub == 's' || sub == 'S') ? 2 : (sub == 'i' || sub == 'I' || sub == 'f') ? 4 : 0;
+        if (sz == 0) return TAGS_MALFORMED;
+        skip = 5 + (uint64_t)cnt * sz;
+        break;
+    }
+    default: return TAGS_MALFORMED;
+    }
+    i += skip;
+    if (i > n) return TAGS_OVERRUN;
+    next = (uint32_t)i;
+    return TAG_FIELD;
+}
 // ---- aligned intervals ------------------------------------------------------------------------------------------------------
 // The maximal gap-free aligned reference intervals of a CIGAR (geometry.aligned_intervals), reduced to what a summary keeps:
 // all of them when there are at most two, else the two nearest to the breakends in the order of a stable sort by distance

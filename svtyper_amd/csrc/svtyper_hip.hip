@@ -74,6 +74,7 @@
 #include "svt_library_arena.h"
 #include "svt_bayes_kernel.h"
 #include "svt_verdict_kernel.h"
+#include "svt_dump_kernel.h"
 #include "svt_host_tables.h"
 #include "svt_host_transfer.h"
 

@@ -15,7 +15,8 @@ route, the `stats=` block.  What the reference's two programs do differently is 
              warn(text), gather(sample, bp, max_reads)      inside handle_line
              render_actions(results, actions)               results -> the text of every output action
              finish(unpaired)             the end of a run
-    data     alignment_outpath            (`svtyper -w`) the evidence dump: tag_and_write below, per chunk, in output order
+    data     alignment_outpath            (`svtyper -w`) the evidence dump: tag_and_write below, per chunk, in output order -- the reads of
+                                                  reader="python", or the finished records of reader="device" (svt_dump_kernel.h)
 
 No method takes a flag that names its caller, and a driver's hooks run per line handed to the per-line route and per
 block, never per site of the bulk route (`BulkFeeder._block` / `_write_block`).
@@ -24,6 +25,7 @@ from __future__ import annotations
 
 import argparse
 import os
+import struct
 import sys
 from itertools import chain
 
@@ -49,6 +51,9 @@ def tag_and_write(evidence, out_bam, written: set) -> None:
     weight from the device (svt_batch_verdicts, bits 0-5).  `written`: the (query_name, flag) set of the whole run."""
     for unit in evidence:
         if unit is None:
+            continue
+        if not isinstance(unit, tuple):                         # the device reader's dump: the unit's reads as finished records, in that order
+            _write_dumped(unit, out_bam, written)
             continue
         fragments, spans, verdicts = unit
         for span in spans:                                      # classic.py:296: sorted(query_name)
@@ -83,6 +88,22 @@ def tag_and_write(evidence, out_bam, written: set) -> None:
                     if key not in written:
                         out_bam.write(read)
                         written.add(key)
+
+
+def _write_dumped(records, out_bam, written: set) -> None:
+    """A unit of the device reader's evidence dump (svt_dump_rules.h: tagged and cut as above, on the GPU): record by record, the
+    key (query_name, flag) read at their fixed offsets, written unless the run wrote it before."""
+    at, n = 0, len(records)
+    while at < n:
+        size = struct.unpack_from("<i", records, at)[0] + 4
+        if size < 36 or at + size > n:
+            raise ValueError("the evidence dump of a unit does not end with a whole record")
+        l_read_name, flag = records[at + 12], struct.unpack_from("<H", records, at + 18)[0]
+        key = (bytes(records[at + 36:at + 36 + l_read_name - 1]).decode("ascii"), flag)
+        if key not in written:
+            out_bam.write_raw(records[at:at + size])
+            written.add(key)
+        at += size
 
 
 def _tag_span(fragment, value: str) -> None:
@@ -156,7 +177,10 @@ class Driver:
     def check_write_alignment(self, reader, geometry, engine):
         """`-w` needs the reads of a chunk alive when its verdicts come back, canonical records to give verdicts on, and an
         engine that gives them."""
-        if reader != "python":
+        # reader="device" hands over the reads as finished records (the evidence dump) when the engine is the one whose batches the
+        # device reader builds: the default engine, or one that declares supports_dump
+        dumps = reader == "device" and (engine is None or getattr(engine, "supports_dump", False))
+        if reader != "python" and not dumps:
             raise ValueError("-w/--write_alignment needs reader='python': reader=%r keeps no reads to write" % (reader,))
         if geometry == "device":
             raise ValueError("-w/--write_alignment needs geometry='host': with geometry='device' there are no canonical records on "
@@ -173,7 +197,8 @@ class Driver:
             collector = NativeUnitCollector(self.samples, native, self.split_weight, self.disc_weight, self.min_aligned,
                                             self.count_mode, self.max_reads, n_threads=self.n_threads,
                                             geometry="walk" if reader == "device" else "device" if geometry == "device" else "reader",
-                                            inflate=inflate)
+                                            inflate=inflate, keep_reads=writing,
+                                            gather=(lambda sample, bp, max_reads: self.gather(sample, bp, max_reads)) if writing else None)
         elif reader == "python":
             collector = UnitCollector(self.samples, self.split_weight, self.disc_weight, self.min_aligned, geometry,
                                       keep_reads=writing)
@@ -211,7 +236,8 @@ class Driver:
         # bulk route (C++ reader): blocks of lines -> breakpoint arrays -> output text in native calls (bulk_vcf.py); lines it
         # hands back, and everything once it stops in front of a BND line it cannot express, take the per-line route above
         bulk = None
-        if (native is not None and (self.bulk_under_debug or not self.debug) and hasattr(self.vcf_in, "read")
+        # (under -w every line takes the per-line route: a unit the dump does not hold needs its breakpoint dict)
+        if (native is not None and not writing and (self.bulk_under_debug or not self.debug) and hasattr(self.vcf_in, "read")
                 and os.environ.get("SVT_BULK_VCF", "1") != "0"):
             from . import bulk_vcf
             if bulk_vcf.available():

@@ -140,6 +140,33 @@ class _InflateStats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class _Dump(C.Structure):
+    """include/svtyper_reads.h: svt_evidence_dump"""
+    _fields_ = [("bytes", C.c_void_p), ("unit_offset", C.POINTER(C.c_uint64)), ("unit_host", C.POINTER(C.c_uint8)),
+                ("n_bytes", C.c_uint64), ("n_reads", C.c_uint64), ("units_dumped", C.c_uint64), ("units_host", C.c_uint64),
+                ("units_outside_dump", C.c_uint64), ("dump_s", C.c_double)]
+
+    COUNTERS = ("n_bytes", "n_reads", "units_dumped", "units_host", "units_outside_dump", "dump_s")
+
+    def take(self, lib, n: int):
+        """(bytes, unit_offset uint64 [n + 1], unit_host uint8 [n], counters) copied out; the C buffers are released"""
+        try:
+            off = np.ctypeslib.as_array(self.unit_offset, shape=(n + 1,)).copy()
+            host = np.ctypeslib.as_array(self.unit_host, shape=(max(n, 1),))[:n].copy()
+            data = C.string_at(self.bytes, int(self.n_bytes)) if self.n_bytes else b""
+            return data, off, host, {k: getattr(self, k) for k in self.COUNTERS}
+        finally:
+            lib.svt_evidence_dump_free(C.byref(self))
+
+
+NO_DUMP = {k: 0 for k in _Dump.COUNTERS}     # the dump counters of a call without a dump
+
+
+def has_dump() -> bool:
+    """this libsvtyper_hip.so has the evidence dump (svt_bam_evidence_device_dump: added without a new ABI number)"""
+    return hasattr(_lib(), "svt_bam_evidence_device_dump")
+
+
 def walk_capacities() -> Dict[str, int]:
     """the fixed capacities of the evidence walk (svt_evidence_walk.h)"""
     L = _lib()
@@ -190,6 +217,14 @@ def _lib():
         L.svt_bam_evidence_walk_open_host.argtypes = L.svt_bam_evidence_walk_host.argtypes
         L.svt_bam_evidence_device_inflate.restype = C.c_int
         L.svt_bam_evidence_device_inflate.argtypes = L.svt_bam_evidence_device.argtypes + [C.POINTER(_InflateStats), C.c_int]
+        if hasattr(L, "svt_bam_evidence_device_dump"):      # (added without a new ABI number: a library built before it lacks the symbols)
+            L.svt_bam_evidence_device_dump.restype = C.c_int
+            L.svt_bam_evidence_device_dump.argtypes = L.svt_bam_evidence_device_inflate.argtypes + [C.c_int, C.POINTER(_Dump)]
+            L.svt_bam_evidence_dump_walk_host.restype = C.c_int
+            L.svt_bam_evidence_dump_walk_host.argtypes = [C.c_void_p, C.POINTER(_Args), C.POINTER(_EvidenceParams), C.c_void_p, C.c_uint64,
+                                                          C.POINTER(_Evidence), C.c_void_p, C.POINTER(_Dump)]
+            L.svt_evidence_dump_free.restype = None
+            L.svt_evidence_dump_free.argtypes = [C.POINTER(_Dump)]
         L.svt_bgzf_inflate_host.restype = C.c_int
         L.svt_bgzf_inflate_host.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
         L.svt_bgzf_inflate_device.restype = C.c_int
@@ -425,18 +460,43 @@ class NativeBam:
             self._L.svt_evidence_free(C.byref(out))
         return off, recs, skipped, flagged[:n], kept[:n]
 
+    def evidence_dump_walk_host(self, windows: np.ndarray, breakpoints: np.ndarray, read_groups: Sequence[str],
+                                read_group_lib: Sequence[int], max_reads: Optional[int], count_mode: int, lib_flank: Sequence[float],
+                                min_aligned: int, split_slop: int, verdicts: np.ndarray, n_threads: int = 0):
+        """svt_bam_evidence_dump_walk_host: the evidence dump of `svtyper -w` with no GPU -- evidence_walk_host() with source
+        rows plus the dump rules (svt_dump_rules.h) on one lane.  `verdicts`: uint8, one per record of evidence_walk_host() on the
+        same arguments, in its record order (there is no host implementation of the verdicts).  Returns (bytes -- finished BAM
+        records, unit after unit --, unit_offset uint64 [n + 1], unit_host uint8 [n]: 1 = outside the walk's or the dump's
+        envelope, no bytes; counters dict)."""
+        if not hasattr(self._L, "svt_bam_evidence_dump_walk_host"):
+            raise hip.SvtyperHipError("this libsvtyper_hip.so has no svt_bam_evidence_dump_walk_host (built before it was added): rebuild it")
+        n, a, g, _keep = self._walk_args(windows, breakpoints, read_groups, read_group_lib, max_reads, count_mode, lib_flank,
+                                         min_aligned, split_slop, n_threads)
+        verdicts = np.ascontiguousarray(verdicts, dtype=np.uint8)
+        out, dump = _Evidence(), _Dump()
+        flagged = np.zeros(max(n, 1), np.uint8)
+        self._call(self._L.svt_bam_evidence_dump_walk_host(self._h, C.byref(a), C.byref(g), verdicts.ctypes.data if verdicts.size else None,
+                                                           int(verdicts.size), C.byref(out), flagged.ctypes.data, C.byref(dump)))
+        self._L.svt_evidence_free(C.byref(out))
+        return dump.take(self._L, n)
+
     def evidence_device(self, windows: np.ndarray, breakpoints: np.ndarray, read_groups: Sequence[str],
                         read_group_lib: Sequence[int], max_reads: Optional[int], count_mode: int, lib_flank: Sequence[float],
                         min_aligned: int, split_slop: int, header, device: int = 0, flags: int = 0, n_threads: int = 0,
-                        inflate: str = "host", count_host_blocks: bool = False):
+                        inflate: str = "host", count_host_blocks: bool = False, dump: bool = False):
         """svt_bam_evidence_device: the reader stage with the walk on the GPU.  `header`: an EvidenceBatch whose units,
         libraries and weights describe the batch (its rec_offset / records are ignored).  Returns (hip.DeviceBatch resident
         in HBM -- what DeviceBatch(EvidenceBatch(*evidence(...))) builds --, skipped uint8 [n], stats dict; under "deep" the
         share of the units of more than walk_capacities()["reads_lds"] kept reads: svt_evidence_deep_stats).
         inflate="device" (svt_bam_evidence_device_inflate): the BGZF members are inflated on the GPU as well; the stats then
-        carry svt_evidence_inflate_stats under "inflate" (`count_host_blocks`: also count the blocks of the host-inflate route)."""
+        carry svt_evidence_inflate_stats under "inflate" (`count_host_blocks`: also count the blocks of the host-inflate route).
+        dump=True (svt_bam_evidence_device_dump): a fourth value, the evidence dump of `svtyper -w` built on the GPU behind the
+        batch -- (bytes, unit_offset, unit_host) as evidence_dump_walk_host() gives them; its counters are stats["dump"], which
+        a call without it reports as zeros."""
         if inflate not in ("host", "device"):
             raise ValueError("inflate must be 'host' or 'device'")
+        if dump and not hasattr(self._L, "svt_bam_evidence_device_dump"):
+            raise hip.SvtyperHipError("this libsvtyper_hip.so has no svt_bam_evidence_device_dump (built before it was added): rebuild it")
         n, a, g, _keep = self._walk_args(windows, breakpoints, read_groups, read_group_lib, max_reads, count_mode, lib_flank,
                                          min_aligned, split_slop, n_threads)
         if header.n_units != n:
@@ -445,6 +505,19 @@ class NativeBam:
         handle = C.c_void_p()
         skipped = np.zeros(max(n, 1), np.uint8)
         st = _DeviceStats()
+        if dump:
+            ist, dmp = _InflateStats(), _Dump()
+            self._call(self._L.svt_bam_evidence_device_dump(self._h, C.byref(a), C.byref(g), C.byref(cb), int(device), int(flags),
+                                                            C.byref(handle), skipped.ctypes.data, C.byref(st), C.byref(ist),
+                                                            1 if count_host_blocks else 0, 1 if inflate == "device" else 0, C.byref(dmp)))
+            batch = hip.DeviceBatch.adopt(handle, n, int(st.n_records), device)
+            data, off, host, counters = dmp.take(self._L, n)
+            stats = st.as_dict()
+            if inflate == "device":
+                stats["inflate"] = ist.as_dict()
+            stats["deep"] = deep_stats()
+            stats["dump"] = counters
+            return batch, skipped[:n], stats, (data, off, host)
         if inflate == "device":
             ist = _InflateStats()
             self._call(self._L.svt_bam_evidence_device_inflate(self._h, C.byref(a), C.byref(g), C.byref(cb), int(device), int(flags),
@@ -453,11 +526,13 @@ class NativeBam:
             stats = st.as_dict()
             stats["inflate"] = ist.as_dict()
             stats["deep"] = deep_stats()
+            stats["dump"] = dict(NO_DUMP)
             return hip.DeviceBatch.adopt(handle, n, int(st.n_records), device), skipped[:n], stats
         self._call(self._L.svt_bam_evidence_device(self._h, C.byref(a), C.byref(g), C.byref(cb), int(device), int(flags),
                                                    C.byref(handle), skipped.ctypes.data, C.byref(st)))
         stats = st.as_dict()
         stats["deep"] = deep_stats()
+        stats["dump"] = dict(NO_DUMP)
         return hip.DeviceBatch.adopt(handle, n, int(st.n_records), device), skipped[:n], stats
 
     def summarise(self, windows: np.ndarray, breakpoints: np.ndarray, read_groups: Sequence[str],
@@ -508,6 +583,13 @@ class _SummariesOwner:
             self._lib.svt_summaries_free(C.byref(self._s))
         except Exception:
             pass
+
+
+def batch_offsets(dbatch) -> np.ndarray:
+    """svt_debug_batch_records without the records: rec_offset uint64 [n_units + 1] of a resident batch of canonical records"""
+    off = np.zeros(dbatch.n_units + 1, np.uint64)
+    hip._check(_lib().svt_debug_batch_records(dbatch._h, off.ctypes.data, None))
+    return off
 
 
 def batch_records(dbatch) -> Tuple[np.ndarray, np.ndarray]:

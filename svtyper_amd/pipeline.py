@@ -33,6 +33,7 @@ Engine = Callable[[EvidenceBatch, int], Results]
 Z = 3            # fetch / straddle flank in standard deviations (classic.py:183)
 SPLIT_SLOP = 3   # slop around the breakpoint for split reads (classic.py:184)
 MIN_LIB_PREVALENCE = 1e-3
+_HOST_UNIT_TURN = threading.Lock()  # keep_reads: the Python reader's file objects belong to one chunk's job at a time
 _READER_TURN = threading.Lock()   # svt_bam_summarise starts a pool of threads that fills the host: one call at a time
 
 
@@ -64,6 +65,10 @@ class HipEngine:
 
     # `verdicts=True` (per call, or for every call from the constructor): Results.verdicts, one byte per record of the batch
     supports_verdicts = True
+
+    # `svtyper -w` with reader="device": the device reader builds the resident batches of this engine's device and its evidence
+    # dump behind them (NativeBam.evidence_device(dump=True))
+    supports_dump = True
 
     def __call__(self, batch: EvidenceBatch, flags: int = 0, site_qual=None, sample_major: int = 0, verdicts=None) -> Results:
         if self.verdicts if verdicts is None else verdicts:
@@ -345,15 +350,28 @@ class NativeUnitCollector:
     every (site, sample) unit and the summaries go straight to the device geometry + likelihood stages."""
 
     def __init__(self, samples: List[Sample], native_bams, split_weight: float, disc_weight: float,
-                 min_aligned: int, count_mode: int, max_reads, n_threads: int = 0, geometry: str = "reader", inflate: str = "host"):
+                 min_aligned: int, count_mode: int, max_reads, n_threads: int = 0, geometry: str = "reader", inflate: str = "host",
+                 keep_reads: bool = False, gather=None):
         """`geometry`: where the breakpoint-dependent predicates (parsers.py:785-857,1122-1215) are evaluated --
         "reader" (default): in the C++ reader's threads, which hands over 16-byte evidence records (svt_bam_evidence) for
         the canonical route of ANY engine; "device": 128-byte fragment summaries go to the device's geometry stage
         (svt_bam_summarise -> svt_batch_create_from_fragments, the HIP engine only); "walk" (the drivers' reader="device"):
         the reader inflates, the evidence records are built on the GPU from the inflated bytes (svt_bam_evidence_device, the
-        HIP engine only; units outside the walk's envelope are the host reader's).  Same records either way."""
+        HIP engine only; units outside the walk's envelope are the host reader's).  Same records either way.
+
+        keep_reads (`svtyper -w`, geometry="walk" only): every call asks for the evidence dump (svt_bam_evidence_device_dump) and the
+        job's Results carry `evidence`, site-major and sample-minor: per unit None (skipped by the max_reads rule), the unit's
+        slice of the dump -- finished BAM records, what driver.tag_and_write writes record by record --, or, for a unit whose reads
+        the dump does not hold (unit_host), the triple the Python reader gives for it: `gather(sample, breakpoint, max_reads)` +
+        packer.pack_fragments(side_table=True) on the sample's open bam.AlignmentFile, with the unit's slice of the batch's
+        verdicts.  The records the host reader spliced in for such a unit are the Python reader's byte for byte, so the verdicts
+        match the triple's side table."""
         if geometry not in ("reader", "device", "walk"):
             raise ValueError("geometry must be 'reader', 'device' or 'walk'")
+        if keep_reads and (geometry != "walk" or gather is None):
+            raise ValueError("keep_reads needs geometry='walk' (the device reader's evidence dump) and a gather function for the units it does not hold")
+        self.keep_reads = keep_reads
+        self.gather = gather
         if inflate not in ("host", "device") or (inflate == "device" and geometry != "walk"):
             raise ValueError("inflate must be 'host' or 'device', and 'device' is only legal with geometry='walk' (reader='device')")
         self.inflate = inflate           # geometry="walk": "device" = the BGZF inflate on the GPU too (svt_bam_evidence_device_inflate)
@@ -368,6 +386,8 @@ class NativeUnitCollector:
         self.split_weight = split_weight
         self.disc_weight = disc_weight
         _library_tables(self, samples)
+        # keep_reads: the index of every library in its group's table (what UnitCollector packs with)
+        self.lib_index = {id(lib): base + i for s, base in zip(samples, self.sample_base) for i, lib in enumerate(s.lib_dict.values())}
         self.rg_tables = []          # per sample: (read group ids, their library's index in the group's table or -1: not active)
         for s, base in zip(samples, self.sample_base):
             libs = list(s.lib_dict.values())
@@ -407,10 +427,12 @@ class NativeUnitCollector:
         kw = _site_qual_kw(engine, len(self.samples), site_quals)
         if (sites or blocks) and self.geometry == "device" and not hasattr(engine, "genotype_fragments"):
             raise TypeError("reader='native' with geometry='device' needs an engine with genotype_fragments (the HIP engine)")
+        if self.keep_reads and blocks:
+            raise ValueError("keep_reads takes its sites one by one (add_site): the units the dump does not hold need their breakpoint dicts")
         t_begin = time.perf_counter()
         prepared = self._prepare(SiteArrays.concat(blocks + [SiteArrays.from_dicts(sites)]))
         prep_s = time.perf_counter() - t_begin
-        return lambda: self._run_prepared(prepared, engine, flags, kw, prep_s)
+        return lambda: self._run_prepared(prepared, engine, flags, kw, prep_s, sites)
 
     def run(self, engine: Engine, flags: int) -> Results:
         return self.take(engine, flags)()
@@ -453,7 +475,7 @@ class NativeUnitCollector:
             prepared.append((bps, win))
         return prepared
 
-    def _run_prepared(self, prepared, engine: Engine, flags: int, kw: dict, prep_s: float = 0.0) -> Results:
+    def _run_prepared(self, prepared, engine: Engine, flags: int, kw: dict, prep_s: float = 0.0, sites=()) -> Results:
         import numpy as np
         from .geometry import FragmentBatch
         n_samp = len(self.samples)
@@ -468,7 +490,7 @@ class NativeUnitCollector:
         if self.geometry == "reader":
             return self._run_records(prepared, engine, flags, kw, lap)
         if self.geometry == "walk":
-            return self._run_walk(prepared, engine, flags, kw, lap)
+            return self._run_walk(prepared, engine, flags, kw, lap, sites)
         for k, (nbam, (bps, win)) in enumerate(zip(self.bams, prepared)):
             rgs, idx = self.rg_tables[k]
             with _READER_TURN:      # (two chunks in flight under ChunkPipeline: one reads, the other is on the device)
@@ -508,7 +530,18 @@ class NativeUnitCollector:
         """mean + 3 sd of every library of sample k's group (svt_batch_create_from_fragments' v_nondel)"""
         return [float(t.mean) + float(t.sd) * 3 for t in self.group_tables[self.group_of[k]]]
 
-    def _run_walk(self, prepared, engine: Engine, flags: int, kw: dict, lap) -> Results:
+    def _host_unit(self, k: int, breakpoint: dict, verdicts):
+        """keep_reads: a unit the dump does not hold, from the Python reader -- what UnitCollector keeps for it"""
+        with _HOST_UNIT_TURN:
+            fragments, many = self.gather(self.samples[k], breakpoint, self.max_reads)
+        if many or not fragments:
+            return None
+        recs, spans = pack_fragments(fragments, breakpoint, self.lib_index, self.min_aligned, SPLIT_SLOP, side_table=True)
+        if len(recs) != len(verdicts):
+            raise RuntimeError("a unit recomputed by the host reader has %d records, the Python reader gives %d" % (len(verdicts), len(recs)))
+        return (fragments, spans, verdicts)
+
+    def _run_walk(self, prepared, engine: Engine, flags: int, kw: dict, lap, sites=()) -> Results:
         """geometry="walk": one resident batch per sample, its records built in HBM by svt_bam_evidence_device (no evidence
         crosses PCIe but the units the host reader recomputes); the 128-byte result records of the samples are put side by
         side site-major, QUAL over a site's samples is summed on the host -- as the per-sample route of geometry="device"."""
@@ -517,7 +550,9 @@ class NativeUnitCollector:
         if not isinstance(getattr(engine, "device", None), int) or not hasattr(engine, "genotype_fragments"):
             raise TypeError("reader='device' needs the HIP engine")
         n_sites = int(prepared[0][0].shape[0])
+        n_samp = len(self.samples)
         per_sample = []
+        evidence = [None] * (n_sites * n_samp) if self.keep_reads else None
         for k, (nbam, (bps, win)) in enumerate(zip(self.bams, prepared)):
             rgs, idx = self.rg_tables[k]
             tables = self.group_tables[self.group_of[k]]
@@ -525,10 +560,27 @@ class NativeUnitCollector:
             head = EvidenceBatch(np.zeros(n_sites + 1, np.uint64), self._unit_headers(k, bps), np.zeros(0, ev.RECORD_DTYPE), tables,
                                  self.split_weight, self.disc_weight)
             with _READER_TURN:
-                d, _skipped, st = nbam.evidence_device(win, bps, rgs, idx, self.max_reads, self.count_mode, flank, self.min_aligned,
-                                                       SPLIT_SLOP, head, engine.device, flags, self.n_threads, inflate=self.inflate,
-                                                       count_host_blocks=os.environ.get("SVT_COUNT_HOST_BLOCKS", "0") == "1")
+                d, _skipped, st, *dump = nbam.evidence_device(win, bps, rgs, idx, self.max_reads, self.count_mode, flank, self.min_aligned,
+                                                              SPLIT_SLOP, head, engine.device, flags, self.n_threads, inflate=self.inflate,
+                                                              count_host_blocks=os.environ.get("SVT_COUNT_HOST_BLOCKS", "0") == "1",
+                                                              **({"dump": True} if self.keep_reads else {}))
             lap("svt_bam_evidence_device")
+            if self.keep_reads:
+                data, unit_off, unit_host = dump[0]
+                view, unit_off = memoryview(data), unit_off.tolist()
+                rec_off = verdicts = None
+                for i in range(n_sites):
+                    if _skipped[i]:
+                        continue
+                    if not unit_host[i]:
+                        evidence[i * n_samp + k] = view[unit_off[i]:unit_off[i + 1]]
+                        continue
+                    if verdicts is None:        # (the batch's verdicts and offsets come to the host only for such a unit)
+                        verdicts = d.verdicts()
+                        from .native_reads import batch_offsets
+                        rec_off = batch_offsets(d).tolist()
+                    evidence[i * n_samp + k] = self._host_unit(k, sites[i], verdicts[rec_off[i]:rec_off[i + 1]])
+                lap("evidence dump")
             for key, v in st.items():
                 if isinstance(v, dict):
                     mine = self.device_stats.setdefault(key, {})
@@ -541,7 +593,10 @@ class NativeUnitCollector:
                 per_sample.append(hip.host_sq(d.results()).rec)
             lap("genotype pass + results")
         res = Results(per_sample[0] if len(per_sample) == 1 else np.stack(per_sample, axis=1).reshape(-1))
-        return _with_site_qual(res, kw)
+        res = _with_site_qual(res, kw)
+        if self.keep_reads:
+            res.evidence = evidence
+        return res
 
     def _run_records(self, prepared, engine: Engine, flags: int, kw: dict, lap) -> Results:
         """geometry="reader": evidence records straight from the reader, ONE canonical batch over the samples of a library
