@@ -224,6 +224,28 @@ int svt_bgzf_inflate_host_verified(const uint8_t* data, uint64_t len, const uint
 int svt_bgzf_inflate_device_verified(const uint8_t* data, uint64_t len, const uint64_t* block_off, uint64_t n, uint8_t* out,
                                      const uint64_t* out_off, uint32_t* status, int device);
 
+/* ---- BGZF deflate by ONE piece of source (additions; the ABI number stays: probe for the symbols) ------------------
+ * svtyper_amd/csrc/svt_deflate.h compresses the payload of a BGZF member, 0 .. 65 280 bytes, into one fixed-Huffman
+ * (or stored) block whose bytes are a function of the payload alone: 64 chunks, a greedy parse per
+ * chunk over a private table seeded with the chunk in front.  It is compiled for the host and for the device
+ * (svt_deflate_kernel.h, one wavefront per member); both write the same bytes.
+ *
+ * Payload k is bytes[off[k] .. off[k + 1]) -- off holds n + 1 non-decreasing offsets.  Whole members (the header
+ * bam.BgzfWriter writes, the deflate bytes, the CRC-32 by svt_crc32.h, ISIZE) land side by side in out[0, capacity)
+ * at out_off[0 .. n] (out_off holds n + 1 entries, out_off[0] = 0).  All arrays are host memory.  SVT_ERR_INVALID:
+ * a payload above 65 280 bytes, offsets that decrease, a capacity below what the members need (out is never
+ * overrun; payload bytes + 31 n always suffice).                                                                    */
+int svt_bgzf_deflate_host(const uint8_t* bytes, const uint64_t* off, uint64_t n, uint8_t* out, uint64_t capacity,
+                          uint64_t* out_off);
+int svt_bgzf_deflate_device(const uint8_t* bytes, const uint64_t* off, uint64_t n, uint8_t* out, uint64_t capacity,
+                            uint64_t* out_off, int device);
+/* the calling thread's most recent svt_bgzf_deflate_device: its kernels by HIP events, apart from the copies */
+typedef struct svt_deflate_times {
+    double crc_kernel_s, deflate_kernel_s, pack_kernel_s;
+    double total_s;             /* the whole call on the host's clock: upload, kernels, download                     */
+} svt_deflate_times;
+int svt_bgzf_deflate_last_times(svt_deflate_times* times);
+
 /* Verify: a property of the handle, off by default (0).  With it on, every call that takes the handle checks the
  * CRC-32 of every BGZF member it inflates, where it inflates it: the host reader's threads (libdeflate's or zlib's
  * crc32), or svt_crc32_kernel behind svt_inflate_kernel for the routes that inflate on the GPU (the expected values

@@ -7,7 +7,7 @@ Only what SURVEY.md section 3.5 lists is implemented:
     AlignmentFile(path, 'rb'): filename, header['RG'], references, lengths, gettid(), fetch(),
                                count(read_callback='all'), mapped, unmapped, close()
     AlignmentFile(path, 'wb', template=...): write(read), close() -- the evidence dump of `svtyper -w`: the template's
-                               header, every record without its sequence, BGZF through zlib
+                               header, every record without its sequence, BGZF through zlib (or deflate="host" / "device")
     AlignedSegment: query_name, flag and its bits, reference_id/name, reference_start (= pos),
                     reference_end, mapping_quality, template_length, cigar (= cigartuples),
                     has_tag/get_tag/set_tag, get_overlap, query_length, query_alignment_length,
@@ -124,15 +124,33 @@ BGZF_EOF = bytes.fromhex("1f8b08040000000000ff0600424302001b00030000000000000000
 _BGZF_PAYLOAD = 0xff00      # bytes of payload per member, htslib's block size: with its header a stored member stays within 64 KiB
 
 
-class BgzfWriter:
-    """A BGZF file written member by member through zlib: at most 65 280 bytes of payload each, its CRC32 and ISIZE behind
-    the deflate stream, the 28-byte empty member at the end.  (Readable by any BGZF reader; not the bytes htslib's deflate
-    would produce.)"""
+DEFLATE_CHOICES = ("zlib", "host", "device")
+_BGZF_BATCH = 256           # finished payloads handed to svt_bgzf_deflate_host / _device in one call
 
-    def __init__(self, path: str, level: int = 6):
-        self._f = open(path, "wb")
+
+def check_deflate(deflate) -> str:
+    if deflate not in DEFLATE_CHOICES:
+        raise ValueError("deflate must be one of %s, not %r" % (", ".join(repr(c) for c in DEFLATE_CHOICES), deflate))
+    return deflate
+
+
+class BgzfWriter:
+    """A BGZF file written member by member: at most 65 280 bytes of payload each, its CRC32 and ISIZE behind the deflate
+    stream, the 28-byte empty member at the end.  `path_or_file`: a path, or a binary file object (closed by close()).
+
+    deflate="zlib": every member goes through zlib at `level` as it is cut.  (Readable by any BGZF reader; not the bytes
+    htslib's deflate would produce.)  deflate="host" / "device": finished payloads are collected and compressed _BGZF_BATCH at a
+    time by one call of the library's own compressor (svtyper_amd/csrc/svt_deflate.h), on this thread or on GPU `device`; the
+    library is imported with the first batch.  Where a payload is cut is decided before anybody compresses it, so the inflated
+    stream and the member boundaries are the same for all three."""
+
+    def __init__(self, path_or_file, level: int = 6, deflate: str = "zlib", device: int = 0):
+        self._deflate = check_deflate(deflate)
+        self._f = path_or_file if hasattr(path_or_file, "write") else open(path_or_file, "wb")
         self._level = level
+        self._device = device
         self._buf = bytearray()
+        self._pending: List[bytes] = []      # (host / device) payloads that are cut and not yet compressed
 
     def write(self, data: bytes) -> None:
         self._buf += data
@@ -147,11 +165,26 @@ class BgzfWriter:
         self.write(data)
 
     def flush(self) -> None:
+        """what is buffered becomes a member of its own (with host / device: once its batch is compressed -- drain())"""
         if self._buf:
             self._member(bytes(self._buf))
             del self._buf[:]
 
+    def drain(self) -> None:
+        """(host / device) the payloads cut so far compressed and written"""
+        if not self._pending:
+            return
+        from . import native_reads
+        members, _off = native_reads.bgzf_deflate(self._pending, device=self._device if self._deflate == "device" else None)
+        del self._pending[:]
+        self._f.write(members.tobytes())
+
     def _member(self, payload: bytes) -> None:
+        if self._deflate != "zlib":
+            self._pending.append(payload)
+            if len(self._pending) >= _BGZF_BATCH:
+                self.drain()
+            return
         for level in (self._level, 0):      # (level 0 = stored: payload + 5 bytes per deflate block, always within a member)
             z = zlib.compressobj(level, zlib.DEFLATED, -15)
             cdata = z.compress(payload) + z.flush()
@@ -163,6 +196,7 @@ class BgzfWriter:
     def close(self) -> None:
         if self._f is not None:
             self.flush()
+            self.drain()
             self._f.write(BGZF_EOF)
             self._f.close()
             self._f = None
@@ -420,7 +454,7 @@ class AlignmentFile:
         if mode.startswith("w"):
             if mode != "wb":
                 raise NotImplementedError("only BAM output (mode 'wb') is written")
-            self._open_for_writing(path, kwargs.get("template", template))
+            self._open_for_writing(path, kwargs.get("template", template), kwargs.get("deflate", "zlib"), kwargs.get("device", 0))
             return
         self._bgzf = BgzfReader(path, verify=bool(kwargs.get("verify", False)))
         raw = []        # the header as it lies in the file: a file opened 'wb' with this one as template starts with these bytes
@@ -621,15 +655,16 @@ class AlignmentFile:
         self._bgzf.close()
 
     # ---- writing (mode 'wb')
-    def _open_for_writing(self, path: str, template):
-        """pysam.AlignmentFile(path, 'wb', template): the template's header text and reference list, byte for byte."""
+    def _open_for_writing(self, path: str, template, deflate: str = "zlib", device: int = 0):
+        """pysam.AlignmentFile(path, 'wb', template): the template's header text and reference list, byte for byte.  `deflate`,
+        `device`: who compresses the members (BgzfWriter)."""
         header = getattr(template, "_header_bytes", None)
         if header is None:
             raise TypeError("mode 'wb' needs template=: an AlignmentFile of this module opened for reading")
         self.text, self.header = template.text, template.header
         self.references, self.lengths = template.references, template.lengths
         self._tid = dict(template._tid)
-        self._writer = BgzfWriter(path)
+        self._writer = BgzfWriter(path, deflate=deflate, device=device)
         self._writer.write(header)
         self._writer.flush()            # (records start in a block of their own, as htslib leaves them)
 

@@ -13,6 +13,7 @@
 
 #include "../../include/svtyper_reads.h"
 #include "svt_crc32.h"
+#include "svt_deflate.h"
 #include "svt_inflate.h"
 
 namespace svt {
@@ -36,6 +37,8 @@ uint32_t host_crc32(const uint8_t* p, size_t n);
 // the host-built tables of svt_crc32.h (built once), and the argument checks of svt_bgzf_crc32_host / _device
 const crc::Tables& crc_tables();
 int crc_check_offsets(const uint8_t* bytes, const uint64_t* off, uint64_t n, const uint32_t* crc);
+// the argument checks of svt_bgzf_deflate_host / _device (svt_deflate.h); `slots`: the bytes all members take at the most
+int deflate_check_args(const uint8_t* bytes, const uint64_t* off, uint64_t n, const uint8_t* out, const uint64_t* out_off, uint64_t& slots);
 // Around a call that takes a handle: what the handle's tally gained in between becomes the calling thread's svt_bgzf_verify_stats.
 // (A call inside a call -- the host scan behind a device scan -- reports into the outer one's figures: the outer scope ends last.)
 struct VerifyScope {

@@ -471,6 +471,21 @@ int crc_check_offsets(const uint8_t* bytes, const uint64_t* off, uint64_t n, con
     return SVT_OK;
 }
 
+// the arguments of svt_bgzf_deflate_host / _device
+int deflate_check_args(const uint8_t* bytes, const uint64_t* off, uint64_t n, const uint8_t* out, const uint64_t* out_off, uint64_t& slots)
+{
+    slots = 0;
+    if (!off || !out_off || (n && !out)) return fail(SVT_ERR_INVALID, "null argument");
+    if (n > 0xFFFFFFFFull) return fail(SVT_ERR_INVALID, "svt_bgzf_deflate: too many members in one call (< 2^32)");
+    for (uint64_t k = 0; k < n; ++k) {
+        if (off[k + 1] < off[k]) return fail(SVT_ERR_INVALID, "svt_bgzf_deflate: off must not decrease");
+        if (off[k + 1] - off[k] > dfl::kMaxPayload) return fail(SVT_ERR_INVALID, "svt_bgzf_deflate: a payload has at most 65280 bytes");
+        slots += dfl::slot_bytes((uint32_t)(off[k + 1] - off[k]));
+    }
+    if (n && off[n] > off[0] && !bytes) return fail(SVT_ERR_INVALID, "null argument");
+    return SVT_OK;
+}
+
 namespace bgzf {
 
 int bgzf_members(const uint8_t* data, uint64_t len, const uint64_t* block_off, uint64_t n, const uint8_t* out, const uint64_t* out_off,

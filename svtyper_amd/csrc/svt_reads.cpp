@@ -1683,6 +1683,36 @@ int svt_bgzf_crc32_host(const uint8_t* bytes, const uint64_t* off, uint64_t n, u
     });
 }
 
+// svt_deflate.h on this thread, member by member: each into a slot of its own first, since its size is known only afterwards
+int svt_bgzf_deflate_host(const uint8_t* bytes, const uint64_t* off, uint64_t n, uint8_t* out, uint64_t capacity, uint64_t* out_off)
+{
+    namespace dfl = svt::dfl;
+    return guarded([&]() -> int {
+        uint64_t slots = 0;
+        if (const int rc = svt::deflate_check_args(bytes, off, n, out, out_off, slots)) return rc;
+        std::unique_ptr<dfl::Scratch<dfl::HostCtx::kWidth>> S(new dfl::Scratch<dfl::HostCtx::kWidth>());
+        std::unique_ptr<svt::crc::Scratch> C(new svt::crc::Scratch());
+        std::vector<uint8_t> slot(dfl::slot_bytes(dfl::kMaxPayload));
+        uint64_t at = 0;
+        out_off[0] = 0;
+        for (uint64_t k = 0; k < n; ++k) {
+            const uint8_t* p = bytes + off[k];
+            const uint32_t len = (uint32_t)(off[k + 1] - off[k]);
+            const uint32_t clen = dfl::deflate_member<dfl::HostCtx>(p, len, slot.data() + dfl::kHeaderBytes, dfl::cdata_bound(len), *S);
+            if (!clen) return fail(SVT_ERR_INVALID, "svt_bgzf_deflate: a payload was refused");
+            const uint64_t size = (uint64_t)dfl::kHeaderBytes + clen + dfl::kTrailerBytes;
+            if (size > capacity - at) return fail(SVT_ERR_INVALID, "svt_bgzf_deflate: capacity is below what the members need");
+            const uint32_t crc = svt::crc::crc_member<svt::crc::HostCtx>(p, len, svt::crc_tables(), *C);
+            for (uint32_t i = 0; i < dfl::kHeaderBytes; ++i) slot[i] = dfl::header_byte(i, clen);
+            for (uint32_t i = 0; i < dfl::kTrailerBytes; ++i) slot[dfl::kHeaderBytes + clen + i] = dfl::trailer_byte(i, crc, len);
+            std::memcpy(out + at, slot.data(), size);
+            at += size;
+            out_off[k + 1] = at;
+        }
+        return SVT_OK;
+    });
+}
+
 int svt_bam_set_verify(svt_bam* bam, int on)
 {
     return guarded([&]() -> int {

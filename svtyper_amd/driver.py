@@ -118,6 +118,7 @@ class Driver:
     site_quals = False
     bulk_under_debug = True
     alignment_outpath = None            # (`svtyper -w`; classic.Classic sets it)
+    deflate = "zlib"                    # who compresses the `-w` BAM's members (bam.BgzfWriter)
 
     def __init__(self, bam_string, vcf_in, vcf_out, min_aligned, split_weight, disc_weight, num_samp, lib_info_path, debug,
                  ref_fasta, sum_quals, max_reads, max_ci_dist, n_threads=0):
@@ -161,7 +162,8 @@ class Driver:
         out_bam, written = None, set()
         if writing:     # classic.py:161-166: the first alignment file is the template, its header is the dump's
             template = AlignmentFile(paths[0], "rb")
-            out_bam = AlignmentFile(self.alignment_outpath, "wb", template=template)
+            out_bam = AlignmentFile(self.alignment_outpath, "wb", template=template, deflate=self.deflate,
+                                    device=getattr(engine, "device", 0))
             template.close()
         self.write_library_file()
         if self.vcf_in is None:
@@ -344,6 +346,11 @@ def parse_arguments(p, bam_help, max_reads, own):
                         "(needs --reader native or device; same library file, same output bytes) [host]")
     p.add_argument("--geometry", choices=("host", "device"), default="host",
                    help="with --reader python: breakpoint-dependent read predicates on the host or on the GPU [host]")
+    # BGZF output (README).  Not listed by --help, like --debug: the help text of both programs is pinned byte for byte
+    # (tests/golden/help_*.txt).  --bgzf: the output VCF as BGZF (.vcf.gz: what bcftools, tabix and IGV read); --deflate: who
+    # compresses BGZF output (--bgzf, -w) -- zlib, or the library's own compressor on the host or on the GPU (same inflated bytes).
+    p.add_argument("--bgzf", action="store_true", help=argparse.SUPPRESS)
+    p.add_argument("--deflate", choices=("zlib", "host", "device"), default="zlib", help=argparse.SUPPRESS)
     args = p.parse_args()
     if args.input_vcf is None and not sys.stdin.isatty():
         args.input_vcf = sys.stdin
@@ -360,12 +367,25 @@ def run_main(driver, sharded_driver, call, args):
                    verify="crc32" if args.verify_bgzf else "off")
     job = sharded.job()
     if job is None:
-        return driver(*call, **options)
+        if not args.bgzf:
+            return driver(*call, **options)
+        with _bgzf_text(call[2], args.deflate, 0) as out:
+            return driver(*call[:2], out, *call[3:], **options)
     rank, world, local_rank = job
     call = call[:2] + (sharded.private_stdout(call[2]),) + call[3:]
     engine = sharded.init(local_rank)
-    sharded_driver(*call, rank=rank, world=world, engine=engine, **options)
+    if args.bgzf and rank == 0:             # (rank 0 writes everything: the others touch nothing)
+        with _bgzf_text(call[2], args.deflate, getattr(engine, "device", local_rank)) as out:
+            sharded_driver(*call[:2], out, *call[3:], rank=rank, world=world, engine=engine, **options)
+    else:
+        sharded_driver(*call, rank=rank, world=world, engine=engine, **options)
     sharded.finish()
+
+
+def _bgzf_text(vcf_out, deflate, device):
+    """`--bgzf`: the output VCF through bgzf_out.open_text (imported only here)"""
+    from . import bgzf_out
+    return bgzf_out.open_text(vcf_out, deflate=deflate, device=device)
 
 
 def run_cli(main):

@@ -130,6 +130,11 @@ def verify_stats() -> dict:
     return st.as_dict()
 
 
+class _DeflateTimes(C.Structure):
+    """include/svtyper_reads.h: svt_deflate_times"""
+    _fields_ = [("crc_kernel_s", C.c_double), ("deflate_kernel_s", C.c_double), ("pack_kernel_s", C.c_double), ("total_s", C.c_double)]
+
+
 class _InflateStats(C.Structure):
     """include/svtyper_reads.h: svt_evidence_inflate_stats"""
     _fields_ = [("blocks_inflated", C.c_uint64), ("blocks_failed", C.c_uint64), ("compressed_bytes", C.c_uint64),
@@ -237,6 +242,13 @@ def _lib():
         L.svt_bgzf_crc32_host.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
         L.svt_bgzf_crc32_device.restype = C.c_int
         L.svt_bgzf_crc32_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_int]
+        if hasattr(L, "svt_bgzf_deflate_host"):    # (added without a new ABI number: a library built before it lacks the symbols)
+            L.svt_bgzf_deflate_host.restype = C.c_int
+            L.svt_bgzf_deflate_host.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p]
+            L.svt_bgzf_deflate_device.restype = C.c_int
+            L.svt_bgzf_deflate_device.argtypes = L.svt_bgzf_deflate_host.argtypes + [C.c_int]
+            L.svt_bgzf_deflate_last_times.restype = C.c_int
+            L.svt_bgzf_deflate_last_times.argtypes = [C.POINTER(_DeflateTimes)]
         L.svt_bam_set_verify.restype = C.c_int
         L.svt_bam_set_verify.argtypes = [C.c_void_p, C.c_int]
         L.svt_bam_get_verify.restype = C.c_int
@@ -693,3 +705,48 @@ def bgzf_inflate(data: bytes, block_off: np.ndarray, out_off: np.ndarray, device
     else:
         hip._check((L.svt_bgzf_inflate_device_verified if verified else L.svt_bgzf_inflate_device)(*args, int(device)))
     return out[:int(out_off[-1])], status[:n]
+
+
+DEFLATE_MAX_PAYLOAD = 65280      # bytes of payload in one member (svt_deflate.h: dfl::kMaxPayload)
+DEFLATE_SLOT_EXTRA = 31          # what a member takes beyond its payload at the most: header, a stored block's 5 bytes, trailer
+
+
+def bgzf_deflate(payloads: Sequence[bytes], device: Optional[int] = None, capacity: Optional[int] = None) -> Tuple[np.ndarray, np.ndarray]:
+    """svt_bgzf_deflate_host (device None) / svt_bgzf_deflate_device: every payload (at most 65 280 bytes) as one whole BGZF
+    member, by the one-source compressor (svt_deflate.h).  Returns (members uint8 [out_off[-1]], out_off uint64 [n + 1]).
+    `capacity`: the room offered for the members (default: what always suffices)."""
+    sizes = np.fromiter((len(p) for p in payloads), np.uint64, len(payloads))
+    off = np.zeros(len(payloads) + 1, np.uint64)
+    np.cumsum(sizes, out=off[1:])
+    return bgzf_deflate_at(b"".join(payloads), off, device, capacity)
+
+
+def bgzf_deflate_at(data: bytes, off: np.ndarray, device: Optional[int] = None, capacity: Optional[int] = None) -> Tuple[np.ndarray, np.ndarray]:
+    """bgzf_deflate over payloads that lie in `data` already: payload k is data[off[k] .. off[k + 1])"""
+    L = _lib()
+    if not hasattr(L, "svt_bgzf_deflate_host"):
+        raise hip.SvtyperHipError("this libsvtyper_hip.so has no svt_bgzf_deflate_host (built before BGZF deflate)")
+    off = np.ascontiguousarray(off, np.uint64)
+    n = int(off.shape[0]) - 1
+    if n < 0:
+        raise ValueError("off must hold n + 1 entries")
+    buf = np.frombuffer(bytes(data), np.uint8) if len(data) else np.zeros(1, np.uint8)
+    if capacity is None:
+        capacity = int(off[-1] - off[0]) + DEFLATE_SLOT_EXTRA * n if int(off[-1]) >= int(off[0]) else 0
+    out = np.zeros(max(int(capacity), 1), np.uint8)
+    out_off = np.zeros(n + 1, np.uint64)
+    args = [buf.ctypes.data, off.ctypes.data, n, out.ctypes.data, int(capacity), out_off.ctypes.data]
+    if device is None:
+        hip._check(L.svt_bgzf_deflate_host(*args))
+    else:
+        hip._check(L.svt_bgzf_deflate_device(*args, int(device)))
+    return out[:int(out_off[-1])], out_off
+
+
+def bgzf_deflate_last_times() -> Dict[str, float]:
+    """svt_bgzf_deflate_last_times: the kernels of this thread's last bgzf_deflate on a device, from HIP events, and the call's
+    wall time"""
+    L = _lib()
+    t = _DeflateTimes()
+    hip._check(L.svt_bgzf_deflate_last_times(C.byref(t)))
+    return {name: float(getattr(t, name)) for name, _ in _DeflateTimes._fields_}
