@@ -1,4 +1,4 @@
-// svt_bam_index.h -- the index of a BAM file, BAI or CSI, as one model (host only; used by svt_reads.cpp).
+// svt_bam_index.h -- the index of a BAM file, BAI or CSI, as one model (host only; used by svt_reads_handle.h and svt_reads_records.h, parts of svt_reads.cpp).
 //
 // Both formats say the same thing in two shapes (SAM spec 5.2, CSIv1): per reference a map bin -> chunks over a binning scheme
 // of `depth` levels whose leaves span 2^min_shift positions, and something that bounds a fetch from below -- the linear index of a

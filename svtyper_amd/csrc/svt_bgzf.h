@@ -1,7 +1,7 @@
 // svt_bgzf.h -- BGZF members on the host, for both translation units of the library: the set of members every arena route
 // inflates (the open-range arena, the library scan's rounds, the parity entries), the ONE host loop that inflates and verifies
 // such a set, and what verify (svt_bam_set_verify) counts.  A member's header is parsed in one place, inf::member_at
-// (svt_inflate.h).  Defined in svt_bgzf_reader.h, a part of svt_reads.cpp with the reader itself; the device side of a set is
+// (svt_inflate.h).  Defined in svt_bgzf_reader.h, the first part of svt_reads.cpp, in front of the reader itself (svt_reads_*.h); the device side of a set is
 // svt_entry_inflate.h.  Internal C++ (not exported: svt_exports.map lets only svt_* C names out).
 #ifndef SVT_BGZF_H
 #define SVT_BGZF_H

@@ -114,7 +114,7 @@ uint32_t verify_member(const uint8_t* out, uint32_t isize, uint32_t stored, svt:
 {
     const auto t0 = std::chrono::steady_clock::now();
     const uint32_t crc = one_source ? svt::crc::crc_member<svt::crc::HostCtx>(out, isize, svt::crc_tables(), *one_source) : svt::host_crc32(out, isize);
-    n.crc_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    n.crc_s += svt::seconds_since(t0);
     ++n.verified;
     if (computed) *computed = crc;
     if (crc == stored) return svt::inf::INF_OK;
@@ -344,7 +344,7 @@ private:
         b->next = next;
         const auto t_inflate = std::chrono::steady_clock::now();
         bool inflated = decoder_.inflate(cdata, clen, b->data.data(), isize);
-        inflate_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - t_inflate).count();
+        inflate_s += svt::seconds_since(t_inflate);
         ++n_inflated;
         if (verify_ && inflated) {                       // a mismatch is a block that does not inflate, with a text of its own
             const uint32_t stored = svt::inf::member_crc(cdata, 0, clen);

@@ -1,7 +1,7 @@
 // svt_dump_rules.h -- the evidence dump of `svtyper -w` from the walk's source rows: verdict bytes + the alignment records in the
 // arena -> the BAM records the reference would have written.
 //
-// ONE piece of source for both places that run it: the host (svt_bam_evidence_dump_walk_host in svt_reads.cpp, any C++17
+// ONE piece of source for both places that run it: the host (svt_bam_evidence_dump_walk_host in svt_reads_walk.h, any C++17
 // compiler; tests/native/asan_dump_rules_main.cpp runs it under AddressSanitizer) and the device (svt_dump_kernel.h).  Two rules:
 //
 //   (a) the decision per fragment -- driver.tag_and_write statement for statement (classic.py:296-413, parsers.py:771-782,

@@ -53,8 +53,6 @@ struct EvidenceCall : CallStream {
                  int device_, unsigned flags_, EvidenceRoute route_, svt_evidence_device_stats& S_)
         : bam(bam_), args(args_), geometry(geometry_), header(header_), device(device_), flags(flags_), route(route_), S(S_) {}
     ~EvidenceCall() { drain(); }
-    static std::chrono::steady_clock::time_point now() { return std::chrono::steady_clock::now(); }
-    static double since(std::chrono::steady_clock::time_point t0) { return std::chrono::duration<double>(now() - t0).count(); }
 
     // host: BAI lookup, and either inflate + arena or the arena's layout from BGZF headers
     int build_arena()
@@ -81,7 +79,7 @@ struct EvidenceCall : CallStream {
     // of the count pass
     int upload_inputs()
     {
-        const auto t0 = now();
+        const auto t0 = std::chrono::steady_clock::now();
         const std::vector<double> flank(geometry->lib_flank, geometry->lib_flank + geometry->n_libs);
         {
             Stager st(s);
@@ -92,11 +90,11 @@ struct EvidenceCall : CallStream {
                 SVT_TRY(d_compressed.get(plan.set.compressed_bytes + 8));
                 SVT_TRY(inflate.upload(plan.set, d_compressed.p, st, bam_verify(bam)));   // (verify: the expected CRC-32s go up with the member table)
                 SVT_TRY(st.finish());
-                I.compressed_upload_s = since(t0);
-                const auto t_kernel = now();
+                I.compressed_upload_s = seconds_since(t0);
+                const auto t_kernel = std::chrono::steady_clock::now();
                 std::vector<uint32_t> member_status;
                 SVT_TRY(inflate.run(d_compressed.p, d_arena.p, s, member_status));
-                I.inflate_kernel_s = since(t_kernel);
+                I.inflate_kernel_s = seconds_since(t_kernel);
                 I.blocks_failed = ew::apply_member_status(plan, member_status, arena);
             } else SVT_TRY(st.copy(d_arena.p, arena.bytes.data(), arena.bytes.size()));
             SVT_TRY(upload(d_ranges, arena.ranges, st));
@@ -117,7 +115,7 @@ struct EvidenceCall : CallStream {
         SVT_TRY(d_reads.alloc(n * sizeof(uint32_t)));
         SVT_TRY(d_off.alloc((n + 1) * sizeof(uint64_t)));
         HIP_TRY(hipStreamSynchronize(s));
-        S.upload_s = since(t0);
+        S.upload_s = seconds_since(t0);
         return SVT_OK;
     }
     // the kernels' arguments over the uploaded buffers
@@ -173,7 +171,7 @@ struct EvidenceCall : CallStream {
         n_deep = (uint32_t)deep_unit.size();
         deep_grid = std::min(n_deep, kDeepMaxSlices);
         if (!n_deep) return SVT_OK;
-        const auto t_deep = now();
+        const auto t_deep = std::chrono::steady_clock::now();
         std::vector<uint32_t> deep_status(n_deep), deep_rows(n_deep);
         DS.units_deep = n_deep;
         DS.workspace_bytes = (uint64_t)deep_grid * ew::kDeepSliceBytes;
@@ -199,7 +197,7 @@ struct EvidenceCall : CallStream {
         HIP_TRY(hipMemcpyAsync(deep_rows.data(), d_deep_rows.p, n_deep * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
         HIP_TRY(hipStreamSynchronize(s));
         for (uint32_t k = 0; k < n_deep; ++k) { status[deep_unit[k]] = deep_status[k]; rows[deep_unit[k]] = deep_rows[k]; }
-        DS.deep_walk_s = since(t_deep);
+        DS.deep_walk_s = seconds_since(t_deep);
         return SVT_OK;
     }
     // host: the units outside the envelope, by the reader itself
@@ -270,13 +268,13 @@ struct EvidenceCall : CallStream {
         }
         HIP_TRY(hipStreamSynchronize(s));
         if (n_deep) {                                            // (behind a sync of its own: its time is reported apart)
-            const auto t_deep = now();
+            const auto t_deep = std::chrono::steady_clock::now();
             da.records = static_cast<uint4*>(d_records.p);
             if (route.dump) hipLaunchKernelGGL(svt_evidence_deep_src_kernel, dim3(deep_grid), dim3(kEvidenceBlock), 0, s, da, d_src_rows.as<ew::SrcRow>());
             else hipLaunchKernelGGL(svt_evidence_deep_kernel<true>, dim3(deep_grid), dim3(kEvidenceBlock), 0, s, da);
             HIP_TRY(hipGetLastError());
             HIP_TRY(hipStreamSynchronize(s));
-            DS.deep_walk_s += since(t_deep);
+            DS.deep_walk_s += seconds_since(t_deep);
         }
         return SVT_OK;
     }
@@ -301,7 +299,7 @@ struct EvidenceCall : CallStream {
     int dump_pass(svt_batch* b)
     {
         svt_evidence_dump& D = *route.dump;
-        const auto t0 = now();
+        const auto t0 = std::chrono::steady_clock::now();
         D.unit_offset = static_cast<uint64_t*>(std::calloc(n + 1, sizeof(uint64_t)));
         D.unit_host = static_cast<uint8_t*>(std::calloc(std::max<uint64_t>(n, 1), 1));
         if (!D.unit_offset || !D.unit_host) return fail(SVT_ERR_NOMEM, "out of host memory");
@@ -309,7 +307,7 @@ struct EvidenceCall : CallStream {
         if (n == 0 || n_rec == 0) {
             D.units_host = host_ids.size();
             D.bytes = static_cast<uint8_t*>(std::malloc(1));
-            D.dump_s = since(t0);
+            D.dump_s = seconds_since(t0);
             return D.bytes ? SVT_OK : fail(SVT_ERR_NOMEM, "out of host memory");
         }
         HIP_TRY(hipStreamSynchronize(b->stream));                // (the batch's tables and offsets are up)
@@ -375,7 +373,7 @@ struct EvidenceCall : CallStream {
             SVT_TRY(d2h_staged(D.bytes, d_dump_bytes.p, D.n_bytes, s));
             if (error) return fail(SVT_ERR_INTERNAL, "svt_bam_evidence_device_dump: a read does not give the bytes it was sized for");
         }
-        D.dump_s = since(t0);
+        D.dump_s = seconds_since(t0);
         return SVT_OK;
     }
 };
@@ -404,20 +402,20 @@ static int svt_bam_evidence_device_impl(const svt_bam* bam, const svt_summarise_
     SVT_TRY(c.upload_inputs());                              // (S.upload_s; device inflate: its kernel too)
     SVT_TRY(c.bind_arguments());
 
-    auto t0 = c.now();
+    auto t0 = std::chrono::steady_clock::now();
     SVT_TRY(c.count_pass());
     SVT_TRY(c.deep_count());
-    S.device_walk_s = c.since(t0);
-    t0 = c.now();
+    S.device_walk_s = seconds_since(t0);
+    t0 = std::chrono::steady_clock::now();
     SVT_TRY(c.host_fallback());
-    S.host_fallback_s = c.since(t0);
+    S.host_fallback_s = seconds_since(t0);
     SVT_TRY(c.offset_scan(skipped_out));
-    t0 = c.now();
+    t0 = std::chrono::steady_clock::now();
     SVT_TRY(c.write_pass());
-    S.device_walk_s += c.since(t0);
-    t0 = c.now();
+    S.device_walk_s += seconds_since(t0);
+    t0 = std::chrono::steady_clock::now();
     SVT_TRY(c.make_batch(out));
-    S.batch_create_s = c.since(t0);
+    S.batch_create_s = seconds_since(t0);
     if (route.dump) {
         const int rc = c.dump_pass(*out);
         if (rc != SVT_OK) {                                      // (no batch without its dump)

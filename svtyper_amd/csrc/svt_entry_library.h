@@ -1,6 +1,6 @@
 // svt_entry_library.h -- part of the single translation unit svtyper_hip.hip (included there, in order; not a stand-alone header):
 // C ABI: svt_bam_scan_libraries_device (include/svtyper_reads.h).  The rounds, the prefix sums, the stop rule, the merge and the
-// host scan for whatever is outside the envelope are lw::scan_libraries (svt_reads.cpp), the same code the host twin runs; here
+// host scan for whatever is outside the envelope are lw::scan_libraries (svt_reads_library.h), the same code the host twin runs; here
 // is only the route's Backend: the arena and the tables in HBM, svt_inflate_kernel and svt_library_kernel.
 
 extern "C++" {

@@ -1,7 +1,7 @@
 // svt_entry_oneshot.h -- part of the single translation unit svtyper_hip.hip (included there, in order; not a stand-alone header):
 // C ABI: svt_trim, svt_genotype (one shot), svt_shard_bounds / svt_chunk_bounds, svt_genotype_multi.
 
-void svt_reads_trim();      // svt_reads.cpp: the reader's pooled gather buffers
+void svt_reads_trim();      // svt_reads_pool.h: the reader's pooled gather buffers
 
 void svt_trim(void)
 {

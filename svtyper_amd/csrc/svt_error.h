@@ -5,6 +5,7 @@
 #include <pthread.h>
 
 #include <atomic>
+#include <chrono>
 #include <condition_variable>
 #include <cstdint>
 #include <exception>
@@ -42,6 +43,12 @@ int guarded(F&& f) noexcept
     } catch (...) {
         return SVT_ERR_INTERNAL;
     }
+}
+
+// wall seconds from `t0` to now: what the stages' statistics are made of
+inline double seconds_since(std::chrono::steady_clock::time_point t0)
+{
+    return std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
 }
 
 // Parked worker threads of the host-side stages.  The calls that use run_threads() are short -- the reader of a chunk,

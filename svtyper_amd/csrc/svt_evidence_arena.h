@@ -1,4 +1,4 @@
-// svt_evidence_arena.h -- what the reader (svt_reads.cpp) hands to the two callers of svt_evidence_walk.h: the arena of inflated
+// svt_evidence_arena.h -- what the reader (svt_reads_arena.h, a part of svt_reads.cpp) hands to the two callers of svt_evidence_walk.h: the arena of inflated
 // BGZF payloads of one call with the per-unit record ranges in it, and the host recomputation of single units.  Internal C++
 // (not exported: svt_exports.map lets only svt_* C names out).
 #ifndef SVT_EVIDENCE_ARENA_H
@@ -54,7 +54,7 @@ struct Arena {
 // number of kept reads is walked once more with the deep tier's tables when they hold that many.
 inline bool deep_tier_unit(uint32_t status, uint32_t n_reads) { return status == EW_READS && n_reads <= kMaxReadsDeep; }
 
-// The arena comes from ONE planner in svt_reads.cpp with two routes.  Shared: the argument checks, the names, every unit's windows
+// The arena comes from ONE planner in svt_reads_arena.h with two routes.  Shared: the argument checks, the names, every unit's windows
 // cut into index chunks on the reader's threads, the runs of blocks the ranges need, the 32-bit limit of the arena's offsets (a
 // unit behind it is preset to EW_RANGE) and the ranges.  A route says how a chunk becomes a range and how a run is placed.
 

@@ -1,6 +1,6 @@
 // svt_evidence_walk.h -- alignment records in inflated BAM bytes -> the evidence records of one (breakpoint, sample) unit.
 //
-// ONE piece of source for both places that run it: the host (svt_bam_evidence_walk_host in svt_reads.cpp, any C++17 compiler:
+// ONE piece of source for both places that run it: the host (svt_bam_evidence_walk_host in svt_reads_walk.h, any C++17 compiler:
 // this is where the walk is proven, fuzzed and sanitised) and the device (svt_evidence_kernel.h, hipcc, one workgroup per unit).
 // What a record means -- its fixed fields, CIGAR, tags, aligned intervals, the split-read candidate -- is svt_record_rules.h,
 // the same functions the host reader's process_unit calls.  The walk's own is here: its capacities and reasons, the two passes
@@ -348,7 +348,7 @@ SVT_HD void gather_window(const Params& P, SC& S, const Tables<typename SC::Idx>
                     if ((uint64_t)pos + 4 > rg.end) { S.status = EW_RANGE; break; }
                     const uint32_t size = ld32(P.arena + pos);
                     if (size < 32 || size > kMaxRecord || (uint64_t)pos + 4 + size > rg.end) { S.status = EW_RANGE; break; }
-                    // the fetch's own stop rule (svt_reads.cpp: fetch() / build_arena): the first record on another reference or at /
+                    // the fetch's own stop rule (fetch() in svt_reads_records.h / build_arena in svt_reads_arena.h): the first record on another reference or at /
                     // behind the window's end ends the window
                     if (P.open_ranges && ((int32_t)ld32(P.arena + pos + 4) != wtid || (int64_t)(int32_t)ld32(P.arena + pos + 8) >= hi)) { S.window_done = 1; break; }
                     S.b.off[nb] = pos + 4;

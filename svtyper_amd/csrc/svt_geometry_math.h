@@ -2,7 +2,7 @@
 // (svtyper/parsers.py:785-857, 1122-1215; the walk of svtyper/classic.py:296-396 per fragment).
 //
 // ONE statement of the predicates for both places that evaluate them: the device stage over fragment summaries
-// (svt_geometry_kernel.h, hipcc) and the native reader when it hands over evidence records directly (svt_reads.cpp, any
+// (svt_geometry_kernel.h, hipcc) and the native reader when it hands over evidence records directly (evidence_unit in svt_reads_fragments.h, any
 // C++17 compiler: 16 bytes per fragment cross PCIe instead of a 128-byte summary).  Plain integer / binary64 arithmetic,
 // no library calls: the two builds produce the same bits (tests/test_native_reads.py compares them record by record on the
 // device's output).

@@ -1,7 +1,7 @@
 // svt_inflate.h -- the raw-deflate payload of one BGZF member -> exactly ISIZE bytes, or a status.
 //
 // ONE piece of source for both places that run it, as svt_evidence_walk.h is: the host (svt_bgzf_inflate_host and the open-range
-// arena of svt_reads.cpp, any C++17 compiler: this is where the decoder is proven, fuzzed and sanitised) and the device
+// arena of svt_reads_arena.h / svt_reads_walk.h, any C++17 compiler: this is where the decoder is proven, fuzzed and sanitised) and the device
 // (svt_inflate_kernel.h, hipcc, one wavefront per member).  Written once against a context `X`: X::lane() / X::lanes() /
 // X::sync().  On the host there is one lane and sync() is nothing.
 //

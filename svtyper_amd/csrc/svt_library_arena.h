@@ -1,4 +1,4 @@
-// svt_library_arena.h -- what svt_reads.cpp hands to the two callers of svt_library_walk.h: the rounds of the record stream
+// svt_library_arena.h -- what svt_reads_library.h (a part of svt_reads.cpp) hands to the two callers of svt_library_walk.h: the rounds of the record stream
 // (members to inflate, segments in the arena they make), and the one driver both routes go through -- rounds, prefix sums, caps,
 // stop rule, merge, the host scan for whatever is outside the envelope.  A route is a Backend: where the arena and the tables
 // live and who runs the walk.  Internal C++ (not exported: svt_exports.map lets only svt_* C names out).

@@ -1,5 +1,5 @@
 // svt_library_walk.h -- alignment records in inflated BAM bytes -> what the three library scans of Library.from_bam compute
-// (svt_bam_scan_library in svt_reads.cpp: read length, insert-size histogram, prevalence), for all libraries of a file at once.
+// (svt_bam_scan_library in svt_reads_library.h: read length, insert-size histogram, prevalence), for all libraries of a file at once.
 //
 // ONE piece of source for both places that run it, like svt_evidence_walk.h: the host (svt_bam_scan_libraries_walk_host, any
 // C++17 compiler: where the walk is proven and sanitised) and the device (svt_library_kernel.h, hipcc, one wavefront per

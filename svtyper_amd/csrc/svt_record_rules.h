@@ -1,6 +1,6 @@
 // svt_record_rules.h -- the rules of one BAM alignment record that the split-read path rests on (the reference's
 // SplitRead.is_valid and its relatives: svtyper/parsers.py:922-1058, 1062-1101, 1242-1253), stated ONCE for the host reader
-// (svt_reads.cpp: process_unit) and the evidence walk (svt_evidence_walk.h, host and gfx950): the fixed fields of a record,
+// (svt_reads_fragments.h: process_unit) and the evidence walk (svt_evidence_walk.h, host and gfx950): the fixed fields of a record,
 // the CIGAR operation classes, the query interval of a CIGAR, the text CIGAR and the fields of an SA entry, the tag grammar,
 // the gap-free aligned intervals, and the arithmetic of a split-read candidate.
 //

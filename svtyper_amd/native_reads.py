@@ -351,10 +351,7 @@ class NativeBam:
         out = _LibraryScan()
         self._call(self._L.svt_bam_scan_library(self._h, len(read_groups), names, int(num_samp), C.byref(out)))
         try:
-            n = int(out.n_hist)
-            keys = np.ctypeslib.as_array(out.hist_keys, shape=(max(n, 1),))[:n].tolist()
-            counts = np.ctypeslib.as_array(out.hist_counts, shape=(max(n, 1),))[:n].tolist()
-            return int(out.read_length), dict(zip(keys, counts)), int(out.in_lib), int(out.total)
+            return int(out.read_length), dict(_histogram(out)), int(out.in_lib), int(out.total)
         finally:
             self._L.svt_library_scan_free(C.byref(out))
 
@@ -386,10 +383,7 @@ class NativeBam:
         try:
             result = []
             for l in range(n_libs):
-                n = int(out[l].n_hist)
-                keys = np.ctypeslib.as_array(out[l].hist_keys, shape=(max(n, 1),))[:n].tolist()
-                cnts = np.ctypeslib.as_array(out[l].hist_counts, shape=(max(n, 1),))[:n].tolist()
-                hist = list(zip(keys, cnts)) if ordered else dict(zip(keys, cnts))
+                hist = _histogram(out[l]) if ordered else dict(_histogram(out[l]))
                 result.append((int(out[l].read_length), hist, int(out[l].in_lib), int(out[l].total)))
             return result
         finally:
@@ -403,33 +397,15 @@ class NativeBam:
         evidence records, the geometry predicates evaluated in the reader's threads (`lib_flank`: mean + 3 sd of every
         library of the batch).  What summarise() + the device geometry stage produce, byte for byte."""
         from .evidence import RECORD_DTYPE
-        windows = np.ascontiguousarray(windows, dtype=FETCH_DTYPE)
-        breakpoints = np.ascontiguousarray(breakpoints, dtype=BREAKPOINT_DTYPE)
-        n = int(windows.shape[0])
-        if breakpoints.shape[0] != n:
-            raise ValueError("windows and breakpoints must have the same length")
-        names = (C.c_char_p * max(1, len(read_groups)))(*[rg.encode() for rg in read_groups])
-        libs = (C.c_int32 * max(1, len(read_groups)))(*[int(x) for x in read_group_lib])
-        flank = (C.c_double * max(1, len(lib_flank)))(*[float(x) for x in lib_flank])
-        a = _Args(n, windows.ctypes.data, breakpoints.ctypes.data, len(read_groups), names, libs,
-                  -1 if max_reads is None else int(max_reads), int(count_mode), int(n_threads))
-        g = _EvidenceParams(len(lib_flank), flank, int(min_aligned), int(split_slop))
+        n, a, g, _keep = self._walk_args(windows, breakpoints, read_groups, read_group_lib, max_reads, count_mode, n_threads,
+                                         lib_flank, min_aligned, split_slop)
         out = _Evidence()
         self._call(self._L.svt_bam_evidence(self._h, C.byref(a), C.byref(g), C.byref(out)))
-        owner = _EvidenceOwner(self._L, out)    # frees the C buffers when the arrays below are gone
-        off = np.ctypeslib.as_array(out.rec_offset, shape=(n + 1,)).copy()
-        total = int(off[-1])
-        skipped = np.ctypeslib.as_array(out.skipped, shape=(max(n, 1),))[:n].copy()
-        if total:
-            raw = (C.c_uint8 * (total * RECORD_DTYPE.itemsize)).from_address(out.records)
-            raw._svt_owner = owner
-            recs = np.frombuffer(raw, dtype=RECORD_DTYPE)
-        else:
-            recs = np.zeros(0, RECORD_DTYPE)
-        return off, recs, skipped
+        return _owned_arrays(self._L.svt_evidence_free, out, n, RECORD_DTYPE)
 
-    def _walk_args(self, windows, breakpoints, read_groups, read_group_lib, max_reads, count_mode, lib_flank, min_aligned,
-                   split_slop, n_threads):
+    def _walk_args(self, windows, breakpoints, read_groups, read_group_lib, max_reads, count_mode, n_threads, lib_flank=None,
+                   min_aligned=0, split_slop=0):
+        """(n, svt_summarise_args, svt_evidence_params -- None without `lib_flank` --, what has to outlive the C call)"""
         windows = np.ascontiguousarray(windows, dtype=FETCH_DTYPE)
         breakpoints = np.ascontiguousarray(breakpoints, dtype=BREAKPOINT_DTYPE)
         n = int(windows.shape[0])
@@ -437,9 +413,11 @@ class NativeBam:
             raise ValueError("windows and breakpoints must have the same length")
         names = (C.c_char_p * max(1, len(read_groups)))(*[rg.encode() for rg in read_groups])
         libs = (C.c_int32 * max(1, len(read_groups)))(*[int(x) for x in read_group_lib])
-        flank = (C.c_double * max(1, len(lib_flank)))(*[float(x) for x in lib_flank])
         a = _Args(n, windows.ctypes.data, breakpoints.ctypes.data, len(read_groups), names, libs,
                   -1 if max_reads is None else int(max_reads), int(count_mode), int(n_threads))
+        if lib_flank is None:
+            return n, a, None, (windows, breakpoints, names, libs)
+        flank = (C.c_double * max(1, len(lib_flank)))(*[float(x) for x in lib_flank])
         g = _EvidenceParams(len(lib_flank), flank, int(min_aligned), int(split_slop))
         return n, a, g, (windows, breakpoints, names, libs, flank)
 
@@ -455,8 +433,8 @@ class NativeBam:
         a fallback: (rec_offset, records, skipped, out_of_envelope uint8 [n] -- 0 or a WALK_REASONS key, such a unit has no
         records --, kept_reads uint32 [n])."""
         from .evidence import RECORD_DTYPE
-        n, a, g, _keep = self._walk_args(windows, breakpoints, read_groups, read_group_lib, max_reads, count_mode, lib_flank,
-                                         min_aligned, split_slop, n_threads)
+        n, a, g, _keep = self._walk_args(windows, breakpoints, read_groups, read_group_lib, max_reads, count_mode, n_threads,
+                                         lib_flank, min_aligned, split_slop)
         out = _Evidence()
         flagged = np.zeros(max(n, 1), np.uint8)
         kept = np.zeros(max(n, 1), np.uint32)
@@ -482,8 +460,8 @@ class NativeBam:
         envelope, no bytes; counters dict)."""
         if not hasattr(self._L, "svt_bam_evidence_dump_walk_host"):
             raise hip.SvtyperHipError("this libsvtyper_hip.so has no svt_bam_evidence_dump_walk_host (built before it was added): rebuild it")
-        n, a, g, _keep = self._walk_args(windows, breakpoints, read_groups, read_group_lib, max_reads, count_mode, lib_flank,
-                                         min_aligned, split_slop, n_threads)
+        n, a, g, _keep = self._walk_args(windows, breakpoints, read_groups, read_group_lib, max_reads, count_mode, n_threads,
+                                         lib_flank, min_aligned, split_slop)
         verdicts = np.ascontiguousarray(verdicts, dtype=np.uint8)
         out, dump = _Evidence(), _Dump()
         flagged = np.zeros(max(n, 1), np.uint8)
@@ -509,92 +487,75 @@ class NativeBam:
             raise ValueError("inflate must be 'host' or 'device'")
         if dump and not hasattr(self._L, "svt_bam_evidence_device_dump"):
             raise hip.SvtyperHipError("this libsvtyper_hip.so has no svt_bam_evidence_device_dump (built before it was added): rebuild it")
-        n, a, g, _keep = self._walk_args(windows, breakpoints, read_groups, read_group_lib, max_reads, count_mode, lib_flank,
-                                         min_aligned, split_slop, n_threads)
+        n, a, g, _keep = self._walk_args(windows, breakpoints, read_groups, read_group_lib, max_reads, count_mode, n_threads,
+                                         lib_flank, min_aligned, split_slop)
         if header.n_units != n:
             raise ValueError("header and windows must have the same number of units")
         cb = header.as_c()
         handle = C.c_void_p()
         skipped = np.zeros(max(n, 1), np.uint8)
-        st = _DeviceStats()
-        if dump:
-            ist, dmp = _InflateStats(), _Dump()
-            self._call(self._L.svt_bam_evidence_device_dump(self._h, C.byref(a), C.byref(g), C.byref(cb), int(device), int(flags),
-                                                            C.byref(handle), skipped.ctypes.data, C.byref(st), C.byref(ist),
-                                                            1 if count_host_blocks else 0, 1 if inflate == "device" else 0, C.byref(dmp)))
-            batch = hip.DeviceBatch.adopt(handle, n, int(st.n_records), device)
-            data, off, host, counters = dmp.take(self._L, n)
-            stats = st.as_dict()
-            if inflate == "device":
-                stats["inflate"] = ist.as_dict()
-            stats["deep"] = deep_stats()
-            stats["dump"] = counters
-            return batch, skipped[:n], stats, (data, off, host)
-        if inflate == "device":
-            ist = _InflateStats()
-            self._call(self._L.svt_bam_evidence_device_inflate(self._h, C.byref(a), C.byref(g), C.byref(cb), int(device), int(flags),
-                                                               C.byref(handle), skipped.ctypes.data, C.byref(st), C.byref(ist),
-                                                               1 if count_host_blocks else 0))
-            stats = st.as_dict()
-            stats["inflate"] = ist.as_dict()
-            stats["deep"] = deep_stats()
-            stats["dump"] = dict(NO_DUMP)
-            return hip.DeviceBatch.adopt(handle, n, int(st.n_records), device), skipped[:n], stats
-        self._call(self._L.svt_bam_evidence_device(self._h, C.byref(a), C.byref(g), C.byref(cb), int(device), int(flags),
-                                                   C.byref(handle), skipped.ctypes.data, C.byref(st)))
+        st, ist, dmp = _DeviceStats(), _InflateStats(), _Dump()
+        if dump:       # the three entry points share their first arguments; each later one took the one before and added a tail
+            entry, tail = self._L.svt_bam_evidence_device_dump, [C.byref(ist), 1 if count_host_blocks else 0, 1 if inflate == "device" else 0, C.byref(dmp)]
+        elif inflate == "device":
+            entry, tail = self._L.svt_bam_evidence_device_inflate, [C.byref(ist), 1 if count_host_blocks else 0]
+        else:
+            entry, tail = self._L.svt_bam_evidence_device, []
+        self._call(entry(self._h, C.byref(a), C.byref(g), C.byref(cb), int(device), int(flags), C.byref(handle), skipped.ctypes.data,
+                         C.byref(st), *tail))
+        batch = hip.DeviceBatch.adopt(handle, n, int(st.n_records), device)
+        dumped = dmp.take(self._L, n) if dump else None
         stats = st.as_dict()
+        if inflate == "device":
+            stats["inflate"] = ist.as_dict()
         stats["deep"] = deep_stats()
-        stats["dump"] = dict(NO_DUMP)
-        return hip.DeviceBatch.adopt(handle, n, int(st.n_records), device), skipped[:n], stats
+        stats["dump"] = dumped[3] if dump else dict(NO_DUMP)
+        return (batch, skipped[:n], stats, dumped[:3]) if dump else (batch, skipped[:n], stats)
 
     def summarise(self, windows: np.ndarray, breakpoints: np.ndarray, read_groups: Sequence[str],
                   read_group_lib: Sequence[int], max_reads: Optional[int], count_mode: int,
                   n_threads: int = 0) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
         """(frag_offset uint64 [n+1], fragments FRAGMENT_DTYPE, skipped uint8 [n])"""
-        windows = np.ascontiguousarray(windows, dtype=FETCH_DTYPE)
-        breakpoints = np.ascontiguousarray(breakpoints, dtype=BREAKPOINT_DTYPE)
-        n = int(windows.shape[0])
-        if breakpoints.shape[0] != n:
-            raise ValueError("windows and breakpoints must have the same length")
-        names = (C.c_char_p * max(1, len(read_groups)))(*[rg.encode() for rg in read_groups])
-        libs = (C.c_int32 * max(1, len(read_groups)))(*[int(x) for x in read_group_lib])
-        a = _Args(n, windows.ctypes.data, breakpoints.ctypes.data, len(read_groups), names, libs,
-                  -1 if max_reads is None else int(max_reads), int(count_mode), int(n_threads))
+        n, a, _g, _keep = self._walk_args(windows, breakpoints, read_groups, read_group_lib, max_reads, count_mode, n_threads)
         out = _Summaries()
         self._call(self._L.svt_bam_summarise(self._h, C.byref(a), C.byref(out)))
-        owner = _SummariesOwner(self._L, out)   # frees the C buffers when the arrays below are gone
-        off = np.ctypeslib.as_array(out.frag_offset, shape=(n + 1,)).copy()
-        total = int(off[-1])
-        skipped = np.ctypeslib.as_array(out.skipped, shape=(max(n, 1),))[:n].copy()
-        if total:   # zero-copy view of the C array (1.4 GB for 10 M fragments)
-            raw = (C.c_uint8 * (total * FRAGMENT_DTYPE.itemsize)).from_address(out.fragments)
-            raw._svt_owner = owner   # every numpy view keeps `raw` alive through .base, and raw keeps the owner
-            frags = np.frombuffer(raw, dtype=FRAGMENT_DTYPE)
-        else:
-            frags = np.zeros(0, FRAGMENT_DTYPE)
-        return off, frags, skipped
+        return _owned_arrays(self._L.svt_summaries_free, out, n, FRAGMENT_DTYPE)
 
 
-class _EvidenceOwner:
-    def __init__(self, lib, evidence):
-        self._lib, self._e = lib, evidence
+class _Owner:
+    """frees the C buffers of a result struct once the arrays that view them are gone"""
+
+    def __init__(self, free, struct):
+        self._free, self._struct = free, struct
 
     def __del__(self):
         try:
-            self._lib.svt_evidence_free(C.byref(self._e))
+            self._free(C.byref(self._struct))
         except Exception:
             pass
 
 
-class _SummariesOwner:
-    def __init__(self, lib, summaries):
-        self._lib, self._s = lib, summaries
+def _owned_arrays(free, out, n: int, dtype) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """(offsets uint64 [n + 1] copied, elements viewed in place, skipped uint8 [n] copied) of an svt_summaries / svt_evidence
+    (offsets, elements, skipped); `free` runs when the elements are gone"""
+    owner = _Owner(free, out)
+    offsets, elements = (getattr(out, name) for name, _ in out._fields_[:2])
+    off = np.ctypeslib.as_array(offsets, shape=(n + 1,)).copy()
+    total = int(off[-1])
+    skipped = np.ctypeslib.as_array(out.skipped, shape=(max(n, 1),))[:n].copy()
+    if not total:
+        return off, np.zeros(0, dtype), skipped
+    raw = (C.c_uint8 * (total * dtype.itemsize)).from_address(elements)    # zero-copy view of the C array (1.4 GB for 10 M fragments)
+    raw._svt_owner = owner     # every numpy view keeps `raw` alive through .base, and raw keeps the owner
+    return off, np.frombuffer(raw, dtype=dtype), skipped
 
-    def __del__(self):
-        try:
-            self._lib.svt_summaries_free(C.byref(self._s))
-        except Exception:
-            pass
+
+def _histogram(scan) -> list:
+    """the (template_length, count) pairs of an svt_library_scan, in the order of the keys' first occurrence"""
+    n = int(scan.n_hist)
+    keys = np.ctypeslib.as_array(scan.hist_keys, shape=(max(n, 1),))[:n].tolist()
+    counts = np.ctypeslib.as_array(scan.hist_counts, shape=(max(n, 1),))[:n].tolist()
+    return list(zip(keys, counts))
 
 
 def batch_offsets(dbatch) -> np.ndarray:

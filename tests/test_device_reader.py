@@ -75,6 +75,24 @@ def test_units_outside_the_envelope_are_the_host_readers(tmp_path, case):
     assert len(want[1]) > 0
 
 
+def test_first_failing_unit_in_unit_order_gives_the_error():
+    """Two units that both go to the host reader and fail there with different texts, on two threads: the call fails with the
+    text of the one that comes first in unit order, whichever thread finishes first.  Both are preset by the arena's planner
+    (a window on a reference the header does not have: "BAM read error"; an svtype behind BND: "bad svtype"), so no walk runs
+    over them."""
+    sites, sample, nbam = W.fixture_input()
+    a = W.unit_arrays(sites[:3], sample, nbam, nr.COUNT_SSO)
+    head = W.header_batch(sample, a[1])
+    texts = ("BAM read error", "bad svtype")
+    for bad_tid, bad_svtype, first in ((1, 2, 0), (2, 1, 1)):
+        win, bps = a[0].copy(), a[1].copy()
+        win["tid_a"][bad_tid] = len(nbam.references) + 1
+        bps["svtype"][bad_svtype] = 200
+        with pytest.raises(hip.SvtyperHipError) as err:
+            nbam.evidence_device(win, bps, a[2], a[3], 1000, nr.COUNT_SSO, a[4], 20, 3, head, 0, 0, 2)
+        assert texts[first] in str(err.value) and texts[1 - first] not in str(err.value)
+
+
 def test_fake_read_bams_equal_the_host_reader(tmp_path):
     for sites, sample, nbam in W.fake_inputs(tmp_path):
         for mode, max_reads in ((nr.COUNT_CLASSIC, None), (nr.COUNT_SSO, 1000), (nr.COUNT_SSO, 30), (nr.COUNT_CLASSIC, 25)):
