@@ -246,6 +246,28 @@ typedef struct svt_deflate_times {
 } svt_deflate_times;
 int svt_bgzf_deflate_last_times(svt_deflate_times* times);
 
+/* The block a member is written as (additions; probe for the symbols).  SVT_DEFLATE_FIXED: the two entries above, byte
+ * for byte.  SVT_DEFLATE_DYNAMIC: the same tokens in one dynamic-Huffman block whose code is made from the member's own
+ * token histogram, wherever that block is strictly shorter than what SVT_DEFLATE_FIXED writes for the
+ * member, and exactly those bytes otherwise -- so no member grows and every capacity rule above holds unchanged.  Host
+ * and device write the same bytes.  Any other mode: SVT_ERR_INVALID.  svt_bgzf_deflate_last_times answers for the
+ * calling thread's last device call of either kind.                                                                 */
+#define SVT_DEFLATE_FIXED 0u
+#define SVT_DEFLATE_DYNAMIC 1u
+int svt_bgzf_deflate_host_mode(const uint8_t* bytes, const uint64_t* off, uint64_t n, uint8_t* out, uint64_t capacity,
+                               uint64_t* out_off, uint32_t mode);
+int svt_bgzf_deflate_device_mode(const uint8_t* bytes, const uint64_t* off, uint64_t n, uint8_t* out, uint64_t capacity,
+                                 uint64_t* out_off, uint32_t mode, int device);
+/* The code-length rule of the dynamic block on its own (the seam svt_bayes_gt is for the likelihoods): `sets`
+ * histograms of `symbols` frequencies each, side by side in freq, -> their code lengths of at most `limit` bits, side
+ * by side in lengths (0: the symbol has no code).  Huffman's optimum wherever that fits the limit, complete and never
+ * over-subscribed otherwise; one used symbol gets one bit, none no code.  On the device one wavefront per histogram,
+ * through the compressor's own source.  SVT_ERR_INVALID: limit other than 7 or 15, symbols outside 1 .. 286, a
+ * histogram whose frequencies sum to 2^32 or more or that uses more than 2^limit symbols.                           */
+int svt_huffman_lengths_host(const uint32_t* freq, uint32_t sets, uint32_t symbols, uint32_t limit, uint8_t* lengths);
+int svt_huffman_lengths_device(const uint32_t* freq, uint32_t sets, uint32_t symbols, uint32_t limit, uint8_t* lengths,
+                               int device);
+
 /* Verify: a property of the handle, off by default (0).  With it on, every call that takes the handle checks the
  * CRC-32 of every BGZF member it inflates, where it inflates it: the host reader's threads (libdeflate's or zlib's
  * crc32), or svt_crc32_kernel behind svt_inflate_kernel for the routes that inflate on the GPU (the expected values

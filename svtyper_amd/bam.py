@@ -125,6 +125,7 @@ _BGZF_PAYLOAD = 0xff00      # bytes of payload per member, htslib's block size: 
 
 
 DEFLATE_CHOICES = ("zlib", "host", "device")
+HUFFMAN_CHOICES = ("fixed", "dynamic")
 _BGZF_BATCH = 256           # finished payloads handed to svt_bgzf_deflate_host / _device in one call
 
 
@@ -132,6 +133,15 @@ def check_deflate(deflate) -> str:
     if deflate not in DEFLATE_CHOICES:
         raise ValueError("deflate must be one of %s, not %r" % (", ".join(repr(c) for c in DEFLATE_CHOICES), deflate))
     return deflate
+
+
+def check_huffman(huffman, deflate) -> str:
+    """`huffman`: the block the library's own compressor writes; "dynamic" needs deflate="host" or "device" """
+    if huffman not in HUFFMAN_CHOICES:
+        raise ValueError("huffman must be one of %s, not %r" % (", ".join(repr(c) for c in HUFFMAN_CHOICES), huffman))
+    if huffman == "dynamic" and deflate == "zlib":
+        raise ValueError("huffman='dynamic' needs deflate='host' or deflate='device': with deflate='zlib' the blocks are zlib's own")
+    return huffman
 
 
 class BgzfWriter:
@@ -142,10 +152,13 @@ class BgzfWriter:
     htslib's deflate would produce.)  deflate="host" / "device": finished payloads are collected and compressed _BGZF_BATCH at a
     time by one call of the library's own compressor (svtyper_amd/csrc/svt_deflate.h), on this thread or on GPU `device`; the
     library is imported with the first batch.  Where a payload is cut is decided before anybody compresses it, so the inflated
-    stream and the member boundaries are the same for all three."""
+    stream and the member boundaries are the same for all three.  huffman="dynamic" (with "host" / "device" only; ValueError with
+    "zlib"): every member that is shorter as a dynamic-Huffman block is written as one; the default "fixed" writes
+    the bytes it always wrote."""
 
-    def __init__(self, path_or_file, level: int = 6, deflate: str = "zlib", device: int = 0):
+    def __init__(self, path_or_file, level: int = 6, deflate: str = "zlib", device: int = 0, huffman: str = "fixed"):
         self._deflate = check_deflate(deflate)
+        self._huffman = check_huffman(huffman, self._deflate)
         self._f = path_or_file if hasattr(path_or_file, "write") else open(path_or_file, "wb")
         self._level = level
         self._device = device
@@ -175,7 +188,8 @@ class BgzfWriter:
         if not self._pending:
             return
         from . import native_reads
-        members, _off = native_reads.bgzf_deflate(self._pending, device=self._device if self._deflate == "device" else None)
+        members, _off = native_reads.bgzf_deflate(self._pending, device=self._device if self._deflate == "device" else None,
+                                                  huffman=self._huffman)
         del self._pending[:]
         self._f.write(members.tobytes())
 
@@ -454,7 +468,8 @@ class AlignmentFile:
         if mode.startswith("w"):
             if mode != "wb":
                 raise NotImplementedError("only BAM output (mode 'wb') is written")
-            self._open_for_writing(path, kwargs.get("template", template), kwargs.get("deflate", "zlib"), kwargs.get("device", 0))
+            self._open_for_writing(path, kwargs.get("template", template), kwargs.get("deflate", "zlib"), kwargs.get("device", 0),
+                                   kwargs.get("huffman", "fixed"))
             return
         self._bgzf = BgzfReader(path, verify=bool(kwargs.get("verify", False)))
         raw = []        # the header as it lies in the file: a file opened 'wb' with this one as template starts with these bytes
@@ -655,16 +670,16 @@ class AlignmentFile:
         self._bgzf.close()
 
     # ---- writing (mode 'wb')
-    def _open_for_writing(self, path: str, template, deflate: str = "zlib", device: int = 0):
+    def _open_for_writing(self, path: str, template, deflate: str = "zlib", device: int = 0, huffman: str = "fixed"):
         """pysam.AlignmentFile(path, 'wb', template): the template's header text and reference list, byte for byte.  `deflate`,
-        `device`: who compresses the members (BgzfWriter)."""
+        `device`, `huffman`: who compresses the members, and into which block (BgzfWriter)."""
         header = getattr(template, "_header_bytes", None)
         if header is None:
             raise TypeError("mode 'wb' needs template=: an AlignmentFile of this module opened for reading")
         self.text, self.header = template.text, template.header
         self.references, self.lengths = template.references, template.lengths
         self._tid = dict(template._tid)
-        self._writer = BgzfWriter(path, deflate=deflate, device=device)
+        self._writer = BgzfWriter(path, deflate=deflate, device=device, huffman=huffman)
         self._writer.write(header)
         self._writer.flush()            # (records start in a block of their own, as htslib leaves them)
 

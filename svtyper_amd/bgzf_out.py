@@ -4,7 +4,8 @@
     sso_genotype(bam, vcf_in, out, ...)
     out.close()                                  # the last member, the EOF member, and the file is closed
 
-The members are cut every 65 280 bytes of UTF-8, wherever that falls; who compresses them is BgzfWriter's `deflate`."""
+The members are cut every 65 280 bytes of UTF-8, wherever that falls; who compresses them is BgzfWriter's `deflate`, and
+into which block its `huffman`."""
 from __future__ import annotations
 
 import io
@@ -49,7 +50,7 @@ class BgzfTextWriter:
         self.close()
 
 
-def open_text(file_or_path, deflate: str = "zlib", device: int = 0, level: int = 6) -> BgzfTextWriter:
+def open_text(file_or_path, deflate: str = "zlib", device: int = 0, level: int = 6, huffman: str = "fixed") -> BgzfTextWriter:
     """`file_or_path`: a path, a binary file object, or a text file object over one (sys.stdout, what argparse.FileType("w")
     opens): its buffer is written to.  close() writes the EOF member and closes what was handed in."""
     target = file_or_path
@@ -57,4 +58,4 @@ def open_text(file_or_path, deflate: str = "zlib", device: int = 0, level: int =
         target.flush()
         target = target.buffer
     name = file_or_path if isinstance(file_or_path, str) else getattr(file_or_path, "name", "<bgzf>")
-    return BgzfTextWriter(BgzfWriter(target, level=level, deflate=deflate, device=device), str(name))
+    return BgzfTextWriter(BgzfWriter(target, level=level, deflate=deflate, device=device, huffman=huffman), str(name))

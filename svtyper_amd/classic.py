@@ -21,7 +21,7 @@ from itertools import chain
 
 from . import __version__, sharded
 from . import evidence as ev
-from .bam import check_deflate
+from .bam import check_deflate, check_huffman
 from .bulk_vcf import QUAL_CLASSIC
 from .driver import Driver, parse_arguments, run_cli, run_main
 from .library import Sample, write_sample_json
@@ -185,18 +185,20 @@ class Classic(Driver):
 
 def sv_genotype(bam_string, vcf_in, vcf_out, min_aligned, split_weight, disc_weight, num_samp, lib_info_path,
                 debug, alignment_outpath, ref_fasta, sum_quals, max_reads, max_ci_dist, *, engine=None, geometry="host",
-                reader=None, stats=None, inflate="host", library_scan="host", verify="off", deflate="zlib"):
+                reader=None, stats=None, inflate="host", library_scan="host", verify="off", deflate="zlib", huffman="fixed"):
     """`alignment_outpath` (-w): the reads that entered the tallies go to a BAM, tagged XV:A:R / XV:A:A as the reference tags them
     (driver.tag_and_write; the tags that depend on p_concordant come from the device, svt_batch_verdicts).  Legal with
     reader="python" (what reader=None then means) or reader="device" (the reads are cut and tagged on the GPU: the evidence dump of
     svt_bam_evidence_device_dump; the default engine, or one with supports_dump) and geometry="host"; ValueError otherwise, and for
     an engine without supports_verdicts.  `deflate`: who compresses that BAM's members -- "zlib", or the library's own compressor on
-    the "host" or on the "device" (bam.BgzfWriter; the same inflated bytes and member boundaries); ValueError for anything else."""
-    check_deflate(deflate)
+    the "host" or on the "device" (bam.BgzfWriter; the same inflated bytes and member boundaries); ValueError for anything else.  `huffman`: "fixed", or "dynamic" for
+    dynamic-Huffman blocks from that compressor (ValueError with deflate="zlib")."""
+    check_huffman(huffman, check_deflate(deflate))
     run = Classic(bam_string, vcf_in, vcf_out, min_aligned, split_weight, disc_weight, num_samp, lib_info_path, debug, ref_fasta,
                   sum_quals, max_reads, max_ci_dist)
     run.alignment_outpath = alignment_outpath
     run.deflate = deflate
+    run.huffman = huffman
     return run.run(CHUNK_UNITS, engine=engine, geometry=geometry, reader=reader, stats=stats, inflate=inflate,
                    library_scan=library_scan, verify=verify)
 
@@ -234,7 +236,7 @@ def main():
     call = (args.bam, args.input_vcf, args.output_vcf, args.min_aligned, args.split_weight, args.disc_weight,
             args.num_samp, args.lib_info_path, args.debug, args.alignment_outpath, args.ref_fasta,
             args.sum_quals, args.max_reads, args.max_ci_dist)
-    own = dict(deflate=args.deflate)        # (of this program alone: the `-w` BAM)
+    own = dict(deflate=args.deflate, huffman=args.huffman)      # (of this program alone: the `-w` BAM)
     return run_main(functools.partial(sv_genotype, **own), functools.partial(sharded.sv_genotype_sharded, **own), call, args)
 
 

@@ -39,6 +39,8 @@ const crc::Tables& crc_tables();
 int crc_check_offsets(const uint8_t* bytes, const uint64_t* off, uint64_t n, const uint32_t* crc);
 // the argument checks of svt_bgzf_deflate_host / _device (svt_deflate.h); `slots`: the bytes all members take at the most
 int deflate_check_args(const uint8_t* bytes, const uint64_t* off, uint64_t n, const uint8_t* out, const uint64_t* out_off, uint64_t& slots);
+// What svt_huffman_lengths_host and _device refuse alike: what dfl::code_lengths asks of its histograms.
+int huffman_check_args(const uint32_t* freq, uint32_t sets, uint32_t symbols, uint32_t limit, const uint8_t* lengths);
 // Around a call that takes a handle: what the handle's tally gained in between becomes the calling thread's svt_bgzf_verify_stats.
 // (A call inside a call -- the host scan behind a device scan -- reports into the outer one's figures: the outer scope ends last.)
 struct VerifyScope {

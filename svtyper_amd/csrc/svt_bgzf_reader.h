@@ -486,6 +486,20 @@ int deflate_check_args(const uint8_t* bytes, const uint64_t* off, uint64_t n, co
     return SVT_OK;
 }
 
+int huffman_check_args(const uint32_t* freq, uint32_t sets, uint32_t symbols, uint32_t limit, const uint8_t* lengths)
+{
+    if (sets && (!freq || !lengths)) return fail(SVT_ERR_INVALID, "null argument");
+    if (limit != 7 && limit != 15) return fail(SVT_ERR_INVALID, "svt_huffman_lengths: limit is 7 or 15");
+    if (symbols < 1 || symbols > dfl::kLitSyms) return fail(SVT_ERR_INVALID, "svt_huffman_lengths: 1 .. 286 symbols");
+    for (uint64_t k = 0; k < sets; ++k) {
+        uint64_t sum = 0, used = 0;
+        for (uint32_t s = 0; s < symbols; ++s) { sum += freq[k * symbols + s]; used += freq[k * symbols + s] != 0; }
+        if (sum > 0xFFFFFFFFull) return fail(SVT_ERR_INVALID, "svt_huffman_lengths: the frequencies of a histogram sum to 2^32 or more");
+        if (used > (1ull << limit)) return fail(SVT_ERR_INVALID, "svt_huffman_lengths: more used symbols than codes of `limit` bits");
+    }
+    return SVT_OK;
+}
+
 namespace bgzf {
 
 int bgzf_members(const uint8_t* data, uint64_t len, const uint64_t* block_off, uint64_t n, const uint8_t* out, const uint64_t* out_off,

@@ -26,6 +26,14 @@
 // that is bank (l / 2 + 32 (e & 1)) of 64 -- two lanes meet in a bank only where they share a dword.  A match's source may lie
 // in the previous lane's chunk: that is payload, which nobody writes, so no sync stands in front of it.
 //
+// The dynamic mode (deflate_member<X, kDynamic>; DESIGN 3.4, "the dynamic block").  The same tokens under a code made for the
+// member: a histogram of the tokens of all chunks (every lane adds its chunk's symbols into Scratch.code.freq through
+// X::add: sums of integers, the same whatever the order), code lengths from the frequencies alone (code_lengths: the symbols
+// ranked across the lanes, the Huffman depths, their repair and the header by lane 0), a second counting parse under that
+// code, and the choice: the dynamic block is written only where it is strictly shorter than what the fixed mode writes,
+// which is written byte for byte otherwise.  So a chunk is parsed three times; no token is kept anywhere.  The header's bits
+// are lane 0's first bits.
+//
 // Every read is checked against `n`, every write against `cap`.  No std::, no allocation.
 #ifndef SVT_DEFLATE_H
 #define SVT_DEFLATE_H
@@ -33,6 +41,14 @@
 #include <stdint.h>
 
 #include "svt_geometry_math.h"
+
+// (a loop that is kept a loop: unrolled over the constant sizes of the small alphabets, the ranking below holds every `t < s`
+// in a register pair of its own)
+#if defined(__clang__)
+#define SVT_DFL_KEEP_LOOP _Pragma("clang loop unroll(disable)")
+#else
+#define SVT_DFL_KEEP_LOOP _Pragma("GCC unroll 1")
+#endif
 
 namespace svt {
 namespace dfl {
@@ -44,6 +60,10 @@ constexpr uint32_t kTable = 1u << kHashBits;
 constexpr uint32_t kEmpty = 0xFFFF;         // no position is 65 535: the last one that is hashed is 65 276
 constexpr uint32_t kMinMatch = 4, kMaxMatch = 258;
 constexpr uint32_t kHeaderBytes = 18, kTrailerBytes = 8;
+constexpr uint32_t kFixed = 0, kDynamic = 1;                    // the block a member may be written as (deflate_member's mode)
+constexpr uint32_t kLitSyms = 286, kDistSyms = 30, kClSyms = 19; // the three alphabets of a dynamic block, side by side:
+constexpr uint32_t kDistAt = kLitSyms, kClAt = kLitSyms + kDistSyms, kSyms = kClAt + kClSyms;
+constexpr uint32_t kEob = 256;
 
 // the most a member's deflate bytes take: a stored block (5 + n), or the two bytes of the empty fixed block
 SVT_HD uint32_t cdata_bound(uint32_t n) { return n ? n + 5 : 2; }
@@ -60,12 +80,35 @@ SVT_HD uint8_t header_byte(uint32_t i, uint32_t clen)
 }
 SVT_HD uint8_t trailer_byte(uint32_t i, uint32_t crc, uint32_t n) { return (uint8_t)((i < 4 ? crc : n) >> (8 * (i & 3))); }
 
-template <uint32_t W>
+// what one code's construction works in (code_lengths)
+struct Build {
+    uint32_t w[kLitSyms];                   // weights in rising order -> parents -> depths (Moffat and Katajainen, in place)
+    uint32_t cnt[16];                       // symbols per code length
+    uint32_t next[16];                      // the next code of each length (canonical_codes)
+    uint16_t order[kLitSyms];               // the used symbols by (frequency, symbol), rising
+};
+
+// the dynamic mode's part of Scratch: literal/length symbols at 0, distance symbols at kDistAt, code-length symbols at kClAt
+struct Code {
+    uint32_t freq[kSyms];
+    uint32_t dstart[kLanes];                // lane l's bits under the dynamic code
+    uint32_t hlit, hdist, hclen, header_bits;
+    uint32_t dynamic;                       // the choice: 1: the dynamic block is written
+    Build build;
+    uint16_t code[kSyms];                   // first bit lowest, as the stream takes it
+    uint8_t len[kSyms];
+};
+
+template <uint32_t W, uint32_t M = kFixed>
 struct Scratch {
     alignas(4) uint16_t table[kTable * W];  // entry e of table l: table[e * W + l]
     uint32_t start[kLanes + 1];             // counts, then the bit at which lane l's bits begin; [64]: the block's bits
     uint32_t tail[kLanes];                  // bit 31: lane l's last bits begin a byte, (its index << 8) | those bits
     uint8_t head[kLanes];                   // lane l's bits of the byte its range begins in, when it begins inside one
+};
+template <uint32_t W>
+struct Scratch<W, kDynamic> : Scratch<W, kFixed> {
+    Code code;
 };
 
 struct HostCtx {
@@ -73,6 +116,7 @@ struct HostCtx {
     static SVT_HD uint32_t lane() { return 0; }
     static SVT_HD uint32_t lanes() { return 1; }
     static SVT_HD void sync() {}
+    static SVT_HD void add(uint32_t* counter) { ++*counter; }
 };
 
 SVT_HD uint32_t le32(const uint8_t* p)
@@ -93,6 +137,28 @@ SVT_HD uint32_t rev(uint32_t v, uint32_t n)
     return v >> (16 - n);
 }
 
+// ---- a match as symbols (RFC 1951 3.2.5): the symbol, how many extra bits and their value -----------------------------------------
+SVT_HD uint32_t length_symbol(uint32_t len, uint32_t& eb, uint32_t& ev)
+{
+    const uint32_t l = len - 3;
+    eb = 0; ev = 0;
+    if (len == 258) return 285;
+    if (l < 8) return 257 + l;
+    eb = (31 - (uint32_t)__builtin_clz(l)) - 2;
+    ev = l & ((1u << eb) - 1);
+    return 261 + 4 * eb + ((l >> eb) & 3);
+}
+SVT_HD uint32_t distance_symbol(uint32_t dist, uint32_t& deb, uint32_t& dev)
+{
+    const uint32_t d = dist - 1;
+    deb = 0; dev = 0;
+    if (d < 4) return d;
+    const uint32_t hb = 31 - (uint32_t)__builtin_clz(d);
+    deb = hb - 1;
+    dev = d & ((1u << deb) - 1);
+    return 2 * hb + ((d >> deb) & 1);
+}
+
 // ---- the fixed Huffman code (RFC 1951 3.2.6): a token as bits, lowest first, and how many -------------------------------------
 SVT_HD uint32_t literal_bits(uint32_t b, uint32_t& n)
 {
@@ -104,41 +170,19 @@ SVT_HD uint32_t literal_bits(uint32_t b, uint32_t& n)
 // match (len 3 .. 258, dist 1 .. 32 768): length code, its extra bits, distance code, its extra bits -- 31 bits at most
 SVT_HD uint32_t match_bits(uint32_t len, uint32_t dist, uint32_t& n)
 {
-    uint32_t sym, eb = 0, ev = 0;
-    const uint32_t l = len - 3;
-    if (len == 258) sym = 285;
-    else if (l < 8) sym = 257 + l;
-    else {
-        eb = (31 - (uint32_t)__builtin_clz(l)) - 2;
-        sym = 261 + 4 * eb + ((l >> eb) & 3);
-        ev = l & ((1u << eb) - 1);
-    }
+    uint32_t eb, ev, deb, dev;
+    const uint32_t sym = length_symbol(len, eb, ev), dsym = distance_symbol(dist, deb, dev);
     uint32_t v;
     if (sym < 280) { v = rev(sym - 256, 7); n = 7; }
     else { v = rev(0xC0 + (sym - 280), 8); n = 8; }
     v |= ev << n;
     n += eb;
-    uint32_t dsym, deb = 0, dev = 0;
-    const uint32_t d = dist - 1;
-    if (d < 4) dsym = d;
-    else {
-        const uint32_t hb = 31 - (uint32_t)__builtin_clz(d);
-        deb = hb - 1;
-        dsym = 2 * hb + ((d >> deb) & 1);
-        dev = d & ((1u << deb) - 1);
-    }
     v |= rev(dsym, 5) << n;
     n += 5;
     v |= dev << n;
     n += deb;
     return v;
 }
-
-// ---- the two things a parse feeds ------------------------------------------------------------------------------------------
-struct Count {
-    uint32_t bits;
-    SVT_HD void put(uint32_t, uint32_t n) { bits += n; }
-};
 
 // bits from `start` on into out[0, cap): whole bytes as they fill, the byte the range begins inside (if any) into `head`
 struct Writer {
@@ -172,6 +216,61 @@ struct Writer {
     }
 };
 
+// ---- the things a parse feeds: a chunk's tokens counted or written, under the fixed code or the member's own -------------------
+struct Count {
+    uint32_t bits;
+    SVT_HD void literal(uint32_t b) { uint32_t n; (void)literal_bits(b, n); bits += n; }
+    SVT_HD void match(uint32_t len, uint32_t dist) { uint32_t n; (void)match_bits(len, dist, n); bits += n; }
+};
+
+struct FixedWrite {
+    Writer& w;
+    SVT_HD void literal(uint32_t b) { uint32_t n; const uint32_t v = literal_bits(b, n); w.put(v, n); }
+    SVT_HD void match(uint32_t len, uint32_t dist) { uint32_t n; const uint32_t v = match_bits(len, dist, n); w.put(v, n); }
+};
+
+// the fixed count, and the tokens' symbols into the member's histogram
+template <class X>
+struct CountAndTally {
+    uint32_t bits;
+    uint32_t* freq;
+    SVT_HD void literal(uint32_t b) { uint32_t n; (void)literal_bits(b, n); bits += n; X::add(freq + b); }
+    SVT_HD void match(uint32_t len, uint32_t dist)
+    {
+        uint32_t n, eb, ev;
+        (void)match_bits(len, dist, n);
+        bits += n;
+        X::add(freq + length_symbol(len, eb, ev));
+        X::add(freq + kDistAt + distance_symbol(dist, eb, ev));
+    }
+};
+
+struct DynamicCount {
+    uint32_t bits;
+    const uint8_t* len;
+    SVT_HD void literal(uint32_t b) { bits += len[b]; }
+    SVT_HD void match(uint32_t length, uint32_t dist)
+    {
+        uint32_t eb, ev, deb, dev;
+        const uint32_t sym = length_symbol(length, eb, ev), dsym = distance_symbol(dist, deb, dev);
+        bits += len[sym] + eb + len[kDistAt + dsym] + deb;
+    }
+};
+
+struct DynamicWrite {
+    Writer& w;
+    const uint16_t* code;
+    const uint8_t* len;
+    SVT_HD void literal(uint32_t b) { w.put(code[b], len[b]); }
+    SVT_HD void match(uint32_t length, uint32_t dist)
+    {
+        uint32_t eb, ev, deb, dev;
+        const uint32_t sym = length_symbol(length, eb, ev), dsym = distance_symbol(dist, deb, dev);
+        w.put(code[sym] | (ev << len[sym]), len[sym] + eb);                                      // 15 + 5 bits at most
+        w.put(code[kDistAt + dsym] | (dev << len[kDistAt + dsym]), len[kDistAt + dsym] + deb);   // 15 + 13
+    }
+};
+
 // Chunk `l` of p[0, n) parsed greedily over the table at `col` (entries W apart), the tokens put into `sink`.
 template <uint32_t W, class Sink>
 SVT_HD void parse_chunk(const uint8_t* p, uint32_t n, uint32_t C, uint32_t l, uint16_t* col, Sink& sink)
@@ -196,57 +295,290 @@ SVT_HD void parse_chunk(const uint8_t* p, uint32_t n, uint32_t C, uint32_t l, ui
                 while (m < lim && p[j + m] == p[i + m]) ++m;
             }
         }
-        uint32_t nb;
         if (m) {
-            const uint32_t v = match_bits(m, i - j, nb);
-            sink.put(v, nb);
+            sink.match(m, i - j);
             for (uint32_t k = i; k < i + m; ++k)
                 if (k + 4 <= n) col[hash(le32(p + k)) * W] = (uint16_t)k;
             i += m;
         } else {
-            const uint32_t v = literal_bits(p[i], nb);
-            sink.put(v, nb);
+            sink.literal(p[i]);
             if (hashed) col[h * W] = (uint16_t)i;
             ++i;
         }
     }
 }
 
-// p[0, n), n <= kMaxPayload, deflated into out[0, cap), cap >= cdata_bound(n).  Returns the bytes written, the same on every
-// lane; 0: refused (n or cap out of range), nothing is written.
+// ---- the member's own code ("the dynamic block") ------------------------------------------------------------------
+// Code lengths of at most `limit` bits (limit <= 15) for freq[0, nsym), nsym <= kLitSyms, the frequencies' sum below 2^32 and no
+// more than 2^limit of them above zero -- a function of the frequencies alone, in integers:
+//   the used symbols (frequency > 0) in rising order of (frequency, symbol);  none: no code;  one: one bit;  else
+//   Huffman's tree over them: the two smallest weights are joined until one is left, and among equal weights a leaf goes before
+//     a joined node, leaves in their order, nodes in the order they were made -- this gives the depths as a multiset;
+//   depths above `limit` become `limit`, and for every unit by which sum 2^(limit - depth) then exceeds 2^limit, one symbol of
+//     the greatest depth below `limit` that has one goes one level down and takes one symbol of depth `limit` up beside it
+//     (counts only: cnt[d] -= 1, cnt[d + 1] += 2, cnt[limit] -= 1; the sum falls by exactly one: zlib's repair);
+//   the lengths are handed out in the symbols' order, the longest first.
+// Where the tree fits the limit this is Huffman's optimum.  All lanes call it; freq is complete and B free behind the sync() it
+// begins with, len is complete behind the one it ends with.  The ranking is the lanes' (every lane ranks its symbols against
+// all others: reads of one address by all lanes), the rest -- a chain of dependent steps over at most 286 entries -- lane 0's.
 template <class X>
-SVT_HD uint32_t deflate_member(const uint8_t* p, uint32_t n, uint8_t* out, uint32_t cap, Scratch<X::kWidth>& S)
+SVT_HD void code_lengths(const uint32_t* freq, uint32_t nsym, uint32_t limit, uint8_t* len, Build& B)
+{
+    X::sync();
+    for (uint32_t s = X::lane(); s < nsym; s += X::lanes()) {
+        const uint32_t f = freq[s];
+        len[s] = 0;
+        if (!f) continue;
+        uint32_t rank = 0;
+        SVT_DFL_KEEP_LOOP
+        for (uint32_t t = 0; t < nsym; ++t) {
+            const uint32_t g = freq[t];
+            rank += g && (g < f || (g == f && t < s));
+        }
+        B.order[rank] = (uint16_t)s;                        // (ranks are a permutation of 0 .. used - 1: below nsym)
+    }
+    X::sync();
+    if (X::lane() == 0) {
+        uint32_t m = 0;
+        SVT_DFL_KEEP_LOOP
+        for (uint32_t t = 0; t < nsym; ++t) m += freq[t] != 0;
+        uint32_t* A = B.w;
+        for (uint32_t i = 0; i < m; ++i) A[i] = freq[B.order[i]];
+        if (m == 1) len[B.order[0]] = 1;
+        if (m >= 2) {
+            // first pass, left to right: the joined nodes' weights, a used-up node's place taken by its parent's index
+            A[0] += A[1];
+            uint32_t root = 0, leaf = 2;
+            for (uint32_t next = 1; next + 1 < m; ++next) {
+                if (leaf >= m || A[root] < A[leaf]) { A[next] = A[root]; A[root++] = next; }
+                else A[next] = A[leaf++];
+                if (leaf >= m || (root < next && A[root] < A[leaf])) { A[next] += A[root]; A[root++] = next; }
+                else A[next] += A[leaf++];
+            }
+            // second pass, right to left: the nodes' depths
+            A[m - 2] = 0;
+            for (uint32_t next = m - 2; next-- > 0;) A[next] = A[A[next]] + 1;
+            // third pass, right to left: the leaves' depths, falling
+            uint32_t avbl = 1, used = 0, depth = 0;
+            int32_t r = (int32_t)m - 2, next = (int32_t)m - 1;
+            while (avbl > 0) {
+                while (r >= 0 && A[r] == depth) { ++used; --r; }
+                while (avbl > used && next >= 0) { A[next--] = depth; --avbl; }
+                if (avbl > used) break;                     // (never: the leaves are out exactly when no place is left)
+                avbl = 2 * used; ++depth; used = 0;
+            }
+            for (uint32_t d = 0; d < 16; ++d) B.cnt[d] = 0;
+            uint32_t kraft = 0;
+            for (uint32_t i = 0; i < m; ++i) {
+                const uint32_t d = A[i] < limit ? A[i] : limit;
+                ++B.cnt[d];
+                kraft += 1u << (limit - d);
+            }
+            for (uint32_t over = kraft - (1u << limit); over > 0; --over) {
+                uint32_t d = limit - 1;
+                while (d > 1 && B.cnt[d] == 0) --d;
+                if (B.cnt[d] == 0 || B.cnt[limit] == 0) break;  // (never, with at most 2^limit symbols)
+                --B.cnt[d]; B.cnt[d + 1] += 2; --B.cnt[limit];
+            }
+            uint32_t i = 0;
+            for (uint32_t d = limit; d >= 1; --d)
+                for (uint32_t c = B.cnt[d]; c > 0 && i < m; --c) len[B.order[i++]] = (uint8_t)d;
+        }
+    }
+    X::sync();
+}
+
+// the canonical codes of len[0, nsym) (RFC 1951 3.2.2), each turned round for the stream; one lane's
+SVT_HD void canonical_codes(const uint8_t* len, uint32_t nsym, uint16_t* code, Build& B)
+{
+    uint32_t* count = B.cnt;
+    uint32_t* next = B.next;
+    for (uint32_t d = 0; d < 16; ++d) count[d] = 0;
+    SVT_DFL_KEEP_LOOP
+    for (uint32_t s = 0; s < nsym; ++s) ++count[len[s] & 15];
+    count[0] = 0;
+    uint32_t c = 0;
+    next[0] = 0;
+    for (uint32_t d = 1; d < 16; ++d) { c = (c + count[d - 1]) << 1; next[d] = c; }
+    SVT_DFL_KEEP_LOOP
+    for (uint32_t s = 0; s < nsym; ++s) {
+        const uint32_t d = len[s] & 15;
+        code[s] = d ? (uint16_t)rev(next[d]++, d) : 0;
+    }
+}
+
+// The code lengths len[0, n) as the run-length operations of the header, each to sink.op(symbol, extra): a run of zeros as 18s
+// of up to 138 while 11 or more are left, then one 17 for 3 .. 10, then single zeros; a run of another length as that length,
+// then 16s of up to 6 while 3 or more are left, then the length itself.  (Literal/length and distance lengths are run through
+// separately: no run crosses from one into the other.)
+template <class Sink>
+SVT_HD void run_length_ops(const uint8_t* len, uint32_t n, Sink& sink)
+{
+    uint32_t i = 0;
+    while (i < n) {
+        const uint32_t v = len[i];
+        uint32_t run = 1;
+        while (i + run < n && len[i + run] == v) ++run;
+        uint32_t left = run;
+        if (v == 0) {
+            while (left >= 11) { const uint32_t take = left < 138 ? left : 138; sink.op(18, take - 11); left -= take; }
+            if (left >= 3) { sink.op(17, left - 3); left = 0; }
+        } else {
+            sink.op(v, 0);
+            --left;
+            while (left >= 3) { const uint32_t take = left < 6 ? left : 6; sink.op(16, take - 3); left -= take; }
+        }
+        for (; left > 0; --left) sink.op(v, 0);
+        i += run;
+    }
+}
+SVT_HD uint32_t op_extra_bits(uint32_t sym) { return sym < 16 ? 0 : sym == 16 ? 2 : sym == 17 ? 3 : 7; }
+struct OpTally {
+    uint32_t* freq;
+    SVT_HD void op(uint32_t sym, uint32_t) { ++freq[sym]; }
+};
+struct OpWrite {
+    Writer& w;
+    const uint16_t* code;
+    const uint8_t* len;
+    SVT_HD void op(uint32_t sym, uint32_t extra) { w.put(code[sym] | (extra << len[sym]), len[sym] + op_extra_bits(sym)); }
+};
+// the order in which the header names the code-length code's lengths
+SVT_HD uint32_t cl_order(uint32_t i)
+{
+    static constexpr uint8_t order[kClSyms] = {16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15};
+    return order[i];
+}
+
+// The histogram of a member's tokens (K.freq, literal/length and distance symbols, the end-of-block not yet in it) -> the three
+// sets of lengths, their codes, HLIT / HDIST / HCLEN and the header's bits.  All lanes call it.
+template <class X>
+SVT_HD void build_code(Code& K)
+{
+    if (X::lane() == 0) ++K.freq[kEob];
+    code_lengths<X>(K.freq, kLitSyms, 15, K.len, K.build);
+    code_lengths<X>(K.freq + kDistAt, kDistSyms, 15, K.len + kDistAt, K.build);
+    for (uint32_t s = X::lane(); s < kClSyms; s += X::lanes()) K.freq[kClAt + s] = 0;
+    X::sync();
+    if (X::lane() == 0) {
+        uint32_t hlit = kLitSyms, hdist = kDistSyms;
+        while (hlit > 257 && K.len[hlit - 1] == 0) --hlit;
+        while (hdist > 1 && K.len[kDistAt + hdist - 1] == 0) --hdist;
+        if (hdist == 1 && K.len[kDistAt] == 0) K.len[kDistAt] = 1;    // no match in the member: one distance code of one bit
+        K.hlit = hlit;
+        K.hdist = hdist;
+        OpTally tally{K.freq + kClAt};
+        run_length_ops(K.len, hlit, tally);
+        run_length_ops(K.len + kDistAt, hdist, tally);
+    }
+    code_lengths<X>(K.freq + kClAt, kClSyms, 7, K.len + kClAt, K.build);
+    if (X::lane() == 0) {
+        canonical_codes(K.len, kLitSyms, K.code, K.build);
+        canonical_codes(K.len + kDistAt, kDistSyms, K.code + kDistAt, K.build);
+        canonical_codes(K.len + kClAt, kClSyms, K.code + kClAt, K.build);
+        uint32_t hclen = kClSyms;
+        while (hclen > 4 && K.len[kClAt + cl_order(hclen - 1)] == 0) --hclen;
+        K.hclen = hclen;
+        uint32_t bits = 3 + 5 + 5 + 4 + 3 * hclen;
+        SVT_DFL_KEEP_LOOP
+        for (uint32_t s = 0; s < kClSyms; ++s) bits += K.freq[kClAt + s] * (K.len[kClAt + s] + op_extra_bits(s));
+        K.header_bits = bits;
+    }
+    X::sync();
+}
+
+// the header of the dynamic block: BFINAL = 1, BTYPE = 10, HLIT, HDIST, HCLEN, the code-length code's lengths, the operations
+SVT_HD void write_dynamic_header(const Code& K, Writer& w)
+{
+    w.put(5, 3);
+    w.put(K.hlit - 257, 5);
+    w.put(K.hdist - 1, 5);
+    w.put(K.hclen - 4, 4);
+    SVT_DFL_KEEP_LOOP
+    for (uint32_t i = 0; i < K.hclen; ++i) w.put(K.len[kClAt + cl_order(i)], 3);
+    OpWrite ops{w, K.code + kClAt, K.len + kClAt};
+    run_length_ops(K.len, K.hlit, ops);
+    run_length_ops(K.len + kDistAt, K.hdist, ops);
+}
+
+// p[0, n), n <= kMaxPayload, deflated into out[0, cap), cap >= cdata_bound(n).  Returns the bytes written, the same on every
+// lane; 0: refused (n or cap out of range), nothing is written.  M = kDynamic: the dynamic block where it is strictly shorter
+// than what M = kFixed writes, those bytes otherwise.
+template <class X, uint32_t M = kFixed>
+SVT_HD uint32_t deflate_member(const uint8_t* p, uint32_t n, uint8_t* out, uint32_t cap, Scratch<X::kWidth, M>& S)
 {
     constexpr uint32_t W = X::kWidth;
     if (n > kMaxPayload || cap < cdata_bound(n)) return 0;
     const uint32_t C = (n + kLanes - 1) / kLanes;
     X::sync();                                              // (nobody still reads start / head of the member before)
+    if constexpr (M == kDynamic) {
+        for (uint32_t s = X::lane(); s < kClAt; s += X::lanes()) S.code.freq[s] = 0;
+        X::sync();
+    }
     for (uint32_t l = X::lane(); l < kLanes; l += X::lanes()) {
-        Count c{(l == 0 ? 3u : 0u) + (l == kLanes - 1 ? 7u : 0u)};
-        parse_chunk<W>(p, n, C, l, S.table + l % W, c);
-        S.start[l] = c.bits;
+        const uint32_t ends = (l == 0 ? 3u : 0u) + (l == kLanes - 1 ? 7u : 0u);
+        if constexpr (M == kDynamic) {
+            CountAndTally<X> c{ends, S.code.freq};
+            parse_chunk<W>(p, n, C, l, S.table + l % W, c);
+            S.start[l] = c.bits;
+        } else {
+            Count c{ends};
+            parse_chunk<W>(p, n, C, l, S.table + l % W, c);
+            S.start[l] = c.bits;
+        }
         S.head[l] = 0;
+    }
+    if constexpr (M == kDynamic) {
+        build_code<X>(S.code);                              // (begins with a sync())
+        for (uint32_t l = X::lane(); l < kLanes; l += X::lanes()) {
+            DynamicCount c{(l == 0 ? S.code.header_bits : 0u) + (l == kLanes - 1 ? S.code.len[kEob] : 0u), S.code.len};
+            parse_chunk<W>(p, n, C, l, S.table + l % W, c);
+            S.code.dstart[l] = c.bits;
+        }
     }
     X::sync();
     if (X::lane() == 0) {                                   // the exclusive prefix sum: 64 steps of one lane, in lane order
+        if constexpr (M == kDynamic) {                      // ... over the counts of the block that is going to be written
+            uint32_t fixed = 0, dynamic = 0;
+            SVT_DFL_KEEP_LOOP
+            for (uint32_t l = 0; l < kLanes; ++l) { fixed += S.start[l]; dynamic += S.code.dstart[l]; }
+            const uint32_t F = (fixed + 7) / 8, D = (dynamic + 7) / 8;
+            S.code.dynamic = D < (n > 0 && F >= 5 + n ? 5 + n : F);
+            if (S.code.dynamic)
+                SVT_DFL_KEEP_LOOP
+                for (uint32_t l = 0; l < kLanes; ++l) S.start[l] = S.code.dstart[l];
+        }
         uint32_t at = 0;
         for (uint32_t l = 0; l < kLanes; ++l) { const uint32_t c = S.start[l]; S.start[l] = at; at += c; }
         S.start[kLanes] = at;
     }
     X::sync();
-    const uint32_t F = (S.start[kLanes] + 7) / 8;
+    const uint32_t F = (S.start[kLanes] + 7) / 8;           // (the dynamic block's bytes where that was chosen: below 5 + n)
     if (n > 0 && F >= 5 + n) {                              // no gain: one stored block
         for (uint32_t i = X::lane(); i < 5 + n; i += X::lanes())
             out[i] = i == 0 ? 1 : i == 1 ? (uint8_t)n : i == 2 ? (uint8_t)(n >> 8) : i == 3 ? (uint8_t)~n : i == 4 ? (uint8_t)(~n >> 8) : p[i - 5];
         return 5 + n;
     }
     // (F < 5 + n <= cap, or n == 0 and F == 2 <= cap: every byte of the block has its place)
+    bool dynamic = false;
+    if constexpr (M == kDynamic) dynamic = S.code.dynamic != 0;
     for (uint32_t l = X::lane(); l < kLanes; l += X::lanes()) {
         Writer w;
         w.begin(out, cap, S.start[l]);
-        if (l == 0) w.put(3, 3);                            // BFINAL = 1, BTYPE = 01
-        parse_chunk<W>(p, n, C, l, S.table + l % W, w);
-        if (l == kLanes - 1) w.put(0, 7);                   // end of block
+        if constexpr (M == kDynamic) {
+            if (dynamic) {
+                if (l == 0) write_dynamic_header(S.code, w);
+                DynamicWrite sink{w, S.code.code, S.code.len};
+                parse_chunk<W>(p, n, C, l, S.table + l % W, sink);
+                if (l == kLanes - 1) w.put(S.code.code[kEob], S.code.len[kEob]);
+            }
+        }
+        if (!dynamic) {
+            if (l == 0) w.put(3, 3);                        // BFINAL = 1, BTYPE = 01
+            FixedWrite sink{w};
+            parse_chunk<W>(p, n, C, l, S.table + l % W, sink);
+            if (l == kLanes - 1) w.put(0, 7);               // end of block
+        }
         uint8_t tail;
         const bool owns = w.end(tail);
         S.head[l] = w.head;

@@ -12,7 +12,10 @@
 //   svt_deflate_pack_kernel  behind a prefix sum on the host: header, deflate bytes, CRC-32 and ISIZE of member k to out_off[k].
 // The CRC-32s are svt_crc32_kernel's over the same jobs on the same stream.  Parsing twice across two launches instead would
 // have cost the parse a third time (svt_deflate.h parses twice as it is) to save a copy of the compressed bytes, which are
-// the smaller side.  Plain loads and stores and LDS integer operations only: no atomics of any kind.
+// the smaller side.  Plain loads and stores and LDS integer operations only.  The fixed mode has no atomics of any kind; the
+// dynamic mode (svt_deflate_kernel<dfl::kDynamic>, 37 816 bytes of LDS: still four waves per CU) adds its tokens' symbols into
+// the member's histogram with atomicAdd on LDS counters -- integer sums, the same in any order -- and has no global atomics.
+// svt_huffman_lengths_kernel runs dfl::code_lengths alone, one wavefront per histogram.
 #ifndef SVT_DEFLATE_KERNEL_H
 #define SVT_DEFLATE_KERNEL_H
 
@@ -30,23 +33,41 @@ struct DeflateDevCtx {
     static __device__ __forceinline__ uint32_t lane() { return threadIdx.x; }
     static __device__ __forceinline__ uint32_t lanes() { return kDeflateBlock; }
     static __device__ __forceinline__ void sync() { __syncthreads(); }
+    static __device__ __forceinline__ void add(uint32_t* counter) { atomicAdd(counter, 1u); }     // (a counter in LDS)
 };
 
 // where member k's slot begins: the slots of the members in front (their payloads and 31 bytes each)
 __host__ __device__ inline uint64_t deflate_slot_at(uint64_t payload_off, uint64_t k) { return payload_off + k * dfl::slot_bytes(0); }
 
 // payload jobs[k] (crc::Job: off, len) of `bytes` -> slots + deflate_slot_at(off, k) + 18; clen[k]: its deflate bytes, 0: refused
+template <uint32_t M>
 __global__ __launch_bounds__(kDeflateBlock) void svt_deflate_kernel(const uint8_t* __restrict__ bytes, uint64_t bytes_len, const crc::Job* __restrict__ jobs,
                                                                     uint32_t n, uint8_t* __restrict__ slots, uint64_t slots_len, uint32_t* __restrict__ clen)
 {
-    __shared__ dfl::Scratch<kDeflateBlock> S;
+    __shared__ dfl::Scratch<kDeflateBlock, M> S;
     for (uint32_t k = blockIdx.x; k < n; k += gridDim.x) {      // (every decision in here is the same for all lanes)
         const crc::Job j = jobs[k];
         const uint64_t at = deflate_slot_at(j.off, k);
         const bool fits = j.len <= dfl::kMaxPayload && j.off <= bytes_len && j.len <= bytes_len - j.off && at <= slots_len &&
                           dfl::slot_bytes(j.len) <= slots_len - at;
-        const uint32_t c = fits ? dfl::deflate_member<DeflateDevCtx>(bytes + j.off, j.len, slots + at + dfl::kHeaderBytes, dfl::cdata_bound(j.len), S) : 0;
+        const uint32_t c = fits ? dfl::deflate_member<DeflateDevCtx, M>(bytes + j.off, j.len, slots + at + dfl::kHeaderBytes, dfl::cdata_bound(j.len), S) : 0;
         if (threadIdx.x == 0) clen[k] = c;
+    }
+}
+
+// histogram k (freq[k * symbols .. + symbols), symbols <= 286) -> its code lengths under `limit`, by dfl::code_lengths
+__global__ __launch_bounds__(kDeflateBlock) void svt_huffman_lengths_kernel(const uint32_t* __restrict__ freq, uint32_t sets, uint32_t symbols, uint32_t limit,
+                                                                            uint8_t* __restrict__ lengths)
+{
+    __shared__ uint32_t f[dfl::kLitSyms];
+    __shared__ uint8_t len[dfl::kLitSyms];
+    __shared__ dfl::Build B;
+    if (symbols > dfl::kLitSyms || limit < 1 || limit > 15) return;
+    for (uint32_t k = blockIdx.x; k < sets; k += gridDim.x) {
+        __syncthreads();                                        // (nobody still reads len of the histogram before)
+        for (uint32_t s = threadIdx.x; s < symbols; s += kDeflateBlock) f[s] = freq[(uint64_t)k * symbols + s];
+        dfl::code_lengths<DeflateDevCtx>(f, symbols, limit, len, B);
+        for (uint32_t s = threadIdx.x; s < symbols; s += kDeflateBlock) lengths[(uint64_t)k * symbols + s] = len[s];
     }
 }
 

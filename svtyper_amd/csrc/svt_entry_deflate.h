@@ -1,15 +1,19 @@
 // svt_entry_deflate.h -- part of the single translation unit svtyper_hip.hip (included there, in order; not a stand-alone header):
 // BGZF deflate on the device.  Payloads go up, svt_crc32_kernel and svt_deflate_kernel run over the same jobs on the call's
 // stream, the sizes come back for a prefix sum on the host, svt_deflate_pack_kernel puts the members side by side, and they
-// come down.  C ABI: svt_bgzf_deflate_device, svt_bgzf_deflate_last_times (include/svtyper_reads.h).
+// come down.  C ABI: svt_bgzf_deflate_device, svt_bgzf_deflate_device_mode, svt_bgzf_deflate_last_times, and the code-length rule
+// on its own, svt_huffman_lengths_device (include/svtyper_reads.h).
 
 extern "C++" {
 
 // the three kernels of the calling thread's last svt_bgzf_deflate_device, from HIP events, and the call's wall time
 static thread_local svt_deflate_times g_deflate_times;
 
-static int svt_bgzf_deflate_device_impl(const uint8_t* bytes, const uint64_t* off, uint64_t n, uint8_t* out, uint64_t capacity, uint64_t* out_off, int device)
+static int svt_bgzf_deflate_device_impl(const uint8_t* bytes, const uint64_t* off, uint64_t n, uint8_t* out, uint64_t capacity, uint64_t* out_off, uint32_t mode,
+                                        int device)
 {
+    if (mode != SVT_DEFLATE_FIXED && mode != SVT_DEFLATE_DYNAMIC)
+        return fail(SVT_ERR_INVALID, "svt_bgzf_deflate: mode is SVT_DEFLATE_FIXED (0) or SVT_DEFLATE_DYNAMIC (1)");
     const auto t0 = std::chrono::steady_clock::now();
     g_deflate_times = svt_deflate_times();
     uint64_t slots = 0;
@@ -48,7 +52,7 @@ static int svt_bgzf_deflate_device_impl(const uint8_t* bytes, const uint64_t* of
     SVT_TRY(launch_crc_kernel(c.d_bytes.as<uint8_t>(), payload_bytes, c.d_jobs.as<crc::Job>(), n, c.d_tables.as<crc::Tables>(), c.d_crc.as<uint32_t>(), nullptr,
                               device, c.s));
     HIP_TRY(hipEventRecord(c.ev[1], c.s));
-    hipLaunchKernelGGL(svt_deflate_kernel, dim3((unsigned)std::min(n, waves)), dim3(kDeflateBlock), 0, c.s, c.d_bytes.as<uint8_t>(), payload_bytes,
+    hipLaunchKernelGGL(mode == SVT_DEFLATE_DYNAMIC ? svt_deflate_kernel<dfl::kDynamic> : svt_deflate_kernel<dfl::kFixed>, dim3((unsigned)std::min(n, waves)), dim3(kDeflateBlock), 0, c.s, c.d_bytes.as<uint8_t>(), payload_bytes,
                        c.d_jobs.as<crc::Job>(), (uint32_t)n, c.d_slots.as<uint8_t>(), slots, c.d_clen.as<uint32_t>());
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(c.ev[2], c.s));
@@ -84,7 +88,41 @@ static int svt_bgzf_deflate_device_impl(const uint8_t* bytes, const uint64_t* of
 
 int svt_bgzf_deflate_device(const uint8_t* bytes, const uint64_t* off, uint64_t n, uint8_t* out, uint64_t capacity, uint64_t* out_off, int device)
 {
-    return guarded([&] { return svt_bgzf_deflate_device_impl(bytes, off, n, out, capacity, out_off, device); });
+    return guarded([&] { return svt_bgzf_deflate_device_impl(bytes, off, n, out, capacity, out_off, SVT_DEFLATE_FIXED, device); });
+}
+
+int svt_bgzf_deflate_device_mode(const uint8_t* bytes, const uint64_t* off, uint64_t n, uint8_t* out, uint64_t capacity, uint64_t* out_off, uint32_t mode,
+                                 int device)
+{
+    return guarded([&] { return svt_bgzf_deflate_device_impl(bytes, off, n, out, capacity, out_off, mode, device); });
+}
+
+int svt_huffman_lengths_device(const uint32_t* freq, uint32_t sets, uint32_t symbols, uint32_t limit, uint8_t* lengths, int device)
+{
+    return guarded([&]() -> int {
+        SVT_TRY(huffman_check_args(freq, sets, symbols, limit, lengths));
+        SVT_TRY(select_device(device));
+        if (sets == 0) return SVT_OK;
+        struct Call : CallStream {                           // (destruction order: CallStream, svt_batch_state.h)
+            DevScratch d_freq, d_len;
+            ~Call() { drain(); }
+        } c;
+        SVT_TRY(c.take());
+        const uint64_t count = (uint64_t)sets * symbols;
+        SVT_TRY(c.d_freq.alloc(count * sizeof(uint32_t)));
+        SVT_TRY(c.d_len.alloc(count));
+        {
+            Stager st(c.s);
+            SVT_TRY(st.copy(c.d_freq.p, freq, count * sizeof(uint32_t)));
+            SVT_TRY(st.finish());
+        }
+        const uint64_t waves = (uint64_t)std::max<uint32_t>(cu_count(device), 1) * kDeflateWavesPerCu;
+        hipLaunchKernelGGL(svt_huffman_lengths_kernel, dim3((unsigned)std::min<uint64_t>(sets, waves)), dim3(kDeflateBlock), 0, c.s, c.d_freq.as<uint32_t>(), sets,
+                           symbols, limit, c.d_len.as<uint8_t>());
+        HIP_TRY(hipGetLastError());
+        SVT_TRY(d2h_staged(lengths, c.d_len.p, count, c.s));
+        return SVT_OK;
+    });
 }
 
 int svt_bgzf_deflate_last_times(svt_deflate_times* times)

@@ -39,31 +39,58 @@ int svt_bgzf_crc32_host(const uint8_t* bytes, const uint64_t* off, uint64_t n, u
 }
 
 // svt_deflate.h on this thread, member by member: each into a slot of its own first, since its size is known only afterwards
+extern "C++" {
+template <uint32_t M>
+static int svt_bgzf_deflate_host_impl(const uint8_t* bytes, const uint64_t* off, uint64_t n, uint8_t* out, uint64_t capacity, uint64_t* out_off)
+{
+    namespace dfl = svt::dfl;
+    uint64_t slots = 0;
+    if (const int rc = svt::deflate_check_args(bytes, off, n, out, out_off, slots)) return rc;
+    std::unique_ptr<dfl::Scratch<dfl::HostCtx::kWidth, M>> S(new dfl::Scratch<dfl::HostCtx::kWidth, M>());
+    std::unique_ptr<svt::crc::Scratch> C(new svt::crc::Scratch());
+    std::vector<uint8_t> slot(dfl::slot_bytes(dfl::kMaxPayload));
+    uint64_t at = 0;
+    out_off[0] = 0;
+    for (uint64_t k = 0; k < n; ++k) {
+        const uint8_t* p = bytes + off[k];
+        const uint32_t len = (uint32_t)(off[k + 1] - off[k]);
+        const uint32_t clen = dfl::deflate_member<dfl::HostCtx, M>(p, len, slot.data() + dfl::kHeaderBytes, dfl::cdata_bound(len), *S);
+        if (!clen) return fail(SVT_ERR_INVALID, "svt_bgzf_deflate: a payload was refused");
+        const uint64_t size = (uint64_t)dfl::kHeaderBytes + clen + dfl::kTrailerBytes;
+        if (size > capacity - at) return fail(SVT_ERR_INVALID, "svt_bgzf_deflate: capacity is below what the members need");
+        const uint32_t crc = svt::crc::crc_member<svt::crc::HostCtx>(p, len, svt::crc_tables(), *C);
+        for (uint32_t i = 0; i < dfl::kHeaderBytes; ++i) slot[i] = dfl::header_byte(i, clen);
+        for (uint32_t i = 0; i < dfl::kTrailerBytes; ++i) slot[dfl::kHeaderBytes + clen + i] = dfl::trailer_byte(i, crc, len);
+        std::memcpy(out + at, slot.data(), size);
+        at += size;
+        out_off[k + 1] = at;
+    }
+    return SVT_OK;
+}
+}  // extern "C++"
+
 int svt_bgzf_deflate_host(const uint8_t* bytes, const uint64_t* off, uint64_t n, uint8_t* out, uint64_t capacity, uint64_t* out_off)
+{
+    return guarded([&] { return svt_bgzf_deflate_host_impl<svt::dfl::kFixed>(bytes, off, n, out, capacity, out_off); });
+}
+
+int svt_bgzf_deflate_host_mode(const uint8_t* bytes, const uint64_t* off, uint64_t n, uint8_t* out, uint64_t capacity, uint64_t* out_off, uint32_t mode)
+{
+    return guarded([&]() -> int {
+        if (mode == SVT_DEFLATE_FIXED) return svt_bgzf_deflate_host_impl<svt::dfl::kFixed>(bytes, off, n, out, capacity, out_off);
+        if (mode == SVT_DEFLATE_DYNAMIC) return svt_bgzf_deflate_host_impl<svt::dfl::kDynamic>(bytes, off, n, out, capacity, out_off);
+        return fail(SVT_ERR_INVALID, "svt_bgzf_deflate: mode is SVT_DEFLATE_FIXED (0) or SVT_DEFLATE_DYNAMIC (1)");
+    });
+}
+
+// dfl::code_lengths on this thread, histogram by histogram
+int svt_huffman_lengths_host(const uint32_t* freq, uint32_t sets, uint32_t symbols, uint32_t limit, uint8_t* lengths)
 {
     namespace dfl = svt::dfl;
     return guarded([&]() -> int {
-        uint64_t slots = 0;
-        if (const int rc = svt::deflate_check_args(bytes, off, n, out, out_off, slots)) return rc;
-        std::unique_ptr<dfl::Scratch<dfl::HostCtx::kWidth>> S(new dfl::Scratch<dfl::HostCtx::kWidth>());
-        std::unique_ptr<svt::crc::Scratch> C(new svt::crc::Scratch());
-        std::vector<uint8_t> slot(dfl::slot_bytes(dfl::kMaxPayload));
-        uint64_t at = 0;
-        out_off[0] = 0;
-        for (uint64_t k = 0; k < n; ++k) {
-            const uint8_t* p = bytes + off[k];
-            const uint32_t len = (uint32_t)(off[k + 1] - off[k]);
-            const uint32_t clen = dfl::deflate_member<dfl::HostCtx>(p, len, slot.data() + dfl::kHeaderBytes, dfl::cdata_bound(len), *S);
-            if (!clen) return fail(SVT_ERR_INVALID, "svt_bgzf_deflate: a payload was refused");
-            const uint64_t size = (uint64_t)dfl::kHeaderBytes + clen + dfl::kTrailerBytes;
-            if (size > capacity - at) return fail(SVT_ERR_INVALID, "svt_bgzf_deflate: capacity is below what the members need");
-            const uint32_t crc = svt::crc::crc_member<svt::crc::HostCtx>(p, len, svt::crc_tables(), *C);
-            for (uint32_t i = 0; i < dfl::kHeaderBytes; ++i) slot[i] = dfl::header_byte(i, clen);
-            for (uint32_t i = 0; i < dfl::kTrailerBytes; ++i) slot[dfl::kHeaderBytes + clen + i] = dfl::trailer_byte(i, crc, len);
-            std::memcpy(out + at, slot.data(), size);
-            at += size;
-            out_off[k + 1] = at;
-        }
+        if (const int rc = svt::huffman_check_args(freq, sets, symbols, limit, lengths)) return rc;
+        std::unique_ptr<dfl::Build> B(new dfl::Build());
+        for (uint64_t k = 0; k < sets; ++k) dfl::code_lengths<dfl::HostCtx>(freq + k * symbols, symbols, limit, lengths + k * symbols, *B);
         return SVT_OK;
     });
 }

@@ -119,6 +119,7 @@ class Driver:
     bulk_under_debug = True
     alignment_outpath = None            # (`svtyper -w`; classic.Classic sets it)
     deflate = "zlib"                    # who compresses the `-w` BAM's members (bam.BgzfWriter)
+    huffman = "fixed"                   # ... and into which block, where it is the library's own compressor
 
     def __init__(self, bam_string, vcf_in, vcf_out, min_aligned, split_weight, disc_weight, num_samp, lib_info_path, debug,
                  ref_fasta, sum_quals, max_reads, max_ci_dist, n_threads=0):
@@ -162,7 +163,7 @@ class Driver:
         out_bam, written = None, set()
         if writing:     # classic.py:161-166: the first alignment file is the template, its header is the dump's
             template = AlignmentFile(paths[0], "rb")
-            out_bam = AlignmentFile(self.alignment_outpath, "wb", template=template, deflate=self.deflate,
+            out_bam = AlignmentFile(self.alignment_outpath, "wb", template=template, deflate=self.deflate, huffman=self.huffman,
                                     device=getattr(engine, "device", 0))
             template.close()
         self.write_library_file()
@@ -348,9 +349,11 @@ def parse_arguments(p, bam_help, max_reads, own):
                    help="with --reader python: breakpoint-dependent read predicates on the host or on the GPU [host]")
     # BGZF output (README).  Not listed by --help, like --debug: the help text of both programs is pinned byte for byte
     # (tests/golden/help_*.txt).  --bgzf: the output VCF as BGZF (.vcf.gz: what bcftools, tabix and IGV read); --deflate: who
-    # compresses BGZF output (--bgzf, -w) -- zlib, or the library's own compressor on the host or on the GPU (same inflated bytes).
+    # compresses BGZF output (--bgzf, -w) -- zlib, or the library's own compressor on the host or on the GPU (same inflated bytes);
+    # --huffman: the block that compressor writes -- fixed, or dynamic where that is shorter (not with --deflate zlib).
     p.add_argument("--bgzf", action="store_true", help=argparse.SUPPRESS)
     p.add_argument("--deflate", choices=("zlib", "host", "device"), default="zlib", help=argparse.SUPPRESS)
+    p.add_argument("--huffman", choices=("fixed", "dynamic"), default="fixed", help=argparse.SUPPRESS)
     args = p.parse_args()
     if args.input_vcf is None and not sys.stdin.isatty():
         args.input_vcf = sys.stdin
@@ -369,23 +372,23 @@ def run_main(driver, sharded_driver, call, args):
     if job is None:
         if not args.bgzf:
             return driver(*call, **options)
-        with _bgzf_text(call[2], args.deflate, 0) as out:
+        with _bgzf_text(call[2], args.deflate, 0, getattr(args, "huffman", "fixed")) as out:
             return driver(*call[:2], out, *call[3:], **options)
     rank, world, local_rank = job
     call = call[:2] + (sharded.private_stdout(call[2]),) + call[3:]
     engine = sharded.init(local_rank)
     if args.bgzf and rank == 0:             # (rank 0 writes everything: the others touch nothing)
-        with _bgzf_text(call[2], args.deflate, getattr(engine, "device", local_rank)) as out:
+        with _bgzf_text(call[2], args.deflate, getattr(engine, "device", local_rank), getattr(args, "huffman", "fixed")) as out:
             sharded_driver(*call[:2], out, *call[3:], rank=rank, world=world, engine=engine, **options)
     else:
         sharded_driver(*call, rank=rank, world=world, engine=engine, **options)
     sharded.finish()
 
 
-def _bgzf_text(vcf_out, deflate, device):
+def _bgzf_text(vcf_out, deflate, device, huffman="fixed"):
     """`--bgzf`: the output VCF through bgzf_out.open_text (imported only here)"""
     from . import bgzf_out
-    return bgzf_out.open_text(vcf_out, deflate=deflate, device=device)
+    return bgzf_out.open_text(vcf_out, deflate=deflate, device=device, huffman=huffman)
 
 
 def run_cli(main):

@@ -249,6 +249,15 @@ def _lib():
             L.svt_bgzf_deflate_device.argtypes = L.svt_bgzf_deflate_host.argtypes + [C.c_int]
             L.svt_bgzf_deflate_last_times.restype = C.c_int
             L.svt_bgzf_deflate_last_times.argtypes = [C.POINTER(_DeflateTimes)]
+        if hasattr(L, "svt_bgzf_deflate_host_mode"):   # (likewise: the dynamic block and the code-length rule on its own)
+            L.svt_bgzf_deflate_host_mode.restype = C.c_int
+            L.svt_bgzf_deflate_host_mode.argtypes = L.svt_bgzf_deflate_host.argtypes + [C.c_uint32]
+            L.svt_bgzf_deflate_device_mode.restype = C.c_int
+            L.svt_bgzf_deflate_device_mode.argtypes = L.svt_bgzf_deflate_host_mode.argtypes + [C.c_int]
+            L.svt_huffman_lengths_host.restype = C.c_int
+            L.svt_huffman_lengths_host.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
+            L.svt_huffman_lengths_device.restype = C.c_int
+            L.svt_huffman_lengths_device.argtypes = L.svt_huffman_lengths_host.argtypes + [C.c_int]
         L.svt_bam_set_verify.restype = C.c_int
         L.svt_bam_set_verify.argtypes = [C.c_void_p, C.c_int]
         L.svt_bam_get_verify.restype = C.c_int
@@ -670,23 +679,36 @@ def bgzf_inflate(data: bytes, block_off: np.ndarray, out_off: np.ndarray, device
 
 DEFLATE_MAX_PAYLOAD = 65280      # bytes of payload in one member (svt_deflate.h: dfl::kMaxPayload)
 DEFLATE_SLOT_EXTRA = 31          # what a member takes beyond its payload at the most: header, a stored block's 5 bytes, trailer
+HUFFMAN_CHOICES = ("fixed", "dynamic")   # include/svtyper_reads.h: SVT_DEFLATE_FIXED, SVT_DEFLATE_DYNAMIC
 
 
-def bgzf_deflate(payloads: Sequence[bytes], device: Optional[int] = None, capacity: Optional[int] = None) -> Tuple[np.ndarray, np.ndarray]:
+def check_huffman(huffman) -> str:
+    if huffman not in HUFFMAN_CHOICES:
+        raise ValueError("huffman must be one of %s, not %r" % (", ".join(repr(c) for c in HUFFMAN_CHOICES), huffman))
+    return huffman
+
+
+def bgzf_deflate(payloads: Sequence[bytes], device: Optional[int] = None, capacity: Optional[int] = None,
+                 huffman: str = "fixed") -> Tuple[np.ndarray, np.ndarray]:
     """svt_bgzf_deflate_host (device None) / svt_bgzf_deflate_device: every payload (at most 65 280 bytes) as one whole BGZF
     member, by the one-source compressor (svt_deflate.h).  Returns (members uint8 [out_off[-1]], out_off uint64 [n + 1]).
-    `capacity`: the room offered for the members (default: what always suffices)."""
+    `capacity`: the room offered for the members (default: what always suffices).  `huffman`: "fixed", or "dynamic" (the
+    _mode entries with SVT_DEFLATE_DYNAMIC): a dynamic-Huffman block for every member that is shorter that way."""
     sizes = np.fromiter((len(p) for p in payloads), np.uint64, len(payloads))
     off = np.zeros(len(payloads) + 1, np.uint64)
     np.cumsum(sizes, out=off[1:])
-    return bgzf_deflate_at(b"".join(payloads), off, device, capacity)
+    return bgzf_deflate_at(b"".join(payloads), off, device, capacity, huffman)
 
 
-def bgzf_deflate_at(data: bytes, off: np.ndarray, device: Optional[int] = None, capacity: Optional[int] = None) -> Tuple[np.ndarray, np.ndarray]:
+def bgzf_deflate_at(data: bytes, off: np.ndarray, device: Optional[int] = None, capacity: Optional[int] = None,
+                    huffman: str = "fixed") -> Tuple[np.ndarray, np.ndarray]:
     """bgzf_deflate over payloads that lie in `data` already: payload k is data[off[k] .. off[k + 1])"""
     L = _lib()
+    dynamic = check_huffman(huffman) == "dynamic"
     if not hasattr(L, "svt_bgzf_deflate_host"):
         raise hip.SvtyperHipError("this libsvtyper_hip.so has no svt_bgzf_deflate_host (built before BGZF deflate)")
+    if dynamic and not hasattr(L, "svt_bgzf_deflate_host_mode"):
+        raise hip.SvtyperHipError("this libsvtyper_hip.so has no svt_bgzf_deflate_host_mode (built before dynamic Huffman blocks)")
     off = np.ascontiguousarray(off, np.uint64)
     n = int(off.shape[0]) - 1
     if n < 0:
@@ -697,11 +719,38 @@ def bgzf_deflate_at(data: bytes, off: np.ndarray, device: Optional[int] = None, 
     out = np.zeros(max(int(capacity), 1), np.uint8)
     out_off = np.zeros(n + 1, np.uint64)
     args = [buf.ctypes.data, off.ctypes.data, n, out.ctypes.data, int(capacity), out_off.ctypes.data]
-    if device is None:
+    if dynamic:
+        if device is None:
+            hip._check(L.svt_bgzf_deflate_host_mode(*args, 1))
+        else:
+            hip._check(L.svt_bgzf_deflate_device_mode(*args, 1, int(device)))
+    elif device is None:
         hip._check(L.svt_bgzf_deflate_host(*args))
     else:
         hip._check(L.svt_bgzf_deflate_device(*args, int(device)))
     return out[:int(out_off[-1])], out_off
+
+
+def huffman_lengths(freq, limit: int, device: Optional[int] = None) -> np.ndarray:
+    """svt_huffman_lengths_host (device None) / _device: the dynamic block's code-length rule on its own.  `freq`: one histogram
+    [symbols] or several [sets, symbols] (symbols <= 286); returns uint8 code lengths of at most `limit` (7 or 15) bits in the
+    same shape."""
+    L = _lib()
+    if not hasattr(L, "svt_huffman_lengths_host"):
+        raise hip.SvtyperHipError("this libsvtyper_hip.so has no svt_huffman_lengths_host (built before dynamic Huffman blocks)")
+    f = np.ascontiguousarray(freq, np.uint32)
+    if f.ndim not in (1, 2) or f.shape[-1] < 1:
+        raise ValueError("freq must be [symbols] or [sets, symbols]")
+    sets, symbols = (1, f.shape[0]) if f.ndim == 1 else f.shape
+    out = np.zeros(f.shape, np.uint8)
+    src = f if f.size else np.zeros(1, np.uint32)
+    dst = out if out.size else np.zeros(1, np.uint8)
+    args = [src.ctypes.data, int(sets), int(symbols), int(limit), dst.ctypes.data]
+    if device is None:
+        hip._check(L.svt_huffman_lengths_host(*args))
+    else:
+        hip._check(L.svt_huffman_lengths_device(*args, int(device)))
+    return out
 
 
 def bgzf_deflate_last_times() -> Dict[str, float]:
