@@ -268,6 +268,73 @@ int svt_huffman_lengths_host(const uint32_t* freq, uint32_t sets, uint32_t symbo
 int svt_huffman_lengths_device(const uint32_t* freq, uint32_t sets, uint32_t symbols, uint32_t limit, uint8_t* lengths,
                                int device);
 
+/* ---- VCF text as lines: sorted, tabix-indexed BGZF output (additions; the ABI number stays: probe for the symbols) ----
+ * svtyper_amd/csrc/svt_vcf_lines.h holds the per-line rule of the tabix VCF preset as one piece of
+ * source for the host and the device (svt_vcf_lines_kernel.h).  A line is the bytes up to and including '\n'; the last
+ * one may lack it.  One record per line, in text order:
+ *   off, len     where the line lies in the text and how long it is (its newline included)
+ *   flags        SVT_TBX_META: it starts with '#'.  SVT_TBX_BAD: not a data line (fewer than 8 tab-separated columns, a
+ *                POS that is not 1 .. 10 decimal digits below 2^31, an empty line).  SVT_TBX_RANGE: end > 2^29, beyond
+ *                what a TBI index addresses (a CSI index is not written).
+ *   beg, end     (data lines) beg = max(POS - 1, 0); end = beg + len(REF), or the value of the first INFO key END (at the
+ *                start of INFO or behind ';', followed by '=' and a digit) where it has at most 10 digits and lies above
+ *                beg; saturated at 2^32 - 1
+ *   chrom_len    bytes of the CHROM column                                                                            */
+typedef struct svt_tbx_line {
+    uint64_t off, len;
+    uint32_t beg, end, chrom_len, flags;
+} svt_tbx_line;
+#define SVT_TBX_META 1u
+#define SVT_TBX_BAD 2u
+#define SVT_TBX_RANGE 4u
+/* what a body line cannot be for svt_vcf_sort_order / svt_tbx_build (bad_kind) */
+#define SVT_TBX_NOT_DATA 1u      /* a '#' line behind the first data line, or a SVT_TBX_BAD one                        */
+#define SVT_TBX_BEYOND 2u        /* SVT_TBX_RANGE                                                                      */
+#define SVT_TBX_CONTIG_AGAIN 3u  /* a contig that reappears behind another one                                         */
+#define SVT_TBX_POS_BACK 4u      /* beg below the beg of the line in front, on the same contig                         */
+/* The line table of text[0, len): lines[0, *n_lines).  SVT_ERR_INVALID where capacity is below the number of lines
+ * (*n_lines is set all the same; the newlines of the text and one always suffice).                                  */
+int svt_vcf_lines_host(const uint8_t* text, uint64_t len, svt_tbx_line* lines, uint64_t capacity, uint64_t* n_lines);
+int svt_vcf_lines_device(const uint8_t* text, uint64_t len, svt_tbx_line* lines, uint64_t capacity, uint64_t* n_lines,
+                         int device);
+/* Line lines[perm[j]] of the text becomes line j of out[0, out_len): out_len is the sum of their lengths.            */
+int svt_vcf_gather_host(const uint8_t* text, uint64_t len, const svt_tbx_line* lines, uint64_t n, const uint64_t* perm,
+                        uint64_t n_perm, uint8_t* out, uint64_t out_len);
+int svt_vcf_gather_device(const uint8_t* text, uint64_t len, const svt_tbx_line* lines, uint64_t n, const uint64_t* perm,
+                          uint64_t n_perm, uint8_t* out, uint64_t out_len, int device);
+/* The order --sort writes: the header (the '#' lines in front of the first other line) as it is, then the body in
+ * stable order by (contig rank, POS): the rank of a contig is its place among the header's ##contig=<ID=...> lines,
+ * the contigs the header does not declare behind them in order of first appearance.  perm holds n entries.  A body
+ * line that is no data line: *bad_line is its 1-based number (SVT_OK, perm undefined); 0 otherwise.                 */
+int svt_vcf_sort_order(const uint8_t* text, uint64_t len, const svt_tbx_line* lines, uint64_t n, uint64_t* perm,
+                       uint64_t* bad_line);
+/* One call for the writer with deflate="device": the text goes up once; its line table is made there; with sort != 0
+ * the keys come down, the order goes up and the lines are gathered into a second buffer; the text as written is cut
+ * every 65 280 bytes and compressed by the kernels of svt_bgzf_deflate_device_mode (the same members, byte for
+ * byte).  out / capacity / out_off (ceil(len / 65280) + 1 entries) as there.  lines[0, *n_lines): the table of the
+ * text as written; src_off[j]: where written line j lies in the caller's text.  *bad_line as svt_vcf_sort_order
+ * (then nothing is compressed).                                                                                      */
+int svt_vcf_bgzf_device(const uint8_t* text, uint64_t len, int sort, uint32_t mode, uint8_t* out, uint64_t capacity,
+                        uint64_t* out_off, svt_tbx_line* lines, uint64_t line_capacity, uint64_t* n_lines,
+                        uint64_t* src_off, uint64_t* bad_line, int device);
+/* the calling thread's most recent svt_vcf_lines_device / _gather_device / _bgzf_device: its kernels by HIP events */
+typedef struct svt_vcf_lines_times {
+    double count_kernel_s, starts_kernel_s, parse_kernel_s, gather_kernel_s;
+    double total_s;             /* the whole call on the host's clock                                                */
+} svt_vcf_lines_times;
+int svt_vcf_lines_last_times(svt_vcf_lines_times* times);
+/* The index fold: the uncompressed bytes of a .tbi (SAM spec 5.2 binning, 14-bit leaves, five levels; the layout of
+ * the tabix format, format = 2 (VCF), col_seq 1, col_beg 2, col_end 0, meta '#', skip 0; pseudo-bin 37450 with the
+ * contig's line count) for the body lines of `lines`, a table of the text as written.  The CHROM of line j is read at
+ * text + (src_off ? src_off[j] : lines[j].off).  Payload k of the BGZF file holds text bytes [k * payload, ...) and
+ * its member begins at file offset member_off[k]; member_off[n_members] is where the members end.  The result is kept
+ * for the calling thread: *size is its length, svt_tbx_take copies it out.  A line the index cannot hold: *bad_line is
+ * its 1-based number, *bad_kind why (SVT_OK, no result); 0 otherwise.                                                */
+int svt_tbx_build(const uint8_t* text, uint64_t len, const uint64_t* src_off, const svt_tbx_line* lines, uint64_t n,
+                  const uint64_t* member_off, uint64_t n_members, uint32_t payload, uint64_t* size, uint64_t* bad_line,
+                  uint32_t* bad_kind);
+int svt_tbx_take(uint8_t* out, uint64_t capacity);
+
 /* Verify: a property of the handle, off by default (0).  With it on, every call that takes the handle checks the
  * CRC-32 of every BGZF member it inflates, where it inflates it: the host reader's threads (libdeflate's or zlib's
  * crc32), or svt_crc32_kernel behind svt_inflate_kernel for the routes that inflate on the GPU (the expected values

@@ -9,50 +9,39 @@ extern "C++" {
 // the three kernels of the calling thread's last svt_bgzf_deflate_device, from HIP events, and the call's wall time
 static thread_local svt_deflate_times g_deflate_times;
 
-static int svt_bgzf_deflate_device_impl(const uint8_t* bytes, const uint64_t* off, uint64_t n, uint8_t* out, uint64_t capacity, uint64_t* out_off, uint32_t mode,
-                                        int device)
+// a device call that compresses: its stream, the buffers of the members' way through the kernels, the events around the three kernels
+struct DeflateCall : CallStream {                            // (destruction order: CallStream, svt_batch_state.h)
+    DevScratch d_bytes, d_jobs, d_tables, d_crc, d_clen, d_slots, d_out_off, d_out;
+    hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    ~DeflateCall()
+    {
+        drain();
+        for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
+    }
+};
+
+// the payloads `jobs` of d_bytes[0, payload_bytes), device memory that c.s has filled -> their members in out, out_off[0 .. n]
+static int deflate_resident(DeflateCall& c, const uint8_t* d_bytes, uint64_t payload_bytes, const std::vector<crc::Job>& jobs, uint64_t slots, uint8_t* out,
+                            uint64_t capacity, uint64_t* out_off, uint32_t mode, int device)
 {
-    if (mode != SVT_DEFLATE_FIXED && mode != SVT_DEFLATE_DYNAMIC)
-        return fail(SVT_ERR_INVALID, "svt_bgzf_deflate: mode is SVT_DEFLATE_FIXED (0) or SVT_DEFLATE_DYNAMIC (1)");
-    const auto t0 = std::chrono::steady_clock::now();
-    g_deflate_times = svt_deflate_times();
-    uint64_t slots = 0;
-    SVT_TRY(deflate_check_args(bytes, off, n, out, out_off, slots));
-    SVT_TRY(select_device(device));
-    out_off[0] = 0;
-    if (n == 0) return SVT_OK;
-    struct DeflateCall : CallStream {                        // (destruction order: CallStream, svt_batch_state.h)
-        DevScratch d_bytes, d_jobs, d_tables, d_crc, d_clen, d_slots, d_out_off, d_out;
-        hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};   // around the three kernels
-        ~DeflateCall()
-        {
-            drain();
-            for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
-        }
-    } c;
-    SVT_TRY(c.take());
+    const uint64_t n = jobs.size();
     for (hipEvent_t& e : c.ev) HIP_TRY(hipEventCreate(&e));
-    const uint64_t payload_bytes = off[n] - off[0];
-    std::vector<crc::Job> jobs(n);
-    for (uint64_t k = 0; k < n; ++k) jobs[k] = crc::Job{off[k] - off[0], (uint32_t)(off[k + 1] - off[k]), 0};
-    SVT_TRY(c.d_bytes.alloc(payload_bytes));
     SVT_TRY(c.d_crc.alloc(n * sizeof(uint32_t)));
     SVT_TRY(c.d_clen.alloc(n * sizeof(uint32_t)));
     SVT_TRY(c.d_slots.alloc(slots));
     SVT_TRY(c.d_out_off.alloc((n + 1) * sizeof(uint64_t)));
     {
         Stager st(c.s);
-        if (payload_bytes) SVT_TRY(st.copy(c.d_bytes.p, bytes + off[0], payload_bytes));
         SVT_TRY(upload(c.d_jobs, jobs, st));
         SVT_TRY(upload_crc_tables(c.d_tables, st));
         SVT_TRY(st.finish());
     }
     const uint64_t waves = (uint64_t)std::max<uint32_t>(cu_count(device), 1) * kDeflateWavesPerCu;
     HIP_TRY(hipEventRecord(c.ev[0], c.s));
-    SVT_TRY(launch_crc_kernel(c.d_bytes.as<uint8_t>(), payload_bytes, c.d_jobs.as<crc::Job>(), n, c.d_tables.as<crc::Tables>(), c.d_crc.as<uint32_t>(), nullptr,
+    SVT_TRY(launch_crc_kernel(d_bytes, payload_bytes, c.d_jobs.as<crc::Job>(), n, c.d_tables.as<crc::Tables>(), c.d_crc.as<uint32_t>(), nullptr,
                               device, c.s));
     HIP_TRY(hipEventRecord(c.ev[1], c.s));
-    hipLaunchKernelGGL(mode == SVT_DEFLATE_DYNAMIC ? svt_deflate_kernel<dfl::kDynamic> : svt_deflate_kernel<dfl::kFixed>, dim3((unsigned)std::min(n, waves)), dim3(kDeflateBlock), 0, c.s, c.d_bytes.as<uint8_t>(), payload_bytes,
+    hipLaunchKernelGGL(mode == SVT_DEFLATE_DYNAMIC ? svt_deflate_kernel<dfl::kDynamic> : svt_deflate_kernel<dfl::kFixed>, dim3((unsigned)std::min(n, waves)), dim3(kDeflateBlock), 0, c.s, d_bytes, payload_bytes,
                        c.d_jobs.as<crc::Job>(), (uint32_t)n, c.d_slots.as<uint8_t>(), slots, c.d_clen.as<uint32_t>());
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(c.ev[2], c.s));
@@ -80,6 +69,33 @@ static int svt_bgzf_deflate_device_impl(const uint8_t* bytes, const uint64_t* of
     g_deflate_times.crc_kernel_s = crc_ms * 1e-3;
     g_deflate_times.deflate_kernel_s = deflate_ms * 1e-3;
     g_deflate_times.pack_kernel_s = pack_ms * 1e-3;
+    return SVT_OK;
+}
+
+static int svt_bgzf_deflate_device_impl(const uint8_t* bytes, const uint64_t* off, uint64_t n, uint8_t* out, uint64_t capacity, uint64_t* out_off, uint32_t mode,
+                                        int device)
+{
+    if (mode != SVT_DEFLATE_FIXED && mode != SVT_DEFLATE_DYNAMIC)
+        return fail(SVT_ERR_INVALID, "svt_bgzf_deflate: mode is SVT_DEFLATE_FIXED (0) or SVT_DEFLATE_DYNAMIC (1)");
+    const auto t0 = std::chrono::steady_clock::now();
+    g_deflate_times = svt_deflate_times();
+    uint64_t slots = 0;
+    SVT_TRY(deflate_check_args(bytes, off, n, out, out_off, slots));
+    SVT_TRY(select_device(device));
+    out_off[0] = 0;
+    if (n == 0) return SVT_OK;
+    DeflateCall c;
+    SVT_TRY(c.take());
+    const uint64_t payload_bytes = off[n] - off[0];
+    std::vector<crc::Job> jobs(n);
+    for (uint64_t k = 0; k < n; ++k) jobs[k] = crc::Job{off[k] - off[0], (uint32_t)(off[k + 1] - off[k]), 0};
+    SVT_TRY(c.d_bytes.alloc(payload_bytes));
+    if (payload_bytes) {
+        Stager st(c.s);
+        SVT_TRY(st.copy(c.d_bytes.p, bytes + off[0], payload_bytes));
+        SVT_TRY(st.finish());
+    }
+    SVT_TRY(deflate_resident(c, c.d_bytes.as<uint8_t>(), payload_bytes, jobs, slots, out, capacity, out_off, mode, device));
     g_deflate_times.total_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     return SVT_OK;
 }

@@ -36,6 +36,8 @@
 #include "svt_host_cpus.h"
 #include "svt_library_arena.h"
 #include "svt_record_rules.h"
+#include "svt_tbx_index.h"
+#include "svt_vcf_lines.h"
 
 namespace {
 using svt::fail;
@@ -57,3 +59,4 @@ using rr::ld32;
 #include "svt_reads_walk.h"            // the one-source walk on the host, its dump, their entry points
 #include "svt_reads_bgzf_entries.h"    // svt_bgzf_inflate_host, _crc32_host, _deflate_host
 #include "svt_reads_library.h"         // svt_bam_scan_library, svt::lw: the segmented library walk
+#include "svt_reads_vcf_entries.h"     // svt_vcf_lines_host, _gather_host, _sort_order, svt_tbx_build: VCF text as lines, the .tbi fold

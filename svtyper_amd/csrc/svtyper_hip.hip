@@ -69,6 +69,7 @@
 #include "svt_inflate_kernel.h"
 #include "svt_crc32_kernel.h"
 #include "svt_deflate_kernel.h"
+#include "svt_vcf_lines_kernel.h"
 #include "svt_bgzf.h"
 #include "svt_evidence_arena.h"
 #include "svt_library_kernel.h"
@@ -192,6 +193,7 @@ void svt_batch_destroy(svt_batch* b) { free_batch(b); }
 #include "svt_entry_debug.h"
 #include "svt_entry_inflate.h"
 #include "svt_entry_deflate.h"
+#include "svt_entry_vcf_lines.h"
 #include "svt_entry_evidence.h"
 #include "svt_entry_library.h"
 #include "svt_entry_oneshot.h"

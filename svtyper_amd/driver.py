@@ -351,13 +351,36 @@ def parse_arguments(p, bam_help, max_reads, own):
     # (tests/golden/help_*.txt).  --bgzf: the output VCF as BGZF (.vcf.gz: what bcftools, tabix and IGV read); --deflate: who
     # compresses BGZF output (--bgzf, -w) -- zlib, or the library's own compressor on the host or on the GPU (same inflated bytes);
     # --huffman: the block that compressor writes -- fixed, or dynamic where that is shorter (not with --deflate zlib).
+    # --sort: (with --bgzf) the body in stable order by (contig rank, POS); --tabix: (with --bgzf -o PATH) PATH.tbi beside the
+    # output (bgzf_out's docstring: both hold the whole output text until the end).
     p.add_argument("--bgzf", action="store_true", help=argparse.SUPPRESS)
     p.add_argument("--deflate", choices=("zlib", "host", "device"), default="zlib", help=argparse.SUPPRESS)
     p.add_argument("--huffman", choices=("fixed", "dynamic"), default="fixed", help=argparse.SUPPRESS)
+    p.add_argument("--sort", action="store_true", help=argparse.SUPPRESS)
+    p.add_argument("--tabix", action="store_true", help=argparse.SUPPRESS)
     args = p.parse_args()
+    if (args.sort or args.tabix) and not args.bgzf:
+        p.error("--sort and --tabix need --bgzf")
+    if args.tabix and args.output_vcf is sys.stdout:
+        p.error("--tabix needs an output file (-o): an index is written beside it")
+    args.input_vcf = gzip_text(args.input_vcf)
     if args.input_vcf is None and not sys.stdin.isatty():
         args.input_vcf = sys.stdin
     return args
+
+
+def gzip_text(vcf_in):
+    """`-i PATH` whose first two bytes are 1f 8b (a .vcf.gz, BGZF or plain gzip): the file read through gzip as text.  Anything
+    else, stdin included, as it is."""
+    path = getattr(vcf_in, "name", None)
+    if vcf_in is None or vcf_in is sys.stdin or not isinstance(path, str) or not os.path.isfile(path):
+        return vcf_in
+    with open(path, "rb") as f:
+        if f.read(2) != b"\x1f\x8b":
+            return vcf_in
+    import gzip
+    vcf_in.close()
+    return gzip.open(path, "rt")
 
 
 def run_main(driver, sharded_driver, call, args):
@@ -372,23 +395,24 @@ def run_main(driver, sharded_driver, call, args):
     if job is None:
         if not args.bgzf:
             return driver(*call, **options)
-        with _bgzf_text(call[2], args.deflate, 0, getattr(args, "huffman", "fixed")) as out:
+        with _bgzf_text(call[2], args.deflate, 0, getattr(args, "huffman", "fixed"), args) as out:
             return driver(*call[:2], out, *call[3:], **options)
     rank, world, local_rank = job
     call = call[:2] + (sharded.private_stdout(call[2]),) + call[3:]
     engine = sharded.init(local_rank)
     if args.bgzf and rank == 0:             # (rank 0 writes everything: the others touch nothing)
-        with _bgzf_text(call[2], args.deflate, getattr(engine, "device", local_rank), getattr(args, "huffman", "fixed")) as out:
+        with _bgzf_text(call[2], args.deflate, getattr(engine, "device", local_rank), getattr(args, "huffman", "fixed"), args) as out:
             sharded_driver(*call[:2], out, *call[3:], rank=rank, world=world, engine=engine, **options)
     else:
         sharded_driver(*call, rank=rank, world=world, engine=engine, **options)
     sharded.finish()
 
 
-def _bgzf_text(vcf_out, deflate, device, huffman="fixed"):
+def _bgzf_text(vcf_out, deflate, device, huffman="fixed", args=None):
     """`--bgzf`: the output VCF through bgzf_out.open_text (imported only here)"""
     from . import bgzf_out
-    return bgzf_out.open_text(vcf_out, deflate=deflate, device=device, huffman=huffman)
+    return bgzf_out.open_text(vcf_out, deflate=deflate, device=device, huffman=huffman, sort=bool(getattr(args, "sort", False)),
+                              index="tbi" if getattr(args, "tabix", False) else None)
 
 
 def run_cli(main):

@@ -135,6 +135,12 @@ class _DeflateTimes(C.Structure):
     _fields_ = [("crc_kernel_s", C.c_double), ("deflate_kernel_s", C.c_double), ("pack_kernel_s", C.c_double), ("total_s", C.c_double)]
 
 
+class _LinesTimes(C.Structure):
+    """include/svtyper_reads.h: svt_vcf_lines_times"""
+    _fields_ = [("count_kernel_s", C.c_double), ("starts_kernel_s", C.c_double), ("parse_kernel_s", C.c_double),
+                ("gather_kernel_s", C.c_double), ("total_s", C.c_double)]
+
+
 class _InflateStats(C.Structure):
     """include/svtyper_reads.h: svt_evidence_inflate_stats"""
     _fields_ = [("blocks_inflated", C.c_uint64), ("blocks_failed", C.c_uint64), ("compressed_bytes", C.c_uint64),
@@ -258,6 +264,17 @@ def _lib():
             L.svt_huffman_lengths_host.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
             L.svt_huffman_lengths_device.restype = C.c_int
             L.svt_huffman_lengths_device.argtypes = L.svt_huffman_lengths_host.argtypes + [C.c_int]
+        if hasattr(L, "svt_vcf_lines_host"):       # (likewise: VCF text as lines, the sorted and indexed BGZF output)
+            P, U64 = C.c_void_p, C.c_uint64
+            for name, argtypes in (("svt_vcf_lines_host", [P, U64, P, U64, P]), ("svt_vcf_lines_device", [P, U64, P, U64, P, C.c_int]),
+                                   ("svt_vcf_gather_host", [P, U64, P, U64, P, U64, P, U64]),
+                                   ("svt_vcf_gather_device", [P, U64, P, U64, P, U64, P, U64, C.c_int]),
+                                   ("svt_vcf_sort_order", [P, U64, P, U64, P, P]),
+                                   ("svt_vcf_bgzf_device", [P, U64, C.c_int, C.c_uint32, P, U64, P, P, U64, P, P, P, C.c_int]),
+                                   ("svt_vcf_lines_last_times", [C.POINTER(_LinesTimes)]),
+                                   ("svt_tbx_build", [P, U64, P, P, U64, P, U64, C.c_uint32, P, P, P]), ("svt_tbx_take", [P, U64])):
+                getattr(L, name).restype = C.c_int
+                getattr(L, name).argtypes = argtypes
         L.svt_bam_set_verify.restype = C.c_int
         L.svt_bam_set_verify.argtypes = [C.c_void_p, C.c_int]
         L.svt_bam_get_verify.restype = C.c_int
@@ -760,3 +777,117 @@ def bgzf_deflate_last_times() -> Dict[str, float]:
     t = _DeflateTimes()
     hip._check(L.svt_bgzf_deflate_last_times(C.byref(t)))
     return {name: float(getattr(t, name)) for name, _ in _DeflateTimes._fields_}
+
+
+# ---- VCF text as lines: the line table, the order --sort writes, the gather, the .tbi fold (include/svtyper_reads.h) ----------
+TBX_LINE = np.dtype([("off", np.uint64), ("len", np.uint64), ("beg", np.uint32), ("end", np.uint32), ("chrom_len", np.uint32),
+                     ("flags", np.uint32)])      # svt_tbx_line
+TBX_META, TBX_BAD, TBX_RANGE = 1, 2, 4
+TBX_NOT_DATA, TBX_BEYOND, TBX_CONTIG_AGAIN, TBX_POS_BACK = 1, 2, 3, 4
+
+
+def _lines_lib():
+    L = _lib()
+    if not hasattr(L, "svt_vcf_lines_host"):
+        raise hip.SvtyperHipError("this libsvtyper_hip.so has no svt_vcf_lines_host (built before sorted, indexed BGZF output)")
+    return L
+
+
+def _text_array(text: bytes) -> np.ndarray:
+    return np.frombuffer(text, np.uint8) if len(text) else np.zeros(1, np.uint8)
+
+
+def vcf_lines(text: bytes, device: Optional[int] = None) -> np.ndarray:
+    """svt_vcf_lines_host (device None) / _device: the line table of `text`, one TBX_LINE record per line in text order"""
+    L = _lines_lib()
+    buf = _text_array(text)
+    capacity = text.count(b"\n") + 1
+    lines = np.zeros(capacity, TBX_LINE)
+    n = C.c_uint64(0)
+    args = [buf.ctypes.data, len(text), lines.ctypes.data, capacity, C.addressof(n)]
+    if device is None:
+        hip._check(L.svt_vcf_lines_host(*args))
+    else:
+        hip._check(L.svt_vcf_lines_device(*args, int(device)))
+    return lines[:n.value]
+
+
+def vcf_gather(text: bytes, lines: np.ndarray, perm, device: Optional[int] = None) -> bytes:
+    """svt_vcf_gather_host (device None) / _device: the lines lines[perm[0]], lines[perm[1]], ... of `text` side by side"""
+    L = _lines_lib()
+    buf = _text_array(text)
+    lines = np.ascontiguousarray(lines, TBX_LINE)
+    perm = np.ascontiguousarray(perm, np.uint64)
+    if perm.size and int(perm.max()) >= lines.shape[0]:
+        raise ValueError("an entry of perm is no line")
+    out_len = int(lines["len"][perm].sum()) if perm.size else 0
+    out = np.zeros(max(out_len, 1), np.uint8)
+    args = [buf.ctypes.data, len(text), lines.ctypes.data if lines.size else None, lines.shape[0], perm.ctypes.data if perm.size else None,
+            perm.shape[0], out.ctypes.data, out_len]
+    if device is None:
+        hip._check(L.svt_vcf_gather_host(*args))
+    else:
+        hip._check(L.svt_vcf_gather_device(*args, int(device)))
+    return out[:out_len].tobytes()
+
+
+def vcf_sort_order(text: bytes, lines: np.ndarray) -> Tuple[np.ndarray, int]:
+    """svt_vcf_sort_order: (perm, 0), or (None, the 1-based number of a body line that is no data line)"""
+    L = _lines_lib()
+    buf = _text_array(text)
+    lines = np.ascontiguousarray(lines, TBX_LINE)
+    perm = np.zeros(max(lines.shape[0], 1), np.uint64)
+    bad = C.c_uint64(0)
+    hip._check(L.svt_vcf_sort_order(buf.ctypes.data, len(text), lines.ctypes.data if lines.size else None, lines.shape[0], perm.ctypes.data,
+                                    C.addressof(bad)))
+    return (None, int(bad.value)) if bad.value else (perm[:lines.shape[0]], 0)
+
+
+def vcf_bgzf_device(text: bytes, sort: bool, huffman: str = "fixed", device: int = 0):
+    """svt_vcf_bgzf_device: `text` up once; (members uint8, out_off uint64 [n + 1], lines as written, src_off uint64, 0), or
+    (None, None, None, None, bad_line) where sorting met a body line that is no data line"""
+    L = _lines_lib()
+    buf = _text_array(text)
+    n = (len(text) + DEFLATE_MAX_PAYLOAD - 1) // DEFLATE_MAX_PAYLOAD
+    capacity = len(text) + DEFLATE_SLOT_EXTRA * n
+    out = np.zeros(max(capacity, 1), np.uint8)
+    out_off = np.zeros(n + 1, np.uint64)
+    line_capacity = text.count(b"\n") + 1
+    lines = np.zeros(line_capacity, TBX_LINE)
+    src_off = np.zeros(line_capacity, np.uint64)
+    n_lines, bad = C.c_uint64(0), C.c_uint64(0)
+    hip._check(L.svt_vcf_bgzf_device(buf.ctypes.data, len(text), int(bool(sort)), int(check_huffman(huffman) == "dynamic"), out.ctypes.data, capacity,
+                                     out_off.ctypes.data, lines.ctypes.data, line_capacity, C.addressof(n_lines), src_off.ctypes.data,
+                                     C.addressof(bad), int(device)))
+    if bad.value:
+        return None, None, None, None, int(bad.value)
+    return out[:int(out_off[-1])], out_off, lines[:n_lines.value], src_off[:n_lines.value], 0
+
+
+def vcf_lines_last_times() -> Dict[str, float]:
+    """svt_vcf_lines_last_times: the line-table and gather kernels of this thread's last device call, from HIP events"""
+    t = _LinesTimes()
+    hip._check(_lines_lib().svt_vcf_lines_last_times(C.byref(t)))
+    return {name: float(getattr(t, name)) for name, _ in _LinesTimes._fields_}
+
+
+def tbx_build(text: bytes, lines: np.ndarray, member_off, src_off=None, payload: int = DEFLATE_MAX_PAYLOAD):
+    """svt_tbx_build + svt_tbx_take: (the uncompressed bytes of the .tbi, 0, 0), or (None, bad_line, bad_kind)"""
+    L = _lines_lib()
+    buf = _text_array(text)
+    lines = np.ascontiguousarray(lines, TBX_LINE)
+    member_off = np.ascontiguousarray(member_off, np.uint64)
+    if member_off.shape[0] < 1:
+        raise ValueError("member_off must hold n + 1 entries")
+    src = None if src_off is None else np.ascontiguousarray(src_off, np.uint64)
+    if src is not None and src.shape[0] != lines.shape[0]:
+        raise ValueError("src_off must hold an entry per line")
+    size, bad, kind = C.c_uint64(0), C.c_uint64(0), C.c_uint32(0)
+    hip._check(L.svt_tbx_build(buf.ctypes.data, len(text), src.ctypes.data if src is not None and src.size else None,
+                               lines.ctypes.data if lines.size else None, lines.shape[0], member_off.ctypes.data, member_off.shape[0] - 1,
+                               int(payload), C.addressof(size), C.addressof(bad), C.addressof(kind)))
+    if bad.value:
+        return None, int(bad.value), int(kind.value)
+    out = np.zeros(max(size.value, 1), np.uint8)
+    hip._check(L.svt_tbx_take(out.ctypes.data, size.value))
+    return out[:size.value].tobytes(), 0, 0
