@@ -335,6 +335,89 @@ int svt_tbx_build(const uint8_t* text, uint64_t len, const uint64_t* src_off, co
                   uint32_t* bad_kind);
 int svt_tbx_take(uint8_t* out, uint64_t capacity);
 
+/* ---- BAM records as spans: the coordinate-sorted, BAI-indexed `-w` dump (additions; the ABI number stays: probe for
+ * svt_bam_spans_host) ----
+ * svtyper_amd/csrc/svt_bam_sort_rules.h holds the per-record rule as one piece of source for the host and the device
+ * (svt_bam_sort_kernel.h).  The records lie side by side in bytes[0, len), block_size first; record i is
+ * bytes[rec_off[i] .. rec_off[i + 1]) -- rec_off holds n + 1 non-decreasing offsets, rec_off[n] <= len, and what lies in
+ * front of rec_off[0] (the BAM header, for the writer) is nobody's record.  One span per record, in that order:
+ *   off, len     where the record lies and how long it is (its block_size field included)
+ *   key          tid' << 33 | (pos + 1) << 1 | reverse: tid' = tid, n_ref for tid = -1 (no coordinate: those go last);
+ *                reverse is flag bit 0x10.  The order --sort-alignment writes is the stable order by key.
+ *   tid, beg     refID and pos (0 for a record without coordinate)
+ *   end          pos + the reference bases its CIGAR consumes (M, D, N, =, X); pos + 1 for an unmapped record (0x4), one
+ *                without CIGAR or with a sum of 0; saturated at 2^32 - 1
+ *   flags        SVT_BAM_UNMAPPED: flag 0x4.  SVT_BAM_NO_COOR: tid = -1.  SVT_BAM_BEYOND: end > 2^29, beyond what a BAI
+ *                addresses (a CSI index is not written).  SVT_BAM_BAD, with why: SVT_BAM_BAD_RECORD (the span is not
+ *                36 bytes, block_size is not the span's length less 4, or the fixed part, name and CIGAR do not fit
+ *                inside block_size), SVT_BAM_BAD_TID (tid >= n_ref or < -1), SVT_BAM_BAD_POS (pos < 0 with a tid,
+ *                pos < -1 without); key, beg and end of such a span are 0.                                            */
+typedef struct svt_bam_span {
+    uint64_t off, len, key;
+    int32_t tid;
+    uint32_t beg, end, flags;
+} svt_bam_span;
+#define SVT_BAM_UNMAPPED 1u
+#define SVT_BAM_NO_COOR 2u
+#define SVT_BAM_BAD 4u
+#define SVT_BAM_BEYOND 8u
+#define SVT_BAM_BAD_RECORD 0x100u
+#define SVT_BAM_BAD_TID 0x200u
+#define SVT_BAM_BAD_POS 0x400u
+/* what a record cannot be for svt_bam_sort_order / svt_bai_build (bad_kind) */
+#define SVT_BAM_KIND_RECORD 1u   /* SVT_BAM_BAD_RECORD                                                                 */
+#define SVT_BAM_KIND_TID 2u      /* SVT_BAM_BAD_TID                                                                    */
+#define SVT_BAM_KIND_POS 3u      /* SVT_BAM_BAD_POS                                                                    */
+#define SVT_BAM_KIND_BEYOND 4u   /* SVT_BAM_BEYOND (the index only)                                                    */
+#define SVT_BAM_KIND_KEY_BACK 5u /* a key below the key of the record in front (the index only)                        */
+/* The span table spans[0, n).  *key_and / *key_or (may be null): the AND and the OR of all keys (~0 and 0 for n = 0) --
+ * a digit of the key in which they agree is one the sort can skip.                                                  */
+int svt_bam_spans_host(const uint8_t* bytes, uint64_t len, const uint64_t* rec_off, uint64_t n, int32_t n_ref,
+                       svt_bam_span* spans, uint64_t* key_and, uint64_t* key_or);
+int svt_bam_spans_device(const uint8_t* bytes, uint64_t len, const uint64_t* rec_off, uint64_t n, int32_t n_ref,
+                         svt_bam_span* spans, uint64_t* key_and, uint64_t* key_or, int device);
+/* The stable order by key: perm[j] is the span that comes j-th (n entries, n < 2^32).  The host sorts with
+ * std::stable_sort; the device with an LSD radix sort of (key, index) over the 8-bit digits in which the keys differ
+ * (svt_bam_sort_kernel.h: a per-tile histogram, an exclusive scan and a stable scatter per digit; where an element goes is
+ * a rank, so the permutation is a function of the keys alone).  A span with SVT_BAM_BAD: *bad_record is its 1-based number,
+ * *bad_kind why (SVT_OK, perm undefined); 0 otherwise.                                                                 */
+int svt_bam_sort_order_host(const svt_bam_span* spans, uint64_t n, uint64_t* perm, uint64_t* bad_record, uint32_t* bad_kind);
+int svt_bam_sort_order_device(const svt_bam_span* spans, uint64_t n, uint64_t* perm, uint64_t* bad_record, uint32_t* bad_kind,
+                              int device);
+/* One call for the writer with deflate="device": bytes[0, len) -- the BAM header in front of rec_off[0], the records behind
+ * it up to rec_off[n] = len -- goes up once; the span table and the keys are made there; with sort != 0 the keys are sorted
+ * there and the records gathered behind the header into a second buffer; the stream as written is cut into members where
+ * bam.BgzfWriter cuts it (the header in members of its own, whole records packed into at most 65 280 bytes, a longer
+ * record cut at 65 280) and compressed by the kernels of svt_bgzf_deflate_device_mode (the same members, byte for byte).
+ * out / capacity / out_off (member_capacity + 1 entries) as there; *n_members members were written, member k holds the
+ * written stream's bytes [member_start[k], member_start[k + 1]) (member_capacity + 1 entries; n + len / 65280 + 2 members
+ * always suffice).  spans[0, n): the table in WRITTEN order, off pointing into the written stream; perm[j]: which record
+ * of the caller's was written j-th.  *bad_record / *bad_kind as svt_bam_sort_order (sort != 0: nothing is compressed).  */
+int svt_bam_sorted_bgzf_device(const uint8_t* bytes, uint64_t len, const uint64_t* rec_off, uint64_t n, int32_t n_ref, int sort,
+                               uint32_t mode, uint8_t* out, uint64_t capacity, uint64_t* out_off, uint64_t member_capacity,
+                               uint64_t* n_members, uint64_t* member_start, svt_bam_span* spans, uint64_t* perm,
+                               uint64_t* bad_record, uint32_t* bad_kind, int device);
+/* the calling thread's most recent svt_bam_spans_device / _sort_order_device / _sorted_bgzf_device: its kernels by HIP
+ * events, the three of the sort summed over its passes                                                               */
+typedef struct svt_bam_sort_times {
+    double keys_kernel_s, histogram_kernel_s, scan_kernel_s, scatter_kernel_s, gather_kernel_s;
+    double total_s;             /* the whole call on the host's clock                                                */
+    uint32_t passes;            /* digits the sort took                                                              */
+    uint32_t reserved;
+} svt_bam_sort_times;
+int svt_bam_sort_last_times(svt_bam_sort_times* times);
+/* The index fold: the bytes of a .bai ("BAI\1", n_ref; per reference its bins with their chunks -- a run of consecutive
+ * records with one bin is one chunk --, pseudo-bin 37450 with (first start, last end) and (mapped, unmapped), and the
+ * 16 kb linear index; n_bin = 0 and n_intv = 0 for a reference without records; the 64-bit n_no_coor at the end) for
+ * `spans`, the table of a stream as written (spans[i].off rising, the records side by side).  Member k of the BGZF
+ * file holds the stream's bytes [member_start[k], member_start[k + 1]) and begins at file offset member_off[k];
+ * member_off[n_members] is where the members end.  A record with SVT_BAM_UNMAPPED and a tid is placed at its position
+ * and counted as unmapped.  The result is kept for the calling thread: *size is its length, svt_bai_take copies it out.
+ * A record the index cannot hold: *bad_record is its 1-based number, *bad_kind why (SVT_OK, no result); 0 otherwise.  */
+int svt_bai_build(const svt_bam_span* spans, uint64_t n, int32_t n_ref, const uint64_t* member_start, const uint64_t* member_off,
+                  uint64_t n_members, uint64_t* size, uint64_t* bad_record, uint32_t* bad_kind);
+int svt_bai_take(uint8_t* out, uint64_t capacity);
+
 /* Verify: a property of the handle, off by default (0).  With it on, every call that takes the handle checks the
  * CRC-32 of every BGZF member it inflates, where it inflates it: the host reader's threads (libdeflate's or zlib's
  * crc32), or svt_crc32_kernel behind svt_inflate_kernel for the routes that inflate on the GPU (the expected values

@@ -457,6 +457,60 @@ def _pseudo_bin(depth: int) -> int:
     return ((1 << (3 * (depth + 1))) - 1) // 7 + 1
 
 
+class BamOrderError(ValueError):
+    """the records cannot be sorted or indexed as they are: `record` is the 1-based number of the record in the way, among
+    those handed to write() / write_raw()"""
+
+    def __init__(self, message: str, record: int):
+        super().__init__(message)
+        self.record = record
+
+
+def coordinate_header(header: bytes) -> bytes:
+    """the BAM header `header` (magic, l_text, text, n_ref, references) saying SO:coordinate: the SO value of its @HD line
+    replaced, SO:coordinate appended to an @HD line without one, `@HD VN:1.6 SO:coordinate` put in front of a text without
+    an @HD line; l_text adjusted, everything else byte for byte.  A header that says so already is returned as it is."""
+    l_text = struct.unpack_from("<i", header, 4)[0]
+    text, rest = header[8:8 + l_text], header[8 + l_text:]
+    if text.startswith(b"@HD\t") or text.startswith(b"@HD\n") or text.rstrip(b"\0") == b"@HD":
+        end = len(text.rstrip(b"\0"))
+        nl = text.find(b"\n", 0, end)
+        stop = end if nl < 0 else nl
+        fields = text[:stop].split(b"\t")
+        if b"SO:coordinate" in fields[1:]:
+            return header
+        if any(f.startswith(b"SO:") for f in fields[1:]):
+            fields = fields[:1] + [b"SO:coordinate" if f.startswith(b"SO:") else f for f in fields[1:]]
+        else:
+            fields.append(b"SO:coordinate")
+        text = b"\t".join(fields) + text[stop:]
+    else:
+        text = b"@HD\tVN:1.6\tSO:coordinate\n" + text
+    return header[:4] + struct.pack("<i", len(text)) + text + rest
+
+
+class _RecordHold:
+    """stands where an AlignmentFile's BgzfWriter stands while sort= / index= hold the records: write_record puts the record
+    behind the header in ONE growing buffer (the stream close() works on: no second copy is made of it) and notes where it
+    ends; close() hands buffer and offsets to `finish`, once"""
+
+    def __init__(self, header: bytes, finish):
+        self.data = bytearray(header)
+        self.offsets = [len(header)]        # record i is data[offsets[i] : offsets[i + 1]]
+        self._finish = finish
+
+    def write_record(self, data: bytes) -> None:
+        self.data += data
+        self.offsets.append(len(self.data))
+
+    def close(self) -> None:
+        finish, self._finish = self._finish, None
+        if finish is not None:
+            data, offsets = self.data, self.offsets
+            self.data, self.offsets = bytearray(), [0]
+            finish(data, offsets)
+
+
 class AlignmentFile:
     """BAM file opened for reading, with its .bai or .csi index when present."""
 
@@ -469,7 +523,8 @@ class AlignmentFile:
             if mode != "wb":
                 raise NotImplementedError("only BAM output (mode 'wb') is written")
             self._open_for_writing(path, kwargs.get("template", template), kwargs.get("deflate", "zlib"), kwargs.get("device", 0),
-                                   kwargs.get("huffman", "fixed"))
+                                   kwargs.get("huffman", "fixed"), kwargs.get("sort", False), kwargs.get("index", None),
+                                   kwargs.get("index_path", None))
             return
         self._bgzf = BgzfReader(path, verify=bool(kwargs.get("verify", False)))
         raw = []        # the header as it lies in the file: a file opened 'wb' with this one as template starts with these bytes
@@ -670,18 +725,114 @@ class AlignmentFile:
         self._bgzf.close()
 
     # ---- writing (mode 'wb')
-    def _open_for_writing(self, path: str, template, deflate: str = "zlib", device: int = 0, huffman: str = "fixed"):
+    _held = None            # (sort= / index=) the _RecordHold that stands where the BgzfWriter stands until close()
+
+    def _open_for_writing(self, path: str, template, deflate: str = "zlib", device: int = 0, huffman: str = "fixed", sort: bool = False,
+                          index=None, index_path=None):
         """pysam.AlignmentFile(path, 'wb', template): the template's header text and reference list, byte for byte.  `deflate`,
-        `device`, `huffman`: who compresses the members, and into which block (BgzfWriter)."""
+        `device`, `huffman`: who compresses the members, and into which block (BgzfWriter).
+
+        `sort=True` (`--sort-alignment`) and `index="bai"` (`--bai`).  With either, nothing is written before close(): the writer
+        keeps the header and every record, which costs host memory equal to the inflated size of the file, and close() works
+        on them as one piece -- their span table (svtyper_amd/csrc/svt_bam_sort_rules.h: key = tid' << 33 | (pos + 1) << 1 |
+        reverse, tid' = n_ref for a record without coordinate; the record's extent on the reference), with `sort` the records in
+        stable order by key and SO:coordinate in the header's @HD line, the members cut exactly where they are cut for records
+        written in that order, and with `index` the .bai at `index_path` (default: path + ".bai").  With deflate="device" the
+        header and the records go to the GPU once and the table, the sort, the gather and the members are made there
+        (svt_bam_sorted_bgzf_device); otherwise on the host, by the same source.  The index fold is host code either way
+        (svt_bai_build).  A record that cannot be sorted or indexed makes close() raise BamOrderError; with `index` and
+        without `sort`, records that are not in key order do so once the BAM is complete, and no index is left behind.
+        Without either option the writer streams as it always did."""
         header = getattr(template, "_header_bytes", None)
         if header is None:
             raise TypeError("mode 'wb' needs template=: an AlignmentFile of this module opened for reading")
+        if index not in (None, "bai"):
+            raise ValueError("index must be None or 'bai', not %r" % (index,))
         self.text, self.header = template.text, template.header
         self.references, self.lengths = template.references, template.lengths
         self._tid = dict(template._tid)
         self._writer = BgzfWriter(path, deflate=deflate, device=device, huffman=huffman)
+        if sort or index is not None:
+            from .bgzf_out import _MemberLog
+            self._sort, self._index = bool(sort), index
+            self._index_path = (os.fspath(path) + ".bai" if index_path is None else index_path) if index is not None else None
+            self._header_out = coordinate_header(header) if sort else header
+            self._bgzf_out = self._writer
+            self._log = self._bgzf_out._f = _MemberLog(self._bgzf_out._f)
+            self._held = self._writer = _RecordHold(self._header_out, self._close_held)
+            return
         self._writer.write(header)
         self._writer.flush()            # (records start in a block of their own, as htslib leaves them)
+
+    def _close_held(self, data: bytearray, offsets: List[int]) -> None:
+        """the header and the held records as one piece: span table, order, members, index.  `data`: the header and the
+        records behind it; record i is data[offsets[i] : offsets[i + 1]]"""
+        import numpy as np
+
+        from . import native_reads as nr
+        w, header_len = self._bgzf_out, offsets[0]
+        if self._index_path is not None and os.path.exists(self._index_path):
+            os.remove(self._index_path)                 # (an index of an earlier file is not left beside this one)
+        n_ref = struct.unpack_from("<i", data, 8 + struct.unpack_from("<i", data, 4)[0])[0]
+        rec_off = np.array(offsets, np.uint64)
+        n = len(offsets) - 1
+        view = memoryview(data)
+        try:
+            if w._deflate == "device":
+                members, _off, _start, spans, perm, bad, kind = nr.bam_sorted_bgzf_device(data, rec_off, n_ref, self._sort, w._huffman,
+                                                                                         w._device)
+                if bad:
+                    raise self._order_error(data, offsets, bad, kind)
+                w._f.write(memoryview(members))         # (the members as they came back: not copied again)
+                del members
+            else:
+                spans, _and, _or = nr.bam_spans(data, rec_off, n_ref)
+                if self._sort:
+                    perm, bad, kind = nr.bam_sort_order(spans)
+                    if bad:
+                        raise self._order_error(data, offsets, bad, kind)
+                    spans = spans[perm]
+                    spans["off"] = np.cumsum(spans["len"]) - spans["len"] + np.uint64(header_len)
+                else:
+                    perm = np.arange(n, dtype=np.uint64)
+                w.write(bytes(view[:header_len]))
+                w.flush()
+                for i in perm.tolist():
+                    w.write_record(bytes(view[offsets[i]:offsets[i + 1]]))     # (a record at a time: the stream is not doubled)
+                w.flush()
+                w.drain()
+        finally:
+            w.close()
+        if self._index is None:
+            return
+        bai, bad, kind = nr.bai_build(spans, n_ref, np.array(self._log.starts, np.uint64), np.array(self._log.offsets, np.uint64))
+        if bad:
+            raise self._order_error(data, offsets, int(perm[bad - 1]) + 1, kind)
+        with open(self._index_path, "wb") as f:
+            f.write(bai)
+
+    def _order_error(self, data, offsets, bad: int, kind: int) -> "BamOrderError":
+        """`bad`: the 1-based number of the record among those handed to write() / write_raw()"""
+        from . import native_reads as nr
+        raw = bytes(data[offsets[bad - 1]:offsets[bad]])
+        where = "record %d" % bad
+        if len(raw) >= 36:
+            tid, pos = struct.unpack_from("<ii", raw, 4)
+            name = raw[36:36 + max(raw[12] - 1, 0)].decode("ascii", "replace")
+            where = "record %d (%s, %d:%d)" % (bad, name, tid, pos)
+        if kind == nr.BAM_KIND_TID:
+            why = "its reference id is none of the header's %d" % len(self.references)
+        elif kind == nr.BAM_KIND_POS:
+            why = "its position is negative"
+        elif kind == nr.BAM_KIND_RECORD:
+            why = "its fixed part, name and CIGAR do not fit inside its block_size"
+        elif kind == nr.BAM_KIND_BEYOND:
+            return BamOrderError("%s: %s ends beyond 2^29, which a .bai index cannot address (a CSI index is not written)"
+                                 % (self.filename, where), bad)
+        else:
+            return BamOrderError("%s: %s is out of order (its key lies below the record in front): a .bai index needs a "
+                                 "coordinate-sorted BAM; no index was written -- use --sort-alignment (sort=True)" % (self.filename, where), bad)
+        return BamOrderError("%s: %s cannot be sorted or indexed (%s)" % (self.filename, where, why), bad)
 
     def write(self, read: AlignedSegment) -> None:
         """One record behind the others: the record as it was read, without its sequence and qualities (l_seq = 0; `bin` stays

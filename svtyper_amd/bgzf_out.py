@@ -41,12 +41,14 @@ class _MemberLog:
     def __init__(self, f):
         self._f = f
         self.offsets = [0]
+        self.starts = [0]       # where each member's payload begins in the inflated stream (its ISIZE says how long it is)
 
     def write(self, data) -> int:
         at, n, base = 0, len(data), self.offsets[-1]
         while at < n and data[at:at + 28] != BGZF_EOF:
             at += struct.unpack_from("<H", data, at + 16)[0] + 1
             self.offsets.append(base + at)
+            self.starts.append(self.starts[-1] + struct.unpack_from("<I", data, at - 4)[0])
         return self._f.write(data)
 
     def flush(self):

@@ -185,20 +185,26 @@ class Classic(Driver):
 
 def sv_genotype(bam_string, vcf_in, vcf_out, min_aligned, split_weight, disc_weight, num_samp, lib_info_path,
                 debug, alignment_outpath, ref_fasta, sum_quals, max_reads, max_ci_dist, *, engine=None, geometry="host",
-                reader=None, stats=None, inflate="host", library_scan="host", verify="off", deflate="zlib", huffman="fixed"):
+                reader=None, stats=None, inflate="host", library_scan="host", verify="off", deflate="zlib", huffman="fixed",
+                alignment_sort=False, alignment_index=None):
     """`alignment_outpath` (-w): the reads that entered the tallies go to a BAM, tagged XV:A:R / XV:A:A as the reference tags them
     (driver.tag_and_write; the tags that depend on p_concordant come from the device, svt_batch_verdicts).  Legal with
     reader="python" (what reader=None then means) or reader="device" (the reads are cut and tagged on the GPU: the evidence dump of
     svt_bam_evidence_device_dump; the default engine, or one with supports_dump) and geometry="host"; ValueError otherwise, and for
     an engine without supports_verdicts.  `deflate`: who compresses that BAM's members -- "zlib", or the library's own compressor on
     the "host" or on the "device" (bam.BgzfWriter; the same inflated bytes and member boundaries); ValueError for anything else.  `huffman`: "fixed", or "dynamic" for
-    dynamic-Huffman blocks from that compressor (ValueError with deflate="zlib")."""
+    dynamic-Huffman blocks from that compressor (ValueError with deflate="zlib").  `alignment_sort` (--sort-alignment): that BAM in
+    stable coordinate order, its header saying SO:coordinate; `alignment_index="bai"` (--bai): its index beside it, at
+    alignment_outpath + ".bai" (bam.AlignmentFile's sort= / index=: both hold every record until the end; BamOrderError for records
+    that cannot be sorted or indexed).  ValueError for either without `alignment_outpath`."""
     check_huffman(huffman, check_deflate(deflate))
     run = Classic(bam_string, vcf_in, vcf_out, min_aligned, split_weight, disc_weight, num_samp, lib_info_path, debug, ref_fasta,
                   sum_quals, max_reads, max_ci_dist)
     run.alignment_outpath = alignment_outpath
     run.deflate = deflate
     run.huffman = huffman
+    run.alignment_sort = bool(alignment_sort)
+    run.alignment_index = alignment_index
     return run.run(CHUNK_UNITS, engine=engine, geometry=geometry, reader=reader, stats=stats, inflate=inflate,
                    library_scan=library_scan, verify=verify)
 
@@ -222,7 +228,14 @@ def get_args():
         p.add_argument("-w", "--write_alignment", metavar="FILE", dest="alignment_outpath", type=str, default=None,
                        help="write relevant reads to BAM file")
         p.add_argument("--verbose", action="store_true", default=False, help="Report status updates")
-    return parse_arguments(p, "BAM or CRAM file(s), comma-separated if genotyping multiple samples", None, own)
+        # the `-w` BAM in coordinate order / with its .bai beside it (README; bam.AlignmentFile: sort=, index="bai").  Not listed by
+        # --help, like --sort and --tabix: the help text is pinned byte for byte.
+        p.add_argument("--sort-alignment", dest="alignment_sort", action="store_true", help=argparse.SUPPRESS)
+        p.add_argument("--bai", dest="alignment_bai", action="store_true", help=argparse.SUPPRESS)
+    args = parse_arguments(p, "BAM or CRAM file(s), comma-separated if genotyping multiple samples", None, own)
+    if (args.alignment_sort or args.alignment_bai) and args.alignment_outpath is None:
+        p.error("--sort-alignment and --bai need -w/--write_alignment")
+    return args
 
 
 def main():
@@ -237,7 +250,8 @@ def main():
             args.num_samp, args.lib_info_path, args.debug, args.alignment_outpath, args.ref_fasta,
             args.sum_quals, args.max_reads, args.max_ci_dist)
     own = dict(deflate=args.deflate, huffman=args.huffman)      # (of this program alone: the `-w` BAM)
-    return run_main(functools.partial(sv_genotype, **own), functools.partial(sharded.sv_genotype_sharded, **own), call, args)
+    order = dict(alignment_sort=args.alignment_sort, alignment_index="bai" if args.alignment_bai else None)
+    return run_main(functools.partial(sv_genotype, **own, **order), functools.partial(sharded.sv_genotype_sharded, **own), call, args)
 
 
 def cli():

@@ -1,0 +1,316 @@
+// svt_entry_bam_sort.h -- part of the single translation unit svtyper_hip.hip (included there, in order, behind
+// svt_entry_vcf_lines.h; not a stand-alone header): BAM records as spans on the device.  The stream and its table of record offsets
+// go up, svt_bam_keys_kernel writes the span table, the keys and their AND / OR per workgroup; the host combines those and names
+// the digits in which the keys differ; per digit svt_bam_histogram_kernel, svt_bam_scan_kernel and svt_bam_scatter_kernel; the
+// order comes down, the lengths in that order are prefix-summed and cut into members on the host, svt_vcf_gather_kernel writes
+// the records in that order behind the header, and the deflate kernels run over the member jobs.  C ABI: svt_bam_spans_device,
+// svt_bam_sort_order_device, svt_bam_sorted_bgzf_device, svt_bam_sort_last_times (include/svtyper_reads.h).
+
+extern "C++" {
+
+// the kernels of the calling thread's last call here, from HIP events, and the call's wall time
+static thread_local svt_bam_sort_times g_bam_sort_times;
+
+struct BamSortCall : DeflateCall {                           // (destruction order: CallStream, svt_batch_state.h)
+    DevScratch d_stream, d_rec_off, d_spans, d_keys[2], d_idx[2], d_and, d_or, d_hist, d_perm, d_dst_off, d_sorted;
+    std::vector<hipEvent_t> marks;
+    ~BamSortCall()
+    {
+        drain();
+        for (hipEvent_t e : marks) (void)hipEventDestroy(e);
+    }
+    int begin(const uint8_t* bytes, uint64_t len)
+    {
+        SVT_TRY(take());
+        SVT_TRY(d_stream.alloc(len));
+        if (len) SVT_TRY(h2d_staged(d_stream.p, bytes, len, s));
+        return SVT_OK;
+    }
+    // an event recorded on the call's stream here; marks[*at] is it
+    int mark(size_t* at)
+    {
+        hipEvent_t e = nullptr;
+        HIP_TRY(hipEventCreate(&e));
+        marks.push_back(e);
+        *at = marks.size() - 1;
+        HIP_TRY(hipEventRecord(e, s));
+        return SVT_OK;
+    }
+    int between(size_t a, size_t b, double* seconds)
+    {
+        float ms = 0;
+        HIP_TRY(hipEventElapsedTime(&ms, marks[a], marks[b]));
+        *seconds += ms * 1e-3;
+        return SVT_OK;
+    }
+};
+
+// c.d_stream[0, len) and the caller's rec_off -> the span table in c.d_spans and in `table`, keys and indices in c.d_keys[0] /
+// c.d_idx[0], the AND and the OR of the keys
+static int keys_resident(BamSortCall& c, uint64_t len, const uint64_t* rec_off, uint64_t n, int32_t n_ref, std::vector<svt_bam_span>& table,
+                         uint64_t& key_and, uint64_t& key_or, int device)
+{
+    table.clear();
+    key_and = ~0ull;
+    key_or = 0;
+    if (n == 0) return SVT_OK;
+    const unsigned grid = lines_grid((n + kSortBlock - 1) / kSortBlock, device);
+    SVT_TRY(c.d_rec_off.alloc((n + 1) * sizeof(uint64_t)));
+    SVT_TRY(h2d_staged(c.d_rec_off.p, rec_off, (n + 1) * sizeof(uint64_t), c.s));
+    SVT_TRY(c.d_spans.alloc(n * sizeof(svt_bam_span)));
+    SVT_TRY(c.d_keys[0].alloc(n * sizeof(uint64_t)));
+    SVT_TRY(c.d_idx[0].alloc(n * sizeof(uint32_t)));
+    SVT_TRY(c.d_and.alloc(grid * sizeof(uint64_t)));
+    SVT_TRY(c.d_or.alloc(grid * sizeof(uint64_t)));
+    size_t e0 = 0, e1 = 0;
+    SVT_TRY(c.mark(&e0));
+    hipLaunchKernelGGL(svt_bam_keys_kernel, dim3(grid), dim3(kSortBlock), 0, c.s, c.d_stream.as<uint8_t>(), len, c.d_rec_off.as<uint64_t>(), n, n_ref,
+                       c.d_spans.as<svt_bam_span>(), c.d_keys[0].as<uint64_t>(), c.d_idx[0].as<uint32_t>(), c.d_and.as<uint64_t>(), c.d_or.as<uint64_t>());
+    HIP_TRY(hipGetLastError());
+    SVT_TRY(c.mark(&e1));
+    table.resize(n);
+    std::vector<uint64_t> ands(grid), ors(grid);
+    SVT_TRY(d2h_staged(table.data(), c.d_spans.p, n * sizeof(svt_bam_span), c.s));
+    SVT_TRY(d2h_staged(ands.data(), c.d_and.p, grid * sizeof(uint64_t), c.s));
+    SVT_TRY(d2h_staged(ors.data(), c.d_or.p, grid * sizeof(uint64_t), c.s));
+    HIP_TRY(hipStreamSynchronize(c.s));
+    for (unsigned g = 0; g < grid; ++g) {
+        key_and &= ands[g];
+        key_or |= ors[g];
+    }
+    SVT_TRY(c.between(e0, e1, &g_bam_sort_times.keys_kernel_s));
+    // the kernel's table is the caller's offsets or it is not theirs: what the gather relies on
+    for (uint64_t i = 0; i < n; ++i)
+        if (table[i].off != rec_off[i] || (table[i].len && (table[i].off > len || table[i].len > len - table[i].off)))
+            return fail(SVT_ERR_HIP, "svt_bam_keys_kernel: the spans are not the offset table's");
+    return SVT_OK;
+}
+
+// n (key, index) pairs in c.d_keys[0] / c.d_idx[0] -> order[j]: the index that comes j-th in stable order by key
+static int sort_resident(BamSortCall& c, uint64_t n, uint64_t key_and, uint64_t key_or, std::vector<uint32_t>& order, int device)
+{
+    order.resize(n);
+    const uint64_t differ = n ? key_and ^ key_or : 0;
+    uint32_t shifts[8], passes = 0;
+    for (uint32_t d = 0; d < 8; ++d)
+        if (differ >> (8 * d) & 255) shifts[passes++] = 8 * d;
+    g_bam_sort_times.passes = passes;
+    if (passes == 0) {                              // every key is the same one: the order of arrival
+        for (uint64_t i = 0; i < n; ++i) order[i] = (uint32_t)i;
+        return SVT_OK;
+    }
+    const uint32_t n_tiles = (uint32_t)((n + kSortTile - 1) / kSortTile);
+    const unsigned grid = lines_grid(n_tiles, device);
+    SVT_TRY(c.d_keys[1].alloc(n * sizeof(uint64_t)));
+    SVT_TRY(c.d_idx[1].alloc(n * sizeof(uint32_t)));
+    SVT_TRY(c.d_hist.alloc((uint64_t)n_tiles * 256 * sizeof(uint32_t)));
+    int src = 0;
+    std::vector<size_t> at(4 * passes);
+    for (uint32_t p = 0; p < passes; ++p) {
+        SVT_TRY(c.mark(&at[4 * p]));
+        hipLaunchKernelGGL(svt_bam_histogram_kernel, dim3(grid), dim3(kSortBlock), 0, c.s, c.d_keys[src].as<uint64_t>(), n, n_tiles, shifts[p],
+                           c.d_hist.as<uint32_t>());
+        HIP_TRY(hipGetLastError());
+        SVT_TRY(c.mark(&at[4 * p + 1]));
+        hipLaunchKernelGGL(svt_bam_scan_kernel, dim3(1), dim3(kSortBlock), 0, c.s, c.d_hist.as<uint32_t>(), (uint64_t)n_tiles * 256);
+        HIP_TRY(hipGetLastError());
+        SVT_TRY(c.mark(&at[4 * p + 2]));
+        hipLaunchKernelGGL(svt_bam_scatter_kernel, dim3(grid), dim3(kSortBlock), 0, c.s, c.d_keys[src].as<uint64_t>(), c.d_idx[src].as<uint32_t>(), n, n_tiles,
+                           shifts[p], c.d_hist.as<uint32_t>(), c.d_keys[src ^ 1].as<uint64_t>(), c.d_idx[src ^ 1].as<uint32_t>());
+        HIP_TRY(hipGetLastError());
+        SVT_TRY(c.mark(&at[4 * p + 3]));
+        src ^= 1;
+    }
+    SVT_TRY(d2h_staged(order.data(), c.d_idx[src].p, n * sizeof(uint32_t), c.s));
+    HIP_TRY(hipStreamSynchronize(c.s));
+    for (uint32_t p = 0; p < passes; ++p) {
+        SVT_TRY(c.between(at[4 * p], at[4 * p + 1], &g_bam_sort_times.histogram_kernel_s));
+        SVT_TRY(c.between(at[4 * p + 1], at[4 * p + 2], &g_bam_sort_times.scan_kernel_s));
+        SVT_TRY(c.between(at[4 * p + 2], at[4 * p + 3], &g_bam_sort_times.scatter_kernel_s));
+    }
+    // the kernels' order is a permutation or it is not theirs: what the gather and the callers rely on
+    std::vector<uint8_t> seen(n, 0);
+    for (uint64_t j = 0; j < n; ++j) {
+        if (order[j] >= n || seen[order[j]]) return fail(SVT_ERR_HIP, "svt_bam_scatter_kernel: the order is no permutation");
+        seen[order[j]] = 1;
+    }
+    return SVT_OK;
+}
+
+static int svt_bam_spans_device_impl(const uint8_t* bytes, uint64_t len, const uint64_t* rec_off, uint64_t n, int32_t n_ref, svt_bam_span* spans,
+                                     uint64_t* key_and, uint64_t* key_or, int device)
+{
+    const auto t0 = std::chrono::steady_clock::now();
+    g_bam_sort_times = svt_bam_sort_times();
+    if ((len && !bytes) || !rec_off || (n && !spans)) return fail(SVT_ERR_INVALID, "null argument");
+    if (n_ref < 0) return fail(SVT_ERR_INVALID, "svt_bam_spans: n_ref is negative");
+    if (n >> 32) return fail(SVT_ERR_INVALID, "svt_bam_spans: too many records in one call (< 2^32)");
+    SVT_TRY(select_device(device));
+    BamSortCall c;
+    SVT_TRY(c.begin(bytes, len));
+    std::vector<svt_bam_span> table;
+    uint64_t a = ~0ull, o = 0;
+    SVT_TRY(keys_resident(c, len, rec_off, n, n_ref, table, a, o, device));
+    if (n) std::memcpy(spans, table.data(), n * sizeof(svt_bam_span));
+    if (key_and) *key_and = a;
+    if (key_or) *key_or = o;
+    g_bam_sort_times.total_s = seconds_since(t0);
+    return SVT_OK;
+}
+
+static int svt_bam_sort_order_device_impl(const svt_bam_span* spans, uint64_t n, uint64_t* perm, uint64_t* bad_record, uint32_t* bad_kind, int device)
+{
+    const auto t0 = std::chrono::steady_clock::now();
+    g_bam_sort_times = svt_bam_sort_times();
+    if ((n && (!spans || !perm)) || !bad_record || !bad_kind) return fail(SVT_ERR_INVALID, "null argument");
+    if (n >> 32) return fail(SVT_ERR_INVALID, "svt_bam_sort_order: too many records in one call (< 2^32)");
+    SVT_TRY(select_device(device));
+    *bad_record = bsr::first_bad(spans, n, *bad_kind);
+    if (*bad_record || n == 0) return SVT_OK;
+    BamSortCall c;
+    SVT_TRY(c.take());
+    std::vector<uint64_t> keys(n);
+    std::vector<uint32_t> idx(n), order;
+    uint64_t a = ~0ull, o = 0;
+    for (uint64_t i = 0; i < n; ++i) {
+        keys[i] = spans[i].key;
+        idx[i] = (uint32_t)i;
+        a &= keys[i];
+        o |= keys[i];
+    }
+    {
+        Stager st(c.s);
+        SVT_TRY(upload(c.d_keys[0], keys, st));
+        SVT_TRY(upload(c.d_idx[0], idx, st));
+        SVT_TRY(st.finish());
+    }
+    SVT_TRY(sort_resident(c, n, a, o, order, device));
+    for (uint64_t j = 0; j < n; ++j) perm[j] = order[j];
+    g_bam_sort_times.total_s = seconds_since(t0);
+    return SVT_OK;
+}
+
+static int svt_bam_sorted_bgzf_device_impl(const uint8_t* bytes, uint64_t len, const uint64_t* rec_off, uint64_t n, int32_t n_ref, int sort, uint32_t mode,
+                                           uint8_t* out, uint64_t capacity, uint64_t* out_off, uint64_t member_capacity, uint64_t* n_members,
+                                           uint64_t* member_start, svt_bam_span* spans, uint64_t* perm, uint64_t* bad_record, uint32_t* bad_kind, int device)
+{
+    const auto t0 = std::chrono::steady_clock::now();
+    g_bam_sort_times = svt_bam_sort_times();
+    g_deflate_times = svt_deflate_times();
+    if (mode != SVT_DEFLATE_FIXED && mode != SVT_DEFLATE_DYNAMIC)
+        return fail(SVT_ERR_INVALID, "svt_bam_sorted_bgzf: mode is SVT_DEFLATE_FIXED (0) or SVT_DEFLATE_DYNAMIC (1)");
+    if (!rec_off || !out_off || !n_members || !member_start || !bad_record || !bad_kind || (len && (!bytes || !out)) || (n && (!spans || !perm)))
+        return fail(SVT_ERR_INVALID, "null argument");
+    if (n_ref < 0) return fail(SVT_ERR_INVALID, "svt_bam_sorted_bgzf: n_ref is negative");
+    if (n >> 32) return fail(SVT_ERR_INVALID, "svt_bam_sorted_bgzf: too many records in one call (< 2^32)");
+    if (rec_off[0] > len || rec_off[n] != len) return fail(SVT_ERR_INVALID, "svt_bam_sorted_bgzf: the records end where the bytes end");
+    for (uint64_t i = 0; i < n; ++i)
+        if (rec_off[i] > rec_off[i + 1]) return fail(SVT_ERR_INVALID, "svt_bam_sorted_bgzf: rec_off must not decrease");
+    *n_members = 0;
+    *bad_record = 0;
+    *bad_kind = 0;
+    out_off[0] = 0;
+    member_start[0] = 0;
+    SVT_TRY(select_device(device));
+    if (len == 0) return SVT_OK;
+    BamSortCall c;
+    SVT_TRY(c.begin(bytes, len));
+    const uint64_t header_len = rec_off[0];
+    std::vector<svt_bam_span> table;
+    uint64_t key_and = ~0ull, key_or = 0;
+    SVT_TRY(keys_resident(c, len, rec_off, n, n_ref, table, key_and, key_or, device));
+    const uint8_t* d_written = c.d_stream.as<uint8_t>();
+    if (sort) {
+        *bad_record = bsr::first_bad(table.data(), n, *bad_kind);
+        if (*bad_record) return SVT_OK;
+        std::vector<uint32_t> order;
+        SVT_TRY(sort_resident(c, n, key_and, key_or, order, device));
+        std::vector<uint64_t> dst_off(n);
+        uint64_t at = header_len;
+        for (uint64_t j = 0; j < n; ++j) {
+            perm[j] = order[j];
+            dst_off[j] = at;
+            at += table[order[j]].len;
+        }
+        if (at != len) return fail(SVT_ERR_INTERNAL, "svt_bam_sorted_bgzf: the records' lengths do not sum to the stream's");
+        SVT_TRY(c.d_sorted.alloc(len));
+        if (header_len) HIP_TRY(hipMemcpyAsync(c.d_sorted.p, c.d_stream.p, header_len, hipMemcpyDeviceToDevice, c.s));
+        if (n) {
+            SVT_TRY(c.d_perm.alloc(n * sizeof(uint64_t)));
+            {
+                Stager st(c.s);
+                SVT_TRY(st.copy(c.d_perm.p, perm, n * sizeof(uint64_t)));
+                SVT_TRY(upload(c.d_dst_off, dst_off, st));
+                SVT_TRY(st.finish());
+            }
+            size_t e0 = 0, e1 = 0;
+            SVT_TRY(c.mark(&e0));
+            hipLaunchKernelGGL(svt_vcf_gather_kernel<svt_bam_span>, dim3(lines_grid(((n + 63) / 64 + kLinesWaves - 1) / kLinesWaves, device)), dim3(kLinesBlock), 0,
+                               c.s, c.d_stream.as<uint8_t>(), len, c.d_spans.as<svt_bam_span>(), n, c.d_perm.as<uint64_t>(), c.d_dst_off.as<uint64_t>(), n,
+                               c.d_sorted.as<uint8_t>(), len);
+            HIP_TRY(hipGetLastError());
+            SVT_TRY(c.mark(&e1));
+            HIP_TRY(hipStreamSynchronize(c.s));
+            SVT_TRY(c.between(e0, e1, &g_bam_sort_times.gather_kernel_s));
+        }
+        d_written = c.d_sorted.as<uint8_t>();
+        for (uint64_t j = 0; j < n; ++j) {
+            spans[j] = table[order[j]];
+            spans[j].off = dst_off[j];
+        }
+    } else {
+        for (uint64_t j = 0; j < n; ++j) {
+            spans[j] = table[j];
+            perm[j] = j;
+        }
+    }
+    std::vector<uint64_t> start;
+    bsr::cut_members(header_len, n, [&](uint64_t j) { return spans[j].len; }, start);        // cut where bam.BgzfWriter cuts
+    const uint64_t members = start.size() - 1;
+    if (members > member_capacity) return fail(SVT_ERR_INVALID, "svt_bam_sorted_bgzf: member_capacity is below the number of members");
+    if (members > 0xFFFFFFFFull) return fail(SVT_ERR_INVALID, "svt_bam_sorted_bgzf: too many members in one call (< 2^32)");
+    std::vector<crc::Job> jobs(members);
+    uint64_t slots = 0;
+    for (uint64_t k = 0; k < members; ++k) {
+        jobs[k] = crc::Job{start[k], (uint32_t)(start[k + 1] - start[k]), 0};
+        slots += dfl::slot_bytes(jobs[k].len);
+        member_start[k] = start[k];
+    }
+    member_start[members] = start[members];
+    SVT_TRY(deflate_resident(c, d_written, len, jobs, slots, out, capacity, out_off, mode, device));
+    *n_members = members;
+    g_bam_sort_times.total_s = g_deflate_times.total_s = seconds_since(t0);
+    return SVT_OK;
+}
+
+}  // extern "C++"
+
+int svt_bam_spans_device(const uint8_t* bytes, uint64_t len, const uint64_t* rec_off, uint64_t n, int32_t n_ref, svt_bam_span* spans, uint64_t* key_and,
+                         uint64_t* key_or, int device)
+{
+    return guarded([&] { return svt_bam_spans_device_impl(bytes, len, rec_off, n, n_ref, spans, key_and, key_or, device); });
+}
+
+int svt_bam_sort_order_device(const svt_bam_span* spans, uint64_t n, uint64_t* perm, uint64_t* bad_record, uint32_t* bad_kind, int device)
+{
+    return guarded([&] { return svt_bam_sort_order_device_impl(spans, n, perm, bad_record, bad_kind, device); });
+}
+
+int svt_bam_sorted_bgzf_device(const uint8_t* bytes, uint64_t len, const uint64_t* rec_off, uint64_t n, int32_t n_ref, int sort, uint32_t mode, uint8_t* out,
+                               uint64_t capacity, uint64_t* out_off, uint64_t member_capacity, uint64_t* n_members, uint64_t* member_start,
+                               svt_bam_span* spans, uint64_t* perm, uint64_t* bad_record, uint32_t* bad_kind, int device)
+{
+    return guarded([&] {
+        return svt_bam_sorted_bgzf_device_impl(bytes, len, rec_off, n, n_ref, sort, mode, out, capacity, out_off, member_capacity, n_members, member_start,
+                                               spans, perm, bad_record, bad_kind, device);
+    });
+}
+
+int svt_bam_sort_last_times(svt_bam_sort_times* times)
+{
+    return guarded([&]() -> int {
+        if (!times) return fail(SVT_ERR_INVALID, "null argument");
+        *times = g_bam_sort_times;
+        return SVT_OK;
+    });
+}

@@ -106,7 +106,7 @@ static int gather_resident(LinesCall& c, uint64_t len, uint64_t n, const uint64_
         SVT_TRY(st.finish());
     }
     HIP_TRY(hipEventRecord(c.lev[4], c.s));
-    hipLaunchKernelGGL(svt_vcf_gather_kernel, dim3(lines_grid(((n_perm + 63) / 64 + kLinesWaves - 1) / kLinesWaves, device)), dim3(kLinesBlock), 0, c.s,
+    hipLaunchKernelGGL(svt_vcf_gather_kernel<svt_tbx_line>, dim3(lines_grid(((n_perm + 63) / 64 + kLinesWaves - 1) / kLinesWaves, device)), dim3(kLinesBlock), 0, c.s,
                        c.d_text.as<uint8_t>(), len, c.d_lines.as<svt_tbx_line>(), n, c.d_perm.as<uint64_t>(), c.d_dst_off.as<uint64_t>(), n_perm,
                        c.d_sorted.as<uint8_t>(), out_len);
     HIP_TRY(hipGetLastError());

@@ -27,7 +27,9 @@
 #include <vector>
 
 #include "../../include/svtyper_reads.h"
+#include "svt_bai_index.h"
 #include "svt_bam_index.h"
+#include "svt_bam_sort_rules.h"
 #include "svt_bgzf.h"
 #include "svt_dump_rules.h"
 #include "svt_error.h"
@@ -60,3 +62,4 @@ using rr::ld32;
 #include "svt_reads_bgzf_entries.h"    // svt_bgzf_inflate_host, _crc32_host, _deflate_host
 #include "svt_reads_library.h"         // svt_bam_scan_library, svt::lw: the segmented library walk
 #include "svt_reads_vcf_entries.h"     // svt_vcf_lines_host, _gather_host, _sort_order, svt_tbx_build: VCF text as lines, the .tbi fold
+#include "svt_reads_bam_sort_entries.h" // svt_bam_spans_host, _sort_order_host, svt_bai_build: BAM records as spans, the .bai fold

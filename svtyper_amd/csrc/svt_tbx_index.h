@@ -21,17 +21,52 @@ namespace tbx {
 constexpr uint32_t kPseudoBin = 37450;
 constexpr uint64_t kUnset = ~0ull;
 
-struct Contig {
-    std::string name;
-    std::map<uint32_t, std::vector<std::pair<uint64_t, uint64_t>>> bins;
-    std::vector<uint64_t> ioff;
-    uint64_t lines = 0, first = 0, last = 0;
-};
-
 struct Builder {
     std::vector<uint8_t> out;
     void u32(uint32_t v) { for (int k = 0; k < 4; ++k) out.push_back((uint8_t)(v >> (8 * k))); }
     void u64(uint64_t v) { for (int k = 0; k < 8; ++k) out.push_back((uint8_t)(v >> (8 * k))); }
+};
+
+// the fold of one contig, shared with the .bai of svt_bai_index.h (whose records can be unmapped: the pseudo-bin's second count)
+struct Contig {
+    std::string name;
+    std::map<uint32_t, std::vector<std::pair<uint64_t, uint64_t>>> bins;
+    std::vector<uint64_t> ioff;
+    uint64_t lines = 0, unmapped = 0, first = 0, last = 0;
+    uint32_t last_bin = ~0u;
+    // one more record [beg, end) of the contig, behind the others, at virtual offsets [s, e)
+    void add(uint64_t beg, uint64_t end, uint64_t s, uint64_t e)
+    {
+        const uint32_t bin = reg2bin(beg, end);
+        if (bin == last_bin) bins[bin].back().second = e;
+        else bins[bin].emplace_back(s, e);
+        last_bin = bin;
+        const uint64_t w1 = (end - 1) >> 14;
+        if (ioff.size() <= w1) ioff.resize(w1 + 1, kUnset);
+        for (uint64_t w = beg >> 14; w <= w1; ++w) ioff[w] = std::min(ioff[w], s);
+        if (!lines++) first = s;
+        last = e;
+    }
+    // n_bin, the bins, the pseudo-bin, n_intv, the linear index; a contig without records: n_bin = 0, n_intv = 0
+    void write(Builder& b)
+    {
+        if (!lines) {
+            b.u32(0); b.u32(0);
+            return;
+        }
+        b.u32((uint32_t)bins.size() + 1);
+        for (const auto& bin : bins) {
+            b.u32(bin.first);
+            b.u32((uint32_t)bin.second.size());
+            for (const auto& chunk : bin.second) { b.u64(chunk.first); b.u64(chunk.second); }
+        }
+        b.u32(kPseudoBin); b.u32(2);
+        b.u64(first); b.u64(last); b.u64(lines - unmapped); b.u64(unmapped);
+        for (uint64_t w = ioff.size(); w-- > 1;)
+            if (ioff[w - 1] == kUnset) ioff[w - 1] = ioff[w];
+        b.u32((uint32_t)ioff.size());
+        for (uint64_t v : ioff) b.u64(v);
+    }
 };
 
 // svt_tbx_build (include/svtyper_reads.h) without its argument checks: 0 and the bytes in `out`, or the 1-based number of the line
@@ -49,7 +84,6 @@ inline uint64_t build(const uint8_t* text, const uint64_t* src_off, const svt_tb
     std::unordered_map<std::string, uint32_t> tid_of;
     Contig* cur = nullptr;
     std::string name;
-    uint32_t last_bin = 0;
     uint64_t last_beg = 0;
     for (uint64_t i = header_lines(lines, n); i < n; ++i) {
         const svt_tbx_line& l = lines[i];
@@ -63,20 +97,11 @@ inline uint64_t build(const uint8_t* text, const uint64_t* src_off, const svt_tb
             contigs.emplace_back();
             cur = &contigs.back();
             cur->name = name;
-            last_bin = ~0u;
         } else if (l.beg < last_beg) { bad_kind = SVT_TBX_POS_BACK; return i + 1; }
         last_beg = l.beg;
         const uint64_t beg = l.beg, end = std::max<uint64_t>(l.end, beg + 1);      // (an empty REF still takes its base)
         const uint64_t s = voff(l.off), e = voff(l.off + l.len);
-        const uint32_t bin = reg2bin(beg, end);
-        if (bin == last_bin) cur->bins[bin].back().second = e;
-        else cur->bins[bin].emplace_back(s, e);
-        last_bin = bin;
-        const uint64_t w1 = (end - 1) >> 14;
-        if (cur->ioff.size() <= w1) cur->ioff.resize(w1 + 1, kUnset);
-        for (uint64_t w = beg >> 14; w <= w1; ++w) cur->ioff[w] = std::min(cur->ioff[w], s);
-        if (!cur->lines++) cur->first = s;
-        cur->last = e;
+        cur->add(beg, end, s, e);
     }
     Builder b;
     b.out.assign({'T', 'B', 'I', 1});
@@ -89,20 +114,7 @@ inline uint64_t build(const uint8_t* text, const uint64_t* src_off, const svt_tb
         b.out.insert(b.out.end(), c.name.begin(), c.name.end());
         b.out.push_back(0);
     }
-    for (Contig& c : contigs) {
-        b.u32((uint32_t)c.bins.size() + 1);
-        for (const auto& bin : c.bins) {
-            b.u32(bin.first);
-            b.u32((uint32_t)bin.second.size());
-            for (const auto& chunk : bin.second) { b.u64(chunk.first); b.u64(chunk.second); }
-        }
-        b.u32(kPseudoBin); b.u32(2);
-        b.u64(c.first); b.u64(c.last); b.u64(c.lines); b.u64(0);
-        for (uint64_t w = c.ioff.size(); w-- > 1;)
-            if (c.ioff[w - 1] == kUnset) c.ioff[w - 1] = c.ioff[w];
-        b.u32((uint32_t)c.ioff.size());
-        for (uint64_t v : c.ioff) b.u64(v);
-    }
+    for (Contig& c : contigs) c.write(b);
     out.swap(b.out);
     return 0;
 }

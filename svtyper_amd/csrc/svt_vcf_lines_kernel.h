@@ -113,8 +113,10 @@ __global__ __launch_bounds__(kLinesBlock) void svt_vcf_parse_kernel(const uint8_
     }
 }
 
-// line lines[perm[j]] of text -> out + dst_off[j], j < n_perm
-__global__ __launch_bounds__(kLinesBlock) void svt_vcf_gather_kernel(const uint8_t* __restrict__ text, uint64_t len, const svt_tbx_line* __restrict__ lines,
+// line lines[perm[j]] of text -> out + dst_off[j], j < n_perm.  Row: a table's record with `off` and `len` (svt_tbx_line; svt_bam_span,
+// whose "lines" are the records of svt_bam_sort_kernel.h)
+template <typename Row>
+__global__ __launch_bounds__(kLinesBlock) void svt_vcf_gather_kernel(const uint8_t* __restrict__ text, uint64_t len, const Row* __restrict__ lines,
                                                                      uint64_t n, const uint64_t* __restrict__ perm, const uint64_t* __restrict__ dst_off,
                                                                      uint64_t n_perm, uint8_t* __restrict__ out, uint64_t out_len)
 {
@@ -124,12 +126,12 @@ __global__ __launch_bounds__(kLinesBlock) void svt_vcf_gather_kernel(const uint8
         const uint64_t j = w * 64 + lane;
         unsigned long long src = 0, dst = 0, size = 0;
         if (j < n_perm && perm[j] < n) {
-            const svt_tbx_line l = lines[perm[j]];
+            const uint64_t l_off = lines[perm[j]].off, l_len = lines[perm[j]].len;
             const uint64_t d = dst_off[j];
-            if (l.off <= len && l.len <= len - l.off && d <= out_len && l.len <= out_len - d) {
-                src = l.off;
+            if (l_off <= len && l_len <= len - l_off && d <= out_len && l_len <= out_len - d) {
+                src = l_off;
                 dst = d;
-                size = l.len;
+                size = l_len;
             }
         }
         if (size <= kGatherShort)

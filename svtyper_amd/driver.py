@@ -17,6 +17,8 @@ route, the `stats=` block.  What the reference's two programs do differently is 
              finish(unpaired)             the end of a run
     data     alignment_outpath            (`svtyper -w`) the evidence dump: tag_and_write below, per chunk, in output order -- the reads of
                                                   reader="python", or the finished records of reader="device" (svt_dump_kernel.h)
+             alignment_sort, alignment_index   (`--sort-alignment`, `--bai`) that BAM coordinate-sorted / with its .bai: the writer's
+                                                  sort= and index= (bam.AlignmentFile), which hold the records until close()
 
 No method takes a flag that names its caller, and a driver's hooks run per line handed to the per-line route and per
 block, never per site of the bulk route (`BulkFeeder._block` / `_write_block`).
@@ -120,6 +122,8 @@ class Driver:
     alignment_outpath = None            # (`svtyper -w`; classic.Classic sets it)
     deflate = "zlib"                    # who compresses the `-w` BAM's members (bam.BgzfWriter)
     huffman = "fixed"                   # ... and into which block, where it is the library's own compressor
+    alignment_sort = False              # the `-w` BAM in coordinate order (bam.AlignmentFile: sort=)
+    alignment_index = None              # ... and "bai": its index beside it (index=)
 
     def __init__(self, bam_string, vcf_in, vcf_out, min_aligned, split_weight, disc_weight, num_samp, lib_info_path, debug,
                  ref_fasta, sum_quals, max_reads, max_ci_dist, n_threads=0):
@@ -133,6 +137,10 @@ class Driver:
     def run(self, chunk_units, engine=None, geometry="host", reader=None, stats=None, inflate="host", library_scan="host",
             verify="off"):
         writing = self.alignment_outpath is not None
+        if not writing and (self.alignment_sort or self.alignment_index is not None):
+            raise ValueError("alignment_sort / alignment_index (--sort-alignment, --bai) need -w/--write_alignment: they are about that BAM")
+        if self.alignment_index not in (None, "bai"):
+            raise ValueError("alignment_index must be None or 'bai', not %r" % (self.alignment_index,))
         if writing and reader is None:
             reader = "python"           # the one route that keeps the reads it tallied
         reader = resolve_reader(reader)
@@ -163,8 +171,11 @@ class Driver:
         out_bam, written = None, set()
         if writing:     # classic.py:161-166: the first alignment file is the template, its header is the dump's
             template = AlignmentFile(paths[0], "rb")
+            order = dict(sort=True) if self.alignment_sort else {}
+            if self.alignment_index is not None:
+                order["index"] = self.alignment_index
             out_bam = AlignmentFile(self.alignment_outpath, "wb", template=template, deflate=self.deflate, huffman=self.huffman,
-                                    device=getattr(engine, "device", 0))
+                                    device=getattr(engine, "device", 0), **order)
             template.close()
         self.write_library_file()
         if self.vcf_in is None:

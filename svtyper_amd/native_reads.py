@@ -141,6 +141,13 @@ class _LinesTimes(C.Structure):
                 ("gather_kernel_s", C.c_double), ("total_s", C.c_double)]
 
 
+class _BamSortTimes(C.Structure):
+    """include/svtyper_reads.h: svt_bam_sort_times"""
+    _fields_ = [("keys_kernel_s", C.c_double), ("histogram_kernel_s", C.c_double), ("scan_kernel_s", C.c_double),
+                ("scatter_kernel_s", C.c_double), ("gather_kernel_s", C.c_double), ("total_s", C.c_double), ("passes", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
 class _InflateStats(C.Structure):
     """include/svtyper_reads.h: svt_evidence_inflate_stats"""
     _fields_ = [("blocks_inflated", C.c_uint64), ("blocks_failed", C.c_uint64), ("compressed_bytes", C.c_uint64),
@@ -273,6 +280,15 @@ def _lib():
                                    ("svt_vcf_bgzf_device", [P, U64, C.c_int, C.c_uint32, P, U64, P, P, U64, P, P, P, C.c_int]),
                                    ("svt_vcf_lines_last_times", [C.POINTER(_LinesTimes)]),
                                    ("svt_tbx_build", [P, U64, P, P, U64, P, U64, C.c_uint32, P, P, P]), ("svt_tbx_take", [P, U64])):
+                getattr(L, name).restype = C.c_int
+                getattr(L, name).argtypes = argtypes
+        if hasattr(L, "svt_bam_spans_host"):       # (likewise: BAM records as spans, the sorted and indexed `-w` dump)
+            P, U64, I32 = C.c_void_p, C.c_uint64, C.c_int32
+            for name, argtypes in (("svt_bam_spans_host", [P, U64, P, U64, I32, P, P, P]), ("svt_bam_spans_device", [P, U64, P, U64, I32, P, P, P, C.c_int]),
+                                   ("svt_bam_sort_order_host", [P, U64, P, P, P]), ("svt_bam_sort_order_device", [P, U64, P, P, P, C.c_int]),
+                                   ("svt_bam_sorted_bgzf_device", [P, U64, P, U64, I32, C.c_int, C.c_uint32, P, U64, P, U64, P, P, P, P, P, P, C.c_int]),
+                                   ("svt_bam_sort_last_times", [C.POINTER(_BamSortTimes)]),
+                                   ("svt_bai_build", [P, U64, I32, P, P, U64, P, P, P]), ("svt_bai_take", [P, U64])):
                 getattr(L, name).restype = C.c_int
                 getattr(L, name).argtypes = argtypes
         L.svt_bam_set_verify.restype = C.c_int
@@ -890,4 +906,109 @@ def tbx_build(text: bytes, lines: np.ndarray, member_off, src_off=None, payload:
         return None, int(bad.value), int(kind.value)
     out = np.zeros(max(size.value, 1), np.uint8)
     hip._check(L.svt_tbx_take(out.ctypes.data, size.value))
+    return out[:size.value].tobytes(), 0, 0
+
+
+# ---- BAM records as spans: the span table, the order --sort-alignment writes, the .bai fold (include/svtyper_reads.h) -----------
+BAM_SPAN = np.dtype([("off", np.uint64), ("len", np.uint64), ("key", np.uint64), ("tid", np.int32), ("beg", np.uint32),
+                     ("end", np.uint32), ("flags", np.uint32)])      # svt_bam_span
+BAM_UNMAPPED, BAM_NO_COOR, BAM_BAD, BAM_BEYOND = 1, 2, 4, 8
+BAM_BAD_RECORD, BAM_BAD_TID, BAM_BAD_POS = 0x100, 0x200, 0x400
+BAM_KIND_RECORD, BAM_KIND_TID, BAM_KIND_POS, BAM_KIND_BEYOND, BAM_KIND_KEY_BACK = 1, 2, 3, 4, 5
+
+
+def _spans_lib():
+    L = _lib()
+    if not hasattr(L, "svt_bam_spans_host"):
+        raise hip.SvtyperHipError("this libsvtyper_hip.so has no svt_bam_spans_host (built before the sorted, indexed -w dump)")
+    return L
+
+
+def bam_spans(data: bytes, rec_off, n_ref: int, device: Optional[int] = None) -> Tuple[np.ndarray, int, int]:
+    """svt_bam_spans_host (device None) / _device: (the span table of the records data[rec_off[i] .. rec_off[i + 1]), one BAM_SPAN
+    each; the AND of their keys; the OR)"""
+    L = _spans_lib()
+    buf = _text_array(data)
+    rec_off = np.ascontiguousarray(rec_off, np.uint64)
+    n = int(rec_off.shape[0]) - 1
+    if n < 0:
+        raise ValueError("rec_off must hold n + 1 entries")
+    spans = np.zeros(max(n, 1), BAM_SPAN)
+    key_and, key_or = C.c_uint64(0), C.c_uint64(0)
+    args = [buf.ctypes.data, len(data), rec_off.ctypes.data, n, int(n_ref), spans.ctypes.data, C.addressof(key_and), C.addressof(key_or)]
+    if device is None:
+        hip._check(L.svt_bam_spans_host(*args))
+    else:
+        hip._check(L.svt_bam_spans_device(*args, int(device)))
+    return spans[:n], int(key_and.value), int(key_or.value)
+
+
+def bam_sort_order(spans: np.ndarray, device: Optional[int] = None):
+    """svt_bam_sort_order_host (device None) / _device: (perm, 0, 0), or (None, the 1-based number of a record that cannot be
+    sorted, why: BAM_KIND_*)"""
+    L = _spans_lib()
+    spans = np.ascontiguousarray(spans, BAM_SPAN)
+    n = spans.shape[0]
+    perm = np.zeros(max(n, 1), np.uint64)
+    bad, kind = C.c_uint64(0), C.c_uint32(0)
+    args = [spans.ctypes.data if n else None, n, perm.ctypes.data, C.addressof(bad), C.addressof(kind)]
+    if device is None:
+        hip._check(L.svt_bam_sort_order_host(*args))
+    else:
+        hip._check(L.svt_bam_sort_order_device(*args, int(device)))
+    return (None, int(bad.value), int(kind.value)) if bad.value else (perm[:n], 0, 0)
+
+
+def bam_sorted_bgzf_device(data: bytes, rec_off, n_ref: int, sort: bool, huffman: str = "fixed", device: int = 0):
+    """svt_bam_sorted_bgzf_device: `data` (the header in front of rec_off[0], the records behind it) up once; (members uint8,
+    out_off uint64 [m + 1], member_start uint64 [m + 1], spans as written, perm uint64, 0, 0), or (None, None, None, None, None,
+    bad_record, bad_kind) where sorting met a record that cannot be sorted"""
+    L = _spans_lib()
+    buf = _text_array(data)
+    rec_off = np.ascontiguousarray(rec_off, np.uint64)
+    n = int(rec_off.shape[0]) - 1
+    if n < 0:
+        raise ValueError("rec_off must hold n + 1 entries")
+    member_capacity = n + len(data) // DEFLATE_MAX_PAYLOAD + 2
+    capacity = len(data) + DEFLATE_SLOT_EXTRA * member_capacity
+    out = np.zeros(max(capacity, 1), np.uint8)
+    out_off = np.zeros(member_capacity + 1, np.uint64)
+    member_start = np.zeros(member_capacity + 1, np.uint64)
+    spans = np.zeros(max(n, 1), BAM_SPAN)
+    perm = np.zeros(max(n, 1), np.uint64)
+    n_members, bad, kind = C.c_uint64(0), C.c_uint64(0), C.c_uint32(0)
+    hip._check(L.svt_bam_sorted_bgzf_device(buf.ctypes.data, len(data), rec_off.ctypes.data, n, int(n_ref), int(bool(sort)),
+                                            int(check_huffman(huffman) == "dynamic"), out.ctypes.data, capacity, out_off.ctypes.data,
+                                            member_capacity, C.addressof(n_members), member_start.ctypes.data, spans.ctypes.data,
+                                            perm.ctypes.data, C.addressof(bad), C.addressof(kind), int(device)))
+    if bad.value:
+        return None, None, None, None, None, int(bad.value), int(kind.value)
+    m = int(n_members.value)
+    return out[:int(out_off[m])], out_off[:m + 1], member_start[:m + 1], spans[:n], perm[:n], 0, 0
+
+
+def bam_sort_last_times() -> Dict[str, float]:
+    """svt_bam_sort_last_times: the kernels of this thread's last device call over BAM spans, from HIP events (the sort's three
+    summed over its passes), and `passes`: the digits the sort took"""
+    t = _BamSortTimes()
+    hip._check(_spans_lib().svt_bam_sort_last_times(C.byref(t)))
+    return {name: (int if name == "passes" else float)(getattr(t, name)) for name, _ in _BamSortTimes._fields_ if name != "reserved"}
+
+
+def bai_build(spans: np.ndarray, n_ref: int, member_start, member_off):
+    """svt_bai_build + svt_bai_take: (the bytes of the .bai, 0, 0), or (None, bad_record, bad_kind).  `spans`: the table of the
+    stream as written; member k holds its bytes [member_start[k], member_start[k + 1]) and begins at file offset member_off[k]"""
+    L = _spans_lib()
+    spans = np.ascontiguousarray(spans, BAM_SPAN)
+    member_start = np.ascontiguousarray(member_start, np.uint64)
+    member_off = np.ascontiguousarray(member_off, np.uint64)
+    if member_start.shape[0] < 1 or member_start.shape[0] != member_off.shape[0]:
+        raise ValueError("member_start and member_off must hold n + 1 entries each")
+    size, bad, kind = C.c_uint64(0), C.c_uint64(0), C.c_uint32(0)
+    hip._check(L.svt_bai_build(spans.ctypes.data if spans.size else None, spans.shape[0], int(n_ref), member_start.ctypes.data,
+                               member_off.ctypes.data, member_start.shape[0] - 1, C.addressof(size), C.addressof(bad), C.addressof(kind)))
+    if bad.value:
+        return None, int(bad.value), int(kind.value)
+    out = np.zeros(max(size.value, 1), np.uint8)
+    hip._check(L.svt_bai_take(out.ctypes.data, size.value))
     return out[:size.value].tobytes(), 0, 0

@@ -1,0 +1,505 @@
+"""The coordinate-sorted, BAI-indexed `-w` BAM: corpus and an independent checker.  Nothing here imports svtyper_amd.
+
+The checker restates the rule in plain Python -- key = tid' << 33 | (pos + 1) << 1 | reverse with tid' = n_ref for tid = -1; a
+record's extent [pos, pos + reference bases of M D N = X), one base for an unmapped record, one without CIGAR or with a sum
+of 0 --, takes sorted() as the order, packs members as bam.BgzfWriter.write_record does, writes and reads a .bai, checks an
+index's structure against the file (chunks ascending, inside the file, starting at record starts) and answers region queries
+through bins and linear index over members it inflates itself, compared with a scan of all records.  Byte equality with
+htslib's .bai is not claimed anywhere: what is asked of an index is that every query through it finds what the scan finds."""
+import random
+import struct
+import zlib
+
+PAYLOAD = 65280
+TILE = 1024                 # svt_bam_sort_kernel.h: kSortTile, the elements of one workgroup per pass
+UNMAPPED, NO_COOR, BAD, BEYOND = 1, 2, 4, 8
+BAD_RECORD, BAD_TID, BAD_POS = 0x100, 0x200, 0x400
+KIND_RECORD, KIND_TID, KIND_POS, KIND_BEYOND, KIND_KEY_BACK = 1, 2, 3, 4, 5
+BAI_END = 1 << 29
+M, I, D, N, S, H, P, EQ, X = range(9)
+
+
+# ------------------------------------------------------------------------------------------ encoding
+def header(text, refs):
+    """a BAM header: `text` (str) and `refs`, a list of (name, length)"""
+    t = text.encode("ascii")
+    out = b"BAM\1" + struct.pack("<i", len(t)) + t + struct.pack("<i", len(refs))
+    for name, length in refs:
+        nm = name.encode("ascii") + b"\0"
+        out += struct.pack("<i", len(nm)) + nm + struct.pack("<i", length)
+    return out
+
+
+def refs(n):
+    return [("chr%d" % (i + 1), BAI_END + (1 << 20)) for i in range(n)]
+
+
+def rec(name, tid, pos, flag=0, cigar=(), size=None, tags=b"XV" + b"AR"):
+    """a record as `svtyper -w` writes them (l_seq = 0); `size`: its whole length, made up with a Z tag"""
+    nm = name.encode("ascii") + b"\0"
+    cig = b"".join(struct.pack("<I", n << 4 | op) for op, n in cigar)
+    body = struct.pack("<iiBBHHHiiii", tid, pos, len(nm), 30, 0, len(cigar), flag, 0, -1, -1, 0) + nm + cig + tags
+    if size is not None:
+        fill = size - 4 - len(body) - 4
+        assert fill >= 0, "size too small"
+        body += b"ZZZ" + b"a" * fill + b"\0"
+    return struct.pack("<i", len(body)) + body
+
+
+HEADERS = {
+    "so_coordinate": "@HD\tVN:1.5\tSO:coordinate\n@SQ\tSN:chr1\tLN:1000\n@PG\tID:x\n",
+    "so_unsorted": "@HD\tVN:1.5\tSO:unsorted\tGO:none\n@SQ\tSN:chr1\tLN:1000\n",
+    "hd_no_so": "@HD\tVN:1.4\n@SQ\tSN:chr1\tLN:1000\n",
+    "no_hd": "@SQ\tSN:chr1\tLN:1000\n@CO\tSO:unsorted in a comment\n",
+}
+WANT_HEADERS = {
+    "so_coordinate": HEADERS["so_coordinate"],
+    "so_unsorted": "@HD\tVN:1.5\tSO:coordinate\tGO:none\n@SQ\tSN:chr1\tLN:1000\n",
+    "hd_no_so": "@HD\tVN:1.4\tSO:coordinate\n@SQ\tSN:chr1\tLN:1000\n",
+    "no_hd": "@HD\tVN:1.6\tSO:coordinate\n" + HEADERS["no_hd"],
+}
+
+
+class Case:
+    def __init__(self, records, n_ref=3, head="so_coordinate", refuse=None):
+        self.records, self.n_ref = list(records), n_ref
+        self.header = header(HEADERS[head], refs(n_ref))
+        # None, or (when, record number, kind): when = "sort" (sort or index), "index" (index only) or "order" (index without sort)
+        self.refuse = refuse
+
+
+def _shuffled(n, seed, n_ref=3, with_no_coor=True):
+    rnd = random.Random(seed)
+    out = []
+    for i in range(n):
+        tid = rnd.randrange(-1 if with_no_coor else 0, n_ref)
+        pos = rnd.randrange(0, 200000) if tid >= 0 else -1
+        flag = rnd.choice((0, 16, 0x41, 0x91)) | (4 if tid < 0 else 0)
+        out.append(rec("r%d" % i, tid, pos, flag, [(M, rnd.randrange(1, 150))] if tid >= 0 else ()))
+    return out
+
+
+def _cases():
+    c = {}
+    for n in (0, 1, 63, 64, 65, TILE - 1, TILE, TILE + 1):
+        c["n%d" % n] = Case(_shuffled(n, 100 + n))
+    c["all_keys_equal"] = Case([rec("same%03d" % i, 1, 500, 0, [(M, 50)]) for i in range(130)])
+    c["forward_and_reverse"] = Case([rec("fr%d" % i, 0, 1000, 16 if i % 3 else 0, [(M, 30)]) for i in range(20)])
+    wide = []
+    rnd = random.Random(7)
+    for i in range(200):
+        tid = (0, 255, 256, 299, -1)[i % 5]
+        wide.append(rec("w%d" % i, tid, rnd.randrange(0, 5000) if tid >= 0 else -1, 4 if tid < 0 else 0, [(M, 10)] if tid >= 0 else ()))
+    c["n_ref_300"] = Case(wide, n_ref=300)
+    edges = [0, 126, 127, 255, 256, 65535, 65536, (1 << 24) - 1, 1 << 24]
+    c["digit_edges"] = Case([rec("e%d_%d" % (p, k), k % 2, p, 16 * (k & 1), [(M, 5)]) for k in range(3) for p in reversed(edges)])
+    c["end_at_2_29"] = Case([rec("last", 0, BAI_END - 10, 0, [(M, 10)]), rec("first", 0, 5, 0, [(M, 10)])])
+    c["end_beyond_2_29"] = Case([rec("ok", 0, 5, 0, [(M, 10)]), rec("beyond", 0, BAI_END - 10, 0, [(M, 11)])],
+                                refuse=("index", 2, KIND_BEYOND))
+    c["cigars"] = Case([
+        rec("none", 0, 70000),
+        rec("ishp", 0, 60000, 0, [(S, 5), (I, 10), (H, 3), (P, 2)]),
+        rec("mix", 0, 50000, 0, [(M, 10), (D, 5), (N, 1000), (EQ, 7), (X, 3), (I, 4), (S, 2)]),
+        rec("placeholder", 0, 40000, 0, [(S, 100), (N, 30000)]),
+        rec("thousand", 0, 30000, 0, [((M, D, I, N)[k % 4], 1 + k % 7) for k in range(1000)]),
+        rec("unmapped_placed", 0, 20000, 4, [(M, 5000)]),
+        rec("across_16k", 1, 16384 - 10, 0, [(M, 20)]),
+        rec("across_level1", 1, (1 << 17) - 5, 16, [(M, 10)]),
+        rec("nocoor", -1, -1, 4),
+    ])
+    c["long_record"] = Case([rec("long", 1, 300, 0, [(M, 10)], size=70000)] + [rec("s%d" % i, 0, 900 - i, 0, [(M, 10)]) for i in range(40)])
+    # Ten records of 6 528 bytes are one member's 65 280 exactly.  They have the lowest keys, so in sorted order they stand right
+    # behind the header's member and fill one member to its last byte; the short ones, handed over first, follow in the next.
+    # member_edge_last: nothing follows, the full member is the file's last and its last record ends where the members end.
+    full = [rec("full%d" % i, 0, 1000 - i, 0, [(M, 10)], size=6528) for i in range(10)]
+    c["member_edge"] = Case([rec("z%d" % i, 2, 10 + i, 0, [(M, 10)]) for i in range(5)] + full[:5]
+                            + [rec("a%d" % i, 1, 50 - i, 0, [(M, 10)]) for i in range(5)] + full[5:])
+    c["member_edge_last"] = Case(full)
+    c["three_members"] = Case([rec("t%d" % i, i % 3, (i * 7919) % 100000, 16 * (i & 1), [(M, 40)], size=150) for i in range(1500)])
+    c["refuse_tid"] = Case([rec("a", 0, 5, 0, [(M, 5)]), rec("b", 1, 5, 0, [(M, 5)]), rec("badtid", 3, 5, 0, [(M, 5)])],
+                           refuse=("sort", 3, KIND_TID))
+    c["refuse_pos"] = Case([rec("a", 0, 5, 0, [(M, 5)]), rec("negpos", 1, -5, 0, [(M, 5)])], refuse=("sort", 2, KIND_POS))
+    lying = bytearray(rec("lying", 0, 7, 0, [(M, 5)]))
+    struct.pack_into("<H", lying, 16, 1000)          # n_cigar_op: 4 000 bytes of CIGAR in a record of 50
+    c["refuse_record"] = Case([bytes(lying), rec("a", 0, 5, 0, [(M, 5)])], refuse=("sort", 1, KIND_RECORD))
+    c["unsorted_bai_alone"] = Case([rec("a", 0, 100, 0, [(M, 5)]), rec("b", 0, 200, 0, [(M, 5)]), rec("c", 0, 150, 0, [(M, 5)]),
+                                    rec("d", 1, 5, 0, [(M, 5)])], refuse=("order", 3, KIND_KEY_BACK))
+    for head in HEADERS:
+        c["header_" + head] = Case(_shuffled(10, 5), head=head)
+    return c
+
+
+CASES = _cases()
+SORTABLE = sorted(name for name, case in CASES.items() if case.refuse is None or case.refuse[0] != "sort")
+INDEXABLE = sorted(name for name, case in CASES.items() if case.refuse is None)
+
+
+def single_pass_case():
+    """keys that differ in one 8-bit digit only: tid 0, forward, pos 0 .. 126"""
+    rnd = random.Random(11)
+    return Case([rec("p%d" % i, 0, rnd.randrange(0, 127), 0, [(M, 3)]) for i in range(TILE + 77)], n_ref=1)
+
+
+def every_digit_case():
+    """keys that differ in every byte, so no digit can be skipped: positions spread to 2^29 fill bytes 0 .. 3, and tid' << 33 fills
+    bytes 4 .. 7 with reference ids spread over a large n_ref (tid = -1, which becomes n_ref, among them)"""
+    rnd = random.Random(12)
+    n_ref = (1 << 30) + (1 << 23) + (1 << 15) + 1        # tid' << 33 reaches bytes 4 .. 7
+    records = []
+    for i in range(2 * TILE + 5):
+        tid = rnd.choice((0, n_ref - 1, (1 << 23) + 77, (1 << 15) + 3, 255, -1))
+        pos = rnd.randrange(0, BAI_END - 200) if tid >= 0 else -1
+        records.append(rec("d%d" % i, tid, pos, 16 * (i & 1) | (4 if tid < 0 else 0), [(M, 100)] if tid >= 0 else ()))
+    case = Case([], n_ref=1)
+    case.records, case.n_ref = records, n_ref            # (the header keeps one reference: only n_ref goes to the rule)
+    return case
+
+
+# ------------------------------------------------------------------------------------------ the rule
+def span(raw, n_ref):
+    """(key, tid, beg, end, flags) of the record `raw` (its block_size field included)"""
+    bad = (0, 0, 0, 0, BAD | BAD_RECORD)
+    if len(raw) < 36 or len(raw) - 4 > 0x7FFFFFFF or struct.unpack_from("<I", raw, 0)[0] != len(raw) - 4:
+        return bad
+    tid, pos, l_name, _mapq, _bin, n_cigar, flag = struct.unpack_from("<iiBBHHH", raw, 4)
+    if 36 + l_name + 4 * n_cigar > len(raw):
+        return bad
+    if tid >= n_ref or tid < -1:
+        return (0, tid, 0, 0, BAD | BAD_TID)
+    if pos < -1 or (pos < 0 and tid >= 0):
+        return (0, tid, 0, 0, BAD | BAD_POS)
+    flags = UNMAPPED if flag & 4 else 0
+    key = (n_ref if tid < 0 else tid) << 33 | (pos + 1) << 1 | (flag >> 4 & 1)
+    if tid < 0:
+        return (key, tid, 0, 0, flags | NO_COOR)
+    ref_len = 0
+    if not flag & 4:
+        for k in range(n_cigar):
+            c = struct.unpack_from("<I", raw, 36 + l_name + 4 * k)[0]
+            if c & 15 in (M, D, N, EQ, X):
+                ref_len += c >> 4
+    end = pos + (ref_len or 1)
+    if end > BAI_END:
+        flags |= BEYOND
+    return (key, tid, pos, min(end, 0xFFFFFFFF), flags)
+
+
+def table(header_len, records, n_ref):
+    """rows (off, len, key, tid, beg, end, flags) of `records` lying side by side behind a header of header_len bytes"""
+    rows, at = [], header_len
+    for raw in records:
+        rows.append((at, len(raw)) + span(raw, n_ref))
+        at += len(raw)
+    return rows
+
+
+def keys(records, n_ref):
+    return [span(raw, n_ref)[0] for raw in records]
+
+
+def order(records, n_ref):
+    ks = keys(records, n_ref)
+    return sorted(range(len(records)), key=lambda i: (ks[i], i))
+
+
+def first_bad(records, n_ref):
+    for i, raw in enumerate(records):
+        f = span(raw, n_ref)[4]
+        if f & BAD:
+            return i + 1, KIND_TID if f & BAD_TID else KIND_POS if f & BAD_POS else KIND_RECORD
+    return 0, 0
+
+
+def coordinate_header(head):
+    """the header rule: SO:coordinate in the @HD line"""
+    l_text = struct.unpack_from("<i", head, 4)[0]
+    text, rest = head[8:8 + l_text].decode("ascii"), head[8 + l_text:]
+    lines = text.split("\n")
+    if lines[0].split("\t")[0] == "@HD":
+        fields = lines[0].split("\t")
+        if "SO:coordinate" in fields:
+            return head
+        if any(f.startswith("SO:") for f in fields[1:]):
+            fields = [("SO:coordinate" if f.startswith("SO:") and i else f) for i, f in enumerate(fields)]
+        else:
+            fields.append("SO:coordinate")
+        lines[0] = "\t".join(fields)
+        text = "\n".join(lines)
+    else:
+        text = "@HD\tVN:1.6\tSO:coordinate\n" + text
+    t = text.encode("ascii")
+    return head[:4] + struct.pack("<i", len(t)) + t + rest
+
+
+# ------------------------------------------------------------------------------------------ members
+def payloads(head, records):
+    """the payloads of the members a writer makes of `head` flushed and `records` handed to write_record one by one"""
+    out, buf = [], bytearray(head)
+    while len(buf) >= PAYLOAD:
+        out.append(bytes(buf[:PAYLOAD]))
+        del buf[:PAYLOAD]
+    if buf:
+        out.append(bytes(buf))
+        buf = bytearray()
+    for raw in records:
+        if buf and len(buf) + len(raw) > PAYLOAD:
+            out.append(bytes(buf))
+            buf = bytearray()
+        buf += raw
+        while len(buf) >= PAYLOAD:
+            out.append(bytes(buf[:PAYLOAD]))
+            del buf[:PAYLOAD]
+    if buf:
+        out.append(bytes(buf))
+    return out
+
+
+EOF = bytes.fromhex("1f8b08040000000000ff0600424302001b0003000000000000000000")
+
+
+def members(data):
+    """[(file offset, payload)] of the BGZF file `data`, the EOF member left out; every member inflated here and its CRC checked"""
+    out, at = [], 0
+    while at < len(data):
+        assert data[at:at + 4] == b"\x1f\x8b\x08\x04" and data[at + 12:at + 16] == b"BC\x02\0", "not a BGZF member at %d" % at
+        size = struct.unpack_from("<H", data, at + 16)[0] + 1
+        payload = zlib.decompress(data[at + 18:at + size - 8], -15)
+        crc, isize = struct.unpack_from("<II", data, at + size - 8)
+        assert zlib.crc32(payload) & 0xFFFFFFFF == crc and len(payload) == isize
+        out.append((at, payload))
+        at += size
+    assert data.endswith(EOF) and out and out[-1][1] == b"", "no EOF member"
+    return out[:-1]
+
+
+class Written:
+    """a BAM file as written: its header, its records in file order, and the map between virtual offsets and the stream"""
+
+    def __init__(self, data):
+        self.size = len(data)
+        self.members = members(data)
+        self.stream = b"".join(p for _off, p in self.members)
+        self.starts = []
+        at = 0
+        for _off, p in self.members:
+            self.starts.append(at)
+            at += len(p)
+        s = self.stream
+        assert s[:4] == b"BAM\1"
+        l_text = struct.unpack_from("<i", s, 4)[0]
+        self.text = s[8:8 + l_text].decode("ascii")
+        self.n_ref = struct.unpack_from("<i", s, 8 + l_text)[0]
+        at = 12 + l_text
+        for _ in range(self.n_ref):
+            at += 8 + struct.unpack_from("<i", s, at)[0]
+        self.header = s[:at]
+        self.records, self.offsets = [], []
+        while at < len(s):
+            size = 4 + struct.unpack_from("<i", s, at)[0]
+            self.offsets.append(at)
+            self.records.append(s[at:at + size])
+            at += size
+        assert at == len(s)
+        self.rows = [span(raw, self.n_ref) for raw in self.records]      # (key, tid, beg, end, flags) per record
+        self.end_of_members = self.members[-1][0] + self._member_size(data, self.members[-1][0]) if self.members else 0
+
+    @staticmethod
+    def _member_size(data, at):
+        return struct.unpack_from("<H", data, at + 16)[0] + 1
+
+    def position(self, voff):
+        """where virtual offset `voff` points in the stream, or None where it points at nothing"""
+        coff, uoff = voff >> 16, voff & 0xFFFF
+        if coff == self.end_of_members and uoff == 0:
+            return len(self.stream)
+        for k, (off, p) in enumerate(self.members):
+            if off == coff:
+                return self.starts[k] + uoff if uoff <= len(p) else None
+        return None
+
+    def voffset(self, pos):
+        """the virtual offset of stream position `pos`: in the member that holds the byte, the end of the members behind the last"""
+        for k in range(len(self.members) - 1, -1, -1):
+            if self.starts[k] <= pos < self.starts[k] + len(self.members[k][1]):
+                return self.members[k][0] << 16 | (pos - self.starts[k])
+        return self.end_of_members << 16
+
+
+# ------------------------------------------------------------------------------------------ the index
+def reg2bin(beg, end):
+    end -= 1
+    for shift, first in ((14, 4681), (17, 585), (20, 73), (23, 9), (26, 1)):
+        if beg >> shift == end >> shift:
+            return first + (beg >> shift)
+    return 0
+
+
+def reg2bins(beg, end):
+    end -= 1
+    bins = [0]
+    for shift, first in ((26, 1), (23, 9), (20, 73), (17, 585), (14, 4681)):
+        bins.extend(range(first + (beg >> shift), first + (end >> shift) + 1))
+    return bins
+
+
+def build_bai(w):
+    """the .bai of the Written file `w`, by the rule of the issue: one chunk per run of consecutive records with one bin"""
+    per_ref = [dict(bins={}, linear=[], n=0, unmapped=0, first=0, last=0, last_bin=None) for _ in range(w.n_ref)]
+    no_coor = 0
+    for raw, at in zip(w.records, w.offsets):
+        _key, tid, beg, end, flags = span(raw, w.n_ref)
+        assert not flags & (BAD | BEYOND)
+        if flags & NO_COOR:
+            no_coor += 1
+            continue
+        r = per_ref[tid]
+        s, e = w.voffset(at), w.voffset(at + len(raw))
+        b = reg2bin(beg, end)
+        if b == r["last_bin"]:
+            r["bins"][b][-1][1] = e
+        else:
+            r["bins"].setdefault(b, []).append([s, e])
+        r["last_bin"] = b
+        while len(r["linear"]) <= (end - 1) >> 14:
+            r["linear"].append(None)
+        for win in range(beg >> 14, ((end - 1) >> 14) + 1):
+            if r["linear"][win] is None or s < r["linear"][win]:
+                r["linear"][win] = s
+        if not r["n"]:
+            r["first"] = s
+        r["last"] = e
+        r["n"] += 1
+        r["unmapped"] += bool(flags & UNMAPPED)
+    out = b"BAI\1" + struct.pack("<i", w.n_ref)
+    for r in per_ref:
+        if not r["n"]:
+            out += struct.pack("<ii", 0, 0)
+            continue
+        out += struct.pack("<i", len(r["bins"]) + 1)
+        for b in sorted(r["bins"]):
+            out += struct.pack("<Ii", b, len(r["bins"][b])) + b"".join(struct.pack("<QQ", s, e) for s, e in r["bins"][b])
+        out += struct.pack("<IiQQQQ", 37450, 2, r["first"], r["last"], r["n"] - r["unmapped"], r["unmapped"])
+        lin = r["linear"]
+        for win in range(len(lin) - 2, -1, -1):
+            if lin[win] is None:
+                lin[win] = lin[win + 1]
+        out += struct.pack("<i", len(lin)) + b"".join(struct.pack("<Q", v) for v in lin)
+    return out + struct.pack("<Q", no_coor)
+
+
+def read_bai(data):
+    """{"refs": [{"bins": {bin: [(beg, end)]}, "pseudo": None | [(..), (..)], "linear": [...]}], "no_coor": n}; the whole of `data` is used"""
+    assert data[:4] == b"BAI\1", "no BAI magic"
+    n_ref = struct.unpack_from("<i", data, 4)[0]
+    at, out = 8, []
+    for _ in range(n_ref):
+        n_bin = struct.unpack_from("<i", data, at)[0]
+        at += 4
+        bins, pseudo = {}, None
+        for _ in range(n_bin):
+            b, n_chunk = struct.unpack_from("<Ii", data, at)
+            at += 8
+            chunks = [struct.unpack_from("<QQ", data, at + 16 * k) for k in range(n_chunk)]
+            at += 16 * n_chunk
+            if b == 37450:
+                assert pseudo is None and n_chunk == 2
+                pseudo = chunks
+            else:
+                assert b not in bins and b < 37449 and n_chunk > 0
+                bins[b] = chunks
+        n_intv = struct.unpack_from("<i", data, at)[0]
+        at += 4
+        linear = list(struct.unpack_from("<%dQ" % n_intv, data, at))
+        at += 8 * n_intv
+        out.append(dict(bins=bins, pseudo=pseudo, linear=linear))
+    no_coor = struct.unpack_from("<Q", data, at)[0]
+    assert at + 8 == len(data), "bytes behind n_no_coor, or none of it"
+    return dict(refs=out, no_coor=no_coor)
+
+
+def check_structure(bai, w):
+    """`bai` (read_bai) against the Written file `w`: references, chunks ascending, inside the file and starting at record starts,
+    bins that can hold their records, pseudo-bins and n_no_coor equal to a scan's counts"""
+    assert len(bai["refs"]) == w.n_ref
+    starts = set(w.offsets)
+    rows = w.rows
+    assert bai["no_coor"] == sum(1 for r in rows if r[4] & NO_COOR)
+    for tid, ref in enumerate(bai["refs"]):
+        mine = [(r, at, len(raw)) for r, at, raw in zip(rows, w.offsets, w.records) if r[1] == tid and not r[4] & NO_COOR]
+        if not mine:
+            assert not ref["bins"] and ref["pseudo"] is None and not ref["linear"], "a reference without records has n_bin = 0, n_intv = 0"
+            continue
+        for b, chunks in ref["bins"].items():
+            last_end = 0
+            for beg, end in chunks:
+                assert beg < end and beg >= last_end, "chunks of bin %d do not ascend" % b
+                last_end = end
+                pb, pe = w.position(beg), w.position(end)
+                assert pb is not None and pe is not None and pb in starts, "a chunk of bin %d does not start at a record" % b
+                assert pe in starts or pe == len(w.stream), "a chunk of bin %d does not end at a record's end" % b
+                assert end >> 16 <= w.end_of_members
+        unmapped = sum(1 for r, _at, _n in mine if r[4] & UNMAPPED)
+        (first, last), (n_mapped, n_unmapped) = ref["pseudo"]
+        assert (n_mapped, n_unmapped) == (len(mine) - unmapped, unmapped)
+        assert w.position(first) == mine[0][1] and w.position(last) == mine[-1][1] + mine[-1][2]
+        assert len(ref["linear"]) == max(((r[3] - 1) >> 14) + 1 for r, _at, _n in mine)
+        for v in ref["linear"]:
+            assert w.position(v) in starts, "a linear-index entry is no record start"
+
+
+def scan(w, tid, beg, end):
+    return [at for (_key, t, b, e, flags), at in zip(w.rows, w.offsets) if t == tid and not flags & NO_COOR and b < end and e > beg]
+
+
+def query(bai, w, tid, beg, end):
+    """the record starts the index leads to for [beg, end) on `tid`"""
+    ref = bai["refs"][tid]
+    lin = ref["linear"]
+    min_off = 0 if not lin else lin[beg >> 14] if beg >> 14 < len(lin) else lin[-1]
+    found = set()
+    index_of = {at: i for i, at in enumerate(w.offsets)}
+    for b in reg2bins(beg, min(end, BAI_END)):
+        for cb, ce in ref["bins"].get(b, ()):
+            if ce <= min_off:
+                continue
+            i, stop = index_of[w.position(cb)], w.position(ce)
+            while i < len(w.offsets) and w.offsets[i] < stop:
+                _key, t, rb, re_, flags = w.rows[i]
+                if t == tid and not flags & NO_COOR and rb < end and re_ > beg:
+                    found.add(w.offsets[i])
+                i += 1
+    return sorted(found)
+
+
+def regions(w, seed=1):
+    """(tid, beg, end): every 16 kb and bin edge next to a record, +-1, and 200 seeded random ones"""
+    out = set()
+    rnd = random.Random(seed)
+    rows = [r for r in w.rows if not r[4] & (NO_COOR | BAD)]
+    for _key, tid, beg, end, _flags in rows:
+        for shift in (14, 17, 20, 23, 26):
+            for edge in {beg >> shift << shift, (beg >> shift) + 1 << shift, (end - 1) >> shift << shift, ((end - 1) >> shift) + 1 << shift}:
+                for lo in (edge - 1, edge, edge + 1):
+                    if 0 <= lo < BAI_END:
+                        out.add((tid, lo, lo + 1))
+                        out.add((tid, max(lo - 100, 0), lo + 1))
+        out.add((tid, beg, end))
+        out.add((tid, max(beg - 1, 0), beg))
+        out.add((tid, end, end + 1))
+    if len(out) > 1000:                                  # (a large case: a seeded sample of the edges, the random ones on top)
+        out = set(rnd.sample(sorted(out), 1000))
+    tids = sorted({r[1] for r in rows}) or [0]
+    top = max([r[3] for r in rows] or [1]) + 20000
+    more = set()
+    while len(more) < 200:
+        tid, lo = rnd.choice(tids), rnd.randrange(0, top)
+        more.add((tid, lo, lo + rnd.choice((1, 10, 1000, 20000, 1 << 18))))
+    return sorted(out | more)
+
+
+def check_queries(bai, w, seed=1):
+    n = 0
+    for tid, beg, end in regions(w, seed):
+        assert query(bai, w, tid, beg, end) == scan(w, tid, beg, end), "region %d:%d-%d" % (tid, beg, end)
+        n += 1
+    return n
