@@ -1,5 +1,5 @@
 """Text output as BGZF (`--bgzf`: a .vcf.gz that bcftools, tabix and IGV read as a stream; with `sort=True, index="tbi"` one they
-can query by region): a text file-like object over bam.BgzfWriter.
+can query by region): a text file-like object over bgzf.BgzfWriter.
 
     out = open_text("calls.vcf.gz", deflate="device")
     sso_genotype(bam, vcf_in, out, ...)
@@ -20,11 +20,8 @@ from __future__ import annotations
 
 import io
 import os
-import struct
 
-from .bam import BGZF_EOF, BgzfWriter
-
-_PAYLOAD = 0xff00       # bam.BgzfWriter's payload per member
+from .bgzf import PAYLOAD, BgzfWriter, close_held
 
 
 class VcfOrderError(ValueError):
@@ -33,29 +30,6 @@ class VcfOrderError(ValueError):
     def __init__(self, message: str, line: int):
         super().__init__(message)
         self.line = line
-
-
-class _MemberLog:
-    """a binary file that notes where every BGZF member written to it begins (each write is whole members)"""
-
-    def __init__(self, f):
-        self._f = f
-        self.offsets = [0]
-        self.starts = [0]       # where each member's payload begins in the inflated stream (its ISIZE says how long it is)
-
-    def write(self, data) -> int:
-        at, n, base = 0, len(data), self.offsets[-1]
-        while at < n and data[at:at + 28] != BGZF_EOF:
-            at += struct.unpack_from("<H", data, at + 16)[0] + 1
-            self.offsets.append(base + at)
-            self.starts.append(self.starts[-1] + struct.unpack_from("<I", data, at - 4)[0])
-        return self._f.write(data)
-
-    def flush(self):
-        self._f.flush()
-
-    def close(self):
-        self._f.close()
 
 
 class BgzfTextWriter:
@@ -71,8 +45,6 @@ class BgzfTextWriter:
         self.closed = False
         self._sort, self._index, self._index_path = bool(sort), index, index_path
         self._held = [] if (sort or index) else None     # the whole text, until close()
-        if self._held is not None:
-            self._log = writer._f = _MemberLog(writer._f)
 
     def write(self, text: str) -> int:
         if self.closed:
@@ -103,50 +75,49 @@ class BgzfTextWriter:
                 self._close_held()
 
     def _close_held(self) -> None:
-        """the held text as one piece: line table, order, members, index"""
+        """the held text as one piece: line table, order, members, index -- what bgzf.close_held asks of its writer"""
         import numpy as np
 
         from . import native_reads as nr
-        w = self._writer
         text = b"".join(self._held)
         self._held = []
-        if self._index_path is not None and os.path.exists(self._index_path):
-            os.remove(self._index_path)                 # (an index of an earlier file is not left beside this one)
         if self._sort and text and not text.endswith(b"\n"):
             text += b"\n"                               # (a last line that moves takes a newline with it)
-        try:
+
+        def members(w, text=text):
+            """-> (a text, the table of the lines as written, where each lies in that text: None = where the table says)"""
             if w._deflate == "device":
-                members, _off, lines, src_off, bad = nr.vcf_bgzf_device(text, self._sort, w._huffman, w._device)
+                made, _off, lines, src_off, bad = nr.vcf_bgzf_device(text, self._sort, w._huffman, w._device)
                 if bad:
                     raise self._order_error(text, nr.vcf_lines(text), bad, nr.TBX_NOT_DATA)
-                w._f.write(members.tobytes())
-            else:
-                lines, src_off = nr.vcf_lines(text), None
-                if self._sort:
-                    perm, bad = nr.vcf_sort_order(text, lines)
-                    if bad:
-                        raise self._order_error(text, lines, bad, nr.TBX_NOT_DATA)
-                    text = nr.vcf_gather(text, lines, perm)
-                    lines = lines[perm]
-                    lines["off"] = np.cumsum(lines["len"]) - lines["len"]
-                for at in range(0, len(text), _PAYLOAD):
-                    w.write(text[at:at + _PAYLOAD])
-                w.flush()
-                w.drain()
-        finally:
-            w.close()
-        if self._index is None:
-            return
-        member_off = np.array(self._log.offsets, np.uint64)
-        tbi, bad, kind = nr.tbx_build(text, lines, member_off, src_off)
-        if bad:
+                w._f.write(made.tobytes())
+                return text, lines, src_off
+            lines = nr.vcf_lines(text)
+            if self._sort:
+                perm, bad = nr.vcf_sort_order(text, lines)
+                if bad:
+                    raise self._order_error(text, lines, bad, nr.TBX_NOT_DATA)
+                text = nr.vcf_gather(text, lines, perm)
+                lines = lines[perm]
+                lines["off"] = np.cumsum(lines["len"]) - lines["len"]
+            for at in range(0, len(text), PAYLOAD):
+                w.write(text[at:at + PAYLOAD])
+            return text, lines, None
+
+        def order_error(held, bad, kind):
+            text, lines, src_off = held
             if src_off is not None:
                 lines = lines.copy()
                 lines["off"] = src_off
-            raise self._order_error(text, lines, bad, kind)
-        index = BgzfWriter(self._index_path)
-        index.write(tbi)
-        index.close()
+            return self._order_error(text, lines, bad, kind)
+
+        def write_as_bgzf(path, tbi):
+            index = BgzfWriter(path)
+            index.write(tbi)
+            index.close()
+        close_held(self._writer, self._index_path, members,
+                   self._index and (lambda held, log: nr.tbx_build(held[0], held[1], np.array(log.offsets, np.uint64), held[2])), order_error,
+                   write_as_bgzf)
 
     def _order_error(self, text, lines, bad, kind) -> VcfOrderError:
         """`lines`: a table whose `off` points into `text`"""

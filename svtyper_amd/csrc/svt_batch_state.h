@@ -111,6 +111,30 @@ struct CallStream {
     void drain() { if (s) (void)hipStreamSynchronize(s); }
 };
 
+// A CallStream whose kernels are timed: mark() records an event of the call's own on the stream, between() adds the time from one
+// mark to another once the stream has passed both.  The events go behind the deriving struct's drain(), in front of the stream's return.
+struct TimedCallStream : CallStream {
+    std::vector<hipEvent_t> marks;
+    ~TimedCallStream() { for (hipEvent_t e : marks) (void)hipEventDestroy(e); }
+    // an event recorded on the call's stream here; marks[*at] is it
+    int mark(size_t* at)
+    {
+        hipEvent_t e = nullptr;
+        HIP_TRY(hipEventCreate(&e));
+        marks.push_back(e);
+        *at = marks.size() - 1;
+        HIP_TRY(hipEventRecord(e, s));
+        return SVT_OK;
+    }
+    int between(size_t a, size_t b, double* seconds)
+    {
+        float ms = 0;
+        HIP_TRY(hipEventElapsedTime(&ms, marks[a], marks[b]));
+        *seconds += ms * 1e-3;
+        return SVT_OK;
+    }
+};
+
 template <typename T>
 int upload(T** dptr, const std::vector<T>& v, Stager& st)
 {

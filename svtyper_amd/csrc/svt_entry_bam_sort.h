@@ -1,9 +1,10 @@
 // svt_entry_bam_sort.h -- part of the single translation unit svtyper_hip.hip (included there, in order, behind
-// svt_entry_vcf_lines.h; not a stand-alone header): BAM records as spans on the device.  The stream and its table of record offsets
-// go up, svt_bam_keys_kernel writes the span table, the keys and their AND / OR per workgroup; the host combines those and names
-// the digits in which the keys differ; per digit svt_bam_histogram_kernel, svt_bam_scan_kernel and svt_bam_scatter_kernel; the
-// order comes down, the lengths in that order are prefix-summed and cut into members on the host, svt_vcf_gather_kernel writes
-// the records in that order behind the header, and the deflate kernels run over the member jobs.  C ABI: svt_bam_spans_device,
+// svt_entry_vcf_lines.h; not a stand-alone header): BAM records as spans on the device.  What is this header's: the span table
+// (keys_resident: svt_bam_keys_kernel writes spans, keys and their AND / OR per workgroup, the host combines those), the radix
+// passes over the digits in which the keys differ (sort_resident: svt_bam_histogram_kernel, svt_bam_scan_kernel and
+// svt_bam_scatter_kernel per digit), the argument checks and the caller's arrays.  What it shares lives in svt_entry_deflate.h:
+// the upload (OrderedCall::begin), the gather behind the header copy (gather_resident<svt_bam_span>), the members from
+// bsr::cut_members' boundaries (deflate_members), the marks that time the kernels.  C ABI: svt_bam_spans_device,
 // svt_bam_sort_order_device, svt_bam_sorted_bgzf_device, svt_bam_sort_last_times (include/svtyper_reads.h).
 
 extern "C++" {
@@ -11,38 +12,9 @@ extern "C++" {
 // the kernels of the calling thread's last call here, from HIP events, and the call's wall time
 static thread_local svt_bam_sort_times g_bam_sort_times;
 
-struct BamSortCall : DeflateCall {                           // (destruction order: CallStream, svt_batch_state.h)
-    DevScratch d_stream, d_rec_off, d_spans, d_keys[2], d_idx[2], d_and, d_or, d_hist, d_perm, d_dst_off, d_sorted;
-    std::vector<hipEvent_t> marks;
-    ~BamSortCall()
-    {
-        drain();
-        for (hipEvent_t e : marks) (void)hipEventDestroy(e);
-    }
-    int begin(const uint8_t* bytes, uint64_t len)
-    {
-        SVT_TRY(take());
-        SVT_TRY(d_stream.alloc(len));
-        if (len) SVT_TRY(h2d_staged(d_stream.p, bytes, len, s));
-        return SVT_OK;
-    }
-    // an event recorded on the call's stream here; marks[*at] is it
-    int mark(size_t* at)
-    {
-        hipEvent_t e = nullptr;
-        HIP_TRY(hipEventCreate(&e));
-        marks.push_back(e);
-        *at = marks.size() - 1;
-        HIP_TRY(hipEventRecord(e, s));
-        return SVT_OK;
-    }
-    int between(size_t a, size_t b, double* seconds)
-    {
-        float ms = 0;
-        HIP_TRY(hipEventElapsedTime(&ms, marks[a], marks[b]));
-        *seconds += ms * 1e-3;
-        return SVT_OK;
-    }
+struct BamSortCall : OrderedCall {                           // (svt_entry_deflate.h; destruction order: CallStream, svt_batch_state.h)
+    DevScratch d_rec_off, d_spans, d_keys[2], d_idx[2], d_and, d_or, d_hist;
+    ~BamSortCall() { drain(); }
 };
 
 // c.d_stream[0, len) and the caller's rec_off -> the span table in c.d_spans and in `table`, keys and indices in c.d_keys[0] /
@@ -197,8 +169,7 @@ static int svt_bam_sorted_bgzf_device_impl(const uint8_t* bytes, uint64_t len, c
     const auto t0 = std::chrono::steady_clock::now();
     g_bam_sort_times = svt_bam_sort_times();
     g_deflate_times = svt_deflate_times();
-    if (mode != SVT_DEFLATE_FIXED && mode != SVT_DEFLATE_DYNAMIC)
-        return fail(SVT_ERR_INVALID, "svt_bam_sorted_bgzf: mode is SVT_DEFLATE_FIXED (0) or SVT_DEFLATE_DYNAMIC (1)");
+    SVT_TRY(deflate_check_mode("svt_bam_sorted_bgzf", mode));
     if (!rec_off || !out_off || !n_members || !member_start || !bad_record || !bad_kind || (len && (!bytes || !out)) || (n && (!spans || !perm)))
         return fail(SVT_ERR_INVALID, "null argument");
     if (n_ref < 0) return fail(SVT_ERR_INVALID, "svt_bam_sorted_bgzf: n_ref is negative");
@@ -235,24 +206,8 @@ static int svt_bam_sorted_bgzf_device_impl(const uint8_t* bytes, uint64_t len, c
         if (at != len) return fail(SVT_ERR_INTERNAL, "svt_bam_sorted_bgzf: the records' lengths do not sum to the stream's");
         SVT_TRY(c.d_sorted.alloc(len));
         if (header_len) HIP_TRY(hipMemcpyAsync(c.d_sorted.p, c.d_stream.p, header_len, hipMemcpyDeviceToDevice, c.s));
-        if (n) {
-            SVT_TRY(c.d_perm.alloc(n * sizeof(uint64_t)));
-            {
-                Stager st(c.s);
-                SVT_TRY(st.copy(c.d_perm.p, perm, n * sizeof(uint64_t)));
-                SVT_TRY(upload(c.d_dst_off, dst_off, st));
-                SVT_TRY(st.finish());
-            }
-            size_t e0 = 0, e1 = 0;
-            SVT_TRY(c.mark(&e0));
-            hipLaunchKernelGGL(svt_vcf_gather_kernel<svt_bam_span>, dim3(lines_grid(((n + 63) / 64 + kLinesWaves - 1) / kLinesWaves, device)), dim3(kLinesBlock), 0,
-                               c.s, c.d_stream.as<uint8_t>(), len, c.d_spans.as<svt_bam_span>(), n, c.d_perm.as<uint64_t>(), c.d_dst_off.as<uint64_t>(), n,
-                               c.d_sorted.as<uint8_t>(), len);
-            HIP_TRY(hipGetLastError());
-            SVT_TRY(c.mark(&e1));
-            HIP_TRY(hipStreamSynchronize(c.s));
-            SVT_TRY(c.between(e0, e1, &g_bam_sort_times.gather_kernel_s));
-        }
+        SVT_TRY(gather_resident(c, c.d_stream.as<uint8_t>(), len, c.d_spans.as<svt_bam_span>(), n, perm, dst_off, c.d_sorted.as<uint8_t>(), len,
+                                &g_bam_sort_times.gather_kernel_s, device));
         d_written = c.d_sorted.as<uint8_t>();
         for (uint64_t j = 0; j < n; ++j) {
             spans[j] = table[order[j]];
@@ -265,19 +220,11 @@ static int svt_bam_sorted_bgzf_device_impl(const uint8_t* bytes, uint64_t len, c
         }
     }
     std::vector<uint64_t> start;
-    bsr::cut_members(header_len, n, [&](uint64_t j) { return spans[j].len; }, start);        // cut where bam.BgzfWriter cuts
+    bsr::cut_members(header_len, n, [&](uint64_t j) { return spans[j].len; }, start);        // cut where bgzf.BgzfWriter cuts
     const uint64_t members = start.size() - 1;
     if (members > member_capacity) return fail(SVT_ERR_INVALID, "svt_bam_sorted_bgzf: member_capacity is below the number of members");
-    if (members > 0xFFFFFFFFull) return fail(SVT_ERR_INVALID, "svt_bam_sorted_bgzf: too many members in one call (< 2^32)");
-    std::vector<crc::Job> jobs(members);
-    uint64_t slots = 0;
-    for (uint64_t k = 0; k < members; ++k) {
-        jobs[k] = crc::Job{start[k], (uint32_t)(start[k + 1] - start[k]), 0};
-        slots += dfl::slot_bytes(jobs[k].len);
-        member_start[k] = start[k];
-    }
-    member_start[members] = start[members];
-    SVT_TRY(deflate_resident(c, d_written, len, jobs, slots, out, capacity, out_off, mode, device));
+    std::memcpy(member_start, start.data(), start.size() * sizeof(uint64_t));
+    SVT_TRY(deflate_members(c, "svt_bam_sorted_bgzf", d_written, start.data(), members, out, capacity, out_off, mode, device));
     *n_members = members;
     g_bam_sort_times.total_s = g_deflate_times.total_s = seconds_since(t0);
     return SVT_OK;
@@ -306,11 +253,4 @@ int svt_bam_sorted_bgzf_device(const uint8_t* bytes, uint64_t len, const uint64_
     });
 }
 
-int svt_bam_sort_last_times(svt_bam_sort_times* times)
-{
-    return guarded([&]() -> int {
-        if (!times) return fail(SVT_ERR_INVALID, "null argument");
-        *times = g_bam_sort_times;
-        return SVT_OK;
-    });
-}
+int svt_bam_sort_last_times(svt_bam_sort_times* times) { return guarded([&] { return last_times(times, g_bam_sort_times); }); }

@@ -1,7 +1,9 @@
 // svt_entry_vcf_lines.h -- part of the single translation unit svtyper_hip.hip (included there, in order, behind
-// svt_entry_deflate.h; not a stand-alone header): VCF text as lines on the device.  The text goes up, svt_vcf_count_kernel counts
-// its newlines per tile, the counts come down for a prefix sum on the host, svt_vcf_starts_kernel and svt_vcf_parse_kernel write
-// the line table; svt_vcf_gather_kernel writes the lines in another order.  C ABI: svt_vcf_lines_device, svt_vcf_gather_device,
+// svt_entry_deflate.h; not a stand-alone header): VCF text as lines on the device.  What is this header's: the line table
+// (lines_resident: svt_vcf_count_kernel counts newlines per tile, the counts come down for a prefix sum on the host,
+// svt_vcf_starts_kernel and svt_vcf_parse_kernel write the table), the argument checks and the caller's arrays.  What it shares
+// lives in svt_entry_deflate.h: the upload (OrderedCall::begin), the gather (gather_resident<svt_tbx_line>), the members cut every
+// dfl::kMaxPayload bytes (deflate_members), the marks that time the kernels.  C ABI: svt_vcf_lines_device, svt_vcf_gather_device,
 // svt_vcf_bgzf_device (table, order, gather and the deflate kernels over one upload), svt_vcf_lines_last_times
 // (include/svtyper_reads.h).
 
@@ -10,32 +12,12 @@ extern "C++" {
 // the kernels of the calling thread's last call here, from HIP events, and the call's wall time
 static thread_local svt_vcf_lines_times g_lines_times;
 
-struct LinesCall : DeflateCall {                             // (destruction order: CallStream, svt_batch_state.h)
-    DevScratch d_text, d_counts, d_base, d_lines, d_perm, d_dst_off, d_sorted;
-    hipEvent_t lev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    ~LinesCall()
-    {
-        drain();
-        for (hipEvent_t e : lev) if (e) (void)hipEventDestroy(e);
-    }
-    int begin(const uint8_t* text, uint64_t len)
-    {
-        SVT_TRY(take());
-        for (hipEvent_t& e : lev) HIP_TRY(hipEventCreate(&e));
-        SVT_TRY(d_text.alloc(len));
-        Stager st(s);
-        if (len) SVT_TRY(st.copy(d_text.p, text, len));
-        return st.finish();
-    }
+struct LinesCall : OrderedCall {                             // (svt_entry_deflate.h; destruction order: CallStream, svt_batch_state.h)
+    DevScratch d_counts, d_base, d_lines;
+    ~LinesCall() { drain(); }
 };
 
-static unsigned lines_grid(uint64_t work_groups, int device)
-{
-    const uint64_t most = (uint64_t)std::max<uint32_t>(cu_count(device), 1) * 8;
-    return (unsigned)std::max<uint64_t>(std::min(work_groups, most), 1);
-}
-
-// c.d_text[0, len) -> its line table in c.d_lines and in `table`; `last` is the text's last byte
+// c.d_stream[0, len) -> its line table in c.d_lines and in `table`; `last` is the text's last byte
 static int lines_resident(LinesCall& c, uint64_t len, uint8_t last, std::vector<svt_tbx_line>& table, int device)
 {
     table.clear();
@@ -43,10 +25,11 @@ static int lines_resident(LinesCall& c, uint64_t len, uint8_t last, std::vector<
     const uint64_t n_tiles = (len + tbx::kTile - 1) / tbx::kTile;
     const unsigned grid = lines_grid((n_tiles + kLinesWaves - 1) / kLinesWaves, device);
     SVT_TRY(c.d_counts.alloc(n_tiles * sizeof(uint32_t)));
-    HIP_TRY(hipEventRecord(c.lev[0], c.s));
-    hipLaunchKernelGGL(svt_vcf_count_kernel, dim3(grid), dim3(kLinesBlock), 0, c.s, c.d_text.as<uint8_t>(), len, n_tiles, c.d_counts.as<uint32_t>());
+    size_t e[5] = {};
+    SVT_TRY(c.mark(&e[0]));
+    hipLaunchKernelGGL(svt_vcf_count_kernel, dim3(grid), dim3(kLinesBlock), 0, c.s, c.d_stream.as<uint8_t>(), len, n_tiles, c.d_counts.as<uint32_t>());
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(c.lev[1], c.s));
+    SVT_TRY(c.mark(&e[1]));
     std::vector<uint32_t> counts(n_tiles);
     SVT_TRY(d2h_staged(counts.data(), c.d_counts.p, n_tiles * sizeof(uint32_t), c.s));
     std::vector<uint64_t> base(n_tiles);
@@ -64,24 +47,20 @@ static int lines_resident(LinesCall& c, uint64_t len, uint8_t last, std::vector<
         SVT_TRY(upload(c.d_base, base, st));
         SVT_TRY(st.finish());
     }
-    HIP_TRY(hipEventRecord(c.lev[2], c.s));
-    hipLaunchKernelGGL(svt_vcf_starts_kernel, dim3(grid), dim3(kLinesBlock), 0, c.s, c.d_text.as<uint8_t>(), len, n_tiles, c.d_base.as<uint64_t>(),
+    SVT_TRY(c.mark(&e[2]));
+    hipLaunchKernelGGL(svt_vcf_starts_kernel, dim3(grid), dim3(kLinesBlock), 0, c.s, c.d_stream.as<uint8_t>(), len, n_tiles, c.d_base.as<uint64_t>(),
                        c.d_lines.as<svt_tbx_line>(), n_lines);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(c.lev[3], c.s));
+    SVT_TRY(c.mark(&e[3]));
     hipLaunchKernelGGL(svt_vcf_parse_kernel, dim3(lines_grid((n_lines + kLinesBlock - 1) / kLinesBlock, device)), dim3(kLinesBlock), 0, c.s,
-                       c.d_text.as<uint8_t>(), len, c.d_lines.as<svt_tbx_line>(), n_lines);
+                       c.d_stream.as<uint8_t>(), len, c.d_lines.as<svt_tbx_line>(), n_lines);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(c.lev[4], c.s));
+    SVT_TRY(c.mark(&e[4]));
     table.resize(n_lines);
     SVT_TRY(d2h_staged(table.data(), c.d_lines.p, n_lines * sizeof(svt_tbx_line), c.s));
-    float count_ms = 0, starts_ms = 0, parse_ms = 0;
-    HIP_TRY(hipEventElapsedTime(&count_ms, c.lev[0], c.lev[1]));
-    HIP_TRY(hipEventElapsedTime(&starts_ms, c.lev[2], c.lev[3]));
-    HIP_TRY(hipEventElapsedTime(&parse_ms, c.lev[3], c.lev[4]));
-    g_lines_times.count_kernel_s = count_ms * 1e-3;
-    g_lines_times.starts_kernel_s = starts_ms * 1e-3;
-    g_lines_times.parse_kernel_s = parse_ms * 1e-3;
+    SVT_TRY(c.between(e[0], e[1], &g_lines_times.count_kernel_s));
+    SVT_TRY(c.between(e[2], e[3], &g_lines_times.starts_kernel_s));
+    SVT_TRY(c.between(e[3], e[4], &g_lines_times.parse_kernel_s));
     // the kernels' table tiles the text or it is not theirs: what the gather and the callers rely on
     uint64_t at = 0;
     for (const svt_tbx_line& l : table) {
@@ -89,32 +68,6 @@ static int lines_resident(LinesCall& c, uint64_t len, uint8_t last, std::vector<
         at += l.len;
     }
     if (at != len) return fail(SVT_ERR_HIP, "svt_vcf_starts_kernel: the lines do not tile the text");
-    return SVT_OK;
-}
-
-// the lines `perm` of c.d_text (table c.d_lines, n lines) side by side in c.d_sorted[0, out_len); dst_off from tbx::gather_plan
-static int gather_resident(LinesCall& c, uint64_t len, uint64_t n, const uint64_t* perm, const std::vector<uint64_t>& dst_off, uint64_t out_len, int device)
-{
-    const uint64_t n_perm = dst_off.size();
-    SVT_TRY(c.d_sorted.alloc(out_len));
-    if (n_perm == 0) return SVT_OK;
-    SVT_TRY(c.d_perm.alloc(n_perm * sizeof(uint64_t)));
-    {
-        Stager st(c.s);
-        SVT_TRY(st.copy(c.d_perm.p, perm, n_perm * sizeof(uint64_t)));
-        SVT_TRY(upload(c.d_dst_off, dst_off, st));
-        SVT_TRY(st.finish());
-    }
-    HIP_TRY(hipEventRecord(c.lev[4], c.s));
-    hipLaunchKernelGGL(svt_vcf_gather_kernel<svt_tbx_line>, dim3(lines_grid(((n_perm + 63) / 64 + kLinesWaves - 1) / kLinesWaves, device)), dim3(kLinesBlock), 0, c.s,
-                       c.d_text.as<uint8_t>(), len, c.d_lines.as<svt_tbx_line>(), n, c.d_perm.as<uint64_t>(), c.d_dst_off.as<uint64_t>(), n_perm,
-                       c.d_sorted.as<uint8_t>(), out_len);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(c.lev[5], c.s));
-    HIP_TRY(hipStreamSynchronize(c.s));
-    float gather_ms = 0;
-    HIP_TRY(hipEventElapsedTime(&gather_ms, c.lev[4], c.lev[5]));
-    g_lines_times.gather_kernel_s = gather_ms * 1e-3;
     return SVT_OK;
 }
 
@@ -150,7 +103,9 @@ static int svt_vcf_gather_device_impl(const uint8_t* text, uint64_t len, const s
     SVT_TRY(c.begin(text, len));
     SVT_TRY(c.d_lines.alloc(n * sizeof(svt_tbx_line)));
     if (n) SVT_TRY(h2d_staged(c.d_lines.p, lines, n * sizeof(svt_tbx_line), c.s));
-    SVT_TRY(gather_resident(c, len, n, perm, dst_off, out_len, device));
+    SVT_TRY(c.d_sorted.alloc(out_len));
+    SVT_TRY(gather_resident(c, c.d_stream.as<uint8_t>(), len, c.d_lines.as<svt_tbx_line>(), n, perm, dst_off, c.d_sorted.as<uint8_t>(), out_len,
+                            &g_lines_times.gather_kernel_s, device));
     if (out_len) SVT_TRY(d2h_staged(out, c.d_sorted.p, out_len, c.s));
     g_lines_times.total_s = seconds_since(t0);
     return SVT_OK;
@@ -162,11 +117,8 @@ static int svt_vcf_bgzf_device_impl(const uint8_t* text, uint64_t len, int sort,
     const auto t0 = std::chrono::steady_clock::now();
     g_lines_times = svt_vcf_lines_times();
     g_deflate_times = svt_deflate_times();
-    if (mode != SVT_DEFLATE_FIXED && mode != SVT_DEFLATE_DYNAMIC)
-        return fail(SVT_ERR_INVALID, "svt_vcf_bgzf: mode is SVT_DEFLATE_FIXED (0) or SVT_DEFLATE_DYNAMIC (1)");
+    SVT_TRY(deflate_check_mode("svt_vcf_bgzf", mode));
     if (!out_off || !n_lines || !bad_line || (len && (!text || !out))) return fail(SVT_ERR_INVALID, "null argument");
-    const uint64_t n_members = (len + dfl::kMaxPayload - 1) / dfl::kMaxPayload;
-    if (n_members > 0xFFFFFFFFull) return fail(SVT_ERR_INVALID, "svt_vcf_bgzf: too many members in one call (< 2^32)");
     *n_lines = 0;
     *bad_line = 0;
     out_off[0] = 0;
@@ -180,13 +132,15 @@ static int svt_vcf_bgzf_device_impl(const uint8_t* text, uint64_t len, int sort,
     *n_lines = n;
     if (n > line_capacity) return fail(SVT_ERR_INVALID, "svt_vcf_bgzf: line_capacity is below the number of lines");
     if (!lines || !src_off) return fail(SVT_ERR_INVALID, "null argument");
-    const uint8_t* d_written = c.d_text.as<uint8_t>();
+    const uint8_t* d_written = c.d_stream.as<uint8_t>();
     if (sort) {
         std::vector<uint64_t> perm(n), dst_off;
         *bad_line = tbx::sort_order(text, table.data(), n, perm.data());
         if (*bad_line) return SVT_OK;
         if (const char* why = tbx::gather_plan(len, table.data(), n, perm.data(), n, len, dst_off)) return fail(SVT_ERR_INTERNAL, why);
-        SVT_TRY(gather_resident(c, len, n, perm.data(), dst_off, len, device));
+        SVT_TRY(c.d_sorted.alloc(len));
+        SVT_TRY(gather_resident(c, c.d_stream.as<uint8_t>(), len, c.d_lines.as<svt_tbx_line>(), n, perm.data(), dst_off, c.d_sorted.as<uint8_t>(), len,
+                                &g_lines_times.gather_kernel_s, device));
         d_written = c.d_sorted.as<uint8_t>();
         for (uint64_t j = 0; j < n; ++j) {
             lines[j] = table[perm[j]];
@@ -199,14 +153,10 @@ static int svt_vcf_bgzf_device_impl(const uint8_t* text, uint64_t len, int sort,
             src_off[j] = table[j].off;
         }
     }
-    std::vector<crc::Job> jobs(n_members);
-    uint64_t slots = 0;
-    for (uint64_t k = 0; k < n_members; ++k) {              // cut where bam.BgzfWriter cuts
-        const uint64_t at = k * dfl::kMaxPayload;
-        jobs[k] = crc::Job{at, (uint32_t)std::min<uint64_t>(dfl::kMaxPayload, len - at), 0};
-        slots += dfl::slot_bytes(jobs[k].len);
-    }
-    SVT_TRY(deflate_resident(c, d_written, len, jobs, slots, out, capacity, out_off, mode, device));
+    std::vector<uint64_t> start;                                // cut where bgzf.BgzfWriter cuts
+    for (uint64_t at = 0; at < len; at += dfl::kMaxPayload) start.push_back(at);
+    start.push_back(len);
+    SVT_TRY(deflate_members(c, "svt_vcf_bgzf", d_written, start.data(), start.size() - 1, out, capacity, out_off, mode, device));
     g_lines_times.total_s = g_deflate_times.total_s = seconds_since(t0);
     return SVT_OK;
 }
@@ -232,11 +182,4 @@ int svt_vcf_bgzf_device(const uint8_t* text, uint64_t len, int sort, uint32_t mo
     });
 }
 
-int svt_vcf_lines_last_times(svt_vcf_lines_times* times)
-{
-    return guarded([&]() -> int {
-        if (!times) return fail(SVT_ERR_INVALID, "null argument");
-        *times = g_lines_times;
-        return SVT_OK;
-    });
-}
+int svt_vcf_lines_last_times(svt_vcf_lines_times* times) { return guarded([&] { return last_times(times, g_lines_times); }); }

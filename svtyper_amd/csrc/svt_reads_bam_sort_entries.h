@@ -26,7 +26,7 @@ int svt_bam_sort_order_host(const svt_bam_span* spans, uint64_t n, uint64_t* per
     });
 }
 
-static thread_local std::vector<uint8_t> g_bai_result;
+static thread_local HeldResult g_bai_result;            // (svt_reads_vcf_entries.h)
 
 int svt_bai_build(const svt_bam_span* spans, uint64_t n, int32_t n_ref, const uint64_t* member_start, const uint64_t* member_off, uint64_t n_members,
                   uint64_t* size, uint64_t* bad_record, uint32_t* bad_kind)
@@ -34,34 +34,27 @@ int svt_bai_build(const svt_bam_span* spans, uint64_t n, int32_t n_ref, const ui
     return guarded([&]() -> int {
         if ((n && !spans) || !member_start || !member_off || !size || !bad_record || !bad_kind) return fail(SVT_ERR_INVALID, "null argument");
         if (n_ref < 0) return fail(SVT_ERR_INVALID, "svt_bai_build: n_ref is negative");
-        for (uint64_t k = 0; k < n_members; ++k) {
+        for (uint64_t k = 0; k < n_members; ++k)
             if (member_start[k + 1] < member_start[k] || member_start[k + 1] - member_start[k] > 65536)
                 return fail(SVT_ERR_INVALID, "svt_bai_build: member_start must not decrease, a member holds at most 65536 bytes");
-            if (member_off[k + 1] < member_off[k] || member_off[k + 1] >> 48) return fail(SVT_ERR_INVALID, "svt_bai_build: member_off must not decrease (< 2^48)");
-        }
+        if (const int rc = check_member_off("svt_bai_build", member_off, n_members)) return rc;
         uint64_t at = n ? spans[0].off : 0;
         if (n && at < member_start[0]) return fail(SVT_ERR_INVALID, "svt_bai_build: a record lies in front of the members");
         for (uint64_t i = 0; i < n; ++i) {            // the table of a stream as written: the records side by side
             if (spans[i].off != at || spans[i].len > member_start[n_members] - at) return fail(SVT_ERR_INVALID, "svt_bai_build: the records do not tile the stream");
             at += spans[i].len;
         }
-        g_bai_result.clear();
-        *size = 0;
         *bad_kind = 0;
-        *bad_record = svt::bai::build(spans, n, n_ref, member_start, member_off, n_members, g_bai_result, *bad_kind);
-        *size = g_bai_result.size();
+        g_bai_result.build(size, [&](std::vector<uint8_t>& bai) {
+            *bad_record = svt::bai::build(spans, n, n_ref, member_start, member_off, n_members, bai, *bad_kind);
+        });
         return SVT_OK;
     });
 }
 
 int svt_bai_take(uint8_t* out, uint64_t capacity)
 {
-    return guarded([&]() -> int {
-        if (g_bai_result.size() > capacity || (!out && !g_bai_result.empty())) return fail(SVT_ERR_INVALID, "svt_bai_take: capacity is below the result");
-        if (!g_bai_result.empty()) std::memcpy(out, g_bai_result.data(), g_bai_result.size());
-        std::vector<uint8_t>().swap(g_bai_result);
-        return SVT_OK;
-    });
+    return guarded([&] { return g_bai_result.take("svt_bai_take", out, capacity); });
 }
 
 }  // extern "C"

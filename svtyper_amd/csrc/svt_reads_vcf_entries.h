@@ -1,5 +1,31 @@
 // svt_reads_vcf_entries.h -- part of the translation unit svt_reads.cpp (included there, in order; not a stand-alone header): the
-// host entry points over VCF text as lines (svt_vcf_lines.h) and the index fold (svt_tbx_index.h).
+// host entry points over VCF text as lines (svt_vcf_lines.h) and the index fold (svt_tbx_index.h); and what that fold's entries share
+// with the .bai fold's (svt_reads_bam_sort_entries.h): the result holder and the check of member_off.
+namespace {
+
+// An index built into a thread-local buffer by a *_build entry, which reports its size; the *_take entry hands it over once and frees it.
+struct HeldResult {
+    std::vector<uint8_t> bytes;
+    template <typename Fill> void build(uint64_t* size, Fill&& fill) { bytes.clear(); *size = 0; fill(bytes); *size = bytes.size(); }
+    int take(const char* entry, uint8_t* out, uint64_t capacity)
+    {
+        if (bytes.size() > capacity || (!out && !bytes.empty())) return fail(SVT_ERR_INVALID, std::string(entry) + ": capacity is below the result");
+        if (!bytes.empty()) std::memcpy(out, bytes.data(), bytes.size());
+        std::vector<uint8_t>().swap(bytes);
+        return SVT_OK;
+    }
+};
+
+// member_off[0 .. n_members]: where the members begin in the file, as virtual offsets can say it
+int check_member_off(const char* entry, const uint64_t* member_off, uint64_t n_members)
+{
+    for (uint64_t k = 0; k < n_members; ++k)
+        if (member_off[k + 1] < member_off[k] || member_off[k + 1] >> 48) return fail(SVT_ERR_INVALID, std::string(entry) + ": member_off must not decrease (< 2^48)");
+    return SVT_OK;
+}
+
+}  // namespace
+
 extern "C" {
 
 int svt_vcf_lines_host(const uint8_t* text, uint64_t len, svt_tbx_line* lines, uint64_t capacity, uint64_t* n_lines)
@@ -37,7 +63,7 @@ int svt_vcf_sort_order(const uint8_t* text, uint64_t len, const svt_tbx_line* li
     });
 }
 
-static thread_local std::vector<uint8_t> g_tbx_result;
+static thread_local HeldResult g_tbx_result;
 
 int svt_tbx_build(const uint8_t* text, uint64_t len, const uint64_t* src_off, const svt_tbx_line* lines, uint64_t n, const uint64_t* member_off,
                   uint64_t n_members, uint32_t payload, uint64_t* size, uint64_t* bad_line, uint32_t* bad_kind)
@@ -53,25 +79,18 @@ int svt_tbx_build(const uint8_t* text, uint64_t len, const uint64_t* src_off, co
             if (src > len || lines[i].chrom_len > len - src) return fail(SVT_ERR_INVALID, "svt_tbx_build: a CHROM lies outside the text");
             at += lines[i].len;
         }
-        for (uint64_t k = 0; k < n_members; ++k)
-            if (member_off[k + 1] < member_off[k] || member_off[k + 1] >> 48) return fail(SVT_ERR_INVALID, "svt_tbx_build: member_off must not decrease (< 2^48)");
-        g_tbx_result.clear();
-        *size = 0;
+        if (const int rc = check_member_off("svt_tbx_build", member_off, n_members)) return rc;
         *bad_kind = 0;
-        *bad_line = svt::tbx::build(text, src_off, lines, n, len, member_off, n_members, payload, g_tbx_result, *bad_kind);
-        *size = g_tbx_result.size();
+        g_tbx_result.build(size, [&](std::vector<uint8_t>& tbi) {
+            *bad_line = svt::tbx::build(text, src_off, lines, n, len, member_off, n_members, payload, tbi, *bad_kind);
+        });
         return SVT_OK;
     });
 }
 
 int svt_tbx_take(uint8_t* out, uint64_t capacity)
 {
-    return guarded([&]() -> int {
-        if (g_tbx_result.size() > capacity || (!out && !g_tbx_result.empty())) return fail(SVT_ERR_INVALID, "svt_tbx_take: capacity is below the result");
-        if (!g_tbx_result.empty()) std::memcpy(out, g_tbx_result.data(), g_tbx_result.size());
-        std::vector<uint8_t>().swap(g_tbx_result);
-        return SVT_OK;
-    });
+    return guarded([&] { return g_tbx_result.take("svt_tbx_take", out, capacity); });
 }
 
 }  // extern "C"

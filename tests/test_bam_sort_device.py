@@ -78,6 +78,23 @@ def test_one_call_entry(hip_device, huffman):
     assert nr.bgzf_deflate_last_times()["deflate_kernel_s"] > 0
 
 
+def test_times_of_sorted_and_unsorted_calls(hip_device):
+    """every kernel of a call is timed between marks of its own, the sort's summed over its passes, and nothing of one call is
+    left in the next one's times on the same thread"""
+    case = B.CASES["three_members"]
+    data, rec_off = stream_of(case)
+    sort_kernels = ("histogram_kernel_s", "scan_kernel_s", "scatter_kernel_s")
+    assert nr.bam_sorted_bgzf_device(data, rec_off, case.n_ref, True, "fixed", hip_device)[5] == 0
+    times = nr.bam_sort_last_times()
+    print("sorted", times)
+    assert times["keys_kernel_s"] > 0 and times["gather_kernel_s"] > 0 and all(times[k] > 0 for k in sort_kernels) and times["passes"] >= 1
+    assert nr.bam_sorted_bgzf_device(data, rec_off, case.n_ref, False, "fixed", hip_device)[5] == 0
+    times = nr.bam_sort_last_times()
+    print("unsorted", times)
+    assert times["keys_kernel_s"] > 0 and times["passes"] == 0
+    assert times["gather_kernel_s"] == 0.0 and all(times[k] == 0.0 for k in sort_kernels)
+
+
 @pytest.mark.parametrize("huffman", ["fixed", "dynamic"])
 def test_writer_on_the_device_writes_the_hosts_files(tmp_path, hip_device, huffman):
     for k, name in enumerate(B.INDEXABLE):

@@ -76,6 +76,26 @@ def test_one_call_entry(hip_device, huffman, sort):
     assert set(times) == {"count_kernel_s", "starts_kernel_s", "parse_kernel_s", "gather_kernel_s", "total_s"} and times["count_kernel_s"] > 0
 
 
+def test_times_of_sorted_and_unsorted_calls(hip_device):
+    """every kernel of a call is timed between marks of its own (the gather's are not the parse's), and nothing of one call is
+    left in the next one's times on the same thread"""
+    text = X.ORDERS["contig_reappears"]
+    if not text.endswith(b"\n"):
+        text += b"\n"
+    assert X.sorted_text(text) != text              # (its lines really move)
+    kernels = ("count_kernel_s", "starts_kernel_s", "parse_kernel_s", "gather_kernel_s")
+    assert nr.vcf_bgzf_device(text, True, "fixed", hip_device)[4] == 0
+    times, deflate = nr.vcf_lines_last_times(), nr.bgzf_deflate_last_times()
+    print("sorted", times, deflate)
+    assert all(times[k] > 0 for k in kernels)
+    assert deflate["crc_kernel_s"] > 0 and deflate["deflate_kernel_s"] > 0 and deflate["pack_kernel_s"] > 0
+    assert times["total_s"] >= sum(times[k] for k in kernels) + deflate["crc_kernel_s"] + deflate["deflate_kernel_s"] + deflate["pack_kernel_s"]
+    assert nr.vcf_bgzf_device(text, False, "fixed", hip_device)[4] == 0
+    times = nr.vcf_lines_last_times()
+    print("unsorted", times)
+    assert times["gather_kernel_s"] == 0.0 and all(times[k] > 0 for k in kernels[:3])
+
+
 @pytest.mark.parametrize("huffman", ["fixed", "dynamic"])
 def test_writer_on_the_device_writes_the_hosts_files(tmp_path, hip_device, huffman):
     for k, name in enumerate(sorted(X.TEXTS) + sorted(X.ORDERS)):

@@ -13,7 +13,9 @@ For the device legs the kernels' own times from HIP events: the keys, sort and g
 the deflate kernels of the same call (svt_bgzf_deflate_last_times); and `host_stable_sort`: std::stable_sort of the same keys
 (svt_bam_sort_order_host) beside the device sort (svt_bam_sort_order_device, wall and kernels).  Every sorted file is checked
 against the checker of tests/baicases.py once, on the untimed runs, and device files with host files.  Prints one JSON object
-and, with --out FILE, writes it there.  GPU box only.
+and, with --out FILE, writes it there.  GPU box only.  --deflate device (a comma-separated choice of zlib,host,device; default
+all three) times those legs alone; with --package-root DIR (without --plain-only: a checkout that has the options) that is how
+one commit is measured against another in one session (profiles/held_close_ab.json).
 
 The plain legs are the code path of the commit before the options, and profiles/bam_sort_ab.json keeps them re-measured on that
 commit under `parent_commit_plain`.  Two commands make the file, PARENT being a built checkout of that commit:
@@ -45,6 +47,7 @@ def arg(name, default):
 
 reps, times, copies, out_path, device = arg("--reps", 5), arg("--times", 20), arg("--copies", 50), arg("--out", ""), arg("--device", 0)
 data = os.path.join(ROOT, "tests", "data")
+DEFLATES = tuple(arg("--deflate", "zlib,host,device").split(","))
 IN_BAM = os.path.join(data, "NA12878.target_loci.sorted.bam")
 
 
@@ -85,13 +88,13 @@ MODES = {"plain": {}, "sort": {"sort": True}, "sort_index": {"sort": True, "inde
 plain_only = "--plain-only" in sys.argv
 if plain_only:
     MODES = {"plain": {}}
-result = {"reps": reps, "times": times, "copies": copies, "device": device, "package": "another checkout (--package-root)" if "--package-root" in sys.argv else "this checkout", "plain_only": plain_only}
+result = {"reps": reps, "times": times, "copies": copies, "device": device, "package": "another checkout (--package-root)" if "--package-root" in sys.argv else "this checkout", "plain_only": plain_only, "deflates": list(DEFLATES)}
 template, fixture = dump()
 with tempfile.TemporaryDirectory() as tmp:
     path = os.path.join(tmp, "ev.bam")
     for name, records in (("bam", fixture), ("bam_x", [raw for k in range(copies) for raw in moved(fixture, k)])):
         entry = {"records": len(records), "record_bytes": sum(len(r) for r in records)}
-        legs = [(deflate, mode) for deflate in ("zlib", "host", "device") for mode in MODES]
+        legs = [(deflate, mode) for deflate in DEFLATES for mode in MODES]
         files, ok = {}, True
         n_ref = len(template.references)
         order = B.order(records, n_ref)
@@ -103,7 +106,8 @@ with tempfile.TemporaryDirectory() as tmp:
             if mode == "sort_index":
                 B.check_structure(B.read_bai(files[deflate, mode][1]), w)
         entry["records_and_structure"] = ok
-        entry["device_equals_host"] = all(files["device", mode] == files["host", mode] for mode in MODES)
+        if "device" in DEFLATES and "host" in DEFLATES:
+            entry["device_equals_host"] = all(files["device", mode] == files["host", mode] for mode in MODES)
         walls = {leg: [] for leg in legs}
         kernels, sorts = [], {"host_stable_sort_ms": [], "device_sort_wall_ms": [], "device_sort_kernels_ms": []}
         rec_off = np.cumsum([0] + [len(r) for r in records]).astype(np.uint64)
@@ -123,7 +127,7 @@ with tempfile.TemporaryDirectory() as tmp:
             sorts["device_sort_wall_ms"].append((time.perf_counter() - t0) * 1e3)
             t = nr.bam_sort_last_times()
             sorts["device_sort_kernels_ms"].append((t["histogram_kernel_s"] + t["scan_kernel_s"] + t["scatter_kernel_s"]) * 1e3)
-        for deflate in ("zlib", "host", "device"):
+        for deflate in DEFLATES:
             entry[deflate] = {mode: {"wall_ms_median": statistics.median(walls[deflate, mode]), "wall_ms_min": min(walls[deflate, mode]),
                                      "wall_ms_max": max(walls[deflate, mode])} for mode in MODES}
             if plain_only:
@@ -132,7 +136,7 @@ with tempfile.TemporaryDirectory() as tmp:
             entry[deflate]["sort_over_plain"] = entry[deflate]["sort"]["wall_ms_median"] / base
             entry[deflate]["sort_index_over_plain"] = entry[deflate]["sort_index"]["wall_ms_median"] / base
         result[name] = entry
-        if plain_only:
+        if plain_only or "device" not in DEFLATES:
             continue
         entry["sort_alone"] = {k: {"median": statistics.median(v), "min": min(v)} for k, v in sorts.items()}
         entry["device"]["passes"] = kernels[0]["passes"]

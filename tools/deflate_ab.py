@@ -28,6 +28,7 @@ import zlib
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from svtyper_amd import bam, classic  # noqa: E402
+from svtyper_amd.bgzf import PAYLOAD  # noqa: E402
 from svtyper_amd import native_reads as nr  # noqa: E402
 
 
@@ -38,7 +39,6 @@ def arg(name, default):
 reps, times, out_path, device = arg("--reps", 5), arg("--times", 20), arg("--out", ""), arg("--device", 0)
 huffman = "--huffman" in sys.argv
 data = os.path.join(ROOT, "tests", "data")
-PAYLOAD = 0xff00
 
 
 def vcf_payloads():

@@ -13,7 +13,11 @@ yardstick for the native fold.  --reps timed runs (default 5) after one untimed 
 For the device legs the kernels' own times from HIP events: the line-table and gather kernels (svt_vcf_lines_last_times) beside
 the deflate kernels of the same call (svt_bgzf_deflate_last_times).  Every file is inflated and compared with the expected text
 once, on the untimed runs, and device files with host files.  Prints one JSON object and, with --out FILE, writes it there.
-GPU box only."""
+GPU box only.
+
+--deflate device (a comma-separated choice of zlib,host,device; default all three) times those legs alone, and --package-root
+DIR takes svtyper_amd from another built checkout: how one commit is measured against another in one session
+(profiles/held_close_ab.json)."""
 import gzip
 import io
 import json
@@ -24,7 +28,7 @@ import tempfile
 import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+sys.path.insert(0, sys.argv[sys.argv.index("--package-root") + 1] if "--package-root" in sys.argv else ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import tbxcases as X  # noqa: E402
 from svtyper_amd import bgzf_out  # noqa: E402
@@ -36,6 +40,7 @@ def arg(name, default):
 
 
 reps, times, out_path, device = arg("--reps", 5), arg("--times", 20), arg("--out", ""), arg("--device", 0)
+DEFLATES = tuple(arg("--deflate", "zlib,host,device").split(","))
 data = os.path.join(ROOT, "tests", "data")
 
 
@@ -59,13 +64,13 @@ def close_time(text, index_path, **options):
 
 
 MODES = {"plain": {}, "index": {"index": "tbi"}, "sort_index": {"sort": True, "index": "tbi"}}
-result = {"reps": reps, "times": times, "device": device}
+result = {"reps": reps, "times": times, "device": device, "deflates": list(DEFLATES), "package_root": arg("--package-root", ROOT)}
 with tempfile.TemporaryDirectory() as tmp:
     index_path = os.path.join(tmp, "t.tbi")
     for name, text in (("vcf", repeated("example.gt.vcf", 100)), ("vcf_in", repeated("example.vcf", times))):
         ordered = X.sorted_text(text)
         entry = {"text_bytes": len(text), "lines": text.count(b"\n")}
-        legs = [(deflate, mode) for deflate in ("zlib", "host", "device") for mode in MODES]
+        legs = [(deflate, mode) for deflate in DEFLATES for mode in MODES]
         files, ok = {}, True
         for deflate, mode in legs:                                     # untimed: the library loaded, the kernels loaded
             _t, files[deflate, mode] = close_time(ordered if mode == "index" else text, index_path, deflate=deflate, device=device, **MODES[mode])
@@ -74,10 +79,11 @@ with tempfile.TemporaryDirectory() as tmp:
                 tbi = X.read_tbi(open(index_path, "rb").read())
                 X.check_structure(files[deflate, mode], tbi)
         entry["round_trip_and_structure"] = ok
-        entry["device_equals_host"] = all(files["device", mode] == files["host", mode] for mode in MODES)
+        if "device" in DEFLATES and "host" in DEFLATES:
+            entry["device_equals_host"] = all(files["device", mode] == files["host", mode] for mode in MODES)
         walls = {leg: [] for leg in legs}
         python_index, kernels = [], []
-        member_off = X.Members(files["host", "index"]).order
+        member_off = X.Members(files[DEFLATES[0], "index"]).order
         for _ in range(reps):
             for deflate, mode in legs:
                 t, _raw = close_time(ordered if mode == "index" else text, index_path, deflate=deflate, device=device, **MODES[mode])
@@ -87,13 +93,16 @@ with tempfile.TemporaryDirectory() as tmp:
             t0 = time.perf_counter()
             X.build_tbi(ordered, member_off)
             python_index.append((time.perf_counter() - t0) * 1e3)
-        for deflate in ("zlib", "host", "device"):
+        for deflate in DEFLATES:
             entry[deflate] = {mode: {"wall_ms_median": statistics.median(walls[deflate, mode]), "wall_ms_min": min(walls[deflate, mode]),
                                      "wall_ms_max": max(walls[deflate, mode])} for mode in MODES}
             base = entry[deflate]["plain"]["wall_ms_median"]
             entry[deflate]["index_over_plain"] = entry[deflate]["index"]["wall_ms_median"] / base
             entry[deflate]["sort_index_over_plain"] = entry[deflate]["sort_index"]["wall_ms_median"] / base
         entry["python_index"] = {"wall_ms_median": statistics.median(python_index), "wall_ms_min": min(python_index)}
+        if "device" not in DEFLATES:
+            result[name] = entry
+            continue
         entry["device"]["kernels_ms_median"] = {k[:-2] + "_ms": statistics.median(t[k] for t in kernels) * 1e3 for k in kernels[0] if k.endswith("kernel_s")}
         lines_ms = sum(v for k, v in entry["device"]["kernels_ms_median"].items() if not k.startswith("deflate_"))
         entry["device"]["line_kernels_over_deflate_kernel"] = lines_ms / entry["device"]["kernels_ms_median"]["deflate_deflate_kernel_ms"]
