@@ -275,7 +275,7 @@ int svt_huffman_lengths_device(const uint32_t* freq, uint32_t sets, uint32_t sym
  *   off, len     where the line lies in the text and how long it is (its newline included)
  *   flags        SVT_TBX_META: it starts with '#'.  SVT_TBX_BAD: not a data line (fewer than 8 tab-separated columns, a
  *                POS that is not 1 .. 10 decimal digits below 2^31, an empty line).  SVT_TBX_RANGE: end > 2^29, beyond
- *                what a TBI index addresses (a CSI index is not written).
+ *                what a TBI index addresses (a CSI index holds it: svt_csi_build_vcf).
  *   beg, end     (data lines) beg = max(POS - 1, 0); end = beg + len(REF), or the value of the first INFO key END (at the
  *                start of INFO or behind ';', followed by '=' and a digit) where it has at most 10 digits and lies above
  *                beg; saturated at 2^32 - 1
@@ -348,7 +348,7 @@ int svt_tbx_take(uint8_t* out, uint64_t capacity);
  *   end          pos + the reference bases its CIGAR consumes (M, D, N, =, X); pos + 1 for an unmapped record (0x4), one
  *                without CIGAR or with a sum of 0; saturated at 2^32 - 1
  *   flags        SVT_BAM_UNMAPPED: flag 0x4.  SVT_BAM_NO_COOR: tid = -1.  SVT_BAM_BEYOND: end > 2^29, beyond what a BAI
- *                addresses (a CSI index is not written).  SVT_BAM_BAD, with why: SVT_BAM_BAD_RECORD (the span is not
+ *                addresses (a CSI index holds it: svt_csi_build_bam).  SVT_BAM_BAD, with why: SVT_BAM_BAD_RECORD (the span is not
  *                36 bytes, block_size is not the span's length less 4, or the fixed part, name and CIGAR do not fit
  *                inside block_size), SVT_BAM_BAD_TID (tid >= n_ref or < -1), SVT_BAM_BAD_POS (pos < 0 with a tid,
  *                pos < -1 without); key, beg and end of such a span are 0.                                            */
@@ -417,6 +417,66 @@ int svt_bam_sort_last_times(svt_bam_sort_times* times);
 int svt_bai_build(const svt_bam_span* spans, uint64_t n, int32_t n_ref, const uint64_t* member_start, const uint64_t* member_off,
                   uint64_t n_members, uint64_t* size, uint64_t* bad_record, uint32_t* bad_kind);
 int svt_bai_take(uint8_t* out, uint64_t capacity);
+
+/* ---- a CSI index for the sorted `-w` BAM and the sorted VCF (additions; the ABI number stays: probe for svt_csi_build_bam) ----
+ * The same fold as svt_bai_build / svt_tbx_build in a scheme (min_shift 14, depth): depth is the smallest d >= 5 for which
+ * 2^(14 + 3 d) covers the file -- svt_csi_depth(max_end), with max_end the longest l_ref of a BAM header, or the largest end
+ * among the body lines of a VCF's line table.  Positions are below 2^32, so depth is 5 or 6.  The bytes are the UNCOMPRESSED
+ * CSIv1 (the writers put them through BGZF):
+ *   header       "CSI\1", min_shift, depth, l_aux, aux, n_ref.  BAM: l_aux = 0.  VCF: aux is the tabix block -- seven 32-bit
+ *                words format 2, col_seq 1, col_beg 2, col_end 0, meta '#', skip 0, l_nm, then the NUL-terminated names --
+ *                and n_ref the number of contigs
+ *   per reference  n_bin; per bin, in rising order: bin, loffset, n_chunk, the chunks (a run of consecutive records with one
+ *                bin is one chunk); then the pseudo-bin (8^(depth+1) - 1) / 7 + 1 with loffset 0 and the two chunks
+ *                (first start, last end), (mapped, unmapped) -- (lines, 0) for a VCF; n_bin = 0 for a reference without records
+ *   trailer      the 64-bit n_no_coor (0 for a VCF)
+ *   loffset      of a bin: the virtual offset of the first record of that reference, in file order, that ends behind the
+ *                bin's first position -- no record that overlaps a position at or behind the bin's start lies in front of it
+ * Virtual offsets are svt_bai_build's: a position at a member's end is the next member's offset 0, the end of the data is
+ * member_off[n_members] << 16.  A record or line whose end exceeds 2^(14 + 3 depth) or equals the saturated 0xFFFFFFFF is
+ * refused as SVT_BAM_KIND_BEYOND / SVT_TBX_BEYOND: the decision comes from `end`, not from the SVT_BAM_BEYOND /
+ * SVT_TBX_RANGE flag, which keeps meaning end > 2^29.  Arguments, result and refusals otherwise as svt_bai_build /
+ * svt_tbx_build (KEY_BACK, CONTIG_AGAIN and POS_BACK included); svt_csi_take hands over the calling thread's last result
+ * of either build or of the device fold.  Byte equality with htslib's .csi, or its choice of depth, is not claimed.      */
+uint32_t svt_csi_depth(uint64_t max_end);
+int svt_csi_build_bam(const svt_bam_span* spans, uint64_t n, int32_t n_ref, uint64_t l_ref_max, const uint64_t* member_start,
+                      const uint64_t* member_off, uint64_t n_members, uint64_t* size, uint64_t* bad_record, uint32_t* bad_kind);
+int svt_csi_build_vcf(const uint8_t* text, uint64_t len, const uint64_t* src_off, const svt_tbx_line* lines, uint64_t n,
+                      const uint64_t* member_off, uint64_t n_members, uint32_t payload, uint64_t* size, uint64_t* bad_line,
+                      uint32_t* bad_kind);
+int svt_csi_take(uint8_t* out, uint64_t capacity);
+/* The BAM's CSI fold on the device (svtyper_amd/csrc/svt_bam_index_kernel.h): svt_csi_build_bam's arguments and result, byte for
+ * byte, over the caller's table -- one lane per record for virtual offset, bin and the first refusal (one 64-bit integer
+ * minimum), one three-phase scan (per-tile partials, one workgroup over them, apply: no workgroup waits for another) carrying
+ * the runs' numbers, the count of unmapped records and the running maximum of tid << 32 | end, the runs sorted by the radix
+ * passes of svt_bam_sort_order_device, a bounded binary search per bin for its loffset and two per reference for its row.
+ * What comes down is O(runs + n_ref): the sorted runs (key, start, end), the group heads' loffsets and a row per reference;
+ * the host checks them (sorted, start <= end, heads consistent: SVT_ERR_HIP otherwise) and serialises them with the
+ * serialiser of svt_csi_build_bam.  The bytes are left for svt_csi_take.                                               */
+int svt_bam_index_fold_device(const svt_bam_span* spans, uint64_t n, int32_t n_ref, uint64_t l_ref_max, const uint64_t* member_start,
+                              const uint64_t* member_off, uint64_t n_members, uint64_t* size, uint64_t* bad_record,
+                              uint32_t* bad_kind, int device);
+/* svt_bam_sorted_bgzf_device with that fold behind the members: the stream goes up once and the spans are never uploaded
+ * again -- after the members are made only member_start / out_off go up, n_members + 1 words each (out_off[k] is member k's
+ * file offset: the members are the file).  *csi_size: the length of the .csi bytes left for svt_csi_take;
+ * *index_bad_record / *index_bad_kind: the 1-based number, in WRITTEN order, of a record the index cannot hold and why (the
+ * members are complete, no index bytes), 0 otherwise.  Everything else as svt_bam_sorted_bgzf_device; where that call
+ * writes nothing (len = 0, or *bad_record != 0) there is no fold and *csi_size is 0.                                    */
+int svt_bam_sorted_bgzf_csi_device(const uint8_t* bytes, uint64_t len, const uint64_t* rec_off, uint64_t n, int32_t n_ref,
+                                   uint64_t l_ref_max, int sort, uint32_t mode, uint8_t* out, uint64_t capacity, uint64_t* out_off,
+                                   uint64_t member_capacity, uint64_t* n_members, uint64_t* member_start, svt_bam_span* spans,
+                                   uint64_t* perm, uint64_t* bad_record, uint32_t* bad_kind, uint64_t* csi_size,
+                                   uint64_t* index_bad_record, uint32_t* index_bad_kind, int device);
+/* the calling thread's most recent device fold (either entry): its kernels by HIP events -- the scan's three phases summed,
+ * the run-key kernel and the radix passes summed -- and the fold's time on the host's clock                            */
+typedef struct svt_bam_index_times {
+    double record_kernel_s, scan_kernel_s, sort_kernel_s, loffset_kernel_s, reference_kernel_s;
+    double total_s;
+    uint64_t runs;              /* runs of consecutive records with one bin                                             */
+    uint32_t passes;            /* digits the runs' sort took                                                           */
+    uint32_t reserved;
+} svt_bam_index_times;
+int svt_bam_index_last_times(svt_bam_index_times* times);
 
 /* Verify: a property of the handle, off by default (0).  With it on, every call that takes the handle checks the
  * CRC-32 of every BGZF member it inflates, where it inflates it: the host reader's threads (libdeflate's or zlib's

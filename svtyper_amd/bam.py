@@ -339,7 +339,7 @@ class AlignmentFile:
                 raise NotImplementedError("only BAM output (mode 'wb') is written")
             self._open_for_writing(path, kwargs.get("template", template), kwargs.get("deflate", "zlib"), kwargs.get("device", 0),
                                    kwargs.get("huffman", "fixed"), kwargs.get("sort", False), kwargs.get("index", None),
-                                   kwargs.get("index_path", None))
+                                   kwargs.get("index_path", None), kwargs.get("csi", False))
             return
         self._bgzf = BgzfReader(path, verify=bool(kwargs.get("verify", False)))
         raw = []        # the header as it lies in the file: a file opened 'wb' with this one as template starts with these bytes
@@ -541,9 +541,10 @@ class AlignmentFile:
 
     # ---- writing (mode 'wb')
     _held = None            # (sort= / index=) the _RecordHold that stands where the BgzfWriter stands until close()
+    _device_fold = True     # (deflate="device", csi) the CSI fold on the GPU; False: svt_csi_build_bam on the host (tools/csi_ab.py's other leg)
 
     def _open_for_writing(self, path: str, template, deflate: str = "zlib", device: int = 0, huffman: str = "fixed", sort: bool = False,
-                          index=None, index_path=None):
+                          index=None, index_path=None, csi: bool = False):
         """pysam.AlignmentFile(path, 'wb', template): the template's header text and reference list, byte for byte.  `deflate`,
         `device`, `huffman`: who compresses the members, and into which block (BgzfWriter).
 
@@ -554,8 +555,15 @@ class AlignmentFile:
         stable order by key and SO:coordinate in the header's @HD line, the members cut exactly where they are cut for records
         written in that order, and with `index` the .bai at `index_path` (default: path + ".bai").  With deflate="device" the
         header and the records go to the GPU once and the table, the sort, the gather and the members are made there
-        (svt_bam_sorted_bgzf_device); otherwise on the host, by the same source.  The index fold is host code either way
-        (svt_bai_build).  A record that cannot be sorted or indexed makes close() raise BamOrderError; with `index` and
+        (svt_bam_sorted_bgzf_device); otherwise on the host, by the same source.  The .bai fold is host code either way
+        (svt_bai_build).
+
+        `csi=True` (`--alignment-csi`): the index asked for, in the CSI container (as pysam's tabix_index(..., csi=True) and
+        `samtools index -c` spell it) -- a CSIv1 index in the scheme (14, depth) whose depth is the smallest >= 5 that covers
+        the header's longest reference, BGZF-compressed, at `index_path` (default: path + ".csi").  It holds records beyond
+        2^29.  With deflate="device" its fold runs on the GPU behind the members (svt_bam_sorted_bgzf_csi_device), otherwise on
+        the host (svt_csi_build_bam): the same bytes.  `index="csi"` is not a spelling of it (ValueError), and `csi=True` without
+        `index` is a ValueError.  An index of an earlier file is removed in either format, .bai and .csi.  A record that cannot be sorted or indexed makes close() raise BamOrderError; with `index` and
         without `sort`, records that are not in key order do so once the BAM is complete, and no index is left behind.
         Without either option the writer streams as it always did."""
         header = getattr(template, "_header_bytes", None)
@@ -563,13 +571,16 @@ class AlignmentFile:
             raise TypeError("mode 'wb' needs template=: an AlignmentFile of this module opened for reading")
         if index not in (None, "bai"):
             raise ValueError("index must be None or 'bai', not %r" % (index,))
+        if csi and index is None:
+            raise ValueError("csi=True says which container the index goes into: it needs index='bai'")
         self.text, self.header = template.text, template.header
         self.references, self.lengths = template.references, template.lengths
         self._tid = dict(template._tid)
         self._writer = BgzfWriter(path, deflate=deflate, device=device, huffman=huffman)
         if sort or index is not None:
-            self._sort, self._index = bool(sort), index
-            self._index_path = (os.fspath(path) + ".bai" if index_path is None else index_path) if index is not None else None
+            self._sort, self._index, self._csi = bool(sort), index, bool(csi)
+            self._index_path = (os.fspath(path) + (".csi" if csi else ".bai") if index_path is None else index_path) if index is not None else None
+            self._stale = (os.fspath(path) + ".bai", os.fspath(path) + ".csi") if index is not None else ()
             self._header_out = coordinate_header(header) if sort else header
             self._bgzf_out = self._writer
             self._held = self._writer = _RecordHold(self._header_out, self._close_held)
@@ -587,8 +598,19 @@ class AlignmentFile:
         n_ref = struct.unpack_from("<i", data, 8 + struct.unpack_from("<i", data, 4)[0])[0]
         rec_off = np.array(offsets, np.uint64)
 
+        l_ref_max = max(self.lengths, default=0)
+        folded = []                         # (deflate="device", csi) what the device fold behind the members left: (bytes, bad, kind)
+
         def members(w):
             """-> (the spans as written, the order they were written in)"""
+            if w._deflate == "device" and self._index and self._csi and self._device_fold:
+                made, _off, _start, spans, perm, csi, ibad, ikind, bad, kind = nr.bam_sorted_bgzf_csi_device(data, rec_off, n_ref, l_ref_max, self._sort,
+                                                                                                              w._huffman, w._device)
+                if bad:
+                    raise self._order_error(data, offsets, bad, kind)
+                w._f.write(memoryview(made))
+                folded.append((csi, ibad, ikind))
+                return spans, perm
             if w._deflate == "device":
                 made, _off, _start, spans, perm, bad, kind = nr.bam_sorted_bgzf_device(data, rec_off, n_ref, self._sort, w._huffman, w._device)
                 if bad:
@@ -610,12 +632,25 @@ class AlignmentFile:
                 w.write_record(bytes(view[offsets[i]:offsets[i + 1]]))     # (a record at a time: the stream is not doubled)
             return spans, perm
 
-        def write_plainly(path, bai):
+        def fold(held, log):
+            if folded:
+                return folded[0]
+            starts, member_off = np.array(log.starts, np.uint64), np.array(log.offsets, np.uint64)
+            if self._csi:
+                return nr.csi_build_bam(held[0], n_ref, l_ref_max, starts, member_off)
+            return nr.bai_build(held[0], n_ref, starts, member_off)
+
+        def write_index(path, index):
+            if self._csi:                   # (a .csi is BGZF, as a .tbi is)
+                out = BgzfWriter(path)
+                out.write(index)
+                out.close()
+                return
             with open(path, "wb") as f:
-                f.write(bai)
-        close_held(self._bgzf_out, self._index_path, members,
-                   self._index and (lambda held, log: nr.bai_build(held[0], n_ref, np.array(log.starts, np.uint64), np.array(log.offsets, np.uint64))),
-                   lambda held, bad, kind: self._order_error(data, offsets, int(held[1][bad - 1]) + 1, kind), write_plainly)
+                f.write(index)
+        close_held(self._bgzf_out, self._index_path, members, self._index and fold,
+                   lambda held, bad, kind: self._order_error(data, offsets, int(held[1][bad - 1]) + 1, kind), write_index,
+                   stale=self._stale if self._index else ())
 
     def _order_error(self, data, offsets, bad: int, kind: int) -> "BamOrderError":
         """`bad`: the 1-based number of the record among those handed to write() / write_raw()"""
@@ -632,12 +667,18 @@ class AlignmentFile:
             why = "its position is negative"
         elif kind == nr.BAM_KIND_RECORD:
             why = "its fixed part, name and CIGAR do not fit inside its block_size"
+        elif kind == nr.BAM_KIND_BEYOND and getattr(self, "_csi", False):
+            depth = nr.csi_depth(max(self.lengths, default=0))
+            return BamOrderError("%s: %s ends beyond 2^%d, the limit of the .csi index's scheme (min_shift 14, depth %d, from the header's "
+                                 "longest reference): it lies beyond its header's contigs; no index was written"
+                                 % (self.filename, where, 14 + 3 * depth, depth), bad)
         elif kind == nr.BAM_KIND_BEYOND:
-            return BamOrderError("%s: %s ends beyond 2^29, which a .bai index cannot address (a CSI index is not written)"
-                                 % (self.filename, where), bad)
+            return BamOrderError("%s: %s ends beyond 2^29, which a .bai index cannot address (a CSI index is not written: ask for one "
+                                 "with --alignment-csi (csi=True))" % (self.filename, where), bad)
         else:
-            return BamOrderError("%s: %s is out of order (its key lies below the record in front): a .bai index needs a "
-                                 "coordinate-sorted BAM; no index was written -- use --sort-alignment (sort=True)" % (self.filename, where), bad)
+            return BamOrderError("%s: %s is out of order (its key lies below the record in front): a %s index needs a "
+                                 "coordinate-sorted BAM; no index was written -- use --sort-alignment (sort=True)"
+                                 % (self.filename, where, ".csi" if getattr(self, "_csi", False) else ".bai"), bad)
         return BamOrderError("%s: %s cannot be sorted or indexed (%s)" % (self.filename, where, why), bad)
 
     def write(self, read: AlignedSegment) -> None:

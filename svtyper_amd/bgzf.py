@@ -221,16 +221,19 @@ class _MemberLog:
         self._f.close()
 
 
-def close_held(w: BgzfWriter, index_path, members, fold, order_error, write_index) -> None:
+def close_held(w: BgzfWriter, index_path, members, fold, order_error, write_index, stale=()) -> None:
     """The close of a writer that held its whole output until now, over its BgzfWriter `w` (nothing written to it yet): the
     members are logged as they are written, an index of an earlier file is not left beside this one, the data file is complete
     and closed whatever happens, and only then is the index folded and written, or refused.  The writer supplies
         members(w) -> held            writes every member through `w` (or whole members to w._f); raises where the order is refused
         fold(held, log) -> (index bytes, bad, kind)     from the _MemberLog's offsets / starts; None: no index was asked for
-        order_error(held, bad, kind)  the exception for a fold that stopped at `bad`;  write_index(index_path, index bytes)"""
+        order_error(held, bad, kind)  the exception for a fold that stopped at `bad`;  write_index(index_path, index bytes)
+    `stale`: the default index paths of the output in either format (X.bai and X.csi; X.tbi and X.csi) -- an index of an earlier
+    file under one of them would be read in place of the one written now (the project's own readers prefer a .bai)."""
     log = w._f = _MemberLog(w._f)
-    if index_path is not None and os.path.exists(index_path):
-        os.remove(index_path)
+    for path in ((index_path,) if index_path is not None else ()) + tuple(stale):
+        if os.path.exists(path):
+            os.remove(path)
     try:
         held = members(w)
     finally:

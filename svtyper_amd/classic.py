@@ -195,7 +195,8 @@ def sv_genotype(bam_string, vcf_in, vcf_out, min_aligned, split_weight, disc_wei
     the "host" or on the "device" (bam.BgzfWriter; the same inflated bytes and member boundaries); ValueError for anything else.  `huffman`: "fixed", or "dynamic" for
     dynamic-Huffman blocks from that compressor (ValueError with deflate="zlib").  `alignment_sort` (--sort-alignment): that BAM in
     stable coordinate order, its header saying SO:coordinate; `alignment_index="bai"` (--bai): its index beside it, at
-    alignment_outpath + ".bai" (bam.AlignmentFile's sort= / index=: both hold every record until the end; BamOrderError for records
+    alignment_outpath + ".bai"; `alignment_index="csi"` (--alignment-csi): a CSI index instead, at alignment_outpath + ".csi", which
+    also holds records beyond 2^29 (bam.AlignmentFile's sort= / index= / csi=: both hold every record until the end; BamOrderError for records
     that cannot be sorted or indexed).  ValueError for either without `alignment_outpath`."""
     check_huffman(huffman, check_deflate(deflate))
     run = Classic(bam_string, vcf_in, vcf_out, min_aligned, split_weight, disc_weight, num_samp, lib_info_path, debug, ref_fasta,
@@ -232,9 +233,14 @@ def get_args():
         # --help, like --sort and --tabix: the help text is pinned byte for byte.
         p.add_argument("--sort-alignment", dest="alignment_sort", action="store_true", help=argparse.SUPPRESS)
         p.add_argument("--bai", dest="alignment_bai", action="store_true", help=argparse.SUPPRESS)
+        p.add_argument("--alignment-csi", dest="alignment_csi", action="store_true", help=argparse.SUPPRESS)
     args = parse_arguments(p, "BAM or CRAM file(s), comma-separated if genotyping multiple samples", None, own)
     if (args.alignment_sort or args.alignment_bai) and args.alignment_outpath is None:
         p.error("--sort-alignment and --bai need -w/--write_alignment")
+    if args.alignment_csi and args.alignment_outpath is None:
+        p.error("--alignment-csi needs -w/--write_alignment")
+    if args.alignment_csi and args.alignment_bai:
+        p.error("--alignment-csi and --bai name two formats for one index: give one of them")
     return args
 
 
@@ -250,7 +256,7 @@ def main():
             args.num_samp, args.lib_info_path, args.debug, args.alignment_outpath, args.ref_fasta,
             args.sum_quals, args.max_reads, args.max_ci_dist)
     own = dict(deflate=args.deflate, huffman=args.huffman)      # (of this program alone: the `-w` BAM)
-    order = dict(alignment_sort=args.alignment_sort, alignment_index="bai" if args.alignment_bai else None)
+    order = dict(alignment_sort=args.alignment_sort, alignment_index="csi" if args.alignment_csi else "bai" if args.alignment_bai else None)
     return run_main(functools.partial(sv_genotype, **own, **order), functools.partial(sharded.sv_genotype_sharded, **own), call, args)
 
 

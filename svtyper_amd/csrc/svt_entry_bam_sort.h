@@ -5,7 +5,8 @@
 // svt_bam_scatter_kernel per digit), the argument checks and the caller's arrays.  What it shares lives in svt_entry_deflate.h:
 // the upload (OrderedCall::begin), the gather behind the header copy (gather_resident<svt_bam_span>), the members from
 // bsr::cut_members' boundaries (deflate_members), the marks that time the kernels.  C ABI: svt_bam_spans_device,
-// svt_bam_sort_order_device, svt_bam_sorted_bgzf_device, svt_bam_sort_last_times (include/svtyper_reads.h).
+// svt_bam_sort_order_device, svt_bam_sorted_bgzf_device, svt_bam_sort_last_times (include/svtyper_reads.h).  The one-call entry's
+// body takes a hook that runs behind the members while its tables are resident: svt_entry_bam_index.h's CSI fold.
 
 extern "C++" {
 
@@ -162,9 +163,14 @@ static int svt_bam_sort_order_device_impl(const svt_bam_span* spans, uint64_t n,
     return SVT_OK;
 }
 
+// what svt_bam_sorted_bgzf_csi_device (svt_entry_bam_index.h) does behind the members, while the call's tables are resident:
+// (the call, whether the records were gathered, the number of members)
+using BamFoldHook = std::function<int(BamSortCall&, bool, uint64_t)>;
+
 static int svt_bam_sorted_bgzf_device_impl(const uint8_t* bytes, uint64_t len, const uint64_t* rec_off, uint64_t n, int32_t n_ref, int sort, uint32_t mode,
                                            uint8_t* out, uint64_t capacity, uint64_t* out_off, uint64_t member_capacity, uint64_t* n_members,
-                                           uint64_t* member_start, svt_bam_span* spans, uint64_t* perm, uint64_t* bad_record, uint32_t* bad_kind, int device)
+                                           uint64_t* member_start, svt_bam_span* spans, uint64_t* perm, uint64_t* bad_record, uint32_t* bad_kind, int device,
+                                           const BamFoldHook* behind = nullptr)
 {
     const auto t0 = std::chrono::steady_clock::now();
     g_bam_sort_times = svt_bam_sort_times();
@@ -226,6 +232,7 @@ static int svt_bam_sorted_bgzf_device_impl(const uint8_t* bytes, uint64_t len, c
     std::memcpy(member_start, start.data(), start.size() * sizeof(uint64_t));
     SVT_TRY(deflate_members(c, "svt_bam_sorted_bgzf", d_written, start.data(), members, out, capacity, out_off, mode, device));
     *n_members = members;
+    if (behind) SVT_TRY((*behind)(c, sort != 0, members));
     g_bam_sort_times.total_s = g_deflate_times.total_s = seconds_since(t0);
     return SVT_OK;
 }

@@ -24,6 +24,23 @@ int check_member_off(const char* entry, const uint64_t* member_off, uint64_t n_m
     return SVT_OK;
 }
 
+// what svt_tbx_build and svt_csi_build_vcf ask of their tables, in the entry's name
+int check_line_table(const char* entry, uint64_t len, const uint64_t* src_off, const svt_tbx_line* lines, uint64_t n, const uint64_t* member_off,
+                     uint64_t n_members, uint32_t payload)
+{
+    const std::string who(entry);
+    if (payload < 1 || payload > 65536) return fail(SVT_ERR_INVALID, who + ": a payload has 1 .. 65536 bytes");
+    if (len > n_members * (uint64_t)payload) return fail(SVT_ERR_INVALID, who + ": the members hold less than the text");
+    uint64_t at = 0;
+    for (uint64_t i = 0; i < n; ++i) {            // the table of a text as written: the lines side by side
+        if (lines[i].off != at || lines[i].len > len - at) return fail(SVT_ERR_INVALID, who + ": the lines do not tile the text");
+        const uint64_t src = src_off ? src_off[i] : lines[i].off;
+        if (src > len || lines[i].chrom_len > len - src) return fail(SVT_ERR_INVALID, who + ": a CHROM lies outside the text");
+        at += lines[i].len;
+    }
+    return check_member_off(entry, member_off, n_members);
+}
+
 }  // namespace
 
 extern "C" {
@@ -70,16 +87,7 @@ int svt_tbx_build(const uint8_t* text, uint64_t len, const uint64_t* src_off, co
 {
     return guarded([&]() -> int {
         if ((len && !text) || (n && !lines) || !member_off || !size || !bad_line || !bad_kind) return fail(SVT_ERR_INVALID, "null argument");
-        if (payload < 1 || payload > 65536) return fail(SVT_ERR_INVALID, "svt_tbx_build: a payload has 1 .. 65536 bytes");
-        if (len > n_members * (uint64_t)payload) return fail(SVT_ERR_INVALID, "svt_tbx_build: the members hold less than the text");
-        uint64_t at = 0;
-        for (uint64_t i = 0; i < n; ++i) {            // the table of a text as written: the lines side by side
-            if (lines[i].off != at || lines[i].len > len - at) return fail(SVT_ERR_INVALID, "svt_tbx_build: the lines do not tile the text");
-            const uint64_t src = src_off ? src_off[i] : lines[i].off;
-            if (src > len || lines[i].chrom_len > len - src) return fail(SVT_ERR_INVALID, "svt_tbx_build: a CHROM lies outside the text");
-            at += lines[i].len;
-        }
-        if (const int rc = check_member_off("svt_tbx_build", member_off, n_members)) return rc;
+        if (const int rc = check_line_table("svt_tbx_build", len, src_off, lines, n, member_off, n_members, payload)) return rc;
         *bad_kind = 0;
         g_tbx_result.build(size, [&](std::vector<uint8_t>& tbi) {
             *bad_line = svt::tbx::build(text, src_off, lines, n, len, member_off, n_members, payload, tbi, *bad_kind);

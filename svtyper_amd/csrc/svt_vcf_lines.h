@@ -14,6 +14,7 @@
 
 #include "../../include/svtyper_reads.h"
 #include "svt_geometry_math.h"
+#include "svt_index_scheme.h"
 
 namespace svt {
 namespace tbx {
@@ -73,16 +74,7 @@ SVT_HD void parse_line(const uint8_t* p, uint64_t len, svt_tbx_line& r)
 }
 
 // the bin of [beg, end) (SAM spec 5.3: 14-bit leaves, five levels)
-SVT_HD uint32_t reg2bin(uint64_t beg, uint64_t end)
-{
-    --end;
-    if (beg >> 14 == end >> 14) return (uint32_t)(((1u << 15) - 1) / 7 + (beg >> 14));
-    if (beg >> 17 == end >> 17) return (uint32_t)(((1u << 12) - 1) / 7 + (beg >> 17));
-    if (beg >> 20 == end >> 20) return (uint32_t)(((1u << 9) - 1) / 7 + (beg >> 20));
-    if (beg >> 23 == end >> 23) return (uint32_t)(((1u << 6) - 1) / 7 + (beg >> 23));
-    if (beg >> 26 == end >> 26) return (uint32_t)(((1u << 3) - 1) / 7 + (beg >> 26));
-    return 0;
-}
+SVT_HD uint32_t reg2bin(uint64_t beg, uint64_t end) { return idx::reg2bin(beg, end, idx::kBaiDepth); }
 
 }  // namespace tbx
 }  // namespace svt

@@ -38,6 +38,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <memory>
 #include <mutex>
 #include <string>
@@ -71,6 +72,8 @@
 #include "svt_deflate_kernel.h"
 #include "svt_vcf_lines_kernel.h"
 #include "svt_bam_sort_kernel.h"
+#include "svt_bam_index_kernel.h"
+#include "svt_bai_index.h"
 #include "svt_bgzf.h"
 #include "svt_evidence_arena.h"
 #include "svt_library_kernel.h"
@@ -196,6 +199,7 @@ void svt_batch_destroy(svt_batch* b) { free_batch(b); }
 #include "svt_entry_deflate.h"
 #include "svt_entry_vcf_lines.h"
 #include "svt_entry_bam_sort.h"
+#include "svt_entry_bam_index.h"
 #include "svt_entry_evidence.h"
 #include "svt_entry_library.h"
 #include "svt_entry_oneshot.h"

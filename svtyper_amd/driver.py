@@ -17,7 +17,7 @@ route, the `stats=` block.  What the reference's two programs do differently is 
              finish(unpaired)             the end of a run
     data     alignment_outpath            (`svtyper -w`) the evidence dump: tag_and_write below, per chunk, in output order -- the reads of
                                                   reader="python", or the finished records of reader="device" (svt_dump_kernel.h)
-             alignment_sort, alignment_index   (`--sort-alignment`, `--bai`) that BAM coordinate-sorted / with its .bai: the writer's
+             alignment_sort, alignment_index   (`--sort-alignment`, `--bai` / `--alignment-csi`) that BAM coordinate-sorted / with its .bai or .csi: the writer's
                                                   sort= and index= (bam.AlignmentFile), which hold the records until close()
 
 No method takes a flag that names its caller, and a driver's hooks run per line handed to the per-line route and per
@@ -123,7 +123,7 @@ class Driver:
     deflate = "zlib"                    # who compresses the `-w` BAM's members (bam.BgzfWriter)
     huffman = "fixed"                   # ... and into which block, where it is the library's own compressor
     alignment_sort = False              # the `-w` BAM in coordinate order (bam.AlignmentFile: sort=)
-    alignment_index = None              # ... and "bai": its index beside it (index=)
+    alignment_index = None              # ... and "bai" / "csi": its index beside it (index="bai"; "csi": with csi=True)
 
     def __init__(self, bam_string, vcf_in, vcf_out, min_aligned, split_weight, disc_weight, num_samp, lib_info_path, debug,
                  ref_fasta, sum_quals, max_reads, max_ci_dist, n_threads=0):
@@ -139,8 +139,8 @@ class Driver:
         writing = self.alignment_outpath is not None
         if not writing and (self.alignment_sort or self.alignment_index is not None):
             raise ValueError("alignment_sort / alignment_index (--sort-alignment, --bai) need -w/--write_alignment: they are about that BAM")
-        if self.alignment_index not in (None, "bai"):
-            raise ValueError("alignment_index must be None or 'bai', not %r" % (self.alignment_index,))
+        if self.alignment_index not in (None, "bai", "csi"):
+            raise ValueError("alignment_index must be None, 'bai' or 'csi', not %r" % (self.alignment_index,))
         if writing and reader is None:
             reader = "python"           # the one route that keeps the reads it tallied
         reader = resolve_reader(reader)
@@ -172,8 +172,10 @@ class Driver:
         if writing:     # classic.py:161-166: the first alignment file is the template, its header is the dump's
             template = AlignmentFile(paths[0], "rb")
             order = dict(sort=True) if self.alignment_sort else {}
-            if self.alignment_index is not None:
-                order["index"] = self.alignment_index
+            if self.alignment_index is not None:    # (the writer spells a CSI as pysam does: the index asked for, csi=True)
+                order["index"] = "bai"
+                if self.alignment_index == "csi":
+                    order["csi"] = True
             out_bam = AlignmentFile(self.alignment_outpath, "wb", template=template, deflate=self.deflate, huffman=self.huffman,
                                     device=getattr(engine, "device", 0), **order)
             template.close()
@@ -363,17 +365,25 @@ def parse_arguments(p, bam_help, max_reads, own):
     # compresses BGZF output (--bgzf, -w) -- zlib, or the library's own compressor on the host or on the GPU (same inflated bytes);
     # --huffman: the block that compressor writes -- fixed, or dynamic where that is shorter (not with --deflate zlib).
     # --sort: (with --bgzf) the body in stable order by (contig rank, POS); --tabix: (with --bgzf -o PATH) PATH.tbi beside the
-    # output (bgzf_out's docstring: both hold the whole output text until the end).
+    # output (bgzf_out's docstring: both hold the whole output text until the end); --csi: the same index in the CSI container,
+    # PATH.csi, which also holds contigs beyond 512 Mbp (not together with --tabix).
     p.add_argument("--bgzf", action="store_true", help=argparse.SUPPRESS)
     p.add_argument("--deflate", choices=("zlib", "host", "device"), default="zlib", help=argparse.SUPPRESS)
     p.add_argument("--huffman", choices=("fixed", "dynamic"), default="fixed", help=argparse.SUPPRESS)
     p.add_argument("--sort", action="store_true", help=argparse.SUPPRESS)
     p.add_argument("--tabix", action="store_true", help=argparse.SUPPRESS)
+    p.add_argument("--csi", action="store_true", help=argparse.SUPPRESS)
     args = p.parse_args()
     if (args.sort or args.tabix) and not args.bgzf:
         p.error("--sort and --tabix need --bgzf")
+    if args.csi and not args.bgzf:
+        p.error("--csi needs --bgzf")
+    if args.csi and args.tabix:
+        p.error("--csi and --tabix name two formats for one index: give one of them")
     if args.tabix and args.output_vcf is sys.stdout:
         p.error("--tabix needs an output file (-o): an index is written beside it")
+    if args.csi and args.output_vcf is sys.stdout:
+        p.error("--csi needs an output file (-o): an index is written beside it")
     args.input_vcf = gzip_text(args.input_vcf)
     if args.input_vcf is None and not sys.stdin.isatty():
         args.input_vcf = sys.stdin
@@ -423,7 +433,8 @@ def _bgzf_text(vcf_out, deflate, device, huffman="fixed", args=None):
     """`--bgzf`: the output VCF through bgzf_out.open_text (imported only here)"""
     from . import bgzf_out
     return bgzf_out.open_text(vcf_out, deflate=deflate, device=device, huffman=huffman, sort=bool(getattr(args, "sort", False)),
-                              index="tbi" if getattr(args, "tabix", False) else None)
+                              index="tbi" if getattr(args, "tabix", False) or getattr(args, "csi", False) else None,
+                              csi=bool(getattr(args, "csi", False)))
 
 
 def run_cli(main):

@@ -148,6 +148,11 @@ class _BamSortTimes(C.Structure):
                 ("reserved", C.c_uint32)]
 
 
+class _BamIndexTimes(C.Structure):
+    _fields_ = [(name, C.c_double) for name in ("record_kernel_s", "scan_kernel_s", "sort_kernel_s", "loffset_kernel_s", "reference_kernel_s",
+                                                "total_s")] + [("runs", C.c_uint64), ("passes", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 class _InflateStats(C.Structure):
     """include/svtyper_reads.h: svt_evidence_inflate_stats"""
     _fields_ = [("blocks_inflated", C.c_uint64), ("blocks_failed", C.c_uint64), ("compressed_bytes", C.c_uint64),
@@ -289,6 +294,18 @@ def _lib():
                                    ("svt_bam_sorted_bgzf_device", [P, U64, P, U64, I32, C.c_int, C.c_uint32, P, U64, P, U64, P, P, P, P, P, P, C.c_int]),
                                    ("svt_bam_sort_last_times", [C.POINTER(_BamSortTimes)]),
                                    ("svt_bai_build", [P, U64, I32, P, P, U64, P, P, P]), ("svt_bai_take", [P, U64])):
+                getattr(L, name).restype = C.c_int
+                getattr(L, name).argtypes = argtypes
+        if hasattr(L, "svt_csi_build_bam"):        # (likewise: a CSI index for the sorted outputs, the BAM's fold on the device)
+            P, U64, I32 = C.c_void_p, C.c_uint64, C.c_int32
+            L.svt_csi_depth.restype = C.c_uint32
+            L.svt_csi_depth.argtypes = [U64]
+            for name, argtypes in (("svt_csi_build_bam", [P, U64, I32, U64, P, P, U64, P, P, P]),
+                                   ("svt_csi_build_vcf", [P, U64, P, P, U64, P, U64, C.c_uint32, P, P, P]), ("svt_csi_take", [P, U64]),
+                                   ("svt_bam_index_fold_device", [P, U64, I32, U64, P, P, U64, P, P, P, C.c_int]),
+                                   ("svt_bam_sorted_bgzf_csi_device", [P, U64, P, U64, I32, U64, C.c_int, C.c_uint32, P, U64, P, U64, P, P, P, P, P, P, P, P,
+                                                                       P, C.c_int]),
+                                   ("svt_bam_index_last_times", [C.POINTER(_BamIndexTimes)])):
                 getattr(L, name).restype = C.c_int
                 getattr(L, name).argtypes = argtypes
         L.svt_bam_set_verify.restype = C.c_int
@@ -887,9 +904,11 @@ def vcf_lines_last_times() -> Dict[str, float]:
     return {name: float(getattr(t, name)) for name, _ in _LinesTimes._fields_}
 
 
-def tbx_build(text: bytes, lines: np.ndarray, member_off, src_off=None, payload: int = DEFLATE_MAX_PAYLOAD):
-    """svt_tbx_build + svt_tbx_take: (the uncompressed bytes of the .tbi, 0, 0), or (None, bad_line, bad_kind)"""
-    L = _lines_lib()
+def tbx_build(text: bytes, lines: np.ndarray, member_off, src_off=None, payload: int = DEFLATE_MAX_PAYLOAD, csi: bool = False):
+    """svt_tbx_build + svt_tbx_take: (the uncompressed bytes of the .tbi, 0, 0), or (None, bad_line, bad_kind); csi=True:
+    svt_csi_build_vcf + svt_csi_take, the uncompressed bytes of the .csi"""
+    L = _csi_lib() if csi else _lines_lib()
+    build, take = (L.svt_csi_build_vcf, L.svt_csi_take) if csi else (L.svt_tbx_build, L.svt_tbx_take)
     buf = _text_array(text)
     lines = np.ascontiguousarray(lines, TBX_LINE)
     member_off = np.ascontiguousarray(member_off, np.uint64)
@@ -899,13 +918,13 @@ def tbx_build(text: bytes, lines: np.ndarray, member_off, src_off=None, payload:
     if src is not None and src.shape[0] != lines.shape[0]:
         raise ValueError("src_off must hold an entry per line")
     size, bad, kind = C.c_uint64(0), C.c_uint64(0), C.c_uint32(0)
-    hip._check(L.svt_tbx_build(buf.ctypes.data, len(text), src.ctypes.data if src is not None and src.size else None,
-                               lines.ctypes.data if lines.size else None, lines.shape[0], member_off.ctypes.data, member_off.shape[0] - 1,
-                               int(payload), C.addressof(size), C.addressof(bad), C.addressof(kind)))
+    hip._check(build(buf.ctypes.data, len(text), src.ctypes.data if src is not None and src.size else None,
+                     lines.ctypes.data if lines.size else None, lines.shape[0], member_off.ctypes.data, member_off.shape[0] - 1,
+                     int(payload), C.addressof(size), C.addressof(bad), C.addressof(kind)))
     if bad.value:
         return None, int(bad.value), int(kind.value)
     out = np.zeros(max(size.value, 1), np.uint8)
-    hip._check(L.svt_tbx_take(out.ctypes.data, size.value))
+    hip._check(take(out.ctypes.data, size.value))
     return out[:size.value].tobytes(), 0, 0
 
 
@@ -1012,3 +1031,86 @@ def bai_build(spans: np.ndarray, n_ref: int, member_start, member_off):
     out = np.zeros(max(size.value, 1), np.uint8)
     hip._check(L.svt_bai_take(out.ctypes.data, size.value))
     return out[:size.value].tobytes(), 0, 0
+
+
+# ---- a CSI index for the sorted outputs: the depth, the BAM's fold on the host and on the device (include/svtyper_reads.h) ----------
+def _csi_lib():
+    L = _lib()
+    if not hasattr(L, "svt_csi_build_bam"):
+        raise hip.SvtyperHipError("this libsvtyper_hip.so has no svt_csi_build_bam (built before CSI indexes were written)")
+    return L
+
+
+def csi_depth(max_end: int) -> int:
+    """svt_csi_depth: the depth of the scheme (14, depth) a file gets whose largest end (BAM: longest l_ref) is `max_end`"""
+    return int(_csi_lib().svt_csi_depth(int(max_end)))
+
+
+def _member_tables(member_start, member_off):
+    member_start = np.ascontiguousarray(member_start, np.uint64)
+    member_off = np.ascontiguousarray(member_off, np.uint64)
+    if member_start.shape[0] < 1 or member_start.shape[0] != member_off.shape[0]:
+        raise ValueError("member_start and member_off must hold n + 1 entries each")
+    return member_start, member_off
+
+
+def _csi_taken(L, size, bad, kind):
+    if bad.value:
+        return None, int(bad.value), int(kind.value)
+    out = np.zeros(max(size.value, 1), np.uint8)
+    hip._check(L.svt_csi_take(out.ctypes.data, size.value))
+    return out[:size.value].tobytes(), 0, 0
+
+
+def csi_build_bam(spans: np.ndarray, n_ref: int, l_ref_max: int, member_start, member_off, device: Optional[int] = None):
+    """svt_csi_build_bam (device None) / svt_bam_index_fold_device, + svt_csi_take: (the uncompressed bytes of the .csi, 0, 0), or
+    (None, bad_record, bad_kind).  Arguments as bai_build; `l_ref_max`: the longest reference of the header"""
+    L = _csi_lib()
+    spans = np.ascontiguousarray(spans, BAM_SPAN)
+    member_start, member_off = _member_tables(member_start, member_off)
+    size, bad, kind = C.c_uint64(0), C.c_uint64(0), C.c_uint32(0)
+    args = [spans.ctypes.data if spans.size else None, spans.shape[0], int(n_ref), int(l_ref_max), member_start.ctypes.data, member_off.ctypes.data,
+            member_start.shape[0] - 1, C.addressof(size), C.addressof(bad), C.addressof(kind)]
+    if device is None:
+        hip._check(L.svt_csi_build_bam(*args))
+    else:
+        hip._check(L.svt_bam_index_fold_device(*args, int(device)))
+    return _csi_taken(L, size, bad, kind)
+
+
+def bam_sorted_bgzf_csi_device(data: bytes, rec_off, n_ref: int, l_ref_max: int, sort: bool, huffman: str = "fixed", device: int = 0):
+    """svt_bam_sorted_bgzf_csi_device: bam_sorted_bgzf_device with the CSI fold on the device behind the members -- (members, out_off,
+    member_start, spans, perm, csi bytes or None, index_bad, index_kind, 0, 0), or (None, ..., bad_record, bad_kind) where sorting
+    met a record that cannot be sorted.  index_bad: the 1-based number, in written order, of a record the index cannot hold"""
+    L = _csi_lib()
+    buf = _text_array(data)
+    rec_off = np.ascontiguousarray(rec_off, np.uint64)
+    n = int(rec_off.shape[0]) - 1
+    if n < 0:
+        raise ValueError("rec_off must hold n + 1 entries")
+    member_capacity = n + len(data) // DEFLATE_MAX_PAYLOAD + 2
+    capacity = len(data) + DEFLATE_SLOT_EXTRA * member_capacity
+    out = np.zeros(max(capacity, 1), np.uint8)
+    out_off = np.zeros(member_capacity + 1, np.uint64)
+    member_start = np.zeros(member_capacity + 1, np.uint64)
+    spans = np.zeros(max(n, 1), BAM_SPAN)
+    perm = np.zeros(max(n, 1), np.uint64)
+    n_members, bad, kind, size = C.c_uint64(0), C.c_uint64(0), C.c_uint32(0), C.c_uint64(0)
+    index_bad, index_kind = C.c_uint64(0), C.c_uint32(0)
+    hip._check(L.svt_bam_sorted_bgzf_csi_device(buf.ctypes.data, len(data), rec_off.ctypes.data, n, int(n_ref), int(l_ref_max), int(bool(sort)),
+                                                int(check_huffman(huffman) == "dynamic"), out.ctypes.data, capacity, out_off.ctypes.data,
+                                                member_capacity, C.addressof(n_members), member_start.ctypes.data, spans.ctypes.data,
+                                                perm.ctypes.data, C.addressof(bad), C.addressof(kind), C.addressof(size),
+                                                C.addressof(index_bad), C.addressof(index_kind), int(device)))
+    if bad.value:
+        return None, None, None, None, None, None, 0, 0, int(bad.value), int(kind.value)
+    m = int(n_members.value)
+    csi, ibad, ikind = _csi_taken(L, size, index_bad, index_kind)
+    return out[:int(out_off[m])], out_off[:m + 1], member_start[:m + 1], spans[:n], perm[:n], csi, ibad, ikind, 0, 0
+
+
+def bam_index_last_times() -> Dict[str, float]:
+    """svt_bam_index_last_times: the kernels of this thread's last device fold, from HIP events; `runs`, and `passes` of the runs' sort"""
+    t = _BamIndexTimes()
+    hip._check(_csi_lib().svt_bam_index_last_times(C.byref(t)))
+    return {name: (int if name in ("runs", "passes") else float)(getattr(t, name)) for name, _ in _BamIndexTimes._fields_ if name != "reserved"}
