@@ -406,6 +406,32 @@ typedef struct svt_bam_sort_times {
     uint32_t reserved;
 } svt_bam_sort_times;
 int svt_bam_sort_last_times(svt_bam_sort_times* times);
+/* ---- first occurrences of a record stream (additions; the ABI number stays: probe for svt_bam_first_host) ----
+ * Which records of a stream (the layout of svt_bam_spans: bytes, len, rec_off with n + 1 non-decreasing offsets) are the first
+ * with their key, in the caller's order.  The key is what `svtyper -w` writes a read once by: the l_read_name - 1 name bytes at
+ * offset 36 and the 16-bit flag at offset 18 (svtyper_amd/csrc/svt_bam_first_rules.h: one piece of source for the host and the
+ * device).  keep[i] = 1 iff no j < i has a key equal to record i's -- same flag, same length, same bytes --, else 0; *n_kept is
+ * the sum of keep.  A record that is not well-formed (its span is below 36 bytes or leaves the bytes, block_size is not the
+ * span's length less 4, l_read_name is 0, or 36 + l_read_name exceeds the span): *bad_record is the 1-based number of the first
+ * such record (SVT_OK, keep undefined); 0 otherwise.  n = 0 is legal; n >= 2^32 or a decreasing rec_off is SVT_ERR_INVALID.
+ * The host keeps a hash set of views into the bytes.  The device (svt_bam_first_kernel.h) hashes every record's key (FNV-1a,
+ * 64 bits), sorts (hash, index) with the stable radix passes of svt_bam_sort_order_device, and lets one lane per sorted
+ * position walk back over its run of equal hashes until it meets an equal key: the sort is stable, so what stands in front
+ * of it there is earlier in the caller's order.  hash_bits (1..64, else SVT_ERR_INVALID; callers pass 64): how many low bits
+ * of the hash are kept -- fewer make distinct keys share a run, which changes the cost and not the answer (tests).        */
+int svt_bam_first_host(const uint8_t* bytes, uint64_t len, const uint64_t* rec_off, uint64_t n, uint8_t* keep, uint64_t* n_kept,
+                       uint64_t* bad_record);
+int svt_bam_first_device(const uint8_t* bytes, uint64_t len, const uint64_t* rec_off, uint64_t n, uint8_t* keep, uint64_t* n_kept,
+                         uint64_t* bad_record, uint32_t hash_bits, int device);
+/* the calling thread's most recent svt_bam_first_device: its kernels by HIP events, the three of the sort summed over its
+ * passes                                                                                                              */
+typedef struct svt_bam_first_times {
+    double hash_kernel_s, histogram_kernel_s, scan_kernel_s, scatter_kernel_s, mark_kernel_s;
+    double total_s;             /* the whole call on the host's clock                                                */
+    uint32_t passes;            /* digits the sort took                                                              */
+    uint32_t reserved;
+} svt_bam_first_times;
+int svt_bam_first_last_times(svt_bam_first_times* times);
 /* The index fold: the bytes of a .bai ("BAI\1", n_ref; per reference its bins with their chunks -- a run of consecutive
  * records with one bin is one chunk --, pseudo-bin 37450 with (first start, last end) and (mapped, unmapped), and the
  * 16 kb linear index; n_bin = 0 and n_intv = 0 for a reference without records; the 64-bit n_no_coor at the end) for

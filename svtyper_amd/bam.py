@@ -304,6 +304,53 @@ def coordinate_header(header: bytes) -> bytes:
     return header[:4] + struct.pack("<i", len(text)) + text + rest
 
 
+def record_of(read) -> bytes:
+    """The record AlignmentFile.write puts behind the others for `read`, block_size first: the record as it was read, without its
+    sequence and qualities (l_seq = 0; `bin` stays the original's), its tag area the original's without the names set_tag was
+    given, those appended in the order they were set.  (The one assembly: the file writer and RecordSink both call it.)"""
+    raw = read._raw
+    l_read_name, n_cigar = raw[8], struct.unpack_from("<H", raw, 12)[0]
+    body_end = 32 + l_read_name + 4 * n_cigar
+    tags = read._tagbytes
+    for key in read._set_tags or ():
+        tags = _without_tag(tags, key)
+    for key in read._set_tags or ():
+        tags += _encode_tag(key, read._tags[key])
+    rec = raw[:16] + b"\0\0\0\0" + raw[20:body_end] + tags
+    return struct.pack("<i", len(rec)) + rec
+
+
+def whole_record(record_bytes) -> bytes:
+    """what write_raw takes: one whole record, block_size and block_size bytes"""
+    if len(record_bytes) < 36 or struct.unpack_from("<i", record_bytes, 0)[0] != len(record_bytes) - 4:
+        raise ValueError("write_raw takes one whole record: block_size and block_size bytes")
+    return bytes(record_bytes)
+
+
+class RecordSink:
+    """A write-only stand-in for the `-w` writer that keeps what it is given: write(read), write_raw(bytes) and close() as
+    AlignmentFile has them in mode 'wb', the records side by side in `data`, record i being data[offsets[i] : offsets[i + 1]] --
+    byte for byte what the file writer would have handed to its BGZF layer (record_of, whole_record).  The sharded `-w` run
+    (sharded.py) gives every rank one and gathers them."""
+
+    def __init__(self):
+        self.data = bytearray()
+        self.offsets = [0]
+        self.closed = False
+
+    def write(self, read) -> None:
+        self.write_raw(record_of(read))
+
+    def write_raw(self, record_bytes) -> None:
+        if self.closed:
+            raise IOError("the record sink is closed")
+        self.data += whole_record(record_bytes)
+        self.offsets.append(len(self.data))
+
+    def close(self) -> None:
+        self.closed = True
+
+
 class _RecordHold:
     """stands where an AlignmentFile's BgzfWriter stands while sort= / index= hold the records: write_record puts the record
     behind the header in ONE growing buffer (the stream close() works on: no second copy is made of it) and notes where it
@@ -317,6 +364,26 @@ class _RecordHold:
     def write_record(self, data: bytes) -> None:
         self.data += data
         self.offsets.append(len(self.data))
+
+    def extend(self, data, rec_off, chosen) -> None:
+        """the records `chosen` (rising indices) of data / rec_off (AlignmentFile.write_raw_many) behind the others: their bytes in
+        one piece where they are all of them, else gathered run by run of neighbours (numpy: nothing per record)"""
+        import numpy as np
+        if len(chosen) == 0:
+            return
+        lens = (rec_off[1:] - rec_off[:-1])[chosen]
+        if len(chosen) == rec_off.shape[0] - 1:
+            piece = memoryview(data)[int(rec_off[0]):int(rec_off[-1])]
+        else:
+            src = np.frombuffer(data, np.uint8)
+            # a run: chosen records that are neighbours in `data`; one slice each
+            heads = np.flatnonzero(np.concatenate(([True], chosen[1:] != chosen[:-1] + 1)))
+            tails = np.concatenate((heads[1:], [len(chosen)])) - 1
+            lo, hi = rec_off[:-1][chosen[heads]].tolist(), rec_off[1:][chosen[tails]].tolist()
+            piece = np.concatenate([src[a:b] for a, b in zip(lo, hi)]).tobytes() if len(lo) > 1 else bytes(src[lo[0]:hi[0]])
+        base = self.offsets[-1]
+        self.data += piece
+        self.offsets.extend((base + np.cumsum(lens)).tolist())
 
     def close(self) -> None:
         finish, self._finish = self._finish, None
@@ -688,25 +755,46 @@ class AlignmentFile:
         a float as f."""
         if self._writer is None:
             raise IOError("%s is not open for writing" % self.filename)
-        raw = read._raw
-        l_read_name, n_cigar = raw[8], struct.unpack_from("<H", raw, 12)[0]
-        body_end = 32 + l_read_name + 4 * n_cigar
-        tags = read._tagbytes
-        for key in read._set_tags or ():
-            tags = _without_tag(tags, key)
-        for key in read._set_tags or ():
-            tags += _encode_tag(key, read._tags[key])
-        rec = raw[:16] + b"\0\0\0\0" + raw[20:body_end] + tags
-        self._writer.write_record(struct.pack("<i", len(rec)) + rec)
+        self._writer.write_record(record_of(read))
 
     def write_raw(self, record_bytes: bytes) -> None:
         """One FINISHED record behind the others -- its block_size and everything behind it, as write() would have put it
         together (the device reader's evidence dump hands over such records) -- through the same BgzfWriter.write_record."""
         if self._writer is None:
             raise IOError("%s is not open for writing" % self.filename)
-        if len(record_bytes) < 36 or struct.unpack_from("<i", record_bytes, 0)[0] != len(record_bytes) - 4:
-            raise ValueError("write_raw takes one whole record: block_size and block_size bytes")
-        self._writer.write_record(bytes(record_bytes))
+        self._writer.write_record(whole_record(record_bytes))
+
+    def write_raw_many(self, data, rec_off, keep=None) -> None:
+        """FINISHED records side by side -- record i is data[rec_off[i] : rec_off[i + 1]] (n + 1 offsets, block_size first, as
+        write_raw takes them one at a time) --, those with keep[i] != 0 (all of them without `keep`), in that order.  A writer that
+        holds its records (sort= / index=) takes the kept bytes and their offsets in one append: no Python runs per record, and the
+        records are checked where close() makes their span table.  A streaming writer hands them to write_raw one by one."""
+        import numpy as np
+        if self._writer is None:
+            raise IOError("%s is not open for writing" % self.filename)
+        rec_off = np.ascontiguousarray(rec_off, np.int64)
+        n = rec_off.shape[0] - 1
+        if n < 0 or rec_off[0] < 0 or rec_off[-1] > len(data) or (np.diff(rec_off) < 0).any():
+            raise ValueError("write_raw_many: rec_off holds n + 1 rising offsets into data")
+        if keep is not None and len(keep) != n:
+            raise ValueError("write_raw_many: keep holds one entry per record")
+        chosen = np.arange(n) if keep is None else np.flatnonzero(np.asarray(keep))
+        if self._held is not None:
+            if len(chosen):             # what write_raw asks of a record, of all of them at once
+                lo, lens = rec_off[:-1][chosen], (rec_off[1:] - rec_off[:-1])[chosen]
+                if (lens < 36).any():
+                    raise ValueError("write_raw takes one whole record: block_size and block_size bytes")
+                src = np.frombuffer(data, np.uint8)
+                size = (src[lo].astype(np.int64) | src[lo + 1].astype(np.int64) << 8 | src[lo + 2].astype(np.int64) << 16
+                        | src[lo + 3].astype(np.int64) << 24)
+                if (size != lens - 4).any():
+                    raise ValueError("write_raw takes one whole record: block_size and block_size bytes")
+            self._held.extend(data, rec_off, chosen)
+            return
+        view = memoryview(data)
+        lo, hi = rec_off[:-1][chosen].tolist(), rec_off[1:][chosen].tolist()
+        for a, b in zip(lo, hi):
+            self.write_raw(view[a:b])
 
     # ---- iteration
     def _next_record(self) -> Optional[AlignedSegment]:

@@ -186,7 +186,7 @@ class Classic(Driver):
 def sv_genotype(bam_string, vcf_in, vcf_out, min_aligned, split_weight, disc_weight, num_samp, lib_info_path,
                 debug, alignment_outpath, ref_fasta, sum_quals, max_reads, max_ci_dist, *, engine=None, geometry="host",
                 reader=None, stats=None, inflate="host", library_scan="host", verify="off", deflate="zlib", huffman="fixed",
-                alignment_sort=False, alignment_index=None):
+                alignment_sort=False, alignment_index=None, alignment_out=None):
     """`alignment_outpath` (-w): the reads that entered the tallies go to a BAM, tagged XV:A:R / XV:A:A as the reference tags them
     (driver.tag_and_write; the tags that depend on p_concordant come from the device, svt_batch_verdicts).  Legal with
     reader="python" (what reader=None then means) or reader="device" (the reads are cut and tagged on the GPU: the evidence dump of
@@ -197,7 +197,9 @@ def sv_genotype(bam_string, vcf_in, vcf_out, min_aligned, split_weight, disc_wei
     stable coordinate order, its header saying SO:coordinate; `alignment_index="bai"` (--bai): its index beside it, at
     alignment_outpath + ".bai"; `alignment_index="csi"` (--alignment-csi): a CSI index instead, at alignment_outpath + ".csi", which
     also holds records beyond 2^29 (bam.AlignmentFile's sort= / index= / csi=: both hold every record until the end; BamOrderError for records
-    that cannot be sorted or indexed).  ValueError for either without `alignment_outpath`."""
+    that cannot be sorted or indexed).  ValueError for either without `alignment_outpath`.  `alignment_out`: a writer that takes the
+    dump's records instead of a file opened at `alignment_outpath` (write / write_raw / close, e.g. bam.RecordSink: what
+    sharded.sv_genotype_sharded gives every rank); the checks above apply as they do to a path."""
     check_huffman(huffman, check_deflate(deflate))
     run = Classic(bam_string, vcf_in, vcf_out, min_aligned, split_weight, disc_weight, num_samp, lib_info_path, debug, ref_fasta,
                   sum_quals, max_reads, max_ci_dist)
@@ -206,6 +208,7 @@ def sv_genotype(bam_string, vcf_in, vcf_out, min_aligned, split_weight, disc_wei
     run.huffman = huffman
     run.alignment_sort = bool(alignment_sort)
     run.alignment_index = alignment_index
+    run.alignment_out = alignment_out
     return run.run(CHUNK_UNITS, engine=engine, geometry=geometry, reader=reader, stats=stats, inflate=inflate,
                    library_scan=library_scan, verify=verify)
 
@@ -234,6 +237,8 @@ def get_args():
         p.add_argument("--sort-alignment", dest="alignment_sort", action="store_true", help=argparse.SUPPRESS)
         p.add_argument("--bai", dest="alignment_bai", action="store_true", help=argparse.SUPPRESS)
         p.add_argument("--alignment-csi", dest="alignment_csi", action="store_true", help=argparse.SUPPRESS)
+        # under torch.distributed.run: the ranks' dumps gathered onto rank 0, which writes the one `-w` BAM (sharded.sv_genotype_sharded)
+        p.add_argument("--gather-alignment", dest="alignment_gather", action="store_true", help=argparse.SUPPRESS)
     args = parse_arguments(p, "BAM or CRAM file(s), comma-separated if genotyping multiple samples", None, own)
     if (args.alignment_sort or args.alignment_bai) and args.alignment_outpath is None:
         p.error("--sort-alignment and --bai need -w/--write_alignment")
@@ -241,13 +246,17 @@ def get_args():
         p.error("--alignment-csi needs -w/--write_alignment")
     if args.alignment_csi and args.alignment_bai:
         p.error("--alignment-csi and --bai name two formats for one index: give one of them")
+    if args.alignment_gather and args.alignment_outpath is None:
+        p.error("--gather-alignment needs -w/--write_alignment")
+    if args.alignment_gather and sharded.job() is None:
+        p.error("--gather-alignment is for a run of several ranks under torch.distributed.run: one process writes its dump itself")
     return args
 
 
 def main():
     args = get_args()
     if args.alignment_outpath is not None:
-        if sharded.job() is not None:
+        if sharded.job() is not None and not args.alignment_gather:
             raise ValueError(sharded.WRITE_ALIGNMENT_SHARDED)
         if args.reader is None:
             args.reader = "python"      # the reader that keeps the reads it tallied (sv_genotype: reader=None with -w)
@@ -257,7 +266,7 @@ def main():
             args.sum_quals, args.max_reads, args.max_ci_dist)
     own = dict(deflate=args.deflate, huffman=args.huffman)      # (of this program alone: the `-w` BAM)
     order = dict(alignment_sort=args.alignment_sort, alignment_index="csi" if args.alignment_csi else "bai" if args.alignment_bai else None)
-    return run_main(functools.partial(sv_genotype, **own, **order), functools.partial(sharded.sv_genotype_sharded, **own), call, args)
+    return run_main(functools.partial(sv_genotype, **own, **order), functools.partial(sharded.sv_genotype_sharded, **own, **order, alignment_gather=args.alignment_gather), call, args)
 
 
 def cli():

@@ -1,7 +1,7 @@
 // svt_entry_bam_sort.h -- part of the single translation unit svtyper_hip.hip (included there, in order, behind
 // svt_entry_vcf_lines.h; not a stand-alone header): BAM records as spans on the device.  What is this header's: the span table
 // (keys_resident: svt_bam_keys_kernel writes spans, keys and their AND / OR per workgroup, the host combines those), the radix
-// passes over the digits in which the keys differ (sort_resident: svt_bam_histogram_kernel, svt_bam_scan_kernel and
+// passes over the digits in which the keys differ (radix_passes, and sort_resident over them: svt_bam_histogram_kernel, svt_bam_scan_kernel and
 // svt_bam_scatter_kernel per digit), the argument checks and the caller's arrays.  What it shares lives in svt_entry_deflate.h:
 // the upload (OrderedCall::begin), the gather behind the header copy (gather_resident<svt_bam_span>), the members from
 // bsr::cut_members' boundaries (deflate_members), the marks that time the kernels.  C ABI: svt_bam_spans_device,
@@ -59,27 +59,33 @@ static int keys_resident(BamSortCall& c, uint64_t len, const uint64_t* rec_off, 
     return SVT_OK;
 }
 
-// n (key, index) pairs in c.d_keys[0] / c.d_idx[0] -> order[j]: the index that comes j-th in stable order by key
-static int sort_resident(BamSortCall& c, uint64_t n, uint64_t key_and, uint64_t key_or, std::vector<uint32_t>& order, int device)
+// The radix passes over n (key, index) pairs in c.d_keys[0] / c.d_idx[0], launched on c.s: one histogram, scan and scatter per
+// 8-bit digit in which the keys differ, least significant first.  The pairs end up, in stable order by key, in c.d_keys[src] /
+// c.d_idx[src] (no pass: where they were).  Both users of the sort go through here: the record sort below (with its caller the
+// index fold, svt_entry_bam_index.h) and the first-occurrence pass (svt_entry_bam_first.h).
+struct RadixPasses {
+    uint32_t passes = 0;
+    int src = 0;
+    std::vector<size_t> at;                         // four marks per pass
+};
+
+static int radix_passes(BamSortCall& c, uint64_t n, uint64_t key_and, uint64_t key_or, RadixPasses& r, int device)
 {
-    order.resize(n);
     const uint64_t differ = n ? key_and ^ key_or : 0;
-    uint32_t shifts[8], passes = 0;
+    uint32_t shifts[8];
+    r = RadixPasses();
     for (uint32_t d = 0; d < 8; ++d)
-        if (differ >> (8 * d) & 255) shifts[passes++] = 8 * d;
-    g_bam_sort_times.passes = passes;
-    if (passes == 0) {                              // every key is the same one: the order of arrival
-        for (uint64_t i = 0; i < n; ++i) order[i] = (uint32_t)i;
-        return SVT_OK;
-    }
+        if (differ >> (8 * d) & 255) shifts[r.passes++] = 8 * d;
+    if (r.passes == 0) return SVT_OK;
     const uint32_t n_tiles = (uint32_t)((n + kSortTile - 1) / kSortTile);
     const unsigned grid = lines_grid(n_tiles, device);
     SVT_TRY(c.d_keys[1].alloc(n * sizeof(uint64_t)));
     SVT_TRY(c.d_idx[1].alloc(n * sizeof(uint32_t)));
     SVT_TRY(c.d_hist.alloc((uint64_t)n_tiles * 256 * sizeof(uint32_t)));
     int src = 0;
-    std::vector<size_t> at(4 * passes);
-    for (uint32_t p = 0; p < passes; ++p) {
+    std::vector<size_t>& at = r.at;
+    at.resize(4 * r.passes);
+    for (uint32_t p = 0; p < r.passes; ++p) {
         SVT_TRY(c.mark(&at[4 * p]));
         hipLaunchKernelGGL(svt_bam_histogram_kernel, dim3(grid), dim3(kSortBlock), 0, c.s, c.d_keys[src].as<uint64_t>(), n, n_tiles, shifts[p],
                            c.d_hist.as<uint32_t>());
@@ -94,13 +100,35 @@ static int sort_resident(BamSortCall& c, uint64_t n, uint64_t key_and, uint64_t 
         SVT_TRY(c.mark(&at[4 * p + 3]));
         src ^= 1;
     }
-    SVT_TRY(d2h_staged(order.data(), c.d_idx[src].p, n * sizeof(uint32_t), c.s));
-    HIP_TRY(hipStreamSynchronize(c.s));
-    for (uint32_t p = 0; p < passes; ++p) {
-        SVT_TRY(c.between(at[4 * p], at[4 * p + 1], &g_bam_sort_times.histogram_kernel_s));
-        SVT_TRY(c.between(at[4 * p + 1], at[4 * p + 2], &g_bam_sort_times.scan_kernel_s));
-        SVT_TRY(c.between(at[4 * p + 2], at[4 * p + 3], &g_bam_sort_times.scatter_kernel_s));
+    r.src = src;
+    return SVT_OK;
+}
+
+// the passes' kernels by their marks, once c.s has passed them: added to the three sums
+static int radix_times(BamSortCall& c, const RadixPasses& r, double* histogram_s, double* scan_s, double* scatter_s)
+{
+    for (uint32_t p = 0; p < r.passes; ++p) {
+        SVT_TRY(c.between(r.at[4 * p], r.at[4 * p + 1], histogram_s));
+        SVT_TRY(c.between(r.at[4 * p + 1], r.at[4 * p + 2], scan_s));
+        SVT_TRY(c.between(r.at[4 * p + 2], r.at[4 * p + 3], scatter_s));
     }
+    return SVT_OK;
+}
+
+// n (key, index) pairs in c.d_keys[0] / c.d_idx[0] -> order[j]: the index that comes j-th in stable order by key
+static int sort_resident(BamSortCall& c, uint64_t n, uint64_t key_and, uint64_t key_or, std::vector<uint32_t>& order, int device)
+{
+    order.resize(n);
+    RadixPasses r;
+    SVT_TRY(radix_passes(c, n, key_and, key_or, r, device));
+    g_bam_sort_times.passes = r.passes;
+    if (r.passes == 0) {                            // every key is the same one: the order of arrival
+        for (uint64_t i = 0; i < n; ++i) order[i] = (uint32_t)i;
+        return SVT_OK;
+    }
+    SVT_TRY(d2h_staged(order.data(), c.d_idx[r.src].p, n * sizeof(uint32_t), c.s));
+    HIP_TRY(hipStreamSynchronize(c.s));
+    SVT_TRY(radix_times(c, r, &g_bam_sort_times.histogram_kernel_s, &g_bam_sort_times.scan_kernel_s, &g_bam_sort_times.scatter_kernel_s));
     // the kernels' order is a permutation or it is not theirs: what the gather and the callers rely on
     std::vector<uint8_t> seen(n, 0);
     for (uint64_t j = 0; j < n; ++j) {

@@ -29,6 +29,7 @@
 #include "../../include/svtyper_reads.h"
 #include "svt_bai_index.h"
 #include "svt_bam_index.h"
+#include "svt_bam_first_rules.h"
 #include "svt_bam_sort_rules.h"
 #include "svt_bgzf.h"
 #include "svt_dump_rules.h"

@@ -1,5 +1,6 @@
 // svt_reads_bam_sort_entries.h -- part of the translation unit svt_reads.cpp (included there, in order; not a stand-alone header):
-// the host entry points over BAM records as spans (svt_bam_sort_rules.h) and the .bai fold (svt_bai_index.h).
+// the host entry points over BAM records as spans (svt_bam_sort_rules.h), the .bai fold (svt_bai_index.h) and the first occurrences
+// of a record stream (svt_bam_first_rules.h).
 extern "C" {
 
 int svt_bam_spans_host(const uint8_t* bytes, uint64_t len, const uint64_t* rec_off, uint64_t n, int32_t n_ref, svt_bam_span* spans, uint64_t* key_and,
@@ -22,6 +23,18 @@ int svt_bam_sort_order_host(const svt_bam_span* spans, uint64_t n, uint64_t* per
         if ((n && (!spans || !perm)) || !bad_record || !bad_kind) return fail(SVT_ERR_INVALID, "null argument");
         if (n >> 32) return fail(SVT_ERR_INVALID, "svt_bam_sort_order: too many records in one call (< 2^32)");
         *bad_record = svt::bsr::sort_order(spans, n, perm, *bad_kind);
+        return SVT_OK;
+    });
+}
+
+int svt_bam_first_host(const uint8_t* bytes, uint64_t len, const uint64_t* rec_off, uint64_t n, uint8_t* keep, uint64_t* n_kept, uint64_t* bad_record)
+{
+    return guarded([&]() -> int {
+        if ((len && !bytes) || !rec_off || (n && !keep) || !n_kept || !bad_record) return fail(SVT_ERR_INVALID, "null argument");
+        if (n >> 32) return fail(SVT_ERR_INVALID, "svt_bam_first: too many records in one call (< 2^32)");
+        for (uint64_t i = 0; i < n; ++i)
+            if (rec_off[i] > rec_off[i + 1]) return fail(SVT_ERR_INVALID, "svt_bam_first: rec_off must not decrease");
+        *bad_record = svt::bfr::first_host(bytes, len, rec_off, n, keep, *n_kept);
         return SVT_OK;
     });
 }

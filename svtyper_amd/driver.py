@@ -17,6 +17,7 @@ route, the `stats=` block.  What the reference's two programs do differently is 
              finish(unpaired)             the end of a run
     data     alignment_outpath            (`svtyper -w`) the evidence dump: tag_and_write below, per chunk, in output order -- the reads of
                                                   reader="python", or the finished records of reader="device" (svt_dump_kernel.h)
+             alignment_out                a writer that stands in for that BAM (bam.RecordSink: the sharded run, sharded.py)
              alignment_sort, alignment_index   (`--sort-alignment`, `--bai` / `--alignment-csi`) that BAM coordinate-sorted / with its .bai or .csi: the writer's
                                                   sort= and index= (bam.AlignmentFile), which hold the records until close()
 
@@ -92,6 +93,22 @@ def tag_and_write(evidence, out_bam, written: set) -> None:
                         written.add(key)
 
 
+def open_alignment_writer(path, template_path, deflate, huffman, alignment_sort, alignment_index, device):
+    """The `-w` BAM opened for writing, its header the template file's: with the run's compressor, and its order and index as the
+    writer spells them (bam.AlignmentFile: sort=, index="bai", csi=True).  The one-process run opens it before its first record,
+    the gathered run (sharded.py) on rank 0 once every rank's records are there."""
+    template = AlignmentFile(template_path, "rb")
+    order = dict(sort=True) if alignment_sort else {}
+    if alignment_index is not None:         # (the writer spells a CSI as pysam does: the index asked for, csi=True)
+        order["index"] = "bai"
+        if alignment_index == "csi":
+            order["csi"] = True
+    try:
+        return AlignmentFile(path, "wb", template=template, deflate=deflate, huffman=huffman, device=device, **order)
+    finally:
+        template.close()
+
+
 def _write_dumped(records, out_bam, written: set) -> None:
     """A unit of the device reader's evidence dump (svt_dump_rules.h: tagged and cut as above, on the GPU): record by record, the
     key (query_name, flag) read at their fixed offsets, written unless the run wrote it before."""
@@ -124,6 +141,8 @@ class Driver:
     huffman = "fixed"                   # ... and into which block, where it is the library's own compressor
     alignment_sort = False              # the `-w` BAM in coordinate order (bam.AlignmentFile: sort=)
     alignment_index = None              # ... and "bai" / "csi": its index beside it (index="bai"; "csi": with csi=True)
+    alignment_out = None                # a writer to use instead of opening alignment_outpath (write / write_raw / close: bam.RecordSink
+                                        # under sharded.py); the run is then a `-w` run whether or not a path is given
 
     def __init__(self, bam_string, vcf_in, vcf_out, min_aligned, split_weight, disc_weight, num_samp, lib_info_path, debug,
                  ref_fasta, sum_quals, max_reads, max_ci_dist, n_threads=0):
@@ -136,7 +155,7 @@ class Driver:
 
     def run(self, chunk_units, engine=None, geometry="host", reader=None, stats=None, inflate="host", library_scan="host",
             verify="off"):
-        writing = self.alignment_outpath is not None
+        writing = self.alignment_outpath is not None or self.alignment_out is not None
         if not writing and (self.alignment_sort or self.alignment_index is not None):
             raise ValueError("alignment_sort / alignment_index (--sort-alignment, --bai) need -w/--write_alignment: they are about that BAM")
         if self.alignment_index not in (None, "bai", "csi"):
@@ -169,16 +188,11 @@ class Driver:
         self.samples = [setup_sample(b, lib_info, self.num_samp, MIN_LIB_PREVALENCE, nb, library_scan, scan_device, inflate)
                         for b, nb in zip(bams, native or [None] * len(bams))]
         out_bam, written = None, set()
-        if writing:     # classic.py:161-166: the first alignment file is the template, its header is the dump's
-            template = AlignmentFile(paths[0], "rb")
-            order = dict(sort=True) if self.alignment_sort else {}
-            if self.alignment_index is not None:    # (the writer spells a CSI as pysam does: the index asked for, csi=True)
-                order["index"] = "bai"
-                if self.alignment_index == "csi":
-                    order["csi"] = True
-            out_bam = AlignmentFile(self.alignment_outpath, "wb", template=template, deflate=self.deflate, huffman=self.huffman,
-                                    device=getattr(engine, "device", 0), **order)
-            template.close()
+        if self.alignment_out is not None:
+            out_bam = self.alignment_out
+        elif writing:   # classic.py:161-166: the first alignment file is the template, its header is the dump's
+            out_bam = open_alignment_writer(self.alignment_outpath, paths[0], self.deflate, self.huffman, self.alignment_sort,
+                                            self.alignment_index, getattr(engine, "device", 0))
         self.write_library_file()
         if self.vcf_in is None:
             if out_bam is not None:     # classic.py:177-180
@@ -190,7 +204,8 @@ class Driver:
             if out_bam is not None:     # classic.py:527-531
                 out_bam.close()
 
-    def check_write_alignment(self, reader, geometry, engine):
+    @staticmethod
+    def check_write_alignment(reader, geometry, engine):
         """`-w` needs the reads of a chunk alive when its verdicts come back, canonical records to give verdicts on, and an
         engine that gives them."""
         # reader="device" hands over the reads as finished records (the evidence dump) when the engine is the one whose batches the

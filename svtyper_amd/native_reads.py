@@ -148,6 +148,13 @@ class _BamSortTimes(C.Structure):
                 ("reserved", C.c_uint32)]
 
 
+class _BamFirstTimes(C.Structure):
+    """include/svtyper_reads.h: svt_bam_first_times"""
+    _fields_ = [("hash_kernel_s", C.c_double), ("histogram_kernel_s", C.c_double), ("scan_kernel_s", C.c_double),
+                ("scatter_kernel_s", C.c_double), ("mark_kernel_s", C.c_double), ("total_s", C.c_double), ("passes", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
 class _BamIndexTimes(C.Structure):
     _fields_ = [(name, C.c_double) for name in ("record_kernel_s", "scan_kernel_s", "sort_kernel_s", "loffset_kernel_s", "reference_kernel_s",
                                                 "total_s")] + [("runs", C.c_uint64), ("passes", C.c_uint32), ("reserved", C.c_uint32)]
@@ -306,6 +313,13 @@ def _lib():
                                    ("svt_bam_sorted_bgzf_csi_device", [P, U64, P, U64, I32, U64, C.c_int, C.c_uint32, P, U64, P, U64, P, P, P, P, P, P, P, P,
                                                                        P, C.c_int]),
                                    ("svt_bam_index_last_times", [C.POINTER(_BamIndexTimes)])):
+                getattr(L, name).restype = C.c_int
+                getattr(L, name).argtypes = argtypes
+        if hasattr(L, "svt_bam_first_host"):       # (likewise: first occurrences of a record stream, the gathered `-w` dump)
+            P, U64 = C.c_void_p, C.c_uint64
+            for name, argtypes in (("svt_bam_first_host", [P, U64, P, U64, P, P, P]),
+                                   ("svt_bam_first_device", [P, U64, P, U64, P, P, P, C.c_uint32, C.c_int]),
+                                   ("svt_bam_first_last_times", [C.POINTER(_BamFirstTimes)])):
                 getattr(L, name).restype = C.c_int
                 getattr(L, name).argtypes = argtypes
         L.svt_bam_set_verify.restype = C.c_int
@@ -1012,6 +1026,46 @@ def bam_sort_last_times() -> Dict[str, float]:
     t = _BamSortTimes()
     hip._check(_spans_lib().svt_bam_sort_last_times(C.byref(t)))
     return {name: (int if name == "passes" else float)(getattr(t, name)) for name, _ in _BamSortTimes._fields_ if name != "reserved"}
+
+
+def _first_lib():
+    L = _lib()
+    if not hasattr(L, "svt_bam_first_host"):
+        raise hip.SvtyperHipError("this libsvtyper_hip.so has no svt_bam_first_host (built before the gathered -w dump)")
+    return L
+
+
+def bam_first(data, rec_off, device: Optional[int] = None, hash_bits: int = 64) -> Tuple[Optional[np.ndarray], int]:
+    """svt_bam_first_host (device None) / _device: (keep, 0) -- keep[i] = 1 iff no record in front of record i of
+    data[rec_off[i] .. rec_off[i + 1]) has its (query name, flag), one uint8 each --, or (None, the 1-based number of the first
+    record that is not well-formed).  `hash_bits` (the device alone): the low bits of the key's hash the device sorts by."""
+    L = _first_lib()
+    buf = _text_array(data)
+    rec_off = np.ascontiguousarray(rec_off, np.uint64)
+    n = int(rec_off.shape[0]) - 1
+    if n < 0:
+        raise ValueError("rec_off must hold n + 1 entries")
+    keep = np.zeros(max(n, 1), np.uint8)
+    n_kept, bad = C.c_uint64(0), C.c_uint64(0)
+    args = [buf.ctypes.data, len(data), rec_off.ctypes.data, n, keep.ctypes.data, C.addressof(n_kept), C.addressof(bad)]
+    if device is None:
+        hip._check(L.svt_bam_first_host(*args))
+    else:
+        hip._check(L.svt_bam_first_device(*args, int(hash_bits), int(device)))
+    if bad.value:
+        return None, int(bad.value)
+    keep = keep[:n]
+    if int(keep.sum()) != n_kept.value:
+        raise hip.SvtyperHipError("svt_bam_first: n_kept is not the sum of keep")
+    return keep, 0
+
+
+def bam_first_last_times() -> Dict[str, float]:
+    """svt_bam_first_last_times: the kernels of this thread's last svt_bam_first_device, from HIP events (the sort's three summed
+    over its passes), and `passes`: the digits the sort took"""
+    t = _BamFirstTimes()
+    hip._check(_first_lib().svt_bam_first_last_times(C.byref(t)))
+    return {name: (int if name == "passes" else float)(getattr(t, name)) for name, _ in _BamFirstTimes._fields_ if name != "reserved"}
 
 
 def bai_build(spans: np.ndarray, n_ref: int, member_start, member_off):

@@ -255,15 +255,115 @@ def finish() -> None:
 
 
 WRITE_ALIGNMENT_SHARDED = ("-w/--write_alignment is not available under torch.distributed.run: every rank would write the same "
-                           "file; run the dump in one process")
+                           "file; run the dump in one process, or give --gather-alignment (alignment_gather=True): the ranks' dumps "
+                           "are then gathered onto rank 0, which holds all of them in host memory and writes the one file")
 
 
-def sv_genotype_sharded(bam_string, vcf_in, vcf_out, *rest, rank: int, world: int, **kw) -> None:
-    """classic.sv_genotype's arguments (lib_info_path is the 8th positional, alignment_outpath the 10th) plus rank / world."""
+def _check_gathered_write(path, world, kw) -> str:
+    """What a gathered `-w` run asks of its arguments, on every rank and in front of the first collective: a rank that raised
+    alone would leave the others waiting in a gather.  These are the checks the run itself makes later (classic.sv_genotype,
+    Driver.run), in their words.  -> the reader the run uses"""
+    from .bam import check_deflate, check_huffman
+    from .driver import Driver
+    from .pipeline import check_inflate, check_library_scan, check_verify, resolve_reader
+    if path is None:
+        raise ValueError("alignment_gather (--gather-alignment) needs -w/--write_alignment: it is about that BAM")
+    if world < 2:
+        raise ValueError("alignment_gather (--gather-alignment) is for a job of several ranks (torch.distributed.run): one process "
+                         "writes its dump itself")
+    check_huffman(kw.get("huffman", "fixed"), check_deflate(kw.get("deflate", "zlib")))
+    if kw.get("alignment_index") not in (None, "bai", "csi"):
+        raise ValueError("alignment_index must be None, 'bai' or 'csi', not %r" % (kw.get("alignment_index"),))
+    reader = resolve_reader(kw.get("reader") or "python")
+    Driver.check_write_alignment(reader, kw.get("geometry", "host"), kw.get("engine"))
+    check_inflate(reader, kw.get("inflate", "host"))
+    check_library_scan(reader, kw.get("library_scan", "host"))
+    check_verify(kw.get("verify", "off"))
+    return reader
+
+
+def _gather_records(sink, rank: int, world: int):
+    """Every rank's RecordSink onto rank 0: one exchange of (bytes, records) per rank, then the record bytes and the records'
+    lengths (uint32) through distributed.gather_bytes.  -> (bytes uint8, lengths uint32, records per rank) on rank 0, None elsewhere."""
+    import numpy as np
+    import torch
+    import torch.distributed as dist
+    from . import distributed as D
+
+    device = _backend_device()
+    raw = np.frombuffer(sink.data, np.uint8)
+    lens = np.diff(np.asarray(sink.offsets, np.int64)).astype(np.uint32)
+    sizes = torch.zeros(2 * world, dtype=torch.int64, device=device)
+    sizes[2 * rank], sizes[2 * rank + 1] = raw.size, lens.size
+    dist.all_reduce(sizes)
+    sizes = [int(x) for x in sizes.tolist()]
+    n_bytes, n_records = sizes[0::2], sizes[1::2]
+    got_bytes = D.gather_bytes(torch.from_numpy(raw).to(device), n_bytes, dst=0)
+    got_lens = D.gather_bytes(torch.from_numpy(lens.view(np.uint8).copy()).to(device), [4 * c for c in n_records], dst=0)
+    if rank != 0:
+        return None
+    return got_bytes.cpu().numpy(), got_lens.cpu().numpy().view(np.uint32), n_records
+
+
+def _write_gathered(gathered, path, bam_string, kw) -> dict:
+    """Rank 0, behind the last collective: the ranks' records side by side in rank order, which is output order (plan_shards) --
+    so a key's first occurrence in the stream is the one the one-process run wrote.  native_reads.bam_first marks those (on the
+    engine's device when the members are compressed there, on the host otherwise), and the one writer takes them in one call."""
+    import numpy as np
+    from . import native_reads as nr
+    from .driver import open_alignment_writer
+
+    data, lens, n_records = gathered
+    rec_off = np.concatenate((np.zeros(1, np.uint64), np.cumsum(lens, dtype=np.uint64)))
+    if int(rec_off[-1]) != data.shape[0] or sum(n_records) != lens.shape[0]:
+        raise ValueError("the gathered evidence dump does not end with a whole record")
+    deflate = kw.get("deflate", "zlib")
+    device = getattr(kw.get("engine"), "device", 0)
+    keep, bad = nr.bam_first(data, rec_off, device=device if deflate == "device" else None)
+    if bad:
+        r, before = 0, 0
+        while before + n_records[r] < bad:
+            before += n_records[r]
+            r += 1
+        raise ValueError("the evidence dump of rank %d: its record %d is not a whole BAM record (block_size, read name); nothing was "
+                         "written" % (r, bad - before))
+    out = open_alignment_writer(path, bam_string.split(",")[0], deflate, kw.get("huffman", "fixed"), kw.get("alignment_sort", False),
+                                kw.get("alignment_index"), device)
+    try:
+        out.write_raw_many(data, rec_off, keep)
+    finally:
+        out.close()
+    return {"records": int(lens.shape[0]), "kept": int(keep.sum()), "records_per_rank": list(n_records)}
+
+
+def sv_genotype_sharded(bam_string, vcf_in, vcf_out, *rest, rank: int, world: int, alignment_gather: bool = False, **kw) -> None:
+    """classic.sv_genotype's arguments (lib_info_path is the 8th positional, alignment_outpath the 10th) plus rank / world.
+
+    `alignment_outpath` (-w) is refused unless `alignment_gather=True` (--gather-alignment).  With it, every rank runs its share
+    into a bam.RecordSink -- its own (query_name, flag) set de-duplicates what it meets twice --, the sinks are gathered onto rank 0
+    behind the text, and rank 0 writes the first occurrence of every key in rank order to the one file, with the run's deflate /
+    huffman / alignment_sort / alignment_index: the file of the one-process run.  Rank 0 holds the sum of the dumps in host memory.
+    With `stats=`: rank 0's stats["alignment_gather"] = {"records", "kept", "records_per_rank"}."""
     from .classic import sv_genotype
-    if len(rest) > 6 and rest[6] is not None:
-        raise ValueError(WRITE_ALIGNMENT_SHARDED)
-    run_sharded(sv_genotype, bam_string, vcf_in, vcf_out, *rest, rank=rank, world=world, lib_info_index=4, **kw)
+    path = rest[6] if len(rest) > 6 else None
+    if not alignment_gather:
+        if path is not None:
+            raise ValueError(WRITE_ALIGNMENT_SHARDED)
+        return run_sharded(sv_genotype, bam_string, vcf_in, vcf_out, *rest, rank=rank, world=world, lib_info_index=4, **kw)
+    from .bam import RecordSink
+    kw["reader"] = _check_gathered_write(path, world, kw)
+    if vcf_in is None:                      # classic.py:177-180: the header-only BAM, from rank 0 alone
+        if rank == 0:
+            return sv_genotype(bam_string, None, vcf_out, *rest, **kw)
+        return sv_genotype(bam_string, None, vcf_out, *rest[:6], None, *rest[7:], alignment_out=RecordSink(), **kw)
+    sink = RecordSink()
+    run_sharded(sv_genotype, bam_string, vcf_in, vcf_out, *rest[:6], None, *rest[7:], rank=rank, world=world, lib_info_index=4,
+                alignment_out=sink, **kw)
+    gathered = _gather_records(sink, rank, world)
+    if rank == 0:                           # (every collective of the run lies behind: what raises now leaves nobody waiting in one)
+        counts = _write_gathered(gathered, path, bam_string, kw)
+        if kw.get("stats") is not None:
+            kw["stats"]["alignment_gather"] = counts
 
 
 def sso_genotype_sharded(bam_string, vcf_in, vcf_out, *rest, rank: int, world: int, **kw) -> None:
