@@ -378,7 +378,7 @@ int svt_bam_spans_device(const uint8_t* bytes, uint64_t len, const uint64_t* rec
                          svt_bam_span* spans, uint64_t* key_and, uint64_t* key_or, int device);
 /* The stable order by key: perm[j] is the span that comes j-th (n entries, n < 2^32).  The host sorts with
  * std::stable_sort; the device with an LSD radix sort of (key, index) over the 8-bit digits in which the keys differ
- * (svt_bam_sort_kernel.h: a per-tile histogram, an exclusive scan and a stable scatter per digit; where an element goes is
+ * (svt_radix_sort_kernel.h: a per-tile histogram, an exclusive scan and a stable scatter per digit; where an element goes is
  * a rank, so the permutation is a function of the keys alone).  A span with SVT_BAM_BAD: *bad_record is its 1-based number,
  * *bad_kind why (SVT_OK, perm undefined); 0 otherwise.                                                                 */
 int svt_bam_sort_order_host(const svt_bam_span* spans, uint64_t n, uint64_t* perm, uint64_t* bad_record, uint32_t* bad_kind);

@@ -4,8 +4,8 @@
 //   svt_bam_first_hash_kernel  one lane per record, from the stream and the table of record offsets: bfr::key_at checks the record
 //                              and reads its key, keys[i] = key_hash & mask, idx[i] = i; a record that is not well-formed goes
 //                              into *bad as the smallest such index (one 64-bit atomic minimum) and hashes to 0.  The AND and the
-//                              OR of a workgroup's hashes go to key_and[block] / key_or[block], as svt_bam_keys_kernel's do.
-//   the radix passes of svt_bam_sort_kernel.h over (hash, index), as they are: stable, so inside a run of equal hashes the
+//                              OR of a workgroup's hashes go to key_and[block] / key_or[block] (radix_store_and_or).
+//   the radix passes of svt_radix_sort_kernel.h over (hash, index), as they are: stable, so inside a run of equal hashes the
 //   indices rise
 //   svt_bam_first_mark_kernel  one lane per sorted position j, i = idx[j]: it walks back over idx[j - 1], idx[j - 2], ... while
 //                              their hash is its own, and stops at the first whose key is equal: keep[i] = 0.  At the start of
@@ -19,7 +19,7 @@
 #define SVT_BAM_FIRST_KERNEL_H
 
 #include "svt_bam_first_rules.h"
-#include "svt_bam_sort_kernel.h"
+#include "svt_radix_sort_kernel.h"
 
 namespace svt {
 
@@ -30,7 +30,6 @@ __global__ __launch_bounds__(kSortBlock) void svt_bam_first_hash_kernel(const ui
                                                                         uint64_t* __restrict__ key_and, uint64_t* __restrict__ key_or,
                                                                         unsigned long long* __restrict__ bad)
 {
-    __shared__ uint64_t part_and[kSortWaves], part_or[kSortWaves];
     uint64_t a = ~0ull, o = 0;
     for (uint64_t i = (uint64_t)blockIdx.x * kSortBlock + threadIdx.x; i < n; i += (uint64_t)gridDim.x * kSortBlock) {
         bfr::Key k;
@@ -42,24 +41,7 @@ __global__ __launch_bounds__(kSortBlock) void svt_bam_first_hash_kernel(const ui
         a &= h;
         o |= h;
     }
-    for (int d = 32; d; d >>= 1) {                  // (behind the loop: every lane is here)
-        a &= (uint64_t)__shfl_xor((unsigned long long)a, d);
-        o |= (uint64_t)__shfl_xor((unsigned long long)o, d);
-    }
-    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) {
-        part_and[wave] = a;
-        part_or[wave] = o;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (uint32_t w = 1; w < kSortWaves; ++w) {
-            a &= part_and[w];
-            o |= part_or[w];
-        }
-        key_and[blockIdx.x] = a;
-        key_or[blockIdx.x] = o;
-    }
+    radix_store_and_or(a, o, key_and, key_or);
 }
 
 // keys / idx: the (hash, index) pairs in stable order by hash

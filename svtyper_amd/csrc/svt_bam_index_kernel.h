@@ -22,8 +22,8 @@
 //                                   run r - 1 at its own start (the records lie side by side); the first record that is not
 //                                   placed ends the last run, or the last record does at the end of the data.
 //   No workgroup waits for another one anywhere: three launches, no look-back, no spin.
-//   svt_bam_index_run_keys_kernel   idx[r] = r and the AND / OR of a workgroup's run keys (as svt_bam_keys_kernel): the radix passes
-//                                   of svt_bam_sort_kernel.h then sort (key, r), skipping the digits in which all keys agree
+//   svt_bam_index_run_keys_kernel   idx[r] = r and the AND / OR of a workgroup's run keys (radix_store_and_or): the radix passes
+//                                   of svt_radix_sort_kernel.h then sort (key, r), skipping the digits in which all keys agree
 //   svt_bam_index_loffset_kernel    one lane per sorted run q: the run (key, s, e) gathered through the sorted indices; for a group
 //                                   head -- a run whose key differs from the sorted run in front -- loffset = s_j for the first j
 //                                   with M_j > tid << 32 | bin_start(bin), a bounded binary search over the monotone M (one
@@ -35,7 +35,8 @@
 #ifndef SVT_BAM_INDEX_KERNEL_H
 #define SVT_BAM_INDEX_KERNEL_H
 
-#include "svt_bam_sort_kernel.h"
+#include "svt_bam_sort_rules.h"
+#include "svt_radix_sort_kernel.h"
 #include "svt_index_scheme.h"
 
 namespace svt {
@@ -286,31 +287,13 @@ __global__ __launch_bounds__(kSortBlock) void svt_bam_index_apply_kernel(uint64_
 __global__ __launch_bounds__(kSortBlock) void svt_bam_index_run_keys_kernel(const uint64_t* __restrict__ run_key, uint64_t n_runs, uint32_t* __restrict__ idx,
                                                                             uint64_t* __restrict__ key_and, uint64_t* __restrict__ key_or)
 {
-    __shared__ uint64_t part_and[kSortWaves], part_or[kSortWaves];
     uint64_t a = ~0ull, o = 0;
     for (uint64_t r = (uint64_t)blockIdx.x * kSortBlock + threadIdx.x; r < n_runs; r += (uint64_t)gridDim.x * kSortBlock) {
         idx[r] = (uint32_t)r;
         a &= run_key[r];
         o |= run_key[r];
     }
-    for (int d = 32; d; d >>= 1) {
-        a &= (uint64_t)__shfl_xor((unsigned long long)a, d);
-        o |= (uint64_t)__shfl_xor((unsigned long long)o, d);
-    }
-    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) {
-        part_and[wave] = a;
-        part_or[wave] = o;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (uint32_t w = 1; w < kSortWaves; ++w) {
-            a &= part_and[w];
-            o |= part_or[w];
-        }
-        key_and[blockIdx.x] = a;
-        key_or[blockIdx.x] = o;
-    }
+    radix_store_and_or(a, o, key_and, key_or);
 }
 
 // the first j in [0, n) with m[j] > target, n where there is none; m does not fall

@@ -1,7 +1,7 @@
 // svt_entry_bam_first.h -- part of the single translation unit svtyper_hip.hip (included there, in order, behind
 // svt_entry_bam_sort.h; not a stand-alone header): first occurrences of a BAM record stream on the device.  The stream and the
-// offset table go up once; svt_bam_first_hash_kernel checks every record and writes (hash, index); the pairs go through
-// radix_passes (svt_entry_bam_sort.h: the record sort's passes, not a copy of them); svt_bam_first_mark_kernel compares
+// offset table go up once; svt_bam_first_hash_kernel checks every record and writes (hash, index); the pairs go through the
+// call's RadixSort (svt_entry_radix_sort.h: the one sort, not a copy of it); svt_bam_first_mark_kernel compares
 // neighbours inside runs of equal hashes and counts; keep and the workgroups' counts come down.  C ABI: svt_bam_first_device,
 // svt_bam_first_last_times (include/svtyper_reads.h); the host twin is svt_bam_first_host (svt_reads_bam_sort_entries.h).
 
@@ -10,8 +10,9 @@ extern "C++" {
 // the kernels of the calling thread's last svt_bam_first_device, from HIP events, and the call's wall time
 static thread_local svt_bam_first_times g_bam_first_times;
 
-struct BamFirstCall : BamSortCall {                          // (destruction order: CallStream, svt_batch_state.h)
-    DevScratch d_bad, d_keep, d_kept;
+struct BamFirstCall : OrderedCall {                          // (svt_entry_deflate.h; destruction order: CallStream, svt_batch_state.h)
+    DevScratch d_rec_off, d_bad, d_keep, d_kept;
+    RadixSort sort;                                          // (a member, so freed behind drain())
     ~BamFirstCall() { drain(); }
 };
 
@@ -35,28 +36,22 @@ static int svt_bam_first_device_impl(const uint8_t* bytes, uint64_t len, const u
     }
     BamFirstCall c;
     SVT_TRY(c.begin(bytes, len));
-    const unsigned grid = lines_grid((n + kSortBlock - 1) / kSortBlock, device);
+    unsigned grid = 0;
     SVT_TRY(c.d_rec_off.alloc((n + 1) * sizeof(uint64_t)));
     SVT_TRY(h2d_staged(c.d_rec_off.p, rec_off, (n + 1) * sizeof(uint64_t), c.s));
-    SVT_TRY(c.d_keys[0].alloc(n * sizeof(uint64_t)));
-    SVT_TRY(c.d_idx[0].alloc(n * sizeof(uint32_t)));
-    SVT_TRY(c.d_and.alloc(grid * sizeof(uint64_t)));
-    SVT_TRY(c.d_or.alloc(grid * sizeof(uint64_t)));
+    SVT_TRY(c.sort.room(n));
+    SVT_TRY(c.sort.key_grid(n, device, &grid));
     SVT_TRY(c.d_bad.alloc(sizeof(unsigned long long)));
     HIP_TRY(hipMemsetAsync(c.d_bad.p, 0xFF, sizeof(unsigned long long), c.s));          // kFirstNoBad
     size_t e[4] = {};
     SVT_TRY(c.mark(&e[0]));
     hipLaunchKernelGGL(svt_bam_first_hash_kernel, dim3(grid), dim3(kSortBlock), 0, c.s, c.d_stream.as<uint8_t>(), len, c.d_rec_off.as<uint64_t>(), n,
-                       bfr::hash_mask(hash_bits), c.d_keys[0].as<uint64_t>(), c.d_idx[0].as<uint32_t>(), c.d_and.as<uint64_t>(), c.d_or.as<uint64_t>(),
-                       c.d_bad.as<unsigned long long>());
+                       bfr::hash_mask(hash_bits), c.sort.keys(), c.sort.idx(), c.sort.part_and(), c.sort.part_or(), c.d_bad.as<unsigned long long>());
     HIP_TRY(hipGetLastError());
     SVT_TRY(c.mark(&e[1]));
-    std::vector<uint64_t> ands(grid), ors(grid);
     unsigned long long bad = kFirstNoBad;
-    SVT_TRY(d2h_staged(ands.data(), c.d_and.p, grid * sizeof(uint64_t), c.s));
-    SVT_TRY(d2h_staged(ors.data(), c.d_or.p, grid * sizeof(uint64_t), c.s));
     SVT_TRY(d2h_staged(&bad, c.d_bad.p, sizeof bad, c.s));
-    HIP_TRY(hipStreamSynchronize(c.s));
+    SVT_TRY(c.sort.combine(c));
     SVT_TRY(c.between(e[0], e[1], &g_bam_first_times.hash_kernel_s));
     if (bad != kFirstNoBad) {
         if (bad >= n) return fail(SVT_ERR_HIP, "svt_bam_first_hash_kernel: the record it refuses is none of the stream's");
@@ -64,27 +59,21 @@ static int svt_bam_first_device_impl(const uint8_t* bytes, uint64_t len, const u
         g_bam_first_times.total_s = seconds_since(t0);
         return SVT_OK;
     }
-    uint64_t key_and = ~0ull, key_or = 0;
-    for (unsigned g = 0; g < grid; ++g) {
-        key_and &= ands[g];
-        key_or |= ors[g];
-    }
-    RadixPasses r;
-    SVT_TRY(radix_passes(c, n, key_and, key_or, r, device));
-    g_bam_first_times.passes = r.passes;
+    SVT_TRY(c.sort.passes(c, device));
     SVT_TRY(c.d_keep.alloc(n));
     SVT_TRY(c.d_kept.alloc(grid * sizeof(uint32_t)));
     HIP_TRY(hipMemsetAsync(c.d_keep.p, 0xFF, n, c.s));       // (a record the mark kernel did not reach shows below)
     SVT_TRY(c.mark(&e[2]));
     hipLaunchKernelGGL(svt_bam_first_mark_kernel, dim3(grid), dim3(kSortBlock), 0, c.s, c.d_stream.as<uint8_t>(), len, c.d_rec_off.as<uint64_t>(), n,
-                       c.d_keys[r.src].as<uint64_t>(), c.d_idx[r.src].as<uint32_t>(), c.d_keep.as<uint8_t>(), c.d_kept.as<uint32_t>());
+                       c.sort.sorted_keys(), c.sort.sorted_idx(), c.d_keep.as<uint8_t>(), c.d_kept.as<uint32_t>());
     HIP_TRY(hipGetLastError());
     SVT_TRY(c.mark(&e[3]));
     std::vector<uint32_t> kept(grid);
     SVT_TRY(d2h_staged(keep, c.d_keep.p, n, c.s));
     SVT_TRY(d2h_staged(kept.data(), c.d_kept.p, grid * sizeof(uint32_t), c.s));
     HIP_TRY(hipStreamSynchronize(c.s));
-    SVT_TRY(radix_times(c, r, &g_bam_first_times.histogram_kernel_s, &g_bam_first_times.scan_kernel_s, &g_bam_first_times.scatter_kernel_s));
+    svt_bam_first_times& t = g_bam_first_times;
+    SVT_TRY(c.sort.times(c, &t.passes, &t.histogram_kernel_s, &t.scan_kernel_s, &t.scatter_kernel_s));
     SVT_TRY(c.between(e[2], e[3], &g_bam_first_times.mark_kernel_s));
     // every record got its 0 or 1 and the workgroups' counts are their sum, or the answer is not the kernels'
     uint64_t reduced = 0, summed = 0;

@@ -1,10 +1,10 @@
 // svt_entry_bam_index.h -- part of the single translation unit svtyper_hip.hip (included there, in order, behind
 // svt_entry_bam_sort.h; not a stand-alone header): the CSI fold of the `-w` BAM on the device.  What is this header's: the launches
 // of svt_bam_index_kernel.h over a span table that is resident already (fold_resident: the record kernel, the three-phase scan
-// with the compaction in its last phase, the runs through sort_resident's radix passes, the loffsets, the per-reference rows),
-// the check of what came down, the serialiser's call (svt_tbx_index.h: csi::serialise -- the host fold's) and the bytes left for
-// svt_csi_take.  What goes up for the fold is member_start / member_off, n_members + 1 words each; what comes down is
-// O(runs + n_ref).  C ABI: svt_bam_index_fold_device, svt_bam_sorted_bgzf_csi_device, svt_bam_index_last_times.
+// with the compaction in its last phase, the runs through the fold's own RadixSort (svt_entry_radix_sort.h), the loffsets, the
+// per-reference rows), the check of what came down, the serialiser's call (svt_tbx_index.h: csi::serialise -- the host fold's)
+// and the bytes left for svt_csi_take.  What goes up for the fold is member_start / member_off, n_members + 1 words each; what
+// comes down is O(runs + n_ref).  C ABI: svt_bam_index_fold_device, svt_bam_sorted_bgzf_csi_device, svt_bam_index_last_times.
 
 extern "C++" {
 
@@ -15,7 +15,9 @@ std::vector<uint8_t>& csi_held_bytes();             // (svt_reads.cpp: the calli
 // the kernels of the calling thread's last fold here, from HIP events, and the fold's wall time
 static thread_local svt_bam_index_times g_bam_index_times;
 
-struct BamIndexCall : BamSortCall {                          // (destruction order: CallStream, svt_batch_state.h)
+struct BamIndexCall : TimedCallStream {                      // (destruction order: CallStream, svt_batch_state.h)
+    DevScratch d_spans;                                      // svt_bam_index_fold_device's upload; the one-call entry's table is the record call's
+    RadixSort sort;                                          // the runs' (key, run) pairs (a member, so freed behind drain())
     DevScratch d_member_start, d_member_off, d_s, d_m, d_rkey, d_flag, d_unm, d_tile_heads, d_tile_unmapped, d_tile_top, d_small, d_run_s, d_run_e, d_runs,
         d_loff, d_rows;
     ~BamIndexCall() { drain(); }
@@ -52,8 +54,7 @@ static int fold_resident(BamIndexCall& f, const svt_bam_span* d_spans, const uin
         SVT_TRY(f.d_tile_unmapped.alloc(n_tiles * sizeof(uint32_t)));
         SVT_TRY(f.d_tile_top.alloc(n_tiles * sizeof(uint64_t)));
         SVT_TRY(f.d_small.alloc(4 * sizeof(uint64_t)));
-        SVT_TRY(f.d_keys[0].alloc(n * sizeof(uint64_t)));           // the runs' keys and indices: what sort_resident sorts
-        SVT_TRY(f.d_idx[0].alloc(n * sizeof(uint32_t)));
+        SVT_TRY(f.sort.room(n));                                    // the runs' keys and indices: n at the most
         SVT_TRY(f.d_run_s.alloc(n * sizeof(uint64_t)));
         SVT_TRY(f.d_run_e.alloc(n * sizeof(uint64_t)));
         uint64_t small[4] = {~0ull, 0, 0, 0};                       // first refusal (a minimum), records without coordinate, heads, unmapped
@@ -76,7 +77,7 @@ static int fold_resident(BamIndexCall& f, const svt_bam_span* d_spans, const uin
         HIP_TRY(hipGetLastError());
         hipLaunchKernelGGL(svt_bam_index_apply_kernel, dim3(tile_grid), dim3(kSortBlock), 0, f.s, f.d_m.as<uint64_t>(), f.d_flag.as<uint8_t>(),
                            f.d_s.as<uint64_t>(), f.d_rkey.as<uint64_t>(), n, n_tiles, f.d_tile_heads.as<uint32_t>(), f.d_tile_unmapped.as<uint32_t>(),
-                           f.d_tile_top.as<uint64_t>(), end_voff, f.d_unm.as<uint32_t>(), f.d_keys[0].as<uint64_t>(), f.d_run_s.as<uint64_t>(),
+                           f.d_tile_top.as<uint64_t>(), end_voff, f.d_unm.as<uint32_t>(), f.sort.keys(), f.d_run_s.as<uint64_t>(),
                            f.d_run_e.as<uint64_t>(), n);
         HIP_TRY(hipGetLastError());
         SVT_TRY(f.mark(&e[2]));
@@ -97,38 +98,24 @@ static int fold_resident(BamIndexCall& f, const svt_bam_span* d_spans, const uin
         const uint64_t n_placed = n - no_coor;
         g_bam_index_times.runs = n_runs;
         if (n_runs) {
-            const unsigned grid = lines_grid((n_runs + kSortBlock - 1) / kSortBlock, device);
-            SVT_TRY(f.d_and.alloc(grid * sizeof(uint64_t)));
-            SVT_TRY(f.d_or.alloc(grid * sizeof(uint64_t)));
+            unsigned grid = 0;
+            SVT_TRY(f.sort.key_grid(n_runs, device, &grid));
             SVT_TRY(f.d_runs.alloc(n_runs * sizeof(idx::Run)));
             SVT_TRY(f.d_loff.alloc(n_runs * sizeof(uint64_t)));
             SVT_TRY(f.mark(&e[0]));
-            hipLaunchKernelGGL(svt_bam_index_run_keys_kernel, dim3(grid), dim3(kSortBlock), 0, f.s, f.d_keys[0].as<uint64_t>(), n_runs, f.d_idx[0].as<uint32_t>(),
-                               f.d_and.as<uint64_t>(), f.d_or.as<uint64_t>());
+            hipLaunchKernelGGL(svt_bam_index_run_keys_kernel, dim3(grid), dim3(kSortBlock), 0, f.s, f.sort.keys(), n_runs, f.sort.idx(), f.sort.part_and(),
+                               f.sort.part_or());
             HIP_TRY(hipGetLastError());
             SVT_TRY(f.mark(&e[1]));
-            std::vector<uint64_t> ands(grid), ors(grid);
-            SVT_TRY(d2h_staged(ands.data(), f.d_and.p, grid * sizeof(uint64_t), f.s));
-            SVT_TRY(d2h_staged(ors.data(), f.d_or.p, grid * sizeof(uint64_t), f.s));
-            HIP_TRY(hipStreamSynchronize(f.s));
+            SVT_TRY(f.sort.combine(f));
             SVT_TRY(f.between(e[0], e[1], &g_bam_index_times.sort_kernel_s));
-            uint64_t key_and = ~0ull, key_or = 0;
-            for (unsigned g = 0; g < grid; ++g) {
-                key_and &= ands[g];
-                key_or |= ors[g];
-            }
-            const svt_bam_sort_times records_sort = g_bam_sort_times;       // (sort_resident keeps its times there: the record sort's stay)
-            g_bam_sort_times = svt_bam_sort_times();
             std::vector<uint32_t> order;
-            const int rc = sort_resident(f, n_runs, key_and, key_or, order, device);
-            g_bam_index_times.passes = g_bam_sort_times.passes;
-            g_bam_index_times.sort_kernel_s += g_bam_sort_times.histogram_kernel_s + g_bam_sort_times.scan_kernel_s + g_bam_sort_times.scatter_kernel_s;
-            g_bam_sort_times = records_sort;
-            SVT_TRY(rc);
-            const int src = (int)(g_bam_index_times.passes & 1);    // where the last pass left keys and indices (no pass: where they were put)
+            SVT_TRY(f.sort.order(f, order, device));
+            double& sort_s = g_bam_index_times.sort_kernel_s;       // the run-key kernel and the three pass kernels summed
+            SVT_TRY(f.sort.times(f, &g_bam_index_times.passes, &sort_s, &sort_s, &sort_s));
             SVT_TRY(f.mark(&e[0]));
-            hipLaunchKernelGGL(svt_bam_index_loffset_kernel, dim3(grid), dim3(kSortBlock), 0, f.s, f.d_keys[src].as<uint64_t>(), f.d_idx[src].as<uint32_t>(),
-                               n_runs, f.d_run_s.as<uint64_t>(), f.d_run_e.as<uint64_t>(), f.d_m.as<uint64_t>(), f.d_s.as<uint64_t>(), n_placed, depth,
+            hipLaunchKernelGGL(svt_bam_index_loffset_kernel, dim3(grid), dim3(kSortBlock), 0, f.s, f.sort.sorted_keys(), f.sort.sorted_idx(), n_runs,
+                               f.d_run_s.as<uint64_t>(), f.d_run_e.as<uint64_t>(), f.d_m.as<uint64_t>(), f.d_s.as<uint64_t>(), n_placed, depth,
                                f.d_runs.as<idx::Run>(), f.d_loff.as<uint64_t>());
             HIP_TRY(hipGetLastError());
             SVT_TRY(f.mark(&e[1]));

@@ -1,12 +1,12 @@
 // svt_entry_bam_sort.h -- part of the single translation unit svtyper_hip.hip (included there, in order, behind
-// svt_entry_vcf_lines.h; not a stand-alone header): BAM records as spans on the device.  What is this header's: the span table
-// (keys_resident: svt_bam_keys_kernel writes spans, keys and their AND / OR per workgroup, the host combines those), the radix
-// passes over the digits in which the keys differ (radix_passes, and sort_resident over them: svt_bam_histogram_kernel, svt_bam_scan_kernel and
-// svt_bam_scatter_kernel per digit), the argument checks and the caller's arrays.  What it shares lives in svt_entry_deflate.h:
-// the upload (OrderedCall::begin), the gather behind the header copy (gather_resident<svt_bam_span>), the members from
-// bsr::cut_members' boundaries (deflate_members), the marks that time the kernels.  C ABI: svt_bam_spans_device,
-// svt_bam_sort_order_device, svt_bam_sorted_bgzf_device, svt_bam_sort_last_times (include/svtyper_reads.h).  The one-call entry's
-// body takes a hook that runs behind the members while its tables are resident: svt_entry_bam_index.h's CSI fold.
+// svt_entry_radix_sort.h; not a stand-alone header): BAM records as spans on the device.  What is this header's: the span table
+// (keys_resident: svt_bam_keys_kernel writes spans, keys and their AND / OR per workgroup), the record sort over the call's
+// RadixSort (sort_resident: svt_entry_radix_sort.h has the passes, their buffers and their times), the argument checks and the
+// caller's arrays.  What it shares lives in svt_entry_deflate.h: the upload (OrderedCall::begin), the gather behind the header
+// copy (gather_resident<svt_bam_span>), the members from bsr::cut_members' boundaries (deflate_members), the marks that time the
+// kernels.  C ABI: svt_bam_spans_device, svt_bam_sort_order_device, svt_bam_sorted_bgzf_device, svt_bam_sort_last_times
+// (include/svtyper_reads.h).  The one-call entry's body takes a hook that runs behind the members while its tables are resident:
+// svt_entry_bam_index.h's CSI fold.
 
 extern "C++" {
 
@@ -14,43 +14,32 @@ extern "C++" {
 static thread_local svt_bam_sort_times g_bam_sort_times;
 
 struct BamSortCall : OrderedCall {                           // (svt_entry_deflate.h; destruction order: CallStream, svt_batch_state.h)
-    DevScratch d_rec_off, d_spans, d_keys[2], d_idx[2], d_and, d_or, d_hist;
+    DevScratch d_rec_off, d_spans;
+    RadixSort sort;                                          // (svt_entry_radix_sort.h: a member, so freed behind drain())
     ~BamSortCall() { drain(); }
 };
 
-// c.d_stream[0, len) and the caller's rec_off -> the span table in c.d_spans and in `table`, keys and indices in c.d_keys[0] /
-// c.d_idx[0], the AND and the OR of the keys
-static int keys_resident(BamSortCall& c, uint64_t len, const uint64_t* rec_off, uint64_t n, int32_t n_ref, std::vector<svt_bam_span>& table,
-                         uint64_t& key_and, uint64_t& key_or, int device)
+// c.d_stream[0, len) and the caller's rec_off -> the span table in c.d_spans and in `table`, keys and indices in c.sort with the
+// AND and the OR of the keys
+static int keys_resident(BamSortCall& c, uint64_t len, const uint64_t* rec_off, uint64_t n, int32_t n_ref, std::vector<svt_bam_span>& table, int device)
 {
     table.clear();
-    key_and = ~0ull;
-    key_or = 0;
     if (n == 0) return SVT_OK;
-    const unsigned grid = lines_grid((n + kSortBlock - 1) / kSortBlock, device);
+    unsigned grid = 0;
     SVT_TRY(c.d_rec_off.alloc((n + 1) * sizeof(uint64_t)));
     SVT_TRY(h2d_staged(c.d_rec_off.p, rec_off, (n + 1) * sizeof(uint64_t), c.s));
     SVT_TRY(c.d_spans.alloc(n * sizeof(svt_bam_span)));
-    SVT_TRY(c.d_keys[0].alloc(n * sizeof(uint64_t)));
-    SVT_TRY(c.d_idx[0].alloc(n * sizeof(uint32_t)));
-    SVT_TRY(c.d_and.alloc(grid * sizeof(uint64_t)));
-    SVT_TRY(c.d_or.alloc(grid * sizeof(uint64_t)));
+    SVT_TRY(c.sort.room(n));
+    SVT_TRY(c.sort.key_grid(n, device, &grid));
     size_t e0 = 0, e1 = 0;
     SVT_TRY(c.mark(&e0));
     hipLaunchKernelGGL(svt_bam_keys_kernel, dim3(grid), dim3(kSortBlock), 0, c.s, c.d_stream.as<uint8_t>(), len, c.d_rec_off.as<uint64_t>(), n, n_ref,
-                       c.d_spans.as<svt_bam_span>(), c.d_keys[0].as<uint64_t>(), c.d_idx[0].as<uint32_t>(), c.d_and.as<uint64_t>(), c.d_or.as<uint64_t>());
+                       c.d_spans.as<svt_bam_span>(), c.sort.keys(), c.sort.idx(), c.sort.part_and(), c.sort.part_or());
     HIP_TRY(hipGetLastError());
     SVT_TRY(c.mark(&e1));
     table.resize(n);
-    std::vector<uint64_t> ands(grid), ors(grid);
     SVT_TRY(d2h_staged(table.data(), c.d_spans.p, n * sizeof(svt_bam_span), c.s));
-    SVT_TRY(d2h_staged(ands.data(), c.d_and.p, grid * sizeof(uint64_t), c.s));
-    SVT_TRY(d2h_staged(ors.data(), c.d_or.p, grid * sizeof(uint64_t), c.s));
-    HIP_TRY(hipStreamSynchronize(c.s));
-    for (unsigned g = 0; g < grid; ++g) {
-        key_and &= ands[g];
-        key_or |= ors[g];
-    }
+    SVT_TRY(c.sort.combine(c));
     SVT_TRY(c.between(e0, e1, &g_bam_sort_times.keys_kernel_s));
     // the kernel's table is the caller's offsets or it is not theirs: what the gather relies on
     for (uint64_t i = 0; i < n; ++i)
@@ -59,83 +48,12 @@ static int keys_resident(BamSortCall& c, uint64_t len, const uint64_t* rec_off, 
     return SVT_OK;
 }
 
-// The radix passes over n (key, index) pairs in c.d_keys[0] / c.d_idx[0], launched on c.s: one histogram, scan and scatter per
-// 8-bit digit in which the keys differ, least significant first.  The pairs end up, in stable order by key, in c.d_keys[src] /
-// c.d_idx[src] (no pass: where they were).  Both users of the sort go through here: the record sort below (with its caller the
-// index fold, svt_entry_bam_index.h) and the first-occurrence pass (svt_entry_bam_first.h).
-struct RadixPasses {
-    uint32_t passes = 0;
-    int src = 0;
-    std::vector<size_t> at;                         // four marks per pass
-};
-
-static int radix_passes(BamSortCall& c, uint64_t n, uint64_t key_and, uint64_t key_or, RadixPasses& r, int device)
+// the pairs of c.sort -> order[j]: the index that comes j-th in stable order by key; the passes' times into g_bam_sort_times
+static int sort_resident(BamSortCall& c, std::vector<uint32_t>& order, int device)
 {
-    const uint64_t differ = n ? key_and ^ key_or : 0;
-    uint32_t shifts[8];
-    r = RadixPasses();
-    for (uint32_t d = 0; d < 8; ++d)
-        if (differ >> (8 * d) & 255) shifts[r.passes++] = 8 * d;
-    if (r.passes == 0) return SVT_OK;
-    const uint32_t n_tiles = (uint32_t)((n + kSortTile - 1) / kSortTile);
-    const unsigned grid = lines_grid(n_tiles, device);
-    SVT_TRY(c.d_keys[1].alloc(n * sizeof(uint64_t)));
-    SVT_TRY(c.d_idx[1].alloc(n * sizeof(uint32_t)));
-    SVT_TRY(c.d_hist.alloc((uint64_t)n_tiles * 256 * sizeof(uint32_t)));
-    int src = 0;
-    std::vector<size_t>& at = r.at;
-    at.resize(4 * r.passes);
-    for (uint32_t p = 0; p < r.passes; ++p) {
-        SVT_TRY(c.mark(&at[4 * p]));
-        hipLaunchKernelGGL(svt_bam_histogram_kernel, dim3(grid), dim3(kSortBlock), 0, c.s, c.d_keys[src].as<uint64_t>(), n, n_tiles, shifts[p],
-                           c.d_hist.as<uint32_t>());
-        HIP_TRY(hipGetLastError());
-        SVT_TRY(c.mark(&at[4 * p + 1]));
-        hipLaunchKernelGGL(svt_bam_scan_kernel, dim3(1), dim3(kSortBlock), 0, c.s, c.d_hist.as<uint32_t>(), (uint64_t)n_tiles * 256);
-        HIP_TRY(hipGetLastError());
-        SVT_TRY(c.mark(&at[4 * p + 2]));
-        hipLaunchKernelGGL(svt_bam_scatter_kernel, dim3(grid), dim3(kSortBlock), 0, c.s, c.d_keys[src].as<uint64_t>(), c.d_idx[src].as<uint32_t>(), n, n_tiles,
-                           shifts[p], c.d_hist.as<uint32_t>(), c.d_keys[src ^ 1].as<uint64_t>(), c.d_idx[src ^ 1].as<uint32_t>());
-        HIP_TRY(hipGetLastError());
-        SVT_TRY(c.mark(&at[4 * p + 3]));
-        src ^= 1;
-    }
-    r.src = src;
-    return SVT_OK;
-}
-
-// the passes' kernels by their marks, once c.s has passed them: added to the three sums
-static int radix_times(BamSortCall& c, const RadixPasses& r, double* histogram_s, double* scan_s, double* scatter_s)
-{
-    for (uint32_t p = 0; p < r.passes; ++p) {
-        SVT_TRY(c.between(r.at[4 * p], r.at[4 * p + 1], histogram_s));
-        SVT_TRY(c.between(r.at[4 * p + 1], r.at[4 * p + 2], scan_s));
-        SVT_TRY(c.between(r.at[4 * p + 2], r.at[4 * p + 3], scatter_s));
-    }
-    return SVT_OK;
-}
-
-// n (key, index) pairs in c.d_keys[0] / c.d_idx[0] -> order[j]: the index that comes j-th in stable order by key
-static int sort_resident(BamSortCall& c, uint64_t n, uint64_t key_and, uint64_t key_or, std::vector<uint32_t>& order, int device)
-{
-    order.resize(n);
-    RadixPasses r;
-    SVT_TRY(radix_passes(c, n, key_and, key_or, r, device));
-    g_bam_sort_times.passes = r.passes;
-    if (r.passes == 0) {                            // every key is the same one: the order of arrival
-        for (uint64_t i = 0; i < n; ++i) order[i] = (uint32_t)i;
-        return SVT_OK;
-    }
-    SVT_TRY(d2h_staged(order.data(), c.d_idx[r.src].p, n * sizeof(uint32_t), c.s));
-    HIP_TRY(hipStreamSynchronize(c.s));
-    SVT_TRY(radix_times(c, r, &g_bam_sort_times.histogram_kernel_s, &g_bam_sort_times.scan_kernel_s, &g_bam_sort_times.scatter_kernel_s));
-    // the kernels' order is a permutation or it is not theirs: what the gather and the callers rely on
-    std::vector<uint8_t> seen(n, 0);
-    for (uint64_t j = 0; j < n; ++j) {
-        if (order[j] >= n || seen[order[j]]) return fail(SVT_ERR_HIP, "svt_bam_scatter_kernel: the order is no permutation");
-        seen[order[j]] = 1;
-    }
-    return SVT_OK;
+    SVT_TRY(c.sort.order(c, order, device));
+    svt_bam_sort_times& t = g_bam_sort_times;
+    return c.sort.times(c, &t.passes, &t.histogram_kernel_s, &t.scan_kernel_s, &t.scatter_kernel_s);
 }
 
 static int svt_bam_spans_device_impl(const uint8_t* bytes, uint64_t len, const uint64_t* rec_off, uint64_t n, int32_t n_ref, svt_bam_span* spans,
@@ -150,11 +68,10 @@ static int svt_bam_spans_device_impl(const uint8_t* bytes, uint64_t len, const u
     BamSortCall c;
     SVT_TRY(c.begin(bytes, len));
     std::vector<svt_bam_span> table;
-    uint64_t a = ~0ull, o = 0;
-    SVT_TRY(keys_resident(c, len, rec_off, n, n_ref, table, a, o, device));
+    SVT_TRY(keys_resident(c, len, rec_off, n, n_ref, table, device));
     if (n) std::memcpy(spans, table.data(), n * sizeof(svt_bam_span));
-    if (key_and) *key_and = a;
-    if (key_or) *key_or = o;
+    if (key_and) *key_and = c.sort.key_and;
+    if (key_or) *key_or = c.sort.key_or;
     g_bam_sort_times.total_s = seconds_since(t0);
     return SVT_OK;
 }
@@ -179,13 +96,15 @@ static int svt_bam_sort_order_device_impl(const svt_bam_span* spans, uint64_t n,
         a &= keys[i];
         o |= keys[i];
     }
+    SVT_TRY(c.sort.room(n));
     {
         Stager st(c.s);
-        SVT_TRY(upload(c.d_keys[0], keys, st));
-        SVT_TRY(upload(c.d_idx[0], idx, st));
+        SVT_TRY(st.copy(c.sort.keys(), keys.data(), n * sizeof(uint64_t)));
+        SVT_TRY(st.copy(c.sort.idx(), idx.data(), n * sizeof(uint32_t)));
         SVT_TRY(st.finish());
     }
-    SVT_TRY(sort_resident(c, n, a, o, order, device));
+    c.sort.given(n, a, o);
+    SVT_TRY(sort_resident(c, order, device));
     for (uint64_t j = 0; j < n; ++j) perm[j] = order[j];
     g_bam_sort_times.total_s = seconds_since(t0);
     return SVT_OK;
@@ -222,14 +141,13 @@ static int svt_bam_sorted_bgzf_device_impl(const uint8_t* bytes, uint64_t len, c
     SVT_TRY(c.begin(bytes, len));
     const uint64_t header_len = rec_off[0];
     std::vector<svt_bam_span> table;
-    uint64_t key_and = ~0ull, key_or = 0;
-    SVT_TRY(keys_resident(c, len, rec_off, n, n_ref, table, key_and, key_or, device));
+    SVT_TRY(keys_resident(c, len, rec_off, n, n_ref, table, device));
     const uint8_t* d_written = c.d_stream.as<uint8_t>();
     if (sort) {
         *bad_record = bsr::first_bad(table.data(), n, *bad_kind);
         if (*bad_record) return SVT_OK;
         std::vector<uint32_t> order;
-        SVT_TRY(sort_resident(c, n, key_and, key_or, order, device));
+        SVT_TRY(sort_resident(c, order, device));
         std::vector<uint64_t> dst_off(n);
         uint64_t at = header_len;
         for (uint64_t j = 0; j < n; ++j) {

@@ -11,7 +11,7 @@ import struct
 import zlib
 
 PAYLOAD = 65280
-TILE = 1024                 # svt_bam_sort_kernel.h: kSortTile, the elements of one workgroup per pass
+TILE = 1024                 # svt_radix_sort_kernel.h: kSortTile, the elements of one workgroup per pass
 UNMAPPED, NO_COOR, BAD, BEYOND = 1, 2, 4, 8
 BAD_RECORD, BAD_TID, BAD_POS = 0x100, 0x200, 0x400
 KIND_RECORD, KIND_TID, KIND_POS, KIND_BEYOND, KIND_KEY_BACK = 1, 2, 3, 4, 5

@@ -1,5 +1,5 @@
 """GPU: the span table, the radix sort and the one-call entry of the coordinate-sorted, BAI-indexed `-w` BAM on the device
-(svt_bam_sort_kernel.h) against their host twins and the checker of tests/baicases.py; the writer with deflate="device" against
+(svt_bam_sort_kernel.h, svt_radix_sort_kernel.h) against their host twins and the checker of tests/baicases.py; the writer with deflate="device" against
 the files deflate="host" writes, byte for byte; sv_genotype -w over the fixture, sorted and indexed, in process with the Python
 reader and as the command line in a child process with the device reader."""
 import os
@@ -50,6 +50,50 @@ def test_both_kinds_of_sorting_pass_run(hip_device, which, passes):
     assert bad == 0 and perm.tolist() == B.order(case.records, case.n_ref)
     times = nr.bam_sort_last_times()
     assert times["passes"] == passes and times["scatter_kernel_s"] > 0 and times["histogram_kernel_s"] > 0 and times["scan_kernel_s"] > 0
+
+
+SORT_COUNTS = (1, 64, 65, 1023, 1024, 1025, 2049)     # one lane, the wavefront's edge, the tile's edge on both sides, a second tile nearly empty
+# the digits in which a family's keys differ: no pass; one; two with skipped digits between; an odd number, so the result lies
+# in the other buffer; all eight with two values a digit (256 distinct keys at the most), so most keys have equals
+KEY_FAMILIES = {"equal": (), "digit_7": (7,), "digits_0_7": (0, 7), "digits_0_3_5": (0, 3, 5), "all_eight_few_values": tuple(range(8))}
+
+
+def family_keys(family, n):
+    """n seeded keys that agree everywhere but in the family's digits"""
+    digits = KEY_FAMILIES[family]
+    rng = np.random.default_rng([n, sorted(KEY_FAMILIES).index(family)])
+    keys = np.full(n, 0x0123456789ABCDEF, np.uint64)
+    for d in digits:
+        values = rng.choice(256, 2, replace=False) if len(digits) == 8 else np.arange(256)
+        drawn = values[rng.integers(0, len(values), n)].astype(np.uint64)
+        keys = keys & ~np.uint64(255 << 8 * d) | drawn << np.uint64(8 * d)
+    return keys
+
+
+def passes_of(keys):
+    """the digits in which the keys differ: what the sort takes a pass for"""
+    differ = int(np.bitwise_and.reduce(keys)) ^ int(np.bitwise_or.reduce(keys))
+    return sum(1 for d in range(8) if differ >> (8 * d) & 255)
+
+
+def key_spans(keys):
+    spans = np.zeros(len(keys), nr.BAM_SPAN)            # flags 0: the order is by `key` and by nothing else
+    spans["key"] = keys
+    return spans
+
+
+@pytest.mark.parametrize("family", sorted(KEY_FAMILIES))
+def test_the_sort_over_arbitrary_keys(hip_device, family):
+    """the radix sort as a component: keys that are no BAM record's, every count around a wavefront and a tile"""
+    for n in SORT_COUNTS:
+        keys = family_keys(family, n)
+        passes = passes_of(keys)
+        assert passes == (len(KEY_FAMILIES[family]) if n >= 64 else 0), (family, n)
+        spans = key_spans(keys)
+        perm, bad, _kind = nr.bam_sort_order(spans, device=hip_device)
+        assert bad == 0 and nr.bam_sort_last_times()["passes"] == passes, (family, n)
+        assert perm.tolist() == np.argsort(keys, kind="stable").tolist(), (family, n)
+        assert perm.tobytes() == nr.bam_sort_order(spans)[0].tobytes(), (family, n)
 
 
 @pytest.mark.parametrize("huffman", ["fixed", "dynamic"])

@@ -4,6 +4,7 @@ tests/test_csi_output_host.py, so this is not the code under test checking itsel
 shapes at which the kernels can go wrong: record counts around a wavefront, a workgroup and a tile of 1 024, runs carried across
 tiles, a tail without coordinate that starts on a tile border, a record across members.  Then the writer with deflate="device"."""
 import os
+import random
 
 import numpy as np
 import pytest
@@ -163,6 +164,69 @@ def test_saturated_end_is_refused_at_depth_6(hip_device):
     assert both(spans, 1, (1 << 31) - 1, start, off, hip_device) == (None, 70, nr.BAM_KIND_BEYOND)
     spans[69]["end"] = 0xFFFFFFFE
     assert both(spans, 1, (1 << 31) - 1, start, off, hip_device)[1] == 0
+
+
+def passes_of(keys):
+    """the digits in which the keys differ: what a radix sort of them takes a pass for (as bamfirstcases.radix_passes for hashes)"""
+    keys = [int(k) for k in keys]
+    differ = 0
+    for k in keys:
+        differ |= k ^ keys[0]
+    return sum(1 for d in range(8) if differ >> (8 * d) & 255)
+
+
+def test_two_sorts_in_one_call_keep_their_own_times(hip_device):
+    """svt_bam_sorted_bgzf_csi_device sorts twice on one thread: the records by key and, in the fold behind the members, the runs by
+    tid << 32 | bin.  Here the two take pass counts of different parity -- the record keys (pos + 1) << 1 of pos = 16384 w differ in
+    digits 1 and 2, the leaf bins 4681 + w in digit 0 alone --, so each result lies in another of its sort's two buffers, and each
+    sort's passes and seconds are its own call's."""
+    rnd = random.Random(7)
+    ws = list(range(182)) + [rnd.randrange(182) for _ in range(1025 - 182)]
+    rnd.shuffle(ws)
+    case = K.Case([B.rec("r%d" % i, 0, 16384 * w, 0, K._m(20)) for i, w in enumerate(ws)], [K.D5])
+    sort_kernels = ("histogram_kernel_s", "scan_kernel_s", "scatter_kernel_s")
+
+    def stream(records):
+        rec_off = np.cumsum([len(case.header)] + [len(r) for r in records]).astype(np.uint64)
+        return case.header + b"".join(records), rec_off
+
+    def host_route(records, sort):
+        """(members, out_off, the .csi, the span table as written) of the host's entries"""
+        data, rec_off = stream(records)
+        spans = nr.bam_spans(data, rec_off, case.n_ref)[0]
+        perm = nr.bam_sort_order(spans)[0] if sort else np.arange(len(records), dtype=np.uint64)
+        written = spans[perm]
+        written["off"] = np.cumsum(written["len"]) - written["len"] + np.uint64(len(case.header))
+        payloads = B.payloads(case.header, [records[i] for i in perm.tolist()])
+        members, out_off = nr.bgzf_deflate(payloads)
+        start = np.cumsum([0] + [len(p) for p in payloads]).astype(np.uint64)
+        csi, bad, _kind = nr.csi_build_bam(written, case.n_ref, K.D5, start, out_off)
+        assert bad == 0
+        return members, out_off, csi, written, spans
+
+    members, out_off, csi, written, spans = host_route(case.records, True)
+    bins = [K.reg2bin(int(r["beg"]), max(int(r["end"]), int(r["beg"]) + 1), 5) for r in written]
+    record_passes, run_passes = passes_of(spans["key"]), passes_of([int(r["tid"]) << 32 | b for r, b in zip(written, bins)])
+    assert (record_passes, run_passes) == (2, 1) and sorted(set(bins)) == list(range(4681, 4681 + 182))
+    data, rec_off = stream(case.records)
+    got = nr.bam_sorted_bgzf_csi_device(data, rec_off, case.n_ref, K.D5, True, "fixed", hip_device)
+    assert got[6:] == (0, 0, 0, 0)
+    assert got[0].tobytes() == members.tobytes() and got[1].tolist() == out_off.tolist() and got[5] == csi
+    assert got[3].tobytes() == written.tobytes()
+    sort_times, index_times = nr.bam_sort_last_times(), nr.bam_index_last_times()
+    print("record sort", sort_times, "fold", index_times)
+    assert sort_times["passes"] == record_passes and all(sort_times[k] > 0 for k in sort_kernels)
+    assert index_times["passes"] == run_passes and index_times["sort_kernel_s"] > 0 and index_times["runs"] == len(set(bins))
+    # the same records in order already, written as they come: no record sort, the fold's sort as before
+    in_order = [case.records[i] for i in got[4].tolist()]
+    members, out_off, csi, written, _spans = host_route(in_order, False)
+    data, rec_off = stream(in_order)
+    got = nr.bam_sorted_bgzf_csi_device(data, rec_off, case.n_ref, K.D5, False, "fixed", hip_device)
+    assert got[6:] == (0, 0, 0, 0)
+    assert got[0].tobytes() == members.tobytes() and got[1].tolist() == out_off.tolist() and got[5] == csi
+    sort_times = nr.bam_sort_last_times()
+    assert sort_times["passes"] == 0 and all(sort_times[k] == 0.0 for k in sort_kernels)
+    assert nr.bam_index_last_times()["passes"] == run_passes and nr.bam_index_last_times()["runs"] == len(set(bins))
 
 
 WRITTEN = [("bai", "three_members"), ("bai", "long_record"), ("bai", "member_edge_last"), ("bai", "n1025"), ("csi", "far"), ("csi", "running_maximum"),
