@@ -47,6 +47,7 @@
 
 #include "../../include/svtyper_hip.h"
 #include "../../include/svtyper_reads.h"
+#include "../../include/svtyper_bcf.h"
 
 #ifndef SVT_WINDOW_TILES
 #define SVT_WINDOW_TILES 2   // library-window mode: tiles per wave of large launches (1 = always one)
@@ -75,6 +76,7 @@
 #include "svt_bam_sort_kernel.h"
 #include "svt_bam_first_kernel.h"
 #include "svt_bam_index_kernel.h"
+#include "svt_bcf_kernel.h"
 #include "svt_bai_index.h"
 #include "svt_bgzf.h"
 #include "svt_evidence_arena.h"
@@ -204,6 +206,7 @@ void svt_batch_destroy(svt_batch* b) { free_batch(b); }
 #include "svt_entry_bam_sort.h"
 #include "svt_entry_bam_first.h"
 #include "svt_entry_bam_index.h"
+#include "svt_entry_bcf.h"
 #include "svt_entry_evidence.h"
 #include "svt_entry_library.h"
 #include "svt_entry_oneshot.h"

@@ -388,10 +388,17 @@ def parse_arguments(p, bam_help, max_reads, own):
     p.add_argument("--sort", action="store_true", help=argparse.SUPPRESS)
     p.add_argument("--tabix", action="store_true", help=argparse.SUPPRESS)
     p.add_argument("--csi", action="store_true", help=argparse.SUPPRESS)
+    # --bcf: the output as BCF2.2 in BGZF (bcf_out's docstring: what bcftools merge / concat / view -r read fastest); it takes
+    # --sort, --csi (PATH.csi, the one index a BCF has), --deflate and --huffman, and neither --bgzf nor --tabix, which are about VCF text.
+    p.add_argument("--bcf", action="store_true", help=argparse.SUPPRESS)
     args = p.parse_args()
-    if (args.sort or args.tabix) and not args.bgzf:
+    if args.bcf and args.bgzf:
+        p.error("--bcf and --bgzf name two formats for one output: give one of them")
+    if args.bcf and args.tabix:
+        p.error("--tabix indexes VCF text: the index of a --bcf output is --csi")
+    if (args.sort or args.tabix) and not (args.bgzf or args.bcf):
         p.error("--sort and --tabix need --bgzf")
-    if args.csi and not args.bgzf:
+    if args.csi and not (args.bgzf or args.bcf):
         p.error("--csi needs --bgzf")
     if args.csi and args.tabix:
         p.error("--csi and --tabix name two formats for one index: give one of them")
@@ -429,14 +436,14 @@ def run_main(driver, sharded_driver, call, args):
                    verify="crc32" if args.verify_bgzf else "off")
     job = sharded.job()
     if job is None:
-        if not args.bgzf:
+        if not (args.bgzf or getattr(args, "bcf", False)):
             return driver(*call, **options)
         with _bgzf_text(call[2], args.deflate, 0, getattr(args, "huffman", "fixed"), args) as out:
             return driver(*call[:2], out, *call[3:], **options)
     rank, world, local_rank = job
     call = call[:2] + (sharded.private_stdout(call[2]),) + call[3:]
     engine = sharded.init(local_rank)
-    if args.bgzf and rank == 0:             # (rank 0 writes everything: the others touch nothing)
+    if (args.bgzf or getattr(args, "bcf", False)) and rank == 0:             # (rank 0 writes everything: the others touch nothing)
         with _bgzf_text(call[2], args.deflate, getattr(engine, "device", local_rank), getattr(args, "huffman", "fixed"), args) as out:
             sharded_driver(*call[:2], out, *call[3:], rank=rank, world=world, engine=engine, **options)
     else:
@@ -445,7 +452,11 @@ def run_main(driver, sharded_driver, call, args):
 
 
 def _bgzf_text(vcf_out, deflate, device, huffman="fixed", args=None):
-    """`--bgzf`: the output VCF through bgzf_out.open_text (imported only here)"""
+    """`--bgzf`: the output VCF through bgzf_out.open_text; `--bcf`: through bcf_out.open_bcf (imported only here)"""
+    if getattr(args, "bcf", False):
+        from . import bcf_out
+        return bcf_out.open_bcf(vcf_out, deflate=deflate, device=device, huffman=huffman, sort=bool(getattr(args, "sort", False)),
+                                index="csi" if getattr(args, "csi", False) else None)
     from . import bgzf_out
     return bgzf_out.open_text(vcf_out, deflate=deflate, device=device, huffman=huffman, sort=bool(getattr(args, "sort", False)),
                               index="tbi" if getattr(args, "tabix", False) or getattr(args, "csi", False) else None,

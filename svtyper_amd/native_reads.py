@@ -1168,3 +1168,89 @@ def bam_index_last_times() -> Dict[str, float]:
     t = _BamIndexTimes()
     hip._check(_csi_lib().svt_bam_index_last_times(C.byref(t)))
     return {name: (int if name in ("runs", "passes") else float)(getattr(t, name)) for name, _ in _BamIndexTimes._fields_ if name != "reserved"}
+
+
+# ---- VCF text as a BCF2.2 stream: the records on the host and on the device (include/svtyper_bcf.h) ----------
+BCF_KINDS = {1: "columns", 2: "contig", 3: "pos", 4: "filter", 5: "info_key", 6: "format_key", 7: "info_value", 8: "format_value",
+             9: "samples", 10: "qual"}     # SVT_BCF_KIND_*
+BCF_SORT, BCF_EXACT_FLOATS = 1, 2
+
+
+class _BcfInfo(C.Structure):
+    _fields_ = [(name, C.c_uint64) for name in ("bytes_len", "n_offsets", "n_records", "header_len", "stream_len", "bad_line", "host_lines",
+                                                "l_ref_max")] + [("bad_kind", C.c_uint32), ("bad_at", C.c_uint32), ("n_ref", C.c_int32),
+                                                                 ("n_sample", C.c_uint32)]
+
+
+class _BcfTimes(C.Structure):
+    _fields_ = [("measure_kernel_s", C.c_double), ("write_kernel_s", C.c_double), ("total_s", C.c_double)]
+
+
+_bcf_declared = False
+
+
+def _bcf_lib():
+    global _bcf_declared
+    L = _lib()
+    if not hasattr(L, "svt_bcf_encode_host"):
+        raise hip.SvtyperHipError("this libsvtyper_hip.so has no svt_bcf_encode_host (built before BCF output)")
+    if not _bcf_declared:
+        P, U64, U32, INFO = C.c_void_p, C.c_uint64, C.c_uint32, C.POINTER(_BcfInfo)
+        for name, argtypes in (("svt_bcf_encode_host", [P, U64, U32, INFO]), ("svt_bcf_encode_device", [P, U64, U32, INFO, C.c_int]),
+                               ("svt_bcf_bgzf_device", [P, U64, U32, U32, INFO, C.c_int]), ("svt_bcf_take", [P, U64, P, U64, P, P, U64]),
+                               ("svt_bcf_last_times", [C.POINTER(_BcfTimes)])):
+            getattr(L, name).restype = C.c_int
+            getattr(L, name).argtypes = argtypes
+        _bcf_declared = True
+    return L
+
+
+def _bcf_taken(L, info, members: bool) -> dict:
+    """the fields of `info`, and with no refusal what the call left: bytes (uint8), offsets (uint64), spans (BAM_SPAN) and, for
+    members, starts (uint64)"""
+    got = {name: int(getattr(info, name)) for name, _ in _BcfInfo._fields_}
+    if info.bad_line:
+        return got
+    data = np.zeros(max(info.bytes_len, 1), np.uint8)
+    offsets = np.zeros(max(info.n_offsets, 1), np.uint64)
+    starts = np.zeros(max(info.n_offsets, 1), np.uint64)
+    spans = np.zeros(max(info.n_records, 1), BAM_SPAN)
+    hip._check(L.svt_bcf_take(data.ctypes.data, info.bytes_len, offsets.ctypes.data, info.n_offsets, starts.ctypes.data if members else None,
+                              spans.ctypes.data, info.n_records))
+    got.update(bytes=data[:info.bytes_len], offsets=offsets[:info.n_offsets], spans=spans[:info.n_records])
+    if members:
+        got["starts"] = starts[:info.n_offsets]
+    return got
+
+
+def bcf_encode(text: bytes, sort: bool = False, device: Optional[int] = None, exact_floats: bool = False) -> dict:
+    """svt_bcf_encode_host (device None) / _device, + svt_bcf_take: the BCF2.2 stream of the VCF `text` -- a dict of svt_bcf_info's
+    fields and, where bad_line is 0, `bytes` (header_len bytes of header, then the records), `offsets` (records + 1) and `spans`.
+    `exact_floats` (the host alone): floats by the device's rule first, so that host_lines counts what the device would hand over"""
+    L = _bcf_lib()
+    buf = _text_array(text)
+    info = _BcfInfo()
+    flags = (BCF_SORT if sort else 0) | (BCF_EXACT_FLOATS if exact_floats and device is None else 0)
+    if device is None:
+        hip._check(L.svt_bcf_encode_host(buf.ctypes.data, len(text), flags, C.byref(info)))
+    else:
+        hip._check(L.svt_bcf_encode_device(buf.ctypes.data, len(text), flags, C.byref(info), int(device)))
+    return _bcf_taken(L, info, False)
+
+
+def bcf_bgzf_device(text: bytes, sort: bool = False, huffman: str = "fixed", device: int = 0) -> dict:
+    """svt_bcf_bgzf_device + svt_bcf_take: `text` up once; as bcf_encode, with `bytes` the BGZF members of the stream side by side,
+    `offsets` where each begins in them and `starts` where each member's payload begins in the stream (members + 1 each)"""
+    L = _bcf_lib()
+    buf = _text_array(text)
+    info = _BcfInfo()
+    hip._check(L.svt_bcf_bgzf_device(buf.ctypes.data, len(text), BCF_SORT if sort else 0, int(check_huffman(huffman) == "dynamic"), C.byref(info),
+                                     int(device)))
+    return _bcf_taken(L, info, True)
+
+
+def bcf_last_times() -> Dict[str, float]:
+    """svt_bcf_last_times: the two kernels of this thread's last device call over BCF records, from HIP events"""
+    t = _BcfTimes()
+    hip._check(_bcf_lib().svt_bcf_last_times(C.byref(t)))
+    return {name: float(getattr(t, name)) for name, _ in _BcfTimes._fields_}
