@@ -323,6 +323,62 @@ typedef struct svt_vcf_lines_times {
     double total_s;             /* the whole call on the host's clock                                                */
 } svt_vcf_lines_times;
 int svt_vcf_lines_last_times(svt_vcf_lines_times* times);
+/* Per-sample VCFs joined by line number (svtyper_amd/paste.py; the reference's scripts/vcf_paste.py, and with
+ * SVT_PASTE_AFREQ its scripts/vcf_allele_freq.py behind it).  Added without a new SVT_ABI_VERSION: probe for the symbol.
+ * One call takes one block: text[0, len) holds n_lines body lines of the master and of each of the n_inputs inputs, every
+ * line with its newline; file f's line j is line first_line[f] + j of the text (file 0: the master, f: input f - 1).
+ * info_table (SVT_PASTE_AFREQ): the output header's INFO ids in its order, "V<id>\n" each, "F<id>\n" for a Flag.
+ * results[0, n_lines): one record per output line:
+ *   qual         the master's QUAL and every input's, added in file order
+ *   counts       (SVT_PASTE_AFREQ) how often allele 0 .. 7 stands in a GT; nonref: the GTs with a non-reference allele
+ *   flags        SVT_PASTE_SLOW_*: why the line was left to the plain C++ of the host (a QUAL outside the exact float
+ *                rule, fewer than nine columns, a GT that is not digits joined by one separator or has more than eight
+ *                alleles, an allele index above the ALT count, more than seven ALTs); SVT_PASTE_UNSAFE: SVT_PASTE_SAFE
+ *                found CHROM, POS or ID (bad_field 0, 1, 2) of input bad_input to differ from the master's
+ *   part_len     the inputs' sample columns with a tab in front of each input's; line_len: the output line
+ * out[0, info->out_len): the block's output lines.  A line that cannot be written: info->bad_line is its 1-based number in
+ * the block, bad_file the file (as above), bad_kind SVT_PASTE_BAD_*, and nothing is written (SVT_OK all the same).
+ * SVT_ERR_INVALID where capacity is below the output.  svt_vcf_paste_device: the same bytes and results from the two
+ * kernels of svt_vcf_paste_kernel.h; bits 8-9 of flags choose how the write kernel spreads its lanes over the sample
+ * parts (0: the default, 1: a lane, 2: a quarter of the wavefront, 3: the wavefront per part).                        */
+typedef struct svt_paste_line {
+    double qual;
+    uint32_t counts[8];
+    uint32_t nonref, flags, bad_input, bad_field, part_len, line_len;
+} svt_paste_line;
+typedef struct svt_paste_info {
+    uint64_t out_len, host_lines, bad_line;
+    uint32_t bad_file, bad_kind, bad_field, reserved;
+} svt_paste_info;
+#define SVT_PASTE_SUM_QUALS 1u
+#define SVT_PASTE_AFREQ 2u
+#define SVT_PASTE_SAFE 4u
+#define SVT_PASTE_LAYOUT_SHIFT 8
+#define SVT_PASTE_SLOW_QUAL 1u
+#define SVT_PASTE_SLOW_COLUMNS 2u
+#define SVT_PASTE_SLOW_GT 4u
+#define SVT_PASTE_SLOW_ALLELE 8u
+#define SVT_PASTE_SLOW_ALT 16u
+#define SVT_PASTE_UNSAFE 32u
+#define SVT_PASTE_BAD_QUAL 1u     /* a QUAL that float() refuses                                                        */
+#define SVT_PASTE_BAD_COLUMNS 2u  /* a line without the column the scripts index                                        */
+#define SVT_PASTE_BAD_GT 3u       /* a GT whose alleles int() refuses                                                   */
+#define SVT_PASTE_BAD_ALLELE 4u   /* an allele index beyond the ALT count                                               */
+#define SVT_PASTE_BAD_POS 5u      /* (SVT_PASTE_AFREQ) a POS that int() refuses                                         */
+#define SVT_PASTE_BAD_UNSAFE 6u   /* SVT_PASTE_SAFE: bad_field of bad_file differs from the master's                    */
+int svt_vcf_paste_host(const uint8_t* text, uint64_t len, const uint64_t* first_line, uint32_t n_inputs, uint64_t n_lines,
+                       uint32_t flags, const uint8_t* info_table, uint64_t info_len, uint8_t* out, uint64_t capacity,
+                       svt_paste_line* results, svt_paste_info* info);
+int svt_vcf_paste_device(const uint8_t* text, uint64_t len, const uint64_t* first_line, uint32_t n_inputs, uint64_t n_lines,
+                         uint32_t flags, const uint8_t* info_table, uint64_t info_len, uint8_t* out, uint64_t capacity,
+                         svt_paste_line* results, svt_paste_info* info, int device);
+/* the calling thread's most recent svt_vcf_paste_device: its kernels by HIP events, its copies on the host's clock    */
+typedef struct svt_vcf_paste_times {
+    double lines_kernels_s, measure_kernel_s, write_kernel_s;
+    double upload_s, download_s, host_s;   /* the text up; the results and the pasted text down; the lines' first columns */
+    double total_s;
+} svt_vcf_paste_times;
+int svt_vcf_paste_last_times(svt_vcf_paste_times* times);
 /* The index fold: the uncompressed bytes of a .tbi (SAM spec 5.2 binning, 14-bit leaves, five levels; the layout of
  * the tabix format, format = 2 (VCF), col_seq 1, col_beg 2, col_end 0, meta '#', skip 0; pseudo-bin 37450 with the
  * contig's line count) for the body lines of `lines`, a table of the text as written.  The CHROM of line j is read at

@@ -118,8 +118,8 @@ SVT_HD bool parse_int(const uint8_t* p, uint32_t b, uint32_t e, int64_t& v)
     return v >= kInt32Floor && v <= 2147483647ll;
 }
 
-// 0: f is (float)strtod(p[b, e)), computed exactly; 2: outside the envelope (the header of this file)
-SVT_HD uint32_t float_exact(const uint8_t* p, uint32_t b, uint32_t e, float& f)
+// 0: v is strtod(p[b, e)), computed exactly; 2: outside the envelope (the header of this file)
+SVT_HD uint32_t double_exact(const uint8_t* p, uint32_t b, uint32_t e, double& v)
 {
     uint32_t i = b;
     const bool neg = i < e && p[i] == '-';
@@ -160,7 +160,16 @@ SVT_HD uint32_t float_exact(const uint8_t* p, uint32_t b, uint32_t e, float& f)
     double p10 = 1.0;                               // exact: every power up to 10^22 is a double
     for (int32_t k = e10 < 0 ? -e10 : e10; k; --k) p10 *= 10.0;
     const double d = e10 < 0 ? (double)m / p10 : (double)m * p10;
-    f = (float)(neg ? -d : d);
+    v = neg ? -d : d;
+    return 0;
+}
+
+// 0: f is (float)strtod(p[b, e)), computed exactly; 2: outside the envelope
+SVT_HD uint32_t float_exact(const uint8_t* p, uint32_t b, uint32_t e, float& f)
+{
+    double d = 0.0;
+    if (const uint32_t rc = double_exact(p, b, e, d)) return rc;
+    f = (float)d;
     return 0;
 }
 

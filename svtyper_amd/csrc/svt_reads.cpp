@@ -42,6 +42,7 @@
 #include "svt_record_rules.h"
 #include "svt_tbx_index.h"
 #include "svt_vcf_lines.h"
+#include "svt_vcf_paste.h"
 
 namespace {
 using svt::fail;
@@ -66,3 +67,4 @@ using rr::ld32;
 #include "svt_reads_vcf_entries.h"     // svt_vcf_lines_host, _gather_host, _sort_order, svt_tbx_build: VCF text as lines, the .tbi fold
 #include "svt_reads_bam_sort_entries.h" // svt_bam_spans_host, _sort_order_host, svt_bai_build: BAM records as spans, the .bai fold
 #include "svt_reads_bcf_entries.h"     // svt_bcf_encode_host, svt_bcf_take: VCF text as a BCF stream
+#include "svt_reads_paste_entries.h"   // svt_vcf_paste_host: per-sample VCFs joined by line number, AF and NSAMP

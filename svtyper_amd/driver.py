@@ -375,6 +375,17 @@ def parse_arguments(p, bam_help, max_reads, own):
                         "(needs --reader native or device; same library file, same output bytes) [host]")
     p.add_argument("--geometry", choices=("host", "device"), default="host",
                    help="with --reader python: breakpoint-dependent read predicates on the host or on the GPU [host]")
+    add_output_arguments(p)
+    args = p.parse_args()
+    check_output_arguments(p, args, args.output_vcf)
+    args.input_vcf = gzip_text(args.input_vcf)
+    if args.input_vcf is None and not sys.stdin.isatty():
+        args.input_vcf = sys.stdin
+    return args
+
+
+def add_output_arguments(p):
+    """the options about the output file's format, of `svtyper`, `svtyper-sso` and `svtyper_amd.paste` alike"""
     # BGZF output (README, DESIGN 4).  Not listed by --help, like --debug: the help text of both programs is pinned byte for byte
     # (tests/golden/help_*.txt).  --bgzf: the output VCF as BGZF (.vcf.gz: what bcftools, tabix and IGV read); --deflate: who
     # compresses BGZF output (--bgzf, -w) -- zlib, or the library's own compressor on the host or on the GPU (same inflated bytes);
@@ -391,7 +402,10 @@ def parse_arguments(p, bam_help, max_reads, own):
     # --bcf: the output as BCF2.2 in BGZF (bcf_out's docstring: what bcftools merge / concat / view -r read fastest); it takes
     # --sort, --csi (PATH.csi, the one index a BCF has), --deflate and --huffman, and neither --bgzf nor --tabix, which are about VCF text.
     p.add_argument("--bcf", action="store_true", help=argparse.SUPPRESS)
-    args = p.parse_args()
+
+
+def check_output_arguments(p, args, output):
+    """the usage errors of those options; `output`: the opened output file"""
     if args.bcf and args.bgzf:
         p.error("--bcf and --bgzf name two formats for one output: give one of them")
     if args.bcf and args.tabix:
@@ -402,14 +416,10 @@ def parse_arguments(p, bam_help, max_reads, own):
         p.error("--csi needs --bgzf")
     if args.csi and args.tabix:
         p.error("--csi and --tabix name two formats for one index: give one of them")
-    if args.tabix and args.output_vcf is sys.stdout:
+    if args.tabix and output is sys.stdout:
         p.error("--tabix needs an output file (-o): an index is written beside it")
-    if args.csi and args.output_vcf is sys.stdout:
+    if args.csi and output is sys.stdout:
         p.error("--csi needs an output file (-o): an index is written beside it")
-    args.input_vcf = gzip_text(args.input_vcf)
-    if args.input_vcf is None and not sys.stdin.isatty():
-        args.input_vcf = sys.stdin
-    return args
 
 
 def gzip_text(vcf_in):

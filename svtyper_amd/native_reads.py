@@ -141,6 +141,18 @@ class _LinesTimes(C.Structure):
                 ("gather_kernel_s", C.c_double), ("total_s", C.c_double)]
 
 
+class _PasteInfo(C.Structure):
+    """include/svtyper_reads.h: svt_paste_info"""
+    _fields_ = [("out_len", C.c_uint64), ("host_lines", C.c_uint64), ("bad_line", C.c_uint64), ("bad_file", C.c_uint32),
+                ("bad_kind", C.c_uint32), ("bad_field", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class _PasteTimes(C.Structure):
+    """include/svtyper_reads.h: svt_vcf_paste_times"""
+    _fields_ = [(name, C.c_double) for name in ("lines_kernels_s", "measure_kernel_s", "write_kernel_s", "upload_s", "download_s", "host_s",
+                                                "total_s")]
+
+
 class _BamSortTimes(C.Structure):
     """include/svtyper_reads.h: svt_bam_sort_times"""
     _fields_ = [("keys_kernel_s", C.c_double), ("histogram_kernel_s", C.c_double), ("scan_kernel_s", C.c_double),
@@ -294,6 +306,14 @@ def _lib():
                                    ("svt_tbx_build", [P, U64, P, P, U64, P, U64, C.c_uint32, P, P, P]), ("svt_tbx_take", [P, U64])):
                 getattr(L, name).restype = C.c_int
                 getattr(L, name).argtypes = argtypes
+        if hasattr(L, "svt_vcf_paste_host"):       # (likewise: per-sample VCFs joined by line number, AF and NSAMP)
+            P, U64, U32 = C.c_void_p, C.c_uint64, C.c_uint32
+            L.svt_vcf_paste_host.restype = C.c_int
+            L.svt_vcf_paste_host.argtypes = [P, U64, P, U32, U64, U32, P, U64, P, U64, P, C.POINTER(_PasteInfo)]
+            L.svt_vcf_paste_device.restype = C.c_int
+            L.svt_vcf_paste_device.argtypes = L.svt_vcf_paste_host.argtypes + [C.c_int]
+            L.svt_vcf_paste_last_times.restype = C.c_int
+            L.svt_vcf_paste_last_times.argtypes = [C.POINTER(_PasteTimes)]
         if hasattr(L, "svt_bam_spans_host"):       # (likewise: BAM records as spans, the sorted and indexed `-w` dump)
             P, U64, I32 = C.c_void_p, C.c_uint64, C.c_int32
             for name, argtypes in (("svt_bam_spans_host", [P, U64, P, U64, I32, P, P, P]), ("svt_bam_spans_device", [P, U64, P, U64, I32, P, P, P, C.c_int]),
@@ -916,6 +936,57 @@ def vcf_lines_last_times() -> Dict[str, float]:
     t = _LinesTimes()
     hip._check(_lines_lib().svt_vcf_lines_last_times(C.byref(t)))
     return {name: float(getattr(t, name)) for name, _ in _LinesTimes._fields_}
+
+
+PASTE_LINE = np.dtype([("qual", np.float64), ("counts", np.uint32, (8,)), ("nonref", np.uint32), ("flags", np.uint32),
+                       ("bad_input", np.uint32), ("bad_field", np.uint32), ("part_len", np.uint32), ("line_len", np.uint32)])    # svt_paste_line
+PASTE_SUM_QUALS, PASTE_AFREQ, PASTE_SAFE, PASTE_LAYOUT_SHIFT = 1, 2, 4, 8
+PASTE_SLOW_QUAL, PASTE_SLOW_COLUMNS, PASTE_SLOW_GT, PASTE_SLOW_ALLELE, PASTE_SLOW_ALT, PASTE_UNSAFE = 1, 2, 4, 8, 16, 32
+PASTE_SLOW = PASTE_SLOW_QUAL | PASTE_SLOW_COLUMNS | PASTE_SLOW_GT | PASTE_SLOW_ALLELE | PASTE_SLOW_ALT
+PASTE_BAD_QUAL, PASTE_BAD_COLUMNS, PASTE_BAD_GT, PASTE_BAD_ALLELE, PASTE_BAD_POS, PASTE_BAD_UNSAFE = 1, 2, 3, 4, 5, 6
+PASTE_LAYOUTS = {"default": 0, "lane": 1, "quarter": 2, "wave": 3}
+
+
+def _paste_lib():
+    L = _lib()
+    if not hasattr(L, "svt_vcf_paste_host"):
+        raise hip.SvtyperHipError("this libsvtyper_hip.so has no svt_vcf_paste_host (built before svtyper_amd.paste)")
+    return L
+
+
+def vcf_paste(text: bytes, first_line, n_inputs: int, n_lines: int, flags: int, info_table: bytes = b"", device: Optional[int] = None,
+              layout: str = "default"):
+    """svt_vcf_paste_host (device None) / _device over one block: `text` holds n_lines lines of the master and of every input, file
+    f's from line first_line[f] on.  (the pasted lines as bytes, results PASTE_LINE [n_lines], info); info: host_lines, and where a
+    line cannot be written bad_line (1-based in the block), bad_file (0: the master, f: input f - 1), bad_kind, bad_field -- the
+    bytes are then empty"""
+    L = _paste_lib()
+    buf = _text_array(text)
+    first_line = np.ascontiguousarray(first_line, np.uint64)
+    if first_line.shape[0] != n_inputs + 1:
+        raise ValueError("first_line has one entry for the master and one per input")
+    info_buf = _text_array(info_table)
+    # an output line is its master's and inputs' bytes, a QUAL and -- under PASTE_AFREQ -- "AF=...;NSAMP=..." with up to
+    # 12 bytes per ALT, of which the master's line has less than it has bytes
+    capacity = 14 * len(text) + (400 + len(info_table)) * max(n_lines, 1)
+    out = np.empty(max(capacity, 1), np.uint8)
+    results = np.zeros(max(n_lines, 1), PASTE_LINE)
+    info = _PasteInfo()
+    args = [buf.ctypes.data, len(text), first_line.ctypes.data, n_inputs, n_lines, int(flags) | PASTE_LAYOUTS[layout] << PASTE_LAYOUT_SHIFT,
+            info_buf.ctypes.data, len(info_table), out.ctypes.data, capacity, results.ctypes.data, C.byref(info)]
+    if device is None:
+        hip._check(L.svt_vcf_paste_host(*args))
+    else:
+        hip._check(L.svt_vcf_paste_device(*args, int(device)))
+    report = {name: int(getattr(info, name)) for name, _ in _PasteInfo._fields_ if name != "reserved"}
+    return out[:info.out_len].tobytes(), results[:n_lines], report
+
+
+def vcf_paste_last_times() -> Dict[str, float]:
+    """svt_vcf_paste_last_times: the kernels of this thread's last svt_vcf_paste_device from HIP events, its copies on the host's clock"""
+    t = _PasteTimes()
+    hip._check(_paste_lib().svt_vcf_paste_last_times(C.byref(t)))
+    return {name: float(getattr(t, name)) for name, _ in _PasteTimes._fields_}
 
 
 def tbx_build(text: bytes, lines: np.ndarray, member_off, src_off=None, payload: int = DEFLATE_MAX_PAYLOAD, csi: bool = False):
