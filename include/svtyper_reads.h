@@ -379,6 +379,87 @@ typedef struct svt_vcf_paste_times {
     double total_s;
 } svt_vcf_paste_times;
 int svt_vcf_paste_last_times(svt_vcf_paste_times* times);
+/* The read-depth classifier of DEL and DUP lines (svtyper_amd/classify.py; the reference's scripts/sv_classifier.py).
+ * Added without a new SVT_ABI_VERSION: probe for the symbol.  One call takes one block: text[0, len) holds body lines of the
+ * cohort VCF, every line with its newline, each with n_samples sample columns.  male, female, excluded [n_samples]: one
+ * byte per sample of the header, 1 where the gender file says 1 (male) or 2 (female) and where the exclude file names
+ * the sample; a sample the gender file does not name is SVT_CLASSIFY_NO_GENDER in male and in female.  format_table: the
+ * output header's FORMAT ids in its order ("GT\n" first), "<id>\n" each.  skip [n_lines] or NULL: 1 for a line the
+ * caller has settled already (an MEI): its record is route SVT_CLASSIFY_SKIPPED and nothing else is looked at.
+ * results[0, *n_lines), capacity records: one per line of the text:
+ *   route        SVT_CLASSIFY_VERBATIM (the first INFO item "SVTYPE=" is not DEL or DUP: the line is written as it is),
+ *                _LOW (fewer than 10 positive samples: medians), _HIGH (the regression), _DROPPED (a later SVTYPE item
+ *                is neither: the script writes nothing), _SKIPPED
+ *   verdict      1: read depth supports the call, the line stays; 0: it is split into two BND lines
+ *   n_pos        the samples not excluded whose GT is neither "./." nor "0/0"
+ *   n_ref, n_alt (low) the two lists of CN values the script compares; quorum: the supporting ones of n_alt;
+ *                median, mad: of the n_ref values (0 where there is none)
+ *   slope, r2, n_regressed   (high) of CN against AB over the samples whose AB is neither "." nor -1 (0 where the
+ *                regression does not run: no CN, a uniform AB or CN)
+ *   flags        SVT_CLASSIFY_SLOW_*: why the line was left to the plain C++ of the host (values and verdict are then
+ *                that code's); SVT_CLASSIFY_NEAR: r2 or the signed slope lies within 1e-9 (relative; absolute for a
+ *                threshold of 0) of its threshold; SVT_CLASSIFY_DEL: the type is DEL
+ * A line the script dies on: info->bad_line is its 1-based number in the block, bad_kind SVT_CLASSIFY_BAD_*, bad_sample
+ * the sample (or 0xFFFFFFFF), bad_text the key or token in the way (SVT_OK all the same).  svt_vcf_classify_device: the
+ * same records from svt_vcf_classify_kernel.h, byte for byte.
+ * svt_vcf_classify_write: the output text of the block from its records (both engines' text is written here): verbatim
+ * lines as they are, kept lines rebuilt as get_var_string does, the others as their two BND lines; out_off[0 .. n_lines]
+ * is where each line's output lies (skipped and dropped lines: nothing).  The text is kept for the calling thread:
+ * info->out_len is its length, svt_vcf_classify_take copies it out.  info_table: as svt_vcf_paste_host's.               */
+typedef struct svt_classify_line {
+    double median, mad, slope, r2;
+    uint32_t route, verdict, n_pos, n_ref, n_alt, quorum, n_regressed, flags;
+} svt_classify_line;
+typedef struct svt_classify_info {
+    uint64_t out_len, host_lines, near_lines, bad_line;
+    uint32_t bad_kind, bad_sample;
+    char bad_text[48];
+} svt_classify_info;
+#define SVT_CLASSIFY_CAPACITY 4096u  /* the samples of a line the kernel holds in LDS                                  */
+#define SVT_CLASSIFY_NO_GENDER 255u
+#define SVT_CLASSIFY_VERBATIM 0u
+#define SVT_CLASSIFY_LOW 1u
+#define SVT_CLASSIFY_HIGH 2u
+#define SVT_CLASSIFY_DROPPED 3u
+#define SVT_CLASSIFY_SKIPPED 4u
+#define SVT_CLASSIFY_SLOW_HEAD 1u      /* fewer than ten columns, a POS or QUAL outside the exact rules, SVTYPE twice   */
+#define SVT_CLASSIFY_SLOW_FORMAT 2u    /* FORMAT is not GT first and the header's keys in the header's order           */
+#define SVT_CLASSIFY_SLOW_COLUMNS 4u   /* not one column per sample of the header                                       */
+#define SVT_CLASSIFY_SLOW_SAMPLE 8u    /* a sample column without exactly FORMAT's fields                               */
+#define SVT_CLASSIFY_SLOW_TOKEN 16u    /* a CN or AB outside bcf::double_exact                                          */
+#define SVT_CLASSIFY_SLOW_CAPACITY 32u /* more than SVT_CLASSIFY_CAPACITY samples, or none                              */
+#define SVT_CLASSIFY_SLOW_GENDER 64u   /* X or Y and a sample without a gender                                          */
+#define SVT_CLASSIFY_SLOW_KEYS 128u    /* the route reads a CN or AB that FORMAT lacks                                  */
+#define SVT_CLASSIFY_SLOW 255u
+#define SVT_CLASSIFY_NEAR 256u
+#define SVT_CLASSIFY_DEL 512u
+#define SVT_CLASSIFY_BAD_COLUMNS 1u    /* fewer than eight columns (IndexError)                                         */
+#define SVT_CLASSIFY_BAD_POS 2u        /* a POS that int() refuses (ValueError)                                         */
+#define SVT_CLASSIFY_BAD_QUAL 3u       /* a QUAL that float() refuses (ValueError)                                      */
+#define SVT_CLASSIFY_BAD_FORMAT 4u     /* a FORMAT key the header does not declare (the script's message, status 1)     */
+#define SVT_CLASSIFY_BAD_KEY 5u        /* bad_text: the FORMAT key a sample or the INFO key the line lacks (KeyError)   */
+#define SVT_CLASSIFY_BAD_NUMBER 6u     /* bad_text: a CN or AB that float() refuses (ValueError)                        */
+#define SVT_CLASSIFY_BAD_NONFINITE 7u  /* bad_text: a CN or AB that is nan or inf (a departure: DESIGN 3.4)             */
+#define SVT_CLASSIFY_BAD_GENDER 8u     /* X or Y and a sample the gender file does not name (KeyError)                  */
+int svt_vcf_classify_host(const uint8_t* text, uint64_t len, uint32_t n_samples, const uint8_t* male, const uint8_t* female,
+                          const uint8_t* excluded, const uint8_t* format_table, uint64_t format_len, const uint8_t* skip,
+                          double slope_threshold, double rsquared_threshold, svt_classify_line* results, uint64_t capacity,
+                          uint64_t* n_lines, svt_classify_info* info);
+int svt_vcf_classify_device(const uint8_t* text, uint64_t len, uint32_t n_samples, const uint8_t* male, const uint8_t* female,
+                            const uint8_t* excluded, const uint8_t* format_table, uint64_t format_len, const uint8_t* skip,
+                            double slope_threshold, double rsquared_threshold, svt_classify_line* results, uint64_t capacity,
+                            uint64_t* n_lines, svt_classify_info* info, int device);
+int svt_vcf_classify_write(const uint8_t* text, uint64_t len, uint32_t n_samples, const uint8_t* info_table, uint64_t info_len,
+                           const uint8_t* format_table, uint64_t format_len, const svt_classify_line* results, uint64_t n_lines,
+                           uint64_t* out_off, svt_classify_info* info);
+int svt_vcf_classify_take(uint8_t* out, uint64_t capacity);
+/* the calling thread's most recent svt_vcf_classify_device: its kernels by HIP events, its copies on the host's clock  */
+typedef struct svt_vcf_classify_times {
+    double lines_kernels_s, classify_kernel_s;
+    double upload_s, download_s, host_s;    /* the text up; the records down; the marked lines on the host             */
+    double total_s;
+} svt_vcf_classify_times;
+int svt_vcf_classify_last_times(svt_vcf_classify_times* times);
 /* The index fold: the uncompressed bytes of a .tbi (SAM spec 5.2 binning, 14-bit leaves, five levels; the layout of
  * the tabix format, format = 2 (VCF), col_seq 1, col_beg 2, col_end 0, meta '#', skip 0; pseudo-bin 37450 with the
  * contig's line count) for the body lines of `lines`, a table of the text as written.  The CHROM of line j is read at

@@ -43,6 +43,7 @@
 #include "svt_tbx_index.h"
 #include "svt_vcf_lines.h"
 #include "svt_vcf_paste.h"
+#include "svt_vcf_classify.h"
 
 namespace {
 using svt::fail;
@@ -68,3 +69,4 @@ using rr::ld32;
 #include "svt_reads_bam_sort_entries.h" // svt_bam_spans_host, _sort_order_host, svt_bai_build: BAM records as spans, the .bai fold
 #include "svt_reads_bcf_entries.h"     // svt_bcf_encode_host, svt_bcf_take: VCF text as a BCF stream
 #include "svt_reads_paste_entries.h"   // svt_vcf_paste_host: per-sample VCFs joined by line number, AF and NSAMP
+#include "svt_reads_classify_entries.h" // svt_vcf_classify_host, _write, _take: the read-depth classifier of DEL and DUP lines

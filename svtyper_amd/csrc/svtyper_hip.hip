@@ -73,6 +73,7 @@
 #include "svt_deflate_kernel.h"
 #include "svt_vcf_lines_kernel.h"
 #include "svt_vcf_paste_kernel.h"
+#include "svt_vcf_classify_kernel.h"
 #include "svt_radix_sort_kernel.h"
 #include "svt_bam_sort_kernel.h"
 #include "svt_bam_first_kernel.h"
@@ -204,6 +205,7 @@ void svt_batch_destroy(svt_batch* b) { free_batch(b); }
 #include "svt_entry_deflate.h"
 #include "svt_entry_vcf_lines.h"
 #include "svt_entry_vcf_paste.h"
+#include "svt_entry_vcf_classify.h"
 #include "svt_entry_radix_sort.h"
 #include "svt_entry_bam_sort.h"
 #include "svt_entry_bam_first.h"

@@ -153,6 +153,17 @@ class _PasteTimes(C.Structure):
                                                 "total_s")]
 
 
+class _ClassifyInfo(C.Structure):
+    """include/svtyper_reads.h: svt_classify_info"""
+    _fields_ = [("out_len", C.c_uint64), ("host_lines", C.c_uint64), ("near_lines", C.c_uint64), ("bad_line", C.c_uint64),
+                ("bad_kind", C.c_uint32), ("bad_sample", C.c_uint32), ("bad_text", C.c_char * 48)]
+
+
+class _ClassifyTimes(C.Structure):
+    """include/svtyper_reads.h: svt_vcf_classify_times"""
+    _fields_ = [(name, C.c_double) for name in ("lines_kernels_s", "classify_kernel_s", "upload_s", "download_s", "host_s", "total_s")]
+
+
 class _BamSortTimes(C.Structure):
     """include/svtyper_reads.h: svt_bam_sort_times"""
     _fields_ = [("keys_kernel_s", C.c_double), ("histogram_kernel_s", C.c_double), ("scan_kernel_s", C.c_double),
@@ -314,6 +325,18 @@ def _lib():
             L.svt_vcf_paste_device.argtypes = L.svt_vcf_paste_host.argtypes + [C.c_int]
             L.svt_vcf_paste_last_times.restype = C.c_int
             L.svt_vcf_paste_last_times.argtypes = [C.POINTER(_PasteTimes)]
+        if hasattr(L, "svt_vcf_classify_host"):    # (likewise: the read-depth classifier of DEL and DUP lines)
+            P, U64, U32, D = C.c_void_p, C.c_uint64, C.c_uint32, C.c_double
+            L.svt_vcf_classify_host.restype = C.c_int
+            L.svt_vcf_classify_host.argtypes = [P, U64, U32, P, P, P, P, U64, P, D, D, P, U64, P, C.POINTER(_ClassifyInfo)]
+            L.svt_vcf_classify_device.restype = C.c_int
+            L.svt_vcf_classify_device.argtypes = L.svt_vcf_classify_host.argtypes + [C.c_int]
+            L.svt_vcf_classify_write.restype = C.c_int
+            L.svt_vcf_classify_write.argtypes = [P, U64, U32, P, U64, P, U64, P, U64, P, C.POINTER(_ClassifyInfo)]
+            L.svt_vcf_classify_take.restype = C.c_int
+            L.svt_vcf_classify_take.argtypes = [P, U64]
+            L.svt_vcf_classify_last_times.restype = C.c_int
+            L.svt_vcf_classify_last_times.argtypes = [C.POINTER(_ClassifyTimes)]
         if hasattr(L, "svt_bam_spans_host"):       # (likewise: BAM records as spans, the sorted and indexed `-w` dump)
             P, U64, I32 = C.c_void_p, C.c_uint64, C.c_int32
             for name, argtypes in (("svt_bam_spans_host", [P, U64, P, U64, I32, P, P, P]), ("svt_bam_spans_device", [P, U64, P, U64, I32, P, P, P, C.c_int]),
@@ -987,6 +1010,86 @@ def vcf_paste_last_times() -> Dict[str, float]:
     t = _PasteTimes()
     hip._check(_paste_lib().svt_vcf_paste_last_times(C.byref(t)))
     return {name: float(getattr(t, name)) for name, _ in _PasteTimes._fields_}
+
+
+CLASSIFY_LINE = np.dtype([("median", np.float64), ("mad", np.float64), ("slope", np.float64), ("r2", np.float64), ("route", np.uint32),
+                          ("verdict", np.uint32), ("n_pos", np.uint32), ("n_ref", np.uint32), ("n_alt", np.uint32), ("quorum", np.uint32),
+                          ("n_regressed", np.uint32), ("flags", np.uint32)])         # svt_classify_line
+CLASSIFY_CAPACITY, CLASSIFY_NO_GENDER = 4096, 255
+CLASSIFY_VERBATIM, CLASSIFY_LOW, CLASSIFY_HIGH, CLASSIFY_DROPPED, CLASSIFY_SKIPPED = 0, 1, 2, 3, 4
+(CLASSIFY_SLOW_HEAD, CLASSIFY_SLOW_FORMAT, CLASSIFY_SLOW_COLUMNS, CLASSIFY_SLOW_SAMPLE, CLASSIFY_SLOW_TOKEN, CLASSIFY_SLOW_CAPACITY,
+ CLASSIFY_SLOW_GENDER, CLASSIFY_SLOW_KEYS) = 1, 2, 4, 8, 16, 32, 64, 128
+CLASSIFY_SLOW, CLASSIFY_NEAR, CLASSIFY_DEL = 255, 256, 512
+(CLASSIFY_BAD_COLUMNS, CLASSIFY_BAD_POS, CLASSIFY_BAD_QUAL, CLASSIFY_BAD_FORMAT, CLASSIFY_BAD_KEY, CLASSIFY_BAD_NUMBER, CLASSIFY_BAD_NONFINITE,
+ CLASSIFY_BAD_GENDER) = 1, 2, 3, 4, 5, 6, 7, 8
+
+
+def _classify_lib():
+    L = _lib()
+    if not hasattr(L, "svt_vcf_classify_host"):
+        raise hip.SvtyperHipError("this libsvtyper_hip.so has no svt_vcf_classify_host (built before svtyper_amd.classify)")
+    return L
+
+
+def _classify_report(info) -> dict:
+    report = {name: int(getattr(info, name)) for name, _ in _ClassifyInfo._fields_ if name != "bad_text"}
+    report["bad_text"] = bytes(info.bad_text).decode("utf-8", "surrogateescape")
+    return report
+
+
+def vcf_classify(text: bytes, male, female, excluded, format_table: bytes, slope_threshold: float, rsquared_threshold: float, skip=None,
+                 device: Optional[int] = None):
+    """svt_vcf_classify_host (device None) / _device over one block of body lines: (records CLASSIFY_LINE, one per line, info);
+    male, female, excluded: one byte per sample of the header; skip: one byte per line or None.  info: host_lines, near_lines and,
+    where the script dies on a line, bad_line (1-based in the block), bad_kind, bad_sample, bad_text"""
+    L = _classify_lib()
+    buf = _text_array(text)
+    tables = [np.ascontiguousarray(t, np.uint8) for t in (male, female, excluded)]
+    n_samples = tables[0].shape[0]
+    if any(t.shape != (n_samples,) for t in tables):
+        raise ValueError("male, female and excluded hold one byte per sample")
+    tables = [t if n_samples else np.zeros(1, np.uint8) for t in tables]
+    capacity = text.count(b"\n") + 1
+    if skip is not None:
+        skip = np.ascontiguousarray(skip, np.uint8)
+        if skip.shape[0] < capacity - (text.endswith(b"\n") or not text):
+            raise ValueError("skip holds one byte per line")
+    fmt = _text_array(format_table)
+    results = np.zeros(capacity, CLASSIFY_LINE)
+    n_lines = C.c_uint64(0)
+    info = _ClassifyInfo()
+    args = [buf.ctypes.data, len(text), n_samples, tables[0].ctypes.data, tables[1].ctypes.data, tables[2].ctypes.data, fmt.ctypes.data,
+            len(format_table), skip.ctypes.data if skip is not None else None, float(slope_threshold), float(rsquared_threshold),
+            results.ctypes.data, capacity, C.addressof(n_lines), C.byref(info)]
+    if device is None:
+        hip._check(L.svt_vcf_classify_host(*args))
+    else:
+        hip._check(L.svt_vcf_classify_device(*args, int(device)))
+    return results[:n_lines.value], _classify_report(info)
+
+
+def vcf_classify_write(text: bytes, n_samples: int, info_table: bytes, format_table: bytes, results: np.ndarray):
+    """svt_vcf_classify_write + _take: (the block's output text, out_off [lines + 1], info); where a line cannot be written (an
+    unsupported call without END, SVLEN or a confidence interval) info has bad_line, bad_kind, bad_text and the text ends in
+    front of that line"""
+    L = _classify_lib()
+    buf, inf, fmt = _text_array(text), _text_array(info_table), _text_array(format_table)
+    results = np.ascontiguousarray(results, CLASSIFY_LINE)
+    out_off = np.zeros(results.shape[0] + 1, np.uint64)
+    info = _ClassifyInfo()
+    hip._check(L.svt_vcf_classify_write(buf.ctypes.data, len(text), int(n_samples), inf.ctypes.data, len(info_table), fmt.ctypes.data,
+                                        len(format_table), results.ctypes.data if results.shape[0] else None, results.shape[0],
+                                        out_off.ctypes.data, C.byref(info)))
+    out = np.empty(max(info.out_len, 1), np.uint8)
+    hip._check(L.svt_vcf_classify_take(out.ctypes.data, info.out_len))
+    return out[:info.out_len].tobytes(), out_off, _classify_report(info)
+
+
+def vcf_classify_last_times() -> Dict[str, float]:
+    """svt_vcf_classify_last_times: the kernels of this thread's last svt_vcf_classify_device from HIP events, its copies on the host's clock"""
+    t = _ClassifyTimes()
+    hip._check(_classify_lib().svt_vcf_classify_last_times(C.byref(t)))
+    return {name: float(getattr(t, name)) for name, _ in _ClassifyTimes._fields_}
 
 
 def tbx_build(text: bytes, lines: np.ndarray, member_off, src_off=None, payload: int = DEFLATE_MAX_PAYLOAD, csi: bool = False):

@@ -108,18 +108,23 @@ def _unquoted(desc: str) -> str:
     return desc[1:-1] if desc.startswith('"') and desc.endswith('"') else desc
 
 
-def afreq_header(header_lines: List[str], chrom_line: str, file_date: str, keep_contigs: bool):
-    """vcf_allele_freq.py's header for the pasted header (`header_lines` without their newlines): (text, INFO table of the native
-    call).  fileformat, fileDate, reference, then the FILTER, INFO, ALT and FORMAT lines rebuilt from their attributes, GT the
-    first FORMAT, AF and NSAMP behind the declared INFOs; everything else is dropped, ##contig too unless `keep_contigs`"""
+def add_attributes(table, values, width, error):
+    """one header line's attributes into its table, the first line of an ID winning"""
+    if len(values) != width:
+        raise error("a header line with %d attributes where %d are read: %s" % (len(values), width, ",".join(values)))
+    if values[0] not in [row[0] for row in table]:
+        table.append(tuple(values))
+
+
+def header_attributes(header_lines: List[str], error):
+    """What the Vcf class of the reference's scripts (vcf_allele_freq.py, sv_classifier.py) reads off a header (`header_lines`
+    without their newlines): (fileformat, reference, FILTER, INFO, ALT, FORMAT tables), GT the first FORMAT; `error`: the
+    exception of a line whose attributes cannot be read"""
     file_format, reference = "VCFv4.2", ""
     filters, infos, alts, formats = [], [], [], [("GT", "1", "String", "Genotype")]
 
     def add(table, values, width):
-        if len(values) != width:
-            raise PasteError("a header line with %d attributes where %d are read: %s" % (len(values), width, ",".join(values)))
-        if values[0] not in [row[0] for row in table]:
-            table.append(tuple(values))
+        add_attributes(table, values, width, error)
 
     for bare in header_lines:
         line = bare + "\n"
@@ -138,20 +143,38 @@ def afreq_header(header_lines: List[str], chrom_line: str, file_date: str, keep_
             elif key == "##FILTER":
                 add(filters, _attributes(line, lambda t: -2), 2)
         except IndexError:
-            raise PasteError("a header line whose attributes are not key=value: %s" % bare) from None
-    add(infos, ["AF", "A", "Float", "Allele Frequency, for each ALT allele, in the same order as listed"], 4)
-    add(infos, ["NSAMP", "1", "Integer", "Number of samples with non-reference genotypes"], 4)
-    out = ["##fileformat=" + file_format, "##fileDate=" + file_date, "##reference=" + reference]
-    out += ['##FILTER=<ID=%s,Description="%s">' % (i, _unquoted(d)) for i, d in filters]
-    out += ['##INFO=<ID=%s,Number=%s,Type=%s,Description="%s">' % (i, n, t, _unquoted(d)) for i, n, t, d in infos]
+            raise error("a header line whose attributes are not key=value: %s" % bare) from None
+    return file_format, reference, filters, infos, alts, formats
+
+
+def declared_lines(infos, alts, formats) -> List[str]:
+    """the ##INFO, ##ALT and ##FORMAT lines rebuilt from their attributes"""
+    out = ['##INFO=<ID=%s,Number=%s,Type=%s,Description="%s">' % (i, n, t, _unquoted(d)) for i, n, t, d in infos]
     out += ['##ALT=<ID=%s,Description="%s">' % (i, _unquoted(d)) for i, d in alts]
     out += ['##FORMAT=<ID=%s,Number=%s,Type=%s,Description="%s">' % (i, n, t, _unquoted(d)) for i, n, t, d in formats]
+    return out
+
+
+def info_table(infos) -> bytes:
+    """the INFO table of the native calls: "V<id>\\n" per id in the header's order, "F<id>\\n" for a Flag"""
+    return "".join(("F" if t == "Flag" else "V") + i + "\n" for i, _, t, _ in infos).encode("utf-8", "surrogateescape")
+
+
+def afreq_header(header_lines: List[str], chrom_line: str, file_date: str, keep_contigs: bool):
+    """vcf_allele_freq.py's header for the pasted header (`header_lines` without their newlines): (text, INFO table of the native
+    call).  fileformat, fileDate, reference, then the FILTER, INFO, ALT and FORMAT lines rebuilt from their attributes, GT the
+    first FORMAT, AF and NSAMP behind the declared INFOs; everything else is dropped, ##contig too unless `keep_contigs`"""
+    file_format, reference, filters, infos, alts, formats = header_attributes(header_lines, PasteError)
+    add_attributes(infos, ["AF", "A", "Float", "Allele Frequency, for each ALT allele, in the same order as listed"], 4, PasteError)
+    add_attributes(infos, ["NSAMP", "1", "Integer", "Number of samples with non-reference genotypes"], 4, PasteError)
+    out = ["##fileformat=" + file_format, "##fileDate=" + file_date, "##reference=" + reference]
+    out += ['##FILTER=<ID=%s,Description="%s">' % (i, _unquoted(d)) for i, d in filters]
+    out += declared_lines(infos, alts, formats)
     if keep_contigs:
         out += [line for line in header_lines if line.startswith("##contig")]
     out.append("\t".join(["#CHROM", "POS", "ID", "REF", "ALT", "QUAL", "FILTER", "INFO"]))
     text = "\n".join(out) + "\t" + "\t".join(chrom_line.rstrip().split("\t")[8:]) + "\n"
-    table = "".join(("F" if t == "Flag" else "V") + i + "\n" for i, _, t, _ in infos)
-    return text, table.encode("utf-8", "surrogateescape")
+    return text, info_table(infos)
 
 
 def paste(vcf_list, master=None, sum_quals=False, afreq=False, safe=False, keep_contigs=False, vcf_out=sys.stdout, engine="host",
