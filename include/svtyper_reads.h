@@ -460,6 +460,69 @@ typedef struct svt_vcf_classify_times {
     double total_s;
 } svt_vcf_classify_times;
 int svt_vcf_classify_last_times(svt_vcf_classify_times* times);
+/* PE, SR, SU and MSQ of a cohort VCF from the genotyper's evidence (svtyper_amd/update_info.py; the reference's
+ * scripts/update_info.py).  Added without a new SVT_ABI_VERSION: probe for the symbol.  One call takes one block, as
+ * svt_vcf_classify_host does: text[0, len) holds body lines, every line with its newline; format_table: the output
+ * header's FORMAT ids in its order ("GT\n" first), "<id>\n" each.  results[0, *n_lines), capacity records, one per line:
+ *   pe, sr       int(AP) and int(AS) added over the header's samples
+ *   sum_sq       the bits of the double that float(SQ) of the positive samples (GT neither "0/0" nor "./.") add up to, in
+ *                sample order from +0.0; num_pos: how many they are
+ *   route        SVT_UPDATE_INFO_RULE: the per-line rule computed the record and the sample part of the output is a slice
+ *                of the input; _PLAIN: the plain C++ of the host did, and the line is written again field by field
+ *   flags        SVT_UPDATE_INFO_SLOW_*: why the line was left to the plain C++
+ * A line the script dies on: info->bad_line is its 1-based number in the block, bad_kind SVT_UPDATE_INFO_BAD_*, bad_sample
+ * the sample (or 0xFFFFFFFF), bad_text the key or token in the way (SVT_OK all the same).  svt_vcf_update_info_device: the
+ * same records from svt_vcf_update_info_kernel.h, byte for byte.
+ * svt_vcf_update_info_write: the output text of the block from its records (both engines' text is written here), every
+ * line rebuilt as the script's get_var_string does with PE, SR, SU and MSQ set; out_off[0 .. n_lines] is where each line's
+ * output lies.  info_table: as svt_vcf_paste_host's, without SNAME and with MSQ.  The text is kept for the calling thread:
+ * info->out_len is its length, svt_vcf_update_info_take copies it out.                                                  */
+typedef struct svt_update_info_line {
+    int64_t pe, sr;
+    uint64_t sum_sq;
+    uint32_t num_pos, route, flags, reserved;
+} svt_update_info_line;
+typedef struct svt_update_info_report {
+    uint64_t out_len, host_lines, bad_line;
+    uint32_t bad_kind, bad_sample;
+    char bad_text[48];
+} svt_update_info_report;
+#define SVT_UPDATE_INFO_CAPACITY 4096u    /* the samples of a line the kernel holds in LDS                              */
+#define SVT_UPDATE_INFO_RULE 0u
+#define SVT_UPDATE_INFO_PLAIN 1u
+#define SVT_UPDATE_INFO_SLOW_HEAD 1u      /* fewer than nine columns, a POS or QUAL outside the exact rules              */
+#define SVT_UPDATE_INFO_SLOW_FORMAT 2u    /* FORMAT is not GT first and the header's keys in the header's order         */
+#define SVT_UPDATE_INFO_SLOW_COLUMNS 4u   /* not one column per sample of the header                                     */
+#define SVT_UPDATE_INFO_SLOW_SAMPLE 8u    /* a sample column without exactly FORMAT's fields                             */
+#define SVT_UPDATE_INFO_SLOW_TOKEN 16u    /* an AP or AS that is not one to nine digits, an SQ outside bcf::double_exact  */
+#define SVT_UPDATE_INFO_SLOW_CAPACITY 32u /* more than SVT_UPDATE_INFO_CAPACITY samples, or none                         */
+#define SVT_UPDATE_INFO_SLOW_KEYS 64u     /* FORMAT lacks AP or AS, or SQ where a sample is positive                     */
+#define SVT_UPDATE_INFO_SLOW 127u
+#define SVT_UPDATE_INFO_BAD_COLUMNS 1u    /* fewer than seven columns (IndexError)                                       */
+#define SVT_UPDATE_INFO_BAD_POS 2u        /* a POS that int() refuses (ValueError)                                       */
+#define SVT_UPDATE_INFO_BAD_QUAL 3u       /* a QUAL that float() refuses (ValueError)                                    */
+#define SVT_UPDATE_INFO_BAD_FORMAT 4u     /* a FORMAT key the header does not declare (the script's message, status 1)   */
+#define SVT_UPDATE_INFO_BAD_KEY 5u        /* bad_text: the FORMAT key the sample lacks (KeyError)                        */
+#define SVT_UPDATE_INFO_BAD_NUMBER 6u     /* bad_text: an AP, AS or SQ that int() or float() refuses (ValueError)        */
+#define SVT_UPDATE_INFO_BAD_NONFINITE 7u  /* bad_text: an SQ that is nan or inf (a departure: DESIGN 3.4)                */
+#define SVT_UPDATE_INFO_BAD_OVERFLOW 8u   /* a count or a sum beyond int64 (a departure: DESIGN 3.4)                     */
+#define SVT_UPDATE_INFO_BAD_EIGHT 9u      /* seven columns (the script's message, status 1)                              */
+int svt_vcf_update_info_host(const uint8_t* text, uint64_t len, uint32_t n_samples, const uint8_t* format_table, uint64_t format_len,
+                             svt_update_info_line* results, uint64_t capacity, uint64_t* n_lines, svt_update_info_report* info);
+int svt_vcf_update_info_device(const uint8_t* text, uint64_t len, uint32_t n_samples, const uint8_t* format_table,
+                               uint64_t format_len, svt_update_info_line* results, uint64_t capacity, uint64_t* n_lines,
+                               svt_update_info_report* info, int device);
+int svt_vcf_update_info_write(const uint8_t* text, uint64_t len, uint32_t n_samples, const uint8_t* info_table, uint64_t info_len,
+                              const uint8_t* format_table, uint64_t format_len, const svt_update_info_line* results,
+                              uint64_t n_lines, uint64_t* out_off, svt_update_info_report* info);
+int svt_vcf_update_info_take(uint8_t* out, uint64_t capacity);
+/* the calling thread's most recent svt_vcf_update_info_device: its kernels by HIP events, its copies on the host's clock */
+typedef struct svt_vcf_update_info_times {
+    double lines_kernels_s, update_info_kernel_s;
+    double upload_s, download_s, host_s;    /* the text up; the records down; the marked lines on the host             */
+    double total_s;
+} svt_vcf_update_info_times;
+int svt_vcf_update_info_last_times(svt_vcf_update_info_times* times);
 /* The index fold: the uncompressed bytes of a .tbi (SAM spec 5.2 binning, 14-bit leaves, five levels; the layout of
  * the tabix format, format = 2 (VCF), col_seq 1, col_beg 2, col_end 0, meta '#', skip 0; pseudo-bin 37450 with the
  * contig's line count) for the body lines of `lines`, a table of the text as written.  The CHROM of line j is read at

@@ -37,6 +37,9 @@ from typing import Optional
 import numpy as np
 
 from . import native_reads as nr
+from .cohort import blocks, chrom_lines, header_text, read_header
+from .cohort import bytes_lines as _bytes_lines
+from .cohort import open_source as _open
 from .paste import BLOCK_BYTES, _text, declared_lines, header_attributes, info_table
 
 FORMAT_MESSAGE = '\nError: invalid FORMAT field, "%s"\n'
@@ -65,18 +68,6 @@ def _bad(name, line, kind, text="", sample=None):
     where = "the line" if sample is None else "sample %s" % sample
     return ClassifyError("%s, line %d: %s" % (name, line, what % dict(text=text, where=where)), name, line, reference,
                          FORMAT_MESSAGE % text if kind == nr.CLASSIFY_BAD_FORMAT else None)
-
-
-def _open(source):
-    if isinstance(source, (str, bytes)):
-        name = source if isinstance(source, str) else source.decode()
-        return name, (gzip.open(name, "rb") if name.endswith(".gz") else open(name, "rb")), True
-    return str(getattr(source, "name", source)), source, False
-
-
-def _bytes_lines(f):
-    for line in f:
-        yield line.encode("utf-8", "surrogateescape") if isinstance(line, str) else line
 
 
 def read_genders(source):
@@ -299,37 +290,21 @@ def classify(vcf_in, gender, exclude=None, annotation=None, f_overlap=0.9, slope
 
 def _run(name, lines, genders, excluded, elements, f_overlap, slope_threshold, rsquared_threshold, vcf_out, device, file_date, block_bytes, stats,
          keep_contigs):
-    header, first = [], None
-    for line in lines:
-        if line[:1] != b"#":
-            first = line
-            break
-        header.append(_text(line))
+    header, first = read_header(lines)
     if first is None:                               # (the header is written when the first body line is met)
         return
     file_format, reference, _filters, infos, alts, formats = header_attributes([h.rstrip("\n") for h in header if h.startswith("##")], ClassifyError)
     samples = []
-    for h in header:
-        if h[1:2] != "#":
-            samples = h.rstrip().split("\t")[9:]
-    vcf_out.write("\n".join(["##fileformat=" + file_format, "##fileDate=" + file_date, "##reference=" + reference] + declared_lines(infos, alts, formats)
-                            + ([h.rstrip("\n") for h in header if h.startswith("##contig")] if keep_contigs else [])
-                            + ["\t".join(["#CHROM", "POS", "ID", "REF", "ALT", "QUAL", "FILTER", "INFO", "FORMAT"] + samples)]) + "\n")
+    for h in chrom_lines(header):
+        samples = h.rstrip().split("\t")[9:]
+    vcf_out.write(header_text(file_format, file_date, reference, declared_lines(infos, alts, formats), header, samples, keep_contigs))
     male = np.array([1 if genders.get(s) == 1 else nr.CLASSIFY_NO_GENDER if s not in genders else 0 for s in samples], np.uint8)
     female = np.array([1 if genders.get(s) == 2 else nr.CLASSIFY_NO_GENDER if s not in genders else 0 for s in samples], np.uint8)
     skipped = np.array([s in excluded for s in samples], np.uint8)
     info_bytes = info_table(infos)
     format_bytes = "".join(i + "\n" for i, _, _, _ in formats).encode("utf-8", "surrogateescape")
     done = len(header)                              # lines of the file in front of the block
-    block, size = [first], len(first)
-    more = True
-    while block:
-        line = next(lines, None) if more else None
-        more = line is not None
-        if more and (size + len(line) <= block_bytes):
-            block.append(line)
-            size += len(line)
-            continue
+    for block in blocks(first, lines, block_bytes):
         bare = not block[-1].endswith(b"\n")        # (the file's last line: rewritten lines end in a newline all the same)
         text = b"".join(block) + (b"\n" if bare else b"")
         skip, mei, pending = None, {}, None
@@ -373,7 +348,6 @@ def _run(name, lines, genders, excluded, elements, f_overlap, slope_threshold, r
         if pending is not None:
             raise pending
         done += len(block)
-        block, size = ([line], len(line)) if more else ([], 0)
 
 
 # ------------------------------------------------------------------------------------------ CLI

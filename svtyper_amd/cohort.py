@@ -1,0 +1,66 @@
+"""What the cohort programs that rewrite a VCF line by line share (svtyper_amd.classify, svtyper_amd.update_info): how an input is
+opened, how its header is read and written again as the Vcf class of the reference's scripts does, and how its body is cut into
+blocks for the native library.  The header's attributes themselves are paste.py's (header_attributes, declared_lines)."""
+from __future__ import annotations
+
+import gzip
+from typing import Iterable, Iterator, List, Optional, Tuple
+
+GZIP_MAGIC = b"\x1f\x8b"
+
+
+def open_source(source, sniff=False):
+    """(name, binary or text file, whether it is ours to close) of a path or an open file.  A path ending in .gz is read through
+    gzip; `sniff`: so is whatever begins with the two bytes of a gzip member (an open file must be able to peek for that)"""
+    if isinstance(source, (str, bytes)):
+        name = source if isinstance(source, str) else source.decode()
+        zipped = name.endswith(".gz")
+        if sniff and not zipped:
+            with open(name, "rb") as f:
+                zipped = f.read(2) == GZIP_MAGIC
+        return name, (gzip.open(name, "rb") if zipped else open(name, "rb")), True
+    name = str(getattr(source, "name", source))
+    if sniff and hasattr(source, "peek") and source.peek(2)[:2] == GZIP_MAGIC:
+        return name, gzip.GzipFile(fileobj=source, mode="rb"), False
+    return name, source, False
+
+
+def bytes_lines(f) -> Iterator[bytes]:
+    for line in f:
+        yield line.encode("utf-8", "surrogateescape") if isinstance(line, str) else line
+
+
+def read_header(lines: Iterator[bytes]) -> Tuple[List[str], Optional[bytes]]:
+    """(the lines in front of the first that does not begin with '#', that line or None)"""
+    header = []
+    for line in lines:
+        if line[:1] != b"#":
+            return header, line
+        header.append(line.decode("utf-8", "surrogateescape"))
+    return header, None
+
+
+def chrom_lines(header: List[str]) -> List[str]:
+    """the header's lines that begin with one '#' alone: the last of them names the samples"""
+    return [h for h in header if h[1:2] != "#"]
+
+
+def header_text(file_format, file_date, reference, declared: List[str], header: List[str], samples: List[str], keep_contigs, with_format=True):
+    """the scripts' get_header: fileformat, fileDate, reference, the declared lines, the input's ##contig lines where they are
+    kept, and the #CHROM line (`with_format`: its FORMAT column and the samples)"""
+    columns = ["#CHROM", "POS", "ID", "REF", "ALT", "QUAL", "FILTER", "INFO"] + (["FORMAT"] + samples if with_format else [])
+    return "\n".join(["##fileformat=" + file_format, "##fileDate=" + file_date, "##reference=" + reference] + declared
+                     + ([h.rstrip("\n") for h in header if h.startswith("##contig")] if keep_contigs else []) + ["\t".join(columns)]) + "\n"
+
+
+def blocks(first: bytes, lines: Iterable[bytes], block_bytes: int) -> Iterator[List[bytes]]:
+    """the body from `first` on in lists of lines of at most `block_bytes` together, a line at the least"""
+    block, size = [first], len(first)
+    for line in lines:
+        if size + len(line) <= block_bytes:
+            block.append(line)
+            size += len(line)
+            continue
+        yield block
+        block, size = [line], len(line)
+    yield block

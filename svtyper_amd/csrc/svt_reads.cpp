@@ -44,6 +44,7 @@
 #include "svt_vcf_lines.h"
 #include "svt_vcf_paste.h"
 #include "svt_vcf_classify.h"
+#include "svt_vcf_update_info.h"
 
 namespace {
 using svt::fail;
@@ -70,3 +71,4 @@ using rr::ld32;
 #include "svt_reads_bcf_entries.h"     // svt_bcf_encode_host, svt_bcf_take: VCF text as a BCF stream
 #include "svt_reads_paste_entries.h"   // svt_vcf_paste_host: per-sample VCFs joined by line number, AF and NSAMP
 #include "svt_reads_classify_entries.h" // svt_vcf_classify_host, _write, _take: the read-depth classifier of DEL and DUP lines
+#include "svt_reads_update_info_entries.h" // svt_vcf_update_info_host, _write, _take: PE, SR, SU and MSQ from the samples' evidence

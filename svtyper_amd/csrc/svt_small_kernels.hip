@@ -19,6 +19,10 @@
 #include "svt_unit_math.h"
 #include "svt_stream_kernel.h"
 #include "svt_split_kernel.h"
+// not a stream kernel: one workgroup per line of a cohort VCF, a launch of a few thousand workgroups that each run one latency
+// chain; its launch is defined beside it for the entry point in svtyper_hip.hip
+#include "svt_vcf_lines.h"
+#include "svt_vcf_update_info_kernel.h"
 
 namespace svt {
 template __global__ void svt_stream_kernel<false, kSingleLds, 1>(const StreamArgs);

@@ -74,6 +74,7 @@
 #include "svt_vcf_lines_kernel.h"
 #include "svt_vcf_paste_kernel.h"
 #include "svt_vcf_classify_kernel.h"
+#include "svt_vcf_update_info.h"                // (its kernel is svt_small_kernels.hip's: svt_vcf_update_info_kernel.h)
 #include "svt_radix_sort_kernel.h"
 #include "svt_bam_sort_kernel.h"
 #include "svt_bam_first_kernel.h"
@@ -206,6 +207,7 @@ void svt_batch_destroy(svt_batch* b) { free_batch(b); }
 #include "svt_entry_vcf_lines.h"
 #include "svt_entry_vcf_paste.h"
 #include "svt_entry_vcf_classify.h"
+#include "svt_entry_vcf_update_info.h"
 #include "svt_entry_radix_sort.h"
 #include "svt_entry_bam_sort.h"
 #include "svt_entry_bam_first.h"

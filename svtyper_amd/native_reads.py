@@ -164,6 +164,17 @@ class _ClassifyTimes(C.Structure):
     _fields_ = [(name, C.c_double) for name in ("lines_kernels_s", "classify_kernel_s", "upload_s", "download_s", "host_s", "total_s")]
 
 
+class _UpdateInfoReport(C.Structure):
+    """include/svtyper_reads.h: svt_update_info_report"""
+    _fields_ = [("out_len", C.c_uint64), ("host_lines", C.c_uint64), ("bad_line", C.c_uint64), ("bad_kind", C.c_uint32),
+                ("bad_sample", C.c_uint32), ("bad_text", C.c_char * 48)]
+
+
+class _UpdateInfoTimes(C.Structure):
+    """include/svtyper_reads.h: svt_vcf_update_info_times"""
+    _fields_ = [(name, C.c_double) for name in ("lines_kernels_s", "update_info_kernel_s", "upload_s", "download_s", "host_s", "total_s")]
+
+
 class _BamSortTimes(C.Structure):
     """include/svtyper_reads.h: svt_bam_sort_times"""
     _fields_ = [("keys_kernel_s", C.c_double), ("histogram_kernel_s", C.c_double), ("scan_kernel_s", C.c_double),
@@ -337,6 +348,18 @@ def _lib():
             L.svt_vcf_classify_take.argtypes = [P, U64]
             L.svt_vcf_classify_last_times.restype = C.c_int
             L.svt_vcf_classify_last_times.argtypes = [C.POINTER(_ClassifyTimes)]
+        if hasattr(L, "svt_vcf_update_info_host"):  # (likewise: PE, SR, SU and MSQ from the samples' evidence)
+            P, U64, U32 = C.c_void_p, C.c_uint64, C.c_uint32
+            L.svt_vcf_update_info_host.restype = C.c_int
+            L.svt_vcf_update_info_host.argtypes = [P, U64, U32, P, U64, P, U64, P, C.POINTER(_UpdateInfoReport)]
+            L.svt_vcf_update_info_device.restype = C.c_int
+            L.svt_vcf_update_info_device.argtypes = L.svt_vcf_update_info_host.argtypes + [C.c_int]
+            L.svt_vcf_update_info_write.restype = C.c_int
+            L.svt_vcf_update_info_write.argtypes = [P, U64, U32, P, U64, P, U64, P, U64, P, C.POINTER(_UpdateInfoReport)]
+            L.svt_vcf_update_info_take.restype = C.c_int
+            L.svt_vcf_update_info_take.argtypes = [P, U64]
+            L.svt_vcf_update_info_last_times.restype = C.c_int
+            L.svt_vcf_update_info_last_times.argtypes = [C.POINTER(_UpdateInfoTimes)]
         if hasattr(L, "svt_bam_spans_host"):       # (likewise: BAM records as spans, the sorted and indexed `-w` dump)
             P, U64, I32 = C.c_void_p, C.c_uint64, C.c_int32
             for name, argtypes in (("svt_bam_spans_host", [P, U64, P, U64, I32, P, P, P]), ("svt_bam_spans_device", [P, U64, P, U64, I32, P, P, P, C.c_int]),
@@ -1090,6 +1113,72 @@ def vcf_classify_last_times() -> Dict[str, float]:
     t = _ClassifyTimes()
     hip._check(_classify_lib().svt_vcf_classify_last_times(C.byref(t)))
     return {name: float(getattr(t, name)) for name, _ in _ClassifyTimes._fields_}
+
+
+UPDATE_INFO_LINE = np.dtype([("pe", np.int64), ("sr", np.int64), ("sum_sq", np.uint64), ("num_pos", np.uint32), ("route", np.uint32),
+                             ("flags", np.uint32), ("reserved", np.uint32)])      # svt_update_info_line; sum_sq: the double's bits
+UPDATE_INFO_CAPACITY = 4096
+UPDATE_INFO_RULE, UPDATE_INFO_PLAIN = 0, 1
+(UPDATE_INFO_SLOW_HEAD, UPDATE_INFO_SLOW_FORMAT, UPDATE_INFO_SLOW_COLUMNS, UPDATE_INFO_SLOW_SAMPLE, UPDATE_INFO_SLOW_TOKEN,
+ UPDATE_INFO_SLOW_CAPACITY, UPDATE_INFO_SLOW_KEYS) = 1, 2, 4, 8, 16, 32, 64
+UPDATE_INFO_SLOW = 127
+(UPDATE_INFO_BAD_COLUMNS, UPDATE_INFO_BAD_POS, UPDATE_INFO_BAD_QUAL, UPDATE_INFO_BAD_FORMAT, UPDATE_INFO_BAD_KEY, UPDATE_INFO_BAD_NUMBER,
+ UPDATE_INFO_BAD_NONFINITE, UPDATE_INFO_BAD_OVERFLOW, UPDATE_INFO_BAD_EIGHT) = 1, 2, 3, 4, 5, 6, 7, 8, 9
+
+
+def _update_info_lib():
+    L = _lib()
+    if not hasattr(L, "svt_vcf_update_info_host"):
+        raise hip.SvtyperHipError("this libsvtyper_hip.so has no svt_vcf_update_info_host (built before svtyper_amd.update_info)")
+    return L
+
+
+def _update_info_report(info) -> dict:
+    report = {name: int(getattr(info, name)) for name, _ in _UpdateInfoReport._fields_ if name != "bad_text"}
+    report["bad_text"] = bytes(info.bad_text).decode("utf-8", "surrogateescape")
+    return report
+
+
+def vcf_update_info(text: bytes, n_samples: int, format_table: bytes, device: Optional[int] = None):
+    """svt_vcf_update_info_host (device None) / _device over one block of body lines: (records UPDATE_INFO_LINE, one per line, info).
+    info: host_lines and, where the script dies on a line, bad_line (1-based in the block), bad_kind, bad_sample, bad_text"""
+    L = _update_info_lib()
+    buf, fmt = _text_array(text), _text_array(format_table)
+    capacity = text.count(b"\n") + 1
+    results = np.zeros(capacity, UPDATE_INFO_LINE)
+    n_lines = C.c_uint64(0)
+    info = _UpdateInfoReport()
+    args = [buf.ctypes.data, len(text), int(n_samples), fmt.ctypes.data, len(format_table), results.ctypes.data, capacity, C.addressof(n_lines),
+            C.byref(info)]
+    if device is None:
+        hip._check(L.svt_vcf_update_info_host(*args))
+    else:
+        hip._check(L.svt_vcf_update_info_device(*args, int(device)))
+    return results[:n_lines.value], _update_info_report(info)
+
+
+def vcf_update_info_write(text: bytes, n_samples: int, info_table: bytes, format_table: bytes, results: np.ndarray):
+    """svt_vcf_update_info_write + _take: (the block's output text, out_off [lines + 1], info); where a line cannot be written info has
+    bad_line, bad_kind, bad_text and the text ends in front of that line"""
+    L = _update_info_lib()
+    buf, inf, fmt = _text_array(text), _text_array(info_table), _text_array(format_table)
+    results = np.ascontiguousarray(results, UPDATE_INFO_LINE)
+    out_off = np.zeros(results.shape[0] + 1, np.uint64)
+    info = _UpdateInfoReport()
+    hip._check(L.svt_vcf_update_info_write(buf.ctypes.data, len(text), int(n_samples), inf.ctypes.data, len(info_table), fmt.ctypes.data,
+                                           len(format_table), results.ctypes.data if results.shape[0] else None, results.shape[0],
+                                           out_off.ctypes.data, C.byref(info)))
+    out = np.empty(max(info.out_len, 1), np.uint8)
+    hip._check(L.svt_vcf_update_info_take(out.ctypes.data, info.out_len))
+    return out[:info.out_len].tobytes(), out_off, _update_info_report(info)
+
+
+def vcf_update_info_last_times() -> Dict[str, float]:
+    """svt_vcf_update_info_last_times: the kernels of this thread's last svt_vcf_update_info_device from HIP events, its copies on the
+    host's clock"""
+    t = _UpdateInfoTimes()
+    hip._check(_update_info_lib().svt_vcf_update_info_last_times(C.byref(t)))
+    return {name: float(getattr(t, name)) for name, _ in _UpdateInfoTimes._fields_}
 
 
 def tbx_build(text: bytes, lines: np.ndarray, member_off, src_off=None, payload: int = DEFLATE_MAX_PAYLOAD, csi: bool = False):
