@@ -75,6 +75,58 @@ typedef struct svt_bcf_times {
 } svt_bcf_times;
 int svt_bcf_last_times(svt_bcf_times* times);
 
+/* ---- BCF2.2 records back to VCF text.  Additions; the ABI number stays: probe for svt_bcf_text_host.
+ * svtyper_amd/csrc/svt_bcf_text.h holds the record rule as one piece of source for the host and the device
+ * (svt_bcf_text_kernel.h: one wavefront per record, lanes over samples).
+ *
+ * `stream[0, len)` is a whole inflated BCF stream in host memory: the magic, l_text, the header text, the records.  The
+ * dictionaries follow IDX= where a header line carries it and the implicit order of the writer above where none does.  The
+ * text is the header without its ,IDX=n attributes and its NUL, then one line per record in the format of DESIGN 3.4: what
+ * `bcftools view` is understood to print -- byte equality with htslib is not claimed, nothing here has htslib.
+ *
+ * Nothing is repaired.  A record the rule refuses stops the call: it returns SVT_OK with info->bad_record (1-based) and
+ * bad_kind set, and nothing is held.  The lowest such record number is reported.  A stream that is no BCF (no magic, a header
+ * without #CHROM line, two names at one IDX) is SVT_ERR_INVALID.                                                        */
+#define SVT_BCF_TEXT_KIND_TRUNCATED 1u  /* the record runs out of the stream, or l_shared < 24                            */
+#define SVT_BCF_TEXT_KIND_INDEX 2u      /* a contig, FILTER, INFO or FORMAT index the dictionaries do not hold            */
+#define SVT_BCF_TEXT_KIND_SAMPLES 3u    /* n_sample is not the header's sample count                                      */
+#define SVT_BCF_TEXT_KIND_TYPE 4u       /* a type code that is none of 0, 1, 2, 3, 5, 7, or one its field cannot have: ID and
+                                           the alleles are characters, FILTER and every key integers, a key one integer   */
+#define SVT_BCF_TEXT_KIND_COUNT 5u      /* a long count whose descriptor is not a single integer, or a vector beyond its part */
+#define SVT_BCF_TEXT_KIND_GT 6u         /* a GT that is not held in an integer type                                       */
+#define SVT_BCF_TEXT_KIND_LENGTH 7u     /* a shared or individual part whose walk does not end exactly at its length      */
+
+#define SVT_BCF_TEXT_EXACT_FLOATS 2u    /* flags (svt_bcf_text_host): floats by the device's exact rule first, snprintf for
+                                           the rest -- info->host_lines and the marks then count as the device route's do */
+
+typedef struct svt_bcf_text_info {
+    uint64_t text_len;          /* what svt_bcf_text_take hands over as `text`: header_len of header, then the lines      */
+    uint64_t n_offsets;         /* entries of `offsets` (records + 1): where each record's line begins in the text        */
+    uint64_t n_records;
+    uint64_t header_len;
+    uint64_t bad_record;
+    uint64_t host_lines;        /* records with a float outside the device's envelope: written by the host twin           */
+    uint64_t chunks;            /* pieces of at most block_bytes of stream, cut at record boundaries, the records ran in  */
+    uint32_t bad_kind, n_sample;
+} svt_bcf_text_info;
+
+/* The text of `stream`, left for svt_bcf_text_take: text, offsets[0 .. n_records] and one mark per record (1: a float outside
+ * the envelope -- on the host route only under SVT_BCF_TEXT_EXACT_FLOATS).  block_bytes: 0 for everything in one chunk.  The
+ * device route uploads each chunk with its record offsets, measures (one text length and one mark per record), lets the host
+ * take the exclusive sum, writes, downloads, and has the host twin write the marked records into their places: the host
+ * route's text, byte for byte.                                                                                        */
+int svt_bcf_text_host(const uint8_t* stream, uint64_t len, uint32_t flags, uint64_t block_bytes, svt_bcf_text_info* info);
+int svt_bcf_text_device(const uint8_t* stream, uint64_t len, uint32_t flags, uint64_t block_bytes, svt_bcf_text_info* info, int device);
+/* hands over what the calling thread's last decoding call left, once: capacities in entries                           */
+int svt_bcf_text_take(uint8_t* text, uint64_t text_capacity, uint64_t* offsets, uint64_t offsets_capacity, uint8_t* marks,
+                      uint64_t marks_capacity);
+/* the calling thread's most recent device call here: kernels and copies by HIP events, summed over its chunks         */
+typedef struct svt_bcf_text_times {
+    double measure_kernel_s, write_kernel_s, upload_s, download_s;
+    double total_s;             /* the whole call on the host's clock                                                    */
+} svt_bcf_text_times;
+int svt_bcf_text_last_times(svt_bcf_text_times* times);
+
 #ifdef __cplusplus
 }
 #endif

@@ -279,7 +279,7 @@ def classify(vcf_in, gender, exclude=None, annotation=None, f_overlap=0.9, slope
     stats.update(lines=0, blocks=0, host_lines=0, near_lines=0, results=[], times={})
     genders, excluded = read_genders(gender), set(read_excluded(exclude))
     elements = read_annotation(annotation) if annotation is not None else None
-    name, f, own = _open(vcf_in)
+    name, f, own = _open(vcf_in, engine=engine, device=device)
     try:
         _run(name, _bytes_lines(f), genders, excluded, elements, f_overlap, slope_threshold, rsquared_threshold, vcf_out,
              device if engine == "device" else None, file_date or time.strftime("%Y%m%d"), block_bytes, stats, keep_contigs)

@@ -9,20 +9,38 @@ from typing import Iterable, Iterator, List, Optional, Tuple
 GZIP_MAGIC = b"\x1f\x8b"
 
 
-def open_source(source, sniff=False):
+def open_source(source, sniff=False, engine="host", device=0):
     """(name, binary or text file, whether it is ours to close) of a path or an open file.  A path ending in .gz is read through
-    gzip; `sniff`: so is whatever begins with the two bytes of a gzip member (an open file must be able to peek for that)"""
+    gzip; `sniff`: so is whatever begins with the two bytes of a gzip member (an open file must be able to peek for that).  A BCF
+    is read as its VCF text (bcf_in.open_text, decoded by `engine` on `device`): a path ending in .bcf, and with `sniff` whatever
+    is BGZF whose payload begins with the BCF magic"""
     if isinstance(source, (str, bytes)):
         name = source if isinstance(source, str) else source.decode()
         zipped = name.endswith(".gz")
-        if sniff and not zipped:
+        bcf = name.endswith(".bcf")
+        if sniff and not bcf:
             with open(name, "rb") as f:
-                zipped = f.read(2) == GZIP_MAGIC
+                zipped = zipped or f.read(2) == GZIP_MAGIC
+            bcf = zipped and _is_bcf(name)
+        if bcf:
+            return name, _bcf_text(name, engine, device), True
         return name, (gzip.open(name, "rb") if zipped else open(name, "rb")), True
     name = str(getattr(source, "name", source))
     if sniff and hasattr(source, "peek") and source.peek(2)[:2] == GZIP_MAGIC:
+        if _is_bcf(source):
+            return name, _bcf_text(source, engine, device), True
         return name, gzip.GzipFile(fileobj=source, mode="rb"), False
     return name, source, False
+
+
+def _is_bcf(source):
+    from . import bcf_in
+    return bcf_in.is_bcf(source)
+
+
+def _bcf_text(source, engine, device):
+    from . import bcf_in
+    return bcf_in.open_text(source, engine=engine, device=device)
 
 
 def bytes_lines(f) -> Iterator[bytes]:

@@ -32,6 +32,7 @@
 #include "svt_bam_first_rules.h"
 #include "svt_bam_sort_rules.h"
 #include "svt_bcf.h"
+#include "svt_bcf_text.h"
 #include "svt_bgzf.h"
 #include "svt_dump_rules.h"
 #include "svt_error.h"
@@ -68,7 +69,7 @@ using rr::ld32;
 #include "svt_reads_library.h"         // svt_bam_scan_library, svt::lw: the segmented library walk
 #include "svt_reads_vcf_entries.h"     // svt_vcf_lines_host, _gather_host, _sort_order, svt_tbx_build: VCF text as lines, the .tbi fold
 #include "svt_reads_bam_sort_entries.h" // svt_bam_spans_host, _sort_order_host, svt_bai_build: BAM records as spans, the .bai fold
-#include "svt_reads_bcf_entries.h"     // svt_bcf_encode_host, svt_bcf_take: VCF text as a BCF stream
+#include "svt_reads_bcf_entries.h"     // svt_bcf_encode_host, svt_bcf_take, svt_bcf_text_host, svt_bcf_text_take: VCF text as a BCF stream and back
 #include "svt_reads_paste_entries.h"   // svt_vcf_paste_host: per-sample VCFs joined by line number, AF and NSAMP
 #include "svt_reads_classify_entries.h" // svt_vcf_classify_host, _write, _take: the read-depth classifier of DEL and DUP lines
 #include "svt_reads_update_info_entries.h" // svt_vcf_update_info_host, _write, _take: PE, SR, SU and MSQ from the samples' evidence

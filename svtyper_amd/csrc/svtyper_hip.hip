@@ -80,6 +80,7 @@
 #include "svt_bam_first_kernel.h"
 #include "svt_bam_index_kernel.h"
 #include "svt_bcf_kernel.h"
+#include "svt_bcf_text_kernel.h"
 #include "svt_bai_index.h"
 #include "svt_bgzf.h"
 #include "svt_evidence_arena.h"
@@ -213,6 +214,7 @@ void svt_batch_destroy(svt_batch* b) { free_batch(b); }
 #include "svt_entry_bam_first.h"
 #include "svt_entry_bam_index.h"
 #include "svt_entry_bcf.h"
+#include "svt_entry_bcf_text.h"
 #include "svt_entry_evidence.h"
 #include "svt_entry_library.h"
 #include "svt_entry_oneshot.h"

@@ -424,13 +424,19 @@ def check_output_arguments(p, args, output):
 
 def gzip_text(vcf_in):
     """`-i PATH` whose first two bytes are 1f 8b (a .vcf.gz, BGZF or plain gzip): the file read through gzip as text.  Anything
-    else, stdin included, as it is."""
+    else, stdin included, as it is.  A BCF (BGZF whose payload begins with the BCF magic) is read as its VCF text, decoded by the
+    host engine of bcf_in: a sites file is small."""
     path = getattr(vcf_in, "name", None)
     if vcf_in is None or vcf_in is sys.stdin or not isinstance(path, str) or not os.path.isfile(path):
         return vcf_in
     with open(path, "rb") as f:
         if f.read(2) != b"\x1f\x8b":
             return vcf_in
+    from . import bcf_in
+    if bcf_in.is_bcf(path):
+        import io
+        vcf_in.close()
+        return io.TextIOWrapper(bcf_in.open_text(path, engine="host"))
     import gzip
     vcf_in.close()
     return gzip.open(path, "rt")

@@ -1517,3 +1517,68 @@ def bcf_last_times() -> Dict[str, float]:
     t = _BcfTimes()
     hip._check(_bcf_lib().svt_bcf_last_times(C.byref(t)))
     return {name: float(getattr(t, name)) for name, _ in _BcfTimes._fields_}
+
+
+# ---- an inflated BCF2.2 stream back to VCF text: the lines on the host and on the device (include/svtyper_bcf.h) ----------
+BCF_TEXT_KINDS = {1: "truncated", 2: "index", 3: "samples", 4: "type", 5: "count", 6: "gt", 7: "length"}     # SVT_BCF_TEXT_KIND_*
+BCF_TEXT_EXACT_FLOATS = 2
+
+
+class _BcfTextInfo(C.Structure):
+    _fields_ = [(name, C.c_uint64) for name in ("text_len", "n_offsets", "n_records", "header_len", "bad_record", "host_lines", "chunks")] + [
+        ("bad_kind", C.c_uint32), ("n_sample", C.c_uint32)]
+
+
+class _BcfTextTimes(C.Structure):
+    _fields_ = [(name, C.c_double) for name in ("measure_kernel_s", "write_kernel_s", "upload_s", "download_s", "total_s")]
+
+
+_bcf_text_declared = False
+
+
+def _bcf_text_lib():
+    global _bcf_text_declared
+    L = _lib()
+    if not hasattr(L, "svt_bcf_text_host"):
+        raise hip.SvtyperHipError("this libsvtyper_hip.so has no svt_bcf_text_host (built before BCF input)")
+    if not _bcf_text_declared:
+        P, U64, U32, INFO = C.c_void_p, C.c_uint64, C.c_uint32, C.POINTER(_BcfTextInfo)
+        for name, argtypes in (("svt_bcf_text_host", [P, U64, U32, U64, INFO]), ("svt_bcf_text_device", [P, U64, U32, U64, INFO, C.c_int]),
+                               ("svt_bcf_text_take", [P, U64, P, U64, P, U64]), ("svt_bcf_text_last_times", [C.POINTER(_BcfTextTimes)])):
+            getattr(L, name).restype = C.c_int
+            getattr(L, name).argtypes = argtypes
+        _bcf_text_declared = True
+    return L
+
+
+def bcf_text(stream: bytes, device: Optional[int] = None, block_bytes: Optional[int] = None, exact_floats: bool = False) -> dict:
+    """svt_bcf_text_host (device None) / _device, + svt_bcf_text_take: the VCF text of the inflated BCF2.2 `stream` -- a dict of
+    svt_bcf_text_info's fields and, where bad_record is 0, `text` (uint8: header_len bytes of header, then one line per record),
+    `offsets` (records + 1: where each line begins) and `marks` (uint8 per record: 1 where the host twin wrote it for a float outside
+    the device's envelope).  `block_bytes`: the records run in chunks of at most that much stream (None: one chunk).  `exact_floats`
+    (the host alone): floats by the device's rule first, so that host_lines and marks are what the device route reports"""
+    L = _bcf_text_lib()
+    buf = _text_array(stream)
+    info = _BcfTextInfo()
+    block = 0 if block_bytes is None else max(int(block_bytes), 1)
+    if device is None:
+        hip._check(L.svt_bcf_text_host(buf.ctypes.data, len(stream), BCF_TEXT_EXACT_FLOATS if exact_floats else 0, block, C.byref(info)))
+    else:
+        hip._check(L.svt_bcf_text_device(buf.ctypes.data, len(stream), 0, block, C.byref(info), int(device)))
+    got = {name: int(getattr(info, name)) for name, _ in _BcfTextInfo._fields_}
+    if info.bad_record:
+        return got
+    text = np.zeros(max(info.text_len, 1), np.uint8)
+    offsets = np.zeros(max(info.n_offsets, 1), np.uint64)
+    marks = np.zeros(max(info.n_records, 1), np.uint8)
+    hip._check(L.svt_bcf_text_take(text.ctypes.data, info.text_len, offsets.ctypes.data, info.n_offsets, marks.ctypes.data, info.n_records))
+    got.update(text=text[:info.text_len], offsets=offsets[:info.n_offsets], marks=marks[:info.n_records])
+    return got
+
+
+def bcf_text_last_times() -> Dict[str, float]:
+    """svt_bcf_text_last_times: the kernels and copies of this thread's last bcf_text on a device, from HIP events, summed over its
+    chunks, and the call's wall time"""
+    t = _BcfTextTimes()
+    hip._check(_bcf_text_lib().svt_bcf_text_last_times(C.byref(t)))
+    return {name: float(getattr(t, name)) for name, _ in _BcfTextTimes._fields_}

@@ -36,6 +36,7 @@ from typing import List, Optional
 import numpy as np
 
 from . import native_reads as nr
+from .cohort import open_source
 
 # a block's lines are a launch's wavefronts, so the device wants many; the host twin is fastest with blocks its caches hold
 BLOCK_BYTES = {"host": 8 << 20, "device": 64 << 20}
@@ -59,10 +60,13 @@ class PasteError(Exception):
 class _Lines:
     """the lines of one file, read ahead and handed back where a block has no room for them"""
 
-    def __init__(self, source):
+    def __init__(self, source, engine="host", device=0):
         if isinstance(source, (str, bytes)):
             self.name = source if isinstance(source, str) else source.decode()
-            self.f = gzip.open(self.name, "rb") if self.name.endswith(".gz") else open(self.name, "rb")
+            if self.name.endswith(".bcf"):          # (by its suffix, as .gz is: cohort.open_source decodes it)
+                self.f = open_source(self.name, engine=engine, device=device)[1]
+            else:
+                self.f = gzip.open(self.name, "rb") if self.name.endswith(".gz") else open(self.name, "rb")
         else:
             self.name = str(getattr(source, "name", source))
             self.f = source
@@ -193,8 +197,8 @@ def paste(vcf_list, master=None, sum_quals=False, afreq=False, safe=False, keep_
     vcf_list = list(vcf_list)
     if not vcf_list:
         raise PasteError("no input: the list of VCF files is empty")
-    inputs = [_Lines(v) for v in vcf_list]
-    files = [_Lines(master if master is not None else inputs[0].name)] + inputs
+    inputs = [_Lines(v, engine, device) for v in vcf_list]
+    files = [_Lines(master if master is not None else inputs[0].name, engine, device)] + inputs
     if stats is None:
         stats = {}
     stats.update(lines=0, blocks=0, host_lines=0, results=[], times={})

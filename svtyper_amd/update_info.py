@@ -13,7 +13,8 @@ PE the sum of the samples' AP, SR the sum of their AS, SU the sum of both and MS
 Not in the reference: `-o`, `keep_contigs` (the input's ##contig lines stay, directly before the #CHROM line, so that the result
 can be sorted by declared rank and written as BCF; as in svtyper_amd.paste), `engine` ("host": the native host twin; "device":
 the HIP kernel of svtyper_amd/csrc/svt_vcf_update_info_kernel.h; the same records, byte for byte, and the same text), gzip input
-(a path ending in .gz, or whatever begins 1f 8b), and the output options of the other programs (--bgzf / --bcf, --sort, --tabix /
+(a path ending in .gz, or whatever begins 1f 8b), BCF input (a path ending in .bcf, or BGZF with the BCF magic: bcf_in.open_text,
+decoded by `engine`), and the output options of the other programs (--bgzf / --bcf, --sort, --tabix /
 --csi, --deflate, --huffman).
 
 Where the script dies with a traceback, UpdateInfoError names the file, the 1-based line, the sample and the key or token in the
@@ -84,7 +85,7 @@ def update_info(vcf_in, vcf_out=sys.stdout, engine="host", device=0, file_date=N
     if stats is None:
         stats = {}
     stats.update(lines=0, blocks=0, host_lines=0, results=[], times={})
-    name, f, own = open_source(vcf_in, sniff=True)
+    name, f, own = open_source(vcf_in, sniff=True, engine=engine, device=device)
     try:
         _run(name, bytes_lines(f), vcf_out, device if engine == "device" else None, file_date or time.strftime("%Y%m%d"), block_bytes, stats,
              keep_contigs)
