@@ -37,7 +37,7 @@ from typing import Optional
 import numpy as np
 
 from . import native_reads as nr
-from .cohort import blocks, chrom_lines, header_text, read_header
+from .cohort import blocks, chrom_lines, finish_block, header_text, read_header
 from .cohort import bytes_lines as _bytes_lines
 from .cohort import open_source as _open
 from .paste import BLOCK_BYTES, _text, declared_lines, header_attributes, info_table
@@ -316,35 +316,20 @@ def _run(name, lines, genders, excluded, elements, f_overlap, slope_threshold, r
                     raise pending
                 bare = False
                 text = b"".join(block)
-        results, info = nr.vcf_classify(text, male, female, skipped, format_bytes, slope_threshold, rsquared_threshold, skip, device)
-        whole = info["bad_line"] - 1 if info["bad_line"] else len(block)       # the lines in front of the one the script dies on
-        if whole < len(block):
-            text = b"".join(block[:whole])
-        out, out_off, written = nr.vcf_classify_write(text, len(samples), info_bytes, format_bytes, results[:whole])
-        if written["bad_line"]:
-            whole = written["bad_line"] - 1
-        elif bare and whole == len(block) and results[-1]["route"] == nr.CLASSIFY_VERBATIM:
-            out = out[:-1]
-        if mei:
-            pieces, at = [], 0
+        records = nr.vcf_classify(text, male, female, skipped, format_bytes, slope_threshold, rsquared_threshold, skip, device)
+
+        def edit(out, out_off, written, whole):     # (called once, by finish_block below)
+            if not written["bad_line"] and bare and whole == len(block) and records[0][-1]["route"] == nr.CLASSIFY_VERBATIM:
+                out = out[:-1]
+            pieces, at = [], 0                      # `-a`: an MEI's text stands in front of its line's (empty) output
             for j in sorted(k for k in mei if k < whole):
                 pieces += [out[at:int(out_off[j])], mei[j].encode("utf-8", "surrogateescape")]
                 at = int(out_off[j])
-            out = b"".join(pieces) + out[at:]
-        vcf_out.write(_text(out))
-        stats["lines"] += whole
-        stats["blocks"] += 1
-        stats["host_lines"] += info["host_lines"]
-        stats["near_lines"] += info["near_lines"]
-        stats["results"].append(results)
-        if device is not None:
-            for key, value in nr.vcf_classify_last_times().items():
-                stats["times"][key] = stats["times"].get(key, 0.0) + value
-        if written["bad_line"]:
-            raise _bad(name, done + whole + 1, written["bad_kind"], written["bad_text"])
-        if info["bad_line"]:
-            sample = samples[info["bad_sample"]] if info["bad_sample"] < len(samples) else None
-            raise _bad(name, done + whole + 1, info["bad_kind"], info["bad_text"], sample)
+            return b"".join(pieces) + out[at:]
+
+        finish_block(name, done, block, text, samples, records,
+                     lambda kept, results: nr.vcf_classify_write(kept, len(samples), info_bytes, format_bytes, results),
+                     nr.vcf_classify_last_times if device is not None else None, _bad, vcf_out, stats, edit)
         if pending is not None:
             raise pending
         done += len(block)

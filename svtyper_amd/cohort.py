@@ -1,6 +1,7 @@
 """What the cohort programs that rewrite a VCF line by line share (svtyper_amd.classify, svtyper_amd.update_info): how an input is
 opened, how its header is read and written again as the Vcf class of the reference's scripts does, and how its body is cut into
-blocks for the native library.  The header's attributes themselves are paste.py's (header_attributes, declared_lines)."""
+blocks for the native library, and what becomes of a block's records (finish_block).  The header's attributes themselves are
+paste.py's (header_attributes, declared_lines)."""
 from __future__ import annotations
 
 import gzip
@@ -82,3 +83,33 @@ def blocks(first: bytes, lines: Iterable[bytes], block_bytes: int) -> Iterator[L
         yield block
         block, size = [line], len(line)
     yield block
+
+
+def finish_block(name, done, block, text, samples, records, write, last_times, bad, vcf_out, stats, edit=None):
+    """What follows a block's records in both programs: the lines in front of the one the script dies on are counted, joined again
+    and written (write(text, results) -> out, out_off, report; edit(out, out_off, report, whole) -> out may change the text), the
+    stats and the device's times are folded in, and the writer's report, then the records', is raised through bad(name, line, kind,
+    text, sample).  `records`: (results, report) of the native call over `text`; `done`: the file's lines in front of the block"""
+    results, info = records
+    whole = info["bad_line"] - 1 if info["bad_line"] else len(block)
+    if whole < len(block):
+        text = b"".join(block[:whole])
+    out, out_off, written = write(text, results[:whole])
+    if written["bad_line"]:
+        whole = written["bad_line"] - 1
+    if edit is not None:
+        out = edit(out, out_off, written, whole)
+    vcf_out.write(out.decode("utf-8", "surrogateescape"))
+    stats["lines"] += whole
+    stats["blocks"] += 1
+    for key in ("host_lines", "near_lines"):
+        if key in info:
+            stats[key] += info[key]
+    stats["results"].append(results)
+    if last_times is not None:
+        for key, value in last_times().items():
+            stats["times"][key] = stats["times"].get(key, 0.0) + value
+    for report in (written, info):
+        if report["bad_line"]:
+            sample = samples[report["bad_sample"]] if report["bad_sample"] < len(samples) else None
+            raise bad(name, done + whole + 1, report["bad_kind"], report["bad_text"], sample)

@@ -71,5 +71,6 @@ using rr::ld32;
 #include "svt_reads_bam_sort_entries.h" // svt_bam_spans_host, _sort_order_host, svt_bai_build: BAM records as spans, the .bai fold
 #include "svt_reads_bcf_entries.h"     // svt_bcf_encode_host, svt_bcf_take, svt_bcf_text_host, svt_bcf_text_take: VCF text as a BCF stream and back
 #include "svt_reads_paste_entries.h"   // svt_vcf_paste_host: per-sample VCFs joined by line number, AF and NSAMP
+#include "svt_reads_cohort_entries.h"  // cohort_write, cohort_take: the writer's entry points of a rule over cohort lines
 #include "svt_reads_classify_entries.h" // svt_vcf_classify_host, _write, _take: the read-depth classifier of DEL and DUP lines
 #include "svt_reads_update_info_entries.h" // svt_vcf_update_info_host, _write, _take: PE, SR, SU and MSQ from the samples' evidence

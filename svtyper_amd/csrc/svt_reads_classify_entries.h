@@ -1,10 +1,6 @@
 // svt_reads_classify_entries.h -- part of the translation unit svt_reads.cpp (included there, in order; not a stand-alone header):
 // the host entry points of the read-depth classifier (svt_vcf_classify.h): the records on the host, and the writer of the output
-// text that both engines' records go through; the device's entry is in svt_entry_vcf_classify.h.
-namespace {
-thread_local std::string g_classify_text;          // svt_vcf_classify_write's, until svt_vcf_classify_take
-}
-
+// text that both engines' records go through (svt_reads_cohort_entries.h); the device's entry is in svt_entry_vcf_classify.h.
 extern "C" {
 
 int svt_vcf_classify_host(const uint8_t* text, uint64_t len, uint32_t n_samples, const uint8_t* male, const uint8_t* female,
@@ -26,31 +22,9 @@ int svt_vcf_classify_write(const uint8_t* text, uint64_t len, uint32_t n_samples
                            const uint8_t* format_table, uint64_t format_len, const svt_classify_line* results, uint64_t n_lines, uint64_t* out_off,
                            svt_classify_info* info)
 {
-    return guarded([&]() -> int {
-        if (!info || !out_off || !format_table || (len && !text) || (n_lines && !results) || (info_len && !info_table))
-            return fail(SVT_ERR_INVALID, "null argument");
-        *info = svt_classify_info();
-        svt::classify::Block b;
-        if (len > svt::paste::kMaxLine) return fail(SVT_ERR_INVALID, "svt_vcf_classify: a block holds less than 2^31 bytes");
-        if (!svt::classify::parse_format_table(format_table, format_len, b.formats) || !svt::paste::parse_info_table(info_table, info_len, b.info))
-            return fail(SVT_ERR_INVALID, "svt_vcf_classify_write: format_table is \"<id>\\n\" per id, info_table \"V<id>\\n\" or \"F<id>\\n\"");
-        b.text = text;
-        b.len = len;
-        b.pr.n_samples = n_samples;
-        std::vector<svt_tbx_line> table;
-        if (const char* why = svt::classify::write_block(b, table, results, n_lines, out_off, g_classify_text, *info)) return fail(SVT_ERR_INVALID, why);
-        return SVT_OK;
-    });
+    return cohort_write<svt::classify::Block>(text, len, n_samples, info_table, info_len, format_table, format_len, results, n_lines, out_off, info);
 }
 
-int svt_vcf_classify_take(uint8_t* out, uint64_t capacity)
-{
-    return guarded([&]() -> int {
-        if (capacity < g_classify_text.size() || (!out && !g_classify_text.empty())) return fail(SVT_ERR_INVALID, "svt_vcf_classify_take: capacity is below the text");
-        if (!g_classify_text.empty()) std::memcpy(out, g_classify_text.data(), g_classify_text.size());
-        std::string().swap(g_classify_text);
-        return SVT_OK;
-    });
-}
+int svt_vcf_classify_take(uint8_t* out, uint64_t capacity) { return cohort_take<svt::classify::Block, svt_classify_line>(out, capacity); }
 
 }  // extern "C"

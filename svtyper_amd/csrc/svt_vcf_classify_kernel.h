@@ -3,10 +3,8 @@
 // samples meet in an order statistic, so it is ONE WORKGROUP OF 256 LANES PER LINE (a line that is no DEL or DUP costs its
 // first columns and nothing else).
 //
-//   head      every lane runs classify::scan_head on the first nine columns (the same addresses: one fetch per wavefront)
-//   starts    the bytes behind the ninth tab in 256 runs, a lane each: tabs counted, an exclusive scan over the workgroup
-//             (shuffles inside a wavefront, the four totals through LDS), then every lane writes where its run's columns begin
-//             into LDS.  Not one column per sample of the header: the line is marked
+//   head, starts   svt_vcf_cohort_line_kernel.h: the first nine columns once per line (classify::check_head in one lane), where the
+//             sample columns begin from 128-bit loads.  Not one column per sample of the header: the line is marked
 //   samples   sample s is lane s % 256's, in strides of 256: classify::parse_sample; the GT class in LDS; the marks or-ed and
 //             the counts added by shuffles
 //   low       the CN of the list the median is taken of as order-preserving keys in LDS (their places by an LDS counter: any
@@ -14,72 +12,27 @@
 //             sort again, the MAD; then the carriers against both (IEEE subtract, multiply by 2, compare), counted by shuffles
 //   high      two passes of centred sums in double: a lane adds its samples in sample order, an xor butterfly joins a
 //             wavefront's lanes, the four results meet as (w0 + w1) + (w2 + w3): the order classify::Tree restates
-// A pass that needs a sample's numbers again parses the column again (its start is in LDS): 52 KB of LDS per workgroup, three
+// A pass that needs a sample's numbers again parses the column again (its start is in LDS): 53 KB of LDS per workgroup, three
 // workgroups to a CU.  Every load is checked against its line's length, which is checked against the text's; every LDS index
 // against the capacity.  No scratch memory, no inline assembly.
 #ifndef SVT_VCF_CLASSIFY_KERNEL_H
 #define SVT_VCF_CLASSIFY_KERNEL_H
 
 #include "svt_vcf_classify.h"
+#include "svt_vcf_cohort_line_kernel.h"
 
 namespace svt {
 
-constexpr int kClassifyBlock = (int)classify::kBlock;
+constexpr int kClassifyBlock = kCohortBlock;
 
 struct ClassifyShared {
     uint64_t keys[classify::kCapacity];
-    uint32_t starts[classify::kCapacity];
+    CohortLineShared<classify::Head, classify::kCapacity> line;
     uint8_t gt[classify::kCapacity];
     double wave_d[4];
     uint32_t wave_u[4];
     uint32_t counter;
 };
-
-__device__ __forceinline__ uint32_t classify_block_sum(uint32_t v, uint32_t* wave_u)
-{
-    for (int d = 32; d; d >>= 1) v += __shfl_xor(v, d);
-    if ((threadIdx.x & 63) == 0) wave_u[threadIdx.x >> 6] = v;
-    __syncthreads();
-    const uint32_t total = wave_u[0] + wave_u[1] + wave_u[2] + wave_u[3];
-    __syncthreads();
-    return total;
-}
-
-__device__ __forceinline__ uint32_t classify_block_or(uint32_t v, uint32_t* wave_u)
-{
-    for (int d = 32; d; d >>= 1) v |= __shfl_xor(v, d);
-    if ((threadIdx.x & 63) == 0) wave_u[threadIdx.x >> 6] = v;
-    __syncthreads();
-    const uint32_t total = wave_u[0] | wave_u[1] | wave_u[2] | wave_u[3];
-    __syncthreads();
-    return total;
-}
-
-// the sum in the order of classify::Tree
-__device__ __forceinline__ double classify_block_sum(double v, double* wave_d)
-{
-    for (int d = 32; d; d >>= 1) v += __shfl_xor(v, d);
-    if ((threadIdx.x & 63) == 0) wave_d[threadIdx.x >> 6] = v;
-    __syncthreads();
-    const double total = (wave_d[0] + wave_d[1]) + (wave_d[2] + wave_d[3]);
-    __syncthreads();
-    return total;
-}
-
-// the maximum (of -v: the minimum)
-__device__ __forceinline__ double classify_block_max(double v, double* wave_d)
-{
-    for (int d = 32; d; d >>= 1) {
-        const double o = __shfl_xor(v, d);
-        v = o > v ? o : v;
-    }
-    if ((threadIdx.x & 63) == 0) wave_d[threadIdx.x >> 6] = v;
-    __syncthreads();
-    double total = wave_d[0];
-    for (int w = 1; w < 4; ++w) total = wave_d[w] > total ? wave_d[w] : total;
-    __syncthreads();
-    return total;
-}
 
 // keys[0, m), m a power of two, ascending
 __device__ __forceinline__ void classify_sort(uint64_t* keys, uint32_t m)
@@ -110,11 +63,11 @@ __global__ __launch_bounds__(kClassifyBlock) void svt_classify_kernel(const uint
     const uint32_t tid = threadIdx.x, n = pr.n_samples;
     for (uint64_t j = blockIdx.x; j < n_lines; j += gridDim.x) {
         __syncthreads();                            // (the line before is done with the LDS)
-        uint64_t off = lines[j].off, size = lines[j].len;
-        if (off > len || size > len - off) off = size = 0;
-        const uint8_t* p = text + off;
-        Head h;
-        scan_head(p, size, format_table, pr.format_len, h);
+        uint64_t size;
+        const uint8_t* p = cohort_line(text, len, lines, j, size);
+        const Head h = cohort_head(sh.line, p, size, [&](uint32_t n_line, bool too_long, const Tabs& t, Head& scanned) {
+            check_head(p, n_line, too_long, t, format_table, pr.format_len, scanned);
+        });
         if (!h.svtype) {
             if (tid == 0) results[j] = empty_record(SVT_CLASSIFY_VERBATIM, 0);
             continue;
@@ -126,37 +79,15 @@ __global__ __launch_bounds__(kClassifyBlock) void svt_classify_kernel(const uint
             if (tid == 0) results[j] = empty_record(SVT_CLASSIFY_LOW, slow | type);
             continue;
         }
-        // where the sample columns begin
-        const uint32_t span = h.n - h.samples_b, run = (span + kClassifyBlock - 1) / kClassifyBlock;
-        const uint32_t run_b = h.samples_b + (tid * run < span ? tid * run : span), run_e = h.samples_b + ((tid + 1) * run < span ? (tid + 1) * run : span);
-        uint32_t tabs = 0;
-        for (uint32_t i = run_b; i < run_e; ++i) tabs += p[i] == '\t';
-        uint32_t inc = tabs;
-        for (int d = 1; d < 64; d <<= 1) {
-            const uint32_t v = __shfl_up(inc, d);
-            if ((int)(tid & 63) >= d) inc += v;
-        }
-        if ((tid & 63) == 63) sh.wave_u[tid >> 6] = inc;
-        __syncthreads();
-        uint32_t before = inc - tabs;
-        for (uint32_t w = 0; w < (tid >> 6); ++w) before += sh.wave_u[w];
-        const uint32_t columns = span ? sh.wave_u[0] + sh.wave_u[1] + sh.wave_u[2] + sh.wave_u[3] + 1 : 0;
-        __syncthreads();
-        if (columns != n) {
+        if (cohort_starts(sh.line, text, len, p, h, n) != n) {
             if (tid == 0) results[j] = empty_record(SVT_CLASSIFY_LOW, SVT_CLASSIFY_SLOW_COLUMNS | type);
             continue;
         }
-        if (tid == 0) sh.starts[0] = h.samples_b;
-        for (uint32_t i = run_b, at = before + 1; i < run_e; ++i)
-            if (p[i] == '\t') {
-                if (at < kCapacity) sh.starts[at] = i + 1;
-                ++at;
-            }
-        __syncthreads();
+        const uint32_t* starts = sh.line.starts;
         // the samples: marks, GT classes, counts
         uint32_t n_pos = 0, male_alt = 0, female_alt = 0;
         for (uint32_t s = tid; s < n; s += kClassifyBlock) {
-            const uint32_t b = sh.starts[s], e = s + 1 < n ? sh.starts[s + 1] - 1 : h.n;
+            const uint32_t b = starts[s], e = starts[s + 1] - 1;
             Sample sm;
             if (b > e || e > h.n) {
                 slow |= SVT_CLASSIFY_SLOW_SAMPLE;
@@ -173,8 +104,8 @@ __global__ __launch_bounds__(kClassifyBlock) void svt_classify_kernel(const uint
             male_alt += alt && male[s] == 1;
             female_alt += alt && female[s] == 1;
         }
-        n_pos = classify_block_sum(n_pos, sh.wave_u);
-        slow = classify_block_or(slow, sh.wave_u);
+        n_pos = block_sum(n_pos, sh.wave_u);
+        slow = block_or(slow, sh.wave_u);
         svt_classify_line r = empty_record(n_pos < kMinPosForRegression ? SVT_CLASSIFY_LOW : SVT_CLASSIFY_HIGH, type);
         r.n_pos = n_pos;
         slow |= route_keys(r.route, h);
@@ -185,8 +116,8 @@ __global__ __launch_bounds__(kClassifyBlock) void svt_classify_kernel(const uint
         }
         const bool del = h.svtype == 1;
         if (r.route == SVT_CLASSIFY_LOW) {
-            male_alt = classify_block_sum(male_alt, sh.wave_u);
-            female_alt = classify_block_sum(female_alt, sh.wave_u);
+            male_alt = block_sum(male_alt, sh.wave_u);
+            female_alt = block_sum(female_alt, sh.wave_u);
             const uint32_t pick = !h.sex ? 0u : male_alt > female_alt ? 1u : 2u;
             if (tid == 0) sh.counter = 0;
             __syncthreads();
@@ -197,13 +128,13 @@ __global__ __launch_bounds__(kClassifyBlock) void svt_classify_kernel(const uint
                 n_alt += list == 2;
                 if (list != 1) continue;
                 Sample sm;
-                parse_sample(p, sh.starts[s], s + 1 < n ? sh.starts[s + 1] - 1 : h.n, h, sm);
+                parse_sample(p, starts[s], starts[s + 1] - 1, h, sm);
                 const uint32_t at = atomicAdd(&sh.counter, 1u);
                 if (at < kCapacity) sh.keys[at] = key_of(sm.cn);
             }
             __syncthreads();
             r.n_ref = sh.counter < kCapacity ? sh.counter : kCapacity;
-            r.n_alt = classify_block_sum(n_alt, sh.wave_u);
+            r.n_alt = block_sum(n_alt, sh.wave_u);
             if (r.n_ref) {
                 uint32_t m = 1;
                 while (m < r.n_ref) m <<= 1;
@@ -223,14 +154,14 @@ __global__ __launch_bounds__(kClassifyBlock) void svt_classify_kernel(const uint
                 for (uint32_t s = tid; s < n; s += kClassifyBlock) {
                     if (excluded[s] || low_list(sh.gt[s], pick, male[s] == 1, female[s] == 1) != 2) continue;
                     Sample sm;
-                    parse_sample(p, sh.starts[s], s + 1 < n ? sh.starts[s + 1] - 1 : h.n, h, sm);
+                    parse_sample(p, starts[s], starts[s + 1] - 1, h, sm);
                     q += supports(sm.cn, r.median, r.mad, del);
                 }
-                r.quorum = classify_block_sum(q, sh.wave_u);
+                r.quorum = block_sum(q, sh.wave_u);
             }
             finish_low(r);
         } else {
-            const bool has_cn = h.cn_i != kNone;
+            const bool has_cn = h.key_at[kCn] != kNone;
             double sx = 0.0, sy = 0.0, sxx = 0.0, syy = 0.0, sxy = 0.0;
             bool distinct = false;
             if (has_cn) {
@@ -238,7 +169,7 @@ __global__ __launch_bounds__(kClassifyBlock) void svt_classify_kernel(const uint
                 uint32_t count = 0;
                 for (uint32_t s = tid; s < n; s += kClassifyBlock) {
                     Sample sm;
-                    parse_sample(p, sh.starts[s], s + 1 < n ? sh.starts[s + 1] - 1 : h.n, h, sm);
+                    parse_sample(p, starts[s], starts[s + 1] - 1, h, sm);
                     if (!sm.has_ab) continue;
                     const double y = h.sex && male[s] == 1 ? sm.cn * 2.0 : sm.cn;
                     ++count;
@@ -249,19 +180,19 @@ __global__ __launch_bounds__(kClassifyBlock) void svt_classify_kernel(const uint
                     y_hi = y > y_hi ? y : y_hi;
                     y_lo = -y > y_lo ? -y : y_lo;
                 }
-                r.n_regressed = classify_block_sum(count, sh.wave_u);
-                sx = classify_block_sum(sx, sh.wave_d);
-                sy = classify_block_sum(sy, sh.wave_d);
-                x_hi = classify_block_max(x_hi, sh.wave_d);
-                x_lo = -classify_block_max(x_lo, sh.wave_d);
-                y_hi = classify_block_max(y_hi, sh.wave_d);
-                y_lo = -classify_block_max(y_lo, sh.wave_d);
+                r.n_regressed = block_sum(count, sh.wave_u);
+                sx = block_sum(sx, sh.wave_d);
+                sy = block_sum(sy, sh.wave_d);
+                x_hi = block_max(x_hi, sh.wave_d);
+                x_lo = -block_max(x_lo, sh.wave_d);
+                y_hi = block_max(y_hi, sh.wave_d);
+                y_lo = -block_max(y_lo, sh.wave_d);
                 distinct = r.n_regressed > 0 && x_lo < x_hi && y_lo < y_hi;
                 if (distinct) {
                     const double mx = sx / (double)r.n_regressed, my = sy / (double)r.n_regressed;
                     for (uint32_t s = tid; s < n; s += kClassifyBlock) {
                         Sample sm;
-                        parse_sample(p, sh.starts[s], s + 1 < n ? sh.starts[s + 1] - 1 : h.n, h, sm);
+                        parse_sample(p, starts[s], starts[s + 1] - 1, h, sm);
                         if (!sm.has_ab) continue;
                         const double y = h.sex && male[s] == 1 ? sm.cn * 2.0 : sm.cn;
                         const double dx = sm.ab - mx, dy = y - my;
@@ -270,9 +201,9 @@ __global__ __launch_bounds__(kClassifyBlock) void svt_classify_kernel(const uint
                         sxy += dx * dy;
                     }
                 }
-                sxx = classify_block_sum(sxx, sh.wave_d);
-                syy = classify_block_sum(syy, sh.wave_d);
-                sxy = classify_block_sum(sxy, sh.wave_d);
+                sxx = block_sum(sxx, sh.wave_d);
+                syy = block_sum(syy, sh.wave_d);
+                sxy = block_sum(sxy, sh.wave_d);
             }
             finish_high(r, has_cn, distinct, sxx, syy, sxy, del, pr);
         }

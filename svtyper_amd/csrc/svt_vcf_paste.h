@@ -6,6 +6,8 @@
 // scripts/vcf_paste.py and scripts/vcf_allele_freq.py, and sanitised) and for the device (svt_vcf_paste_kernel.h, one lane per
 // input).  Every load is checked against the line's length; no std::, no allocation, no array indexed by data.
 //
+// The character classes and Python's float(), int() and '%0.2f' are svt_vcf_cohort_line.h's, shared with the rules over cohort lines.
+//
 // What the scripts do with one input's line: right-strip it, split it at the first nine tabs, read column 6 as a float, take
 // column 9 of the first input as FORMAT, and append whatever stands behind the ninth tab (the "sample part", tabs inside it
 // included).  vcf_allele_freq.py then reads the first ':'-subfield of every column of every part as a GT.
@@ -22,17 +24,18 @@
 
 #include "../../include/svtyper_reads.h"
 #include "svt_bcf.h"
+#include "svt_vcf_cohort_line.h"
 
 namespace svt {
 namespace paste {
 
 constexpr uint32_t kMaxAlt = 7, kMaxPloidy = 8, kMaxPartColumns = 64, kMaxAlleleDigits = 3;
-constexpr uint32_t kMaxLine = 0x7FFFFFFFu;
 constexpr uint32_t kNoInput = 0xFFFFFFFFu, kNoField = 3;
 constexpr uint32_t kSlowMask = SVT_PASTE_SLOW_QUAL | SVT_PASTE_SLOW_COLUMNS | SVT_PASTE_SLOW_GT | SVT_PASTE_SLOW_ALLELE | SVT_PASTE_SLOW_ALT;
 
-SVT_HD bool is_space(uint8_t c) { return c == ' ' || (c >= 9 && c <= 13); }         // what str.rstrip() strips
-SVT_HD bool is_digit(uint8_t c) { return c >= '0' && c <= '9'; }
+using cohort::is_digit;
+using cohort::is_space;
+using cohort::kMaxLine;
 
 // where the columns of one right-stripped line lie
 struct Scan {
@@ -229,19 +232,10 @@ struct Block {
     uint64_t line_len(uint32_t file, uint64_t j) const { return lines[first_line[file] + j].len; }
 };
 
-// "V<id>\n" / "F<id>\n" per INFO id (F: a Flag)
-inline bool parse_info_table(const uint8_t* p, uint64_t n, std::vector<std::pair<std::string, bool>>& info)
-{
-    info.clear();
-    for (uint64_t at = 0; at < n;) {
-        const void* nl = std::memchr(p + at, '\n', n - at);
-        if (!nl || (p[at] != 'V' && p[at] != 'F')) return false;
-        const uint64_t e = (uint64_t)((const uint8_t*)nl - p);
-        info.emplace_back(std::string((const char*)p + at + 1, e - at - 1), p[at] == 'F');
-        at = e + 1;
-    }
-    return true;
-}
+using cohort::fixed2;
+using cohort::parse_info_table;
+using cohort::py_float;
+using cohort::py_int_text;
 
 inline const char* check_block(const Block& b)
 {
@@ -313,66 +307,6 @@ struct Bad {
     uint32_t file = 0, kind = 0, field = kNoField; // file 0: the master, f: input f - 1
 };
 
-inline void strip(const uint8_t* p, uint32_t& b, uint32_t& e)
-{
-    while (b < e && is_space(p[b])) ++b;
-    while (e > b && is_space(p[e - 1])) --e;
-}
-
-inline bool word_is(const uint8_t* p, uint32_t b, uint32_t e, const char* w)
-{
-    if (e - b != std::strlen(w)) return false;
-    for (uint32_t i = 0; i < e - b; ++i)
-        if ((p[b + i] | 0x20) != (uint8_t)w[i]) return false;
-    return true;
-}
-
-// float(token) of Python 2: blanks around it, a sign, inf / infinity / nan, or decimal digits with a point and an exponent
-inline bool py_float(const uint8_t* p, uint32_t b, uint32_t e, double& v)
-{
-    strip(p, b, e);
-    uint32_t i = b;
-    if (i < e && (p[i] == '+' || p[i] == '-')) ++i;
-    if (word_is(p, i, e, "inf") || word_is(p, i, e, "infinity") || word_is(p, i, e, "nan")) {
-        v = word_is(p, i, e, "nan") ? std::nan("") : HUGE_VAL;
-        if (p[b] == '-') v = -v;
-        return true;
-    }
-    uint32_t digits = 0;
-    while (i < e && is_digit(p[i])) { ++i; ++digits; }
-    if (i < e && p[i] == '.') {
-        ++i;
-        while (i < e && is_digit(p[i])) { ++i; ++digits; }
-    }
-    if (!digits) return false;
-    if (i < e && (p[i] | 0x20) == 'e') {
-        ++i;
-        if (i < e && (p[i] == '+' || p[i] == '-')) ++i;
-        if (i == e || !is_digit(p[i])) return false;
-        while (i < e && is_digit(p[i])) ++i;
-    }
-    if (i != e) return false;
-    const std::string token((const char*)p + b, e - b);
-    v = std::strtod(token.c_str(), nullptr);
-    return true;
-}
-
-// str(int(token)): blanks around it, a sign, decimal digits of any number
-inline bool py_int_text(const uint8_t* p, uint32_t b, uint32_t e, std::string& out)
-{
-    strip(p, b, e);
-    const bool neg = b < e && p[b] == '-';
-    if (b < e && (p[b] == '+' || p[b] == '-')) ++b;
-    if (b == e) return false;
-    for (uint32_t i = b; i < e; ++i)
-        if (!is_digit(p[i])) return false;
-    while (e - b > 1 && p[b] == '0') ++b;
-    out.clear();
-    if (neg && p[b] != '0') out += '-';
-    out.append((const char*)p + b, e - b);
-    return true;
-}
-
 // int(token) where it lies inside [-limit, limit]
 inline bool py_small_int(const uint8_t* p, uint32_t b, uint32_t e, int64_t limit, int64_t& v)
 {
@@ -391,14 +325,6 @@ inline std::string py2_str(double v)
     std::string s(buf);
     if (s.find_first_of(".en") == std::string::npos) s += ".0";      // ('e', "inf", "nan": no ".0")
     return s;
-}
-
-inline std::string fixed2(double v)
-{
-    if (std::isnan(v)) return "nan";
-    char buf[400];
-    std::snprintf(buf, sizeof buf, "%0.2f", v);
-    return buf;
 }
 
 // The output line's first columns: CHROM .. FILTER with the QUAL the options ask for, INFO (rebuilt under --afreq), FORMAT.

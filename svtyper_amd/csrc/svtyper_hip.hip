@@ -207,6 +207,7 @@ void svt_batch_destroy(svt_batch* b) { free_batch(b); }
 #include "svt_entry_deflate.h"
 #include "svt_entry_vcf_lines.h"
 #include "svt_entry_vcf_paste.h"
+#include "svt_entry_vcf_cohort.h"
 #include "svt_entry_vcf_classify.h"
 #include "svt_entry_vcf_update_info.h"
 #include "svt_entry_radix_sort.h"

@@ -336,30 +336,8 @@ def _lib():
             L.svt_vcf_paste_device.argtypes = L.svt_vcf_paste_host.argtypes + [C.c_int]
             L.svt_vcf_paste_last_times.restype = C.c_int
             L.svt_vcf_paste_last_times.argtypes = [C.POINTER(_PasteTimes)]
-        if hasattr(L, "svt_vcf_classify_host"):    # (likewise: the read-depth classifier of DEL and DUP lines)
-            P, U64, U32, D = C.c_void_p, C.c_uint64, C.c_uint32, C.c_double
-            L.svt_vcf_classify_host.restype = C.c_int
-            L.svt_vcf_classify_host.argtypes = [P, U64, U32, P, P, P, P, U64, P, D, D, P, U64, P, C.POINTER(_ClassifyInfo)]
-            L.svt_vcf_classify_device.restype = C.c_int
-            L.svt_vcf_classify_device.argtypes = L.svt_vcf_classify_host.argtypes + [C.c_int]
-            L.svt_vcf_classify_write.restype = C.c_int
-            L.svt_vcf_classify_write.argtypes = [P, U64, U32, P, U64, P, U64, P, U64, P, C.POINTER(_ClassifyInfo)]
-            L.svt_vcf_classify_take.restype = C.c_int
-            L.svt_vcf_classify_take.argtypes = [P, U64]
-            L.svt_vcf_classify_last_times.restype = C.c_int
-            L.svt_vcf_classify_last_times.argtypes = [C.POINTER(_ClassifyTimes)]
-        if hasattr(L, "svt_vcf_update_info_host"):  # (likewise: PE, SR, SU and MSQ from the samples' evidence)
-            P, U64, U32 = C.c_void_p, C.c_uint64, C.c_uint32
-            L.svt_vcf_update_info_host.restype = C.c_int
-            L.svt_vcf_update_info_host.argtypes = [P, U64, U32, P, U64, P, U64, P, C.POINTER(_UpdateInfoReport)]
-            L.svt_vcf_update_info_device.restype = C.c_int
-            L.svt_vcf_update_info_device.argtypes = L.svt_vcf_update_info_host.argtypes + [C.c_int]
-            L.svt_vcf_update_info_write.restype = C.c_int
-            L.svt_vcf_update_info_write.argtypes = [P, U64, U32, P, U64, P, U64, P, U64, P, C.POINTER(_UpdateInfoReport)]
-            L.svt_vcf_update_info_take.restype = C.c_int
-            L.svt_vcf_update_info_take.argtypes = [P, U64]
-            L.svt_vcf_update_info_last_times.restype = C.c_int
-            L.svt_vcf_update_info_last_times.argtypes = [C.POINTER(_UpdateInfoTimes)]
+        for rule in (_CLASSIFY, _UPDATE_INFO):      # (likewise: the rules over the lines of a cohort VCF)
+            rule.declare(L)
         if hasattr(L, "svt_bam_spans_host"):       # (likewise: BAM records as spans, the sorted and indexed `-w` dump)
             P, U64, I32 = C.c_void_p, C.c_uint64, C.c_int32
             for name, argtypes in (("svt_bam_spans_host", [P, U64, P, U64, I32, P, P, P]), ("svt_bam_spans_device", [P, U64, P, U64, I32, P, P, P, C.c_int]),
@@ -1035,6 +1013,72 @@ def vcf_paste_last_times() -> Dict[str, float]:
     return {name: float(getattr(t, name)) for name, _ in _PasteTimes._fields_}
 
 
+class _CohortRule:
+    """the ctypes side of one rule over the lines of a cohort VCF: svt_vcf_<rule>_host, _device, _write, _take and _last_times.
+    `middle`: the argument types of _host between (text, len) and (results, capacity, n_lines, info)"""
+
+    def __init__(self, rule, line, info, times, middle):
+        self.rule, self.line, self.info, self.times, self.middle = rule, line, info, times, middle
+
+    def entry(self, L, name):
+        return getattr(L, "svt_vcf_%s_%s" % (self.rule, name))
+
+    def declare(self, L):
+        if not hasattr(L, "svt_vcf_%s_host" % self.rule):           # (a library built before the rule lacks the symbols)
+            return
+        P, U64 = C.c_void_p, C.c_uint64
+        host = [P, U64] + self.middle + [P, U64, P, C.POINTER(self.info)]
+        for name, argtypes in (("host", host), ("device", host + [C.c_int]), ("take", [P, U64]), ("last_times", [C.POINTER(self.times)]),
+                               ("write", [P, U64, C.c_uint32, P, U64, P, U64, P, U64, P, C.POINTER(self.info)])):
+            self.entry(L, name).restype = C.c_int
+            self.entry(L, name).argtypes = argtypes
+
+    def lib(self):
+        L = _lib()
+        if not hasattr(L, "svt_vcf_%s_host" % self.rule):
+            raise hip.SvtyperHipError("this libsvtyper_hip.so has no svt_vcf_%s_host (built before svtyper_amd.%s)" % (self.rule, self.rule))
+        return L
+
+    def report(self, info) -> dict:
+        report = {name: int(getattr(info, name)) for name, _ in self.info._fields_ if name != "bad_text"}
+        report["bad_text"] = bytes(info.bad_text).decode("utf-8", "surrogateescape")
+        return report
+
+    def records(self, text, middle, device):
+        """_host (device None) / _device over one block: (the records, one per line, the report)"""
+        L = self.lib()
+        buf = _text_array(text)
+        capacity = text.count(b"\n") + 1
+        results = np.zeros(capacity, self.line)
+        n_lines = C.c_uint64(0)
+        info = self.info()
+        args = [buf.ctypes.data, len(text)] + middle + [results.ctypes.data, capacity, C.addressof(n_lines), C.byref(info)]
+        if device is None:
+            hip._check(self.entry(L, "host")(*args))
+        else:
+            hip._check(self.entry(L, "device")(*args, int(device)))
+        return results[:n_lines.value], self.report(info)
+
+    def write(self, text, n_samples, info_table, format_table, results):
+        """_write + _take: (the block's output text, out_off [lines + 1], the report)"""
+        L = self.lib()
+        buf, inf, fmt = _text_array(text), _text_array(info_table), _text_array(format_table)
+        results = np.ascontiguousarray(results, self.line)
+        out_off = np.zeros(results.shape[0] + 1, np.uint64)
+        info = self.info()
+        hip._check(self.entry(L, "write")(buf.ctypes.data, len(text), int(n_samples), inf.ctypes.data, len(info_table), fmt.ctypes.data,
+                                          len(format_table), results.ctypes.data if results.shape[0] else None, results.shape[0],
+                                          out_off.ctypes.data, C.byref(info)))
+        out = np.empty(max(info.out_len, 1), np.uint8)
+        hip._check(self.entry(L, "take")(out.ctypes.data, info.out_len))
+        return out[:info.out_len].tobytes(), out_off, self.report(info)
+
+    def last_times(self) -> Dict[str, float]:
+        t = self.times()
+        hip._check(self.entry(self.lib(), "last_times")(C.byref(t)))
+        return {name: float(getattr(t, name)) for name, _ in self.times._fields_}
+
+
 CLASSIFY_LINE = np.dtype([("median", np.float64), ("mad", np.float64), ("slope", np.float64), ("r2", np.float64), ("route", np.uint32),
                           ("verdict", np.uint32), ("n_pos", np.uint32), ("n_ref", np.uint32), ("n_alt", np.uint32), ("quorum", np.uint32),
                           ("n_regressed", np.uint32), ("flags", np.uint32)])         # svt_classify_line
@@ -1047,17 +1091,8 @@ CLASSIFY_SLOW, CLASSIFY_NEAR, CLASSIFY_DEL = 255, 256, 512
  CLASSIFY_BAD_GENDER) = 1, 2, 3, 4, 5, 6, 7, 8
 
 
-def _classify_lib():
-    L = _lib()
-    if not hasattr(L, "svt_vcf_classify_host"):
-        raise hip.SvtyperHipError("this libsvtyper_hip.so has no svt_vcf_classify_host (built before svtyper_amd.classify)")
-    return L
-
-
-def _classify_report(info) -> dict:
-    report = {name: int(getattr(info, name)) for name, _ in _ClassifyInfo._fields_ if name != "bad_text"}
-    report["bad_text"] = bytes(info.bad_text).decode("utf-8", "surrogateescape")
-    return report
+_CLASSIFY = _CohortRule("classify", CLASSIFY_LINE, _ClassifyInfo, _ClassifyTimes,
+                        [C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_double, C.c_double])
 
 
 def vcf_classify(text: bytes, male, female, excluded, format_table: bytes, slope_threshold: float, rsquared_threshold: float, skip=None,
@@ -1065,54 +1100,31 @@ def vcf_classify(text: bytes, male, female, excluded, format_table: bytes, slope
     """svt_vcf_classify_host (device None) / _device over one block of body lines: (records CLASSIFY_LINE, one per line, info);
     male, female, excluded: one byte per sample of the header; skip: one byte per line or None.  info: host_lines, near_lines and,
     where the script dies on a line, bad_line (1-based in the block), bad_kind, bad_sample, bad_text"""
-    L = _classify_lib()
-    buf = _text_array(text)
     tables = [np.ascontiguousarray(t, np.uint8) for t in (male, female, excluded)]
     n_samples = tables[0].shape[0]
     if any(t.shape != (n_samples,) for t in tables):
         raise ValueError("male, female and excluded hold one byte per sample")
     tables = [t if n_samples else np.zeros(1, np.uint8) for t in tables]
-    capacity = text.count(b"\n") + 1
     if skip is not None:
         skip = np.ascontiguousarray(skip, np.uint8)
-        if skip.shape[0] < capacity - (text.endswith(b"\n") or not text):
+        if skip.shape[0] < text.count(b"\n") + 1 - (text.endswith(b"\n") or not text):
             raise ValueError("skip holds one byte per line")
     fmt = _text_array(format_table)
-    results = np.zeros(capacity, CLASSIFY_LINE)
-    n_lines = C.c_uint64(0)
-    info = _ClassifyInfo()
-    args = [buf.ctypes.data, len(text), n_samples, tables[0].ctypes.data, tables[1].ctypes.data, tables[2].ctypes.data, fmt.ctypes.data,
-            len(format_table), skip.ctypes.data if skip is not None else None, float(slope_threshold), float(rsquared_threshold),
-            results.ctypes.data, capacity, C.addressof(n_lines), C.byref(info)]
-    if device is None:
-        hip._check(L.svt_vcf_classify_host(*args))
-    else:
-        hip._check(L.svt_vcf_classify_device(*args, int(device)))
-    return results[:n_lines.value], _classify_report(info)
+    return _CLASSIFY.records(text, [n_samples, tables[0].ctypes.data, tables[1].ctypes.data, tables[2].ctypes.data, fmt.ctypes.data,
+                                    len(format_table), skip.ctypes.data if skip is not None else None, float(slope_threshold),
+                                    float(rsquared_threshold)], device)
 
 
 def vcf_classify_write(text: bytes, n_samples: int, info_table: bytes, format_table: bytes, results: np.ndarray):
     """svt_vcf_classify_write + _take: (the block's output text, out_off [lines + 1], info); where a line cannot be written (an
     unsupported call without END, SVLEN or a confidence interval) info has bad_line, bad_kind, bad_text and the text ends in
     front of that line"""
-    L = _classify_lib()
-    buf, inf, fmt = _text_array(text), _text_array(info_table), _text_array(format_table)
-    results = np.ascontiguousarray(results, CLASSIFY_LINE)
-    out_off = np.zeros(results.shape[0] + 1, np.uint64)
-    info = _ClassifyInfo()
-    hip._check(L.svt_vcf_classify_write(buf.ctypes.data, len(text), int(n_samples), inf.ctypes.data, len(info_table), fmt.ctypes.data,
-                                        len(format_table), results.ctypes.data if results.shape[0] else None, results.shape[0],
-                                        out_off.ctypes.data, C.byref(info)))
-    out = np.empty(max(info.out_len, 1), np.uint8)
-    hip._check(L.svt_vcf_classify_take(out.ctypes.data, info.out_len))
-    return out[:info.out_len].tobytes(), out_off, _classify_report(info)
+    return _CLASSIFY.write(text, n_samples, info_table, format_table, results)
 
 
 def vcf_classify_last_times() -> Dict[str, float]:
     """svt_vcf_classify_last_times: the kernels of this thread's last svt_vcf_classify_device from HIP events, its copies on the host's clock"""
-    t = _ClassifyTimes()
-    hip._check(_classify_lib().svt_vcf_classify_last_times(C.byref(t)))
-    return {name: float(getattr(t, name)) for name, _ in _ClassifyTimes._fields_}
+    return _CLASSIFY.last_times()
 
 
 UPDATE_INFO_LINE = np.dtype([("pe", np.int64), ("sr", np.int64), ("sum_sq", np.uint64), ("num_pos", np.uint32), ("route", np.uint32),
@@ -1126,59 +1138,26 @@ UPDATE_INFO_SLOW = 127
  UPDATE_INFO_BAD_NONFINITE, UPDATE_INFO_BAD_OVERFLOW, UPDATE_INFO_BAD_EIGHT) = 1, 2, 3, 4, 5, 6, 7, 8, 9
 
 
-def _update_info_lib():
-    L = _lib()
-    if not hasattr(L, "svt_vcf_update_info_host"):
-        raise hip.SvtyperHipError("this libsvtyper_hip.so has no svt_vcf_update_info_host (built before svtyper_amd.update_info)")
-    return L
-
-
-def _update_info_report(info) -> dict:
-    report = {name: int(getattr(info, name)) for name, _ in _UpdateInfoReport._fields_ if name != "bad_text"}
-    report["bad_text"] = bytes(info.bad_text).decode("utf-8", "surrogateescape")
-    return report
+_UPDATE_INFO = _CohortRule("update_info", UPDATE_INFO_LINE, _UpdateInfoReport, _UpdateInfoTimes, [C.c_uint32, C.c_void_p, C.c_uint64])
 
 
 def vcf_update_info(text: bytes, n_samples: int, format_table: bytes, device: Optional[int] = None):
     """svt_vcf_update_info_host (device None) / _device over one block of body lines: (records UPDATE_INFO_LINE, one per line, info).
     info: host_lines and, where the script dies on a line, bad_line (1-based in the block), bad_kind, bad_sample, bad_text"""
-    L = _update_info_lib()
-    buf, fmt = _text_array(text), _text_array(format_table)
-    capacity = text.count(b"\n") + 1
-    results = np.zeros(capacity, UPDATE_INFO_LINE)
-    n_lines = C.c_uint64(0)
-    info = _UpdateInfoReport()
-    args = [buf.ctypes.data, len(text), int(n_samples), fmt.ctypes.data, len(format_table), results.ctypes.data, capacity, C.addressof(n_lines),
-            C.byref(info)]
-    if device is None:
-        hip._check(L.svt_vcf_update_info_host(*args))
-    else:
-        hip._check(L.svt_vcf_update_info_device(*args, int(device)))
-    return results[:n_lines.value], _update_info_report(info)
+    fmt = _text_array(format_table)
+    return _UPDATE_INFO.records(text, [int(n_samples), fmt.ctypes.data, len(format_table)], device)
 
 
 def vcf_update_info_write(text: bytes, n_samples: int, info_table: bytes, format_table: bytes, results: np.ndarray):
     """svt_vcf_update_info_write + _take: (the block's output text, out_off [lines + 1], info); where a line cannot be written info has
     bad_line, bad_kind, bad_text and the text ends in front of that line"""
-    L = _update_info_lib()
-    buf, inf, fmt = _text_array(text), _text_array(info_table), _text_array(format_table)
-    results = np.ascontiguousarray(results, UPDATE_INFO_LINE)
-    out_off = np.zeros(results.shape[0] + 1, np.uint64)
-    info = _UpdateInfoReport()
-    hip._check(L.svt_vcf_update_info_write(buf.ctypes.data, len(text), int(n_samples), inf.ctypes.data, len(info_table), fmt.ctypes.data,
-                                           len(format_table), results.ctypes.data if results.shape[0] else None, results.shape[0],
-                                           out_off.ctypes.data, C.byref(info)))
-    out = np.empty(max(info.out_len, 1), np.uint8)
-    hip._check(L.svt_vcf_update_info_take(out.ctypes.data, info.out_len))
-    return out[:info.out_len].tobytes(), out_off, _update_info_report(info)
+    return _UPDATE_INFO.write(text, n_samples, info_table, format_table, results)
 
 
 def vcf_update_info_last_times() -> Dict[str, float]:
     """svt_vcf_update_info_last_times: the kernels of this thread's last svt_vcf_update_info_device from HIP events, its copies on the
     host's clock"""
-    t = _UpdateInfoTimes()
-    hip._check(_update_info_lib().svt_vcf_update_info_last_times(C.byref(t)))
-    return {name: float(getattr(t, name)) for name, _ in _UpdateInfoTimes._fields_}
+    return _UPDATE_INFO.last_times()
 
 
 def tbx_build(text: bytes, lines: np.ndarray, member_off, src_off=None, payload: int = DEFLATE_MAX_PAYLOAD, csi: bool = False):

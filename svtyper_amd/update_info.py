@@ -34,8 +34,8 @@ import time
 from typing import Optional
 
 from . import native_reads as nr
-from .cohort import blocks, bytes_lines, chrom_lines, header_text, open_source, read_header
-from .paste import BLOCK_BYTES, _text, add_attributes, declared_lines, header_attributes, info_table
+from .cohort import blocks, bytes_lines, chrom_lines, finish_block, header_text, open_source, read_header
+from .paste import BLOCK_BYTES, add_attributes, declared_lines, header_attributes, info_table
 
 FORMAT_MESSAGE = '\nError: invalid FORMAT field, "%s"\n'
 COLUMNS_MESSAGE = "\nError: VCF file must have at least 8 columns\n"
@@ -117,25 +117,9 @@ def _run(name, lines, vcf_out, device, file_date, block_bytes, stats, keep_conti
     format_bytes = "".join(i + "\n" for i, _, _, _ in formats).encode("utf-8", "surrogateescape")
     for block in blocks(first, lines, block_bytes):
         text = b"".join(block) + (b"" if block[-1].endswith(b"\n") else b"\n")     # (the file's last line: rewritten lines end in a newline)
-        results, info = nr.vcf_update_info(text, len(samples), format_bytes, device)
-        whole = info["bad_line"] - 1 if info["bad_line"] else len(block)           # the lines in front of the one the script dies on
-        if whole < len(block):
-            text = b"".join(block[:whole])
-        out, _out_off, written = nr.vcf_update_info_write(text, len(samples), info_bytes, format_bytes, results[:whole])
-        if written["bad_line"]:
-            whole = written["bad_line"] - 1
-        vcf_out.write(_text(out))
-        stats["lines"] += whole
-        stats["blocks"] += 1
-        stats["host_lines"] += info["host_lines"]
-        stats["results"].append(results)
-        if device is not None:
-            for key, value in nr.vcf_update_info_last_times().items():
-                stats["times"][key] = stats["times"].get(key, 0.0) + value
-        for report in (written, info):
-            if report["bad_line"]:
-                sample = samples[report["bad_sample"]] if report["bad_sample"] < len(samples) else None
-                raise _bad(name, done + whole + 1, report["bad_kind"], report["bad_text"], sample)
+        finish_block(name, done, block, text, samples, nr.vcf_update_info(text, len(samples), format_bytes, device),
+                     lambda kept, results: nr.vcf_update_info_write(kept, len(samples), info_bytes, format_bytes, results),
+                     nr.vcf_update_info_last_times if device is not None else None, _bad, vcf_out, stats)
         done += len(block)
 
 

@@ -67,7 +67,7 @@ static std::string block(const std::vector<uint8_t>& bytes, size_t len, const Ta
     host_lines += info.host_lines;
     if (info.bad_line) return "!" + std::to_string(info.bad_line) + "," + std::to_string(info.bad_kind);
     classify::Block w;
-    if (!classify::parse_format_table(t.formats.data(), t.formats.size(), w.formats) || !svt::paste::parse_info_table(t.infos.data(), t.infos.size(), w.info))
+    if (!svt::cohort::parse_format_table(t.formats.data(), t.formats.size(), w.formats) || !svt::cohort::parse_info_table(t.infos.data(), t.infos.size(), w.info))
         return "?tables";
     w.text = text.get();
     w.len = len;

@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 
 import test_bcf_host as B
+import test_cohort_line_host as L
 import test_update_info_host as H
 import updateinfocases as K
 from svtyper_amd import native_reads as nr
@@ -90,3 +91,13 @@ def test_command_line_to_a_sorted_indexed_bcf_file(tmp_path, hip_device):
     text = want.getvalue()
     assert text.count("\n1\t") == 5 and text.count(";MSQ=") == 5 and "SNAME" not in text
     assert B.check_indexed(out, text, 1, 249250621)
+
+
+@pytest.mark.parametrize("k", range(len(L.K.LENGTHS)))
+def test_column_starts_at_every_residue_and_length_on_the_device(k, hip_device):
+    """tests/cohortlinecases.py: the sample region at the 16 residues of its address, around one piece, one step and two steps of
+    the 128-bit scan, first and last in its block: the host's records and text, and no line leaves the device"""
+    records, _info, out, _written = L.host("update_info", k)
+    got, info, text, written = L.run("update_info", L.blocks("update_info")[k], device=hip_device)
+    assert info["host_lines"] == 0 and info["bad_line"] == 0 and written["bad_line"] == 0
+    assert got.tobytes() == records.tobytes() and text == out
