@@ -523,6 +523,76 @@ typedef struct svt_vcf_update_info_times {
     double total_s;
 } svt_vcf_update_info_times;
 int svt_vcf_update_info_last_times(svt_vcf_update_info_times* times);
+/* BND mates grouped in front of the paste (svtyper_amd/group_multiline.py; the reference's scripts/vcf_group_multiline.py).
+ * Added without a new SVT_ABI_VERSION: probe for the symbol.  One call takes the WHOLE body (a pair may span the file).
+ * format_table as svt_vcf_update_info_host's.  lines[j] is what the per-line rule (svt_vcf_group.h) reads of line j; plan is
+ * the output in its order: entry {line, source} stands for `line`'s columns 1 to 5, FILTER and INFO with `source`'s QUAL,
+ * FORMAT and sample columns (source == line for a line that is no BND; a pair is (a, a) then (b, a), a the line stored
+ * first).  plan holds 2 * capacity entries.  Where the script dies, report->bad_line is that line's 1-based number, bad_kind
+ * SVT_GROUP_BAD_*, bad_text the key or token in the way, and the plan ends in front of it (SVT_OK all the same).
+ * svt_vcf_group_device: the same lines and the same plan, byte for byte, from svt_vcf_group_kernel.h; hash_bits (1..64):
+ * the bits of the ID hashes it sorts by.  report->host_join: the join ran on the host (always for svt_vcf_group_host; for the
+ * device where a line is marked or the file is not regular); n_bnd: the BND lines the join looked at (the host's
+ * stops at the line the script dies on, the device's takes every line the rule decided).  svt_vcf_group_write: the text of the plan,
+ * out_off[0 .. n_plan], kept for the calling thread (report->out_len, svt_vcf_group_take).                               */
+typedef struct svt_group_line {
+    uint64_t off;                           /* where the line begins in the text                                          */
+    uint32_t len;                           /* its length without trailing blanks                                         */
+    uint32_t id_b, id_n, mate_b, mate_n;    /* the ID column and INFO's MATEID value, relative to the line                */
+    uint32_t flags;                         /* SVT_GROUP_BND, _HAS_MATE, _CI                                              */
+    uint32_t slow;                          /* SVT_GROUP_SLOW_*: outside the rule's envelope, decided in plain C++        */
+    uint32_t bad;                           /* SVT_GROUP_BAD_KEY | key << 8: the script dies ON this line (0: it does not) */
+} svt_group_line;
+typedef struct svt_group_out {
+    uint32_t line, source;
+} svt_group_out;
+typedef struct svt_group_report {
+    uint64_t out_len, host_lines, bad_line;
+    uint32_t bad_kind, bad_sample;
+    uint32_t host_join, n_bnd;
+    char bad_text[48];
+} svt_group_report;
+#define SVT_GROUP_BND 1u                  /* SVTYPE=BND                                                                  */
+#define SVT_GROUP_HAS_MATE 2u             /* a BND with a MATEID value                                                   */
+#define SVT_GROUP_CI 4u                   /* what the script reads of the line's own intervals is there: CIPOS of a BND  */
+                                          /* (read when it pairs), END, CIPOS and CIEND of any other line                */
+#define SVT_GROUP_SLOW_HEAD 1u            /* fewer than eight columns, a POS or QUAL outside the exact rules             */
+#define SVT_GROUP_SLOW_FORMAT 2u          /* FORMAT is not GT first and the header's keys in the header's order          */
+#define SVT_GROUP_SLOW_BARE 4u            /* a key the script reads stands without '='                                   */
+#define SVT_GROUP_SLOW_TOKEN 8u           /* END, or a token of CIPOS or CIEND, that is not '-'? and one to nine digits  */
+#define SVT_GROUP_SLOW_ALT 16u            /* a BND with an empty ALT                                                     */
+#define SVT_GROUP_SLOW 31u
+#define SVT_GROUP_BAD_COLUMNS 1u          /* fewer than seven columns (IndexError)                                       */
+#define SVT_GROUP_BAD_POS 2u              /* a POS that int() refuses (ValueError)                                       */
+#define SVT_GROUP_BAD_QUAL 3u             /* a QUAL that float() refuses (ValueError)                                    */
+#define SVT_GROUP_BAD_FORMAT 4u           /* a FORMAT key the header does not declare (the script's message, status 1)   */
+#define SVT_GROUP_BAD_KEY 5u              /* bad_text: the INFO key the line lacks (KeyError)                            */
+#define SVT_GROUP_BAD_NUMBER 6u           /* bad_text: a token of END, CIPOS or CIEND that int() refuses (ValueError)    */
+#define SVT_GROUP_BAD_BARE 7u             /* bad_text: CIPOS or CIEND without '=' (AttributeError)                       */
+#define SVT_GROUP_BAD_ALT 8u              /* a pair with an empty ALT (IndexError)                                       */
+#define SVT_GROUP_BAD_EIGHT 9u            /* seven columns (the script's message, status 1)                              */
+#define SVT_GROUP_KEY_SVTYPE 0u           /* the keys of SVT_GROUP_BAD_KEY in svt_group_line.bad                         */
+#define SVT_GROUP_KEY_MATEID 1u
+#define SVT_GROUP_KEY_END 2u
+#define SVT_GROUP_KEY_CIPOS 3u
+#define SVT_GROUP_KEY_CIEND 4u
+int svt_vcf_group_host(const uint8_t* text, uint64_t len, uint32_t n_samples, const uint8_t* format_table, uint64_t format_len,
+                       svt_group_line* lines, uint64_t capacity, uint64_t* n_lines, svt_group_out* plan, uint64_t* n_plan,
+                       svt_group_report* report);
+int svt_vcf_group_device(const uint8_t* text, uint64_t len, uint32_t n_samples, const uint8_t* format_table, uint64_t format_len,
+                         svt_group_line* lines, uint64_t capacity, uint64_t* n_lines, svt_group_out* plan, uint64_t* n_plan,
+                         svt_group_report* report, uint32_t hash_bits, int device);
+int svt_vcf_group_write(const uint8_t* text, uint64_t len, uint32_t n_samples, const uint8_t* info_table, uint64_t info_len,
+                        const uint8_t* format_table, uint64_t format_len, const svt_group_line* lines, uint64_t n_lines,
+                        const svt_group_out* plan, uint64_t n_plan, uint64_t* out_off, svt_group_report* report);
+int svt_vcf_group_take(uint8_t* out, uint64_t capacity);
+/* the calling thread's most recent svt_vcf_group_device: its kernels by HIP events, its copies on the host's clock        */
+typedef struct svt_vcf_group_times {
+    double lines_kernels_s, scan_kernel_s, compact_kernels_s, sort_kernels_s, match_kernel_s, plan_kernels_s;
+    double upload_s, download_s, host_s;    /* the text up; the records and the plan down; the host's join and report    */
+    double total_s;
+} svt_vcf_group_times;
+int svt_vcf_group_last_times(svt_vcf_group_times* times);
 /* The index fold: the uncompressed bytes of a .tbi (SAM spec 5.2 binning, 14-bit leaves, five levels; the layout of
  * the tabix format, format = 2 (VCF), col_seq 1, col_beg 2, col_end 0, meta '#', skip 0; pseudo-bin 37450 with the
  * contig's line count) for the body lines of `lines`, a table of the text as written.  The CHROM of line j is read at

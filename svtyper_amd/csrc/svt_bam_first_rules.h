@@ -65,11 +65,17 @@ SVT_HD bool key_equal(const Key& a, const Key& b)
     return true;
 }
 
-// FNV-1a (64 bits) over the name bytes, then the flag's two bytes, low byte first
+// FNV-1a (64 bits) over p[0, n), from `h` on: also the hash of a VCF line's ID (svt_vcf_group.h)
+SVT_HD uint64_t fnv1a(const uint8_t* p, uint32_t n, uint64_t h = 0xcbf29ce484222325ull)
+{
+    for (uint32_t c = 0; c < n; ++c) h = (h ^ p[c]) * 0x100000001b3ull;
+    return h;
+}
+
+// FNV-1a over the name bytes, then the flag's two bytes, low byte first
 SVT_HD uint64_t key_hash(const Key& k)
 {
-    uint64_t h = 0xcbf29ce484222325ull;
-    for (uint32_t c = 0; c < k.len; ++c) h = (h ^ k.name[c]) * 0x100000001b3ull;
+    uint64_t h = fnv1a(k.name, k.len);
     h = (h ^ (k.flag & 255u)) * 0x100000001b3ull;
     h = (h ^ (k.flag >> 8 & 255u)) * 0x100000001b3ull;
     return h;

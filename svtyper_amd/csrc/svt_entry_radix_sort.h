@@ -18,10 +18,12 @@ struct RadixSort {
         return d_idx[0].alloc(capacity * sizeof(uint32_t));
     }
     // n pairs (n <= capacity) are what a key kernel is about to write: the grid to launch it with, part_and() / part_or() for it
-    int key_grid(uint64_t n, int device, unsigned* grid)
+    int key_grid(uint64_t n, int device, unsigned* grid) { return key_grid(n, n, device, grid); }
+    // the same for a key kernel that walks `work` elements to write its n pairs (a compaction: svt_entry_vcf_group.h)
+    int key_grid(uint64_t n, uint64_t work, int device, unsigned* grid)
     {
         n_ = n;
-        grid_ = *grid = lines_grid((n + kSortBlock - 1) / kSortBlock, device);
+        grid_ = *grid = lines_grid((work + kSortBlock - 1) / kSortBlock, device);
         SVT_TRY(d_and.alloc(grid_ * sizeof(uint64_t)));
         return d_or.alloc(grid_ * sizeof(uint64_t));
     }

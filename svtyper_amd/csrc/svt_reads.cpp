@@ -46,6 +46,7 @@
 #include "svt_vcf_paste.h"
 #include "svt_vcf_classify.h"
 #include "svt_vcf_update_info.h"
+#include "svt_vcf_group.h"
 
 namespace {
 using svt::fail;
@@ -74,3 +75,4 @@ using rr::ld32;
 #include "svt_reads_cohort_entries.h"  // cohort_write, cohort_take: the writer's entry points of a rule over cohort lines
 #include "svt_reads_classify_entries.h" // svt_vcf_classify_host, _write, _take: the read-depth classifier of DEL and DUP lines
 #include "svt_reads_update_info_entries.h" // svt_vcf_update_info_host, _write, _take: PE, SR, SU and MSQ from the samples' evidence
+#include "svt_reads_group_entries.h"  // svt_vcf_group_host, _write, _take: BND mates grouped in front of the paste

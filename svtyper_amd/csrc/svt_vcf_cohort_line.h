@@ -1,6 +1,7 @@
 // svt_vcf_cohort_line.h -- a body line of a cohort VCF: what the programs that read such lines share.  The users are
 // svt_vcf_paste.h (the character classes and the text-side number helpers), svt_vcf_classify.h and svt_vcf_update_info.h (all of
-// it); none of them includes another's header.
+// it) and svt_vcf_group.h (the line's tabs, POS, QUAL and FORMAT, the field walk, the script's Variant and its writer; its join
+// over the whole file has drivers of its own); none of them includes another's header.
 //
 // Host and device (SVT_HD): the right-strip, the first nine tabs, the checks of POS, QUAL and FORMAT that both rules make on the
 // head, the walk over the ':' fields of a column.  Every load is checked against the line's length.  What differs between the
@@ -120,15 +121,21 @@ SVT_HD void begin_head(uint32_t n, const Tabs& t, Head& h)
 // The checks on the head of a line of at least eight columns: POS of 1 to 18 digits and QUAL "." or inside bcf::double_exact
 // (else `mark_head`), FORMAT with GT first and the header's keys in the header's order (else `mark_format`).  `keys`: n_keys
 // FORMAT keys of two letters side by side, whose places go to h.key_at
-SVT_HD void check_head(const uint8_t* p, const Tabs& t, const uint8_t* table, uint32_t table_len, uint32_t mark_head, uint32_t mark_format,
-                       const char* keys, uint32_t n_keys, Head& h)
+// the first half on its own, for a rule that also takes lines of eight columns (svt_vcf_group.h): POS and QUAL of a line of at
+// least six tabs
+SVT_HD bool pos_qual_exact(const uint8_t* p, const Tabs& t)
 {
     const uint32_t pos_b = t.tab[0] + 1, pos_e = t.tab[1], qual_b = t.tab[4] + 1, qual_e = t.tab[5];
     bool digits = pos_e > pos_b && pos_e - pos_b <= 18;
     for (uint32_t i = pos_b; i < pos_e; ++i) digits = digits && is_digit(p[i]);
-    if (!digits) h.slow |= mark_head;
     double qual;
-    if (!bcf::is_dot(p, qual_b, qual_e) && bcf::double_exact(p, qual_b, qual_e, qual)) h.slow |= mark_head;
+    return digits && (bcf::is_dot(p, qual_b, qual_e) || !bcf::double_exact(p, qual_b, qual_e, qual));
+}
+
+SVT_HD void check_head(const uint8_t* p, const Tabs& t, const uint8_t* table, uint32_t table_len, uint32_t mark_head, uint32_t mark_format,
+                       const char* keys, uint32_t n_keys, Head& h)
+{
+    if (!pos_qual_exact(p, t)) h.slow |= mark_head;
     uint32_t last = kNone;
     h.n_fmt = walk_fields(p, column_begin(t, 8, h.n), t.tab[8], ':', [&](uint32_t idx, uint32_t b, uint32_t e) {
         const uint32_t k = table_index(table, table_len, p, b, e);

@@ -78,6 +78,7 @@
 #include "svt_radix_sort_kernel.h"
 #include "svt_bam_sort_kernel.h"
 #include "svt_bam_first_kernel.h"
+#include "svt_vcf_group_kernel.h"
 #include "svt_bam_index_kernel.h"
 #include "svt_bcf_kernel.h"
 #include "svt_bcf_text_kernel.h"
@@ -213,6 +214,7 @@ void svt_batch_destroy(svt_batch* b) { free_batch(b); }
 #include "svt_entry_radix_sort.h"
 #include "svt_entry_bam_sort.h"
 #include "svt_entry_bam_first.h"
+#include "svt_entry_vcf_group.h"
 #include "svt_entry_bam_index.h"
 #include "svt_entry_bcf.h"
 #include "svt_entry_bcf_text.h"

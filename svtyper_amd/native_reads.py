@@ -175,6 +175,18 @@ class _UpdateInfoTimes(C.Structure):
     _fields_ = [(name, C.c_double) for name in ("lines_kernels_s", "update_info_kernel_s", "upload_s", "download_s", "host_s", "total_s")]
 
 
+class _GroupReport(C.Structure):
+    """include/svtyper_reads.h: svt_group_report"""
+    _fields_ = [("out_len", C.c_uint64), ("host_lines", C.c_uint64), ("bad_line", C.c_uint64), ("bad_kind", C.c_uint32),
+                ("bad_sample", C.c_uint32), ("host_join", C.c_uint32), ("n_bnd", C.c_uint32), ("bad_text", C.c_char * 48)]
+
+
+class _GroupTimes(C.Structure):
+    """include/svtyper_reads.h: svt_vcf_group_times"""
+    _fields_ = [(name, C.c_double) for name in ("lines_kernels_s", "scan_kernel_s", "compact_kernels_s", "sort_kernels_s", "match_kernel_s",
+                                                "plan_kernels_s", "upload_s", "download_s", "host_s", "total_s")]
+
+
 class _BamSortTimes(C.Structure):
     """include/svtyper_reads.h: svt_bam_sort_times"""
     _fields_ = [("keys_kernel_s", C.c_double), ("histogram_kernel_s", C.c_double), ("scan_kernel_s", C.c_double),
@@ -338,6 +350,14 @@ def _lib():
             L.svt_vcf_paste_last_times.argtypes = [C.POINTER(_PasteTimes)]
         for rule in (_CLASSIFY, _UPDATE_INFO):      # (likewise: the rules over the lines of a cohort VCF)
             rule.declare(L)
+        if hasattr(L, "svt_vcf_group_host"):       # (likewise: BND mates grouped in front of the paste)
+            P, U64, U32 = C.c_void_p, C.c_uint64, C.c_uint32
+            host = [P, U64, U32, P, U64, P, U64, P, P, P, C.POINTER(_GroupReport)]
+            for name, argtypes in (("svt_vcf_group_host", host), ("svt_vcf_group_device", host + [U32, C.c_int]),
+                                   ("svt_vcf_group_write", [P, U64, U32, P, U64, P, U64, P, U64, P, U64, P, C.POINTER(_GroupReport)]),
+                                   ("svt_vcf_group_take", [P, U64]), ("svt_vcf_group_last_times", [C.POINTER(_GroupTimes)])):
+                getattr(L, name).restype = C.c_int
+                getattr(L, name).argtypes = argtypes
         if hasattr(L, "svt_bam_spans_host"):       # (likewise: BAM records as spans, the sorted and indexed `-w` dump)
             P, U64, I32 = C.c_void_p, C.c_uint64, C.c_int32
             for name, argtypes in (("svt_bam_spans_host", [P, U64, P, U64, I32, P, P, P]), ("svt_bam_spans_device", [P, U64, P, U64, I32, P, P, P, C.c_int]),
@@ -1158,6 +1178,73 @@ def vcf_update_info_last_times() -> Dict[str, float]:
     """svt_vcf_update_info_last_times: the kernels of this thread's last svt_vcf_update_info_device from HIP events, its copies on the
     host's clock"""
     return _UPDATE_INFO.last_times()
+
+
+GROUP_LINE = np.dtype([("off", np.uint64), ("len", np.uint32), ("id_b", np.uint32), ("id_n", np.uint32), ("mate_b", np.uint32),
+                       ("mate_n", np.uint32), ("flags", np.uint32), ("slow", np.uint32), ("bad", np.uint32)])     # svt_group_line
+GROUP_OUT = np.dtype([("line", np.uint32), ("source", np.uint32)])                                                 # svt_group_out
+GROUP_BND, GROUP_HAS_MATE, GROUP_CI = 1, 2, 4
+GROUP_SLOW_HEAD, GROUP_SLOW_FORMAT, GROUP_SLOW_BARE, GROUP_SLOW_TOKEN, GROUP_SLOW_ALT = 1, 2, 4, 8, 16
+GROUP_SLOW = 31
+(GROUP_BAD_COLUMNS, GROUP_BAD_POS, GROUP_BAD_QUAL, GROUP_BAD_FORMAT, GROUP_BAD_KEY, GROUP_BAD_NUMBER, GROUP_BAD_BARE, GROUP_BAD_ALT,
+ GROUP_BAD_EIGHT) = 1, 2, 3, 4, 5, 6, 7, 8, 9
+GROUP_KEYS = ("SVTYPE", "MATEID", "END", "CIPOS", "CIEND")
+
+
+def _group_lib():
+    L = _lib()
+    if not hasattr(L, "svt_vcf_group_host"):
+        raise hip.SvtyperHipError("this libsvtyper_hip.so has no svt_vcf_group_host (built before svtyper_amd.group_multiline)")
+    return L
+
+
+def _group_report(info) -> dict:
+    report = {name: int(getattr(info, name)) for name, _ in _GroupReport._fields_ if name != "bad_text"}
+    report["bad_text"] = bytes(info.bad_text).decode("utf-8", "surrogateescape")
+    return report
+
+
+def vcf_group(text: bytes, n_samples: int, format_table: bytes, device: Optional[int] = None, hash_bits: int = 64):
+    """svt_vcf_group_host (device None) / _device over the WHOLE body: (lines GROUP_LINE, one per line, plan GROUP_OUT in output
+    order, report).  report: host_lines, host_join, n_bnd and, where the script dies on a line, bad_line (1-based), bad_kind,
+    bad_text; the plan then ends in front of that line"""
+    L = _group_lib()
+    buf, fmt = _text_array(text), _text_array(format_table)
+    capacity = text.count(b"\n") + 1
+    lines = np.zeros(capacity, GROUP_LINE)
+    plan = np.zeros(2 * capacity, GROUP_OUT)
+    n_lines, n_plan = C.c_uint64(0), C.c_uint64(0)
+    info = _GroupReport()
+    args = [buf.ctypes.data, len(text), int(n_samples), fmt.ctypes.data, len(format_table), lines.ctypes.data, capacity, C.addressof(n_lines),
+            plan.ctypes.data, C.addressof(n_plan), C.byref(info)]
+    if device is None:
+        hip._check(L.svt_vcf_group_host(*args))
+    else:
+        hip._check(L.svt_vcf_group_device(*args, int(hash_bits), int(device)))
+    return lines[:n_lines.value], plan[:n_plan.value], _group_report(info)
+
+
+def vcf_group_write(text: bytes, n_samples: int, info_table: bytes, format_table: bytes, lines: np.ndarray, plan: np.ndarray):
+    """svt_vcf_group_write + _take: (the output text of the plan, out_off [entries + 1], report)"""
+    L = _group_lib()
+    buf, inf, fmt = _text_array(text), _text_array(info_table), _text_array(format_table)
+    lines = np.ascontiguousarray(lines, GROUP_LINE)
+    plan = np.ascontiguousarray(plan, GROUP_OUT)
+    out_off = np.zeros(plan.shape[0] + 1, np.uint64)
+    info = _GroupReport()
+    hip._check(L.svt_vcf_group_write(buf.ctypes.data, len(text), int(n_samples), inf.ctypes.data, len(info_table), fmt.ctypes.data, len(format_table),
+                                     lines.ctypes.data if lines.shape[0] else None, lines.shape[0],
+                                     plan.ctypes.data if plan.shape[0] else None, plan.shape[0], out_off.ctypes.data, C.byref(info)))
+    out = np.empty(max(info.out_len, 1), np.uint8)
+    hip._check(L.svt_vcf_group_take(out.ctypes.data, info.out_len))
+    return out[:info.out_len].tobytes(), out_off, _group_report(info)
+
+
+def vcf_group_last_times() -> Dict[str, float]:
+    """svt_vcf_group_last_times: the kernels of this thread's last svt_vcf_group_device from HIP events, its copies on the host's clock"""
+    t = _GroupTimes()
+    hip._check(_group_lib().svt_vcf_group_last_times(C.byref(t)))
+    return {name: float(getattr(t, name)) for name, _ in _GroupTimes._fields_}
 
 
 def tbx_build(text: bytes, lines: np.ndarray, member_off, src_off=None, payload: int = DEFLATE_MAX_PAYLOAD, csi: bool = False):
