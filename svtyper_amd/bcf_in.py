@@ -7,7 +7,7 @@
 The BGZF members are inflated on the host by the library's member code, every CRC-32 checked; the stream's header and record
 chain are read on the host; the records become lines in the native library (include/svtyper_bcf.h: svt_bcf_text_host, or
 svt_bcf_text_device -- one wavefront per record, lanes over samples; the same text, byte for byte) in chunks of at most
-`block_bytes` of stream (None: paste.BLOCK_BYTES["device"], on either engine).  The text is the header without its ,IDX=n attributes, then one line
+`block_bytes` of stream (None: cohort.BLOCK_BYTES["device"], on either engine).  The text is the header without its ,IDX=n attributes, then one line
 per record in the format of DESIGN 3.4: what `bcftools view` is understood to print; byte equality with htslib is not claimed,
 nothing here has htslib.  The CLI stands where `bcftools view` stood between the cohort steps; with the output options of the
 other programs, `--bgzf --sort --tabix -o x.vcf.gz` converts a BCF in one run.
@@ -26,6 +26,7 @@ import numpy as np
 
 from . import hip
 from . import native_reads as nr
+from .cohort import BLOCK_BYTES, _text, add_program_arguments, parse_program_arguments, run_program
 
 MAGIC = b"BCF\2\2"
 _WHAT = {"truncated": "the record runs out of the stream, or its l_shared is below 24",
@@ -101,7 +102,6 @@ def _inflate(name: str, data: bytes) -> bytes:
 
 def decode(name: str, data: bytes, engine="host", device=0, block_bytes=None, stats: Optional[dict] = None) -> bytes:
     """the VCF text of the BCF file `data` (its BGZF bytes); `name` is what errors call it"""
-    from .paste import BLOCK_BYTES
     if engine not in ("host", "device"):
         raise ValueError("engine is 'host' or 'device'")
     if block_bytes is None:
@@ -142,40 +142,21 @@ def open_text(path_or_file, engine="host", device=0, block_bytes=None, stats: Op
 
 # ------------------------------------------------------------------------------------------ CLI
 def get_args(argv=None):
-    from .driver import add_output_arguments, check_output_arguments
     p = argparse.ArgumentParser(prog="svtyper-bcf-in", formatter_class=argparse.RawTextHelpFormatter, description=(
         "svtyper-bcf-in\ndescription: Write a BCF file as VCF text"))
     p.add_argument(metavar="bcf", dest="bcf_in", nargs="?", type=str, default=None, help="BCF input (default: stdin)")
-    p.add_argument("-o", "--output_vcf", metavar="FILE", type=argparse.FileType("w"), default=sys.stdout,
-                   help="output VCF to write (default: stdout)")
-    p.add_argument("--engine", choices=("host", "device"), default="host",
-                   help="where the records become lines: the native host code or the GPU (same output bytes) [host]")
-    p.add_argument("--device", metavar="INT", type=int, default=0, help="the GPU of --engine device and --deflate device [0]")
-    add_output_arguments(p)
-    args = p.parse_args(argv)
-    check_output_arguments(p, args, args.output_vcf)
-    if args.bcf_in is None and sys.stdin.isatty():
-        p.print_help()
-        sys.exit(1)
-    return args
+    add_program_arguments(p, "where the records become lines: the native host code or the GPU (same output bytes) [host]", keep_contigs_help=None)
+    return parse_program_arguments(p, argv, "bcf_in")
 
 
 def main(argv=None):
-    from .driver import _bgzf_text
-    from .paste import _text
     args = get_args(argv)
     try:
         f = open_text(args.bcf_in if args.bcf_in is not None else sys.stdin.buffer, engine=args.engine, device=args.device)
     except (BcfInputError, OSError) as e:
         sys.stderr.write("Error: %s\n" % e)
         return 1
-    if args.bgzf or args.bcf:
-        with _bgzf_text(args.output_vcf, args.deflate, args.device, args.huffman, args) as out:
-            out.write(_text(f.getvalue()))
-    else:
-        args.output_vcf.write(_text(f.getvalue()))
-        args.output_vcf.flush()
-    return 0
+    return run_program(args, (), lambda out: out.write(_text(f.getvalue())))     # (the input's errors are all met: none is caught here)
 
 
 def cli():

@@ -37,12 +37,11 @@ from typing import Optional
 import numpy as np
 
 from . import native_reads as nr
-from .cohort import blocks, chrom_lines, finish_block, header_text, read_header
+from .cohort import (FORMAT_MESSAGE, _text, add_program_arguments, bad_line, begin_body, blocks, chrom_lines, finish_block, format_table,
+                     header_attributes, info_table, parse_program_arguments, run_options, run_program, run_stats)
 from .cohort import bytes_lines as _bytes_lines
 from .cohort import open_source as _open
-from .paste import BLOCK_BYTES, _text, declared_lines, header_attributes, info_table
 
-FORMAT_MESSAGE = '\nError: invalid FORMAT field, "%s"\n'
 # the script's exception and what to say for each way a line can end the run (native_reads.CLASSIFY_BAD_*)
 _KINDS = {nr.CLASSIFY_BAD_COLUMNS: ("IndexError", "fewer than eight columns"),
           nr.CLASSIFY_BAD_POS: ("ValueError", "a POS that is no integer: %(text)s"),
@@ -52,6 +51,7 @@ _KINDS = {nr.CLASSIFY_BAD_COLUMNS: ("IndexError", "fewer than eight columns"),
           nr.CLASSIFY_BAD_NUMBER: ("ValueError", "%(where)s has a CN or AB that is no number: %(text)s"),
           nr.CLASSIFY_BAD_NONFINITE: (None, "%(where)s has a CN or AB that is not finite: %(text)s"),
           nr.CLASSIFY_BAD_GENDER: ("KeyError", "%(where)s is not in the gender file")}
+_VERBATIM = {nr.CLASSIFY_BAD_FORMAT: lambda text: FORMAT_MESSAGE % text}
 
 
 class ClassifyError(Exception):
@@ -63,11 +63,7 @@ class ClassifyError(Exception):
         self.file, self.line, self.reference, self.verbatim = file, line, reference, verbatim
 
 
-def _bad(name, line, kind, text="", sample=None):
-    reference, what = _KINDS[kind]
-    where = "the line" if sample is None else "sample %s" % sample
-    return ClassifyError("%s, line %d: %s" % (name, line, what % dict(text=text, where=where)), name, line, reference,
-                         FORMAT_MESSAGE % text if kind == nr.CLASSIFY_BAD_FORMAT else None)
+_bad = bad_line(ClassifyError, _KINDS, _VERBATIM)
 
 
 def read_genders(source):
@@ -268,15 +264,8 @@ def classify(vcf_in, gender, exclude=None, annotation=None, f_overlap=0.9, slope
     lines, blocks, host_lines (the lines the host's plain C++ decided), near_lines (the lines whose r2 or slope lies within 1e-9 of
     its threshold), results (the per-line records of every block, native_reads.CLASSIFY_LINE) and, for engine="device", times (the
     sums of vcf_classify_last_times)."""
-    if engine not in ("host", "device"):
-        raise ValueError("engine is 'host' or 'device'")
-    if block_bytes is None:
-        block_bytes = BLOCK_BYTES[engine]
-    if block_bytes < 1:
-        raise ValueError("block_bytes is at least 1")
-    if stats is None:
-        stats = {}
-    stats.update(lines=0, blocks=0, host_lines=0, near_lines=0, results=[], times={})
+    block_bytes = run_options(engine, block_bytes)
+    stats = run_stats(stats, lines=0, blocks=0, host_lines=0, near_lines=0, results=[], times={})
     genders, excluded = read_genders(gender), set(read_excluded(exclude))
     elements = read_annotation(annotation) if annotation is not None else None
     name, f, own = _open(vcf_in, engine=engine, device=device)
@@ -288,22 +277,23 @@ def classify(vcf_in, gender, exclude=None, annotation=None, f_overlap=0.9, slope
             f.close()
 
 
+def header_tables(header):
+    """what the output header is made of, from the input's header lines: (fileformat, reference, the INFO, ALT and FORMAT tables, the
+    samples of the last line that begins with one '#' alone: none without such a line)"""
+    file_format, reference, _filters, infos, alts, formats = header_attributes([h.rstrip("\n") for h in header if h.startswith("##")], ClassifyError)
+    return file_format, reference, infos, alts, formats, ([""] + chrom_lines(header))[-1].rstrip().split("\t")[9:]
+
+
 def _run(name, lines, genders, excluded, elements, f_overlap, slope_threshold, rsquared_threshold, vcf_out, device, file_date, block_bytes, stats,
          keep_contigs):
-    header, first = read_header(lines)
-    if first is None:                               # (the header is written when the first body line is met)
+    body = begin_body(name, lines, vcf_out, file_date, keep_contigs, header_tables, None, with_format=True)
+    if body is None:
         return
-    file_format, reference, _filters, infos, alts, formats = header_attributes([h.rstrip("\n") for h in header if h.startswith("##")], ClassifyError)
-    samples = []
-    for h in chrom_lines(header):
-        samples = h.rstrip().split("\t")[9:]
-    vcf_out.write(header_text(file_format, file_date, reference, declared_lines(infos, alts, formats), header, samples, keep_contigs))
+    done, first, samples, infos, formats = body                 # done: lines of the file in front of the block
+    info_bytes, format_bytes = info_table(infos), format_table(formats)
     male = np.array([1 if genders.get(s) == 1 else nr.CLASSIFY_NO_GENDER if s not in genders else 0 for s in samples], np.uint8)
     female = np.array([1 if genders.get(s) == 2 else nr.CLASSIFY_NO_GENDER if s not in genders else 0 for s in samples], np.uint8)
     skipped = np.array([s in excluded for s in samples], np.uint8)
-    info_bytes = info_table(infos)
-    format_bytes = "".join(i + "\n" for i, _, _, _ in formats).encode("utf-8", "surrogateescape")
-    done = len(header)                              # lines of the file in front of the block
     for block in blocks(first, lines, block_bytes):
         bare = not block[-1].endswith(b"\n")        # (the file's last line: rewritten lines end in a newline all the same)
         text = b"".join(block) + (b"\n" if bare else b"")
@@ -337,7 +327,6 @@ def _run(name, lines, genders, excluded, elements, f_overlap, slope_threshold, r
 
 # ------------------------------------------------------------------------------------------ CLI
 def get_args(argv=None):
-    from .driver import add_output_arguments, check_output_arguments
     p = argparse.ArgumentParser(prog="svtyper-classify", formatter_class=argparse.RawTextHelpFormatter, description=(
         "svtyper-classify\ndescription: classify structural variants by read-depth support"))
     p.add_argument("-i", "--input", metavar="VCF", dest="vcf_in", type=str, default=None, help="VCF input, .gz through gzip [stdin]")
@@ -350,39 +339,16 @@ def get_args(argv=None):
                    help="minimum slope absolute value of regression line to classify as DEL or DUP [1.0]")
     p.add_argument("-r", "--rsquared_threshold", metavar="FLOAT", type=float, default=0.2,
                    help="minimum R^2 correlation value of regression line to classify as DEL or DUP [0.2]")
-    p.add_argument("--keep-contigs", dest="keep_contigs", action="store_true",
-                   help="keep the input's ##contig lines, directly before the #CHROM line")
-    p.add_argument("-o", "--output_vcf", metavar="FILE", type=argparse.FileType("w"), default=sys.stdout,
-                   help="output VCF to write (default: stdout)")
-    p.add_argument("--engine", choices=("host", "device"), default="host",
-                   help="where the lines are tested: the native host code or the GPU (same output bytes) [host]")
-    p.add_argument("--device", metavar="INT", type=int, default=0, help="the GPU of --engine device and --deflate device [0]")
-    add_output_arguments(p)
-    args = p.parse_args(argv)
-    check_output_arguments(p, args, args.output_vcf)
-    if args.vcf_in is None and sys.stdin.isatty():
-        p.print_help()
-        sys.exit(1)
-    return args
+    add_program_arguments(p, "where the lines are tested: the native host code or the GPU (same output bytes) [host]")
+    return parse_program_arguments(p, argv, "vcf_in")
 
 
 def main(argv=None):
-    from .driver import _bgzf_text
     args = get_args(argv)
     call = dict(exclude=args.exclude, annotation=args.annotation, f_overlap=args.f_overlap, slope_threshold=args.slope_threshold,
                 rsquared_threshold=args.rsquared_threshold, engine=args.engine, device=args.device, keep_contigs=args.keep_contigs)
     vcf_in = args.vcf_in if args.vcf_in is not None else sys.stdin.buffer
-    try:
-        if args.bgzf or args.bcf:
-            with _bgzf_text(args.output_vcf, args.deflate, args.device, args.huffman, args) as out:
-                classify(vcf_in, args.gender, vcf_out=out, **call)
-        else:
-            classify(vcf_in, args.gender, vcf_out=args.output_vcf, **call)
-            args.output_vcf.flush()
-    except ClassifyError as e:
-        sys.stderr.write(e.verbatim if e.verbatim is not None else "Error: %s\n" % e)
-        return 1
-    return 0
+    return run_program(args, ClassifyError, lambda out: classify(vcf_in, args.gender, vcf_out=out, **call))
 
 
 def cli():

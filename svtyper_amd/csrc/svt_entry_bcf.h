@@ -69,7 +69,7 @@ static int stream_resident(BcfCall& c, const uint8_t* text, uint64_t len, uint32
     bcf::Dict d;
     std::vector<bcf::Measure> m(n);
     // (one-wave workgroups: four where the line kernels have one of 256)
-    const unsigned grid = (unsigned)std::max<uint64_t>(std::min<uint64_t>((n + kBcfBlock - 1) / kBcfBlock, (uint64_t)std::max<uint32_t>(cu_count(device), 1) * 32), 1);
+    const unsigned grid = capped_grid((n + kBcfBlock - 1) / kBcfBlock, 32, device);
     size_t e[4] = {};
     if (n) {
         SVT_TRY(upload_dict(c, t, d));

@@ -96,8 +96,7 @@ static int svt_bcf_text_device_impl(const uint8_t* stream, uint64_t len, uint32_
         const uint8_t* chunk = stream + chain[from];
         rec_off.resize(k + 1);
         for (uint64_t j = 0; j <= k; ++j) rec_off[j] = chain[from + j] - chain[from];
-        const unsigned grid = (unsigned)std::max<uint64_t>(
-            std::min<uint64_t>((k + kBcfTextWaves - 1) / kBcfTextWaves, (uint64_t)std::max<uint32_t>(cu_count(device), 1) * 8), 1);
+        const unsigned grid = capped_grid((k + kBcfTextWaves - 1) / kBcfTextWaves, 8, device);
         size_t e[8] = {};
         SVT_TRY(c.mark(&e[0]));
         SVT_TRY(h2d_staged(c.d_stream.p, chunk, bytes, c.s));

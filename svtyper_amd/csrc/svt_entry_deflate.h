@@ -111,11 +111,14 @@ struct OrderedCall : DeflateCall {                           // (destruction ord
     }
 };
 
-static unsigned lines_grid(uint64_t work_groups, int device)
+// a grid of `work` workgroups, at most `per_cu` for each of the device's compute units and at least one
+static unsigned capped_grid(uint64_t work, uint32_t per_cu, int device)
 {
-    const uint64_t most = (uint64_t)std::max<uint32_t>(cu_count(device), 1) * 8;
-    return (unsigned)std::max<uint64_t>(std::min(work_groups, most), 1);
+    const uint64_t most = (uint64_t)std::max<uint32_t>(cu_count(device), 1) * per_cu;
+    return (unsigned)std::max<uint64_t>(std::min(work, most), 1);
 }
+
+static unsigned lines_grid(uint64_t work_groups, int device) { return capped_grid(work_groups, 8, device); }
 
 // the rows perm[0 .. dst_off.size()) of d_src[0, len) (table d_table, n rows) side by side in d_dst[0, out_len), row perm[j] at
 // dst_off[j]; the kernel's seconds are added to *kernel_s.  d_src, d_table and d_dst are device memory that c.s has filled

@@ -1,7 +1,7 @@
 // svt_entry_vcf_group.h -- part of the single translation unit svtyper_hip.hip (included there, in order, behind
 // svt_entry_radix_sort.h; not a stand-alone header): BND mates grouped on the device.  One call: the text and the FORMAT table go
-// up once, the line table is made (lines_resident), svt_group_scan_kernel writes the records, the BND lines are compacted by a
-// scan and their (ID hash, line) pairs go through the call's RadixSort (svt_entry_radix_sort.h: the one sort, not a copy of it),
+// up once and the line table is made (cohort_begin, svt_entry_vcf_cohort.h), svt_group_scan_kernel writes the records, the BND
+// lines are compacted by a scan and their (ID hash, line) pairs go through the call's RadixSort (svt_entry_radix_sort.h: the one sort, not a copy of it),
 // svt_group_match_kernel joins, and for a regular file without marked lines a second scan and svt_group_plan_kernel write the
 // plan: the records and the plan come down.  Any marked line, or a file that is not regular: only the records come down and
 // group::join, the host twin's, finishes (report->host_join).  C ABI: svt_vcf_group_device, svt_vcf_group_last_times
@@ -11,8 +11,8 @@ extern "C++" {
 
 static thread_local svt_vcf_group_times g_group_times;
 
-struct GroupCall : LinesCall {                               // (destruction order: CallStream, svt_batch_state.h)
-    DevScratch d_table, d_records, d_bnd, d_emit, d_mate, d_status, d_plan;
+struct GroupCall : CohortCall {                              // (d_tables: the FORMAT table, d_results: the records; destruction order: CallStream)
+    DevScratch d_bnd, d_emit, d_mate, d_status, d_plan;
     RadixSort sort;                                          // (a member, so freed behind drain())
     ~GroupCall() { drain(); }
 };
@@ -29,24 +29,14 @@ static int svt_vcf_group_device_impl(const uint8_t* text, uint64_t len, uint32_t
     if (const char* why = group::take_arguments(text, len, n_samples, format_table, format_len, lines, n_lines, plan, n_plan, report, b))
         return fail(SVT_ERR_INVALID, why);
     if (hash_bits < 1 || hash_bits > 64) return fail(SVT_ERR_INVALID, "svt_vcf_group: hash_bits is 1..64");
-    *n_lines = *n_plan = 0;
-    SVT_TRY(select_device(device));
-    if (!len) return SVT_OK;
+    *n_plan = 0;
     GroupCall c;
-    auto t = std::chrono::steady_clock::now();
-    SVT_TRY(c.begin(text, len));
-    SVT_TRY(c.d_table.alloc(format_len));
-    SVT_TRY(h2d_staged(c.d_table.p, format_table, format_len, c.s));
-    HIP_TRY(hipStreamSynchronize(c.s));
-    times.upload_s = seconds_since(t);
     std::vector<svt_tbx_line> table;
-    SVT_TRY(lines_resident(c, len, text[len - 1], table, device));
-    times.lines_kernels_s = g_lines_times.count_kernel_s + g_lines_times.starts_kernel_s + g_lines_times.parse_kernel_s;
+    SVT_TRY(cohort_begin(c, b, format_table, format_len, table, capacity, n_lines, device, times));
+    if (table.empty()) return SVT_OK;
     const uint64_t n = table.size(), mask = bfr::hash_mask(hash_bits);
-    *n_lines = n;
-    if (n > capacity) return fail(SVT_ERR_INVALID, "svt_vcf_group: capacity is below the number of lines");
     if (n >> 31) return fail(SVT_ERR_INVALID, "svt_vcf_group: too many lines in one call (< 2^31)");
-    SVT_TRY(c.d_records.alloc(n * sizeof(svt_group_line)));
+    SVT_TRY(c.d_results.alloc(n * sizeof(svt_group_line)));
     SVT_TRY(c.d_bnd.alloc((n + 1) * sizeof(uint32_t)));
     SVT_TRY(c.d_emit.alloc((n + 1) * sizeof(uint32_t)));
     SVT_TRY(c.d_mate.alloc(n * sizeof(uint32_t)));
@@ -60,7 +50,7 @@ static int svt_vcf_group_device_impl(const uint8_t* text, uint64_t len, uint32_t
     size_t e[9] = {};
     SVT_TRY(c.mark(&e[0]));
     hipLaunchKernelGGL(svt_group_scan_kernel, dim3(grid), dim3(kSortBlock), 0, c.s, c.d_stream.as<uint8_t>(), len, c.d_lines.as<svt_tbx_line>(), n,
-                       c.d_table.as<uint8_t>(), (uint32_t)format_len, c.d_records.as<svt_group_line>(), c.d_bnd.as<uint32_t>(), c.d_emit.as<uint32_t>(),
+                       c.d_tables.as<uint8_t>(), (uint32_t)format_len, c.d_results.as<svt_group_line>(), c.d_bnd.as<uint32_t>(), c.d_emit.as<uint32_t>(),
                        c.d_status.as<GroupStatus>());
     HIP_TRY(hipGetLastError());
     SVT_TRY(c.mark(&e[1]));
@@ -80,7 +70,7 @@ static int svt_vcf_group_device_impl(const uint8_t* text, uint64_t len, uint32_t
         SVT_TRY(c.sort.key_grid(n_bnd, n, device, &key_grid));      // (n_bnd pairs from a key kernel that walks the n lines)
         SVT_TRY(c.mark(&e[3]));
         hipLaunchKernelGGL(svt_group_compact_kernel, dim3(key_grid), dim3(kSortBlock), 0, c.s, c.d_stream.as<uint8_t>(), len,
-                           c.d_records.as<svt_group_line>(), n, c.d_bnd.as<uint32_t>(), (uint64_t)n_bnd, mask, c.sort.keys(), c.sort.idx(),
+                           c.d_results.as<svt_group_line>(), n, c.d_bnd.as<uint32_t>(), (uint64_t)n_bnd, mask, c.sort.keys(), c.sort.idx(),
                            c.sort.part_and(), c.sort.part_or());
         HIP_TRY(hipGetLastError());
         SVT_TRY(c.mark(&e[4]));
@@ -89,7 +79,7 @@ static int svt_vcf_group_device_impl(const uint8_t* text, uint64_t len, uint32_t
         SVT_TRY(c.sort.passes(c, device));
         SVT_TRY(c.mark(&e[5]));
         hipLaunchKernelGGL(svt_group_match_kernel, dim3(lines_grid((n_bnd + kSortBlock - 1) / kSortBlock, device)), dim3(kSortBlock), 0, c.s,
-                           c.d_stream.as<uint8_t>(), len, c.d_records.as<svt_group_line>(), n, c.sort.sorted_keys(), c.sort.sorted_idx(), (uint64_t)n_bnd,
+                           c.d_stream.as<uint8_t>(), len, c.d_results.as<svt_group_line>(), n, c.sort.sorted_keys(), c.sort.sorted_idx(), (uint64_t)n_bnd,
                            mask, c.d_emit.as<uint32_t>(), c.d_mate.as<uint32_t>(), c.d_status.as<GroupStatus>());
         HIP_TRY(hipGetLastError());
         SVT_TRY(c.mark(&e[6]));
@@ -100,8 +90,8 @@ static int svt_vcf_group_device_impl(const uint8_t* text, uint64_t len, uint32_t
         on_device = !status.irregular;
     }
     if (!on_device) {                               // the records alone: the host twin's join finishes
-        t = std::chrono::steady_clock::now();
-        SVT_TRY(d2h_staged(lines, c.d_records.p, n * sizeof(svt_group_line), c.s));
+        auto t = std::chrono::steady_clock::now();
+        SVT_TRY(d2h_staged(lines, c.d_results.p, n * sizeof(svt_group_line), c.s));
         times.download_s = seconds_since(t);
         t = std::chrono::steady_clock::now();
         if (!group::records_inside(b, lines, n)) return fail(SVT_ERR_HIP, "svt_group_scan_kernel: a record's line is not inside the text");
@@ -124,8 +114,8 @@ static int svt_vcf_group_device_impl(const uint8_t* text, uint64_t len, uint32_t
     SVT_TRY(d2h_staged(&total, c.d_emit.as<uint32_t>() + fatal, sizeof total, c.s));
     SVT_TRY(c.between(e[7], e[8], &times.plan_kernels_s));
     if (total > 2 * n) return fail(SVT_ERR_HIP, "svt_group_plan_kernel: more entries than twice the lines");
-    t = std::chrono::steady_clock::now();
-    SVT_TRY(d2h_staged(lines, c.d_records.p, n * sizeof(svt_group_line), c.s));
+    auto t = std::chrono::steady_clock::now();
+    SVT_TRY(d2h_staged(lines, c.d_results.p, n * sizeof(svt_group_line), c.s));
     if (total) SVT_TRY(d2h_staged(plan, c.d_plan.p, total * sizeof(svt_group_out), c.s));
     times.download_s = seconds_since(t);
     t = std::chrono::steady_clock::now();

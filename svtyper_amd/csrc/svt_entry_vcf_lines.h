@@ -12,6 +12,9 @@ extern "C++" {
 // the kernels of the calling thread's last call here, from HIP events, and the call's wall time
 static thread_local svt_vcf_lines_times g_lines_times;
 
+// what lines_resident's three kernels took together: the lines_kernels_s of the calls that make their line table with it
+static double lines_kernels_s() { return g_lines_times.count_kernel_s + g_lines_times.starts_kernel_s + g_lines_times.parse_kernel_s; }
+
 struct LinesCall : OrderedCall {                             // (svt_entry_deflate.h; destruction order: CallStream, svt_batch_state.h)
     DevScratch d_counts, d_base, d_lines;
     ~LinesCall() { drain(); }

@@ -40,7 +40,7 @@ static int svt_vcf_paste_device_impl(const uint8_t* text, uint64_t len, const ui
     g_paste_times.upload_s = seconds_since(t);
     std::vector<svt_tbx_line> table;
     SVT_TRY(lines_resident(c, len, text[len - 1], table, device));
-    g_paste_times.lines_kernels_s = g_lines_times.count_kernel_s + g_lines_times.starts_kernel_s + g_lines_times.parse_kernel_s;
+    g_paste_times.lines_kernels_s = lines_kernels_s();
     b.lines = table.data();
     b.n_table = table.size();
     if (const char* why = paste::check_block(b)) return fail(SVT_ERR_INVALID, why);
@@ -49,7 +49,7 @@ static int svt_vcf_paste_device_impl(const uint8_t* text, uint64_t len, const ui
     SVT_TRY(h2d_staged(c.d_first.p, first_line, ((uint64_t)n_inputs + 1) * sizeof(uint64_t), c.s));
     SVT_TRY(c.d_results.alloc(n_lines * sizeof(svt_paste_line)));
     SVT_TRY(c.d_places.alloc(cells * sizeof(paste::Place)));
-    const unsigned grid = (unsigned)std::max<uint64_t>(std::min<uint64_t>((n_lines + kPasteWaves - 1) / kPasteWaves, (uint64_t)std::max<uint32_t>(cu_count(device), 1) * 16), 1);
+    const unsigned grid = capped_grid((n_lines + kPasteWaves - 1) / kPasteWaves, 16, device);
     size_t e[4] = {};
     SVT_TRY(c.mark(&e[0]));
     hipLaunchKernelGGL(svt_paste_measure_kernel, dim3(grid), dim3(kPasteBlock), 0, c.s, c.d_stream.as<uint8_t>(), len, c.d_lines.as<svt_tbx_line>(),

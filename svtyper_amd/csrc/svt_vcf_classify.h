@@ -243,6 +243,8 @@ struct Block : cohort::Block {
     static constexpr const char* kName = "svt_vcf_classify";
     static constexpr const char* kCapacityWhy = "svt_vcf_classify: capacity is below the number of lines";
     static constexpr const char* kWriteWhy = "svt_vcf_classify_write: one record per line of the text";
+    static constexpr const char* kLengthWhy = "svt_vcf_classify: a block holds less than 2^31 bytes";
+    static constexpr const char* kFormatWhy = "svt_vcf_classify: format_table is \"<id>\\n\" per id, GT first";
     const uint8_t *male = nullptr, *female = nullptr, *excluded = nullptr, *skip = nullptr;
     Params pr = Params();
     bool is_male(uint32_t s) const { return male[s] == 1; }
@@ -529,23 +531,16 @@ inline const char* take_arguments(const uint8_t* text, uint64_t len, uint32_t n_
                                   double slope_threshold, double rsquared_threshold, const svt_classify_line* results, const uint64_t* n_lines,
                                   svt_classify_info* info, Block& b)
 {
-    if (!info || !n_lines || !results || (len && !text) || !format_table || (n_samples && (!male || !female || !excluded))) return "null argument";
-    *info = svt_classify_info();
-    if (len > cohort::kMaxLine) return "svt_vcf_classify: a block holds less than 2^31 bytes";
-    if (format_len > 0xFFFFu || !cohort::parse_format_table(format_table, format_len, b.formats))
-        return "svt_vcf_classify: format_table is \"<id>\\n\" per id, GT first";
+    if (const char* why = cohort::take_block_arguments(text, len, n_samples, format_table, format_len,
+                                                       n_lines && results && (!n_samples || (male && female && excluded)), info, b))
+        return why;
     if (std::isnan(slope_threshold) || std::isnan(rsquared_threshold)) return "svt_vcf_classify: a threshold is a number";
-    b.text = text;
-    b.len = len;
     b.male = male;
     b.female = female;
     b.excluded = excluded;
     b.skip = skip;
-    b.format_table = format_table;
     b.pr.slope_threshold = slope_threshold;
     b.pr.rsquared_threshold = rsquared_threshold;
-    b.pr.n_samples = n_samples;
-    b.pr.format_len = (uint32_t)format_len;
     return nullptr;
 }
 

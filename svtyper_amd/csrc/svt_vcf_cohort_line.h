@@ -9,8 +9,8 @@
 //
 // Host only: the script's Variant in plain C++ (parse_variant, var_string, generic_tail), Python's float(), int() and '%0.2f',
 // and the drivers that are the same for every rule, written once over the rule's Block: rule_host, write_block and report.  A
-// rule's namespace holds its Block (derived from cohort::Block, with its name and its refusals' texts) and the functions the
-// drivers find by their arguments: check_head, fast_line, settle_block and write_line.
+// rule's namespace holds its Block (derived from cohort::Block, with its name and its refusals' texts, which take_block_arguments
+// and the entries return) and the functions the drivers find by their arguments: check_head, fast_line, settle_block and write_line.
 #ifndef SVT_VCF_COHORT_LINE_H
 #define SVT_VCF_COHORT_LINE_H
 
@@ -273,8 +273,10 @@ struct Bad {
 constexpr uint32_t kBadColumns = 1, kBadPos = 2, kBadQual = 3, kBadFormat = 4, kBadEight = 9;
 static_assert(SVT_CLASSIFY_BAD_COLUMNS == kBadColumns && SVT_CLASSIFY_BAD_POS == kBadPos && SVT_CLASSIFY_BAD_QUAL == kBadQual &&
                   SVT_CLASSIFY_BAD_FORMAT == kBadFormat && SVT_UPDATE_INFO_BAD_COLUMNS == kBadColumns && SVT_UPDATE_INFO_BAD_POS == kBadPos &&
-                  SVT_UPDATE_INFO_BAD_QUAL == kBadQual && SVT_UPDATE_INFO_BAD_FORMAT == kBadFormat && SVT_UPDATE_INFO_BAD_EIGHT == kBadEight,
-              "svt_classify_info and svt_update_info_report name a line's first columns alike");
+                  SVT_UPDATE_INFO_BAD_QUAL == kBadQual && SVT_UPDATE_INFO_BAD_FORMAT == kBadFormat && SVT_UPDATE_INFO_BAD_EIGHT == kBadEight &&
+                  SVT_GROUP_BAD_COLUMNS == kBadColumns && SVT_GROUP_BAD_POS == kBadPos && SVT_GROUP_BAD_QUAL == kBadQual &&
+                  SVT_GROUP_BAD_FORMAT == kBadFormat && SVT_GROUP_BAD_EIGHT == kBadEight,
+              "svt_classify_info, svt_update_info_report and svt_group_report name a line's first columns alike");
 
 // the text under its line table, the header's FORMAT ids and (the writer) its INFO ids; a rule's Block adds its tables
 struct Block {
@@ -320,6 +322,24 @@ struct Variant {
             }
     }
 };
+
+// What every rule's take_arguments does with the text and the FORMAT table: `info` cleared and `b` filled, or what is wrong with
+// them in the rule's words (B::kLengthWhy, B::kFormatWhy).  `others`: the pointers that are the rule's alone are there
+template <class B, class Info>
+const char* take_block_arguments(const uint8_t* text, uint64_t len, uint32_t n_samples, const uint8_t* format_table, uint64_t format_len, bool others,
+                                 Info* info, B& b)
+{
+    if (!info || !others || (len && !text) || !format_table) return "null argument";
+    *info = Info();
+    if (len > kMaxLine) return B::kLengthWhy;
+    if (format_len > 0xFFFFu || !parse_format_table(format_table, format_len, b.formats)) return B::kFormatWhy;
+    b.text = text;
+    b.len = len;
+    b.format_table = format_table;
+    b.pr.n_samples = n_samples;
+    b.pr.format_len = (uint32_t)format_len;
+    return nullptr;
+}
 
 inline uint32_t format_index(const Block& b, const std::string& key)
 {

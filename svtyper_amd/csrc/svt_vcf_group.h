@@ -211,11 +211,11 @@ namespace group {
 using cohort::Bad;
 using cohort::Variant;
 
-static_assert(SVT_GROUP_BAD_COLUMNS == cohort::kBadColumns && SVT_GROUP_BAD_POS == cohort::kBadPos && SVT_GROUP_BAD_QUAL == cohort::kBadQual &&
-                  SVT_GROUP_BAD_FORMAT == cohort::kBadFormat && SVT_GROUP_BAD_EIGHT == cohort::kBadEight,
-              "svt_group_report names a line's first columns as cohort::parse_variant does");
-
 struct Block : cohort::Block {
+    static constexpr const char* kName = "svt_vcf_group";
+    static constexpr const char* kCapacityWhy = "svt_vcf_group: capacity is below the number of lines";
+    static constexpr const char* kLengthWhy = "svt_vcf_group: the body holds less than 2^31 bytes";
+    static constexpr const char* kFormatWhy = "svt_vcf_group: format_table is \"<id>\\n\" per id, GT first";
     Params pr = Params();
 };
 
@@ -225,17 +225,7 @@ inline const char* take_arguments(const uint8_t* text, uint64_t len, uint32_t n_
                                   const svt_group_line* lines, const uint64_t* n_lines, const svt_group_out* plan, const uint64_t* n_plan,
                                   svt_group_report* report, Block& b)
 {
-    if (!report || !n_lines || !n_plan || !lines || !plan || (len && !text) || !format_table) return "null argument";
-    *report = svt_group_report();
-    if (len > kMaxLine) return "svt_vcf_group: the body holds less than 2^31 bytes";
-    if (format_len > 0xFFFFu || !cohort::parse_format_table(format_table, format_len, b.formats))
-        return "svt_vcf_group: format_table is \"<id>\\n\" per id, GT first";
-    b.text = text;
-    b.len = len;
-    b.format_table = format_table;
-    b.pr.n_samples = n_samples;
-    b.pr.format_len = (uint32_t)format_len;
-    return nullptr;
+    return cohort::take_block_arguments(text, len, n_samples, format_table, format_len, n_lines && n_plan && lines && plan, report, b);
 }
 
 // what the join reads of a line: views into the text
@@ -381,7 +371,7 @@ inline const char* group_host(Block& b, svt_group_line* lines, uint64_t capacity
     tbx::lines_host(b.text, b.len, table.data());
     *n_lines = table.size();
     *n_plan = 0;
-    if (table.size() > capacity) return "svt_vcf_group: capacity is below the number of lines";
+    if (table.size() > capacity) return Block::kCapacityWhy;
     if (table.size() >> 31) return "svt_vcf_group: too many lines in one call (< 2^31)";
     for (uint64_t j = 0; j < table.size(); ++j) lines[j] = scan_line(b.text + table[j].off, table[j].off, table[j].len, b.format_table, b.pr.format_len);
     join(b, lines, table.size(), plan, n_plan, report);

@@ -154,23 +154,15 @@ struct Block : cohort::Block {
     static constexpr const char* kName = "svt_vcf_update_info";
     static constexpr const char* kCapacityWhy = "svt_vcf_update_info: capacity is below the number of lines";
     static constexpr const char* kWriteWhy = "svt_vcf_update_info_write: one record per line of the text";
+    static constexpr const char* kLengthWhy = "svt_vcf_update_info: a block holds less than 2^31 bytes";
+    static constexpr const char* kFormatWhy = "svt_vcf_update_info: format_table is \"<id>\\n\" per id, GT first";
     Params pr = Params();
 };
 
 inline const char* take_arguments(const uint8_t* text, uint64_t len, uint32_t n_samples, const uint8_t* format_table, uint64_t format_len,
                                   const svt_update_info_line* results, const uint64_t* n_lines, svt_update_info_report* info, Block& b)
 {
-    if (!info || !n_lines || !results || (len && !text) || !format_table) return "null argument";
-    *info = svt_update_info_report();
-    if (len > cohort::kMaxLine) return "svt_vcf_update_info: a block holds less than 2^31 bytes";
-    if (format_len > 0xFFFFu || !cohort::parse_format_table(format_table, format_len, b.formats))
-        return "svt_vcf_update_info: format_table is \"<id>\\n\" per id, GT first";
-    b.text = text;
-    b.len = len;
-    b.format_table = format_table;
-    b.pr.n_samples = n_samples;
-    b.pr.format_len = (uint32_t)format_len;
-    return nullptr;
+    return cohort::take_block_arguments(text, len, n_samples, format_table, format_len, n_lines && results, info, b);
 }
 
 // The host twin of svt_update_info_kernel for one line: its record, the marks the kernel would set included.  A marked line's

@@ -34,9 +34,8 @@ import time
 from typing import Optional
 
 from . import native_reads as nr
-from .cohort import bytes_lines, chrom_lines, header_text, open_source, read_header
-from .paste import add_attributes, declared_lines, header_attributes, info_table
-from .update_info import COLUMNS_MESSAGE, FORMAT_MESSAGE
+from .cohort import (COLUMNS_MESSAGE, FORMAT_MESSAGE, add_attributes, add_program_arguments, bad_line, begin_body, bytes_lines, chrom_lines,
+                     format_table, header_attributes, info_table, open_source, parse_program_arguments, run_options, run_program, run_stats)
 
 # the FORMAT lines the script declares behind the header's own, unless they are declared
 FORMATS = [("GQ", "1", "Float", "Genotype quality"),
@@ -76,10 +75,7 @@ class GroupError(Exception):
         self.file, self.line, self.token, self.reference, self.verbatim = file, line, token, reference, verbatim
 
 
-def _bad(name, line, kind, text=""):
-    reference, what = _KINDS[kind]
-    verbatim = _VERBATIM[kind](text) if kind in _VERBATIM else None
-    return GroupError("%s, line %d: %s" % (name, line, what % dict(text=text)), name, line, text or None, reference, verbatim)
+_bad = bad_line(GroupError, _KINDS, _VERBATIM, ("token",))
 
 
 def group_multiline(vcf_in, vcf_out=sys.stdout, engine="host", device=0, file_date=None, keep_contigs=False, stats: Optional[dict] = None,
@@ -89,11 +85,8 @@ def group_multiline(vcf_in, vcf_out=sys.stdout, engine="host", device=0, file_da
     line the script dies on, or all), written (output lines), host_lines (the lines the host's plain C++ decided), host_join
     (the join ran on the host: always for engine="host"), records and plan (native_reads.GROUP_LINE, GROUP_OUT) and, for
     engine="device", times (vcf_group_last_times)."""
-    if engine not in ("host", "device"):
-        raise ValueError("engine is 'host' or 'device'")
-    if stats is None:
-        stats = {}
-    stats.update(lines=0, written=0, host_lines=0, host_join=False, records=None, plan=None, times={})
+    run_options(engine)
+    stats = run_stats(stats, lines=0, written=0, host_lines=0, host_join=False, records=None, plan=None, times={})
     name, f, own = open_source(vcf_in, sniff=True, engine=engine, device=device)
     try:
         _run(name, bytes_lines(f), vcf_out, device if engine == "device" else None, file_date or time.strftime("%Y%m%d"), stats, keep_contigs,
@@ -113,17 +106,11 @@ def header_tables(header):
 
 
 def _run(name, lines, vcf_out, device, file_date, stats, keep_contigs, hash_bits):
-    header, first = read_header(lines)
-    if first is None:                               # (the header is written when the first body line is met)
+    begun = begin_body(name, lines, vcf_out, file_date, keep_contigs, header_tables, GroupError)
+    if begun is None:
         return
-    done = len(header)
-    if not chrom_lines(header):                     # (the script's sample list is never bound)
-        raise GroupError("%s, line %d: a body line and no #CHROM line in front of it" % (name, done + 1), name, done + 1, reference="UnboundLocalError")
-    file_format, reference, infos, alts, formats, samples = header_tables(header)
-    vcf_out.write(header_text(file_format, file_date, reference, declared_lines(infos, alts, formats), header, samples, keep_contigs,
-                              with_format=bool(samples)))
-    info_bytes = info_table(infos)
-    format_bytes = "".join(i + "\n" for i, _, _, _ in formats).encode("utf-8", "surrogateescape")
+    done, first, samples, infos, formats = begun
+    info_bytes, format_bytes = info_table(infos), format_table(formats)
     body = [first] + list(lines)                    # the whole body: a pair may span it
     text = b"".join(body) + (b"" if body[-1].endswith(b"\n") else b"\n")
     records, plan, report = nr.vcf_group(text, len(samples), format_bytes, device, hash_bits)
@@ -141,42 +128,18 @@ def _run(name, lines, vcf_out, device, file_date, stats, keep_contigs, hash_bits
 
 # ------------------------------------------------------------------------------------------ CLI
 def get_args(argv=None):
-    from .driver import add_output_arguments, check_output_arguments
     p = argparse.ArgumentParser(prog="svtyper-group-multiline", formatter_class=argparse.RawTextHelpFormatter, description=(
         "svtyper-group-multiline\ndescription: Group multiline variants prior vcf_paste.py"))
     p.add_argument(metavar="vcf", dest="vcf_in", nargs="?", type=str, default=None, help="VCF input, gzip where it is (default: stdin)")
-    p.add_argument("--keep-contigs", dest="keep_contigs", action="store_true",
-                   help="keep the input's ##contig lines, directly before the #CHROM line")
-    p.add_argument("-o", "--output_vcf", metavar="FILE", type=argparse.FileType("w"), default=sys.stdout,
-                   help="output VCF to write (default: stdout)")
-    p.add_argument("--engine", choices=("host", "device"), default="host",
-                   help="where the mates are joined: the native host code or the GPU (same output bytes) [host]")
-    p.add_argument("--device", metavar="INT", type=int, default=0, help="the GPU of --engine device and --deflate device [0]")
-    add_output_arguments(p)
-    args = p.parse_args(argv)
-    check_output_arguments(p, args, args.output_vcf)
-    if args.vcf_in is None and sys.stdin.isatty():
-        p.print_help()
-        sys.exit(1)
-    return args
+    add_program_arguments(p, "where the mates are joined: the native host code or the GPU (same output bytes) [host]")
+    return parse_program_arguments(p, argv, "vcf_in")
 
 
 def main(argv=None):
-    from .driver import _bgzf_text
     args = get_args(argv)
-    call = dict(engine=args.engine, device=args.device, keep_contigs=args.keep_contigs)
     vcf_in = args.vcf_in if args.vcf_in is not None else sys.stdin.buffer
-    try:
-        if args.bgzf or args.bcf:
-            with _bgzf_text(args.output_vcf, args.deflate, args.device, args.huffman, args) as out:
-                group_multiline(vcf_in, vcf_out=out, **call)
-        else:
-            group_multiline(vcf_in, vcf_out=args.output_vcf, **call)
-            args.output_vcf.flush()
-    except GroupError as e:
-        sys.stderr.write(e.verbatim if e.verbatim is not None else "Error: %s\n" % e)
-        return 1
-    return 0
+    return run_program(args, GroupError, lambda out: group_multiline(vcf_in, vcf_out=out, engine=args.engine, device=args.device,
+                                                                     keep_contigs=args.keep_contigs))
 
 
 def cli():

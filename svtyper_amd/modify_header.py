@@ -22,8 +22,8 @@ import argparse
 import sys
 import time
 
-from .cohort import bytes_lines, chrom_lines, header_text, open_source, read_header
-from .paste import _unquoted, add_attributes, declared_lines, header_attributes
+from .cohort import (_unquoted, add_attributes, bytes_lines, chrom_lines, declared_lines, header_attributes, header_text, open_source,
+                     read_header)
 
 
 class ModifyHeaderError(Exception):

@@ -314,21 +314,17 @@ def _lib():
         L.svt_bgzf_crc32_device.restype = C.c_int
         L.svt_bgzf_crc32_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_int]
         if hasattr(L, "svt_bgzf_deflate_host"):    # (added without a new ABI number: a library built before it lacks the symbols)
-            L.svt_bgzf_deflate_host.restype = C.c_int
-            L.svt_bgzf_deflate_host.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p]
-            L.svt_bgzf_deflate_device.restype = C.c_int
-            L.svt_bgzf_deflate_device.argtypes = L.svt_bgzf_deflate_host.argtypes + [C.c_int]
-            L.svt_bgzf_deflate_last_times.restype = C.c_int
-            L.svt_bgzf_deflate_last_times.argtypes = [C.POINTER(_DeflateTimes)]
+            host = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p]
+            for name, argtypes in (("svt_bgzf_deflate_host", host), ("svt_bgzf_deflate_device", host + [C.c_int]),
+                                   ("svt_bgzf_deflate_last_times", [C.POINTER(_DeflateTimes)])):
+                getattr(L, name).restype = C.c_int
+                getattr(L, name).argtypes = argtypes
         if hasattr(L, "svt_bgzf_deflate_host_mode"):   # (likewise: the dynamic block and the code-length rule on its own)
-            L.svt_bgzf_deflate_host_mode.restype = C.c_int
-            L.svt_bgzf_deflate_host_mode.argtypes = L.svt_bgzf_deflate_host.argtypes + [C.c_uint32]
-            L.svt_bgzf_deflate_device_mode.restype = C.c_int
-            L.svt_bgzf_deflate_device_mode.argtypes = L.svt_bgzf_deflate_host_mode.argtypes + [C.c_int]
-            L.svt_huffman_lengths_host.restype = C.c_int
-            L.svt_huffman_lengths_host.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
-            L.svt_huffman_lengths_device.restype = C.c_int
-            L.svt_huffman_lengths_device.argtypes = L.svt_huffman_lengths_host.argtypes + [C.c_int]
+            host, lengths = L.svt_bgzf_deflate_host.argtypes, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
+            for name, argtypes in (("svt_bgzf_deflate_host_mode", host + [C.c_uint32]), ("svt_bgzf_deflate_device_mode", host + [C.c_uint32, C.c_int]),
+                                   ("svt_huffman_lengths_host", lengths), ("svt_huffman_lengths_device", lengths + [C.c_int])):
+                getattr(L, name).restype = C.c_int
+                getattr(L, name).argtypes = argtypes
         if hasattr(L, "svt_vcf_lines_host"):       # (likewise: VCF text as lines, the sorted and indexed BGZF output)
             P, U64 = C.c_void_p, C.c_uint64
             for name, argtypes in (("svt_vcf_lines_host", [P, U64, P, U64, P]), ("svt_vcf_lines_device", [P, U64, P, U64, P, C.c_int]),
@@ -342,22 +338,13 @@ def _lib():
                 getattr(L, name).argtypes = argtypes
         if hasattr(L, "svt_vcf_paste_host"):       # (likewise: per-sample VCFs joined by line number, AF and NSAMP)
             P, U64, U32 = C.c_void_p, C.c_uint64, C.c_uint32
-            L.svt_vcf_paste_host.restype = C.c_int
-            L.svt_vcf_paste_host.argtypes = [P, U64, P, U32, U64, U32, P, U64, P, U64, P, C.POINTER(_PasteInfo)]
-            L.svt_vcf_paste_device.restype = C.c_int
-            L.svt_vcf_paste_device.argtypes = L.svt_vcf_paste_host.argtypes + [C.c_int]
-            L.svt_vcf_paste_last_times.restype = C.c_int
-            L.svt_vcf_paste_last_times.argtypes = [C.POINTER(_PasteTimes)]
-        for rule in (_CLASSIFY, _UPDATE_INFO):      # (likewise: the rules over the lines of a cohort VCF)
-            rule.declare(L)
-        if hasattr(L, "svt_vcf_group_host"):       # (likewise: BND mates grouped in front of the paste)
-            P, U64, U32 = C.c_void_p, C.c_uint64, C.c_uint32
-            host = [P, U64, U32, P, U64, P, U64, P, P, P, C.POINTER(_GroupReport)]
-            for name, argtypes in (("svt_vcf_group_host", host), ("svt_vcf_group_device", host + [U32, C.c_int]),
-                                   ("svt_vcf_group_write", [P, U64, U32, P, U64, P, U64, P, U64, P, U64, P, C.POINTER(_GroupReport)]),
-                                   ("svt_vcf_group_take", [P, U64]), ("svt_vcf_group_last_times", [C.POINTER(_GroupTimes)])):
+            host = [P, U64, P, U32, U64, U32, P, U64, P, U64, P, C.POINTER(_PasteInfo)]
+            for name, argtypes in (("svt_vcf_paste_host", host), ("svt_vcf_paste_device", host + [C.c_int]),
+                                   ("svt_vcf_paste_last_times", [C.POINTER(_PasteTimes)])):
                 getattr(L, name).restype = C.c_int
                 getattr(L, name).argtypes = argtypes
+        for rule in (_CLASSIFY, _UPDATE_INFO, _GROUP):      # (likewise: the rules over the lines of a cohort VCF, BND mates grouped)
+            rule.declare(L)
         if hasattr(L, "svt_bam_spans_host"):       # (likewise: BAM records as spans, the sorted and indexed `-w` dump)
             P, U64, I32 = C.c_void_p, C.c_uint64, C.c_int32
             for name, argtypes in (("svt_bam_spans_host", [P, U64, P, U64, I32, P, P, P]), ("svt_bam_spans_device", [P, U64, P, U64, I32, P, P, P, C.c_int]),
@@ -412,6 +399,29 @@ def _lib():
                                                     C.c_uint64, C.c_int, C.c_int, C.POINTER(_LibraryScan), C.POINTER(_LibraryScanStats)]
         _declared = True
     return L
+
+
+# the groups of entry points that came without a new ABI number, for _need: a symbol of the group and what the group came with
+_LINES = ("svt_vcf_lines_host", "sorted, indexed BGZF output")
+_PASTE = ("svt_vcf_paste_host", "svtyper_amd.paste")
+_SPANS = ("svt_bam_spans_host", "the sorted, indexed -w dump")
+_FIRST = ("svt_bam_first_host", "the gathered -w dump")
+_CSI = ("svt_csi_build_bam", "CSI indexes were written")
+
+
+def _need(symbol: str, since: str):
+    """_lib(), which has `symbol`: one of the entry points that came without a new ABI number, `since` names what they came with"""
+    L = _lib()
+    if not hasattr(L, symbol):
+        raise hip.SvtyperHipError("this libsvtyper_hip.so has no %s (built before %s)" % (symbol, since))
+    return L
+
+
+def _times(struct, entry, ints=()) -> dict:
+    """what a *_last_times entry point says: entry(&t) over a fresh `struct`, every field by its name as a float (`ints`: as an int)"""
+    t = struct()
+    hip._check(entry(C.byref(t)))
+    return {name: (int if name in ints else float)(getattr(t, name)) for name, _ in struct._fields_ if name != "reserved"}
 
 
 class NativeBam:
@@ -884,10 +894,7 @@ def huffman_lengths(freq, limit: int, device: Optional[int] = None) -> np.ndarra
 def bgzf_deflate_last_times() -> Dict[str, float]:
     """svt_bgzf_deflate_last_times: the kernels of this thread's last bgzf_deflate on a device, from HIP events, and the call's
     wall time"""
-    L = _lib()
-    t = _DeflateTimes()
-    hip._check(L.svt_bgzf_deflate_last_times(C.byref(t)))
-    return {name: float(getattr(t, name)) for name, _ in _DeflateTimes._fields_}
+    return _times(_DeflateTimes, _lib().svt_bgzf_deflate_last_times)
 
 
 # ---- VCF text as lines: the line table, the order --sort writes, the gather, the .tbi fold (include/svtyper_reads.h) ----------
@@ -897,20 +904,13 @@ TBX_META, TBX_BAD, TBX_RANGE = 1, 2, 4
 TBX_NOT_DATA, TBX_BEYOND, TBX_CONTIG_AGAIN, TBX_POS_BACK = 1, 2, 3, 4
 
 
-def _lines_lib():
-    L = _lib()
-    if not hasattr(L, "svt_vcf_lines_host"):
-        raise hip.SvtyperHipError("this libsvtyper_hip.so has no svt_vcf_lines_host (built before sorted, indexed BGZF output)")
-    return L
-
-
 def _text_array(text: bytes) -> np.ndarray:
     return np.frombuffer(text, np.uint8) if len(text) else np.zeros(1, np.uint8)
 
 
 def vcf_lines(text: bytes, device: Optional[int] = None) -> np.ndarray:
     """svt_vcf_lines_host (device None) / _device: the line table of `text`, one TBX_LINE record per line in text order"""
-    L = _lines_lib()
+    L = _need(*_LINES)
     buf = _text_array(text)
     capacity = text.count(b"\n") + 1
     lines = np.zeros(capacity, TBX_LINE)
@@ -925,7 +925,7 @@ def vcf_lines(text: bytes, device: Optional[int] = None) -> np.ndarray:
 
 def vcf_gather(text: bytes, lines: np.ndarray, perm, device: Optional[int] = None) -> bytes:
     """svt_vcf_gather_host (device None) / _device: the lines lines[perm[0]], lines[perm[1]], ... of `text` side by side"""
-    L = _lines_lib()
+    L = _need(*_LINES)
     buf = _text_array(text)
     lines = np.ascontiguousarray(lines, TBX_LINE)
     perm = np.ascontiguousarray(perm, np.uint64)
@@ -944,7 +944,7 @@ def vcf_gather(text: bytes, lines: np.ndarray, perm, device: Optional[int] = Non
 
 def vcf_sort_order(text: bytes, lines: np.ndarray) -> Tuple[np.ndarray, int]:
     """svt_vcf_sort_order: (perm, 0), or (None, the 1-based number of a body line that is no data line)"""
-    L = _lines_lib()
+    L = _need(*_LINES)
     buf = _text_array(text)
     lines = np.ascontiguousarray(lines, TBX_LINE)
     perm = np.zeros(max(lines.shape[0], 1), np.uint64)
@@ -957,7 +957,7 @@ def vcf_sort_order(text: bytes, lines: np.ndarray) -> Tuple[np.ndarray, int]:
 def vcf_bgzf_device(text: bytes, sort: bool, huffman: str = "fixed", device: int = 0):
     """svt_vcf_bgzf_device: `text` up once; (members uint8, out_off uint64 [n + 1], lines as written, src_off uint64, 0), or
     (None, None, None, None, bad_line) where sorting met a body line that is no data line"""
-    L = _lines_lib()
+    L = _need(*_LINES)
     buf = _text_array(text)
     n = (len(text) + DEFLATE_MAX_PAYLOAD - 1) // DEFLATE_MAX_PAYLOAD
     capacity = len(text) + DEFLATE_SLOT_EXTRA * n
@@ -977,9 +977,7 @@ def vcf_bgzf_device(text: bytes, sort: bool, huffman: str = "fixed", device: int
 
 def vcf_lines_last_times() -> Dict[str, float]:
     """svt_vcf_lines_last_times: the line-table and gather kernels of this thread's last device call, from HIP events"""
-    t = _LinesTimes()
-    hip._check(_lines_lib().svt_vcf_lines_last_times(C.byref(t)))
-    return {name: float(getattr(t, name)) for name, _ in _LinesTimes._fields_}
+    return _times(_LinesTimes, _need(*_LINES).svt_vcf_lines_last_times)
 
 
 PASTE_LINE = np.dtype([("qual", np.float64), ("counts", np.uint32, (8,)), ("nonref", np.uint32), ("flags", np.uint32),
@@ -991,20 +989,13 @@ PASTE_BAD_QUAL, PASTE_BAD_COLUMNS, PASTE_BAD_GT, PASTE_BAD_ALLELE, PASTE_BAD_POS
 PASTE_LAYOUTS = {"default": 0, "lane": 1, "quarter": 2, "wave": 3}
 
 
-def _paste_lib():
-    L = _lib()
-    if not hasattr(L, "svt_vcf_paste_host"):
-        raise hip.SvtyperHipError("this libsvtyper_hip.so has no svt_vcf_paste_host (built before svtyper_amd.paste)")
-    return L
-
-
 def vcf_paste(text: bytes, first_line, n_inputs: int, n_lines: int, flags: int, info_table: bytes = b"", device: Optional[int] = None,
               layout: str = "default"):
     """svt_vcf_paste_host (device None) / _device over one block: `text` holds n_lines lines of the master and of every input, file
     f's from line first_line[f] on.  (the pasted lines as bytes, results PASTE_LINE [n_lines], info); info: host_lines, and where a
     line cannot be written bad_line (1-based in the block), bad_file (0: the master, f: input f - 1), bad_kind, bad_field -- the
     bytes are then empty"""
-    L = _paste_lib()
+    L = _need(*_PASTE)
     buf = _text_array(text)
     first_line = np.ascontiguousarray(first_line, np.uint64)
     if first_line.shape[0] != n_inputs + 1:
@@ -1028,17 +1019,18 @@ def vcf_paste(text: bytes, first_line, n_inputs: int, n_lines: int, flags: int, 
 
 def vcf_paste_last_times() -> Dict[str, float]:
     """svt_vcf_paste_last_times: the kernels of this thread's last svt_vcf_paste_device from HIP events, its copies on the host's clock"""
-    t = _PasteTimes()
-    hip._check(_paste_lib().svt_vcf_paste_last_times(C.byref(t)))
-    return {name: float(getattr(t, name)) for name, _ in _PasteTimes._fields_}
+    return _times(_PasteTimes, _need(*_PASTE).svt_vcf_paste_last_times)
 
 
 class _CohortRule:
     """the ctypes side of one rule over the lines of a cohort VCF: svt_vcf_<rule>_host, _device, _write, _take and _last_times.
-    `middle`: the argument types of _host between (text, len) and (results, capacity, n_lines, info)"""
+    `middle`: the argument types of _host between (text, len) and (results, capacity, n_lines); `extra`, `device_extra` and
+    `write_extra`: those of the rule's further arrays, in front of _host's info, of _device's device and of _write's out_off.
+    `program`: the module the rule came with"""
 
-    def __init__(self, rule, line, info, times, middle):
+    def __init__(self, rule, line, info, times, middle, extra=(), device_extra=(), write_extra=(), program=None):
         self.rule, self.line, self.info, self.times, self.middle = rule, line, info, times, middle
+        self.extra, self.device_extra, self.write_extra, self.program = list(extra), list(device_extra), list(write_extra), program or rule
 
     def entry(self, L, name):
         return getattr(L, "svt_vcf_%s_%s" % (self.rule, name))
@@ -1047,56 +1039,55 @@ class _CohortRule:
         if not hasattr(L, "svt_vcf_%s_host" % self.rule):           # (a library built before the rule lacks the symbols)
             return
         P, U64 = C.c_void_p, C.c_uint64
-        host = [P, U64] + self.middle + [P, U64, P, C.POINTER(self.info)]
-        for name, argtypes in (("host", host), ("device", host + [C.c_int]), ("take", [P, U64]), ("last_times", [C.POINTER(self.times)]),
-                               ("write", [P, U64, C.c_uint32, P, U64, P, U64, P, U64, P, C.POINTER(self.info)])):
+        host = [P, U64] + self.middle + [P, U64, P] + self.extra + [C.POINTER(self.info)]
+        for name, argtypes in (("host", host), ("device", host + self.device_extra + [C.c_int]), ("take", [P, U64]),
+                               ("last_times", [C.POINTER(self.times)]),
+                               ("write", [P, U64, C.c_uint32, P, U64, P, U64, P, U64] + self.write_extra + [P, C.POINTER(self.info)])):
             self.entry(L, name).restype = C.c_int
             self.entry(L, name).argtypes = argtypes
 
     def lib(self):
-        L = _lib()
-        if not hasattr(L, "svt_vcf_%s_host" % self.rule):
-            raise hip.SvtyperHipError("this libsvtyper_hip.so has no svt_vcf_%s_host (built before svtyper_amd.%s)" % (self.rule, self.rule))
-        return L
+        return _need("svt_vcf_%s_host" % self.rule, "svtyper_amd.%s" % self.program)
 
     def report(self, info) -> dict:
         report = {name: int(getattr(info, name)) for name, _ in self.info._fields_ if name != "bad_text"}
         report["bad_text"] = bytes(info.bad_text).decode("utf-8", "surrogateescape")
         return report
 
-    def records(self, text, middle, device):
-        """_host (device None) / _device over one block: (the records, one per line, the report)"""
+    def records(self, text, middle, device, extra=None, device_extra=()):
+        """_host (device None) / _device over one block: (the records, one per line, the report).  extra(capacity) and
+        `device_extra`: the values of the rule's further arguments, the former for `capacity` lines"""
         L = self.lib()
         buf = _text_array(text)
         capacity = text.count(b"\n") + 1
+        extra = extra(capacity) if extra is not None else []
         results = np.zeros(capacity, self.line)
         n_lines = C.c_uint64(0)
         info = self.info()
-        args = [buf.ctypes.data, len(text)] + middle + [results.ctypes.data, capacity, C.addressof(n_lines), C.byref(info)]
+        args = [buf.ctypes.data, len(text)] + middle + [results.ctypes.data, capacity, C.addressof(n_lines)] + list(extra) + [C.byref(info)]
         if device is None:
             hip._check(self.entry(L, "host")(*args))
         else:
-            hip._check(self.entry(L, "device")(*args, int(device)))
+            hip._check(self.entry(L, "device")(*args, *device_extra, int(device)))
         return results[:n_lines.value], self.report(info)
 
-    def write(self, text, n_samples, info_table, format_table, results):
-        """_write + _take: (the block's output text, out_off [lines + 1], the report)"""
+    def write(self, text, n_samples, info_table, format_table, results, extra=(), entries=None):
+        """_write + _take: (the output text, out_off [entries + 1], the report).  `extra`: the values of the rule's further
+        arguments; `entries`: how many pieces of text the call writes (None: one per record)"""
         L = self.lib()
         buf, inf, fmt = _text_array(text), _text_array(info_table), _text_array(format_table)
         results = np.ascontiguousarray(results, self.line)
-        out_off = np.zeros(results.shape[0] + 1, np.uint64)
+        out_off = np.zeros((results.shape[0] if entries is None else entries) + 1, np.uint64)
         info = self.info()
         hip._check(self.entry(L, "write")(buf.ctypes.data, len(text), int(n_samples), inf.ctypes.data, len(info_table), fmt.ctypes.data,
-                                          len(format_table), results.ctypes.data if results.shape[0] else None, results.shape[0],
+                                          len(format_table), results.ctypes.data if results.shape[0] else None, results.shape[0], *extra,
                                           out_off.ctypes.data, C.byref(info)))
         out = np.empty(max(info.out_len, 1), np.uint8)
         hip._check(self.entry(L, "take")(out.ctypes.data, info.out_len))
         return out[:info.out_len].tobytes(), out_off, self.report(info)
 
     def last_times(self) -> Dict[str, float]:
-        t = self.times()
-        hip._check(self.entry(self.lib(), "last_times")(C.byref(t)))
-        return {name: float(getattr(t, name)) for name, _ in self.times._fields_}
+        return _times(self.times, self.entry(self.lib(), "last_times"))
 
 
 CLASSIFY_LINE = np.dtype([("median", np.float64), ("mad", np.float64), ("slope", np.float64), ("r2", np.float64), ("route", np.uint32),
@@ -1191,66 +1182,42 @@ GROUP_SLOW = 31
 GROUP_KEYS = ("SVTYPE", "MATEID", "END", "CIPOS", "CIEND")
 
 
-def _group_lib():
-    L = _lib()
-    if not hasattr(L, "svt_vcf_group_host"):
-        raise hip.SvtyperHipError("this libsvtyper_hip.so has no svt_vcf_group_host (built before svtyper_amd.group_multiline)")
-    return L
-
-
-def _group_report(info) -> dict:
-    report = {name: int(getattr(info, name)) for name, _ in _GroupReport._fields_ if name != "bad_text"}
-    report["bad_text"] = bytes(info.bad_text).decode("utf-8", "surrogateescape")
-    return report
+_GROUP = _CohortRule("group", GROUP_LINE, _GroupReport, _GroupTimes, [C.c_uint32, C.c_void_p, C.c_uint64], extra=[C.c_void_p, C.c_void_p],
+                     device_extra=[C.c_uint32], write_extra=[C.c_void_p, C.c_uint64], program="group_multiline")
 
 
 def vcf_group(text: bytes, n_samples: int, format_table: bytes, device: Optional[int] = None, hash_bits: int = 64):
     """svt_vcf_group_host (device None) / _device over the WHOLE body: (lines GROUP_LINE, one per line, plan GROUP_OUT in output
     order, report).  report: host_lines, host_join, n_bnd and, where the script dies on a line, bad_line (1-based), bad_kind,
     bad_text; the plan then ends in front of that line"""
-    L = _group_lib()
-    buf, fmt = _text_array(text), _text_array(format_table)
-    capacity = text.count(b"\n") + 1
-    lines = np.zeros(capacity, GROUP_LINE)
-    plan = np.zeros(2 * capacity, GROUP_OUT)
-    n_lines, n_plan = C.c_uint64(0), C.c_uint64(0)
-    info = _GroupReport()
-    args = [buf.ctypes.data, len(text), int(n_samples), fmt.ctypes.data, len(format_table), lines.ctypes.data, capacity, C.addressof(n_lines),
-            plan.ctypes.data, C.addressof(n_plan), C.byref(info)]
-    if device is None:
-        hip._check(L.svt_vcf_group_host(*args))
-    else:
-        hip._check(L.svt_vcf_group_device(*args, int(hash_bits), int(device)))
-    return lines[:n_lines.value], plan[:n_plan.value], _group_report(info)
+    fmt = _text_array(format_table)
+    plan, n_plan = [], C.c_uint64(0)
+
+    def plan_for(capacity):                         # (the records' capacity, from the one count of the body's lines)
+        plan.append(np.zeros(2 * capacity, GROUP_OUT))
+        return [plan[0].ctypes.data, C.addressof(n_plan)]
+
+    lines, report = _GROUP.records(text, [int(n_samples), fmt.ctypes.data, len(format_table)], device, extra=plan_for,
+                                   device_extra=[int(hash_bits)])
+    return lines, plan[0][:n_plan.value], report
 
 
 def vcf_group_write(text: bytes, n_samples: int, info_table: bytes, format_table: bytes, lines: np.ndarray, plan: np.ndarray):
     """svt_vcf_group_write + _take: (the output text of the plan, out_off [entries + 1], report)"""
-    L = _group_lib()
-    buf, inf, fmt = _text_array(text), _text_array(info_table), _text_array(format_table)
-    lines = np.ascontiguousarray(lines, GROUP_LINE)
     plan = np.ascontiguousarray(plan, GROUP_OUT)
-    out_off = np.zeros(plan.shape[0] + 1, np.uint64)
-    info = _GroupReport()
-    hip._check(L.svt_vcf_group_write(buf.ctypes.data, len(text), int(n_samples), inf.ctypes.data, len(info_table), fmt.ctypes.data, len(format_table),
-                                     lines.ctypes.data if lines.shape[0] else None, lines.shape[0],
-                                     plan.ctypes.data if plan.shape[0] else None, plan.shape[0], out_off.ctypes.data, C.byref(info)))
-    out = np.empty(max(info.out_len, 1), np.uint8)
-    hip._check(L.svt_vcf_group_take(out.ctypes.data, info.out_len))
-    return out[:info.out_len].tobytes(), out_off, _group_report(info)
+    return _GROUP.write(text, n_samples, info_table, format_table, lines, extra=[plan.ctypes.data if plan.shape[0] else None, plan.shape[0]],
+                        entries=plan.shape[0])
 
 
 def vcf_group_last_times() -> Dict[str, float]:
     """svt_vcf_group_last_times: the kernels of this thread's last svt_vcf_group_device from HIP events, its copies on the host's clock"""
-    t = _GroupTimes()
-    hip._check(_group_lib().svt_vcf_group_last_times(C.byref(t)))
-    return {name: float(getattr(t, name)) for name, _ in _GroupTimes._fields_}
+    return _GROUP.last_times()
 
 
 def tbx_build(text: bytes, lines: np.ndarray, member_off, src_off=None, payload: int = DEFLATE_MAX_PAYLOAD, csi: bool = False):
     """svt_tbx_build + svt_tbx_take: (the uncompressed bytes of the .tbi, 0, 0), or (None, bad_line, bad_kind); csi=True:
     svt_csi_build_vcf + svt_csi_take, the uncompressed bytes of the .csi"""
-    L = _csi_lib() if csi else _lines_lib()
+    L = _need(*_CSI) if csi else _need(*_LINES)
     build, take = (L.svt_csi_build_vcf, L.svt_csi_take) if csi else (L.svt_tbx_build, L.svt_tbx_take)
     buf = _text_array(text)
     lines = np.ascontiguousarray(lines, TBX_LINE)
@@ -1279,17 +1246,10 @@ BAM_BAD_RECORD, BAM_BAD_TID, BAM_BAD_POS = 0x100, 0x200, 0x400
 BAM_KIND_RECORD, BAM_KIND_TID, BAM_KIND_POS, BAM_KIND_BEYOND, BAM_KIND_KEY_BACK = 1, 2, 3, 4, 5
 
 
-def _spans_lib():
-    L = _lib()
-    if not hasattr(L, "svt_bam_spans_host"):
-        raise hip.SvtyperHipError("this libsvtyper_hip.so has no svt_bam_spans_host (built before the sorted, indexed -w dump)")
-    return L
-
-
 def bam_spans(data: bytes, rec_off, n_ref: int, device: Optional[int] = None) -> Tuple[np.ndarray, int, int]:
     """svt_bam_spans_host (device None) / _device: (the span table of the records data[rec_off[i] .. rec_off[i + 1]), one BAM_SPAN
     each; the AND of their keys; the OR)"""
-    L = _spans_lib()
+    L = _need(*_SPANS)
     buf = _text_array(data)
     rec_off = np.ascontiguousarray(rec_off, np.uint64)
     n = int(rec_off.shape[0]) - 1
@@ -1308,7 +1268,7 @@ def bam_spans(data: bytes, rec_off, n_ref: int, device: Optional[int] = None) ->
 def bam_sort_order(spans: np.ndarray, device: Optional[int] = None):
     """svt_bam_sort_order_host (device None) / _device: (perm, 0, 0), or (None, the 1-based number of a record that cannot be
     sorted, why: BAM_KIND_*)"""
-    L = _spans_lib()
+    L = _need(*_SPANS)
     spans = np.ascontiguousarray(spans, BAM_SPAN)
     n = spans.shape[0]
     perm = np.zeros(max(n, 1), np.uint64)
@@ -1325,7 +1285,7 @@ def bam_sorted_bgzf_device(data: bytes, rec_off, n_ref: int, sort: bool, huffman
     """svt_bam_sorted_bgzf_device: `data` (the header in front of rec_off[0], the records behind it) up once; (members uint8,
     out_off uint64 [m + 1], member_start uint64 [m + 1], spans as written, perm uint64, 0, 0), or (None, None, None, None, None,
     bad_record, bad_kind) where sorting met a record that cannot be sorted"""
-    L = _spans_lib()
+    L = _need(*_SPANS)
     buf = _text_array(data)
     rec_off = np.ascontiguousarray(rec_off, np.uint64)
     n = int(rec_off.shape[0]) - 1
@@ -1352,23 +1312,14 @@ def bam_sorted_bgzf_device(data: bytes, rec_off, n_ref: int, sort: bool, huffman
 def bam_sort_last_times() -> Dict[str, float]:
     """svt_bam_sort_last_times: the kernels of this thread's last device call over BAM spans, from HIP events (the sort's three
     summed over its passes), and `passes`: the digits the sort took"""
-    t = _BamSortTimes()
-    hip._check(_spans_lib().svt_bam_sort_last_times(C.byref(t)))
-    return {name: (int if name == "passes" else float)(getattr(t, name)) for name, _ in _BamSortTimes._fields_ if name != "reserved"}
-
-
-def _first_lib():
-    L = _lib()
-    if not hasattr(L, "svt_bam_first_host"):
-        raise hip.SvtyperHipError("this libsvtyper_hip.so has no svt_bam_first_host (built before the gathered -w dump)")
-    return L
+    return _times(_BamSortTimes, _need(*_SPANS).svt_bam_sort_last_times, ints=("passes",))
 
 
 def bam_first(data, rec_off, device: Optional[int] = None, hash_bits: int = 64) -> Tuple[Optional[np.ndarray], int]:
     """svt_bam_first_host (device None) / _device: (keep, 0) -- keep[i] = 1 iff no record in front of record i of
     data[rec_off[i] .. rec_off[i + 1]) has its (query name, flag), one uint8 each --, or (None, the 1-based number of the first
     record that is not well-formed).  `hash_bits` (the device alone): the low bits of the key's hash the device sorts by."""
-    L = _first_lib()
+    L = _need(*_FIRST)
     buf = _text_array(data)
     rec_off = np.ascontiguousarray(rec_off, np.uint64)
     n = int(rec_off.shape[0]) - 1
@@ -1392,15 +1343,13 @@ def bam_first(data, rec_off, device: Optional[int] = None, hash_bits: int = 64) 
 def bam_first_last_times() -> Dict[str, float]:
     """svt_bam_first_last_times: the kernels of this thread's last svt_bam_first_device, from HIP events (the sort's three summed
     over its passes), and `passes`: the digits the sort took"""
-    t = _BamFirstTimes()
-    hip._check(_first_lib().svt_bam_first_last_times(C.byref(t)))
-    return {name: (int if name == "passes" else float)(getattr(t, name)) for name, _ in _BamFirstTimes._fields_ if name != "reserved"}
+    return _times(_BamFirstTimes, _need(*_FIRST).svt_bam_first_last_times, ints=("passes",))
 
 
 def bai_build(spans: np.ndarray, n_ref: int, member_start, member_off):
     """svt_bai_build + svt_bai_take: (the bytes of the .bai, 0, 0), or (None, bad_record, bad_kind).  `spans`: the table of the
     stream as written; member k holds its bytes [member_start[k], member_start[k + 1]) and begins at file offset member_off[k]"""
-    L = _spans_lib()
+    L = _need(*_SPANS)
     spans = np.ascontiguousarray(spans, BAM_SPAN)
     member_start = np.ascontiguousarray(member_start, np.uint64)
     member_off = np.ascontiguousarray(member_off, np.uint64)
@@ -1417,16 +1366,9 @@ def bai_build(spans: np.ndarray, n_ref: int, member_start, member_off):
 
 
 # ---- a CSI index for the sorted outputs: the depth, the BAM's fold on the host and on the device (include/svtyper_reads.h) ----------
-def _csi_lib():
-    L = _lib()
-    if not hasattr(L, "svt_csi_build_bam"):
-        raise hip.SvtyperHipError("this libsvtyper_hip.so has no svt_csi_build_bam (built before CSI indexes were written)")
-    return L
-
-
 def csi_depth(max_end: int) -> int:
     """svt_csi_depth: the depth of the scheme (14, depth) a file gets whose largest end (BAM: longest l_ref) is `max_end`"""
-    return int(_csi_lib().svt_csi_depth(int(max_end)))
+    return int(_need(*_CSI).svt_csi_depth(int(max_end)))
 
 
 def _member_tables(member_start, member_off):
@@ -1448,7 +1390,7 @@ def _csi_taken(L, size, bad, kind):
 def csi_build_bam(spans: np.ndarray, n_ref: int, l_ref_max: int, member_start, member_off, device: Optional[int] = None):
     """svt_csi_build_bam (device None) / svt_bam_index_fold_device, + svt_csi_take: (the uncompressed bytes of the .csi, 0, 0), or
     (None, bad_record, bad_kind).  Arguments as bai_build; `l_ref_max`: the longest reference of the header"""
-    L = _csi_lib()
+    L = _need(*_CSI)
     spans = np.ascontiguousarray(spans, BAM_SPAN)
     member_start, member_off = _member_tables(member_start, member_off)
     size, bad, kind = C.c_uint64(0), C.c_uint64(0), C.c_uint32(0)
@@ -1465,7 +1407,7 @@ def bam_sorted_bgzf_csi_device(data: bytes, rec_off, n_ref: int, l_ref_max: int,
     """svt_bam_sorted_bgzf_csi_device: bam_sorted_bgzf_device with the CSI fold on the device behind the members -- (members, out_off,
     member_start, spans, perm, csi bytes or None, index_bad, index_kind, 0, 0), or (None, ..., bad_record, bad_kind) where sorting
     met a record that cannot be sorted.  index_bad: the 1-based number, in written order, of a record the index cannot hold"""
-    L = _csi_lib()
+    L = _need(*_CSI)
     buf = _text_array(data)
     rec_off = np.ascontiguousarray(rec_off, np.uint64)
     n = int(rec_off.shape[0]) - 1
@@ -1494,9 +1436,7 @@ def bam_sorted_bgzf_csi_device(data: bytes, rec_off, n_ref: int, l_ref_max: int,
 
 def bam_index_last_times() -> Dict[str, float]:
     """svt_bam_index_last_times: the kernels of this thread's last device fold, from HIP events; `runs`, and `passes` of the runs' sort"""
-    t = _BamIndexTimes()
-    hip._check(_csi_lib().svt_bam_index_last_times(C.byref(t)))
-    return {name: (int if name in ("runs", "passes") else float)(getattr(t, name)) for name, _ in _BamIndexTimes._fields_ if name != "reserved"}
+    return _times(_BamIndexTimes, _need(*_CSI).svt_bam_index_last_times, ints=("runs", "passes"))
 
 
 # ---- VCF text as a BCF2.2 stream: the records on the host and on the device (include/svtyper_bcf.h) ----------
@@ -1580,9 +1520,7 @@ def bcf_bgzf_device(text: bytes, sort: bool = False, huffman: str = "fixed", dev
 
 def bcf_last_times() -> Dict[str, float]:
     """svt_bcf_last_times: the two kernels of this thread's last device call over BCF records, from HIP events"""
-    t = _BcfTimes()
-    hip._check(_bcf_lib().svt_bcf_last_times(C.byref(t)))
-    return {name: float(getattr(t, name)) for name, _ in _BcfTimes._fields_}
+    return _times(_BcfTimes, _bcf_lib().svt_bcf_last_times)
 
 
 # ---- an inflated BCF2.2 stream back to VCF text: the lines on the host and on the device (include/svtyper_bcf.h) ----------
@@ -1645,6 +1583,4 @@ def bcf_text(stream: bytes, device: Optional[int] = None, block_bytes: Optional[
 def bcf_text_last_times() -> Dict[str, float]:
     """svt_bcf_text_last_times: the kernels and copies of this thread's last bcf_text on a device, from HIP events, summed over its
     chunks, and the call's wall time"""
-    t = _BcfTextTimes()
-    hip._check(_bcf_text_lib().svt_bcf_text_last_times(C.byref(t)))
-    return {name: float(getattr(t, name)) for name, _ in _BcfTextTimes._fields_}
+    return _times(_BcfTextTimes, _bcf_text_lib().svt_bcf_text_last_times)

@@ -21,14 +21,13 @@ a master whose header has no #CHROM line makes vcf_allele_freq.py print nothing 
 the body.
 
 The header runs once, in Python; the body goes through the native library in blocks of at most `block_bytes` of text (at
-least one line of every file; None: BLOCK_BYTES[engine]).
+least one line of every file; None: cohort.BLOCK_BYTES[engine]).
 """
 from __future__ import annotations
 
 import argparse
 import gzip
 import itertools
-import re
 import sys
 import time
 from typing import List, Optional
@@ -36,16 +35,14 @@ from typing import List, Optional
 import numpy as np
 
 from . import native_reads as nr
-from .cohort import open_source
+from .cohort import (_text, _unquoted, add_attributes, add_program_arguments, declared_lines, header_attributes, info_table, open_source,
+                     parse_program_arguments, run_options, run_program, run_stats)
 
-# a block's lines are a launch's wavefronts, so the device wants many; the host twin is fastest with blocks its caches hold
-BLOCK_BYTES = {"host": 8 << 20, "device": 64 << 20}
 LENGTH_MESSAGE = "\nError: VCF files differ in length\n"
 FIELDS = ("CHROM", "POS", "ID")
 _KINDS = {nr.PASTE_BAD_QUAL: "a QUAL that is no number", nr.PASTE_BAD_COLUMNS: "too few columns",
           nr.PASTE_BAD_GT: "a GT that is no list of allele numbers", nr.PASTE_BAD_ALLELE: "an allele number beyond the ALT count",
           nr.PASTE_BAD_POS: "a POS that is no integer"}
-_ATTRIBUTES = re.compile(r'(?:[^,"]|"[^"]*")+')         # the attributes of a header line's <...>: commas inside quotes do not split
 
 
 class PasteError(Exception):
@@ -99,71 +96,6 @@ class _Lines:
         self.f.close()
 
 
-def _text(data: bytes) -> str:
-    return data.decode("utf-8", "surrogateescape")
-
-
-def _attributes(line: str, end):
-    inside = line[line.find("<") + 1:end(line)]
-    return [a.split("=")[1] for a in _ATTRIBUTES.findall(inside)]
-
-
-def _unquoted(desc: str) -> str:
-    return desc[1:-1] if desc.startswith('"') and desc.endswith('"') else desc
-
-
-def add_attributes(table, values, width, error):
-    """one header line's attributes into its table, the first line of an ID winning"""
-    if len(values) != width:
-        raise error("a header line with %d attributes where %d are read: %s" % (len(values), width, ",".join(values)))
-    if values[0] not in [row[0] for row in table]:
-        table.append(tuple(values))
-
-
-def header_attributes(header_lines: List[str], error):
-    """What the Vcf class of the reference's scripts (vcf_allele_freq.py, sv_classifier.py) reads off a header (`header_lines`
-    without their newlines): (fileformat, reference, FILTER, INFO, ALT, FORMAT tables), GT the first FORMAT; `error`: the
-    exception of a line whose attributes cannot be read"""
-    file_format, reference = "VCFv4.2", ""
-    filters, infos, alts, formats = [], [], [], [("GT", "1", "String", "Genotype")]
-
-    def add(table, values, width):
-        add_attributes(table, values, width, error)
-
-    for bare in header_lines:
-        line = bare + "\n"
-        key = line.split("=")[0]
-        try:
-            if key == "##fileformat":
-                file_format = line.rstrip().split("=")[1]
-            elif key == "##reference":
-                reference = line.rstrip().split("=")[1]
-            elif key == "##INFO":
-                add(infos, _attributes(line, lambda t: t.find(">")), 4)
-            elif key == "##ALT":
-                add(alts, _attributes(line, lambda t: t.find(">")), 2)
-            elif key == "##FORMAT":
-                add(formats, _attributes(line, lambda t: t.find(">")), 4)
-            elif key == "##FILTER":
-                add(filters, _attributes(line, lambda t: -2), 2)
-        except IndexError:
-            raise error("a header line whose attributes are not key=value: %s" % bare) from None
-    return file_format, reference, filters, infos, alts, formats
-
-
-def declared_lines(infos, alts, formats) -> List[str]:
-    """the ##INFO, ##ALT and ##FORMAT lines rebuilt from their attributes"""
-    out = ['##INFO=<ID=%s,Number=%s,Type=%s,Description="%s">' % (i, n, t, _unquoted(d)) for i, n, t, d in infos]
-    out += ['##ALT=<ID=%s,Description="%s">' % (i, _unquoted(d)) for i, d in alts]
-    out += ['##FORMAT=<ID=%s,Number=%s,Type=%s,Description="%s">' % (i, n, t, _unquoted(d)) for i, n, t, d in formats]
-    return out
-
-
-def info_table(infos) -> bytes:
-    """the INFO table of the native calls: "V<id>\\n" per id in the header's order, "F<id>\\n" for a Flag"""
-    return "".join(("F" if t == "Flag" else "V") + i + "\n" for i, _, t, _ in infos).encode("utf-8", "surrogateescape")
-
-
 def afreq_header(header_lines: List[str], chrom_line: str, file_date: str, keep_contigs: bool):
     """vcf_allele_freq.py's header for the pasted header (`header_lines` without their newlines): (text, INFO table of the native
     call).  fileformat, fileDate, reference, then the FILTER, INFO, ALT and FORMAT lines rebuilt from their attributes, GT the
@@ -188,20 +120,13 @@ def paste(vcf_list, master=None, sum_quals=False, afreq=False, safe=False, keep_
     not closed.  `stats`, a dict, receives lines, blocks, host_lines (the lines the host's slow path wrote), results (the per-line
     records of every block, native_reads.PASTE_LINE) and, for engine="device", times (the sums of vcf_paste_last_times).
     `layout`: how the device's write kernel spreads its lanes over the sample parts (native_reads.PASTE_LAYOUTS)."""
-    if engine not in ("host", "device"):
-        raise ValueError("engine is 'host' or 'device'")
-    if block_bytes is None:
-        block_bytes = BLOCK_BYTES[engine]
-    if block_bytes < 1:
-        raise ValueError("block_bytes is at least 1")
+    block_bytes = run_options(engine, block_bytes)
     vcf_list = list(vcf_list)
     if not vcf_list:
         raise PasteError("no input: the list of VCF files is empty")
     inputs = [_Lines(v, engine, device) for v in vcf_list]
     files = [_Lines(master if master is not None else inputs[0].name, engine, device)] + inputs
-    if stats is None:
-        stats = {}
-    stats.update(lines=0, blocks=0, host_lines=0, results=[], times={})
+    stats = run_stats(stats, lines=0, blocks=0, host_lines=0, results=[], times={})
     try:
         _run(files, sum_quals, afreq, safe, keep_contigs, vcf_out, engine, device, file_date, block_bytes, stats, layout)
     finally:
@@ -288,7 +213,6 @@ def _run(files, sum_quals, afreq, safe, keep_contigs, vcf_out, engine, device, f
 
 # ------------------------------------------------------------------------------------------ CLI
 def get_args(argv=None):
-    from .driver import add_output_arguments, check_output_arguments
     p = argparse.ArgumentParser(prog="svtyper-paste", formatter_class=argparse.RawTextHelpFormatter, description=(
         "svtyper-paste\ndescription: Paste VCFs from multiple samples; optionally add allele frequency information"))
     p.add_argument("-m", "--master", metavar="FILE", type=str, default=None,
@@ -297,37 +221,18 @@ def get_args(argv=None):
     p.add_argument("-f", "--vcf_list", metavar="FILE", required=True, help="Line-delimited list of VCF files to paste")
     p.add_argument("--afreq", action="store_true", help="add AF and NSAMP to INFO, as vcf_allele_freq.py does to the pasted VCF")
     p.add_argument("--safe", action="store_true", help="check that CHROM, POS and ID of every input's lines match the master's")
-    p.add_argument("--keep-contigs", dest="keep_contigs", action="store_true",
-                   help="with --afreq: keep the master's ##contig lines, directly before the #CHROM line")
-    p.add_argument("-o", "--output_vcf", metavar="FILE", type=argparse.FileType("w"), default=sys.stdout,
-                   help="output VCF to write (default: stdout)")
-    p.add_argument("--engine", choices=("host", "device"), default="host",
-                   help="where the lines are joined: the native host code or the GPU (same output bytes) [host]")
-    p.add_argument("--device", metavar="INT", type=int, default=0, help="the GPU of --engine device and --deflate device [0]")
-    add_output_arguments(p)
-    args = p.parse_args(argv)
-    check_output_arguments(p, args, args.output_vcf)
-    return args
+    add_program_arguments(p, "where the lines are joined: the native host code or the GPU (same output bytes) [host]",
+                          "with --afreq: keep the master's ##contig lines, directly before the #CHROM line")
+    return parse_program_arguments(p, argv)
 
 
 def main(argv=None):
-    from .driver import _bgzf_text
     args = get_args(argv)
     with open(args.vcf_list) as f:
         vcf_list = [line.rstrip() for line in f]
     call = dict(master=args.master, sum_quals=args.sum_quals, afreq=args.afreq, safe=args.safe, keep_contigs=args.keep_contigs,
                 engine=args.engine, device=args.device)
-    try:
-        if args.bgzf or args.bcf:
-            with _bgzf_text(args.output_vcf, args.deflate, args.device, args.huffman, args) as out:
-                paste(vcf_list, vcf_out=out, **call)
-        else:
-            paste(vcf_list, vcf_out=args.output_vcf, **call)
-            args.output_vcf.flush()
-    except PasteError as e:
-        sys.stderr.write(e.verbatim if e.verbatim is not None else "Error: %s\n" % e)
-        return 1
-    return 0
+    return run_program(args, PasteError, lambda out: paste(vcf_list, vcf_out=out, **call))
 
 
 def cli():

@@ -24,7 +24,7 @@ of a positive sample that float() reads as nan or inf raises UpdateInfoError (th
 AS or sum beyond int64 (the script goes on with long integers).
 
 The header runs in Python; the body goes through the native library in blocks of at most `block_bytes` of text (None:
-paste.BLOCK_BYTES[engine]): the per-line records from either engine, the output text from one C++ writer.
+cohort.BLOCK_BYTES[engine]): the per-line records from either engine, the output text from one C++ writer.
 """
 from __future__ import annotations
 
@@ -34,11 +34,10 @@ import time
 from typing import Optional
 
 from . import native_reads as nr
-from .cohort import blocks, bytes_lines, chrom_lines, finish_block, header_text, open_source, read_header
-from .paste import BLOCK_BYTES, add_attributes, declared_lines, header_attributes, info_table
+from .cohort import (COLUMNS_MESSAGE, FORMAT_MESSAGE, add_attributes, add_program_arguments, bad_line, begin_body, blocks, bytes_lines,
+                     chrom_lines, finish_block, format_table, header_attributes, info_table, open_source, parse_program_arguments,
+                     run_options, run_program, run_stats)
 
-FORMAT_MESSAGE = '\nError: invalid FORMAT field, "%s"\n'
-COLUMNS_MESSAGE = "\nError: VCF file must have at least 8 columns\n"
 MSQ = ["MSQ", "1", "Float", "Mean sample quality of positively genotyped samples"]
 # the script's exception and what to say for each way a line can end the run (native_reads.UPDATE_INFO_BAD_*)
 _KINDS = {nr.UPDATE_INFO_BAD_COLUMNS: ("IndexError", "fewer than seven columns"),
@@ -63,11 +62,7 @@ class UpdateInfoError(Exception):
         self.file, self.line, self.sample, self.token, self.reference, self.verbatim = file, line, sample, token, reference, verbatim
 
 
-def _bad(name, line, kind, text="", sample=None):
-    reference, what = _KINDS[kind]
-    where = "the line" if sample is None else "sample %s" % sample
-    verbatim = _VERBATIM[kind](text) if kind in _VERBATIM else None
-    return UpdateInfoError("%s, line %d: %s" % (name, line, what % dict(text=text, where=where)), name, line, sample, text or None, reference, verbatim)
+_bad = bad_line(UpdateInfoError, _KINDS, _VERBATIM, ("sample", "token"))
 
 
 def update_info(vcf_in, vcf_out=sys.stdout, engine="host", device=0, file_date=None, keep_contigs=False, block_bytes=None,
@@ -76,15 +71,8 @@ def update_info(vcf_in, vcf_out=sys.stdout, engine="host", device=0, file_date=N
     text sink the drivers accept; it is not closed.  `stats`, a dict, receives lines, blocks, host_lines (the lines the host's plain
     C++ computed), results (the per-line records of every block, native_reads.UPDATE_INFO_LINE) and, for engine="device", times
     (the sums of vcf_update_info_last_times)."""
-    if engine not in ("host", "device"):
-        raise ValueError("engine is 'host' or 'device'")
-    if block_bytes is None:
-        block_bytes = BLOCK_BYTES[engine]
-    if block_bytes < 1:
-        raise ValueError("block_bytes is at least 1")
-    if stats is None:
-        stats = {}
-    stats.update(lines=0, blocks=0, host_lines=0, results=[], times={})
+    block_bytes = run_options(engine, block_bytes)
+    stats = run_stats(stats, lines=0, blocks=0, host_lines=0, results=[], times={})
     name, f, own = open_source(vcf_in, sniff=True, engine=engine, device=device)
     try:
         _run(name, bytes_lines(f), vcf_out, device if engine == "device" else None, file_date or time.strftime("%Y%m%d"), block_bytes, stats,
@@ -104,17 +92,11 @@ def header_tables(header):
 
 
 def _run(name, lines, vcf_out, device, file_date, block_bytes, stats, keep_contigs):
-    header, first = read_header(lines)
-    if first is None:                               # (the header is written when the first body line is met)
+    body = begin_body(name, lines, vcf_out, file_date, keep_contigs, header_tables, UpdateInfoError)
+    if body is None:
         return
-    done = len(header)                              # lines of the file in front of the block
-    if not chrom_lines(header):                     # (the script's sample list is never bound)
-        raise UpdateInfoError("%s, line %d: a body line and no #CHROM line in front of it" % (name, done + 1), name, done + 1, reference="UnboundLocalError")
-    file_format, reference, infos, alts, formats, samples = header_tables(header)
-    vcf_out.write(header_text(file_format, file_date, reference, declared_lines(infos, alts, formats), header, samples, keep_contigs,
-                              with_format=bool(samples)))
-    info_bytes = info_table(infos)
-    format_bytes = "".join(i + "\n" for i, _, _, _ in formats).encode("utf-8", "surrogateescape")
+    done, first, samples, infos, formats = body                 # done: lines of the file in front of the block
+    info_bytes, format_bytes = info_table(infos), format_table(formats)
     for block in blocks(first, lines, block_bytes):
         text = b"".join(block) + (b"" if block[-1].endswith(b"\n") else b"\n")     # (the file's last line: rewritten lines end in a newline)
         finish_block(name, done, block, text, samples, nr.vcf_update_info(text, len(samples), format_bytes, device),
@@ -125,42 +107,18 @@ def _run(name, lines, vcf_out, device, file_date, block_bytes, stats, keep_conti
 
 # ------------------------------------------------------------------------------------------ CLI
 def get_args(argv=None):
-    from .driver import add_output_arguments, check_output_arguments
     p = argparse.ArgumentParser(prog="svtyper-update-info", formatter_class=argparse.RawTextHelpFormatter, description=(
         "svtyper-update-info\ndescription: Update the PE SR fields after SVTyper"))
     p.add_argument(metavar="vcf", dest="vcf_in", nargs="?", type=str, default=None, help="VCF input, gzip where it is (default: stdin)")
-    p.add_argument("--keep-contigs", dest="keep_contigs", action="store_true",
-                   help="keep the input's ##contig lines, directly before the #CHROM line")
-    p.add_argument("-o", "--output_vcf", metavar="FILE", type=argparse.FileType("w"), default=sys.stdout,
-                   help="output VCF to write (default: stdout)")
-    p.add_argument("--engine", choices=("host", "device"), default="host",
-                   help="where the samples are added up: the native host code or the GPU (same output bytes) [host]")
-    p.add_argument("--device", metavar="INT", type=int, default=0, help="the GPU of --engine device and --deflate device [0]")
-    add_output_arguments(p)
-    args = p.parse_args(argv)
-    check_output_arguments(p, args, args.output_vcf)
-    if args.vcf_in is None and sys.stdin.isatty():
-        p.print_help()
-        sys.exit(1)
-    return args
+    add_program_arguments(p, "where the samples are added up: the native host code or the GPU (same output bytes) [host]")
+    return parse_program_arguments(p, argv, "vcf_in")
 
 
 def main(argv=None):
-    from .driver import _bgzf_text
     args = get_args(argv)
-    call = dict(engine=args.engine, device=args.device, keep_contigs=args.keep_contigs)
     vcf_in = args.vcf_in if args.vcf_in is not None else sys.stdin.buffer
-    try:
-        if args.bgzf or args.bcf:
-            with _bgzf_text(args.output_vcf, args.deflate, args.device, args.huffman, args) as out:
-                update_info(vcf_in, vcf_out=out, **call)
-        else:
-            update_info(vcf_in, vcf_out=args.output_vcf, **call)
-            args.output_vcf.flush()
-    except UpdateInfoError as e:
-        sys.stderr.write(e.verbatim if e.verbatim is not None else "Error: %s\n" % e)
-        return 1
-    return 0
+    return run_program(args, UpdateInfoError, lambda out: update_info(vcf_in, vcf_out=out, engine=args.engine, device=args.device,
+                                                                      keep_contigs=args.keep_contigs))
 
 
 def cli():

@@ -46,7 +46,7 @@ def _raw_call(fn, data, off, n, keep, n_kept, bad, *more):
 
 
 def test_what_the_c_entry_refuses(corpus):
-    L = nr._first_lib()
+    L = nr._need(*nr._FIRST)
     data, off = F.stream(corpus["all_unique"])
     n = len(off) - 1
     keep, n_kept, bad = np.zeros(n, np.uint8), C.c_uint64(7), C.c_uint64(7)

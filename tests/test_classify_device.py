@@ -77,11 +77,14 @@ def test_command_line_to_a_sorted_indexed_bcf_file(tmp_path, hip_device):
     assert B.check_indexed(out, text, 1, 249250621)
 
 
-@pytest.mark.parametrize("k", range(len(L.K.LENGTHS)))
+@pytest.mark.parametrize("k", range(len(L.K.LENGTHS) + len(L.EDGES)))
 def test_column_starts_at_every_residue_and_length_on_the_device(k, hip_device):
     """tests/cohortlinecases.py: the sample region at the 16 residues of its address, around one piece, one step and two steps of
-    the 128-bit scan, first and last in its block: the host's records and text, and no line leaves the device"""
-    records, _info, out, _written = L.host("classify", k)
-    got, info, text, written = L.run("classify", L.blocks("classify")[k], device=hip_device)
+    the 128-bit scan, first and last in its block: the host's records and text, and no line leaves the device.  Behind them the
+    edges of a call (test_cohort_line_host.EDGES: no text, one line without its newline, two lines): the host's records, reports
+    and text there too"""
+    records, report, out, wrote = L.host("classify", k)
+    got, info, text, written = L.run("classify", (L.blocks("classify") + L.edges("classify"))[k], device=hip_device)
     assert info["host_lines"] == 0 and info["bad_line"] == 0 and written["bad_line"] == 0
-    assert got.tobytes() == records.tobytes() and text == out
+    assert got.tobytes() == records.tobytes() and text == out and info == report and written == wrote
+    assert len(got) == (16, 0, 1, 2)[max(k - len(L.K.LENGTHS) + 1, 0)]

@@ -17,7 +17,7 @@ import classifycases as K
 import test_classify_host as H
 
 from svtyper_amd import native_reads as nr
-from svtyper_amd import paste
+from svtyper_amd import cohort
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "svtyper_amd", "csrc")
@@ -43,13 +43,13 @@ def test_structure_matches_the_header():
 def tables_of(case):
     lines = case["vcf"].splitlines(True)
     header = [l for l in lines[:next((k for k, l in enumerate(lines) if not l.startswith("#")), len(lines))]]
-    _ff, _ref, _filters, infos, _alts, formats = paste.header_attributes([h.rstrip("\n") for h in header if h.startswith("##")], ValueError)
+    _ff, _ref, _filters, infos, _alts, formats = cohort.header_attributes([h.rstrip("\n") for h in header if h.startswith("##")], ValueError)
     samples = next((h.rstrip().split("\t")[9:] for h in header if not h.startswith("##")), [])
     genders = dict(l.split("\t") for l in case["gender"].splitlines())
     excluded = set((case["exclude"] or "").splitlines())
     code = lambda s, g: 1 if genders.get(s) == g else nr.CLASSIFY_NO_GENDER if s not in genders else 0
     row = [len(samples), bytes(code(s, "1") for s in samples), bytes(code(s, "2") for s in samples), bytes(s in excluded for s in samples),
-           "".join(f[0] + "\n" for f in formats).encode(), paste.info_table(infos)]
+           cohort.format_table(formats), cohort.info_table(infos)]
     return " ".join(str(v) if isinstance(v, int) else (v.hex() or "-") for v in row), "".join(lines[len(header):]), len(header)
 
 

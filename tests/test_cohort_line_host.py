@@ -32,9 +32,21 @@ def run(tool, block, device=None):
     return records, info, out, written
 
 
+EDGES = ("no text", "one line without its newline", "two lines")
+
+
+@functools.lru_cache(maxsize=None)
+def edges(tool):
+    """the first block's lines in the shapes at the edges of a call: what its prologue (the upload, the line table) has the least of"""
+    block = blocks(tool)[0]
+    lines = block["text"].splitlines(True)
+    return [dict(block, text=text) for text in (b"", lines[0][:-1], lines[0] + lines[1])]
+
+
 @functools.lru_cache(maxsize=None)
 def host(tool, k):
-    return run(tool, blocks(tool)[k])
+    """the host engine over block k, the edges counted on behind the blocks"""
+    return run(tool, (blocks(tool) + edges(tool))[k])
 
 
 def test_the_regions_cover_every_residue_and_length():

@@ -6,6 +6,7 @@ passed through with their warning, unpaired breakends, `--sum_quals` over an inc
 CPU only: the likelihood seam is filled by the oracle (as in test_host_pipeline.py); every case runs through the
 portable Python reader and through what a caller with the reference's positional arguments gets (`reader=None`: the
 C++ reader and the bulk VCF route), on cut-down copies of tests/data/example.vcf of a dozen lines."""
+import importlib
 import io
 import json
 import logging
@@ -291,6 +292,18 @@ def test_help_text(monkeypatch, capsys, module, prog):
     monkeypatch.setattr(sys, "argv", [prog, "--help"])
     with pytest.raises(SystemExit) as e:
         module.get_args()
+    assert e.value.code == 0
+    with open(os.path.join(HERE, "golden", "help_%s.txt" % prog)) as f:
+        assert capsys.readouterr().out == f.read()
+
+
+@pytest.mark.parametrize("prog", ["classify", "update_info", "group_multiline", "paste", "bcf_in"])
+def test_cohort_help_text(monkeypatch, capsys, prog):
+    """`--help` of the cohort programs, byte for byte (tests/golden/help_<prog>.txt, 80 columns): the options they share are added
+    by one function (cohort.add_program_arguments), behind each program's own"""
+    monkeypatch.setenv("COLUMNS", "80")
+    with pytest.raises(SystemExit) as e:
+        importlib.import_module("svtyper_amd." + prog).get_args(["--help"])
     assert e.value.code == 0
     with open(os.path.join(HERE, "golden", "help_%s.txt" % prog)) as f:
         assert capsys.readouterr().out == f.read()

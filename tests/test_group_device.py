@@ -12,7 +12,8 @@ import pytest
 import groupcases as K
 import tbxcases as X
 import test_group_host as H
-from svtyper_amd import group_multiline
+from svtyper_amd import cohort, group_multiline
+from svtyper_amd import native_reads as nr
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -68,6 +69,25 @@ def test_four_bit_hashes_collide_and_the_bytes_decide(case, tmp_path, hip_device
     assert text == H.EXPECTED[case["name"]]["expected"]["stdout"]
     assert stats["plan"].tobytes() == host["plan"].tobytes() and stats["records"].tobytes() == host["records"].tobytes()
     assert stats["host_join"] is False and stats["host_lines"] == 0
+
+
+@pytest.mark.parametrize("shape", ["no text", "one line without its newline", "two lines"])
+def test_the_edges_of_a_call_on_the_device(shape, hip_device):
+    """what the call's prologue (the upload, the line table) has the least of, in the lines of last_line_bare, a pair: the host's
+    records, plan, reports and text"""
+    case = next(c for c in H.CASES if c["name"] == "last_line_bare")
+    lines = [l.encode() for l in case["vcf"].splitlines(True)]
+    header, body = [l.decode() for l in lines if l.startswith(b"#")], [l for l in lines if not l.startswith(b"#")]
+    _ff, _ref, infos, _alts, formats, samples = group_multiline.header_tables(header)
+    text = {"no text": b"", "one line without its newline": body[0][:-1], "two lines": body[0] + body[1] + b"\n"}[shape]
+    tables = (len(samples), cohort.info_table(infos), cohort.format_table(formats))
+    want = nr.vcf_group(text, tables[0], tables[2])
+    got = nr.vcf_group(text, tables[0], tables[2], device=hip_device)
+    assert len(got[0]) == text.count(b"\n") + (shape == "one line without its newline") and len(got[1]) == (2 if shape == "two lines" else 0)
+    assert got[0].tobytes() == want[0].tobytes() and got[1].tobytes() == want[1].tobytes()
+    assert got[2] == dict(want[2], host_join=0) and want[2]["host_join"] == 1 and got[2]["bad_line"] == 0     # (where the join ran)
+    wrote, asked = nr.vcf_group_write(text, *tables, got[0], got[1]), nr.vcf_group_write(text, *tables, want[0], want[1])
+    assert wrote[0] == asked[0] and wrote[0].count(b"\n") == len(got[1]) and wrote[2] == asked[2] and wrote[2]["bad_line"] == 0
 
 
 def test_the_regular_cases_are_most_of_the_corpus_and_hold_the_sizes():

@@ -16,7 +16,7 @@ import pytest
 import groupcases as K
 import test_group_host as H
 
-from svtyper_amd import group_multiline, hip, paste
+from svtyper_amd import cohort, group_multiline, hip
 from svtyper_amd import native_reads as nr
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -53,7 +53,7 @@ def tables_of(case):
     body = "".join(lines[n_header:])
     if body and not body.endswith("\n"):
         body += "\n"                                                # (as the module hands it over)
-    return len(samples), "".join(f[0] + "\n" for f in formats).encode(), paste.info_table(infos), body, n_header
+    return len(samples), cohort.format_table(formats), cohort.info_table(infos), body, n_header
 
 
 def test_entry_points_through_ctypes():

@@ -18,7 +18,7 @@ import updateinfocases as K
 
 from svtyper_amd import hip
 from svtyper_amd import native_reads as nr
-from svtyper_amd import paste, update_info
+from svtyper_amd import cohort, update_info
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "svtyper_amd", "csrc")
@@ -47,7 +47,7 @@ def tables_of(case):
     lines = case["vcf"].splitlines(True)
     n_header = next((k for k, l in enumerate(lines) if not l.startswith("#")), len(lines))
     _ff, _ref, infos, _alts, formats, samples = update_info.header_tables(lines[:n_header])
-    return len(samples), "".join(f[0] + "\n" for f in formats).encode(), paste.info_table(infos), "".join(lines[n_header:]), n_header
+    return len(samples), cohort.format_table(formats), cohort.info_table(infos), "".join(lines[n_header:]), n_header
 
 
 def test_entry_points_through_ctypes():

@@ -29,7 +29,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import classifycases as K  # noqa: E402
-from svtyper_amd import classify, paste  # noqa: E402
+from svtyper_amd import classify, cohort  # noqa: E402
 from svtyper_amd import native_reads as nr  # noqa: E402
 
 
@@ -67,9 +67,9 @@ def restated(vcf, genders):
     gender = {v[0]: int(v[1]) for v in (l.split("\t") for l in genders.decode().splitlines())}
     lines = vcf.decode().split("\n")[:-1]
     header = [l for l in lines if l.startswith("#")]
-    _ff, _ref, _filters, infos, alts, formats = paste.header_attributes([h for h in header if h.startswith("##")], ValueError)
+    _ff, _ref, _filters, infos, alts, formats = cohort.header_attributes([h for h in header if h.startswith("##")], ValueError)
     samples = header[-1].split("\t")[9:]
-    out = ["\n".join(["##fileformat=VCFv4.2", "##fileDate=" + FILE_DATE, "##reference=ref.fa"] + paste.declared_lines(infos, alts, formats)
+    out = ["\n".join(["##fileformat=VCFv4.2", "##fileDate=" + FILE_DATE, "##reference=ref.fa"] + cohort.declared_lines(infos, alts, formats)
                      + ["\t".join(header[-1].split("\t")[:9] + samples)]) + "\n"]
     for number, text in enumerate(lines[len(header):]):
         first = next((i.split("=")[1] for i in text.rstrip().split("\t")[7].split(";") if i.startswith("SVTYPE=")), None)
@@ -156,7 +156,7 @@ def kernel_bytes(vcf, records):
 
 
 def main():
-    report = {"reps": reps, "lines": LINES, "device": device, "box": socket.gethostname(), "legs": LEGS, "block_bytes": paste.BLOCK_BYTES}
+    report = {"reps": reps, "lines": LINES, "device": device, "box": socket.gethostname(), "legs": LEGS, "block_bytes": cohort.BLOCK_BYTES}
     if "device" in LEGS:
         report["device_copy_bytes_per_s"] = device_copy_rate()
     for shape in shapes:

@@ -25,7 +25,7 @@ import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-from svtyper_amd import group_multiline, paste  # noqa: E402
+from svtyper_amd import cohort, group_multiline  # noqa: E402
 
 
 def arg(name, default):
@@ -64,7 +64,7 @@ def restated(vcf):
     lines = vcf.decode().split("\n")[:-1]
     header = [l + "\n" for l in lines if l.startswith("#")]
     file_format, reference, infos, alts, formats, samples = group_multiline.header_tables(header)
-    out = ["\n".join(["##fileformat=" + file_format, "##fileDate=" + FILE_DATE, "##reference=" + reference] + paste.declared_lines(infos, alts, formats)
+    out = ["\n".join(["##fileformat=" + file_format, "##fileDate=" + FILE_DATE, "##reference=" + reference] + cohort.declared_lines(infos, alts, formats)
                      + ["\t".join(header[-1].rstrip().split("\t")[:9] + samples)]) + "\n"]
     order = [f[0] for f in formats]
 

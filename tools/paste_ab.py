@@ -26,7 +26,7 @@ import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-from svtyper_amd import paste  # noqa: E402
+from svtyper_amd import cohort, paste  # noqa: E402
 
 
 def arg(name, default):
@@ -133,7 +133,7 @@ def device_copy_rate():
 
 
 def main():
-    report = {"reps": reps, "times": TIMES, "device": device, "box": socket.gethostname(), "legs": LEGS, "block_bytes": BLOCK_BYTES or paste.BLOCK_BYTES}
+    report = {"reps": reps, "times": TIMES, "device": device, "box": socket.gethostname(), "legs": LEGS, "block_bytes": BLOCK_BYTES or cohort.BLOCK_BYTES}
     if "device" in LEGS:
         report["device_copy_bytes_per_s"] = device_copy_rate()
         report["microarch_float4_copy_bytes_per_s"] = 6.29e12

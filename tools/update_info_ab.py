@@ -13,7 +13,7 @@ Legs:
 `kernel`: the bytes of the lines (each once: the head and the sample columns come from HBM once, the second look at a column
 hits the cache) over the kernel's time, and the bytes it loads (the sample columns twice), beside a device-to-device copy of
 256 MiB on the same box (torch, HIP events).  --reps timed runs (default 5) after one untimed run each, medians with their
-ranges.  --device-block-bytes N: the device leg in blocks of N bytes of text (default: paste.BLOCK_BYTES).  Prints one JSON
+ranges.  --device-block-bytes N: the device leg in blocks of N bytes of text (default: cohort.BLOCK_BYTES).  Prints one JSON
 object and, with --out FILE, writes it there.  GPU box only (--legs python,host runs anywhere)."""
 import io
 import json
@@ -29,7 +29,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import updateinfocases as K  # noqa: E402
-from svtyper_amd import paste, update_info  # noqa: E402
+from svtyper_amd import cohort, update_info  # noqa: E402
 
 
 def arg(name, default):
@@ -37,7 +37,7 @@ def arg(name, default):
 
 
 reps, out_path, device = arg("--reps", 5), arg("--out", ""), arg("--device", 0)
-DEVICE_BLOCK = arg("--device-block-bytes", 0)        # 0: paste.BLOCK_BYTES["device"]
+DEVICE_BLOCK = arg("--device-block-bytes", 0)        # 0: cohort.BLOCK_BYTES["device"]
 SHAPES = {"n100": 100, "n1000": 1000}
 shapes = arg("--shapes", "n100,n1000").split(",")
 LEGS = arg("--legs", "python,host,device").split(",")
@@ -55,7 +55,7 @@ def restated(vcf):
     lines = vcf.decode().split("\n")[:-1]
     header = [l + "\n" for l in lines if l.startswith("#")]
     file_format, reference, infos, alts, formats, samples = update_info.header_tables(header)
-    out = ["\n".join(["##fileformat=" + file_format, "##fileDate=" + FILE_DATE, "##reference=" + reference] + paste.declared_lines(infos, alts, formats)
+    out = ["\n".join(["##fileformat=" + file_format, "##fileDate=" + FILE_DATE, "##reference=" + reference] + cohort.declared_lines(infos, alts, formats)
                      + ["\t".join(header[-1].rstrip().split("\t")[:9] + samples)]) + "\n"]
     order = [f[0] for f in formats]
     for text in lines[len(header):]:
@@ -114,7 +114,7 @@ def device_copy_rate():
 
 def main():
     report = {"reps": reps, "lines": LINES, "device": device, "box": socket.gethostname(), "legs": LEGS,
-              "block_bytes": dict(paste.BLOCK_BYTES, **({"device": DEVICE_BLOCK} if DEVICE_BLOCK else {}))}
+              "block_bytes": dict(cohort.BLOCK_BYTES, **({"device": DEVICE_BLOCK} if DEVICE_BLOCK else {}))}
     if "device" in LEGS:
         report["device_copy_bytes_per_s"] = device_copy_rate()
     for shape in shapes:
