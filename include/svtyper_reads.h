@@ -13,7 +13,9 @@
  * and what svtyper_amd/bam.py + fragments.py + geometry.py do in Python (those stay the portable
  * implementation and are the checker of this one: tests/test_native_reads.py).
  *
- * Plain C ABI, host memory only; no GPU is needed for these calls.  BAM with a .bai or a .csi index (no CRAM).
+ * Plain C ABI, host memory only; no GPU is needed for these calls.  BAM with a .bai or a .csi index.  (CRAM 3.0 is read by
+ * svtyper_amd/cram.py on the Python reader route, over svt_rans_decode_* and svt_cram_decode_slice below; the svt_bam_* calls
+ * take no CRAM.)
  */
 #ifndef SVTYPER_READS_H
 #define SVTYPER_READS_H
@@ -935,6 +937,43 @@ int svt_bam_scan_libraries_device(const svt_bam* bam, uint32_t n_libs, const uin
                                   const char* const* read_groups, int64_t num_samp, uint64_t round_bytes,
                                   int inflate_on_device, int device, svt_library_scan* out,
                                   svt_library_scan_stats* stats);
+
+/* ---- CRAM 3.0 (additions without a new SVT_ABI_VERSION: probe for the symbols) ------------------------------------------
+ * svtyper_amd/cram.py reads containers, blocks and indexes; what is native is the rANS 4x8 decoder (block method 4), once for
+ * the host and the device (svt_rans.h), and the slice decoder (svt_cram.h).
+ *
+ * svt_rans_decode_*: block k is data[off[k], off[k + 1]) -- order byte, compressed size, uncompressed size, payload -- and decodes
+ * to out[out_off[k], out_off[k] + out_size[k]).  status[k] is one of SVT_RANS_*; a block that is refused has its output range
+ * zeroed.  Nothing outside the blocks' output ranges is changed.                                                            */
+#define SVT_RANS_OK 0
+#define SVT_RANS_HEADER 1       /* shorter than its header, an order other than 0 and 1, sizes that are not the block's      */
+#define SVT_RANS_FREQ 2         /* the frequency table runs out, repeats itself or does not sum to 4096 (4095)               */
+#define SVT_RANS_INPUT 3        /* the states or the renormalisation bytes run out                                           */
+#define SVT_RANS_SYMBOL 4       /* a state points at no symbol of its context                                                */
+#define SVT_RANS_SIZE 5         /* order 1 with nothing to decode                                                            */
+int svt_rans_decode_host(const uint8_t* data, uint64_t data_len, const uint64_t* off, uint64_t n, const uint64_t* out_off,
+                         const uint64_t* out_size, uint8_t* out, uint64_t out_len, uint32_t* status);
+int svt_rans_decode_device(const uint8_t* data, uint64_t data_len, const uint64_t* off, uint64_t n, const uint64_t* out_off,
+                           const uint64_t* out_size, uint8_t* out, uint64_t out_len, uint32_t* status, int device);
+/* the calling thread's most recent svt_rans_decode_device: copies and kernels by HIP events, the call on the host's clock   */
+typedef struct svt_rans_times {
+    double upload_s, order0_kernel_s, order1_kernel_s, download_s;
+    double total_s;
+} svt_rans_times;
+int svt_rans_last_times(svt_rans_times* times);
+
+/* One slice as BAM records.  comp_header / slice_header: the content of the container's compression header block and of the
+ * slice's header block; blocks / block_off / content_id / is_core: the slice's other blocks with their block method undone,
+ * side by side; rg_ids: the SAM header's @RG ids in order, each ending in NUL; n_ref: the header's references.  The records --
+ * block_size first, SEQ `N` x RL, QUAL 0xFF x RL -- are held for the calling thread: svt_cram_take copies info.bytes bytes and
+ * info.n_records + 1 offsets.  A slice that is refused: SVT_ERR_INVALID, svt_last_error() says what was met.                  */
+typedef struct svt_cram_slice_info {
+    uint64_t n_records, bytes;
+} svt_cram_slice_info;
+int svt_cram_decode_slice(const uint8_t* comp_header, uint64_t comp_len, const uint8_t* slice_header, uint64_t slice_len,
+                          const uint8_t* blocks, const uint64_t* block_off, const int32_t* content_id, const uint8_t* is_core,
+                          uint32_t n_blocks, const char* rg_ids, uint32_t n_rg, int32_t n_ref, svt_cram_slice_info* info);
+int svt_cram_take(uint8_t* records, uint64_t* rec_off);
 
 #ifdef __cplusplus
 }

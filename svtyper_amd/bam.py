@@ -13,7 +13,9 @@ Only what SURVEY.md section 3.5 lists is implemented:
                     has_tag/get_tag/set_tag, get_overlap, query_length, query_alignment_length,
                     infer_query_length, query_sequence = None (the only value it takes)
 
-CRAM is not supported (the reference needs htslib + a reference FASTA for it).
+CRAM 3.0 is read by cram.py (`CramFile`: the same reading surface, its records AlignedSegments over BAM record bytes the native
+slice decoder makes).  SVTyper never looks at bases or qualities, so those records carry SEQ as `N` x read length, QUAL as 0xFF
+x read length and `bin` as reg2bin of their extent, and no reference FASTA is needed.
 If a real pysam is importable, `open_alignment_file` prefers it.
 """
 from __future__ import annotations
@@ -398,7 +400,7 @@ class AlignmentFile:
 
     def __init__(self, path: str, mode: str = "rb", template=None, **kwargs):
         if "c" in mode or path.endswith(".cram"):
-            raise NotImplementedError("CRAM needs htslib; this reader handles BAM only")
+            raise NotImplementedError("this class reads BAM: a CRAM is opened with cram.CramFile (open_alignment_file does)")
         self.filename = path
         self._writer = None
         if mode.startswith("w"):
@@ -878,18 +880,25 @@ class AlignmentFile:
         return n
 
 
-def open_alignment_file(path: str, reference_fasta: Optional[str] = None, verify: bool = False):
-    """pysam.AlignmentFile when pysam is importable, else the built-in BAM reader
+def open_alignment_file(path: str, reference_fasta: Optional[str] = None, verify: bool = False, cram_codec: str = "host", device: int = 0):
+    """pysam.AlignmentFile when pysam is importable, else the built-in BAM reader or, for a *.cram, the built-in CRAM reader
     (svtyper/singlesample.py:53-62 semantics: the extension decides).  `verify`: the built-in reader, checking the CRC32 of
-    every BGZF block it inflates (the drivers' verify="crc32")."""
+    every BGZF block it inflates, or of every CRAM container header and block it reads (the drivers' verify="crc32").
+    `cram_codec`, `device`: who decodes a CRAM's rANS blocks (cram.CramFile)."""
     if not (path.endswith(".bam") or path.endswith(".cram")):
         raise ValueError("Error: %s is not a valid alignment file (*.bam or *.cram)" % path)
     if verify and path.endswith(".bam"):
         return AlignmentFile(path, "rb", verify=True)
+    if path.endswith(".cram") and (verify or cram_codec != "host"):     # (what pysam has no word for: the built-in reader)
+        from .cram import CramFile
+        return CramFile(path, verify=verify, codec=cram_codec, device=device)
     try:
         import pysam  # type: ignore
         if path.endswith(".bam"):
             return pysam.AlignmentFile(path, mode="rb")
         return pysam.AlignmentFile(path, mode="rc", reference_filename=reference_fasta)
     except ImportError:
+        if path.endswith(".cram"):
+            from .cram import CramFile
+            return CramFile(path, codec=cram_codec, device=device)
         return AlignmentFile(path, "rb")

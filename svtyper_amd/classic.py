@@ -186,7 +186,7 @@ class Classic(Driver):
 def sv_genotype(bam_string, vcf_in, vcf_out, min_aligned, split_weight, disc_weight, num_samp, lib_info_path,
                 debug, alignment_outpath, ref_fasta, sum_quals, max_reads, max_ci_dist, *, engine=None, geometry="host",
                 reader=None, stats=None, inflate="host", library_scan="host", verify="off", deflate="zlib", huffman="fixed",
-                alignment_sort=False, alignment_index=None, alignment_out=None):
+                alignment_sort=False, alignment_index=None, alignment_out=None, cram_codec=None):
     """`alignment_outpath` (-w): the reads that entered the tallies go to a BAM, tagged XV:A:R / XV:A:A as the reference tags them
     (driver.tag_and_write; the tags that depend on p_concordant come from the device, svt_batch_verdicts).  Legal with
     reader="python" (what reader=None then means) or reader="device" (the reads are cut and tagged on the GPU: the evidence dump of
@@ -197,7 +197,8 @@ def sv_genotype(bam_string, vcf_in, vcf_out, min_aligned, split_weight, disc_wei
     stable coordinate order, its header saying SO:coordinate; `alignment_index="bai"` (--bai): its index beside it, at
     alignment_outpath + ".bai"; `alignment_index="csi"` (--alignment-csi): a CSI index instead, at alignment_outpath + ".csi", which
     also holds records beyond 2^29 (bam.AlignmentFile's sort= / index= / csi=: both hold every record until the end; BamOrderError for records
-    that cannot be sorted or indexed).  ValueError for either without `alignment_outpath`.  `alignment_out`: a writer that takes the
+    that cannot be sorted or indexed).  `cram_codec` ("host" | "device"; None = "host"): with a *.cram among the alignment files, who
+    decodes its rANS blocks (cram.py; pipeline.check_cram has the usage errors of a CRAM input).  ValueError for either without `alignment_outpath`.  `alignment_out`: a writer that takes the
     dump's records instead of a file opened at `alignment_outpath` (write / write_raw / close, e.g. bam.RecordSink: what
     sharded.sv_genotype_sharded gives every rank); the checks above apply as they do to a path."""
     check_huffman(huffman, check_deflate(deflate))
@@ -209,6 +210,7 @@ def sv_genotype(bam_string, vcf_in, vcf_out, min_aligned, split_weight, disc_wei
     run.alignment_sort = bool(alignment_sort)
     run.alignment_index = alignment_index
     run.alignment_out = alignment_out
+    run.cram_codec = cram_codec
     return run.run(CHUNK_UNITS, engine=engine, geometry=geometry, reader=reader, stats=stats, inflate=inflate,
                    library_scan=library_scan, verify=verify)
 

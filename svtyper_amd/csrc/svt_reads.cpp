@@ -40,6 +40,8 @@
 #include "svt_geometry_math.h"
 #include "svt_host_cpus.h"
 #include "svt_library_arena.h"
+#include "svt_cram.h"
+#include "svt_rans_batch.h"
 #include "svt_record_rules.h"
 #include "svt_tbx_index.h"
 #include "svt_vcf_lines.h"
@@ -76,3 +78,4 @@ using rr::ld32;
 #include "svt_reads_classify_entries.h" // svt_vcf_classify_host, _write, _take: the read-depth classifier of DEL and DUP lines
 #include "svt_reads_update_info_entries.h" // svt_vcf_update_info_host, _write, _take: PE, SR, SU and MSQ from the samples' evidence
 #include "svt_reads_group_entries.h"  // svt_vcf_group_host, _write, _take: BND mates grouped in front of the paste
+#include "svt_entry_cram.h"           // svt_rans_decode_host, svt_cram_decode_slice, svt_cram_take: the CRAM reader's native parts

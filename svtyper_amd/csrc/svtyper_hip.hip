@@ -70,6 +70,8 @@
 #include "svt_evidence_kernel.h"
 #include "svt_inflate_kernel.h"
 #include "svt_crc32_kernel.h"
+#include "svt_rans_kernel.h"
+#include "svt_rans_batch.h"
 #include "svt_deflate_kernel.h"
 #include "svt_vcf_lines_kernel.h"
 #include "svt_vcf_paste_kernel.h"
@@ -218,6 +220,7 @@ void svt_batch_destroy(svt_batch* b) { free_batch(b); }
 #include "svt_entry_bam_index.h"
 #include "svt_entry_bcf.h"
 #include "svt_entry_bcf_text.h"
+#include "svt_entry_rans.h"
 #include "svt_entry_evidence.h"
 #include "svt_entry_library.h"
 #include "svt_entry_oneshot.h"

@@ -35,7 +35,7 @@ from itertools import chain
 from .bam import AlignmentFile, open_alignment_file
 from .library import setup_sample
 from .pipeline import (MIN_LIB_PREVALENCE, BulkFeeder, ChunkPipeline, NativeUnitCollector, UnitCollector, check_inflate,
-                       check_library_scan, check_verify, default_engine, resolve_reader, split_lines, verify_stats)
+                       check_cram, check_library_scan, check_verify, default_engine, resolve_reader, split_lines, verify_stats)
 from .vcf import Variant, Vcf
 
 
@@ -97,7 +97,11 @@ def open_alignment_writer(path, template_path, deflate, huffman, alignment_sort,
     """The `-w` BAM opened for writing, its header the template file's: with the run's compressor, and its order and index as the
     writer spells them (bam.AlignmentFile: sort=, index="bai", csi=True).  The one-process run opens it before its first record,
     the gathered run (sharded.py) on rank 0 once every rank's records are there."""
-    template = AlignmentFile(template_path, "rb")
+    if template_path.endswith(".cram"):     # (a CRAM's SAM header as a BAM holds it: cram.CramFile._header_bytes)
+        from .cram import CramFile
+        template = CramFile(template_path)
+    else:
+        template = AlignmentFile(template_path, "rb")
     order = dict(sort=True) if alignment_sort else {}
     if alignment_index is not None:         # (the writer spells a CSI as pysam does: the index asked for, csi=True)
         order["index"] = "bai"
@@ -141,6 +145,7 @@ class Driver:
     huffman = "fixed"                   # ... and into which block, where it is the library's own compressor
     alignment_sort = False              # the `-w` BAM in coordinate order (bam.AlignmentFile: sort=)
     alignment_index = None              # ... and "bai" / "csi": its index beside it (index="bai"; "csi": with csi=True)
+    cram_codec = None                   # "host" | "device": who decodes the rANS blocks of a CRAM among the inputs (None: the host twin)
     alignment_out = None                # a writer to use instead of opening alignment_outpath (write / write_raw / close: bam.RecordSink
                                         # under sharded.py); the run is then a `-w` run whether or not a path is given
 
@@ -156,6 +161,7 @@ class Driver:
     def run(self, chunk_units, engine=None, geometry="host", reader=None, stats=None, inflate="host", library_scan="host",
             verify="off"):
         writing = self.alignment_outpath is not None or self.alignment_out is not None
+        reader = check_cram(self.bam_string, reader, inflate, library_scan, self.cram_codec)
         if not writing and (self.alignment_sort or self.alignment_index is not None):
             raise ValueError("alignment_sort / alignment_index (--sort-alignment, --bai) need -w/--write_alignment: they are about that BAM")
         if self.alignment_index not in (None, "bai", "csi"):
@@ -174,7 +180,8 @@ class Driver:
             paths.append(path)
             # (`-w` writes the records the built-in reader keeps the raw bytes of)
             bams.append(AlignmentFile(path, "rb", verify=verify_on) if writing and path.endswith(".bam")
-                        else open_alignment_file(path, self.ref_fasta, verify=verify_on))
+                        else open_alignment_file(path, self.ref_fasta, verify=verify_on, cram_codec=self.cram_codec or "host",
+                                                 device=getattr(engine, "device", 0)))
         lib_info = self.read_library_file()
         if self.vcf_in is None:     # classic.py:142-143 (sso_genotype does not get here without a VCF)
             sys.stderr.write("Warning: VCF not found.\n")
@@ -373,10 +380,16 @@ def parse_arguments(p, bam_help, max_reads, own):
                    help="without a library file: the libraries' read length, insert-size histogram and prevalence from three "
                         "scans per library on the host, or from one segmented walk on the GPU for all libraries, members inflated as --inflate says "
                         "(needs --reader native or device; same library file, same output bytes) [host]")
+    # (not listed by --help, like --bgzf: the help text is pinned byte for byte) who decodes the rANS blocks of a CRAM input
+    p.add_argument("--cram-codec", dest="cram_codec", choices=("host", "device"), default=None, help=argparse.SUPPRESS)
     p.add_argument("--geometry", choices=("host", "device"), default="host",
                    help="with --reader python: breakpoint-dependent read predicates on the host or on the GPU [host]")
     add_output_arguments(p)
     args = p.parse_args()
+    try:                        # the usage errors of a CRAM input (pipeline.check_cram)
+        check_cram(args.bam, args.reader, args.inflate, args.library_scan, args.cram_codec)
+    except ValueError as e:
+        p.error(str(e))
     check_output_arguments(p, args, args.output_vcf)
     args.input_vcf = gzip_text(args.input_vcf)
     if args.input_vcf is None and not sys.stdin.isatty():
@@ -448,8 +461,10 @@ def run_main(driver, sharded_driver, call, args):
     from . import sharded
     if args.split_bam is not None:
         sys.stderr.write("Warning: --split_bam (-S) is deprecated. Ignoring %s.\n" % args.split_bam)
-    options = dict(geometry=args.geometry, reader=args.reader or "native", inflate=args.inflate, library_scan=args.library_scan,
+    options = dict(geometry=args.geometry, reader=check_cram(getattr(args, "bam", ""), args.reader) or "native", inflate=args.inflate, library_scan=args.library_scan,
                    verify="crc32" if args.verify_bgzf else "off")
+    if getattr(args, "cram_codec", None) is not None:
+        options["cram_codec"] = args.cram_codec
     job = sharded.job()
     if job is None:
         if not (args.bgzf or getattr(args, "bcf", False)):

@@ -189,6 +189,27 @@ def check_library_scan(reader: str, library_scan: str) -> str:
     return library_scan
 
 
+def check_cram(bam_string, reader: Optional[str], inflate: str = "host", library_scan: str = "host", cram_codec: Optional[str] = None) -> Optional[str]:
+    """What a run asks of its arguments where CRAM is concerned; the drivers call it before anything is opened and the sharded
+    runs before their first collective.  A `.cram` among the alignment files takes the Python reader route (cram.py), so
+    reader=None then means "python" and reader="native" / "device", inflate="device" and library_scan="device" are usage errors;
+    `cram_codec` ("host" | "device": which twin of svt_rans.h decodes the rANS blocks; None = "host") without a CRAM is one too.
+    -> the reader the run uses (None: the default of a run without CRAM)"""
+    has_cram = any(p.endswith(".cram") for p in str(bam_string).split(","))
+    if cram_codec is not None:
+        if cram_codec not in ("host", "device"):
+            raise ValueError("cram_codec must be 'host' or 'device'")
+        if not has_cram:
+            raise ValueError("cram_codec (--cram-codec) is about CRAM input: there is no .cram among the alignment files")
+    if not has_cram:
+        return reader
+    for name, value in (("reader", reader if reader in ("native", "device") else None), ("inflate", inflate if inflate == "device" else None),
+                        ("library_scan", library_scan if library_scan == "device" else None)):
+        if value is not None:
+            raise ValueError("%s=%r is not for CRAM input: CRAM input takes the Python reader route (reader='python')" % (name, value))
+    return "python" if reader is None else reader
+
+
 def resolve_reader(reader: Optional[str]) -> str:
     """`reader=None` (the drivers' default, i.e. what a caller with the reference's positional arguments gets): the C++
     reader of libsvtyper_hip.so when the library is there -- fetch, fragment assembly and the geometry predicates in its

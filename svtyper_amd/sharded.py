@@ -153,6 +153,9 @@ def run_sharded(driver: Callable, bam_string, vcf_in, vcf_out, *rest, rank: int,
                 lib_info_index: int, **kw) -> None:
     """`driver(bam_string, vcf_in, vcf_out, *rest, **kw)` over this rank's share of `vcf_in`; rank 0
     writes everything to `vcf_out`.  Needs an initialised process group."""
+    from .pipeline import check_cram
+    # (on every rank, in front of the first collective: a rank that raised alone would leave the others waiting in it)
+    check_cram(bam_string, kw.get("reader"), kw.get("inflate", "host"), kw.get("library_scan", "host"), kw.get("cram_codec"))
     if vcf_in is None:
         return driver(bam_string, None, vcf_out, *rest, **kw)
     import sys

@@ -241,11 +241,14 @@ class Sso(Driver):
 
 def sso_genotype(bam_string, vcf_in, vcf_out, min_aligned, split_weight, disc_weight, num_samp, lib_info_path,
                  debug, ref_fasta, sum_quals, max_reads, max_ci_dist, cores, batch_size, *, engine=None, geometry="host",
-                 reader=None, stats=None, inflate="host", library_scan="host", verify="off"):
+                 reader=None, stats=None, inflate="host", library_scan="host", verify="off", cram_codec=None):
+    """`cram_codec` ("host" | "device"; None = "host"): with a *.cram input, who decodes its rANS blocks (cram.py; pipeline.check_cram has
+    the usage errors of a CRAM input)."""
     if vcf_in is None:      # singlesample.py:780-781: in front of everything else, the alignment file included
         return
     run = Sso(bam_string, vcf_in, vcf_out, min_aligned, split_weight, disc_weight, num_samp, lib_info_path, debug, ref_fasta,
               sum_quals, max_reads, max_ci_dist, cores=cores)
+    run.cram_codec = cram_codec
     return run.run(CHUNK_UNITS, engine=engine, geometry=geometry, reader=reader, stats=stats, inflate=inflate,
                    library_scan=library_scan, verify=verify)
 
